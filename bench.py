@@ -2,6 +2,7 @@
 """Headline benchmark: poses/sec of the flower-pose hot path on N MI355X (BASELINE.json).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--dtype f16|bf16] [--crop 224] [--batch 256]
+                    [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -14,10 +15,19 @@ batches (weak scaling, no collective on the data path); the finished [K*256,16] 
 are all-gathered ONCE over RCCL inside the timed region (BASELINE configs[3]).  Rank 0 prints
 one JSON line.
 
-The timed loop is un-instrumented.  The `roofline` object comes from a second pass of the same
-steps in the engine's profile mode (HIP events around every launch on the launch stream); the
-`cpu_baseline` object is the CPU oracle (torch fp32, eval mode) timed on the host cores on a
-bounded sample -- a reported baseline, never part of the product path.
+The timed loop is un-instrumented.  A plain run does only what the headline needs: set-up
+(engine, weights, schedule autotune), W warm-up steps, the K timed steps, the optional output
+dump and the result line.  Everything else is measured only with `--full`: the per-step event
+times, the `roofline` object (a second pass of the same steps in the engine's profile mode, HIP
+events around every launch on the launch stream), the parity sample against the oracle, the
+other dtype and the 512 x 512 crop, the fresh-process run without autotune, and the
+`cpu_baseline` object (the CPU oracle, torch fp32, eval mode, timed on the host cores on a
+bounded sample -- a reported baseline, never part of the product path).
+
+`--dump-outputs DIR` writes, after the timed steps, what the last timed step computed as float32
+`.npy` files: `poses.npy` ([N*B,16] pose records of every rank, as gathered on rank 0) and
+`R.npy` (rank 0's [B,9] rotations).  Inputs and weights are seeded, so equal arguments give
+equal inputs from run to run.
 """
 import argparse
 import json
@@ -111,7 +121,8 @@ def no_autotune_child(args) -> dict | None:
     next to the untuned one -- most of r04's gain was the device reaching its sustained clock during autotune, not the schedule)."""
     import subprocess
     cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--steps", str(args.steps), "--warmup", str(args.warmup),
-           "--dtype", args.dtype, "--crop", str(args.crop), "--batch", str(args.batch), "--no-autotune", "--no-alt", "--no-cpu-baseline"]
+           "--dtype", args.dtype, "--crop", str(args.crop), "--batch", str(args.batch), "--full", "--no-autotune", "--no-alt",
+           "--no-cpu-baseline"]
     try:
         proc = subprocess.run(cmd, env=dict(os.environ, FLOPE_BENCH_CHILD="1"), stdout=subprocess.PIPE, stderr=subprocess.DEVNULL,
                               text=True, timeout=300)
@@ -123,6 +134,22 @@ def no_autotune_child(args) -> dict | None:
     except (subprocess.SubprocessError, ValueError, KeyError, OSError):
         pass
     return None
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir: str, arrays: dict) -> None:
+    """Each array as float32 `<out_dir>/<name>.npy`; past 64 MB in all, a fixed seeded sample of rows (in order) of every array."""
+    import numpy as np
+    arrs = {k: v.detach().float().cpu().numpy() for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrs.values())
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrs.items():
+        if total > DUMP_LIMIT_BYTES:
+            keep = max(1, int(a.shape[0] * DUMP_LIMIT_BYTES // total))
+            a = a[np.sort(np.random.default_rng(0).choice(a.shape[0], keep, replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def main():
@@ -138,9 +165,16 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-alt", action="store_true", help="skip the secondary bf16/f16 measurement")
     ap.add_argument("--no-autotune", action="store_true", help="keep the engine's default launch schedule (no set-up measurement)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: per-step and per-kernel times (roofline), parity sample "
+                         "against the oracle, the other dtype, the 512 x 512 crop, the run without autotune and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's outputs as float32 DIR/<name>.npy (rank 0)")
     args = ap.parse_args()
     if args.cfg4:
         args.steps, args.batch, args.crop = 32, 256, 224
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:      # no outer launcher: become one (nothing has touched the GPU yet)
         raise SystemExit(self_launch(args.gpus))
 
@@ -213,7 +247,7 @@ def main():
         D.barrier(); torch.cuda.synchronize(dev)
         dt = D.max_over_ranks(time.perf_counter() - t0, "cpu" if rehearse else dev)
         assert allp.shape == (world * K * B, 16)
-        return eng, x, fmt, dt, R, xyz, poses
+        return eng, x, fmt, dt, R, xyz, poses, allp
 
     def step_times_ms(eng, x, fmt, n, poses, R, xyz):
         """Per-step GPU time: events on the launch stream around every step (the engine forks its slice streams from
@@ -236,8 +270,11 @@ def main():
                 "max_angle_deg": float(O.geodesic_deg(R[:8].view(8, 3, 3).cpu(), Rref).max()),
                 "sample": "8 crops of the bench batch vs fp32 CPU oracle"}
 
-    eng, x, fmt, dt, R, xyz, poses = measure(args.dtype)
+    eng, x, fmt, dt, R, xyz, poses, allp = measure(args.dtype)
     value = world * K * B / dt
+    if rank == 0 and args.dump_outputs:
+        # the last timed step's [B,16] records of every rank (gathered rank-major) and rank 0's rotations, before --full reuses R
+        dump_outputs(args.dump_outputs, {"poses": allp.view(world, K, B, 16)[:, K - 1].reshape(world * B, 16), "R": R})
 
     out = {
         "metric": "poses_per_sec", "value": round(value, 1), "unit": "poses/s", "n_gpus": world, "steps": K,
@@ -250,8 +287,10 @@ def main():
                    "weights": "synthetic_state_dict(seed 0), eval-mode BN folded",
                    "gflop_per_pose": round(eng.flops(1) / 1e9, 4)},
     }
+    if rank == 0 and (args.dtype, S) in tuned:
+        out["autotune"] = tuned[(args.dtype, S)]
 
-    if rank == 0:
+    if rank == 0 and args.full:
         st = step_times_ms(eng, x, fmt, K, poses, R, xyz)
         out["ms_per_step_median"] = round(st[len(st) // 2], 4)
         out["ms_per_step_min"] = round(st[0], 4)
@@ -295,16 +334,14 @@ def main():
             except (OSError, ValueError, KeyError):
                 continue
         out["source_digest"] = source_digest()
-        if (args.dtype, S) in tuned:
-            out["autotune"] = tuned[(args.dtype, S)]
         out["kernels_ms_per_step"] = {k: round(v["ms"], 4) for k, v in sorted(per_kernel.items(), key=lambda kv: -kv[1]["ms"])}
         # ---- parity of this very configuration against the oracle on a sample ---------------------
         out["rot_err_vs_oracle"] = oracle_sample_err(eng, x, fmt, R)
     eng.close()
 
-    if not args.no_alt and world == 1:
+    if args.full and not args.no_alt and world == 1:
         alt = "bf16" if args.dtype == "f16" else "f16"
-        eng2, x2, fmt2, dt2, R2, _, _ = measure(alt)
+        eng2, x2, fmt2, dt2, R2, _, _, _ = measure(alt)
         err2 = oracle_sample_err(eng2, x2, fmt2, R2)
         out["alt_dtype"] = {"dtype": alt, "value": round(K * B / dt2, 1), "ms_per_step": round(dt2 / K * 1e3, 4),
                             "max_abs_R_vs_oracle": err2["max_abs_R"], "meets_1e-3": err2["max_abs_R"] <= 1e-3}
@@ -315,18 +352,18 @@ def main():
         # the reference's own crop size (fast_pose_predictor.py:115-116): 512 x 512, same batch
         if S == 224:
             k5 = max(5, K // 5)
-            eng5, _, _, dt5, _, _, _ = measure(args.dtype, S=512, K=k5, W=2)
+            eng5, _, _, dt5, _, _, _, _ = measure(args.dtype, S=512, K=k5, W=2)
             out["alt_shapes"] = {"512": {"value": round(k5 * B / dt5, 1), "ms_per_step": round(dt5 / k5 * 1e3, 4), "steps": k5,
                                          "step_frac_of_peak": round(k5 * B / dt5 * eng5.flops(1) / 1e12 / PEAK_TFLOPS, 4),
                                          "note": "reference-true crop size, batch %d" % B}}
             eng5.close()
 
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(S, 16)
         big = cpu_baseline(S, 256, budget_s=8.0)
         out["cpu_baseline"]["batch_256"] = {"value": big["value"], "sample": big["sample"]}
 
-    if rank == 0 and world == 1 and not args.no_autotune and os.environ.get("FLOPE_BENCH_CHILD") != "1":
+    if args.full and rank == 0 and world == 1 and not args.no_autotune and os.environ.get("FLOPE_BENCH_CHILD") != "1":
         out["no_autotune"] = no_autotune_child(args)
 
     if rank == 0:

@@ -33,7 +33,7 @@ def _bench_two_ranks(extra_env, outer_launcher=True):
     launcher = ["-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                 "--master-port", str(_free_port())] if outer_launcher else []
     cmd = [sys.executable] + launcher + [os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-                                         "--no-cpu-baseline", "--no-alt"]
+                                         "--full", "--no-cpu-baseline", "--no-alt"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]

@@ -30,7 +30,7 @@ python tools/summarize_prof.py $OUT/calib > $OUT/calib_summary.txt
 python tools/roofline_table.py $OUT > $OUT/roofline.md
 python tools/make_traffic_json.py $OUT > $OUT/traffic.json
 cp $OUT/traffic.json profiles/$(echo $TAG | sed -E "s/^(r[0-9]+).*/\\1/")_traffic.json      # bench.py reads the committed file (newest round first): same sources, same digest
-python bench.py > $OUT/bench.json 2> $OUT/bench.err || exit 16
+python bench.py --full > $OUT/bench.json 2> $OUT/bench.err || exit 16
 echo "bench done"
 YOLO_DTYPE=f32 python tools/bench_e2e.py yolo 4 16 31 > $OUT/e2e.txt 2>&1
 YOLO_DTYPE=f16 python tools/bench_e2e.py yolo > $OUT/e2e_f16_detector.txt 2>&1
