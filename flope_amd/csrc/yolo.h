@@ -24,9 +24,7 @@ struct YConvP {
   int ksteps;                                // Kp / 32
   int out_mode;                              // 0: 16-bit view, 1: float32 view, 2: 2x2 stride-2 transposed conv scatter (16-bit)
   int dc;                                    // out_mode 2: real output channels (rows = 4 * dc, row = (dy*2+dx)*dc + co)
-  int xcd;                                   // set by the launcher: workgroup order remapped so that an XCD owns an image band
   int tile, tiles_x;                         // set by the launcher: LDS-staged 8 x 16 output tiles; tiles per row
-  int wlds, pad2_;                           // set by the launcher: tile path with the weight image staged in LDS as well
   unsigned pw_mg, pw_sh;                     // n / (patch width) as multiply-shift
   // float32 mode, exact-fp32 MFMA kernel (yolo_f32.hip y32m_conv_kernel): weights in A-fragment order of v_mfma_f32_16x16x4_f32,
   // [channel block of 16 nt rows][k16 step][channel tile][lane = kq * 16 + row][4 k] (k = 16 step + 4 kq + element), rows permuted
@@ -60,12 +58,6 @@ struct YMultiOp {
   union U { YConvP c; YDwP d; YBneckP b; } u;
 };
 struct YMultiP { int n, total, lds, pad_; YMultiOp op[kYMultiMax]; };
-
-// ychain_kernel (r05): up to kYChainMax CONSECUTIVE 1x1 stride-1 convs on one small map, run back to back by one grid: a workgroup owns
-// a pixel tile and pushes it through all of them (a 1x1 conv reads its own pixels only), its four waves taking the channel blocks of
-// each conv side by side; what one conv wrote for the tile is visible to the next behind a workgroup barrier.  One launch instead of n.
-constexpr int kYChainMax = 4;
-struct YChainP { int n, tiles, pad0_, pad1_; int nt[kYChainMax]; YConvP op[kYChainMax]; };
 
 struct YPoolP { const void* in; int H, W, C, ldi; void* out; int ldo; int n; };    // n (1..3) cascaded 5x5 s1 p2 max-pools, -inf border;
                                                                                    // result i -> channels [i C, (i+1) C) of out

@@ -174,8 +174,8 @@ __device__ __forceinline__ void yconv_epilogue_unit(const YConvP& p, const int n
   }
 }
 
-// (m_base: first pixel of the wave's two pixel tiles; nblk: channel block -- yconv_body derives them from the workgroup index, the
-// chain kernel hands every wave its own channel block of one shared pixel tile)
+// (m_base: first pixel of the wave's two pixel tiles; nblk: channel block -- yconv_body derives them from the workgroup index.  Kept
+// apart from yconv_body: folding it in changes the compiled kernels (instruction order, register choice))
 template <typename T, int NT, bool K3, bool SPLITK>
 __device__ __forceinline__ void yconv_body_at(const YConvP& p, const int m_base, const int nblk, float* const red, const int bx, const int by) {
   typedef typename Elem<T>::frag frag;
@@ -348,11 +348,6 @@ __device__ __forceinline__ void yconv_body(const YConvP& p, const int bx, const 
   yconv_body_at<T, NT, K3, SPLITK>(p, m_base, by, red, bx, by);
 }
 
-template <typename T, int NT, int MTW>
-__device__ __forceinline__ void ylds_kloop3w(const char* const wl, const int ksteps, const int cg, const unsigned cg_mg, const unsigned cg_sh,
-                                             const char* const lds, const int pitch, const int PW, const int (&poff)[MTW],
-                                             f32x4 (&acc)[MTW][NT]);
-
 // ---------------------------------------------------------------------------------------------------------------
 // Large maps (everything that is not SPLITK): one workgroup = an 8-row x 16-column tile of output pixels, wave w owns rows
 // 2w and 2w+1.  The input patch ((7 s + k) x (15 s + k) pixels, all channels) is staged once into LDS with fully coalesced
@@ -374,59 +369,6 @@ __device__ __forceinline__ void yconv_tile_body(const YConvP& p, const int bx, c
   const int nblk = by;
   const char* const wrow = (const char*)p.w + (size_t)nblk * p.ksteps * (NT * 1024) + lane * 16;
   const int klast = p.ksteps - 1;
-  if constexpr (K3) {
-    // Long K (>= 8 steps): the layer's weights are cold for the one or two workgroups an XCD gets, and a K loop that fetches them
-    // PD steps ahead pays a memory round trip every PD steps.  Stage the channel block's whole weight image into LDS together with
-    // the patch (one round trip) and run the K loop on LDS operands only.
-    if (p.wlds) {
-      char* const wl = lds + PH * PW * pitch;
-      const int nw = p.ksteps * NT * 64, total = PH * PW * p.cg;
-      const char* const wsrc = (const char*)p.w + (size_t)nblk * p.ksteps * (NT * 1024);
-      const char* const in = (const char*)p.in;
-      for (int i0 = tid; i0 < nw + total; i0 += 8 * 256) {
-        u32x4 v[8];
-        int dst[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          const int i = i0 + j * 256;
-          if (i < nw) { v[j] = *(const u32x4*)(wsrc + (size_t)i * 16); dst[j] = PH * PW * pitch + i * 16; continue; }
-          const int ip = min(i - nw, total - 1);
-          const int pp = fastdiv(ip, p.cg_mg, p.cg_sh), c8 = ip - pp * p.cg;
-          const int py = fastdiv(pp, p.pw_mg, p.pw_sh), px = pp - py * PW;
-          const int iy = iy00 + py, ix = ix00 + px;
-          const bool ok = (unsigned)iy < (unsigned)p.Hi && (unsigned)ix < (unsigned)p.Wi;
-          v[j] = ok ? *(const u32x4*)(in + ((size_t)(iy * p.Wi + ix) * p.ldi + c8 * 8) * 2) : u32x4{0u, 0u, 0u, 0u};
-          dst[j] = i - nw < total ? pp * pitch + c8 * 16 : -1;
-        }
-#pragma unroll
-        for (int j = 0; j < 8; ++j)
-          if (dst[j] >= 0) *(u32x4*)(lds + dst[j]) = v[j];
-      }
-      __syncthreads();
-      int poff[MTW];
-#pragma unroll
-      for (int pt = 0; pt < MTW; ++pt) poff[pt] = ((wave * 2 + pt) * s) * PW + c16 * s;
-      f32x4 accw[MTW][NT];
-#pragma unroll
-      for (int ct = 0; ct < NT; ++ct) {
-        const f32x4 b = *(const f32x4*)(p.bias + nblk * (16 * NT) + ct * 16 + g * 4);
-#pragma unroll
-        for (int pt = 0; pt < MTW; ++pt) accw[pt][ct] = b;
-      }
-      ylds_kloop3w<T, NT, MTW>(wl, p.ksteps, p.cg, p.cg_mg, p.cg_sh, lds, pitch, PW, poff, accw);
-      int mm[MTW];
-      bool pv[MTW];
-      const int ox = tx * 16 + c16;
-#pragma unroll
-      for (int pt = 0; pt < MTW; ++pt) {
-        const int oy = ty * 8 + wave * 2 + pt;
-        pv[pt] = oy < p.Ho && ox < p.Wo;
-        mm[pt] = oy * p.Wo + ox;
-      }
-      yconv_epilogue<T, NT, MTW>(p, nblk, g, mm, pv, accw);
-      return;
-    }
-  }
 #ifdef FLOPE_STAG_DBG
   unsigned long long yst[5] = {0, 0, 0, 0, 0};
   const unsigned long long yrt0 = __builtin_amdgcn_s_memrealtime();
@@ -739,23 +681,10 @@ __global__ __launch_bounds__(256) void ybneck_kernel(const YBneckP p) {
   else ybneck_body<T, NT1, NT2, 8>(p, blockIdx.x, ylds);
 }
 
-// Workgroups are handed to the 8 XCDs round-robin (flat id mod 8), each XCD with its own 4 MiB L2.  On the large maps the
-// nine taps of a 3x3 conv re-read every input pixel nine times: with the natural order every XCD touches the whole map
-// (7.5 MB at 184 x 320 x 64) and the re-reads fall out of its L2.  Remapped, XCD x owns one contiguous run of tiles (an
-// image band): flat id b -> start(b mod 8) + b div 8 with start(x) = x * (n div 8) + min(x, n mod 8)  (a bijection on [0, n)).
-__device__ __forceinline__ int xcd_band(const int b, const int n) {
-  const int x = b & 7, q = n >> 3, r = n & 7;
-  return x * q + min(x, r) + (b >> 3);
-}
-
 template <typename T, int NT, bool K3, bool SPLITK>
 __global__ __launch_bounds__(256) void yconv_kernel(const YConvP p) {
   extern __shared__ __attribute__((aligned(16))) char ylds[];        // SPLITK: combine scratch; tile path: the input patch
-  int bx = blockIdx.x, by = blockIdx.y;
-  if (!SPLITK && p.xcd) {
-    const int nbx = gridDim.x, lb = xcd_band(by * nbx + bx, nbx * gridDim.y);
-    by = lb / nbx; bx = lb - by * nbx;
-  }
+  const int bx = blockIdx.x, by = blockIdx.y;
   if constexpr (!SPLITK) {
     if (p.tile) { yconv_tile_body<T, NT, K3>(p, bx, by, ylds); return; }
   }
@@ -816,7 +745,7 @@ __global__ __launch_bounds__(256) void ymulti_kernel(const YMultiP* __restrict__
   int s = 0;
   for (int i = 1; i < P.n; ++i) s = b >= P.op[i].start ? i : s;
   const YMultiOp& o = P.op[s];
-  int lb = b - o.start;                                   // op starts are multiples of 8: lb mod 8 is the XCD
+  const int lb = b - o.start;                             // op starts are multiples of 8: lb mod 8 is the XCD
   if (lb >= o.nblocks) return;
   if (o.code == 12) { ydw_body<T>(o.u.d, lb); return; }
   if (o.code >= 16) {
@@ -831,7 +760,6 @@ __global__ __launch_bounds__(256) void ymulti_kernel(const YMultiP* __restrict__
     }
     return;
   }
-  if (o.u.c.xcd) lb = xcd_band(lb, o.nblocks);
   const int by = lb / o.nbx, bx = lb - by * o.nbx;
   if (o.u.c.tile) {
     switch (o.code) {
@@ -857,27 +785,6 @@ __global__ __launch_bounds__(256) void ymulti_kernel(const YMultiP* __restrict__
     case 9: yconv_body<T, 4, false, true>(o.u.c, bx, by, red); break;
     case 10: yconv_body<T, 4, true, false>(o.u.c, bx, by, red); break;
     default: yconv_body<T, 4, true, true>(o.u.c, bx, by, red); break;
-  }
-}
-
-// A chain of 1x1 convs on a small map in one launch (yolo.h YChainP).  Workgroup = one 32-pixel tile; for every conv of the chain its
-// four waves take channel blocks w, w + 4, ... (the full K loop each: no split-K partial sums), then a workgroup barrier -- which on
-// this target also completes the wave's stores (vmcnt) and makes them visible to the workgroup's later loads (one CU, one L1).
-template <typename T>
-__global__ __launch_bounds__(256) void ychain_kernel(const YChainP* __restrict__ Pd) {
-  const YChainP& P = *Pd;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int m_base = blockIdx.x * 32;
-  for (int i = 0; i < P.n; ++i) {
-    const YConvP& p = P.op[i];
-    const int nt = P.nt[i];
-    const int nby = (p.Cout + 16 * nt - 1) / (16 * nt);
-    for (int b = wave; b < nby; b += 4) {
-      if (nt == 1) yconv_body_at<T, 1, false, false>(p, m_base, b, nullptr, 0, b);
-      else if (nt == 2) yconv_body_at<T, 2, false, false>(p, m_base, b, nullptr, 0, b);
-      else yconv_body_at<T, 4, false, false>(p, m_base, b, nullptr, 0, b);
-    }
-    __syncthreads();
   }
 }
 
@@ -1491,66 +1398,51 @@ static void yconv_go(const YConvP& p, int nt, bool splitk, dim3 grid, int lds, h
 #undef GO
 }
 
-static int g_splitk_max_m = 8192;                           // split-K (one 32-pixel tile per workgroup, K over its 4 waves) up to this map size
-extern "C" int flope_yconv_splitk_max_m(int m) { const int prev = g_splitk_max_m; if (m >= 0) g_splitk_max_m = m; return prev; }
-static int g_wlds_mode = 0;                                  // 1: tile path, 3x3, >= 8 K steps keeps the weight image in LDS too (measured
-                                                             // slower: 0.78 vs 0.74 ms -- 96 KB of LDS leave one workgroup per CU on the large maps)
-extern "C" int flope_yconv_wlds_mode(int mode) { const int prev = g_wlds_mode; if (mode == 0 || mode == 1) g_wlds_mode = mode; return prev; }
-static int g_tile_mode = 1;                                  // 1: LDS-staged 8 x 16 tiles for every non-split-K conv; 0: fragments from global
-extern "C" int flope_yconv_tile_mode(int mode) { const int prev = g_tile_mode; if (mode == 0 || mode == 1) g_tile_mode = mode; return prev; }
+constexpr int kYSplitkMaxM = 8192;                          // split-K (one 32-pixel tile per workgroup, K over its 4 waves) up to this map size
 constexpr int kYTileLdsMax = 96 * 1024, kYBneckLdsMax = 144 * 1024;   // patch alone; patch + weight image(s)
 
-// fills the launch-derived fields of *q (tile, tiles_x, pw_*), -> split-K?, grid, dynamic LDS bytes
-static bool yconv_geometry(const YConvP* p, int nt, YConvP* q, bool* splitk, int* nbx, int* nby, int* lds) {
+// fills the launch-derived fields of *q (tile, tiles_x, pw_*), -> split-K?, grid, dynamic LDS bytes.  tile = 0: no LDS-staged
+// tiles, fragments straight from global memory (the reference path of the tile kernels)
+static bool yconv_geometry(const YConvP* p, int nt, int tile, YConvP* q, bool* splitk, int* nbx, int* nby, int* lds) {
   if ((p->k != 1 && p->k != 3) || p->Cin % 8 || (nt != 1 && nt != 2 && nt != 4) || p->M < 1) return false;
   const int rows = p->out_mode == 2 ? 4 * p->dc : p->Cout;
   if (p->out_mode == 2 && (p->dc % (16 * nt) || p->res)) return false;
   *q = *p;
-  *splitk = p->M <= g_splitk_max_m && p->ksteps >= 8;        // small map, long K: one tile per workgroup, K over its 4 waves
+  *splitk = p->M <= kYSplitkMaxM && p->ksteps >= 8;          // small map, long K: one tile per workgroup, K over its 4 waves
   *nby = (rows + 16 * nt - 1) / (16 * nt);
   const int PW = 15 * p->stride + p->k, PH = 7 * p->stride + p->k, patch = PH * PW * (p->Cin * 2 + 16);
-  q->tile = (!*splitk && g_tile_mode && patch <= kYTileLdsMax) ? 1 : 0;
-  q->wlds = 0;
+  q->tile = (!*splitk && tile && patch <= kYTileLdsMax) ? 1 : 0;
   if (q->tile) {
     q->tiles_x = (p->Wo + 15) / 16;
     *nbx = q->tiles_x * ((p->Ho + 7) / 8);
     flope_host::fastdiv_magic((unsigned)PW, &q->pw_mg, &q->pw_sh);
     *lds = patch;
-    const int wbytes = p->ksteps * nt * 1024;
-    if (g_wlds_mode && p->k == 3 && p->ksteps >= 8 && patch + wbytes <= kYBneckLdsMax) { q->wlds = 1; *lds = patch + wbytes; }
   } else {
     *nbx = *splitk ? (p->M + 31) / 32 : (p->M + 127) / 128;
     *lds = *splitk ? 3 * 2 * nt * 4 * 64 * 4 : 0;
   }
   return true;
 }
-static bool yconv_wants_xcd_bands(const YConvP* p, bool splitk, int nbx, int nby, int mode) {
-  return mode != 0 && !splitk && nbx * nby >= 64 && (mode == 2 || p->k == 3);
-}
-static int g_xcd_mode = 0;                                   // 0 never, 1 3x3 convs on >= 64 workgroups, 2 those and 1x1 convs
-extern "C" int flope_yconv_xcd_mode(int mode) { const int prev = g_xcd_mode; if (mode >= 0 && mode <= 2) g_xcd_mode = mode; return prev; }
 
 // nt = channel tiles of 16 per workgroup column (1, 2 or 4): rows of p->w / p->bias = ceil(Cout / (16 nt)) * 16 nt
-extern "C" int flope_yconv_launch(const YConvP* p, int dtype, int nt, void* stream) {
+extern "C" int flope_yconv_launch(const YConvP* p, int dtype, int nt, int tile, void* stream) {
   bool splitk; int nbx, nby, lds;
   YConvP q;
-  if (!yconv_geometry(p, nt, &q, &splitk, &nbx, &nby, &lds)) return (int)hipErrorInvalidValue;
+  if (!yconv_geometry(p, nt, tile, &q, &splitk, &nbx, &nby, &lds)) return (int)hipErrorInvalidValue;
   const dim3 grid(nbx, nby);
-  q.xcd = yconv_wants_xcd_bands(p, splitk, nbx, nby, g_xcd_mode) ? 1 : 0;
   if (dtype == 0) yconv_go<bf16_t>(q, nt, splitk, grid, lds, (hipStream_t)stream); else yconv_go<f16_t>(q, nt, splitk, grid, lds, (hipStream_t)stream);
   return (int)hipGetLastError();
 }
 
 // ---- several independent ops in one grid (ymulti_kernel) ---------------------------------------------------------
-extern "C" int flope_ymulti_add_conv(YMultiP* m, const YConvP* p, int nt) {
+extern "C" int flope_ymulti_add_conv(YMultiP* m, const YConvP* p, int nt, int tile) {
   bool splitk; int nbx, nby, lds;
   YConvP q;
-  if (m->n >= kYMultiMax || !yconv_geometry(p, nt, &q, &splitk, &nbx, &nby, &lds)) return (int)hipErrorInvalidValue;
+  if (m->n >= kYMultiMax || !yconv_geometry(p, nt, tile, &q, &splitk, &nbx, &nby, &lds)) return (int)hipErrorInvalidValue;
   YMultiOp& o = m->op[m->n++];
   o.code = (nt == 1 ? 0 : nt == 2 ? 4 : 8) + (p->k == 3 ? 2 : 0) + (splitk ? 1 : 0);
   o.nbx = nbx; o.start = m->total; o.nblocks = nbx * nby; o.u.c = q;
   m->lds = std::max(m->lds, lds);
-  o.u.c.xcd = yconv_wants_xcd_bands(p, splitk, nbx, nby, g_xcd_mode) ? 1 : 0;
   m->total += (o.nblocks + 7) / 8 * 8;
   return 0;
 }
@@ -1621,16 +1513,6 @@ extern "C" int flope_ymulti_launch(const YMultiP* m, const YMultiP* m_dev, int d
   return (int)hipGetLastError();
 }
 
-// can this conv be a member of a chain?  (1x1, stride 1, 16-bit output view, a small map)
-extern "C" int flope_ychain_ok(const YConvP* p, int nt) {
-  return p->k == 1 && p->stride == 1 && p->out_mode == 0 && p->M >= 1 && p->M <= 4096 && (nt == 1 || nt == 2 || nt == 4) && p->Hi == p->Ho && p->Wi == p->Wo;
-}
-extern "C" int flope_ychain_launch(const YChainP* c, const YChainP* c_dev, int dtype, void* stream) {
-  if (!c_dev || c->n < 2 || c->n > kYChainMax || c->tiles < 1) return (int)hipErrorInvalidValue;
-  YDISPATCH(dtype, ychain_kernel, dim3(c->tiles), dim3(256), 0, (hipStream_t)stream, c_dev);
-  return (int)hipGetLastError();
-}
-
 extern "C" int flope_ydw_launch(const YDwP* p, int dtype, void* stream) {
   if (p->C % 8) return (int)hipErrorInvalidValue;
   const int total = p->H * p->W * (p->C / 8);
@@ -1639,12 +1521,11 @@ extern "C" int flope_ydw_launch(const YDwP* p, int dtype, void* stream) {
 }
 
 constexpr size_t kYSppfLdsMax = 144 * 1024;
-static int g_pool_lds = 1;                                   // 0: the ring kernel for every map (A/B, parity of the two)
-extern "C" int flope_ypool_lds_mode(int mode) { const int prev = g_pool_lds; if (mode == 0 || mode == 1) g_pool_lds = mode; return prev; }
-extern "C" int flope_ypool_launch(const YPoolP* p, int dtype, void* stream) {
+// use_lds = 0: the ring kernel for every map (the reference path of the LDS kernel)
+extern "C" int flope_ypool_launch(const YPoolP* p, int dtype, int use_lds, void* stream) {
   if (p->C % 8 || p->n < 1 || p->n > 3) return (int)hipErrorInvalidValue;
   const size_t lds = (size_t)2 * p->H * p->W * 16;
-  if (g_pool_lds && lds <= kYSppfLdsMax) {
+  if (use_lds && lds <= kYSppfLdsMax) {
     YDISPATCH(dtype, ysppf_lds_kernel, dim3(p->C / 8), dim3(256), lds, (hipStream_t)stream, *p);
     return (int)hipGetLastError();
   }

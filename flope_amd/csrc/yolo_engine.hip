@@ -22,20 +22,15 @@
 #include <string>
 #include <vector>
 
-extern "C" int flope_yconv_launch(const YConvP* p, int dtype, int nt, void* stream);
+extern "C" int flope_yconv_launch(const YConvP* p, int dtype, int nt, int tile, void* stream);
 extern "C" int flope_ydw_launch(const YDwP* p, int dtype, void* stream);
-extern "C" int flope_ymulti_add_conv(YMultiP* m, const YConvP* p, int nt);
+extern "C" int flope_ymulti_add_conv(YMultiP* m, const YConvP* p, int nt, int tile);
 extern "C" int flope_ymulti_add_dw(YMultiP* m, const YDwP* p);
 extern "C" int flope_ymulti_add_bneck(YMultiP* m, const YConvP* c1, int nt1, const YConvP* c2, int nt2);
 extern "C" int flope_ybneck_fusable(const YConvP* c1, int nt1, const YConvP* c2, int nt2);
 extern "C" int flope_ybneck_launch(const YConvP* c1, int nt1, const YConvP* c2, int nt2, int dtype, void* stream);
 extern "C" int flope_ymulti_launch(const YMultiP* m, const YMultiP* m_dev, int dtype, void* stream);
-extern "C" int flope_yconv_xcd_mode(int mode);
-extern "C" int flope_yconv_tile_mode(int mode);
-extern "C" int flope_yconv_splitk_max_m(int m);
-extern "C" int flope_ypool_lds_mode(int mode);
-extern "C" int flope_yconv_wlds_mode(int mode);
-extern "C" int flope_ypool_launch(const YPoolP* p, int dtype, void* stream);
+extern "C" int flope_ypool_launch(const YPoolP* p, int dtype, int use_lds, void* stream);
 extern "C" int flope_yup_launch(const YUpP* p, void* stream);
 extern "C" int flope_yattn_init();
 extern "C" int flope_yattn_launch(const YAttnP* p, int dtype, int variant, void* stream);
@@ -49,10 +44,6 @@ extern "C" int flope_yread_launch(const void* src, int is_f32, int H, int W, int
 extern "C" int flope_y32_conv_launch(const YConvP* p, void* stream);
 extern "C" int flope_y32m_conv_launch(const YConvP* p, void* stream);
 extern "C" int flope_y32m_conv_ok(const YConvP* p);
-extern "C" int flope_ychain_ok(const YConvP* p, int nt);
-extern "C" int flope_ychain_launch(const YChainP* c, const YChainP* c_dev, int dtype, void* stream);
-extern "C" int flope_y32m_chain_ok(const YConvP* p);
-extern "C" int flope_y32m_chain_launch(const YChainP* c, const YChainP* c_dev, void* stream);
 extern "C" int flope_y32m_multi_add_conv(YMultiP* m, const YConvP* p);
 extern "C" int flope_y32m_multi_add_dw(YMultiP* m, const YDwP* p);
 extern "C" int flope_y32m_multi_launch(const YMultiP* m, const YMultiP* m_dev, void* stream);
@@ -88,8 +79,7 @@ struct Op {
 };
 
 // One launch of the schedule: a single op, or up to kYMultiMax independent conv / depthwise ops of one level in one grid.
-// (r05) ... or a CHAIN of consecutive 1x1 convs on one small map, run back to back by one grid (yolo.h YChainP).
-struct Launch { int op = -1; YMultiP multi; YMultiP* multi_dev = nullptr; std::vector<int> members; YChainP chain; YChainP* chain_dev = nullptr; };
+struct Launch { int op = -1; YMultiP multi; YMultiP* multi_dev = nullptr; std::vector<int> members; };
 
 struct Tap { int is_f32 = 0; const void* ptr = nullptr; int H = 0, W = 0, C = 0, ld = 0; };
 
@@ -119,9 +109,10 @@ struct flope_yolo {
   // than the overlap returned (1.31 ms; removed).  What does pay is putting the independent ops of one dependency level
   // into ONE grid (ymulti_kernel): option "batch", default on.
   int opt_batch = 1;
-  int opt_chain = 0;                                          // runs of 1x1 convs on one small map as one launch (r05: built, measured no faster -- profiles/r05_yolo_chain.txt; off)
   int opt_f32mfma = 1;                                        // float32 mode: convolutions on the exact-fp32 MFMA kernel (0: the plain fused-multiply-add kernels, its checker)
   int opt_bneck = 1;                                          // 1: Bottleneck pairs as one fused launch (ybneck_kernel); 0: two conv launches
+  int opt_tile = 1;                                           // 1: large-map convs stage an 8 x 16 tile's input patch in LDS; 0: fragments from global memory
+  int opt_pool_lds = 1;                                       // 1: SPPF's pools in LDS where the map fits; 0: the ring kernel
   int opt_graph = 0;                                          // 1: flope_yolo_detect replays a captured hipGraph; 0 (default)
   struct Captured { GraphKey key; hipGraphExec_t exec; hipEvent_t done; };   // done: recorded behind the last replay
   std::vector<Captured> graphs;                               // captured detect sequences, most recently used last (<= kGraphCache)
@@ -480,15 +471,15 @@ int launch_op(flope_yolo* e, const Op& op, hipStream_t st) {
     }
   }
   switch (op.kind) {
-    case Op::CONV: return flope_yconv_launch(&op.conv, e->dtype, op.nt, st);
+    case Op::CONV: return flope_yconv_launch(&op.conv, e->dtype, op.nt, e->opt_tile, st);
     case Op::DW: return flope_ydw_launch(&op.dw, e->dtype, st);
-    case Op::POOL: return flope_ypool_launch(&op.pool, e->dtype, st);
+    case Op::POOL: return flope_ypool_launch(&op.pool, e->dtype, e->opt_pool_lds, st);
     case Op::UP: return flope_yup_launch(&op.up, st);
     case Op::ATTN: return flope_yattn_launch(&op.attn, e->dtype, e->opt_generic_attn, st);
     case Op::BNECK: {
       if (e->opt_bneck) return flope_ybneck_launch(&op.conv, op.nt, &op.conv2, op.nt2, e->dtype, st);
-      const int s = flope_yconv_launch(&op.conv, e->dtype, op.nt, st);
-      return s ? s : flope_yconv_launch(&op.conv2, e->dtype, op.nt2, st);
+      const int s = flope_yconv_launch(&op.conv, e->dtype, op.nt, e->opt_tile, st);
+      return s ? s : flope_yconv_launch(&op.conv2, e->dtype, op.nt2, e->opt_tile, st);
     }
   }
   return (int)hipErrorInvalidValue;
@@ -499,7 +490,6 @@ int launch_op(flope_yolo* e, const Op& op, hipStream_t st) {
 inline int sched_index(const flope_yolo* e) { return (e->opt_batch && (e->dtype != FLOPE_DT_F32 || e->opt_f32mfma)) ? 1 : 0; }
 
 int launch_one(flope_yolo* e, const Launch& L, hipStream_t st) {
-  if (L.chain_dev) return e->dtype == FLOPE_DT_F32 ? flope_y32m_chain_launch(&L.chain, L.chain_dev, st) : flope_ychain_launch(&L.chain, L.chain_dev, e->dtype, st);
   if (L.op >= 0) return launch_op(e, e->ops[L.op], st);
   return e->dtype == FLOPE_DT_F32 ? flope_y32m_multi_launch(&L.multi, L.multi_dev, st) : flope_ymulti_launch(&L.multi, L.multi_dev, e->dtype, st);
 }
@@ -507,7 +497,7 @@ int launch_one(flope_yolo* e, const Launch& L, hipStream_t st) {
 std::string launch_name(const flope_yolo* e, const Launch& L) {
   if (L.op >= 0) return e->ops[L.op].name;
   std::string n;
-  for (int i : L.members) n += (n.empty() ? "" : (L.chain_dev ? " -> " : " | ")) + e->ops[i].name;
+  for (int i : L.members) n += (n.empty() ? "" : " | ") + e->ops[i].name;
   return n;
 }
 
@@ -545,78 +535,36 @@ int build_schedules(flope_yolo* e) {
   const bool f32 = e->dtype == FLOPE_DT_F32;
   for (int lv = 0; lv < depth; ++lv) {
     // one grid's dynamic LDS is that of its hungriest op, so a fused Bottleneck (up to 134 KB) leaves the plain convs it shares a
-    // grid with one workgroup per CU -- measured, sharing still wins (0.741 vs 0.757 ms per frame: a launch less per level);
-    // bneck = 2 keeps them in grids of their own
-    std::vector<int> classes[2], single;
+    // grid with one workgroup per CU -- measured, sharing still wins (0.741 vs 0.757 ms per frame: a launch less per level)
+    std::vector<int> batchable, single;
     for (int i = 0; i < n; ++i)
       if (e->ops[i].level == lv) {
         const Op& op = e->ops[i];
         if (f32 && op.kind == Op::CONV && !flope_y32m_conv_ok(&op.conv)) single.push_back(i);   // launch_op falls back to the plain kernel
-        else if (op.kind == Op::CONV || op.kind == Op::DW) classes[0].push_back(i);
-        else if (op.kind == Op::BNECK && e->opt_bneck) classes[e->opt_bneck == 2 ? 1 : 0].push_back(i);
+        else if (op.kind == Op::CONV || op.kind == Op::DW || (op.kind == Op::BNECK && e->opt_bneck)) batchable.push_back(i);
         else single.push_back(i);
       }
     for (int i : single) { Launch L; L.op = i; e->sched[1].push_back(L); }
-    for (const std::vector<int>& batchable : classes)
-      for (size_t at = 0; at < batchable.size(); at += kYMultiMax) {
-        const size_t m = std::min(batchable.size() - at, (size_t)kYMultiMax);
-        Launch L;
-        if (m == 1) { L.op = batchable[at]; e->sched[1].push_back(L); continue; }
-        memset(&L.multi, 0, sizeof L.multi);
-        for (size_t k = 0; k < m; ++k) {
-          const Op& op = e->ops[batchable[at + k]];
-          const int s = f32 ? (op.kind == Op::CONV ? flope_y32m_multi_add_conv(&L.multi, &op.conv) : flope_y32m_multi_add_dw(&L.multi, &op.dw))
-                      : op.kind == Op::CONV ? flope_ymulti_add_conv(&L.multi, &op.conv, op.nt)
-                      : op.kind == Op::DW ? flope_ymulti_add_dw(&L.multi, &op.dw)
-                                          : flope_ymulti_add_bneck(&L.multi, &op.conv, op.nt, &op.conv2, op.nt2);
-          if (s) return yfail(e, FLOPE_EINVAL, "schedule: cannot batch " + op.name);
-          L.members.push_back(batchable[at + k]);
-        }
-        if (hipMalloc((void**)&L.multi_dev, sizeof(YMultiP)) != hipSuccess ||
-            hipMemcpy(L.multi_dev, &L.multi, sizeof(YMultiP), hipMemcpyHostToDevice) != hipSuccess)
-          return yfail(e, FLOPE_EHIP, "schedule: parameter table upload failed");
-        e->owned.push_back(L.multi_dev);
-        e->sched[1].push_back(L);
+    for (size_t at = 0; at < batchable.size(); at += kYMultiMax) {
+      const size_t m = std::min(batchable.size() - at, (size_t)kYMultiMax);
+      Launch L;
+      if (m == 1) { L.op = batchable[at]; e->sched[1].push_back(L); continue; }
+      memset(&L.multi, 0, sizeof L.multi);
+      for (size_t k = 0; k < m; ++k) {
+        const Op& op = e->ops[batchable[at + k]];
+        const int s = f32 ? (op.kind == Op::CONV ? flope_y32m_multi_add_conv(&L.multi, &op.conv) : flope_y32m_multi_add_dw(&L.multi, &op.dw))
+                    : op.kind == Op::CONV ? flope_ymulti_add_conv(&L.multi, &op.conv, op.nt, e->opt_tile)
+                    : op.kind == Op::DW ? flope_ymulti_add_dw(&L.multi, &op.dw)
+                                        : flope_ymulti_add_bneck(&L.multi, &op.conv, op.nt, &op.conv2, op.nt2);
+        if (s) return yfail(e, FLOPE_EINVAL, "schedule: cannot batch " + op.name);
+        L.members.push_back(batchable[at + k]);
       }
-  }
-  // r05: chains.  Consecutive single launches of the level schedule that are 1x1 stride-1 convs on the same small map become ONE launch
-  // (the 23 x 40 map's conv -> conv -> conv runs cost a dependent launch each, ~8 us for ~3 us of kernel): a 1x1 conv reads nothing but
-  // its own pixel, so a workgroup can push its pixel tile through the whole run; everything else the run reads was complete before it.
-  if (e->opt_chain) {
-    std::vector<Launch> out;
-    std::vector<int> run;
-    auto chainable = [&](const Launch& L) {
-      if (L.op < 0 || L.chain_dev) return false;
-      const Op& op = e->ops[L.op];
-      if (op.kind != Op::CONV) return false;
-      return f32 ? (e->opt_f32mfma && flope_y32m_chain_ok(&op.conv) != 0) : flope_ychain_ok(&op.conv, op.nt) != 0;
-    };
-    auto flush = [&]() -> int {
-      for (size_t at = 0; at < run.size();) {
-        const size_t m = std::min(run.size() - at, (size_t)kYChainMax);
-        if (m < 2) { Launch L; L.op = run[at]; out.push_back(L); at += m; continue; }
-        Launch L;
-        memset(&L.chain, 0, sizeof L.chain);
-        L.chain.n = (int)m;
-        const int M = e->ops[run[at]].conv.M;
-        L.chain.tiles = f32 ? (M + 15) / 16 : (M + 31) / 32;
-        for (size_t k = 0; k < m; ++k) { const Op& op = e->ops[run[at + k]]; L.chain.op[k] = op.conv; L.chain.nt[k] = op.nt; L.members.push_back(run[at + k]); }
-        if (hipMalloc((void**)&L.chain_dev, sizeof(YChainP)) != hipSuccess || hipMemcpy(L.chain_dev, &L.chain, sizeof(YChainP), hipMemcpyHostToDevice) != hipSuccess)
-          return yfail(e, FLOPE_EHIP, "schedule: chain table upload failed");
-        e->owned.push_back(L.chain_dev);
-        out.push_back(L);
-        at += m;
-      }
-      run.clear();
-      return FLOPE_OK;
-    };
-    for (const Launch& L : e->sched[1]) {
-      if (chainable(L) && (run.empty() || e->ops[run.back()].conv.M == e->ops[L.op].conv.M)) { run.push_back(L.op); continue; }
-      if (int rc = flush()) return rc;
-      if (chainable(L)) run.push_back(L.op); else out.push_back(L);
+      if (hipMalloc((void**)&L.multi_dev, sizeof(YMultiP)) != hipSuccess ||
+          hipMemcpy(L.multi_dev, &L.multi, sizeof(YMultiP), hipMemcpyHostToDevice) != hipSuccess)
+        return yfail(e, FLOPE_EHIP, "schedule: parameter table upload failed");
+      e->owned.push_back(L.multi_dev);
+      e->sched[1].push_back(L);
     }
-    if (int rc = flush()) return rc;
-    e->sched[1].swap(out);
   }
   return FLOPE_OK;
 }
@@ -877,7 +825,7 @@ extern "C" int flope_yolo_detect(flope_yolo_handle e, const uint8_t* frame_dev, 
   GraphKey key;
   memset(&key, 0, sizeof key);                              // the struct has tail padding and is compared bytewise
   key.frame = frame_dev; key.det = det_dev; key.count = count_dev; key.mask = mask_dev; key.conf = conf; key.iou = iou;
-  key.max_det = max_det; key.batch = e->opt_batch * 4 + e->opt_bneck + e->opt_f32mfma * 16 + e->opt_chain * 32; key.generic_attn = e->opt_generic_attn;
+  key.max_det = max_det; key.batch = e->opt_batch * 4 + e->opt_bneck + e->opt_f32mfma * 16; key.generic_attn = e->opt_generic_attn;
   hipGraphExec_t exec = nullptr;
   for (size_t i = 0; i < e->graphs.size(); ++i)
     if (memcmp(&key, &e->graphs[i].key, sizeof key) == 0) {
@@ -926,33 +874,19 @@ extern "C" int flope_yolo_read_tensor(flope_yolo_handle e, const char* name, flo
 extern "C" int flope_yolo_set_option(flope_yolo_handle e, const char* name, int value) {
   if (!e || !name) return yfail(e, FLOPE_EINVAL, "flope_yolo_set_option: NULL argument");
   if (!strcmp(name, "generic_attn")) { const int prev = e->opt_generic_attn; e->opt_generic_attn = value != 0; return prev; }
-  if (!strcmp(name, "xcd") || !strcmp(name, "tile") || !strcmp(name, "splitk_max_m") || !strcmp(name, "wlds")) {   // process-wide A/B knobs; the batched schedule bakes them in
-    const int prev = !strcmp(name, "xcd") ? flope_yconv_xcd_mode(value) : !strcmp(name, "tile") ? flope_yconv_tile_mode(value)
-                   : !strcmp(name, "wlds") ? flope_yconv_wlds_mode(value) : flope_yconv_splitk_max_m(value);
-    if (e->loaded) {
+  // the schedules and any captured graph bake these in: a change rebuilds this handle's schedules and drops its graphs
+  auto replan = [e](int* opt, int value) -> int {
+    const int prev = *opt; *opt = value;
+    if (e->loaded && prev != value) {
       if (int rc = build_schedules(e)) return rc;
       drop_graphs(e);
     }
     return prev;
-  }
-  if (!strcmp(name, "pool_lds")) return flope_ypool_lds_mode(value);
-  if (!strcmp(name, "bneck")) {
-    const int prev = e->opt_bneck; e->opt_bneck = value < 0 ? 0 : (value > 2 ? 2 : value);
-    if (e->loaded && prev != e->opt_bneck) {
-      if (int rc = build_schedules(e)) return rc;
-      drop_graphs(e);
-    }
-    return prev;
-  }
+  };
+  if (!strcmp(name, "bneck")) return replan(&e->opt_bneck, value != 0);
+  if (!strcmp(name, "tile")) return replan(&e->opt_tile, value != 0);
+  if (!strcmp(name, "pool_lds")) return replan(&e->opt_pool_lds, value != 0);
   if (!strcmp(name, "batch")) { const int prev = e->opt_batch; e->opt_batch = value != 0; return prev; }
-  if (!strcmp(name, "chain")) {
-    const int prev = e->opt_chain; e->opt_chain = value != 0;
-    if (e->loaded && prev != e->opt_chain) {
-      if (int rc = build_schedules(e)) return rc;
-      drop_graphs(e);
-    }
-    return prev;
-  }
   if (!strcmp(name, "f32mfma")) { const int prev = e->opt_f32mfma; e->opt_f32mfma = value != 0; return prev; }
   if (!strcmp(name, "graph")) { const int prev = e->opt_graph; e->opt_graph = value != 0; return prev; }
   return yfail(e, FLOPE_EINVAL, std::string("flope_yolo_set_option: unknown option ") + name);
@@ -999,9 +933,6 @@ extern "C" int flope_yolo_profile(flope_yolo_handle e, const uint8_t* frame_dev,
       const Op& op = e->ops[sched[i].op];
       snprintf(line, sizeof line, "%3zu %7.2f L%-2d %s %s\n", i, u, op.level,
                op.kind == Op::DW ? "dw" : op.kind == Op::POOL ? "pool" : op.kind == Op::UP ? "up" : op.kind == Op::BNECK ? "bottleneck" : "attn", op.name.c_str());
-    } else if (sched[i].chain_dev) {
-      snprintf(line, sizeof line, "%3zu %7.2f L%-2d chain x%d (%d workgroups) %.200s\n", i, u, e->ops[sched[i].members[0]].level, sched[i].chain.n, sched[i].chain.tiles,
-               launch_name(e, sched[i]).c_str());
     } else {
       snprintf(line, sizeof line, "%3zu %7.2f L%-2d multi x%d (%d workgroups) %.200s\n", i, u, e->ops[sched[i].members[0]].level, sched[i].multi.n, sched[i].multi.total,
                launch_name(e, sched[i]).c_str());

@@ -283,21 +283,22 @@ int flope_yolo_forward(flope_yolo_handle h, const uint8_t* frame_dev, void* stre
  * confidence and class of every anchor) -- the last four after flope_yolo_detect.  dims_out[3] = {C,H,W}; dst_dev NULL = size
  * query only. */
 int flope_yolo_read_tensor(flope_yolo_handle h, const char* name, float* dst_dev, int64_t* dims_out, void* stream);
-/* runtime knobs (A/B variants inside one build; each returns the previous value or <0):
+/* options of one handle (each call returns the previous value or <0; an unknown name is FLOPE_EINVAL):
  *   "graph" (default 0): flope_yolo_detect captures its launch sequence into a hipGraph the first time it sees a
  *       (frame_dev, thresholds, output buffers) tuple and replays it afterwards -- keep those pointers stable across frames
- *       (measured as no gain on MI355X: the GPU-side chain of short kernels is the bound, not the host);
+ *       (measured as no gain on MI355X: the GPU-side chain of short kernels is the bound, not the host).
+ * The others force the reference path that tests compare a shipped kernel against; the defaults are the shipped paths:
  *   "batch" (default 1): the independent launches of one dependency level of the graph (the Segment head's box / class /
  *       coefficient branches of a level, the Proto block beside them, parallel 1x1 convs inside C3k) share one grid; 0: one
  *       launch per op in the program order of the ultralytics yaml;
  *   "bneck" (default 1): Bottleneck pairs (3x3 -> 3x3, <= 64 channels) as one fused launch with the intermediate map in LDS;
- *       2: fused, but never in one grid with plain convs; 0: two conv launches;
- *   "generic_attn" (default 0): C2PSA attention on the generic fp32 kernel instead of the MFMA one;
- *   A/B knobs of the conv kernels, process-wide (every handle of the process; the schedule is rebuilt): "tile" (default 1:
- *       large maps stage an 8 x 16 tile's input patch in LDS; 0: fragments straight from global memory), "splitk_max_m"
- *       (default 8192: maps up to this many pixels split K over the four waves of a workgroup), "xcd" (default 0: 1 / 2 remap the
- *       workgroup order so that an XCD owns an image band -- measured as no gain), "pool_lds" (default 1: SPPF's pools in LDS), "wlds" (default 0: 1 stages the weight image of long-K
- *       3x3 tiles in LDS too -- measured slower, 0.78 vs 0.74 ms: 96 KB of LDS leave one workgroup per CU). */
+ *       0: two conv launches;
+ *   "generic_attn" (default 0): 1 runs C2PSA attention on the generic fp32 kernel instead of the MFMA one;
+ *   "f32mfma" (default 1): FLOPE_DT_F32 convolutions and attention on the exact-fp32 MFMA kernels; 0: the plain
+ *       fused-multiply-add kernels, one launch per op;
+ *   "tile" (default 1): large-map convs stage an 8 x 16 tile's input patch in LDS; 0: fragments straight from global memory;
+ *   "pool_lds" (default 1): SPPF's cascaded max-pools in LDS where the map fits; 0: the 13 x 13 ring kernel.
+ * "bneck", "tile" and "pool_lds" rebuild this handle's schedules and drop its captured graphs when they change. */
 int flope_yolo_set_option(flope_yolo_handle h, const char* name, int value);
 /* developer aid: `iters` forwards with a HIP event pair around every launch of the graph; writes a text table (mean
  * microseconds per launch, kind, geometry, state_dict name) into text_out[cap] */

@@ -85,14 +85,13 @@ def test_attention_kernels_agree(ysd):
     y.close()
 
 
-def test_batched_launches_and_graph_replay_do_not_change_a_bit(ysd):
+def test_level_batching_and_graph_replay_do_not_change_a_bit(ysd):
     """Default schedule: the independent ops of one dependency level (Segment-head branches, Proto, the parallel 1x1 convs
     of C3k ...) share one grid (ymulti_kernel).  One launch per op in program order, and a captured hipGraph replay of
     either, give the identical result: every graph output, the head rows, boxes and the mask."""
     from flope_amd.yolo_weights import synthetic_frame
     img = synthetic_frame(9, 1080, 1920)
     y = _engine(ysd, 1080, 1920, 1280)
-    y.set_option("chain", 0)                  # (r05 option, off by default: chained 1x1 convs sum K in one wave instead of four -- their own test below)
     outs, launches = [], []
     for batch, graph in ((1, 1), (0, 0), (1, 0), (0, 1), (1, 1)):        # captured hipGraph replay and eager launches
         y.set_option("batch", batch)
@@ -110,64 +109,30 @@ def test_batched_launches_and_graph_replay_do_not_change_a_bit(ysd):
     y.close()
 
 
-@pytest.mark.parametrize("dtype", ["f16", "f32"])
-def test_chained_1x1_convs_equal_the_separate_launches(ysd, dtype):
-    """r05: runs of consecutive 1x1 convs on one small map (C3k / SPPF / C2PSA on the 23 x 40 map, the tails of the
-    head branches) as ONE launch (option chain = 1): a workgroup pushes its pixel tile through the whole run, its waves taking the
-    channel blocks side by side with the full K loop each.  Against the separate launches (chain = 0, the default: K split over four
-    waves, partial sums added in wave order) the results agree to float32 summation order -- 16-bit maps to a rounding of a few outputs,
-    float32 maps to ~1e-6 -- the detections are the same anchors, and 9 fewer launches run.  Measured (profiles/r05_yolo_chain.txt): no
-    faster (16-bit 0.672 -> 0.667 ms per frame, float32 0.988 -> 1.058): a conv inside a chain costs what its launch did -- the store
-    drain + barrier + cold first loads between two convs are the same dependent round trips a kernel boundary is -- so it stays off."""
-    from flope_amd.yolo_weights import synthetic_frame
-    for (H, W, imgsz) in ((1080, 1920, 1280), (360, 640, 640)):
-        img = synthetic_frame(9, H, W)
-        y = _engine(ysd, H, W, imgsz, dtype)
-        names = ("8", "9", "10", "13", "16", "19", "22", "proto", "box0", "cls1", "coef2", "cls2", "box2")
-        outs, dets, launches = [], [], []
-        for chain in (1, 0):
-            assert y.set_option("chain", chain) in (0, 1)
-            dets.append(y.detect(img, 0.1))
-            outs.append({k: y.read_tensor(k).cpu() for k in names})
-            launches.append(y.launches())
-        y.set_option("chain", 1)
-        tol = 2e-3 if dtype == "f16" else 2e-6
-        for k in names:
-            assert _rel(outs[0][k], outs[1][k]) <= tol, (k, _rel(outs[0][k], outs[1][k]))
-        assert launches[0] <= launches[1] - 6, launches
-        (b1, s1, _, a1, m1), (b0, s0, _, a0, m0) = dets
-        # the same anchors (two confidences a rounding apart may sort either way), the same boxes per anchor
-        assert len(a1) >= 3 and sorted(a1.tolist()) == sorted(a0.tolist())
-        o1, o0 = np.argsort(a1), np.argsort(a0)
-        assert np.abs(b1[o1] - b0[o0]).max() <= (1.0 if dtype == "f16" else 1e-3) and np.abs(s1[o1] - s0[o0]).max() <= (2e-3 if dtype == "f16" else 1e-5)
-        assert (m1 != m0).mean() <= (2e-3 if dtype == "f16" else 1e-5)
-        y.set_option("chain", 0)
-        y.close()
-
-
-def test_lds_tile_path_equals_the_global_fragment_path(ysd):
+def test_lds_tile_and_pool_paths_equal_their_reference_paths(ysd):
     """Large maps stage an 8 x 16 output tile's input patch in LDS (default); option tile=0 reads the same fragments
-    straight from global memory.  Same MFMA sequence per output pixel: every graph output and the head rows identical."""
+    straight from global memory.  Same MFMA sequence per output pixel: every graph output and the head rows identical.
+    Both options belong to one handle: a second detector of the process keeps the defaults."""
     from flope_amd.yolo_weights import synthetic_frame
     for (H, W, imgsz) in ((1080, 1920, 1280), (360, 640, 640), (250, 333, 320)):
         img = synthetic_frame(11, H, W)
         y = _engine(ysd, H, W, imgsz)
         outs = []
-        for tile, wlds in ((1, 1), (0, 1), (1, 0)):          # wlds: long-K 3x3 tiles keep their weight image in LDS as well
+        for tile in (1, 0):
             y.set_option("tile", tile)
-            y.set_option("wlds", wlds)
             y.forward(img)
             outs.append([y.read_tensor(k).cpu().numpy() for k in ("0", "1", "2", "3", "4", "13", "16", "19", "22", "proto", "box0", "cls0", "coef0", "box2")])
-        y.set_option("tile", 1)
-        y.set_option("wlds", 1)
-        for o in outs[1:]:
-            for a, b in zip(outs[0], o):
-                assert np.array_equal(a, b)
+        other = _engine(ysd, H, W, imgsz)                   # built while the first handle has tile = 0
+        assert other.set_option("tile", 1) == 1
+        other.close()
+        assert y.set_option("tile", 1) == 0
+        for a, b in zip(outs[0], outs[1]):
+            assert np.array_equal(a, b)
         # SPPF's three cascaded 5x5 max-pools: the LDS kernel (row / column passes) against the 13 x 13 ring sweep
-        y.set_option("pool_lds", 0)
+        assert y.set_option("pool_lds", 0) == 1
         y.forward(img)
         ring = y.read_tensor("9").cpu().numpy()
-        y.set_option("pool_lds", 1)
+        assert y.set_option("pool_lds", 1) == 0
         y.forward(img)
         assert np.array_equal(ring, y.read_tensor("9").cpu().numpy())
         y.close()
@@ -449,6 +414,9 @@ def test_yolo_error_paths(ysd):
         y.detect(np.zeros((480, 640, 3), np.uint8), max_det=301)
     with pytest.raises(RuntimeError, match="already loaded"):
         y.load_state_dict(ysd)
+    for retired in ("chain", "xcd", "wlds", "splitk_max_m"):      # removed conv variants and launch knobs
+        with pytest.raises(RuntimeError, match="unknown option " + retired):
+            y.set_option(retired, 0)
     y.close()
 
 
