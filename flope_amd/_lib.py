@@ -17,6 +17,14 @@ def STAGE_LAYER(li: int, bi: int) -> int:
     return 2 + (li - 1) * 2 + bi
 
 
+def STAGE_MID(li: int, bi: int) -> int:
+    return 12 + (li - 1) * 2 + bi
+
+
+def STAGE_DS(li: int) -> int:
+    return 20 + (li - 2)
+
+
 # every symbol include/flope_amd.h declares: name -> (restype, argtypes)
 _P, _I, _F, _D = C.c_void_p, C.c_int, C.c_float, C.c_double
 SIGNATURES = {

@@ -111,6 +111,9 @@ struct flope_engine {
   std::vector<Buf> bufs;             // 0 stem_out, 1 pool, then per block: mid, [ds], out
   std::vector<Conv> convs;
   int stage_buf[10];                 // FLOPE_STAGE_* (0..9) -> buffer index
+  int mid_buf[8];                    // FLOPE_STAGE_MID(li, bi) - FLOPE_STAGE_MID(1, 0) -> buffer index
+  int ds_buf[3] = {-1, -1, -1}, ds_conv[3] = {-1, -1, -1};   // FLOPE_STAGE_DS(li) - FLOPE_STAGE_DS(2) -> buffer / conv index
+  bool last_ds_folded[3] = {false, false, false};            // the last forward computed that shortcut inside conv2
   int final_buf = -1;
   float *feat = nullptr, *hidden = nullptr, *W1 = nullptr, *W1p = nullptr, *b1 = nullptr, *W2 = nullptr, *b2 = nullptr;
   float* r9_scratch = nullptr;
@@ -489,12 +492,14 @@ extern "C" int flope_create(int device_id, int height, int width, int max_batch,
         cd.in_buf = cur; cd.out_buf = b_ds; cd.hin = hh; cd.win = ww; cd.hout = ho; cd.wout = wo; cd.relu = 0;
         e->convs.push_back(cd);
         res = b_ds;
+        if (li >= 1) { e->ds_buf[li - 1] = b_ds; e->ds_conv[li - 1] = (int)e->convs.size() - 1; }
       }
       const int b_out = add_buf(co, ho, wo);
       Conv c2; c2.name = p + ".conv2"; c2.bn = p + ".bn2"; c2.cin = co; c2.cout = co; c2.k = 3; c2.stride = 1;
       c2.in_buf = b_mid; c2.out_buf = b_out; c2.res_buf = res; c2.hin = ho; c2.win = wo; c2.hout = ho; c2.wout = wo; c2.relu = 1;
       e->convs.push_back(c2);
       e->stage_buf[FLOPE_STAGE_LAYER(li + 1, bi)] = b_out;
+      e->mid_buf[li * 2 + bi] = b_mid;
       cur = b_out; ch = co; hh = ho; ww = wo;
     }
   e->final_buf = cur;
@@ -934,6 +939,7 @@ static int run_trunk(flope_engine* e, const void* x_dev, int in_format, int batc
   e->ev_n = 0;
   e->last_fused = e->opt_fuse_stem && e->dtype != FLOPE_DT_F32;
   e->last_batch = batch;
+  for (int i = 0; i < 3; ++i) e->last_ds_folded[i] = e->ds_conv[i] >= 0 && e->convs[e->ds_conv[i]].folded;
   int ns = e->opt_streams >= 2 ? e->opt_streams : 1;
   while (ns > 1 && batch / ns < 32) --ns;              // keep every slice large enough to fill the chip
   // profile = 1 times every launch on ONE stream -- but with the kernel variants (tile heights, class walk) the production
@@ -1032,10 +1038,18 @@ extern "C" int flope_read_stage(flope_handle e, int stage, int batch, float* dst
                               hipMemcpyDeviceToDevice, (hipStream_t)stream));
     return FLOPE_OK;
   }
-  if (stage < 0 || stage > 9) return fail(e, FLOPE_EINVAL, "flope_read_stage: unknown stage");
+  int bi = -1;
+  if (stage >= 0 && stage <= 9) bi = e->stage_buf[stage];
+  else if (stage >= FLOPE_STAGE_MID(1, 0) && stage <= FLOPE_STAGE_MID(4, 1)) bi = e->mid_buf[stage - FLOPE_STAGE_MID(1, 0)];
+  else if (stage >= FLOPE_STAGE_DS(2) && stage <= FLOPE_STAGE_DS(4)) {
+    if (e->last_ds_folded[stage - FLOPE_STAGE_DS(2)])
+      return fail(e, FLOPE_ESTATE, "flope_read_stage: the shortcut activation is not materialised when the 1x1 conv is folded into conv2 (set option dsfuse=0)");
+    bi = e->ds_buf[stage - FLOPE_STAGE_DS(2)];
+  }
+  if (bi < 0) return fail(e, FLOPE_EINVAL, "flope_read_stage: unknown stage");
   if (stage == FLOPE_STAGE_STEM && e->last_fused)
     return fail(e, FLOPE_ESTATE, "flope_read_stage: the stem activation is not materialised by the fused stem+maxpool kernel (set option fuse_stem=0)");
-  const Buf& b = e->bufs[e->stage_buf[stage]];
+  const Buf& b = e->bufs[bi];
   dims_out[0] = batch; dims_out[1] = b.C; dims_out[2] = b.h; dims_out[3] = b.w;
   K_TRY(e, "read_stage", flope_read_stage_launch(b.ptr, dst_dev, batch, b.C, b.h, b.w, e->dtype, stream));
   return FLOPE_OK;

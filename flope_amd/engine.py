@@ -17,7 +17,9 @@ _DTYPES = {"bf16": _lib.DT_BF16, "f16": _lib.DT_F16, "f32": _lib.DT_F32,
 
 STAGES = {"stem": _lib.STAGE_STEM, "pool": _lib.STAGE_POOL, "feat": _lib.STAGE_FEAT,
           "hidden": _lib.STAGE_HIDDEN,
-          **{f"layer{li}.{bi}": _lib.STAGE_LAYER(li, bi) for li in range(1, 5) for bi in range(2)}}
+          **{f"layer{li}.{bi}": _lib.STAGE_LAYER(li, bi) for li in range(1, 5) for bi in range(2)},
+          **{f"layer{li}.{bi}.mid": _lib.STAGE_MID(li, bi) for li in range(1, 5) for bi in range(2)},
+          **{f"layer{li}.0.ds": _lib.STAGE_DS(li) for li in range(2, 5)}}
 
 
 def _require_gpu():

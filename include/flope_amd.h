@@ -56,6 +56,10 @@ typedef struct flope_engine* flope_handle;
 #define FLOPE_STAGE_LAYER(li, bi)  (2 + ((li) - 1) * 2 + (bi))   /* li 1..4, bi 0..1 */
 #define FLOPE_STAGE_FEAT    10  /* global average pool     [B,512]  */
 #define FLOPE_STAGE_HIDDEN  11  /* fc.0 + ReLU             [B,2048] */
+/* inside a BasicBlock (element-wise conv tests: every conv's own input and output) */
+#define FLOPE_STAGE_MID(li, bi)    (12 + ((li) - 1) * 2 + (bi))  /* conv1+bn1+relu of the block, li 1..4, bi 0..1 */
+#define FLOPE_STAGE_DS(li)         (20 + ((li) - 2))             /* 1x1 stride-2 shortcut conv + bn of layer li.0, li 2..4;
+                                                                  * FLOPE_ESTATE when the last forward folded it into conv2 (option dsfuse) */
 
 /* ---- life cycle ----------------------------------------------------------
  * Replaces PoseResNet().to(device)   (sunflower/models/posenet.py:6-22,
@@ -148,8 +152,9 @@ int flope_depth_lift(const void* depth_dev, int depth_format, const uint8_t* mas
                      float* xyz_dev, void* stream);
 
 /* ---- introspection (parity tests / DESIGN.md numbers) ----------------------- */
-/* Copy one internal activation of the LAST forward to float32: conv stages as
- * NCHW [B,C,h,w]; FEAT / HIDDEN as [B,n].  dims_out[4] receives the shape. */
+/* Copy one internal activation of the LAST forward to float32: conv stages (STEM, POOL,
+ * LAYER, MID, DS) as NCHW [B,C,h,w]; FEAT / HIDDEN as [B,n].  dims_out[4] receives the shape.
+ * Every block owns its MID and DS buffers, so all taps of one forward can be read after it. */
 int flope_read_stage(flope_handle h, int stage, int batch, float* dst_dev,
                      int64_t* dims_out, void* stream);
 /* runtime knobs (A/B variants inside one build); returns previous value or <0 */

@@ -115,6 +115,7 @@ def forward_stages_emulated(sd: dict, x: torch.Tensor, act_dtype=torch.bfloat16)
             if (p + ".downsample.0.weight") in sd:
                 w, b = fold_bn(sd[p + ".downsample.0.weight"], sd, p + ".downsample.1")
                 idt = rd(F.conv2d(y, rd(w), b, stride=s, padding=0))
+                out[f"layer{li}.{bi}.ds"] = idt
             w, b = fold_bn(sd[p + ".conv2.weight"], sd, p + ".bn2")
             y = rd(F.relu(F.conv2d(z, rd(w), b, stride=1, padding=1) + idt))
             out[f"layer{li}.{bi}"] = y
