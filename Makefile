@@ -21,14 +21,14 @@ $(LIB): $(OBJS)
 	@mkdir -p $(dir $@)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $(OBJS)
 
-$(HARNESS): tests/host_harness/harness.cpp $(CSRC)/pose_math.h $(CSRC)/host_pack.h $(CSRC)/w4_sched.h
+$(HARNESS): tests/host_harness/harness.cpp $(CSRC)/pose_math.h $(CSRC)/host_pack.h $(CSRC)/w4_sched.h $(CSRC)/plan.h
 	g++ -O2 -fPIC -shared -std=c++17 -I$(CSRC) -o $@ $<
 
 # the same host code under AddressSanitizer + UBSan (sanitizers run on the CPU build only):
 #   make asan-test      (builds the sanitized harness and runs tests/test_host.py against it; leak detection is off because the
 #                        interpreter's own libcrypto allocations are reported as leaks at exit)
 HARNESS_ASAN := tests/host_harness/libflope_host_harness_asan.so
-$(HARNESS_ASAN): tests/host_harness/harness.cpp $(CSRC)/pose_math.h $(CSRC)/host_pack.h $(CSRC)/w4_sched.h
+$(HARNESS_ASAN): tests/host_harness/harness.cpp $(CSRC)/pose_math.h $(CSRC)/host_pack.h $(CSRC)/w4_sched.h $(CSRC)/plan.h
 	g++ -O1 -g -fno-omit-frame-pointer -fsanitize=address,undefined -fno-sanitize-recover=undefined -fPIC -shared -std=c++17 -I$(CSRC) -o $@ $<
 asan: $(HARNESS_ASAN)
 asan-test: $(HARNESS_ASAN)

@@ -20,6 +20,7 @@
 //     registers, added in the epilogue) stay in flight across the first barrier;
 // Every tile has the same geometry relative to its patch origin: all per-lane tables are built once per workgroup.
 #include "common.h"
+#include "plan.h"
 
 #define GLDS16(gptr, lptr)                                                                         \
   __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(gptr),          \
@@ -344,17 +345,14 @@ extern "C" int flope_conv_r4_init() {
 }
 
 // can this conv run on conv_r4?  64 -> 64 channels, two output rows = 7 MFMA pixel tiles (Wo = 56), 8-row bands
-extern "C" int flope_conv_r4_ok(const ConvP* p) {
-  return p->stride == 1 && p->ntaps == 9 && p->Cin == 64 && p->Cout == 64 && p->Wo == 56 && p->Ho % 8 == 0 &&
-         10 * (p->Wip + 2) * 4 <= 5 * 512 && p->ksplit <= 1 && !p->ds_in;
-}
+extern "C" int flope_conv_r4_ok(const ConvP* p) { return flope_plan::r4_ok(flope_plan::dims_of(*p)); }
 
 // p->tiles_per_image = Ho / 8, p->total_tiles = B * tiles_per_image, p->w = the conv_stag weight image of a 64 -> 64 layer
 // ([18 steps][64 rows][32 k]), p->mg_pitch / sh_pitch = fastdiv magic of Wip + 2; grid_blocks <= total_tiles (persistent)
 extern "C" int flope_conv_r4_launch(const ConvP* p, int dtype, int grid_blocks, void* stream) {
   if (!flope_conv_r4_ok(p) || !p->mg_pitch || grid_blocks < 1 || grid_blocks > p->total_tiles || p->tiles_per_image != p->Ho / 8)
     return (int)hipErrorInvalidValue;
-  const size_t lds = (size_t)2 * 5 * 8192 + 18 * 4096 + 4 * 2048;      // patch buffers, resident weights, line images
+  const size_t lds = flope_plan::kR4Lds;
   const dim3 grid(grid_blocks), block(256);
   hipStream_t st = (hipStream_t)stream;
   if (dtype == 0) { if (p->res) hipLaunchKernelGGL((conv_r4_kernel<bf16_t, 7, 5, true>), grid, block, lds, st, *p); else hipLaunchKernelGGL((conv_r4_kernel<bf16_t, 7, 5, false>), grid, block, lds, st, *p); }

@@ -17,6 +17,7 @@
 // One barrier per sub-tile (two per band): swap data visible; the second one also publishes the next patch and releases this one.
 // K order: input-channel half, 32-channel half-chunk, tap, channel: results equal conv_w4's within accumulation-order rounding.
 #include "common.h"
+#include "plan.h"
 #include <type_traits>
 
 namespace {
@@ -258,13 +259,9 @@ __global__ __launch_bounds__(512, 1) void conv_s1r_kernel(const ConvP p, const u
 
 // layer shapes this kernel takes: 3x3 stride 1, 128 -> 128 channels, 28-wide map with a multiple of 4 rows; a folded 1x1 stride-2
 // shortcut over 64 input channels (ds_w: pack_s1r_ds image) instead of a residual
-extern "C" int flope_conv_s1r_ok(const ConvP* p) {
-  if (p->ds_in && !(p->ds_Cin == 64 && p->ds_Hip == 2 * p->Ho + 2 && p->ds_Wip == 2 * p->Wo + 2 && p->ds_w && !p->res)) return 0;
-  return p->stride == 1 && p->ntaps == 9 && p->Cin == 128 && p->Cout == 128 && p->Wo == 28 && (p->Ho & 3) == 0 &&
-         p->ksplit <= 1 && p->Wip == p->Wo + 2 && p->Hip == p->Ho + 2;
-}
+extern "C" int flope_conv_s1r_ok(const ConvP* p) { return flope_plan::s1r_ok(flope_plan::dims_of(*p)); }
 
-extern "C" int flope_conv_s1r_lds() { return 2 * 4 * 6 * 32 * 64 + 4 * 14 * 1024; }
+extern "C" int flope_conv_s1r_lds() { return (int)flope_plan::kS1rLds; }
 
 extern "C" int flope_conv_s1r_init() {
   hipError_t e = hipSuccess;

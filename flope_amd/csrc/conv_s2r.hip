@@ -23,6 +23,7 @@
 // K order: half-chunk, tap, channel (conv_mfma's is tap, channel): results equal conv_mfma's within accumulation-order rounding,
 // not bit for bit (tests/test_gpu_parity.py::test_stride2_patch_kernel_against_the_gathered_tile_kernel).
 #include "common.h"
+#include "plan.h"
 #include <type_traits>
 
 namespace {
@@ -213,12 +214,9 @@ __global__ __launch_bounds__(512, 1) void conv_s2r_kernel(const ConvP p, const u
 }  // namespace
 
 // layer shapes this kernel takes: 3x3 stride 2, 64 -> 128 channels, output map 28 wide and a multiple of 4 rows, no residual
-extern "C" int flope_conv_s2r_ok(const ConvP* p) {
-  return p->stride == 2 && p->ntaps == 9 && p->Cin == 64 && p->Cout == 128 && p->Wo == 28 && (p->Ho & 3) == 0 && !p->res && !p->ds_in &&
-         p->ksplit <= 1 && p->Wip == 2 * p->Wo + 2 && p->Hip == 2 * p->Ho + 2;
-}
+extern "C" int flope_conv_s2r_ok(const ConvP* p) { return flope_plan::s2r_ok(flope_plan::dims_of(*p)); }
 
-extern "C" int flope_conv_s2r_lds() { return 2 * 18 * 32 * 128; }
+extern "C" int flope_conv_s2r_lds() { return (int)flope_plan::kS2rLds; }
 
 extern "C" int flope_conv_s2r_init() {
   hipError_t e = hipFuncSetAttribute((const void*)conv_s2r_kernel<bf16_t, 7>, hipFuncAttributeMaxDynamicSharedMemorySize, flope_conv_s2r_lds());

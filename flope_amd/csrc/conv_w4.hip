@@ -35,6 +35,7 @@
 //     image (XOR-swizzled, conflict-free both ways) and leave as 8 whole 128-byte lines per instruction: 2.9 k cycles.  Only the
 //     order of the stores changes -- same bytes, same addresses.
 #include "common.h"
+#include "plan.h"
 #include "w4_sched.h"
 #ifndef FLOPE_W4_SPREAD
 #define FLOPE_W4_SPREAD 2
@@ -648,10 +649,6 @@ __global__ __launch_bounds__(256, 1) void conv_w4_kernel(const ConvP p) {
 #undef W4_WAIT_PIN
 }
 
-static constexpr size_t w4_lds_bytes(int pt, bool own_ds_slot) {
-  return (size_t)2 * pt * 8192 + (size_t)(w4_ring(pt, own_ds_slot) + (own_ds_slot ? 1 : 0)) * 16384 + 12800;
-}
-
 // instantiated variants: one tile per workgroup at MT = 8, 7 (PT = 4, 5, 6) and MT = 6, 5 (PT = 4; r05: 4 dropped, the planner's floor is 5); the class walk at MT = 7
 // (PT = 4, 5; with a folded shortcut the 6-round patch leaves no room for the shortcut's own weight slot)
 #define W4_FOR_VARIANTS(X, T)                                                                                  \
@@ -676,12 +673,8 @@ extern "C" int flope_conv_w4_init() {
   return (int)e;
 }
 
-// lds bytes of a variant: 2 patch buffers, the weight ring (+ 1 double tile for a persistent workgroup's folded shortcut), 12.5 KB in
-// which the lanes trade their shares of the address table and the epilogue builds its line image; 0 = not instantiated
-extern "C" size_t flope_conv_w4_lds(int pt, int mt, int dsf, int pers) {
-  if (pt < 4 || pt > 6 || mt < 5 || mt > 8 || (mt < 7 && pt != 4) || (pers && (mt != 7 || pt > 5))) return 0;
-  return w4_lds_bytes(pt, dsf && pers);
-}
+// lds bytes of a variant (w4_sched.h: w4_lds_bytes); 0 = not instantiated
+extern "C" size_t flope_conv_w4_lds(int pt, int mt, int dsf, int pers) { return flope_plan::w4_lds(pt, mt, dsf, pers); }
 
 // 3x3 stride-1 pad-1, Cin % 64 == 0, Cout % 128 == 0, the skewed patch image (p->skew, p->mg_pitch / sh_pitch):
 // mt = 8 .. 4 pixel tiles per wave = 256 .. 128-pixel workgroup tiles (below 7: pt = 4 only); p->patch_rows_max = PT (4, 5 or 6: the

@@ -27,6 +27,8 @@
 // "how many operations were issued behind the youngest one that must have landed".
 #pragma once
 
+#include <stddef.h>
+
 #ifndef W4_HD
 #if defined(__HIPCC__)
 #define W4_HD __host__ __device__
@@ -43,6 +45,12 @@ W4_HD constexpr int w4_ring(int pt, bool own_ds_slot) {
   for (int n = 5; n >= 3; --n)
     if (2 * pt * 8192 + (n + (own_ds_slot ? 1 : 0)) * 16384 + 12800 <= 160 * 1024) return n;
   return 0;
+}
+
+// LDS bytes of a variant: 2 patch buffers, the weight ring (+ 1 double tile for a persistent workgroup's folded shortcut), 12.5 KB in
+// which the lanes trade their shares of the address table and the epilogue builds its line image
+W4_HD constexpr size_t w4_lds_bytes(int pt, bool own_ds_slot) {
+  return (size_t)2 * pt * 8192 + (size_t)(w4_ring(pt, own_ds_slot) + (own_ds_slot ? 1 : 0)) * 16384 + 12800;
 }
 
 // patch pieces a wave issues in the second sub-step of double step D, and the burst index of the first of them.

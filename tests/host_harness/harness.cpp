@@ -2,10 +2,13 @@
 // with the head kernels, 16-bit conversions, weight packers) to pytest via ctypes so
 // they can be checked against the oracle without a GPU.  Not part of the product.
 #include "host_pack.h"
+#include "plan.h"
 #include "pose_math.h"
 #include "w4_sched.h"
 
 #include <cstdio>
+#include <cstdlib>
+#include <string>
 #include <vector>
 
 extern "C" {
@@ -61,6 +64,78 @@ void hh_pack_s1r(const float* w, int dtype, uint16_t* dst) {
   std::vector<float> wf(w, w + (size_t)128 * 128 * 9);
   std::vector<uint16_t> p = flope_host::pack_s1r(wf, 128, dtype);
   memcpy(dst, p.data(), p.size() * 2);
+}
+
+// ---- the launch planner (flope_amd/csrc/plan.h) ----
+// "name=value,name=value" -> set_option calls in that order; false for an unknown name.  stored (optional): the value each call left
+static bool apply_options(flope_plan::PlanOptions& o, const char* opts, std::vector<int>* stored) {
+  const std::string s = opts ? opts : "";
+  for (size_t a = 0; a < s.size();) {
+    size_t b = s.find(',', a);
+    if (b == std::string::npos) b = s.size();
+    const std::string kv = s.substr(a, b - a);
+    const size_t eq = kv.find('=');
+    a = b + 1;
+    if (kv.empty()) continue;
+    if (eq == std::string::npos) return false;
+    const std::string name = kv.substr(0, eq);
+    const flope_plan::OptionDef* d = flope_plan::find_option(name.c_str());
+    if (!d) return false;
+    flope_plan::set_option(o, name.c_str(), atoi(kv.c_str() + eq + 1), nullptr);
+    if (stored) stored->push_back(o.*(d->member));
+  }
+  return true;
+}
+
+// what an engine of this geometry with these options plans, and what a forward of `batch` crops launches in its last slice:
+// the text of flope_describe_plan, "slices|n|plan_slices|start:count ...", "launches=N", then per launch
+//   layer|label|detail|grid|lds_bytes|mtiles|ntiles|ksplit|mt|cw_imgs|res_lds|total_tiles     (conv launches; else layer|label)
+// Returns the text's length, FLOPE_EINVAL for an unknown option or a buffer that is too small.
+int flope_host_plan_dump(int H, int W, int max_batch, int dtype, int num_cus, const char* opts, int batch, char* buf, int cap) {
+  using namespace flope_plan;
+  PlanOptions o;
+  if (!apply_options(o, opts, nullptr)) return FLOPE_EINVAL;
+  Plan pl = make_plan(H, W, max_batch, dtype);
+  replan(pl, o);
+  std::string out = describe(pl, o);
+  const Slices sl = slices(o, batch, o.profile);
+  out += "slices|" + std::to_string(sl.n) + "|" + std::to_string(sl.plan_slices) + "|";
+  for (int s = 0; s < sl.n; ++s) out += (s ? " " : "") + std::to_string(sl.start[s]) + ":" + std::to_string(sl.count[s]);
+  const std::vector<Launch> L = decide_all(o, pl, slice_ctx(sl, sl.n - 1, batch, num_cus));
+  const int n = forward_launches(pl, o);
+  out += "\nlaunches=" + std::to_string(n) + "\n";
+  for (int i = 0; i < n; ++i) {
+    int conv; double flops;
+    const std::string name = launch_name(pl, o, L, 2048, i, &conv, &flops);
+    if (conv < 0) { out += name + "\n"; continue; }
+    const Launch& l = L[conv];
+    const std::string d = detail(l), layer = name.substr(0, name.find('|') - d.size());
+    char line[320];
+    snprintf(line, sizeof line, "%s|%s|%s|%d|%zu|%d|%d|%d|%d|%d|%d|%d\n", layer.c_str(), label(l).c_str(), d.c_str(), l.grid, l.lds_bytes, l.mtiles,
+             l.ntiles, l.ksplit, l.mt, l.cw_imgs, l.res_lds, l.total_tiles);
+    out += line;
+  }
+  if ((int)out.size() >= cap) return FLOPE_EINVAL;
+  memcpy(buf, out.c_str(), out.size() + 1);
+  return (int)out.size();
+}
+
+// applies the set_option calls of `calls` ("name=value,...") to default options; stored[i] = the value call i left in its option.
+// Returns the number of calls, FLOPE_EINVAL for an unknown name or cap too small.
+int flope_host_set_options(const char* calls, int* stored, int cap) {
+  flope_plan::PlanOptions o;
+  std::vector<int> v;
+  if (!apply_options(o, calls, &v) || (int)v.size() > cap) return FLOPE_EINVAL;
+  for (size_t i = 0; i < v.size(); ++i) stored[i] = v[i];
+  return (int)v.size();
+}
+
+// the value a fresh engine holds for an option; FLOPE_EINVAL for an unknown name
+int flope_host_option_default(const char* name, int* value) {
+  const flope_plan::OptionDef* d = flope_plan::find_option(name);
+  if (!d) return FLOPE_EINVAL;
+  *value = flope_plan::PlanOptions().*(d->member);
+  return 0;
 }
 
 }  // extern "C"

@@ -231,6 +231,37 @@ def test_register_weight_layer2_kernel_against_conv_w4(state_dict, B, dtype, str
         e.close()
 
 
+_PLAN_CASES = [  # (H, W, B, dtype, options) of tests/golden/plan_matrix.json: the benchmarked plan (also bf16), split-K, class walk, 512 x 512, odd shapes, strict fp32
+    (224, 224, 256, "f16", {}), (224, 224, 256, "bf16", {}), (224, 224, 4, "f16", dict(streams=1)),
+    (224, 224, 64, "f16", dict(streams=1, ksplit=0, s1r=0, w4cw=4, w4cwf=2)), (224, 224, 256, "f16", dict(w4cw=4, w4cwf=3)),
+    (512, 512, 2, "f16", {}), (65, 71, 2, "f16", {}), (200, 136, 7, "bf16", dict(dsfuse=0)), (224, 224, 4, "f32", {}),
+    (224, 224, 5, "f16", dict(patch=0, bm256=1, nbuf=2, fuse_stem=1, stag=1, dsfuse=0, gstag=0, stem_persist=0, skew=0, prio=1)),
+]
+
+
+@pytest.mark.parametrize("H,W,B,dtype,opts", _PLAN_CASES, ids=lambda v: str(v).replace(" ", "") if isinstance(v, dict) else str(v))
+def test_live_engine_launches_what_the_planner_and_the_record_say(state_dict, H, W, B, dtype, opts):
+    """Ties the CPU planner (csrc/plan.h, held to tests/golden/plan_matrix.json by tests/test_host.py) to what the library launches:
+    plan text, launch count and the (layer + detail, kernel) of every launch of a live engine equal the record taken from the commit
+    before the planner moved, and flope_launch_info names before the first forward exactly what it names after it."""
+    import os
+    from tools.dump_plan import load
+    doc = load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "plan_matrix.json"))
+    want = [c for c in doc["cases"] if c["kind"] == "forward" and (c["H"], c["W"], c["batch"], c["dtype"]) == (H, W, B, dtype)
+            and c["opts"] == [[k, v] for k, v in sorted(opts.items())]]
+    assert len(want) == 1, (H, W, B, dtype, opts)
+    assert torch.cuda.get_device_properties(0).multi_processor_count == doc["num_cus"]
+    e = _engine(state_dict, H, W, B, dtype, **dict(sorted(opts.items())))
+    assert e.describe_plan() == want[0]["plan"] and e.launches() == want[0]["launches"]
+    before = [[layer, k] for layer, k, _ in e.launch_info(B)]
+    torch.manual_seed(3)
+    _run(e, torch.rand(B, 3, H, W))
+    after = [[layer, k] for layer, k, _ in e.launch_info(B)]
+    assert after == want[0]["info"], (after, want[0]["info"])
+    assert before == after, (before, after)
+    e.close()
+
+
 @pytest.mark.parametrize("dtype,rtol,deg", [("f16", 1e-3, 0.1), ("bf16", 1e-2, 1.0)])
 def test_rotations_vs_fp32_oracle_cfg1(state_dict, golden_cfg1, dtype, rtol, deg):
     """BASELINE cfg1 inputs (16 seeded 224x224 crops) against the committed goldens."""

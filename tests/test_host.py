@@ -436,3 +436,97 @@ def test_conv_w4_queue_model_is_not_stricter_than_the_closed_form(harness):
         subprocess.check_call(["g++", "-std=c++17", "-I", os.path.join(ROOT, "flope_amd", "csrc"), "-o", exe, f])
         r = subprocess.run([exe], capture_output=True, text=True)
         assert r.returncode == 0, r.stdout
+
+
+# ---- the launch planner (flope_amd/csrc/plan.h) against the parent commit's record --------------------------------------------
+_DT = {"bf16": 0, "f16": 1, "f32": 2}
+
+
+def _plan_matrix():
+    from tools.dump_plan import load
+    return load(os.path.join(ROOT, "tests", "golden", "plan_matrix.json"))
+
+
+def _plan_dump(harness, case, num_cus):
+    """-> (plan text, slices [(start, count)], launches [dict]) of the CPU planner for one case of the matrix."""
+    buf = C.create_string_buffer(1 << 16)
+    opts = ",".join(f"{k}={v}" for k, v in case["opts"]).encode()
+    n = harness.flope_host_plan_dump(case["H"], case["W"], case["batch"], _DT[case["dtype"]], num_cus, opts, case["batch"], buf, len(buf))
+    assert n > 0, case
+    text = buf.value.decode()
+    plan, rest = text.split("slices|")
+    sl, rest = rest.split("\nlaunches=")
+    lines = rest.split("\n")
+    assert int(lines[0]) == len(lines[1:-1]) and lines[-1] == ""
+    cols = ("layer", "label", "detail", "grid", "lds_bytes", "mtiles", "ntiles", "ksplit", "mt", "cw_imgs", "res_lds", "total_tiles")
+    launches = []
+    for ln in lines[1:-1]:
+        f = ln.split("|")
+        launches.append({c: (v if c in cols[:3] else int(v)) for c, v in zip(cols, f)})
+    return plan, [tuple(int(v) for v in s.split(":")) for s in sl.split("|")[2].split()], launches
+
+
+def test_planner_reproduces_the_recorded_plans_labels_and_details(harness):
+    """tests/golden/plan_matrix.json was recorded through the C-ABI of the commit BEFORE the planner moved into plan.h
+    (tools/dump_plan.py on an MI355X; its `parent` field names the commit): for every case the CPU planner gives the same plan text
+    and launch count, and for every case with a recorded forward the same layer, kernel label and launch detail per launch of the
+    last slice, string for string."""
+    doc = _plan_matrix()
+    assert len(doc["cases"]) >= 100 and sum(c["kind"] == "forward" for c in doc["cases"]) >= 90
+    for case in doc["cases"]:
+        plan, _, launches = _plan_dump(harness, case, doc["num_cus"])
+        assert plan == case["plan"], case
+        assert len(launches) == case["launches"], case
+        if case["kind"] == "forward":
+            got = [[l["layer"] + l.get("detail", ""), l["label"]] for l in launches]
+            assert got == case["info"], (case["H"], case["W"], case["batch"], case["dtype"], case["opts"])
+
+
+def test_planner_invariants_of_every_launch(harness):
+    """What must hold for any decision, recorded or not (the plan-only cases of the matrix -- persist, rows_grid, gstag = 2,
+    s2r_grid, three and four slices -- are held by this and by the plan text): the grid is a positive multiple of the channel
+    tiles and walks no more than the launch's tiles, LDS fits the CU, split-K only on conv_stag's flat tiles with the residual
+    left to the finalize launch, conv_w4 only at an instantiated tile height, and the slices tile the batch."""
+    doc = _plan_matrix()
+    seen = set()
+    for case in doc["cases"]:
+        _, sl, launches = _plan_dump(harness, case, doc["num_cus"])
+        assert sl[0][0] == 0 and sum(c for _, c in sl) == case["batch"] and all(c >= 1 for _, c in sl), (case, sl)
+        assert all(a[0] + a[1] == b[0] for a, b in zip(sl, sl[1:])), (case, sl)
+        for l in launches:
+            seen.add(l["label"].split(",")[0])
+            if "grid" not in l or l["label"] == "naive_conv_kernel":
+                continue
+            assert l["grid"] >= l["ntiles"] >= 1 and l["grid"] % l["ntiles"] == 0, (case, l)
+            assert l["grid"] <= l["total_tiles"] * max(1, l["ksplit"]), (case, l)
+            assert l["lds_bytes"] <= 160 * 1024, (case, l)
+            if l["ksplit"] > 1:
+                assert l["label"] == "conv_stag_kernel<256x128>" and l["res_lds"] == 0 and l["grid"] == l["total_tiles"] * l["ksplit"], (case, l)
+                assert l["detail"] == f"[split-K x{l['ksplit']}]"
+            if l["label"].startswith("conv_w4"):
+                assert 5 <= l["mt"] <= 8 and l["lds_bytes"] > 0, (case, l)
+            else:
+                assert l["mt"] == 0 and l["cw_imgs"] == 0, (case, l)
+    # every family the planner can name is reached by the matrix (tests/test_gpu_conv_elementwise.py: FAMILIES)
+    assert seen >= {"conv_r4_kernel<8rows x56>", "conv_stag_kernel<8rows x64>", "conv_stag_kernel<512x64>", "conv_stag_kernel<256x128>",
+                    "conv_gstag_kernel<256x128", "conv_s1r_kernel<4rows x28>", "conv_s2r_kernel<4rows x28>", "conv_w4_kernel<256x128>",
+                    "conv_mfma_kernel<128x128", "naive_conv_kernel"}, seen
+
+
+def test_option_table_stores_what_the_recorded_engine_stored(harness):
+    """Every option, every probe value: the value set_option leaves is the one the parent commit's flope_set_option left (read back
+    there as the next call's return value); the defaults are the parent's; an unknown name is refused."""
+    doc = _plan_matrix()
+    vals = doc["probe_values"]
+    assert len(doc["probe"]) == 33
+    for name, rec in doc["probe"].items():
+        stored = (C.c_int * (2 * len(vals)))()
+        calls = ",".join(f"{name}={v}" for v in vals).encode()
+        assert harness.flope_host_set_options(calls, stored, len(stored)) == len(vals), name
+        assert list(stored[:len(vals)]) == rec["stored"], (name, list(stored[:len(vals)]), rec["stored"])
+    # defaults: what a fresh PlanOptions holds = what the first set_option call of the parent returned
+    for name, rec in doc["probe"].items():
+        lib_default = C.c_int()
+        assert harness.flope_host_option_default(name.encode(), C.byref(lib_default)) == 0 and lib_default.value == rec["default"], name
+    assert harness.flope_host_set_options(b"no_such_option=1", (C.c_int * 2)(), 2) == doc["unknown_option"] == -1
+    assert harness.flope_host_plan_dump(224, 224, 4, 1, 256, b"no_such_option=1", 4, C.create_string_buffer(64), 64) == -1
