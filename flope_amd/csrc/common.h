@@ -196,6 +196,17 @@ struct NaiveConvP {    // strict fp32 direct convolution on padded NHWC float te
   int relu;
 };
 
+struct F32mConvP {     // float32 implicit GEMM on the exact-fp32 MFMA (conv_f32m.hip); tensors as NaiveConvP
+  const float* in; float* out; const float* res; const float* w; const float* bias;   // w: A-fragment image (host_pack.h pack_f32m)
+  int B, Hip, Wip, Cin_stored, Cin, Ho, Wo, Hop, Wop, Cout;
+  int KH, KW, stride, in_off;
+  int relu;
+  int M;               // B*Ho*Wo
+  int nsteps;          // 16-deep K steps: KH*KW*Cin/16 (Cin % 16 == 0), stem: ceil(KH*KW / 4) taps of 4 stored channels
+  int csteps;          // K steps per tap (Cin / 16; unused by the stem)
+  unsigned mg_hw, sh_hw, mg_w, sh_w;   // n / (Ho*Wo) and n / Wo as multiply-shift
+};
+
 // ---------------------------------------------------------------------------
 // Shared MFMA epilogue: one lane = one output pixel x (4*NT) consecutive channels.
 // acc + bias (+ residual) (ReLU) -> 16-bit, written as 16-byte NHWC stores into the

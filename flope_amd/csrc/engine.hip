@@ -32,6 +32,8 @@ extern "C" int flope_fc2_procrustes_k4_launch(const float* hidden, const float* 
 extern "C" int flope_prep_input_launch(const void* x, int in_format, int B, int H, int W, void* out, int Hip, int Wip, int dtype, void* stream);
 extern "C" int flope_read_stage_launch(const void* in, float* out, int B, int C, int h, int w, int dtype, void* stream);
 extern "C" int flope_naive_conv_launch(const NaiveConvP* p, void* stream);
+extern "C" int flope_conv_f32m_init();
+extern "C" int flope_conv_f32m_launch(const F32mConvP* p, int mp, int stem, int grid, size_t lds, void* stream);
 extern "C" int flope_conv_stag_init();
 extern "C" int flope_conv_gstag_init();
 extern "C" int flope_conv_w4_init();
@@ -71,6 +73,7 @@ enum Image {
   kWS2r,        // conv_s2r fragment image (16-bit), the 3x3 stride-2 64 -> 128 conv only
   kWS1r,        // conv_s1r fragment image (16-bit), the 3x3 stride-1 128 -> 128 convs
   kWNaive,      // float [ky][kx][ci][cout], strict mode
+  kWF32m,       // float A-fragment image of conv_f32m (float32 engines: uploaded beside kWNaive, option f32mfma picks per forward)
   kBias,        // float [cout]
   kWDsStag,     // downsample conv only: its weights as a conv_stag image
   kWDsS1r,      // the 64 -> 128 downsample conv only: its weights as conv_s1r's extra fragment pair
@@ -97,7 +100,7 @@ struct flope_engine {
   Plan plan;                         // stem geometry, conv shapes and their static plan under `opt`
   void* stem_in = nullptr; size_t stem_in_bytes = 0;
   int* stem_q = nullptr;               // tile queues of the register-weight stem: 1024 ints per batch slice (heads 256 bytes apart; zero between launches)
-  void* stem_w = nullptr; void* stem_w2 = nullptr; float* stem_w_naive = nullptr; float* stem_bias = nullptr;   // stem_w2: per-wave fragment order (stem_pool_r_kernel)
+  void* stem_w = nullptr; void* stem_w2 = nullptr; float* stem_w_naive = nullptr; float* stem_w_f32m = nullptr; float* stem_bias = nullptr;   // stem_w2: per-wave fragment order (stem_pool_r_kernel)
   std::vector<Buf> bufs;             // 0 stem_out, 1 pool, then per block: mid, [ds], out
   std::vector<ConvDev> convs;
   int stage_buf[10];                 // FLOPE_STAGE_* (0..9) -> buffer index
@@ -335,6 +338,10 @@ extern "C" int flope_create(int device_id, int height, int width, int max_batch,
     if (s == 0) s = flope_conv_s1r_init();
     if (s != 0) { int rc = fail(nullptr, FLOPE_EHIP, std::string("kernel attribute setup: ") + hipGetErrorString((hipError_t)s)); flope_destroy(e); return rc; }
   }
+  if (dtype == FLOPE_DT_F32) {
+    const int s = flope_conv_f32m_init();
+    if (s != 0) { int rc = fail(nullptr, FLOPE_EHIP, std::string("kernel attribute setup: ") + hipGetErrorString((hipError_t)s)); flope_destroy(e); return rc; }
+  }
   const size_t B = (size_t)max_batch;
   e->stem_in_bytes = B * pl.sHip * pl.sWip * 4 * e->esz;
   CREATE_TRY(hipMalloc(&e->stem_in, e->stem_in_bytes));
@@ -400,7 +407,7 @@ extern "C" int flope_destroy(flope_handle e) {
   for (Buf& b : e->bufs) if (b.ptr) hipFree(b.ptr);
   for (ConvDev& c : e->convs)
     for (void* p : c.img) if (p) hipFree(p);
-  void* singles[] = {e->stem_in, e->stem_q, e->stem_w, e->stem_w2, e->stem_w_naive, e->stem_bias, e->feat, e->hidden, e->W1, e->W1p, e->b1, e->W2, e->b2, e->r9_scratch, e->split_ws};
+  void* singles[] = {e->stem_in, e->stem_q, e->stem_w, e->stem_w2, e->stem_w_naive, e->stem_w_f32m, e->stem_bias, e->feat, e->hidden, e->W1, e->W1p, e->b1, e->W2, e->b2, e->r9_scratch, e->split_ws};
   for (void* p : singles) if (p) hipFree(p);
   for (hipEvent_t ev : e->ev) hipEventDestroy(ev);
   for (int i = 0; i < 4; ++i) { if (e->side[i]) hipStreamDestroy(e->side[i]); if (e->ev_join[i]) hipEventDestroy(e->ev_join[i]); }
@@ -421,6 +428,8 @@ extern "C" int flope_debug_read_ws(flope_handle e, void* dst_host, size_t offset
 }
 
 // the options, their clamps and which of them the static plan depends on: plan.h (option_table)
+//   f32mfma (float32 engines; stored and ignored by the 16-bit ones): 1 = the stem and the 19 trunk convs run on conv_f32m_kernel
+//   (exact-fp32 MFMA), 0 (default) = on naive_conv_kernel.  Both weight images are resident, so it may be flipped between forwards.
 extern "C" int flope_set_option(flope_handle e, const char* name, int value) {
   if (!e || !name) return fail(e, FLOPE_EINVAL, "flope_set_option: NULL argument");
   const OptionDef* d = find_option(name);
@@ -452,7 +461,10 @@ extern "C" int flope_load_weights(flope_handle e, int n, const char* const* name
   // stem
   if ((rc = fold(e, ts, "base.conv1", "base.bn1", 64, 3, 7, &wf, &bf)) != 0) return rc;
   if ((rc = upload(e, bf, (void**)&e->stem_bias)) != 0) return rc;
-  if (e->dtype == FLOPE_DT_F32) { if ((rc = upload(e, naive_layout(wf, 64, 3, 7), (void**)&e->stem_w_naive)) != 0) return rc; }
+  if (e->dtype == FLOPE_DT_F32) {
+    if ((rc = upload(e, naive_layout(wf, 64, 3, 7), (void**)&e->stem_w_naive)) != 0) return rc;
+    if ((rc = upload(e, pack_f32m_stem(wf), (void**)&e->stem_w_f32m)) != 0) return rc;
+  }
   else {
     if ((rc = upload(e, pack_stem(wf, e->dtype), &e->stem_w)) != 0) return rc;
     if ((rc = upload(e, pack_stem_frag(wf, e->dtype), &e->stem_w2)) != 0) return rc;
@@ -462,7 +474,10 @@ extern "C" int flope_load_weights(flope_handle e, int n, const char* const* name
     ConvDev& c = e->convs[i];
     if ((rc = fold(e, ts, conv_name(s), conv_name(s, true), s.cout, s.cin, s.k, &wf, &bf)) != 0) return rc;
     if ((rc = upload(e, bf, &c.img[kBias])) != 0) return rc;
-    if (e->dtype == FLOPE_DT_F32) { if ((rc = upload(e, naive_layout(wf, s.cout, s.cin, s.k), &c.img[kWNaive])) != 0) return rc; }
+    if (e->dtype == FLOPE_DT_F32) {
+      if ((rc = upload(e, naive_layout(wf, s.cout, s.cin, s.k), &c.img[kWNaive])) != 0) return rc;
+      if ((rc = upload(e, pack_f32m(wf, s.cout, s.cin, s.k), &c.img[kWF32m])) != 0) return rc;
+    }
     else {
       if ((rc = upload(e, pack_conv(wf, s.cout, s.cin, s.k, e->dtype), &c.img[kWPacked])) != 0) return rc;
       if (has_stag_image(s) && (rc = upload(e, pack_conv32(wf, s.cout, s.cin, e->dtype), &c.img[kWStag])) != 0) return rc;
@@ -538,7 +553,18 @@ static int run_slice(flope_engine* e, const void* x_dev, int in_format, int star
   } else {
     SMARK();
     K_TRY(e, "prep_input", flope_prep_input_launch(xs, in_format, batch, e->H, e->W, stem_in, pl.sHip, pl.sWip, dt, stream));
-    if (dt == FLOPE_DT_F32) {
+    if (dt == FLOPE_DT_F32 && o.f32mfma) {
+      const Launch L = f32m_stem_launch(pl, x);
+      F32mConvP p; memset(&p, 0, sizeof(p));
+      p.in = (const float*)stem_in; p.out = (float*)stem_out; p.w = e->stem_w_f32m; p.bias = e->stem_bias;
+      p.B = batch; p.Hip = pl.sHip; p.Wip = pl.sWip; p.Cin_stored = 4; p.Cin = 3; p.Ho = pl.Hs; p.Wo = pl.Ws;
+      p.Hop = pl.Hs + 2; p.Wop = pl.Ws + 2; p.Cout = 64; p.KH = 7; p.KW = 7; p.stride = 2; p.in_off = 0; p.relu = 1;
+      p.M = batch * pl.Hs * pl.Ws; p.nsteps = kF32mStemSteps;
+      fastdiv_magic((unsigned)(pl.Hs * pl.Ws), &p.mg_hw, &p.sh_hw);
+      fastdiv_magic((unsigned)pl.Ws, &p.mg_w, &p.sh_w);
+      SMARK();
+      K_TRY(e, "stem (fp32 MFMA)", flope_conv_f32m_launch(&p, L.mt, 1, L.grid, L.lds_bytes, stream));
+    } else if (dt == FLOPE_DT_F32) {
       NaiveConvP p; memset(&p, 0, sizeof(p));
       p.in = (const float*)stem_in; p.out = (float*)stem_out; p.w = e->stem_w_naive; p.bias = e->stem_bias;
       p.B = batch; p.Hip = pl.sHip; p.Wip = pl.sWip; p.Cin_stored = 4; p.Cin = 3; p.Ho = pl.Hs; p.Wo = pl.Ws;
@@ -562,7 +588,7 @@ static int run_slice(flope_engine* e, const void* x_dev, int in_format, int star
     const ConvShape& s = pl.shape[i];
     const Launch L = c.last = decide(o, pl, (int)i, x);
     ConvP p, pf;
-    if (L.family != kFolded && L.family != kNaive) conv_params(e, (int)i, L, start, batch, &p, &pf);
+    if (L.family != kFolded && L.family != kNaive && L.family != kF32m) conv_params(e, (int)i, L, start, batch, &p, &pf);
     if (L.family != kFolded) SMARK();
     switch (L.family) {
       case kFolded: break;                           // computed inside the next launch (conv_stag DSF)
@@ -575,6 +601,20 @@ static int run_slice(flope_engine* e, const void* x_dev, int in_format, int star
         q.Hop = s.hout + 2; q.Wop = s.wout + 2; q.Cout = s.cout; q.KH = s.k; q.KW = s.k; q.stride = s.stride;
         q.in_off = s.k == 3 ? 0 : 1; q.relu = s.relu;
         K_TRY(e, conv_name(s).c_str(), flope_naive_conv_launch(&q, stream));
+        break;
+      }
+      case kF32m: {
+        F32mConvP q; memset(&q, 0, sizeof(q));
+        q.in = (const float*)buf_at(e, c.in_buf, start); q.out = (float*)buf_at(e, c.out_buf, start);
+        q.res = c.res_buf >= 0 ? (const float*)buf_at(e, c.res_buf, start) : nullptr;
+        q.w = (const float*)c.img[kWF32m]; q.bias = (const float*)c.img[kBias];
+        q.B = batch; q.Hip = s.hin + 2; q.Wip = s.win + 2; q.Cin_stored = s.cin; q.Cin = s.cin; q.Ho = s.hout; q.Wo = s.wout;
+        q.Hop = s.hout + 2; q.Wop = s.wout + 2; q.Cout = s.cout; q.KH = s.k; q.KW = s.k; q.stride = s.stride;
+        q.in_off = s.k == 3 ? 0 : 1; q.relu = s.relu;
+        q.M = batch * s.hout * s.wout; q.csteps = s.cin / 16; q.nsteps = f32m_steps(s.cin, s.k);
+        fastdiv_magic((unsigned)(s.hout * s.wout), &q.mg_hw, &q.sh_hw);
+        fastdiv_magic((unsigned)s.wout, &q.mg_w, &q.sh_w);
+        K_TRY(e, conv_name(s).c_str(), flope_conv_f32m_launch(&q, L.mt, 0, L.grid, L.lds_bytes, stream));
         break;
       }
       case kGstag: K_TRY(e, conv_name(s).c_str(), flope_conv_gstag_launch(&p, dt, stream)); break;

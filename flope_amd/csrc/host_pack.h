@@ -231,6 +231,42 @@ inline std::vector<float> naive_layout(const std::vector<float>& wf, int cout, i
   return out;
 }
 
+// conv_f32m (float32 trunk on v_mfma_f32_16x16x4_f32): a wave owns 64 output channels as four MFMA row tiles ct and reads its A
+// fragments from global memory, one 16-byte load per lane = four consecutive k, element s feeding MFMA s of a 16-deep step:
+// [cout / 64 blocks][K / 16 steps][4 ct][64 lanes][4]  <-  W[f32m_channel(block, ct, lane & 15)][k = 16 step + 4 (lane >> 4) + s]
+// MFMA D rows 4 g .. 4 g + 3 of tile ct are then channels 64 block + 16 g + 4 ct .. + 3: a lane ends with 16 consecutive channels
+// of its pixel.  k = (ky * kw + kx) * cin + ci (cin % 16 == 0: a step lies inside one tap).
+inline int f32m_channel(int blk, int ct, int i) { return blk * 64 + (i >> 2) * 16 + ct * 4 + (i & 3); }
+inline int f32m_steps(int cin, int k) { return k * k * cin / 16; }
+
+inline std::vector<float> pack_f32m(const std::vector<float>& wf, int cout, int cin, int k) {
+  const int nsteps = f32m_steps(cin, k);
+  std::vector<float> out((size_t)cout * nsteps * 16);
+  for (int blk = 0; blk < cout / 64; ++blk)
+    for (int ks = 0; ks < nsteps; ++ks)
+      for (int ct = 0; ct < 4; ++ct)
+        for (int lane = 0; lane < 64; ++lane)
+          for (int s = 0; s < 4; ++s) {
+            const int co = f32m_channel(blk, ct, lane & 15), kk = ks * 16 + 4 * (lane >> 4) + s, tap = kk / cin, ci = kk % cin;
+            out[((((size_t)blk * nsteps + ks) * 4 + ct) * 64 + lane) * 4 + s] = wf[(((size_t)co * cin + ci) * k + tap / k) * k + tap % k];
+          }
+  return out;
+}
+
+// the 7x7 stem in the same image: k = 4 tap + c over the 4 stored input channels (tap = 7 ky + kx), 13 steps; zero for c = 3 and
+// for the three taps that pad K = 196 to 208
+constexpr int kF32mStemSteps = 13;
+inline std::vector<float> pack_f32m_stem(const std::vector<float>& wf) {
+  std::vector<float> out((size_t)64 * kF32mStemSteps * 16, 0.f);
+  for (int ks = 0; ks < kF32mStemSteps; ++ks)
+    for (int ct = 0; ct < 4; ++ct)
+      for (int lane = 0; lane < 64; ++lane)
+        for (int s = 0; s < 3; ++s) {
+          const int co = f32m_channel(0, ct, lane & 15), tap = ks * 4 + (lane >> 4);
+          if (tap < 49) out[(((size_t)ks * 4 + ct) * 64 + lane) * 4 + s] = wf[(((size_t)co * 3 + s) * 7 + tap / 7) * 7 + tap % 7];
+        }
+  return out;
+}
 
 // fc.0 weights W1 [N][K] (N % 16 == 0, K % 32 == 0) in the A-fragment order of fc1_packed_kernel:
 // [n tile][K / 32][2][lane = g * 16 + r][4]  <-  W1[(tile * 16 + r) * K + kb * 32 + h * 16 + 4 g + s]

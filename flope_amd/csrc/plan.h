@@ -23,6 +23,7 @@ constexpr size_t kGstagLds = 3 * 32768 + 3 * 16384;
 constexpr size_t kR4Lds = (size_t)2 * 5 * 8192 + 18 * 4096 + 4 * 2048;      // patch buffers, resident weights, line images
 constexpr size_t kS1rLds = 2 * 4 * 6 * 32 * 64 + 4 * 14 * 1024;
 constexpr size_t kS2rLds = 2 * 18 * 32 * 128;
+constexpr size_t kF32mLds = kLdsTwoBlocks + 4096;   // conv_f32m: reserved, never touched -- more than half a CU's LDS = one workgroup per CU
 
 // ---- options ---------------------------------------------------------------------------------------------------------------
 struct PlanOptions {
@@ -58,6 +59,7 @@ struct PlanOptions {
   int ldspad = 0;        // conv_mfma: KB of LDS added to a launch (occupancy experiments)
   int dbg = 0;           // diagnostic builds: ablation bits, 64 / 128 = clock stamps
   int nbuf = 2;          // conv_mfma ring depth asked for (3 where the weight tile is 16 KB per step)
+  int f32mfma = 0;       // FLOPE_DT_F32 only: 1 = stem and trunk convs on the exact-fp32 MFMA (conv_f32m.hip), 0 = naive_conv_kernel (the checker)
   int profile = 0;       // 1: one slice, an event around every launch (flope_profile_read); 2: the slices as in production, events on every slice's stream (flope_profile_timeline)
 };
 
@@ -102,6 +104,7 @@ inline const std::vector<OptionDef>& option_table() {
       {"dbg", &O::dbg, kClamp, INT_MIN, INT_MAX, false},
       {"nbuf", &O::nbuf, kNbuf, 2, 3, true},
       {"profile", &O::profile, kClamp, 0, 2, false},
+      {"f32mfma", &O::f32mfma, kBool, 0, 1, false},
   };
   return t;
 }
@@ -411,7 +414,7 @@ inline SliceCtx slice_ctx(const Slices& sl, int s, int whole_batch, int num_cus)
 }
 
 // ---- the decision for one conv of one slice ---------------------------------------------------------------------------------------
-enum Family { kFolded, kNaive, kGstag, kS1r, kR4, kW4, kStagFlat, kStag512x64, kStagBands, kS2r, kMfma };   // kFolded: no launch of its own
+enum Family { kFolded, kNaive, kGstag, kS1r, kR4, kW4, kStagFlat, kStag512x64, kStagBands, kS2r, kMfma, kF32m };   // kFolded: no launch of its own
 
 struct Launch {
   int family = kFolded;
@@ -429,6 +432,33 @@ struct Launch {
   int dbg = 0, dbg_lds_off = 0;  // ConvP::dbg / dbg_lds_off
   int stamps = 0;                // diagnostic builds: the launch leaves clock stamps in its region of the split-K workspace
 };
+
+// conv_f32m (float32 on the exact-fp32 MFMA): a wave owns mp x 16 pixels x 64 channels, a workgroup four consecutive pixel tiles
+// of one 64-channel block, and a CU holds ONE workgroup (kF32mLds; measured).  So a launch takes whole rounds of
+// `cus` workgroups, and a workgroup's time grows with mp: the cheapest of mp = 4 / 2 / 1 by rounds x (4 mp + 1) -- the + 1 stands
+// for a workgroup's prologue and epilogue, an estimate of a quarter of one pixel tile's K loop -- ties to the larger tile (fewer
+// weight loads per MFMA).  (Every output is summed in the same order whatever mp is.)
+inline int f32m_mp(int M, int cout, int cus) {
+  int best = 4;
+  long best_cost = -1;
+  for (int mp = 4; mp >= 1; mp >>= 1) {
+    const long wgs = (long)((M + 64 * mp - 1) / (64 * mp)) * (cout / 64);
+    const long cost = (wgs + cus - 1) / cus * (4 * mp + 1);
+    if (best_cost < 0 || cost < best_cost) { best_cost = cost; best = mp; }
+  }
+  return best;
+}
+inline void f32m_launch(Launch& L, int M, int cout, int cus) {
+  L = Launch();
+  L.family = kF32m; L.mt = f32m_mp(M, cout, cus); L.lds_bytes = kF32mLds;
+  L.mtiles = (M + 64 * L.mt - 1) / (64 * L.mt); L.ntiles = cout / 64;
+  L.total_tiles = L.grid = L.mtiles * L.ntiles;
+}
+inline Launch f32m_stem_launch(const Plan& pl, const SliceCtx& x) {
+  Launch L;
+  f32m_launch(L, x.batch * pl.Hs * pl.Ws, 64, x.num_cus);
+  return L;
+}
 
 inline ConvDims conv_dims(const Plan& pl, int i) {
   const ConvShape& s = pl.shape[i];
@@ -450,6 +480,7 @@ inline Launch decide(const PlanOptions& o, const Plan& pl, int i, const SliceCtx
   L.ntiles = c.ntiles; L.patch_rounds = c.rows_max; L.dbg = o.dbg;
   L.total_tiles = L.grid = L.mtiles * L.ntiles;
   L.cfg = c.cfg; L.patch = c.patch; L.nbuf = c.nbuf;
+  if (pl.dtype == FLOPE_DT_F32 && o.f32mfma) { f32m_launch(L, M, s.cout, cus); return L; }
   if (pl.dtype == FLOPE_DT_F32) { L.family = kNaive; return L; }
   ConvDims d = conv_dims(pl, i);
   if (c.stag == 3) {
@@ -595,6 +626,11 @@ inline std::string label(const Launch& L) {
     case kStag512x64: return "conv_stag_kernel<512x64>";
     case kStagBands: return "conv_stag_kernel<8rows x64>";
     case kS2r: return "conv_s2r_kernel<4rows x28>";
+    case kF32m: {
+      char k[64];
+      snprintf(k, sizeof k, "conv_f32m_kernel<%dx64>", 64 * L.mt);
+      return k;
+    }
     case kMfma: {
       int BM, BN; tile_dims(L.cfg, &BM, &BN);
       char k[96];
@@ -633,7 +669,11 @@ inline std::string launch_name(const Plan& pl, const PlanOptions& o, const std::
   const double stem_flops = 2.0 * pl.Hs * pl.Ws * 64 * 147;
   if (nh == 1 && idx == 0) { *flops = stem_flops; return "input+stem+maxpool|stem_pool_kernel"; }
   if (nh == 3 && idx == 0) return "prep_input|prep_input_kernel";
-  if (nh == 3 && idx == 1) { *flops = stem_flops; return pl.dtype == FLOPE_DT_F32 ? "stem|naive_conv_kernel" : "stem|stem_mfma_kernel"; }
+  if (nh == 3 && idx == 1) {
+    *flops = stem_flops;
+    if (pl.dtype == FLOPE_DT_F32 && o.f32mfma) return "stem|conv_f32m_kernel<7x7,4ch>";
+    return pl.dtype == FLOPE_DT_F32 ? "stem|naive_conv_kernel" : "stem|stem_mfma_kernel";
+  }
   if (nh == 3 && idx == 2) return "maxpool|maxpool_kernel";
   idx -= nh;
   if (idx == nc) return "avgpool|avgpool_kernel";

@@ -12,7 +12,8 @@ import torch
 from . import _lib
 from .weights import validate_state_dict
 
-_DTYPES = {"bf16": _lib.DT_BF16, "f16": _lib.DT_F16, "f32": _lib.DT_F32,
+# "f32" is the strict checker (naive_conv_kernel); "f32m" is the same float32 engine with option f32mfma = 1 (exact-fp32 MFMA trunk)
+_DTYPES = {"bf16": _lib.DT_BF16, "f16": _lib.DT_F16, "f32": _lib.DT_F32, "f32m": _lib.DT_F32,
            torch.bfloat16: _lib.DT_BF16, torch.float16: _lib.DT_F16, torch.float32: _lib.DT_F32}
 
 STAGES = {"stem": _lib.STAGE_STEM, "pool": _lib.STAGE_POOL, "feat": _lib.STAGE_FEAT,
@@ -64,6 +65,8 @@ class PoseEngine:
         _lib.check(rc)
         self.handle = h
         self._keep = None
+        if dtype == "f32m":
+            self.set_option("f32mfma", 1)
 
     def close(self):
         if getattr(self, "handle", None):

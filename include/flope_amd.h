@@ -43,6 +43,8 @@ typedef struct flope_engine* flope_handle;
 #define FLOPE_DT_BF16       0   /* MFMA v_mfma_f32_16x16x32_bf16 */
 #define FLOPE_DT_F16        1   /* MFMA v_mfma_f32_16x16x32_f16  */
 #define FLOPE_DT_F32        2   /* strict mode: plain fp32 direct convolution (no MFMA) */
+/* FLOPE_DT_F32 with flope_set_option(h, "f32mfma", 1): the same float32 buffers and stages, the stem and the 19 trunk convs on
+ * v_mfma_f32_16x16x4_f32 (exact float32 products and sums; differs from the strict mode in summation order only). */
 
 /* layout / dtype of the crop batch handed to flope_forward */
 #define FLOPE_IN_F32_NCHW   0   /* reference API: float32 [B,3,H,W] in [0,1] (posenet.py:31) */
@@ -157,7 +159,10 @@ int flope_depth_lift(const void* depth_dev, int depth_format, const uint8_t* mas
  * Every block owns its MID and DS buffers, so all taps of one forward can be read after it. */
 int flope_read_stage(flope_handle h, int stage, int batch, float* dst_dev,
                      int64_t* dims_out, void* stream);
-/* runtime knobs (A/B variants inside one build); returns previous value or <0 */
+/* runtime knobs (A/B variants inside one build); returns previous value or <0
+ *   "f32mfma" (default 0): FLOPE_DT_F32 engines run the stem and every trunk conv on the exact-fp32 MFMA kernel (conv_f32m_kernel)
+ *   instead of naive_conv_kernel; may be flipped between forwards (both weight images are loaded).  Stored and ignored by
+ *   FLOPE_DT_F16 / BF16 engines. */
 int flope_set_option(flope_handle h, const char* name, int value);
 /* developer aid of diagnostic builds (-DFLOPE_STAG_DBG, option "dbg" = 64): in-kernel clock stamps that conv launch i of
  * the last forward left in the split-K workspace at byte offset i * 1048576 ({clk0, clk1, rt0, rt1} uint64 per workgroup and
