@@ -62,6 +62,16 @@ SIGNATURES = {
     "flope_frame_finish": (_I, [_P, _I, _P, _I]),
     "flope_frame_to_poses": (_I, [_P, _P, _P, _I, _P, _P, _P, _I, _F, C.POINTER(_F), _F, _F, _P, _I, _P]),
     "flope_frame_read_boxes": (_I, [_P, _I, _P, _P, _I]),
+    "flope_guard_create": (_I, [_P, _P, _I, _I, C.POINTER(_P)]),
+    "flope_guard_destroy": (_I, [_P]),
+    "flope_guard_last_error": (C.c_char_p, [_P]),
+    "flope_guard_set_gap_min": (_F, [_P, _F]),
+    "flope_guard_forward": (_I, [_P, _I, _P, _I, _I, _P, _I, _P, _P, _P, _P, _P]),
+    "flope_guard_repair": (_I, [_P, _I, _P]),
+    "flope_guard_forward_repaired": (_I, [_P, _P, _I, _I, _P, _I, _P, _P, _P, _P, _P]),
+    "flope_guard_read_selection": (_I, [_P, _I, _P, _I]),
+    "flope_frame_create_guarded": (_I, [_P, _I, _I, _I, _I, C.POINTER(_P)]),
+    "flope_frame_read_gaps": (_I, [_P, _I, _P, _I]),
     "flope_stream_create_cu_mask": (_I, [_I, C.POINTER(C.c_uint32), _I, C.POINTER(_P)]),
     "flope_stream_destroy": (_I, [_I, _P]),
     "flope_yolo_create": (_I, [_I, _I, _I, _I, _I, C.POINTER(_P)]),

@@ -290,6 +290,9 @@ extern "C" int flope_engine_geometry(flope_handle h, int* max_batch, int* dtype,
   return FLOPE_OK;
 }
 
+// library-internal (guard.h): the guard checks that its two engines share the head's width
+extern "C" int flope_engine_bod(flope_handle h) { return h ? h->bod : FLOPE_EINVAL; }
+
 extern "C" const char* flope_last_error(flope_handle h) { return h ? h->err.c_str() : g_last_error.c_str(); }
 
 extern "C" int flope_create(int device_id, int height, int width, int max_batch, int dtype, int backbone_out_dim,

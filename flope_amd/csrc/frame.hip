@@ -19,6 +19,7 @@
 #include <stdint.h>
 #include <string>
 #include "../../include/flope_amd.h"
+#include "guard.h"
 
 namespace {
 thread_local std::string g_frame_error;
@@ -36,11 +37,16 @@ struct Slot {
   hipEvent_t ev_sel = nullptr, ev_done = nullptr;
   int state = 0;                 // 0 idle, 1 selected, 2 enqueued
   int n = 0;                     // boxes enqueued
+  // guarded handles only (flope_frame_create_guarded)
+  float* gap = nullptr;          // device [cap]: the guard's conditioning figure of every crop
+  void* stream = nullptr;        // the stream flope_frame_enqueue ran on: flope_frame_finish repairs on it
+  int gap_n = -1;                // crops of the last finished frame (flope_frame_read_gaps); -1: none yet
 };
 }  // namespace
 
 struct flope_frame {
   flope_handle eng = nullptr;
+  flope_guard_handle guard = nullptr;   // guarded mode: eng is the guard's f16 engine and slot i uses slot i of the guard
   int device = 0, H = 0, W = 0, crop = 0, cap = 0, nslots = 0, eng_maxB = 0, fmt = 0;
   size_t crop_bytes = 0;
   Slot* slots = nullptr;
@@ -89,7 +95,7 @@ __global__ __launch_bounds__(64) void frame_select_kernel(const float* __restric
 
 void free_slot(Slot& s) {
   if (s.ev_done) { hipEventSynchronize(s.ev_done); }
-  void* dev[] = {s.boxes, s.nsel, s.depth_scratch, s.dv, s.xyz, s.Rt, s.rel, s.crops};
+  void* dev[] = {s.boxes, s.nsel, s.depth_scratch, s.dv, s.xyz, s.Rt, s.rel, s.crops, s.gap};
   for (void* p : dev) if (p) hipFree(p);
   void* host[] = {s.nsel_host, s.Rt_host, s.rel_host};
   for (void* p : host) if (p) hipHostFree(p);
@@ -101,9 +107,8 @@ void free_slot(Slot& s) {
 
 extern "C" const char* flope_frame_last_error(flope_frame_handle f) { return f ? f->err.c_str() : g_frame_error.c_str(); }
 
-extern "C" int flope_frame_create(flope_handle pose_engine, int frame_h, int frame_w, int max_boxes, int slots, flope_frame_handle* out) {
-  if (!out) return ffail(nullptr, FLOPE_EINVAL, "flope_frame_create: out is NULL");
-  *out = nullptr;
+namespace {
+int frame_create(flope_handle pose_engine, flope_guard_handle guard, int frame_h, int frame_w, int max_boxes, int slots, flope_frame_handle* out) {
   int maxB = 0, dtype = 0, eh = 0, ew = 0, dev = 0;
   if (!pose_engine || flope_engine_geometry(pose_engine, &maxB, &dtype, &eh, &ew, &dev) != FLOPE_OK)
     return ffail(nullptr, FLOPE_EINVAL, "flope_frame_create: bad PoseResNet engine handle");
@@ -111,9 +116,11 @@ extern "C" int flope_frame_create(flope_handle pose_engine, int frame_h, int fra
     return ffail(nullptr, FLOPE_EINVAL, "flope_frame_create: frame up to 32767 x 32767 (int16 boxes), 1..4096 boxes, 1..16 slots, a square crop engine");
   if (hipSetDevice(dev) != hipSuccess) return ffail(nullptr, FLOPE_EHIP, "flope_frame_create: hipSetDevice failed");
   flope_frame* f = new flope_frame();
-  f->eng = pose_engine; f->device = dev; f->H = frame_h; f->W = frame_w; f->crop = eh; f->cap = max_boxes; f->nslots = slots; f->eng_maxB = maxB;
+  f->eng = pose_engine; f->guard = guard; f->device = dev; f->H = frame_h; f->W = frame_w; f->crop = eh; f->cap = max_boxes; f->nslots = slots; f->eng_maxB = maxB;
   // crops in the trunk's own 16-bit NHWC layout where there is one (bit-identical to float32 crops: the stem rounds to that type)
-  f->fmt = dtype == FLOPE_DT_F16 ? FLOPE_IN_F16_NHWC : (dtype == FLOPE_DT_BF16 ? FLOPE_IN_BF16_NHWC : FLOPE_IN_F32_NCHW);
+  // a guarded handle keeps float32 crops: the f16 stem rounds them on load exactly as it rounds the 16-bit ones, and the float32 repair
+  // sees them unrounded
+  f->fmt = guard ? FLOPE_IN_F32_NCHW : dtype == FLOPE_DT_F16 ? FLOPE_IN_F16_NHWC : (dtype == FLOPE_DT_BF16 ? FLOPE_IN_BF16_NHWC : FLOPE_IN_F32_NCHW);
   f->crop_bytes = (size_t)f->crop * f->crop * 3 * (f->fmt == FLOPE_IN_F32_NCHW ? 4 : 2);
   f->slots = new Slot[slots];
   const size_t cap = (size_t)max_boxes, npix = (size_t)frame_h * frame_w;
@@ -124,7 +131,7 @@ extern "C" int flope_frame_create(flope_handle pose_engine, int frame_h, int fra
          hipMalloc((void**)&s.depth_scratch, ((npix + 15) & ~(size_t)15) + 16 + 512 * cap) == hipSuccess &&
          hipMalloc((void**)&s.dv, cap * sizeof(float)) == hipSuccess && hipMalloc((void**)&s.xyz, cap * 3 * sizeof(float)) == hipSuccess &&
          hipMalloc((void**)&s.Rt, cap * 16 * sizeof(float)) == hipSuccess && hipMalloc((void**)&s.rel, cap * sizeof(int32_t)) == hipSuccess &&
-         hipMalloc(&s.crops, cap * f->crop_bytes) == hipSuccess &&
+         hipMalloc(&s.crops, cap * f->crop_bytes) == hipSuccess && (!guard || hipMalloc((void**)&s.gap, cap * sizeof(float)) == hipSuccess) &&
          hipHostMalloc((void**)&s.nsel_host, 2 * sizeof(int), hipHostMallocDefault) == hipSuccess &&
          hipHostMalloc((void**)&s.Rt_host, cap * 16 * sizeof(float), hipHostMallocDefault) == hipSuccess &&
          hipHostMalloc((void**)&s.rel_host, cap * sizeof(int32_t), hipHostMallocDefault) == hipSuccess &&
@@ -137,6 +144,23 @@ extern "C" int flope_frame_create(flope_handle pose_engine, int frame_h, int fra
   }
   *out = f;
   return FLOPE_OK;
+}
+}  // namespace
+
+extern "C" int flope_frame_create(flope_handle pose_engine, int frame_h, int frame_w, int max_boxes, int slots, flope_frame_handle* out) {
+  if (!out) return ffail(nullptr, FLOPE_EINVAL, "flope_frame_create: out is NULL");
+  *out = nullptr;
+  return frame_create(pose_engine, nullptr, frame_h, frame_w, max_boxes, slots, out);
+}
+
+extern "C" int flope_frame_create_guarded(flope_guard_handle guard, int frame_h, int frame_w, int max_boxes, int slots, flope_frame_handle* out) {
+  if (!out) return ffail(nullptr, FLOPE_EINVAL, "flope_frame_create_guarded: out is NULL");
+  *out = nullptr;
+  int gslots = 0;
+  flope_handle fast = flope_guard_fast_engine(guard, &gslots);
+  if (!fast) return ffail(nullptr, FLOPE_EINVAL, "flope_frame_create_guarded: NULL guard handle");
+  if (slots > gslots) return ffail(nullptr, FLOPE_EINVAL, "flope_frame_create_guarded: more slots than the guard has (" + std::to_string(gslots) + ")");
+  return frame_create(fast, guard, frame_h, frame_w, max_boxes, slots, out);
 }
 
 extern "C" int flope_frame_destroy(flope_frame_handle f) {
@@ -181,15 +205,27 @@ extern "C" int flope_frame_enqueue(flope_frame_handle f, int slot, const uint8_t
     return ffail(f, FLOPE_EHIP, "flope_frame_enqueue: depth lift failed");
   if (flope_crop_resize_mask(frame_dev, mask_dev, f->H, f->W, s.boxes + (size_t)f->cap * 4, n, f->crop, f->fmt, s.crops, stream) != 0)
     return ffail(f, FLOPE_EHIP, "flope_frame_enqueue: crop kernel failed");
-  for (int off = 0; off < n; off += f->eng_maxB) {           // (more boxes than the engine's batch: several forwards)
+  s.stream = stream;
+  for (int off = 0; f->guard && off < n; off += f->eng_maxB) {
+    // guarded: the f16 forward and the guard's selection per chunk; every chunk but the last is repaired here (one guard slot holds
+    // one forward), the last one in flope_frame_finish.  A failure leaves frame slot and guard slot idle.
+    const int m = n - off < f->eng_maxB ? n - off : f->eng_maxB;
+    int rc = flope_guard_forward(f->guard, slot, (const char*)s.crops + (size_t)off * f->crop_bytes, f->fmt, m, s.xyz + (size_t)off * 3, 1, nullptr, nullptr,
+                                 s.Rt + (size_t)off * 16, s.gap + off, stream);
+    if (rc == FLOPE_OK && off + m < n) rc = flope_guard_repair(f->guard, slot, stream);
+    if (rc < 0) { s.state = 0; return ffail(f, rc, std::string("flope_frame_enqueue: ") + flope_guard_last_error(f->guard)); }
+  }
+  for (int off = 0; !f->guard && off < n; off += f->eng_maxB) {           // (more boxes than the engine's batch: several forwards)
     const int m = n - off < f->eng_maxB ? n - off : f->eng_maxB;
     const int rc = flope_forward_poses(f->eng, (const char*)s.crops + (size_t)off * f->crop_bytes, f->fmt, m, s.xyz + (size_t)off * 3, 1, nullptr, nullptr,
                                        s.Rt + (size_t)off * 16, stream);
     if (rc != FLOPE_OK) return ffail(f, rc, std::string("flope_frame_enqueue: ") + flope_last_error(f->eng));
   }
   if (hipMemcpyAsync(s.Rt_host, s.Rt, (size_t)n * 16 * sizeof(float), hipMemcpyDeviceToHost, st) != hipSuccess ||
-      hipMemcpyAsync(s.rel_host, s.rel, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, st) != hipSuccess || hipEventRecord(s.ev_done, st) != hipSuccess)
+      hipMemcpyAsync(s.rel_host, s.rel, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, st) != hipSuccess || hipEventRecord(s.ev_done, st) != hipSuccess) {
+    if (f->guard) { flope_guard_cancel(f->guard, slot); s.state = 0; }
     return ffail(f, FLOPE_EHIP, "flope_frame_enqueue: result copy failed");
+  }
   return n;
 }
 
@@ -198,8 +234,19 @@ extern "C" int flope_frame_finish(flope_frame_handle f, int slot, double* poses_
   if (slot < 0 || slot >= f->nslots) return ffail(f, FLOPE_EINVAL, "flope_frame_finish: bad slot");
   Slot& s = f->slots[slot];
   if (s.state != 2) return ffail(f, FLOPE_ESTATE, "flope_frame_finish: nothing enqueued in this slot");
+  if (f->guard && s.n > 0) {
+    // the guard's one host wait (the number of flagged crops) sits here, where the host waits anyway; repaired rows travel again
+    const int fixed = flope_guard_repair(f->guard, slot, s.stream);
+    if (fixed < 0) { s.state = 0; return ffail(f, fixed, std::string("flope_frame_finish: ") + flope_guard_last_error(f->guard)); }
+    if (fixed > 0 && (hipMemcpyAsync(s.Rt_host, s.Rt, (size_t)s.n * 16 * sizeof(float), hipMemcpyDeviceToHost, (hipStream_t)s.stream) != hipSuccess ||
+                      hipEventRecord(s.ev_done, (hipStream_t)s.stream) != hipSuccess)) {
+      s.state = 0;
+      return ffail(f, FLOPE_EHIP, "flope_frame_finish: copy of the repaired poses failed");
+    }
+  }
   if (hipSetDevice(f->device) != hipSuccess || hipEventSynchronize(s.ev_done) != hipSuccess) return ffail(f, FLOPE_EHIP, "flope_frame_finish: waiting for the poses failed");
   s.state = 0;
+  s.gap_n = s.n;
   int k = 0;
   for (int i = 0; i < s.n; ++i) {
     if (!s.rel_host[i]) continue;
@@ -232,4 +279,15 @@ extern "C" int flope_frame_read_boxes(flope_frame_handle f, int slot, int32_t* g
                 hipMemcpy(sq_host, s.boxes + (size_t)f->cap * 4, (size_t)n * 16, hipMemcpyDeviceToHost) != hipSuccess))
     return ffail(f, FLOPE_EHIP, "flope_frame_read_boxes: copy failed");
   return n;
+}
+
+// test hook (guarded handles): the guard's conditioning figure of every crop of the slot's last finished frame, float32 [n]; returns n
+extern "C" int flope_frame_read_gaps(flope_frame_handle f, int slot, float* gap_host, int cap) {
+  if (!f || slot < 0 || slot >= f->nslots) return ffail(f, FLOPE_EINVAL, "flope_frame_read_gaps: bad handle / slot");
+  Slot& s = f->slots[slot];
+  if (!f->guard || s.state == 2 || s.gap_n < 0) return ffail(f, FLOPE_ESTATE, "flope_frame_read_gaps: no finished frame of a guarded handle in this slot");
+  if (s.gap_n > cap || (s.gap_n > 0 && !gap_host)) return ffail(f, FLOPE_EINVAL, "flope_frame_read_gaps: gap_host too small");
+  if (s.gap_n > 0 && (hipSetDevice(f->device) != hipSuccess || hipMemcpy(gap_host, s.gap, (size_t)s.gap_n * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess))
+    return ffail(f, FLOPE_EHIP, "flope_frame_read_gaps: copy failed");
+  return s.gap_n;
 }

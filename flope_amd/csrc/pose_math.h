@@ -163,6 +163,115 @@ FLOPE_HD inline void procrustes3x3(const float* M, float* R) {
   if (!procrustes3x3_newton(M, R)) procrustes3x3_jacobi(M, R);
 }
 
+// ---------------------------------------------------------------------------
+// Conditioning of the Procrustes problem above:  gap(M) = s2 + sign(det M) s3  in M's own units, the quantity that amplifies an
+// error dM of M into the rotation (|dR| gap <= 3 |dM|).  With l1 >= l2 the two largest eigenvalues of Horn's N,
+//     l1 = s1 + s2 + sign(det M) s3,   l2 = s1 - s2 - sign(det M) s3,   gap = (l1 - l2) / 2 = l1 - s1.
+// Fast path: l1 by the Newton iteration of procrustes3x3_newton (well conditioned whenever the gap is not tiny), s1^2 as the largest
+// eigenvalue of M^T M in closed form (trigonometric solution of the cubic: absolute error <= ~1e-8 |M|_F^2 even where s1 = s2, the
+// case of every rotation-like M).  A polynomial cannot give l2 itself: a near-rotation has l2 = l3 = l4, a triple root.  When Newton
+// cannot certify l1 (top eigenvalue nearly repeated <=> the gap is below ~1e-3 |M|_F) both eigenvalues come from a cyclic Jacobi
+// solve of N, which is backward stable at any multiplicity: the true small value, not a failure.  NaN for a non-finite M, 0 for M = 0.
+FLOPE_HD inline float procrustes_gap3x3(const float* M) {
+  double m[9], amax = 0.0;
+  bool finite = true;
+  for (int i = 0; i < 9; ++i) {
+    m[i] = M[i];
+    const double a = fabs(m[i]);
+    finite = finite && (a <= 3.4028234663852886e38);
+    amax = a > amax ? a : amax;
+  }
+  if (!finite) return __builtin_nanf("");
+  if (amax == 0.0) return 0.f;
+  double fro2 = 0.0;
+  const double ia = 1.0 / amax;                       // (amax >= 1.4e-45: finite)
+  for (int i = 0; i < 9; ++i) { m[i] *= ia; fro2 += m[i] * m[i]; }        // 1 <= fro2 <= 9 (to rounding) whatever the float's exponent was
+  const double fro = sqrt(fro2), inv = 1.0 / fro;
+  for (int i = 0; i < 9; ++i) m[i] *= inv;
+  double n[4][4];
+  n[0][0] = m[0] + m[4] + m[8];  n[1][1] = m[0] - m[4] - m[8];  n[2][2] = -m[0] + m[4] - m[8];  n[3][3] = -m[0] - m[4] + m[8];
+  n[0][1] = n[1][0] = m[7] - m[5];  n[0][2] = n[2][0] = m[2] - m[6];  n[0][3] = n[3][0] = m[3] - m[1];
+  n[1][2] = n[2][1] = m[1] + m[3];  n[1][3] = n[3][1] = m[2] + m[6];  n[2][3] = n[3][2] = m[5] + m[7];
+  const double detM = det3(m[0], m[1], m[2], m[3], m[4], m[5], m[6], m[7], m[8]);
+  const double c1 = -8.0 * detM;
+  const double c0 =
+      n[0][0] * det3(n[1][1], n[1][2], n[1][3], n[2][1], n[2][2], n[2][3], n[3][1], n[3][2], n[3][3]) -
+      n[0][1] * det3(n[1][0], n[1][2], n[1][3], n[2][0], n[2][2], n[2][3], n[3][0], n[3][2], n[3][3]) +
+      n[0][2] * det3(n[1][0], n[1][1], n[1][3], n[2][0], n[2][1], n[2][3], n[3][0], n[3][1], n[3][3]) -
+      n[0][3] * det3(n[1][0], n[1][1], n[1][2], n[2][0], n[2][1], n[2][2], n[3][0], n[3][1], n[3][2]);
+  float lf = 1.7320509f, c1f = (float)c1, c0f = (float)c0;
+  for (int it = 0; it < 10; ++it) {
+    const float l2 = lf * lf;
+    const float pv = (l2 - 2.f) * l2 + c1f * lf + c0f, dv = (4.f * l2 - 4.f) * lf + c1f;
+    if (!(dv > 1e-6f)) break;
+    lf -= pv / dv;
+    if (pv <= 2e-6f * dv) break;                       // float32 has nothing more to give (a near-rotation starts on its root)
+  }
+  double l = (double)lf * (1.0 + 1e-6) + 1e-9;        // the upper side: Newton descends monotonically onto the largest root
+  bool ok = false;
+  for (int it = 0; it < 10; ++it) {
+    const double l2 = l * l;
+    const double pv = (l2 - 2.0) * l2 + c1 * l + c0, dv = (4.0 * l2 - 4.0) * l + c1;
+    if (!(dv > 1e-4)) break;                           // P'(l1) = (l1 - l2)(l1 - l3)(l1 - l4): rounding noise of P (1e-15) / 1e-4
+    const double dl = pv / dv;
+    l -= dl;
+    if (fabs(dl) <= 1e-11 * l) { ok = true; break; }
+  }
+  double gap;
+  if (ok) {
+    // K = M^T M - I / 3 (trace 0);  its largest eigenvalue is 2 p cos(acos(det(K / p) / 2) / 3)
+    const double k00 = m[0] * m[0] + m[3] * m[3] + m[6] * m[6] - 1.0 / 3.0, k11 = m[1] * m[1] + m[4] * m[4] + m[7] * m[7] - 1.0 / 3.0,
+                 k22 = m[2] * m[2] + m[5] * m[5] + m[8] * m[8] - 1.0 / 3.0, k01 = m[0] * m[1] + m[3] * m[4] + m[6] * m[7],
+                 k02 = m[0] * m[2] + m[3] * m[5] + m[6] * m[8], k12 = m[1] * m[2] + m[4] * m[5] + m[7] * m[8];
+    const double p2 = (k00 * k00 + k11 * k11 + k22 * k22 + 2.0 * (k01 * k01 + k02 * k02 + k12 * k12)) / 6.0;
+    double mu1 = 1.0 / 3.0;
+    if (p2 > 1e-30) {
+      const double p = sqrt(p2);
+      double r = det3(k00, k01, k02, k01, k11, k12, k02, k12, k22) / (2.0 * p2 * p);
+      r = r < -1.0 ? -1.0 : (r > 1.0 ? 1.0 : r);
+      mu1 += 2.0 * p * cos(acos(r) / 3.0);
+    }
+    gap = l - sqrt(mu1);
+  } else {
+    for (int sweep = 0; sweep < 12; ++sweep) {         // the rotations of procrustes3x3_jacobi, eigenvalues only
+      double offn = 0.0, diagn = 0.0;
+      for (int i = 0; i < 4; ++i)
+        for (int j = 0; j < 4; ++j) (i == j ? diagn : offn) += n[i][j] * n[i][j];
+      if (offn <= 1e-30 * diagn || offn == 0.0) break;
+      for (int pp = 0; pp < 3; ++pp)
+        for (int qq = pp + 1; qq < 4; ++qq) {
+          const double apq = n[pp][qq];
+          if (apq == 0.0) continue;
+          const double theta = (n[qq][qq] - n[pp][pp]) / (2.0 * apq);
+          const double t = (theta >= 0.0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
+          const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
+          for (int k = 0; k < 4; ++k) {
+            const double akp = n[k][pp], akq = n[k][qq];
+            n[k][pp] = c * akp - s * akq;
+            n[k][qq] = s * akp + c * akq;
+          }
+          for (int k = 0; k < 4; ++k) {
+            const double apk = n[pp][k], aqk = n[qq][k];
+            n[pp][k] = c * apk - s * aqk;
+            n[qq][k] = s * apk + c * aqk;
+          }
+        }
+    }
+    double e1 = n[0][0] > n[1][1] ? n[0][0] : n[1][1], e2 = n[0][0] > n[1][1] ? n[1][1] : n[0][0];
+#pragma unroll
+    for (int i = 2; i < 4; ++i) {
+      const double v = n[i][i];
+      e2 = v > e1 ? e1 : (v > e2 ? v : e2);
+      e1 = v > e1 ? v : e1;
+    }
+    gap = 0.5 * (e1 - e2);
+  }
+  return (float)(gap * fro * amax);
+}
+
+// A crop is repaired when its gap is NOT known to reach the threshold: NaN (a non-finite M) is flagged, +inf is not.
+FLOPE_HD inline bool procrustes_gap_flagged(float gap, float gap_min) { return !(gap >= gap_min); }
+
 // nullify_yaw (mvg.py:240-251 with scipy extrinsic 'zyx'): zeroing the first Euler angle
 // equals R' = R * Rz(a)^T with a = atan2(-R01, R00): column 2 is
 // kept, R'01 = 0.

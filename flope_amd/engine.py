@@ -275,6 +275,142 @@ class PoseEngine:
         return buf.value.decode()
 
 
+class GuardedPoseEngine:
+    """The guarded mode (include/flope_amd.h flope_guard_*): a PoseEngine("f16") for the whole batch, the
+    device's own conditioning figure gap(M) per crop, and a PoseEngine("f32m") that runs again only the crops with
+    !(gap >= gap_min) and overwrites their rows.  Same hot-path interface as PoseEngine; `last_gap` (float32 [B] on the device)
+    and `last_repaired` describe the most recent forward."""
+
+    SLOTS = 16                                       # forwards that may await their repair at once (per slot: 40 bytes per crop)
+
+    def __init__(self, height: int, width: int, max_batch: int, max_repair: int = 32, device=None,
+                 backbone_out_dim: int = 2048, gap_min: float = 0.5, slots: int = SLOTS):
+        _require_gpu()
+        self.fast = PoseEngine(height, width, max_batch, "f16", device, backbone_out_dim)
+        self.max_repair = max(1, min(int(max_repair), int(max_batch)))
+        self.exact = PoseEngine(height, width, self.max_repair, "f32m", self.fast.device, backbone_out_dim)
+        self.lib, self.device = self.fast.lib, self.fast.device
+        self.height, self.width, self.max_batch = self.fast.height, self.fast.width, self.fast.max_batch
+        self.backbone_out_dim, self.slots = self.fast.backbone_out_dim, int(slots)
+        self.dtype_code = self.fast.dtype_code
+        g = C.c_void_p()
+        with torch.cuda.device(self.device):
+            rc = self.lib.flope_guard_create(self.fast.handle, self.exact.handle, self.max_repair, self.slots, C.byref(g))
+        if rc != 0:
+            raise RuntimeError(f"flope_amd error {rc}: {(self.lib.flope_guard_last_error(None) or b'').decode()}")
+        self.guard_handle = g
+        self.handle = self.fast.handle               # engine-level introspection goes to the f16 engine
+        self.last_gap, self.last_repaired = None, 0
+        self._keep = None
+        self.gap_min = gap_min
+
+    def close(self):
+        if getattr(self, "guard_handle", None):
+            self.lib.flope_guard_destroy(self.guard_handle)
+            self.guard_handle = None
+            self.fast.close()
+            self.exact.close()
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _gcheck(self, rc: int) -> int:
+        if rc < 0:
+            raise RuntimeError(f"flope_amd error {rc}: {(self.lib.flope_guard_last_error(self.guard_handle) or b'').decode()}")
+        return rc
+
+    @property
+    def gap_min(self) -> float:
+        return self._gap_min
+
+    @gap_min.setter
+    def gap_min(self, value: float) -> None:
+        self._gap_min = float(value)
+        self.lib.flope_guard_set_gap_min(self.guard_handle, self._gap_min)
+
+    def load_state_dict(self, sd: dict) -> None:
+        self.fast.load_state_dict(sd)
+        self.exact.load_state_dict(sd)
+
+    # -- hot path: the two stages (several forwards in flight: one slot each) and their sequence ----------------------------------
+    def guard_forward(self, slot: int, x, fmt: int, xyz, nullify: bool, r9, R, Rt, gap) -> None:
+        """Asynchronous: f16 forward into the caller's buffers + selection.  The caller keeps every buffer alive and unchanged
+        until guard_repair(slot) returns."""
+        self.fast._check_into(x, fmt, xyz=(xyz, 3), r9=(r9, 9), R=(R, 9), Rt=(Rt, 16), gap=(gap, 1))
+        ptr = lambda t: t.data_ptr() if t is not None else None   # noqa: E731
+        self._gcheck(self.lib.flope_guard_forward(self.guard_handle, int(slot), x.data_ptr(), fmt, x.shape[0], ptr(xyz), int(bool(nullify)),
+                                                  ptr(r9), ptr(R), ptr(Rt), ptr(gap), _stream_ptr(self.device)))
+
+    def guard_repair(self, slot: int) -> int:
+        """Waits (host) for the number of flagged crops of the slot's forward, enqueues their float32 repair; -> that number."""
+        with torch.cuda.device(self.device):
+            return self._gcheck(self.lib.flope_guard_repair(self.guard_handle, int(slot), _stream_ptr(self.device)))
+
+    def read_selection(self, slot: int = 0):
+        """test hook: indices of the crops the slot's last repair found flagged (ascending list of int)"""
+        idx = (C.c_int32 * self.max_batch)()
+        n = self._gcheck(self.lib.flope_guard_read_selection(self.guard_handle, int(slot), idx, self.max_batch))
+        return [int(idx[i]) for i in range(n)]
+
+    def forward(self, x: torch.Tensor, want_r9: bool = True, want_R: bool = True):
+        """-> (r9 [B,9] | None, R [B,3,3] | None), float32 on the engine's device, flagged rows repaired."""
+        fmt = self.fast._check_input(x)
+        x = x.contiguous()
+        B = x.shape[0]
+        r9 = torch.empty((B, 9), dtype=torch.float32, device=self.device)
+        R = torch.empty((B, 3, 3), dtype=torch.float32, device=self.device) if want_R else None
+        gap = torch.empty(B, dtype=torch.float32, device=self.device)
+        self.guard_forward(0, x, fmt, None, False, r9, R, None, gap)
+        self.last_repaired = self.guard_repair(0)
+        self.last_gap, self._keep = gap, x
+        return (r9 if want_r9 else None), R
+
+    def forward_into(self, x: torch.Tensor, fmt: int, r9: torch.Tensor | None, R: torch.Tensor | None) -> None:
+        gap = torch.empty(x.shape[0], dtype=torch.float32, device=self.device)
+        self.guard_forward(0, x, fmt, None, False, r9, R, None, gap)
+        self.last_repaired = self.guard_repair(0)
+        self.last_gap = gap
+
+    def forward_poses_into(self, x: torch.Tensor, fmt: int, xyz: torch.Tensor | None, nullify: bool, Rt: torch.Tensor,
+                           R: torch.Tensor | None = None, r9: torch.Tensor | None = None, gap: torch.Tensor | None = None) -> None:
+        """crops -> [B,16] poses as PoseEngine.forward_poses_into, flagged rows repaired (one host wait of 4 bytes).  Pass `gap`
+        (float32 [B]) to keep the call allocation-free."""
+        if gap is None:
+            gap = torch.empty(x.shape[0], dtype=torch.float32, device=self.device)
+        self.guard_forward(0, x, fmt, xyz, nullify, r9, R, Rt, gap)
+        self.last_repaired = self.guard_repair(0)
+        self.last_gap = gap
+
+    # -- everything else is the f16 engine's ------------------------------------------------------------------------------------
+    def extract_features(self, x: torch.Tensor) -> torch.Tensor:
+        return self.fast.extract_features(x)
+
+    def read_stage(self, name: str, batch: int) -> torch.Tensor:
+        return self.fast.read_stage(name, batch)
+
+    def autotune(self, *args, **kwargs) -> dict:
+        return self.fast.autotune(*args, **kwargs)
+
+    def set_option(self, name: str, value: int) -> int:
+        return self.fast.set_option(name, value)
+
+    def flops(self, batch: int) -> float:
+        return self.fast.flops(batch)
+
+    def launches(self) -> int:
+        return self.fast.launches()
+
+    def launch_info(self, batch: int):
+        return self.fast.launch_info(batch)
+
+    def describe_plan(self) -> str:
+        return self.fast.describe_plan()
+
+
 # ---- handle-less kernels ---------------------------------------------------------
 
 def _as_dev_f32(t: torch.Tensor, cols: int):

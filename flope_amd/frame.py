@@ -10,18 +10,21 @@ import numpy as np
 import torch
 
 from . import _lib
-from .engine import PoseEngine, _stream_ptr
+from .engine import GuardedPoseEngine, PoseEngine, _stream_ptr
 
 
 class FramePoses:
-    def __init__(self, engine: PoseEngine, frame_h: int, frame_w: int, max_boxes: int = 300, slots: int = 1):
+    def __init__(self, engine: PoseEngine | GuardedPoseEngine, frame_h: int, frame_w: int, max_boxes: int = 300, slots: int = 1):
         self.lib = _lib.load()
         self.engine = engine                     # kept alive: the handle borrows it
         self.device = engine.device
         self.frame_h, self.frame_w, self.max_boxes, self.slots = int(frame_h), int(frame_w), int(max_boxes), int(slots)
         h = C.c_void_p()
         with torch.cuda.device(self.device):
-            rc = self.lib.flope_frame_create(engine.handle, self.frame_h, self.frame_w, self.max_boxes, self.slots, C.byref(h))
+            if getattr(engine, "guard_handle", None):    # a GuardedPoseEngine: f16 forward in enqueue, float32 repair in finish
+                rc = self.lib.flope_frame_create_guarded(engine.guard_handle, self.frame_h, self.frame_w, self.max_boxes, self.slots, C.byref(h))
+            else:
+                rc = self.lib.flope_frame_create(engine.handle, self.frame_h, self.frame_w, self.max_boxes, self.slots, C.byref(h))
         if rc != 0:
             raise RuntimeError(f"flope_frame_create: {(self.lib.flope_frame_last_error(None) or b'').decode()}")
         self.handle = h
@@ -99,3 +102,9 @@ class FramePoses:
         sq = np.empty((self.max_boxes, 4), dtype=np.int32)
         n = self._check(self.lib.flope_frame_read_boxes(self.handle, slot, good.ctypes.data, sq.ctypes.data, self.max_boxes))
         return good[:n].copy(), sq[:n].copy()
+
+    def read_gaps(self, slot: int = 0) -> np.ndarray:
+        """test hook (guarded engines): the guard's conditioning figure of every crop of the slot's last finished frame, float32 [n]"""
+        gap = np.empty(self.max_boxes, dtype=np.float32)
+        n = self._check(self.lib.flope_frame_read_gaps(self.handle, slot, gap.ctypes.data, self.max_boxes))
+        return gap[:n].copy()

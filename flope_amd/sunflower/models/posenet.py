@@ -19,7 +19,7 @@ import os
 import torch
 import torch.nn as nn
 
-from flope_amd.engine import PoseEngine
+from flope_amd.engine import GuardedPoseEngine, PoseEngine
 
 _STAGES = ((64, 64, 1), (64, 128, 2), (128, 256, 2), (256, 512, 2))
 
@@ -90,7 +90,11 @@ class PoseResNet(nn.Module):
             if slot is not None:
                 slot[0].close()
             mb = max(self._max_batch, int(batch))
-            slot = [PoseEngine(hw[0], hw[1], mb, self.compute_dtype, torch.device("cuda", index), self.backbone_out_dim), -1]
+            if self.compute_dtype == "guard":            # f16 for every crop, float32 again for the ill-conditioned ones
+                eng = GuardedPoseEngine(hw[0], hw[1], mb, device=torch.device("cuda", index), backbone_out_dim=self.backbone_out_dim)
+            else:
+                eng = PoseEngine(hw[0], hw[1], mb, self.compute_dtype, torch.device("cuda", index), self.backbone_out_dim)
+            slot = [eng, -1]
             self._engines[key] = slot
         if slot[1] != self._version:
             slot[0].load_state_dict(self.state_dict())

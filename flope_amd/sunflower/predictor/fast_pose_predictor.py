@@ -235,8 +235,8 @@ class FastPosePredictor:
         def finish(slot):
             return fctx.finish(slot)
 
+        detecting, posing = [], []                     # frame indices / frame-handle slots in flight per stage (oldest first)
         try:
-            detecting, posing = [], []                 # frame indices / frame-handle slots in flight per stage (oldest first)
             for t, (rgb, depth) in enumerate(frames):
                 stage_detect(t, rgb, depth)
                 detecting.append(t)
@@ -248,9 +248,16 @@ class FastPosePredictor:
                 posing.append(stage_pose(u))
                 if len(posing) > 1:
                     yield finish(posing.pop(0))
-            for slot in posing:
-                yield finish(slot)
+            while posing:
+                yield finish(posing.pop(0))
         finally:
+            # a consumer that stops early (break / close) leaves enqueued frames behind: finish them, so that no slot of the frame
+            # handle (or of a guard behind it) stays armed for the next get_flower_poses
+            for slot in posing:
+                try:
+                    finish(slot)
+                except RuntimeError:
+                    pass
             torch.cuda.synchronize(dev)
             for d, g in zip(dets, prev_graph):
                 d.set_option("graph", g)

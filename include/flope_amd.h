@@ -227,6 +227,51 @@ int flope_frame_to_poses(flope_frame_handle f, const float* det_dev, const int32
 /* test hook: the boxes flope_frame_select kept, as detected (good_host) and squared (sq_host), int32 [n,4] each; returns n */
 int flope_frame_read_boxes(flope_frame_handle f, int slot, int32_t* good_host, int32_t* sq_host, int cap);
 
+/* ---- guarded mode: the f16 trunk, repaired per crop in float32 where the crop's own M is ill-conditioned ------------------------
+ * The rotation error of a 16-bit trunk is its error dM of the head output amplified by Procrustes: |dR| gap <= 3 |dM| with
+ * gap(M) = s2 + sign(det M) s3 (singular values of M, M's own units).  f16 keeps |dR| <= 1e-3 where gap >= 0.5; the float32 trunk on
+ * the exact-fp32 MFMA (option "f32mfma") keeps it everywhere, at a tenth of the rate.  A guard handle borrows one engine of each
+ * kind: the whole batch runs in f16, the device computes every crop's gap, and only the crops with !(gap >= gap_min) (a non-finite
+ * M included) run again in float32 and overwrite their rows, which are then bit for bit what the float32 engine gives for those
+ * crops alone; every other row is the f16 engine's, untouched.
+ *   fast: a FLOPE_DT_F16 engine; exact: a FLOPE_DT_F32 engine (the caller sets "f32mfma" on it, or not) with the same device, crop
+ *   size and backbone_out_dim; both with weights loaded before the first forward and alive for as long as the guard is.  bf16 is
+ *   refused (it would need gap_min = 6.9: every crop repaired).  max_repair <= exact's max_batch: crops per float32 forward (more
+ *   flagged crops run as several).  slots (1..16): forwards that may await their repair at the same time.
+ *   flope_guard_forward  asynchronous like flope_forward_poses (same arguments; Rt_dev may be NULL as well, at least one output is
+ *                        needed): f16 forward into the caller's outputs on `stream`; the selection kernel (gap per crop, index
+ *                        list, the NUMBER of flagged crops to pinned host memory, an event) runs behind it on a stream of the
+ *                        guard's own, so later work on `stream` does not wait for it.  gap_dev: float32 [batch] or NULL, valid
+ *                        once flope_guard_repair has returned.
+ *   flope_guard_repair   waits on the host for that number (4 bytes -- the one host wait of the mode, as in flope_frame_enqueue: HIP
+ *                        grids are sized on the host).  0: returns 0 and enqueues nothing.  Otherwise enqueues, per max_repair
+ *                        crops: gather -> flope_forward_poses(exact) -> scatter into rows idx[i] of r9 / R / Rt; returns the number
+ *                        of crops repaired.  x_dev, xyz_dev and the outputs must stay alive and unchanged from forward until
+ *                        repair returns; `stream` should be the forward's stream (or one ordered behind it).
+ *   flope_guard_forward_repaired = the two in sequence on slot 0.
+ * Call order: repair without forward, or forward on a slot that awaits its repair, is FLOPE_ESTATE; a failed call leaves the slot
+ * idle.  Repairs share the exact engine and one staging batch: like forwards of one engine they must not run concurrently. */
+typedef struct flope_guard* flope_guard_handle;
+int flope_guard_create(flope_handle fast, flope_handle exact, int max_repair, int slots, flope_guard_handle* out);
+int flope_guard_destroy(flope_guard_handle g);
+const char* flope_guard_last_error(flope_guard_handle g);
+/* threshold of the selection (default 0.5: the domain tests/test_gpu_parity.py asserts for f16); returns the previous value */
+float flope_guard_set_gap_min(flope_guard_handle g, float gap_min);
+int flope_guard_forward(flope_guard_handle g, int slot, const void* x_dev, int in_format, int batch, const float* xyz_dev, int nullify_yaw,
+                        float* r9_dev, float* R_dev, float* Rt_dev, float* gap_dev, void* stream);
+int flope_guard_repair(flope_guard_handle g, int slot, void* stream);
+int flope_guard_forward_repaired(flope_guard_handle g, const void* x_dev, int in_format, int batch, const float* xyz_dev, int nullify_yaw,
+                                 float* r9_dev, float* R_dev, float* Rt_dev, float* gap_dev, void* stream);
+/* test hook: the crops the slot's last repair found flagged, ascending, int32 [n]; returns n */
+int flope_guard_read_selection(flope_guard_handle g, int slot, int32_t* idx_host, int cap);
+/* flope_frame_* over a guard: slot i of the frame uses slot i of the guard (slots <= the guard's).  Crops are float32 NCHW;
+ * flope_frame_enqueue calls flope_guard_forward, flope_frame_finish runs flope_guard_repair before it reads the poses (its host
+ * wait is where the guard's belongs); a frame with more boxes than the f16 engine's max_batch repairs all but its last forward
+ * inside flope_frame_enqueue. */
+int flope_frame_create_guarded(flope_guard_handle g, int frame_h, int frame_w, int max_boxes, int slots, flope_frame_handle* out);
+/* test hook (guarded frame handles): gap of every crop of the slot's last finished frame, float32 [n]; returns n */
+int flope_frame_read_gaps(flope_frame_handle f, int slot, float* gap_host, int cap);
+
 /* ---- TransformerEncoder (reference scripts/tf_encoder.py:5-27) -------------
  * Replaces `TransformerEncoder(input_dim, model_dim, out_dim, num_heads, num_layers, ff_dim,
  * dropout)` + `.load_state_dict()` + `forward(x)` in eval mode (dropout = identity):
