@@ -283,4 +283,43 @@ inline std::vector<float> pack_fc1(const float* W1, int N, int K) {
   return out;
 }
 
+// tf_linear_f32m (float32 encoder linears on v_mfma_f32_16x16x4_f32, tf_encoder.hip): W [N][K] row-major as in the checkpoint ->
+// [block of 64 features][K / 16 steps][nct feature tiles][64 lanes][4]  <-  W[tf_f32m_feature(block, nct, ct, lane & 15)][k = 16 step + 4 (lane >> 4) + s]
+// One (step, tile) is one contiguous KiB per wave.  N is padded to whole 16-row tiles with zero rows, so the last block has
+// nct = 1 .. 4 tiles (every block before it has 4); K is padded to whole steps with zero weights.  MFMA D rows 4 g .. 4 g + 3 of
+// tile ct are features 64 block + 4 nct g + 4 ct .. + 3: a lane ends with 4 nct consecutive features of its token (the idea of
+// lds_row_to_channel, which is the case nct = 4).
+inline int tf_f32m_steps(int K) { return (K + 15) / 16; }
+inline int tf_f32m_nct(int N, int blk) { const int t = (N + 15) / 16 - blk * 4; return t < 4 ? t : 4; }
+inline int tf_f32m_feature(int blk, int nct, int ct, int i) { return blk * 64 + (i >> 2) * 4 * nct + ct * 4 + (i & 3); }
+inline size_t tf_f32m_floats(int N, int K) { return (size_t)((N + 15) / 16 * 16) * tf_f32m_steps(K) * 16; }
+
+inline std::vector<float> pack_tf_f32m(const float* W, int N, int K) {
+  const int nsteps = tf_f32m_steps(K), nblk = (N + 63) / 64;
+  std::vector<float> out(tf_f32m_floats(N, K), 0.f);
+  for (int blk = 0; blk < nblk; ++blk) {
+    const int nct = tf_f32m_nct(N, blk);
+    for (int ks = 0; ks < nsteps; ++ks)
+      for (int ct = 0; ct < nct; ++ct)
+        for (int lane = 0; lane < 64; ++lane)
+          for (int s = 0; s < 4; ++s) {
+            const int n = tf_f32m_feature(blk, nct, ct, lane & 15), k = ks * 16 + 4 * (lane >> 4) + s;
+            if (n < N && k < K) out[(((size_t)blk * nsteps * 4 + (size_t)ks * nct + ct) * 64 + lane) * 4 + s] = W[(size_t)n * K + k];
+          }
+  }
+  return out;
+}
+
+// token tiles per wave of a tf_linear_f32m launch: whole rounds of `slots` workgroups (64 mp tokens x 64 features each) cost
+// 4 mp + 1 (mp steps of token loads and MFMAs per weight step, plus prologue and epilogue); ties go to the larger tile
+inline int tf_f32m_mp(int M, int N, int slots) {
+  int best = 4;
+  long best_cost = -1;
+  for (int mp = 4; mp >= 1; mp >>= 1) {
+    const long wgs = (long)((M + 64 * mp - 1) / (64 * mp)) * ((N + 63) / 64), cost = (wgs + slots - 1) / slots * (4 * mp + 1);
+    if (best_cost < 0 || cost < best_cost) { best = mp; best_cost = cost; }
+  }
+  return best;
+}
+
 }  // namespace flope_host

@@ -4,6 +4,8 @@
 //     ->  out_layer Linear(d, out);   eval-mode semantics (dropout = identity), no mask, no positions.
 // Two arithmetic modes share one launch sequence:
 //   FLOPE_DT_F32          every op in fp32 on the vector ALU (any dimensions; pins the reference's toy fixture)
+//     option f32mfma = 1  the same buffers and launches, linears with K % 4 == 0 on tf_linear_f32m and attention with
+//                         head_dim % 4 == 0 (<= 128) on tf_attn_f32m: v_mfma_f32_16x16x4_f32, exact float32, another summation order
 //   FLOPE_DT_F16 / BF16   activations in HBM as 16-bit row-major [tokens][features];
 //                         linears whose (N % 128 == 0, K % 64 == 0) run on v_mfma_f32_16x16x32 (tf_gemm_mfma),
 //                         attention with head_dim 64 runs on MFMA with the softmax in registers (tf_attn_mfma);
@@ -518,12 +520,246 @@ __global__ __launch_bounds__(1024) void tf_attn_mfma(const T* __restrict__ qkv, 
   }
 }
 
+// ---- float32 on the exact-fp32 matrix instruction (FLOPE_DT_F32 with option f32mfma = 1) ---------------------------------
+// v_mfma_f32_16x16x4_f32 takes float32 operands and accumulates in float32: every product-sum is an fmaf chain, so these kernels
+// differ from tf_linear_generic / tf_attn_generic (option 0, the checker) in summation order only.
+//
+// tf_linear_f32m: Y[M][N] = X[M][K] W^T + b (+ R) (ReLU).  Weights = A operand, 16 tokens = B operand (as conv_f32m_kernel and
+// fc1_packed_kernel).  A lane's 16-byte load is four consecutive k of its weight row / its token, element s feeds MFMA s of a
+// 16-deep step on BOTH operands.  K % 4 == 0; the last step of a K that is no multiple of 16 re-reads k = K - 4 .. K - 1 against
+// zero weights.  Weights come packed in A-fragment order (host_pack.h pack_tf_f32m): a wave's load of one (step, feature tile)
+// is one contiguous KiB.  Wave tile: MP x 16 tokens x 64 features (4 MP independent accumulator tiles); the four waves of a
+// workgroup take consecutive token tiles of one 64-feature block and share its weights through L1 / L2.  The last block of an N
+// that is no multiple of 64 has nct < 4 feature tiles: the wave computes tile nct - 1 again in their place and does not store it.
+// Operands straight from global memory, the next step's loads in flight under this step's MFMAs; no barrier, no split-K, no
+// atomics: every output is summed in one k order whatever M, MP, the grid or the batch are.
+// Epilogue: accumulators start at the bias (padded to whole blocks); a lane ends with 4 nct consecutive features of its token ->
+// residual by 16-byte loads, ReLU, 16-byte stores (element-wise where N % 4 != 0: out_layer); tokens past M are clamped in the
+// loop and masked here, features past N masked here.
+template <int MP, bool RELU, bool RES>
+__global__ __launch_bounds__(256) void tf_linear_f32m(const float* __restrict__ X, const float* __restrict__ Wp, const float* __restrict__ bp,
+                                                      const float* __restrict__ R, float* __restrict__ Y, int M, int K, int N, int nsteps) {
+  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int kq = lane >> 4, c16 = lane & 15;
+  const int nblk = (N + 63) >> 6;
+  const int mtile = blockIdx.x / nblk, blk = blockIdx.x - mtile * nblk;
+  const int m0 = (mtile * 4 + wave) * (16 * MP);
+  if (m0 >= M) return;                                     // (no barrier below)
+  const int nct = min(4, ((N + 15) >> 4) - blk * 4);
+  const float* xp[MP];
+#pragma unroll
+  for (int t = 0; t < MP; ++t) xp[t] = X + (size_t)min(m0 + t * 16 + c16, M - 1) * K;
+  const f32x4* const wb = (const f32x4*)Wp + (size_t)blk * nsteps * 256 + lane;
+  const int f0 = blk * 64 + kq * 4 * nct;
+  int cto[4];
+  f32x4 acc[MP][4];
+#pragma unroll
+  for (int ct = 0; ct < 4; ++ct) {
+    cto[ct] = min(ct, nct - 1);
+    const f32x4 b = *(const f32x4*)(bp + f0 + cto[ct] * 4);
+    cto[ct] *= 64;
+#pragma unroll
+    for (int t = 0; t < MP; ++t) acc[t][ct] = b;
+  }
+  auto load = [&](int ks, f32x4 (&x)[MP], f32x4 (&w)[4]) {
+    const int ko = min(ks * 16 + 4 * kq, K - 4);
+#pragma unroll
+    for (int t = 0; t < MP; ++t) x[t] = *(const f32x4*)(xp[t] + ko);
+    const f32x4* const ws = wb + ks * nct * 64;
+#pragma unroll
+    for (int ct = 0; ct < 4; ++ct) w[ct] = ws[cto[ct]];
+  };
+  auto mfma = [&](const f32x4 (&x)[MP], const f32x4 (&w)[4]) {
+#pragma unroll
+    for (int s = 0; s < 4; ++s)
+#pragma unroll
+      for (int t = 0; t < MP; ++t)
+#pragma unroll
+        for (int ct = 0; ct < 4; ++ct) acc[t][ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(w[ct][s], x[t][s], acc[t][ct], 0, 0, 0);
+  };
+  f32x4 xa[MP], wa[4], xb[MP], wc[4];
+  // (no load of the loop is conditional and the tail is peeled: behind a conditional load the compiler waits for every load in
+  // flight, the step just issued included -- DESIGN.md 14)
+  load(0, xa, wa);
+  int ks = 0;
+  for (; ks + 2 < nsteps; ks += 2) {
+    load(ks + 1, xb, wc);
+    __builtin_amdgcn_sched_barrier(0);
+    mfma(xa, wa);
+    __builtin_amdgcn_sched_barrier(0);
+    load(ks + 2, xa, wa);
+    __builtin_amdgcn_sched_barrier(0);
+    mfma(xb, wc);
+    __builtin_amdgcn_sched_barrier(0);
+  }
+  if (ks + 1 < nsteps) {
+    load(ks + 1, xb, wc);
+    mfma(xa, wa);
+    mfma(xb, wc);
+  } else {
+    mfma(xa, wa);
+  }
+  // lane (kq, c16): token c16 of each tile x features 64 blk + 4 nct kq + 4 ct + q
+  const bool vec = (N & 3) == 0;
+#pragma unroll
+  for (int t = 0; t < MP; ++t) {
+    const int m = m0 + t * 16 + c16;
+    if (m >= M) continue;
+#pragma unroll
+    for (int ct = 0; ct < 4; ++ct) {
+      const int f = f0 + ct * 4;
+      if (ct >= nct || f >= N) continue;
+      const size_t o = (size_t)m * N + f;
+      f32x4 v = acc[t][ct];
+      if (vec) {
+        if constexpr (RES) {
+          const f32x4 rv = *(const f32x4*)(R + o);
+          v[0] += rv[0]; v[1] += rv[1]; v[2] += rv[2]; v[3] += rv[3];
+        }
+        if constexpr (RELU) { v[0] = fmaxf(v[0], 0.f); v[1] = fmaxf(v[1], 0.f); v[2] = fmaxf(v[2], 0.f); v[3] = fmaxf(v[3], 0.f); }
+        *(f32x4*)(Y + o) = v;
+      } else {
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+          if (f + q < N) {
+            float s = v[q];
+            if constexpr (RES) s += R[o + q];
+            if constexpr (RELU) s = fmaxf(s, 0.f);
+            Y[o + q] = s;
+          }
+      }
+    }
+  }
+}
+
+// tf_attn_f32m: y32m_attn_kernel (yolo_f32.hip) for any head_dim % 4 == 0 up to 16 NT.  One workgroup = 16 queries of one
+// (sequence, head), four waves; q / k / v of head h are columns h dh, d + h dh, 2 d + h dh of the [M][3 d] row.
+//   1. scores  S^T[key][query] = K[key][:] . Q[query][:] over head_dim (A = 16 key rows, B = the 16 queries, a lane's 16-byte load
+//      = four consecutive dims, element s feeds MFMA s; dims past head_dim: the query fragment is zero and the key load re-reads
+//      its last four dims); a wave takes every fourth key tile, two at a time; x scale, into LDS as S[query][key] (row pitch
+//      Lp + 4 floats: the value pass reads it conflict-free); keys past L get -3e38;
+//   2. softmax over the keys in float32, 16 lanes per query: max, expf, sum, one division, p = e * (1 / l); keys past L get 0;
+//   3. values  O^T[dim][query] = V^T[dim][key] . P^T[key][query] (A = 16 dims of V for 4 keys, B = P from LDS; a wave takes every
+//      fourth group of 4 keys; the waves' partial sums are added in wave order through LDS).
+// Nothing depends on the sequence's position in the batch.  LDS: 16 (Lp + 4) + 3 NT 256 floats, at most kTfAttnLds.
+constexpr size_t kTfAttnLds = 160 * 1024;
+template <int NT>
+__global__ __launch_bounds__(256) void tf_attn_f32m(const float* __restrict__ qkv, float* __restrict__ out, int L, int d, int H, float scale) {
+  extern __shared__ __attribute__((aligned(16))) float Sm[];      // [16][pitch] scores / probabilities | [3][NT][64][4] partial outputs
+  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int kq = lane >> 4, c16 = lane & 15;
+  const int b = blockIdx.x / H, h = blockIdx.x - b * H, dh = d / H, q0 = blockIdx.y * 16;
+  const int Lp = (L + 15) & ~15, pitch = Lp + 4, ld = 3 * d;
+  const float* const base = qkv + (size_t)b * L * ld + h * dh;
+  float* const red = Sm + 16 * pitch;
+  // 1. scores
+  {
+    f32x4 qf[NT];
+    int dimc[NT];
+    const float* qp = base + (size_t)min(q0 + c16, L - 1) * ld;
+#pragma unroll
+    for (int st = 0; st < NT; ++st) {
+      const int dim = st * 16 + 4 * kq;
+      dimc[st] = min(dim, dh - 4);
+      const f32x4 v = *(const f32x4*)(qp + dimc[st]);
+      qf[st] = dim < dh ? v : f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+    const int ntile = Lp >> 4;
+    for (int kt = wave; kt < ntile; kt += 8) {
+      const int kt1 = kt + 4;
+      const float* kp0 = base + (size_t)min(kt * 16 + c16, L - 1) * ld + d;
+      const float* kp1 = base + (size_t)min(kt1 * 16 + c16, L - 1) * ld + d;
+      f32x4 k0[NT], k1[NT];
+#pragma unroll
+      for (int st = 0; st < NT; ++st) { k0[st] = *(const f32x4*)(kp0 + dimc[st]); k1[st] = *(const f32x4*)(kp1 + dimc[st]); }
+      f32x4 d0 = {0.f, 0.f, 0.f, 0.f}, d1 = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int st = 0; st < NT; ++st)
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {
+          d0 = __builtin_amdgcn_mfma_f32_16x16x4f32(k0[st][s], qf[st][s], d0, 0, 0, 0);
+          d1 = __builtin_amdgcn_mfma_f32_16x16x4f32(k1[st][s], qf[st][s], d1, 0, 0, 0);
+        }
+      // lane (kq, c16): keys tile * 16 + 4 kq + r of query c16
+      f32x4 o;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) o[r] = kt * 16 + 4 * kq + r < L ? d0[r] * scale : -3.0e38f;
+      *(f32x4*)(Sm + c16 * pitch + kt * 16 + 4 * kq) = o;
+      if (kt1 < ntile) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) o[r] = kt1 * 16 + 4 * kq + r < L ? d1[r] * scale : -3.0e38f;
+        *(f32x4*)(Sm + c16 * pitch + kt1 * 16 + 4 * kq) = o;
+      }
+    }
+  }
+  __syncthreads();
+  // 2. softmax (thread = query tid >> 4, keys tid & 15, + 16, ...)
+  {
+    const int kl = tid & 15;
+    float* Sq = Sm + (tid >> 4) * pitch;
+    float mx = -3.0e38f;
+    for (int j = kl; j < L; j += 16) mx = fmaxf(mx, Sq[j]);
+#pragma unroll
+    for (int o = 8; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 16));
+    float l = 0.f;
+    for (int j = kl; j < L; j += 16) { const float e = expf(Sq[j] - mx); Sq[j] = e; l += e; }
+#pragma unroll
+    for (int o = 8; o > 0; o >>= 1) l += __shfl_xor(l, o, 16);
+    const float inv = 1.f / l;
+    for (int j = kl; j < Lp; j += 16) Sq[j] = j < L ? Sq[j] * inv : 0.f;
+  }
+  __syncthreads();
+  // 3. values: group g covers keys 4 g .. 4 g + 3; lane (kq, c16): A = V[4 g + kq][ct * 16 + c16], B = P[query c16][4 g + kq]
+  f32x4 acc[NT];
+  int dimv[NT];
+#pragma unroll
+  for (int ct = 0; ct < NT; ++ct) { acc[ct] = f32x4{0.f, 0.f, 0.f, 0.f}; dimv[ct] = min(ct * 16 + c16, dh - 1); }
+  const int ng = Lp >> 2;
+  const float* const vb = base + 2 * d;
+  for (int g0 = wave; g0 < ng; g0 += 16) {                 // four groups of this wave per trip
+    float av[4][NT], bv[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const int g = g0 + 4 * u, key = min(4 * g + kq, L - 1);
+      bv[u] = g < ng ? Sm[c16 * pitch + 4 * g + kq] : 0.f;
+#pragma unroll
+      for (int ct = 0; ct < NT; ++ct) av[u][ct] = vb[(size_t)key * ld + dimv[ct]];
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u)
+#pragma unroll
+      for (int ct = 0; ct < NT; ++ct) acc[ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[u][ct], bv[u], acc[ct], 0, 0, 0);
+  }
+  if (wave > 0) {
+#pragma unroll
+    for (int ct = 0; ct < NT; ++ct) *(f32x4*)(red + (((wave - 1) * NT + ct) * 64 + lane) * 4) = acc[ct];
+  }
+  __syncthreads();
+  if (wave > 0) return;
+#pragma unroll
+  for (int w = 0; w < 3; ++w)
+#pragma unroll
+    for (int ct = 0; ct < NT; ++ct) {
+      const f32x4 r = *(const f32x4*)(red + ((w * NT + ct) * 64 + lane) * 4);
+#pragma unroll
+      for (int q = 0; q < 4; ++q) acc[ct][q] += r[q];
+    }
+  // lane (kq, c16): query c16, dims ct * 16 + 4 kq + r
+  if (q0 + c16 < L) {
+    float* o = out + ((size_t)b * L + q0 + c16) * d + h * dh + 4 * kq;
+#pragma unroll
+    for (int ct = 0; ct < NT; ++ct)
+      if (ct * 16 + 4 * kq < dh) *(f32x4*)(o + ct * 16) = acc[ct];
+  }
+}
+
 }  // namespace
 
 // ---- handle ----------------------------------------------------------------------------------------------------
 struct TfLinear {
   float* w = nullptr; float* b = nullptr;   // fp32 [N][K], [N]
   void* packed = nullptr;                    // MFMA image (16-bit) when eligible
+  float* pk32 = nullptr; float* bpad = nullptr;   // FLOPE_DT_F32, K % 4 == 0: pack_tf_f32m image and the bias padded to whole 64-feature blocks
   int N = 0, K = 0, Kp = 0;                  // Kp: K rounded up to 64 (the packed image's K)
 };
 struct TfLayer { TfLinear in_proj, out_proj, lin1, lin2; float *n1w = nullptr, *n1b = nullptr, *n2w = nullptr, *n2b = nullptr; };
@@ -531,6 +767,9 @@ struct TfLayer { TfLinear in_proj, out_proj, lin1, lin2; float *n1w = nullptr, *
 struct flope_tf_encoder {
   int device = 0, in_dim = 0, d = 0, out_dim = 0, H = 0, nl = 0, ff = 0, max_tokens = 0, Mpad = 0, dtype = 0, esz = 2;
   int opt_generic = 0;                       // 1: force the generic kernels (A/B checks)
+  int opt_f32m = 0;                          // 1: FLOPE_DT_F32 linears and attention on v_mfma_f32_16x16x4_f32 where eligible (stored and ignored by 16-bit handles)
+  int opt_f32m_lds = 0;                      // KiB of untouched LDS a tf_linear_f32m launch reserves (> 80: one workgroup per CU)
+  int cus = 256;
   bool loaded = false;
   TfLinear emb, outl;
   std::vector<TfLayer> layers;
@@ -585,6 +824,22 @@ template <typename V> int tf_upload(flope_tf_encoder* e, const V* src, size_t co
 template <typename T>
 int launch_linear(flope_tf_encoder* e, const TfLinear& l, const void* X, int x_f32, const void* R, void* Y, int y_f32,
                   int M, int relu, hipStream_t st) {
+  if constexpr (std::is_same<T, float>::value) {
+    if (e->opt_f32m && l.pk32 && !(((uintptr_t)X | (uintptr_t)Y | (uintptr_t)R) & 15)) {
+      const size_t lds = (size_t)e->opt_f32m_lds * 1024;
+      const int mp = tf_f32m_mp(M, l.N, e->cus * (lds > 80 * 1024 ? 1 : 2)), nsteps = tf_f32m_steps(l.K);
+      const dim3 grid((unsigned)((M + 64 * mp - 1) / (64 * mp) * ((l.N + 63) / 64)));
+#define TF_GO3(MP_, RELU_, RES_)                                                                                       \
+  hipLaunchKernelGGL((tf_linear_f32m<MP_, RELU_, RES_>), grid, dim3(256), lds, st, (const float*)X, l.pk32, l.bpad, \
+                     (const float*)R, (float*)Y, M, l.K, l.N, nsteps)
+#define TF_GO2(MP_) do { if (relu && !R) TF_GO3(MP_, true, false); else if (R && !relu) TF_GO3(MP_, false, true); else if (!R) TF_GO3(MP_, false, false); else return tf_fail(e, FLOPE_EINVAL, "tf_linear_f32m: no ReLU + residual form"); } while (0)
+      if (mp == 4) TF_GO2(4); else if (mp == 2) TF_GO2(2); else TF_GO2(1);
+#undef TF_GO2
+#undef TF_GO3
+      TF_HIP(e, hipGetLastError());
+      return 0;
+    }
+  }
   if (l.packed && !y_f32 && !e->opt_generic) {
     if constexpr (!std::is_same<T, float>::value) {
       if (x_f32) {                                   // network input: fp32 [M][K] -> 16-bit [M][Kp]
@@ -638,6 +893,18 @@ int run_forward(flope_tf_encoder* e, const float* x, int B, int L, float* y, hip
         fast_attn = true;
         hipLaunchKernelGGL((tf_attn_mfma<T>), dim3(B * e->H), dim3(Lp / 32 * 64), (size_t)Lp * 256, st, (const T*)e->qkv,
                            (T*)e->att, L, d, e->H, Lp, 1.4426950408889634f / sqrtf(64.f));
+      }
+    }
+    if constexpr (std::is_same<T, float>::value) {
+      const int dh = d / e->H, nt = dh <= 16 ? 1 : dh <= 32 ? 2 : dh <= 64 ? 4 : 8;       // 16-wide tiles of head_dim the kernel is built for
+      const size_t lds = ((size_t)16 * (((L + 15) & ~15) + 4) + (size_t)3 * nt * 256) * sizeof(float);
+      if (e->opt_f32m && dh % 4 == 0 && dh <= 128 && lds <= kTfAttnLds) {
+        fast_attn = true;
+        const dim3 grid(B * e->H, (L + 15) / 16);
+        const float scale = 1.f / sqrtf((float)dh);
+#define TF_ATT(NT_) hipLaunchKernelGGL((tf_attn_f32m<NT_>), grid, dim3(256), lds, st, (const float*)e->qkv, (float*)e->att, L, d, e->H, scale)
+        if (nt == 1) TF_ATT(1); else if (nt == 2) TF_ATT(2); else if (nt == 4) TF_ATT(4); else TF_ATT(8);
+#undef TF_ATT
       }
     }
     if (!fast_attn) {
@@ -706,6 +973,14 @@ extern "C" int flope_tf_create(int device_id, int input_dim, int model_dim, int 
     TF_ATTR(f16_t, false, false); TF_ATTR(f16_t, false, true); TF_ATTR(f16_t, true, false); TF_ATTR(f16_t, true, true);
     TF_ATTR(bf16_t, false, false); TF_ATTR(bf16_t, false, true); TF_ATTR(bf16_t, true, false); TF_ATTR(bf16_t, true, true);
 #undef TF_ATTR
+    const void* const f32m[] = {(const void*)tf_linear_f32m<4, false, false>, (const void*)tf_linear_f32m<4, true, false>, (const void*)tf_linear_f32m<4, false, true>,
+                                (const void*)tf_linear_f32m<2, false, false>, (const void*)tf_linear_f32m<2, true, false>, (const void*)tf_linear_f32m<2, false, true>,
+                                (const void*)tf_linear_f32m<1, false, false>, (const void*)tf_linear_f32m<1, true, false>, (const void*)tf_linear_f32m<1, false, true>,
+                                (const void*)tf_attn_f32m<1>, (const void*)tf_attn_f32m<2>, (const void*)tf_attn_f32m<4>, (const void*)tf_attn_f32m<8>};
+    for (const void* f : f32m)
+      if (hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kTfAttnLds) != hipSuccess)
+        return fin(tf_fail(nullptr, FLOPE_EHIP, "flope_tf_create: hipFuncSetAttribute failed"));
+    if (hipDeviceGetAttribute(&e->cus, hipDeviceAttributeMultiprocessorCount, device_id) != hipSuccess || e->cus < 1) e->cus = 256;
   }
   *out = e;
   return FLOPE_OK;
@@ -722,6 +997,11 @@ extern "C" int flope_tf_destroy(flope_tf_handle e) {
 extern "C" int flope_tf_set_option(flope_tf_handle e, const char* name, int value) {
   if (!e || !name) return FLOPE_EINVAL;
   if (!strcmp(name, "generic")) { const int old = e->opt_generic; e->opt_generic = value ? 1 : 0; return old; }
+  if (!strcmp(name, "f32mfma")) { const int old = e->opt_f32m; e->opt_f32m = value ? 1 : 0; return old; }
+  if (!strcmp(name, "f32mlds")) {
+    if (value < 0 || value > 160) return tf_fail(e, FLOPE_EINVAL, "flope_tf_set_option: f32mlds is 0 .. 160 (KiB)");
+    const int old = e->opt_f32m_lds; e->opt_f32m_lds = value; return old;
+  }
   return tf_fail(e, FLOPE_EINVAL, std::string("flope_tf_set_option: unknown option ") + name);
 }
 
@@ -760,6 +1040,12 @@ extern "C" int flope_tf_load_weights(flope_tf_handle e, int n, const char* const
     if (e->dtype != FLOPE_DT_F32 && N % 128 == 0 && (K % 64 == 0 || l == &e->emb)) {
       const std::vector<uint16_t> pk = pack_linear(w, N, K, e->dtype);
       if ((rc = tf_upload(e, pk.data(), pk.size(), &l->packed))) return rc;
+    }
+    if (e->dtype == FLOPE_DT_F32 && K % 4 == 0) {      // both images: option f32mfma flips between forwards without a reload
+      const std::vector<float> pk = pack_tf_f32m(w, N, K);
+      std::vector<float> bp((size_t)(N + 63) / 64 * 64, 0.f);
+      memcpy(bp.data(), b, (size_t)N * sizeof(float));
+      if ((rc = tf_upload(e, pk.data(), pk.size(), (void**)&l->pk32)) || (rc = tf_upload(e, bp.data(), bp.size(), (void**)&l->bpad))) return rc;
     }
     return 0;
   };

@@ -44,6 +44,11 @@ class TransformerEncoder:
         if rc:
             msg = self.lib.flope_tf_last_error(None)
             raise RuntimeError(f"flope_tf_create failed ({rc}): {msg.decode() if msg else ''}")
+        if dtype == "f32m":                      # a FLOPE_DT_F32 handle with the linears and attention on the exact-fp32 MFMA
+            rc = self.lib.flope_tf_set_option(self.handle, b"f32mfma", 1)
+            if rc < 0:
+                self.close()
+                raise RuntimeError(f"flope_tf_set_option(f32mfma) failed ({rc})")
 
     def _check(self, rc):
         if rc:

@@ -280,6 +280,10 @@ int flope_frame_read_gaps(flope_frame_handle f, int slot, float* gap_host, int c
  * dtype FLOPE_DT_F32: fp32 everywhere (any dimensions).  FLOPE_DT_F16 / BF16: 16-bit activations,
  * fp32 accumulation; linears with N % 128 == 0 and K % 64 == 0 and attention with head_dim 64
  * (seq_len <= 512) run on MFMA, everything else on generic kernels.
+ * FLOPE_DT_F32 with flope_tf_set_option(h, "f32mfma", 1): the same float32 buffers and launch sequence, every linear with
+ * K % 4 == 0 and every attention with head_dim % 4 == 0, head_dim <= 128 and 16 score rows of seq_len floats within 160 KiB of LDS
+ * on v_mfma_f32_16x16x4_f32 (exact float32 products and sums: differs from the strict mode in summation order only); the other
+ * ops of the handle stay on the generic kernels, LayerNorm is unchanged.
  * max_tokens bounds batch*seq_len of any later forward.  Same ownership / error rules as above. */
 typedef struct flope_tf_encoder* flope_tf_handle;
 int flope_tf_create(int device_id, int input_dim, int model_dim, int out_dim, int num_heads,
@@ -295,7 +299,13 @@ int flope_tf_load_weights(flope_tf_handle h, int n, const char* const* names,
 /* x_dev float32 [batch, seq_len, input_dim] -> y_dev float32 [batch, seq_len, out_dim] */
 int flope_tf_forward(flope_tf_handle h, const float* x_dev, int batch, int seq_len, float* y_dev,
                      void* stream);
-/* "generic" = 1 forces the generic kernels (A/B checks); returns previous value or <0 */
+/* returns the previous value, or <0 (FLOPE_EINVAL for an unknown name)
+ *   "generic" (default 0): 1 forces the generic kernels on 16-bit handles (A/B checks);
+ *   "f32mfma" (default 0): FLOPE_DT_F32 handles run every eligible linear and attention on the exact-fp32 MFMA kernels
+ *       (tf_linear_f32m, tf_attn_f32m) instead of the generic ones; may be flipped between forwards (flope_tf_load_weights on a
+ *       float32 handle uploads both weight images).  Stored and ignored by FLOPE_DT_F16 / BF16 handles;
+ *   "f32mlds" (default 0; 0 .. 160): KiB of untouched LDS every tf_linear_f32m launch reserves; more than 80 leaves one
+ *       workgroup per CU (measurement knob: DESIGN.md 16). */
 int flope_tf_set_option(flope_tf_handle h, const char* name, int value);
 /* algorithmic FLOPs of one forward (2*MAC: linears + QK^T + PV) */
 double flope_tf_forward_flops(flope_tf_handle h, int batch, int seq_len);
