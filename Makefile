@@ -7,6 +7,7 @@ OBJDIR   := build/obj
 LIB      := flope_amd/lib/libflope_amd.so
 HARNESS  := tests/host_harness/libflope_host_harness.so
 HARNESS_F32M := tests/host_harness/libflope_host_f32m.so
+HARNESS_F32M_KSPLIT := tests/host_harness/libflope_host_f32m_ksplit.so
 HARNESS_GUARD := tests/host_harness/libflope_host_guard.so
 HARNESS_TF_F32M := tests/host_harness/libflope_host_tf_f32m.so
 SRCS     := $(wildcard $(CSRC)/*.hip)
@@ -14,7 +15,7 @@ OBJS     := $(patsubst $(CSRC)/%.hip,$(OBJDIR)/%.o,$(SRCS))
 HDRS     := $(wildcard $(CSRC)/*.h) include/flope_amd.h
 HIPFLAGS := --offload-arch=$(ARCH) -O3 -fPIC -std=c++17 -Wno-unused-value -Iinclude
 
-all: $(LIB) $(HARNESS) $(HARNESS_F32M) $(HARNESS_GUARD) $(HARNESS_TF_F32M)
+all: $(LIB) $(HARNESS) $(HARNESS_F32M) $(HARNESS_F32M_KSPLIT) $(HARNESS_GUARD) $(HARNESS_TF_F32M)
 
 $(OBJDIR)/%.o: $(CSRC)/%.hip $(HDRS)
 	@mkdir -p $(OBJDIR)
@@ -30,6 +31,11 @@ $(HARNESS): tests/host_harness/harness.cpp $(CSRC)/pose_math.h $(CSRC)/host_pack
 # packers and operand feed of the float32 MFMA trunk (tests/test_f32m_host.py)
 $(HARNESS_F32M): tests/host_harness/harness_f32m.cpp $(CSRC)/host_pack.h $(CSRC)/w4_sched.h $(CSRC)/plan.h
 	g++ -O2 -fPIC -shared -std=c++17 -I$(CSRC) -o $@ $<
+
+# planner helpers and the split launch + finalize walk of the float32 MFMA trunk's split-K form (tests/test_f32m_ksplit_host.py,
+# tests/test_gpu_f32m_ksplit.py); linked with harness_f32m.cpp, whose walk is the S = 1 case
+$(HARNESS_F32M_KSPLIT): tests/host_harness/harness_f32m_ksplit.cpp tests/host_harness/harness_f32m.cpp $(CSRC)/host_pack.h $(CSRC)/w4_sched.h $(CSRC)/plan.h
+	g++ -O2 -fPIC -shared -std=c++17 -I$(CSRC) -o $@ tests/host_harness/harness_f32m_ksplit.cpp tests/host_harness/harness_f32m.cpp
 
 # packer and operand feed of the float32 MFMA encoder linear (tests/test_tf_f32m_host.py, tests/test_gpu_tf_f32m.py)
 $(HARNESS_TF_F32M): tests/host_harness/harness_tf_f32m.cpp $(CSRC)/host_pack.h
@@ -60,7 +66,7 @@ dbg: $(DBGOBJS)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $(DBGDIR)/libflope_amd_dbg.so $(DBGOBJS)
 
 clean:
-	rm -rf build $(LIB) $(HARNESS) $(HARNESS_F32M) $(HARNESS_GUARD) $(HARNESS_TF_F32M)
+	rm -rf build $(LIB) $(HARNESS) $(HARNESS_F32M) $(HARNESS_F32M_KSPLIT) $(HARNESS_GUARD) $(HARNESS_TF_F32M)
 
 # stand-alone measurement programs used by tools/collect_profiles.sh and DESIGN.md section 9 (not part of the library)
 TOOLBINS := build/fetch_calib build/launch_floor build/loop_probe build/loop_probe32 build/dma_issue_probe

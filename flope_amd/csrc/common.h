@@ -205,6 +205,10 @@ struct F32mConvP {     // float32 implicit GEMM on the exact-fp32 MFMA (conv_f32
   int nsteps;          // 16-deep K steps: KH*KW*Cin/16 (Cin % 16 == 0), stem: ceil(KH*KW / 4) taps of 4 stored channels
   int csteps;          // K steps per tap (Cin / 16; unused by the stem)
   unsigned mg_hw, sh_hw, mg_w, sh_w;   // n / (Ho*Wo) and n / Wo as multiply-shift
+  // split-K (plan.h f32m_ksplit): workgroup blockIdx.x handles tile blockIdx.x / ksplit and share blockIdx.x % ksplit of the K steps
+  // and stores raw partial sums to split_ws[share][M][Cout]; conv_f32m_finalize_kernel owns bias / residual / ReLU.  <= 1: off.
+  int ksplit;
+  float* split_ws;
 };
 
 // ---------------------------------------------------------------------------

@@ -33,7 +33,7 @@ extern "C" int flope_prep_input_launch(const void* x, int in_format, int B, int 
 extern "C" int flope_read_stage_launch(const void* in, float* out, int B, int C, int h, int w, int dtype, void* stream);
 extern "C" int flope_naive_conv_launch(const NaiveConvP* p, void* stream);
 extern "C" int flope_conv_f32m_init();
-extern "C" int flope_conv_f32m_launch(const F32mConvP* p, int mp, int stem, int grid, size_t lds, void* stream);
+extern "C" int flope_conv_f32m_launch(const F32mConvP* p, int mp, int stem, int grid, size_t lds, size_t ws_bytes, void* stream);
 extern "C" int flope_conv_stag_init();
 extern "C" int flope_conv_gstag_init();
 extern "C" int flope_conv_w4_init();
@@ -388,6 +388,9 @@ extern "C" int flope_create(int device_id, int height, int width, int max_batch,
     CREATE_TRY(hipMalloc((void**)&e->split_ws, e->split_ws_bytes));
     CREATE_TRY(hipMalloc((void**)&e->stem_q, 4 * 1024 * sizeof(int)));
     CREATE_TRY(hipMemset(e->stem_q, 0, 4 * 1024 * sizeof(int)));
+  } else {                              // conv_f32m split-K partials (option f32m_ksplit): one round of the largest tile, plan.h
+    e->split_ws_bytes = f32m_ws_bytes(e->num_cus);
+    CREATE_TRY(hipMalloc((void**)&e->split_ws, e->split_ws_bytes));
   }
   for (int i = 0; i < 4; ++i) {
     CREATE_TRY(hipStreamCreateWithFlags(&e->side[i], hipStreamNonBlocking));
@@ -433,6 +436,8 @@ extern "C" int flope_debug_read_ws(flope_handle e, void* dst_host, size_t offset
 // the options, their clamps and which of them the static plan depends on: plan.h (option_table)
 //   f32mfma (float32 engines; stored and ignored by the 16-bit ones): 1 = the stem and the 19 trunk convs run on conv_f32m_kernel
 //   (exact-fp32 MFMA), 0 (default) = on naive_conv_kernel.  Both weight images are resident, so it may be flipped between forwards.
+//   f32m_ksplit (float32 engines with f32mfma = 1; stored and ignored otherwise): split-K of conv_f32m for small batches, 0 (default)
+//   = off, 1 = per launch by plan.h's cost model, 2..32 = that many shares wherever a split is allowed.  May be flipped between forwards.
 extern "C" int flope_set_option(flope_handle e, const char* name, int value) {
   if (!e || !name) return fail(e, FLOPE_EINVAL, "flope_set_option: NULL argument");
   const OptionDef* d = find_option(name);
@@ -566,7 +571,7 @@ static int run_slice(flope_engine* e, const void* x_dev, int in_format, int star
       fastdiv_magic((unsigned)(pl.Hs * pl.Ws), &p.mg_hw, &p.sh_hw);
       fastdiv_magic((unsigned)pl.Ws, &p.mg_w, &p.sh_w);
       SMARK();
-      K_TRY(e, "stem (fp32 MFMA)", flope_conv_f32m_launch(&p, L.mt, 1, L.grid, L.lds_bytes, stream));
+      K_TRY(e, "stem (fp32 MFMA)", flope_conv_f32m_launch(&p, L.mt, 1, L.grid, L.lds_bytes, 0, stream));
     } else if (dt == FLOPE_DT_F32) {
       NaiveConvP p; memset(&p, 0, sizeof(p));
       p.in = (const float*)stem_in; p.out = (float*)stem_out; p.w = e->stem_w_naive; p.bias = e->stem_bias;
@@ -617,7 +622,8 @@ static int run_slice(flope_engine* e, const void* x_dev, int in_format, int star
         q.M = batch * s.hout * s.wout; q.csteps = s.cin / 16; q.nsteps = f32m_steps(s.cin, s.k);
         fastdiv_magic((unsigned)(s.hout * s.wout), &q.mg_hw, &q.sh_hw);
         fastdiv_magic((unsigned)s.wout, &q.mg_w, &q.sh_w);
-        K_TRY(e, conv_name(s).c_str(), flope_conv_f32m_launch(&q, L.mt, 0, L.grid, L.lds_bytes, stream));
+        if (L.ksplit > 1) { q.ksplit = L.ksplit; q.split_ws = e->split_ws; }   // split launch + finalize (which owns bias / residual / ReLU)
+        K_TRY(e, conv_name(s).c_str(), flope_conv_f32m_launch(&q, L.mt, 0, L.grid, L.lds_bytes, e->split_ws_bytes, stream));
         break;
       }
       case kGstag: K_TRY(e, conv_name(s).c_str(), flope_conv_gstag_launch(&p, dt, stream)); break;

@@ -60,6 +60,7 @@ struct PlanOptions {
   int dbg = 0;           // diagnostic builds: ablation bits, 64 / 128 = clock stamps
   int nbuf = 2;          // conv_mfma ring depth asked for (3 where the weight tile is 16 KB per step)
   int f32mfma = 0;       // FLOPE_DT_F32 only: 1 = stem and trunk convs on the exact-fp32 MFMA (conv_f32m.hip), 0 = naive_conv_kernel (the checker)
+  int f32m_ksplit = 0;   // FLOPE_DT_F32 with f32mfma = 1 only: 0 = off, 1 = split-K per launch by the cost model of f32m_ksplit(), 2..32 = force that share count (rounded down to 2 / 4 / 8 / 16 / 32) wherever a split is allowed
   int profile = 0;       // 1: one slice, an event around every launch (flope_profile_read); 2: the slices as in production, events on every slice's stream (flope_profile_timeline)
 };
 
@@ -105,6 +106,7 @@ inline const std::vector<OptionDef>& option_table() {
       {"nbuf", &O::nbuf, kNbuf, 2, 3, true},
       {"profile", &O::profile, kClamp, 0, 2, false},
       {"f32mfma", &O::f32mfma, kBool, 0, 1, false},
+      {"f32m_ksplit", &O::f32m_ksplit, kClamp, 0, 32, false},
   };
   return t;
 }
@@ -454,6 +456,45 @@ inline void f32m_launch(Launch& L, int M, int cout, int cus) {
   L.mtiles = (M + 64 * L.mt - 1) / (64 * L.mt); L.ntiles = cout / 64;
   L.total_tiles = L.grid = L.mtiles * L.ntiles;
 }
+
+// ---- split-K of conv_f32m (option f32m_ksplit) ----
+// A conv_f32m workgroup walks all n = K / 16 steps of its tile alone, so at small batches a launch is a few workgroups that each
+// run 36 .. 288 serial steps on an otherwise idle chip.  A split launch gives every tile S workgroups; workgroup `share` walks the
+// steps [f32m_share_begin(n, S, share), f32m_share_begin(n, S, share + 1)) from +0 and stores raw partial sums, and a second,
+// ordered launch (conv_f32m_finalize_kernel) adds bias + share 0 + share 1 + ... in that order, the residual, ReLU.
+// THE partition formula: the engine, the kernel's host-side guard and the host walk of tests/host_harness all use this one.
+constexpr int f32m_share_begin(int nsteps, int S, int share) { return (int)((long)share * nsteps / S); }
+constexpr int kF32mMinShareSteps = 4;        // every share walks at least this many steps (the 4-step 1x1 shortcut of layer 2 never splits)
+constexpr int kF32mMaxSplit = 32;
+// the partial sums of one split launch: at most one round of the chip (total_tiles * S <= cus) of the largest tile (256 pixels x
+// 64 channels), 16 MiB at 256 CUs -- S * M * Cout <= total_tiles * S * (64 mp) * 64 fits by that rule
+inline size_t f32m_ws_bytes(int cus) { return (size_t)cus * 256 * 64 * sizeof(float); }
+// Cost model of option value 1, in shader-clock cycles at the 2.4 GHz maximum clock: a share's serial K loop + the finalize launch
+// where S > 1, fitted to the per-launch table of tools/bench_f32m_ksplit.py --per-launch (profiles/f32m_ksplit_per_launch.txt,
+// DESIGN.md 17; one MI355X, profile = 1, B = 1 x 224^2, MP = 1):
+//   kF32mStepCycles = 655 per pixel tile of the wave: unsplit launches of n = 36 / 72 / 144 / 288 steps take 15.5 / 25.5 / 45 / 84.6 us
+//     = 6 us (what a 4-step launch costs as well) + 0.273 us per step -- 1.28 x the 512 cycles of 16 back-to-back MFMAs
+//   finalize = kF32mFinalizeCycles + S kF32mFinalizeShareCycles = 4300 + 720 S (1.8 us + 0.3 us per share): what a split launch of
+//     S = 2 / 4 / 8 / 16 / 32 shares of layer 4 (n = 288) takes beyond 6 us + 0.273 us ceil(n / S): 2.5 / 3.2 / 4.1 / 6.3 / 11.1 us;
+//     layer 3 (n = 144) gives 2.2 / 3.0 / 4.4 / 7.1.  The per-share term (finalize reads S partial sums per output, one after the
+//     other) is why x32 measured SLOWER than x16 there; the first, derived model (512 cycles, one 4 us launch) picked x32.
+constexpr long kF32mStepCycles = 655, kF32mFinalizeCycles = 4300, kF32mFinalizeShareCycles = 720;
+// S for a conv_f32m launch of total_tiles workgroups of mp pixel tiles per wave and nsteps K steps; option as PlanOptions::f32m_ksplit.
+// A split is allowed when (a) the batch runs in one slice (one workspace per engine), (b) total_tiles * S <= cus (at most one
+// round) and (c) every share has >= kF32mMinShareSteps steps.  Returns 1 where none is allowed or none pays.
+inline int f32m_ksplit(int option, int total_tiles, int mp, int nsteps, int plan_slices, int cus) {
+  if (option <= 0 || plan_slices != 1) return 1;
+  int best = 1;
+  long best_cost = (long)nsteps * kF32mStepCycles * mp;
+  for (int S = 2; S <= kF32mMaxSplit; S *= 2) {
+    if ((long)total_tiles * S > cus || nsteps / S < kF32mMinShareSteps) break;
+    if (option >= 2) { if (S <= option) best = S; continue; }
+    const long cost = (long)((nsteps + S - 1) / S) * kF32mStepCycles * mp + kF32mFinalizeCycles + S * kF32mFinalizeShareCycles;
+    if (cost < best_cost) { best_cost = cost; best = S; }
+  }
+  return best;
+}
+
 inline Launch f32m_stem_launch(const Plan& pl, const SliceCtx& x) {
   Launch L;
   f32m_launch(L, x.batch * pl.Hs * pl.Ws, 64, x.num_cus);
@@ -480,7 +521,14 @@ inline Launch decide(const PlanOptions& o, const Plan& pl, int i, const SliceCtx
   L.ntiles = c.ntiles; L.patch_rounds = c.rows_max; L.dbg = o.dbg;
   L.total_tiles = L.grid = L.mtiles * L.ntiles;
   L.cfg = c.cfg; L.patch = c.patch; L.nbuf = c.nbuf;
-  if (pl.dtype == FLOPE_DT_F32 && o.f32mfma) { f32m_launch(L, M, s.cout, cus); return L; }
+  if (pl.dtype == FLOPE_DT_F32 && o.f32mfma) {
+    f32m_launch(L, M, s.cout, cus);
+    if (o.f32m_ksplit) {                             // (the stem, 13 steps, has its own launch and is never split)
+      L.ksplit = f32m_ksplit(o.f32m_ksplit, L.total_tiles, L.mt, s.k * s.k * s.cin / 16, x.plan_slices, cus);
+      L.grid = L.total_tiles * L.ksplit;
+    }
+    return L;
+  }
   if (pl.dtype == FLOPE_DT_F32) { L.family = kNaive; return L; }
   ConvDims d = conv_dims(pl, i);
   if (c.stag == 3) {

@@ -12,8 +12,9 @@ import torch
 from . import _lib
 from .weights import validate_state_dict
 
-# "f32" is the strict checker (naive_conv_kernel); "f32m" is the same float32 engine with option f32mfma = 1 (exact-fp32 MFMA trunk)
-_DTYPES = {"bf16": _lib.DT_BF16, "f16": _lib.DT_F16, "f32": _lib.DT_F32, "f32m": _lib.DT_F32,
+# "f32" is the strict checker (naive_conv_kernel); "f32m" is the same float32 engine with option f32mfma = 1 (exact-fp32 MFMA trunk);
+# "f32mk" is "f32m" with option f32m_ksplit = 1 (split-K for small batches: a crop's bits then depend on the batch size)
+_DTYPES = {"bf16": _lib.DT_BF16, "f16": _lib.DT_F16, "f32": _lib.DT_F32, "f32m": _lib.DT_F32, "f32mk": _lib.DT_F32,
            torch.bfloat16: _lib.DT_BF16, torch.float16: _lib.DT_F16, torch.float32: _lib.DT_F32}
 
 STAGES = {"stem": _lib.STAGE_STEM, "pool": _lib.STAGE_POOL, "feat": _lib.STAGE_FEAT,
@@ -65,8 +66,10 @@ class PoseEngine:
         _lib.check(rc)
         self.handle = h
         self._keep = None
-        if dtype == "f32m":
+        if dtype in ("f32m", "f32mk"):
             self.set_option("f32mfma", 1)
+        if dtype == "f32mk":
+            self.set_option("f32m_ksplit", 1)
 
     def close(self):
         if getattr(self, "handle", None):
@@ -277,18 +280,20 @@ class PoseEngine:
 
 class GuardedPoseEngine:
     """The guarded mode (include/flope_amd.h flope_guard_*): a PoseEngine("f16") for the whole batch, the
-    device's own conditioning figure gap(M) per crop, and a PoseEngine("f32m") that runs again only the crops with
-    !(gap >= gap_min) and overwrites their rows.  Same hot-path interface as PoseEngine; `last_gap` (float32 [B] on the device)
+    device's own conditioning figure gap(M) per crop, and a PoseEngine(exact_dtype) -- "f32m", or "f32mk" for its split-K form,
+    which is what a repair of a few crops wants -- that runs again only the crops with !(gap >= gap_min) and overwrites their rows.  Same hot-path interface as PoseEngine; `last_gap` (float32 [B] on the device)
     and `last_repaired` describe the most recent forward."""
 
     SLOTS = 16                                       # forwards that may await their repair at once (per slot: 40 bytes per crop)
 
     def __init__(self, height: int, width: int, max_batch: int, max_repair: int = 32, device=None,
-                 backbone_out_dim: int = 2048, gap_min: float = 0.5, slots: int = SLOTS):
+                 backbone_out_dim: int = 2048, gap_min: float = 0.5, slots: int = SLOTS, exact_dtype: str = "f32m"):
         _require_gpu()
+        if exact_dtype not in ("f32m", "f32mk"):
+            raise ValueError(f"exact_dtype must be 'f32m' or 'f32mk', got {exact_dtype!r}")
         self.fast = PoseEngine(height, width, max_batch, "f16", device, backbone_out_dim)
         self.max_repair = max(1, min(int(max_repair), int(max_batch)))
-        self.exact = PoseEngine(height, width, self.max_repair, "f32m", self.fast.device, backbone_out_dim)
+        self.exact = PoseEngine(height, width, self.max_repair, exact_dtype, self.fast.device, backbone_out_dim)
         self.lib, self.device = self.fast.lib, self.fast.device
         self.height, self.width, self.max_batch = self.fast.height, self.fast.width, self.fast.max_batch
         self.backbone_out_dim, self.slots = self.fast.backbone_out_dim, int(slots)

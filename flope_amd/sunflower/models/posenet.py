@@ -90,8 +90,9 @@ class PoseResNet(nn.Module):
             if slot is not None:
                 slot[0].close()
             mb = max(self._max_batch, int(batch))
-            if self.compute_dtype == "guard":            # f16 for every crop, float32 again for the ill-conditioned ones
-                eng = GuardedPoseEngine(hw[0], hw[1], mb, device=torch.device("cuda", index), backbone_out_dim=self.backbone_out_dim)
+            if self.compute_dtype in ("guard", "guardk"):   # f16 for every crop, float32 again for the ill-conditioned ones ("guardk": on the split-K float32 trunk)
+                eng = GuardedPoseEngine(hw[0], hw[1], mb, device=torch.device("cuda", index), backbone_out_dim=self.backbone_out_dim,
+                                        exact_dtype="f32mk" if self.compute_dtype == "guardk" else "f32m")
             else:
                 eng = PoseEngine(hw[0], hw[1], mb, self.compute_dtype, torch.device("cuda", index), self.backbone_out_dim)
             slot = [eng, -1]

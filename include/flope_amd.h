@@ -44,7 +44,10 @@ typedef struct flope_engine* flope_handle;
 #define FLOPE_DT_F16        1   /* MFMA v_mfma_f32_16x16x32_f16  */
 #define FLOPE_DT_F32        2   /* strict mode: plain fp32 direct convolution (no MFMA) */
 /* FLOPE_DT_F32 with flope_set_option(h, "f32mfma", 1): the same float32 buffers and stages, the stem and the 19 trunk convs on
- * v_mfma_f32_16x16x4_f32 (exact float32 products and sums; differs from the strict mode in summation order only). */
+ * v_mfma_f32_16x16x4_f32 (exact float32 products and sums; differs from the strict mode in summation order only).
+ * With flope_set_option(h, "f32m_ksplit", 1) on top of it: split-K for small batches -- a trunk conv whose launch would leave most
+ * of the chip idle runs as S workgroups per tile, each a share of K from +0, and an ordered second launch adds bias + share 0 +
+ * share 1 + ... + residual in that fixed order (another summation order again, still float32 throughout). */
 
 /* layout / dtype of the crop batch handed to flope_forward */
 #define FLOPE_IN_F32_NCHW   0   /* reference API: float32 [B,3,H,W] in [0,1] (posenet.py:31) */
@@ -162,7 +165,15 @@ int flope_read_stage(flope_handle h, int stage, int batch, float* dst_dev,
 /* runtime knobs (A/B variants inside one build); returns previous value or <0
  *   "f32mfma" (default 0): FLOPE_DT_F32 engines run the stem and every trunk conv on the exact-fp32 MFMA kernel (conv_f32m_kernel)
  *   instead of naive_conv_kernel; may be flipped between forwards (both weight images are loaded).  Stored and ignored by
- *   FLOPE_DT_F16 / BF16 engines. */
+ *   FLOPE_DT_F16 / BF16 engines.
+ *   "f32m_ksplit" (default 0; stored clamped to 0..32): split-K of conv_f32m_kernel.  0 = off: launches, labels and every bit of
+ *   every output as without the option.  1 = the planner picks a share count S in {1, 2, 4, 8, 16, 32} per conv launch (allowed only
+ *   where the batch runs in one slice, tiles * S <= compute units and every share keeps >= 4 K steps; the stem is never split).
+ *   2..32 = force that S, rounded down to a power of two, wherever a split is allowed (tests, A/B runs).  Split launches show as
+ *   "layer[split-K xS]" in flope_launch_info; flope_forward_launches counts the conv once (its finalize launch belongs to it).
+ *   NOTE: with the option on, S depends on the batch, so a crop's bits depend on HOW MANY crops run with it -- not on its position
+ *   in the batch, not on its neighbours, not on the run.  May be flipped between forwards.  Stored and ignored by FLOPE_DT_F16 /
+ *   BF16 engines and by FLOPE_DT_F32 engines with "f32mfma" = 0. */
 int flope_set_option(flope_handle h, const char* name, int value);
 /* developer aid of diagnostic builds (-DFLOPE_STAG_DBG, option "dbg" = 64): in-kernel clock stamps that conv launch i of
  * the last forward left in the split-K workspace at byte offset i * 1048576 ({clk0, clk1, rt0, rt1} uint64 per workgroup and

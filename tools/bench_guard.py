@@ -10,7 +10,8 @@ are small and distinct):
     host-synchronised loop (forward, repair, next forward) and the two-slot loop (forward i + 1 enqueued before repair i) in
     poses/s against the plain loop that never synchronises.
   * flagged > 0: device time of the guarded pair (forward, host wait, gather, float32 forward, scatter) against the plain forward,
-    and the added time against an f32m forward of that many crops alone on the same float32 engine.
+    and the added time against an f32m forward of that many crops alone on the same float32 engine; the same two figures with the
+    float32 engine's option f32m_ksplit = 1 (what GuardedPoseEngine(exact_dtype="f32mk") runs).
 --e2e: frame -> poses with the built-in detector (synthetic weights, 1080p), FLOPE_DTYPE=guard against f16, no crop flagged,
 sequential and pipelined.  One JSON document; every figure is named for what it is."""
 import argparse
@@ -134,11 +135,22 @@ def bench_shape(B, S, flagged, pairs, iters, sd):
 
             for _ in range(2):
                 exact_alone()
-            p_us, g_us, e_us = [], [], []
+            p_us, g_us, e_us, gk_us, ek_us = [], [], [], [], []
+            g.exact.set_option("f32m_ksplit", 1)              # the exact_dtype="f32mk" arm: the same guard, the float32 engine's option flipped
+            for _ in range(2):
+                pair()
+                exact_alone()
+            g.exact.set_option("f32m_ksplit", 0)
             for _ in range(pairs):
                 p_us.append(device_us(plain, iters))
                 g_us.append(device_us(pair, iters))
                 e_us.append(device_us(exact_alone, iters))
+                g.exact.set_option("f32m_ksplit", 1)
+                gk_us.append(device_us(pair, iters))
+                ek_us.append(device_us(exact_alone, iters))
+                g.exact.set_option("f32m_ksplit", 0)
+            row["guard_forward_and_repair_f32mk_us"], row["f32mk_forward_of_flagged_crops_alone_us"] = stats(gk_us), stats(ek_us)
+            row["added_f32mk_us"] = round(statistics.median(gk_us) - statistics.median(p_us), 1)
             row["plain_forward_poses_us"], row["guard_forward_and_repair_us"], row["f32m_forward_of_flagged_crops_alone_us"] = stats(p_us), stats(g_us), stats(e_us)
             row["added_us"] = round(statistics.median(g_us) - statistics.median(p_us), 1)
             row["added_over_f32m_alone"] = round(row["added_us"] / statistics.median(e_us), 3)
