@@ -10,12 +10,13 @@ HARNESS_F32M := tests/host_harness/libflope_host_f32m.so
 HARNESS_F32M_KSPLIT := tests/host_harness/libflope_host_f32m_ksplit.so
 HARNESS_GUARD := tests/host_harness/libflope_host_guard.so
 HARNESS_TF_F32M := tests/host_harness/libflope_host_tf_f32m.so
+HARNESS_TF_ATTN := tests/host_harness/libflope_host_tf_attn.so
 SRCS     := $(wildcard $(CSRC)/*.hip)
 OBJS     := $(patsubst $(CSRC)/%.hip,$(OBJDIR)/%.o,$(SRCS))
 HDRS     := $(wildcard $(CSRC)/*.h) include/flope_amd.h
 HIPFLAGS := --offload-arch=$(ARCH) -O3 -fPIC -std=c++17 -Wno-unused-value -Iinclude
 
-all: $(LIB) $(HARNESS) $(HARNESS_F32M) $(HARNESS_F32M_KSPLIT) $(HARNESS_GUARD) $(HARNESS_TF_F32M)
+all: $(LIB) $(HARNESS) $(HARNESS_F32M) $(HARNESS_F32M_KSPLIT) $(HARNESS_GUARD) $(HARNESS_TF_F32M) $(HARNESS_TF_ATTN)
 
 $(OBJDIR)/%.o: $(CSRC)/%.hip $(HDRS)
 	@mkdir -p $(OBJDIR)
@@ -39,6 +40,11 @@ $(HARNESS_F32M_KSPLIT): tests/host_harness/harness_f32m_ksplit.cpp tests/host_ha
 
 # packer and operand feed of the float32 MFMA encoder linear (tests/test_tf_f32m_host.py, tests/test_gpu_tf_f32m.py)
 $(HARNESS_TF_F32M): tests/host_harness/harness_tf_f32m.cpp $(CSRC)/host_pack.h
+	g++ -O2 -fPIC -shared -std=c++17 -I$(CSRC) -o $@ $<
+
+# attention kernel selection of the encoder and the constants of its launches (tests/test_tf_attn_plan_host.py,
+# tests/test_gpu_tf_attn_tiled.py)
+$(HARNESS_TF_ATTN): tests/host_harness/harness_tf_attn.cpp $(CSRC)/tf_attn_plan.h include/flope_amd.h
 	g++ -O2 -fPIC -shared -std=c++17 -I$(CSRC) -o $@ $<
 
 # conditioning figure and flag predicate of the guarded mode (tests/test_guard_host.py)
@@ -66,7 +72,7 @@ dbg: $(DBGOBJS)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $(DBGDIR)/libflope_amd_dbg.so $(DBGOBJS)
 
 clean:
-	rm -rf build $(LIB) $(HARNESS) $(HARNESS_F32M) $(HARNESS_F32M_KSPLIT) $(HARNESS_GUARD) $(HARNESS_TF_F32M)
+	rm -rf build $(LIB) $(HARNESS) $(HARNESS_F32M) $(HARNESS_F32M_KSPLIT) $(HARNESS_GUARD) $(HARNESS_TF_F32M) $(HARNESS_TF_ATTN)
 
 # stand-alone measurement programs used by tools/collect_profiles.sh and DESIGN.md section 9 (not part of the library)
 TOOLBINS := build/fetch_calib build/launch_floor build/loop_probe build/loop_probe32 build/dma_issue_probe

@@ -8,12 +8,14 @@
 //                         head_dim % 4 == 0 (<= 128) on tf_attn_f32m: v_mfma_f32_16x16x4_f32, exact float32, another summation order
 //   FLOPE_DT_F16 / BF16   activations in HBM as 16-bit row-major [tokens][features];
 //                         linears whose (N % 128 == 0, K % 64 == 0) run on v_mfma_f32_16x16x32 (tf_gemm_mfma),
-//                         attention with head_dim 64 runs on MFMA with the softmax in registers (tf_attn_mfma);
+//                         attention with head_dim 64 and at most 512 keys runs on MFMA with the softmax in registers (tf_attn_mfma);
+//     option attn_tiled   head_dim 32 / 64 / 96 / 128 at any length on the streaming form of that kernel (tf_attn_tiled);
 //                         everything else (embedding, out_layer, odd shapes) falls to the generic kernels.
 // Bias, residual add and ReLU live in the linear kernels' epilogues; LayerNorm is one wave per token row.
 #include "../../include/flope_amd.h"
 #include "common.h"
 #include "host_pack.h"
+#include "tf_attn_plan.h"
 
 #include <math.h>
 #include <string.h>
@@ -520,6 +522,188 @@ __global__ __launch_bounds__(1024) void tf_attn_mfma(const T* __restrict__ qkv, 
   }
 }
 
+// ---- MFMA attention, head_dim 32 HD32 (32 .. 128), any sequence length (option attn_tiled) -------------------------
+// tf_attn_mfma's arithmetic -- the same lane-to-key map, 32-key steps in ascending key order, expression order -- with K and V
+// streamed instead of resident.  Workgroup = 128 queries of one (batch, head): four waves of 32 queries, Q fragments in registers;
+// grid (B H, ceil(L / 128)).  Keys arrive in blocks of kTfAttnTiledKB = 64 (two 32-key steps) through a ring of kTfAttnTiledRing = 2
+// LDS stages (K block | V block, rows of RB = 64 HD32 bytes).  Register staging: block t + 1 is loaded into VGPRs in front of the
+// barrier of block t, stays in flight under block t's MFMAs and is written to the other stage behind them.  One barrier per block:
+// it publishes the writes of stage t & 1 and tells that every wave is done reading stage (t + 1) & 1 (block t - 1).
+// Keys at or past L: the lane loads row L - 1 instead (never a row past the sequence: the buffer may end at row B L) and writes
+// zeros to LDS; their scores become -inf before the maximum.  Block 0 always holds key 0 < L, so every query's running maximum is
+// finite from the first step on, and exp2(-inf - max) is 0, never NaN; a 32-key step that lies wholly past L is skipped by a
+// branch on the step index (the same for every lane).
+// ds_read_b64_tr_b16 needs EXEC all ones: no early return, no lane-dependent branch around the key loop; queries past L are clamped
+// to L - 1 and not stored.
+// LDS images (bank = (addr / 4) % 64 for ds_read_b128 and the transposed read; r = key row in its block, c = 16-byte chunk of the
+// row; both XORs stay inside an aligned group of four chunks, so rows of 12 chunks are safe):
+//   K rows, ds_read_b128 (a 16-lane group = 16 rows li, eight of them at chunk c0 and eight at c0 ^ 1):
+//     64-B and 192-B rows   c ^ (-(r >> 2) & 3)   rows r, r + 4, r + 8, r + 12 start on one slot quad and take its four slots
+//     128-B rows            c ^ ((r >> 1) & 7)    (tf_attn_mfma's)
+//     256-B rows            c ^ (r & 15)
+//   V rows, transposed read (a 32-lane half = 8 rows x one 32-byte column pair p; the XOR moves whole pairs):
+//     64-B and 192-B rows   p ^ ((r >> 2) & 1)    128-B rows  p ^ ((r >> 1) & 3)  (tf_attn_mfma's)    256-B rows  p ^ (r & 7)
+//   each makes the 8 rows of a half cover the 8 32-byte segments of the 256-byte bank row once.
+template <int HD32> __device__ __forceinline__ int tf_tiled_kswz(int r) {
+  return HD32 == 2 ? (r >> 1) & 7 : HD32 == 4 ? r & 15 : (-(r >> 2)) & 3;
+}
+template <int HD32> __device__ __forceinline__ int tf_tiled_vswz(int r) {
+  return (HD32 == 2 ? (r >> 1) & 3 : HD32 == 4 ? r & 7 : (r >> 2) & 1) << 1;
+}
+
+template <typename T, int HD32>
+__global__ __launch_bounds__(256, 2) void tf_attn_tiled(const T* __restrict__ qkv, T* __restrict__ out, int L, int d, int H,
+                                                        float scale_log2e) {
+  typedef typename Elem<T>::frag frag;
+  constexpr int HD = 32 * HD32, RB = 64 * HD32, NCH = 4 * HD32;     // head_dim, bytes and 16-byte chunks of a row
+  constexpr int KB = flope_tf_plan::kTfAttnTiledKB, BLK = KB * RB, STAGE = 2 * BLK;
+  static_assert(flope_tf_plan::kTfAttnTiledRing == 2 && KB == 64, "the loop below is written for two stages of two 32-key steps");
+  extern __shared__ __attribute__((aligned(16))) char smem[];      // [2 stages][K block [64][RB] | V block [64][RB]]
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, g = lane >> 4, li = lane & 15;
+  const int b = blockIdx.x / H, h = blockIdx.x - b * H;
+  const T* base = qkv + (size_t)b * L * 3 * d + h * HD;
+  const int nb = (L + KB - 1) / KB;
+
+  // staging role: HD32 chunks of K and of V per thread and block
+  int srow[HD32], ssrc[HD32], sdk[HD32], sdv[HD32];
+#pragma unroll
+  for (int i = 0; i < HD32; ++i) {
+    const int idx = tid + i * 256, row = idx / NCH, ch = idx - row * NCH;
+    srow[i] = row;
+    ssrc[i] = ch * 8;
+    sdk[i] = row * RB + ((ch ^ tf_tiled_kswz<HD32>(row)) << 4);
+    sdv[i] = BLK + row * RB + ((ch ^ tf_tiled_vswz<HD32>(row)) << 4);
+  }
+  u32x4 kr[HD32], vr[HD32];
+  auto gload = [&](int kb0) {
+#pragma unroll
+    for (int i = 0; i < HD32; ++i) {
+      const int row = kb0 + srow[i];
+      const T* src = base + (size_t)(row < L ? row : L - 1) * 3 * d + ssrc[i];
+      const u32x4 kv = *(const u32x4*)(src + d), vv = *(const u32x4*)(src + 2 * d);
+      const u32x4 z = {0, 0, 0, 0};
+      kr[i] = row < L ? kv : z;
+      vr[i] = row < L ? vv : z;
+    }
+  };
+  auto lwrite = [&](int stage) {
+    char* s = smem + stage * STAGE;
+#pragma unroll
+    for (int i = 0; i < HD32; ++i) {
+      *(u32x4*)(s + sdk[i]) = kr[i];
+      *(u32x4*)(s + sdv[i]) = vr[i];
+    }
+  };
+  gload(0);
+  lwrite(0);
+
+  const int q0 = blockIdx.y * flope_tf_plan::kTfAttnTiledQueries + wave * 32;
+  frag qf[2][HD32];
+#pragma unroll
+  for (int qt = 0; qt < 2; ++qt) {
+    int qi = q0 + qt * 16 + li;
+    qi = qi < L ? qi : L - 1;
+#pragma unroll
+    for (int ks = 0; ks < HD32; ++ks) qf[qt][ks] = *(const frag*)(base + (size_t)qi * 3 * d + (ks * 4 + g) * 8);
+  }
+  float mrun[2] = {-INFINITY, -INFINITY}, lrun[2] = {0.f, 0.f};
+  f32x4 o[2][2 * HD32];
+#pragma unroll
+  for (int qt = 0; qt < 2; ++qt)
+#pragma unroll
+    for (int dt = 0; dt < 2 * HD32; ++dt) o[qt][dt] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+  const int ksw = tf_tiled_kswz<HD32>(li);       // K-image swizzle of this lane's key row (row = 16-aligned + li)
+  const int trq = li >> 2, trp = li & 3;         // transposed-read role of this lane inside its 16-lane group
+  const int vrow = g * 4 + trq;                  // ... its V row in a 32-key step (and vrow + 16); the swizzle sees vrow & 7
+  const int vsw = tf_tiled_vswz<HD32>(vrow);
+
+  for (int t = 0; t < nb; ++t) {
+    gload((t + 1) * KB);                         // (past the last block: row L - 1 again, zeros, a stage nobody reads)
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    BLOCK_BARRIER();
+    const char* Ki = smem + (t & 1) * STAGE;
+    const char* Vi = Ki + BLK;
+#pragma unroll
+    for (int st = 0; st < KB / 32; ++st) {
+      const int kl = st * 32, kb = t * KB + kl;
+      if (kb >= L) continue;                     // uniform: EXEC stays all ones
+      f32x4 s[2][2];
+#pragma unroll
+      for (int u = 0; u < 2; ++u)
+#pragma unroll
+        for (int qt = 0; qt < 2; ++qt) s[u][qt] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int u = 0; u < 2; ++u)
+#pragma unroll
+        for (int ks = 0; ks < HD32; ++ks) {
+          const frag kf = *(const frag*)(Ki + (kl + u * 16 + li) * RB + (((ks * 4 + g) ^ ksw) << 4));
+#pragma unroll
+          for (int qt = 0; qt < 2; ++qt) s[u][qt] = Elem<T>::mfma(kf, qf[qt][ks], s[u][qt]);
+        }
+      frag pf[2];
+#pragma unroll
+      for (int qt = 0; qt < 2; ++qt) {
+        float v[8];
+        float mx = -INFINITY;
+#pragma unroll
+        for (int u = 0; u < 2; ++u)
+#pragma unroll
+          for (int q = 0; q < 4; ++q) {
+            const int key = kb + u * 16 + g * 4 + q;
+            const float x = key < L ? s[u][qt][q] * scale_log2e : -INFINITY;
+            v[u * 4 + q] = x;
+            mx = fmaxf(mx, x);
+          }
+        mx = fmaxf(mx, __shfl_xor(mx, 16));
+        mx = fmaxf(mx, __shfl_xor(mx, 32));
+        const float mnew = fmaxf(mrun[qt], mx);
+        const float alpha = __builtin_amdgcn_exp2f(mrun[qt] - mnew);
+        float ps = 0.f;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) { v[i] = __builtin_amdgcn_exp2f(v[i] - mnew); ps += v[i]; }
+        lrun[qt] = lrun[qt] * alpha + ps;
+        mrun[qt] = mnew;
+#pragma unroll
+        for (int dt = 0; dt < 2 * HD32; ++dt) o[qt][dt] *= alpha;
+        u32x4 pk;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) pk[i] = pack2<T>(v[i * 2], v[i * 2 + 1]);
+        pf[qt] = __builtin_bit_cast(frag, pk);
+      }
+#pragma unroll
+      for (int dt = 0; dt < 2 * HD32; ++dt) {
+        const int a0 = (kl + vrow) * RB + (((dt * 2 + (trp >> 1)) ^ vsw) << 4) + (trp & 1) * 8;
+        const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(Vi + a0));
+        const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(Vi + a0 + 16 * RB));
+        const s16x8 v8 = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+        const frag vf = __builtin_bit_cast(frag, v8);
+#pragma unroll
+        for (int qt = 0; qt < 2; ++qt) o[qt][dt] = Elem<T>::mfma(vf, pf[qt], o[qt][dt]);
+      }
+    }
+    lwrite((t + 1) & 1);
+  }
+#pragma unroll
+  for (int qt = 0; qt < 2; ++qt) {
+    float lt = lrun[qt];
+    lt += __shfl_xor(lt, 16);
+    lt += __shfl_xor(lt, 32);
+    const float inv = 1.f / lt;
+    const int qi = q0 + qt * 16 + li;
+    if (qi < L) {
+      T* dst = out + ((size_t)b * L + qi) * d + h * HD + g * 4;
+#pragma unroll
+      for (int dt = 0; dt < 2 * HD32; ++dt) {
+        u32x2 w2;
+        w2[0] = pack2<T>(o[qt][dt][0] * inv, o[qt][dt][1] * inv);
+        w2[1] = pack2<T>(o[qt][dt][2] * inv, o[qt][dt][3] * inv);
+        *(u32x2*)(dst + dt * 16) = w2;
+      }
+    }
+  }
+}
+
 // ---- float32 on the exact-fp32 matrix instruction (FLOPE_DT_F32 with option f32mfma = 1) ---------------------------------
 // v_mfma_f32_16x16x4_f32 takes float32 operands and accumulates in float32: every product-sum is an fmaf chain, so these kernels
 // differ from tf_linear_generic / tf_attn_generic (option 0, the checker) in summation order only.
@@ -642,7 +826,7 @@ __global__ __launch_bounds__(256) void tf_linear_f32m(const float* __restrict__ 
 //   3. values  O^T[dim][query] = V^T[dim][key] . P^T[key][query] (A = 16 dims of V for 4 keys, B = P from LDS; a wave takes every
 //      fourth group of 4 keys; the waves' partial sums are added in wave order through LDS).
 // Nothing depends on the sequence's position in the batch.  LDS: 16 (Lp + 4) + 3 NT 256 floats, at most kTfAttnLds.
-constexpr size_t kTfAttnLds = 160 * 1024;
+using flope_tf_plan::kTfAttnLds;
 template <int NT>
 __global__ __launch_bounds__(256) void tf_attn_f32m(const float* __restrict__ qkv, float* __restrict__ out, int L, int d, int H, float scale) {
   extern __shared__ __attribute__((aligned(16))) float Sm[];      // [16][pitch] scores / probabilities | [3][NT][64][4] partial outputs
@@ -768,6 +952,7 @@ struct flope_tf_encoder {
   int device = 0, in_dim = 0, d = 0, out_dim = 0, H = 0, nl = 0, ff = 0, max_tokens = 0, Mpad = 0, dtype = 0, esz = 2;
   int opt_generic = 0;                       // 1: force the generic kernels (A/B checks)
   int opt_f32m = 0;                          // 1: FLOPE_DT_F32 linears and attention on v_mfma_f32_16x16x4_f32 where eligible (stored and ignored by 16-bit handles)
+  int opt_tiled = 0;                         // 16-bit handles: 1 = tf_attn_tiled where the choice would be tf_attn_generic, 2 = also in place of tf_attn_mfma (stored and ignored by float32 handles)
   int opt_f32m_lds = 0;                      // KiB of untouched LDS a tf_linear_f32m launch reserves (> 80: one workgroup per CU)
   int cus = 256;
   bool loaded = false;
@@ -879,6 +1064,45 @@ int launch_linear(flope_tf_encoder* e, const TfLinear& l, const void* X, int x_f
   return 0;
 }
 
+// One attention launch: softmax(q k^T / sqrt(head_dim)) v per head, qkv [B][L][3 d] -> att [B][L][d].  The kernel is the one
+// tf_attn_plan.h picks; returns its FLOPE_TF_ATTN_* id, or < 0.
+template <typename T>
+int launch_attention(flope_tf_encoder* e, const void* qkv, void* att, int B, int L, hipStream_t st) {
+  using namespace flope_tf_plan;
+  const int d = e->d, H = e->H, dh = d / H;
+  const int pick = tf_attn_pick(e->dtype, dh, L, e->opt_generic, e->opt_f32m, e->opt_tiled, !(((uintptr_t)qkv | (uintptr_t)att) & 15));
+  if constexpr (!std::is_same<T, float>::value) {
+    if (pick == FLOPE_TF_ATTN_MFMA64) {
+      const int Lp = tf_attn_pad32(L);
+      hipLaunchKernelGGL((tf_attn_mfma<T>), dim3(B * H), dim3(Lp / 32 * 64), tf_attn_mfma64_lds(L), st, (const T*)qkv, (T*)att, L, d, H, Lp,
+                         1.4426950408889634f / sqrtf(64.f));
+    } else if (pick == FLOPE_TF_ATTN_TILED) {
+      const dim3 grid(B * H, (L + kTfAttnTiledQueries - 1) / kTfAttnTiledQueries);
+      const float scale_log2e = 1.4426950408889634f / sqrtf((float)dh);
+#define TF_ATT(HD32_) hipLaunchKernelGGL((tf_attn_tiled<T, HD32_>), grid, dim3(256), tf_attn_tiled_lds(dh), st, (const T*)qkv, (T*)att, L, d, H, scale_log2e)
+      if (dh == 32) TF_ATT(1); else if (dh == 64) TF_ATT(2); else if (dh == 96) TF_ATT(3); else TF_ATT(4);
+#undef TF_ATT
+    }
+  }
+  if constexpr (std::is_same<T, float>::value) {
+    if (pick == FLOPE_TF_ATTN_F32M) {
+      const int nt = tf_attn_f32m_nt(dh);
+      const size_t lds = tf_attn_f32m_lds(dh, L);
+      const dim3 grid(B * H, (L + 15) / 16);
+      const float scale = 1.f / sqrtf((float)dh);
+#define TF_ATT(NT_) hipLaunchKernelGGL((tf_attn_f32m<NT_>), grid, dim3(256), lds, st, (const float*)qkv, (float*)att, L, d, H, scale)
+      if (nt == 1) TF_ATT(1); else if (nt == 2) TF_ATT(2); else if (nt == 4) TF_ATT(4); else TF_ATT(8);
+#undef TF_ATT
+    }
+  }
+  if (pick == FLOPE_TF_ATTN_GENERIC) {
+    const int nw = 4, gy = (L + nw - 1) / nw < 64 ? (L + nw - 1) / nw : 64;
+    hipLaunchKernelGGL((tf_attn_generic<T>), dim3(B * H, gy), dim3(nw * 64), (size_t)nw * L * 4, st, (const T*)qkv, (T*)att, L, d, H);
+  }
+  TF_HIP(e, hipGetLastError());
+  return pick;
+}
+
 template <typename T>
 int run_forward(flope_tf_encoder* e, const float* x, int B, int L, float* y, hipStream_t st) {
   const int M = B * L, d = e->d;
@@ -886,33 +1110,7 @@ int run_forward(flope_tf_encoder* e, const float* x, int B, int L, float* y, hip
   if ((rc = launch_linear<T>(e, e->emb, x, 1, nullptr, e->h, 0, M, 0, st))) return rc;
   for (TfLayer& ly : e->layers) {
     if ((rc = launch_linear<T>(e, ly.in_proj, e->h, 0, nullptr, e->qkv, 0, M, 0, st))) return rc;
-    const int Lp = (L + 31) / 32 * 32;
-    bool fast_attn = false;
-    if constexpr (!std::is_same<T, float>::value) {
-      if (!e->opt_generic && d / e->H == 64 && Lp <= 512) {
-        fast_attn = true;
-        hipLaunchKernelGGL((tf_attn_mfma<T>), dim3(B * e->H), dim3(Lp / 32 * 64), (size_t)Lp * 256, st, (const T*)e->qkv,
-                           (T*)e->att, L, d, e->H, Lp, 1.4426950408889634f / sqrtf(64.f));
-      }
-    }
-    if constexpr (std::is_same<T, float>::value) {
-      const int dh = d / e->H, nt = dh <= 16 ? 1 : dh <= 32 ? 2 : dh <= 64 ? 4 : 8;       // 16-wide tiles of head_dim the kernel is built for
-      const size_t lds = ((size_t)16 * (((L + 15) & ~15) + 4) + (size_t)3 * nt * 256) * sizeof(float);
-      if (e->opt_f32m && dh % 4 == 0 && dh <= 128 && lds <= kTfAttnLds) {
-        fast_attn = true;
-        const dim3 grid(B * e->H, (L + 15) / 16);
-        const float scale = 1.f / sqrtf((float)dh);
-#define TF_ATT(NT_) hipLaunchKernelGGL((tf_attn_f32m<NT_>), grid, dim3(256), lds, st, (const float*)e->qkv, (float*)e->att, L, d, e->H, scale)
-        if (nt == 1) TF_ATT(1); else if (nt == 2) TF_ATT(2); else if (nt == 4) TF_ATT(4); else TF_ATT(8);
-#undef TF_ATT
-      }
-    }
-    if (!fast_attn) {
-      const int nw = 4, gy = (L + nw - 1) / nw < 64 ? (L + nw - 1) / nw : 64;
-      hipLaunchKernelGGL((tf_attn_generic<T>), dim3(B * e->H, gy), dim3(nw * 64), (size_t)nw * L * 4, st, (const T*)e->qkv,
-                         (T*)e->att, L, d, e->H);
-    }
-    TF_HIP(e, hipGetLastError());
+    if ((rc = launch_attention<T>(e, e->qkv, e->att, B, L, st)) < 0) return rc;
     if ((rc = launch_linear<T>(e, ly.out_proj, e->att, 0, e->h, e->h2, 0, M, 0, st))) return rc;
     auto ln = [&](const void* in, void* out, const float* w, const float* b) {
       if constexpr (!std::is_same<T, float>::value) {
@@ -980,6 +1178,11 @@ extern "C" int flope_tf_create(int device_id, int input_dim, int model_dim, int 
     for (const void* f : f32m)
       if (hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kTfAttnLds) != hipSuccess)
         return fin(tf_fail(nullptr, FLOPE_EHIP, "flope_tf_create: hipFuncSetAttribute failed"));
+    // tf_attn_tiled: 16 / 32 / 48 / 64 KiB; the widest sits at the 64 KiB a launch gets without asking
+    const void* const tiled[] = {(const void*)tf_attn_tiled<f16_t, 4>, (const void*)tf_attn_tiled<bf16_t, 4>};
+    for (const void* f : tiled)
+      if (hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)flope_tf_plan::tf_attn_tiled_lds(128)) != hipSuccess)
+        return fin(tf_fail(nullptr, FLOPE_EHIP, "flope_tf_create: hipFuncSetAttribute failed"));
     if (hipDeviceGetAttribute(&e->cus, hipDeviceAttributeMultiprocessorCount, device_id) != hipSuccess || e->cus < 1) e->cus = 256;
   }
   *out = e;
@@ -998,6 +1201,10 @@ extern "C" int flope_tf_set_option(flope_tf_handle e, const char* name, int valu
   if (!e || !name) return FLOPE_EINVAL;
   if (!strcmp(name, "generic")) { const int old = e->opt_generic; e->opt_generic = value ? 1 : 0; return old; }
   if (!strcmp(name, "f32mfma")) { const int old = e->opt_f32m; e->opt_f32m = value ? 1 : 0; return old; }
+  if (!strcmp(name, "attn_tiled")) {
+    if (value < 0 || value > 2) return tf_fail(e, FLOPE_EINVAL, "flope_tf_set_option: attn_tiled is 0, 1 or 2");
+    const int old = e->opt_tiled; e->opt_tiled = value; return old;
+  }
   if (!strcmp(name, "f32mlds")) {
     if (value < 0 || value > 160) return tf_fail(e, FLOPE_EINVAL, "flope_tf_set_option: f32mlds is 0 .. 160 (KiB)");
     const int old = e->opt_f32m_lds; e->opt_f32m_lds = value; return old;
@@ -1087,6 +1294,21 @@ extern "C" int flope_tf_forward(flope_tf_handle e, const float* x_dev, int batch
   if (e->dtype == FLOPE_DT_F32) return run_forward<float>(e, x_dev, batch, seq_len, y_dev, st);
   if (e->dtype == FLOPE_DT_F16) return run_forward<f16_t>(e, x_dev, batch, seq_len, y_dev, st);
   return run_forward<bf16_t>(e, x_dev, batch, seq_len, y_dev, st);
+}
+
+extern "C" int flope_tf_attention(flope_tf_handle e, const void* qkv_dev, int batch, int seq_len, void* out_dev, void* stream) {
+  if (!e) return tf_fail(nullptr, FLOPE_EINVAL, "flope_tf_attention: NULL handle");
+  if (batch < 1 || seq_len < 1) return tf_fail(e, FLOPE_EINVAL, "flope_tf_attention: non-positive size");
+  if (!qkv_dev || !out_dev) return tf_fail(e, FLOPE_EINVAL, "flope_tf_attention: NULL buffer");
+  if ((long long)batch * seq_len > e->max_tokens)
+    return tf_fail(e, FLOPE_EINVAL, "flope_tf_attention: batch*seq_len exceeds max_tokens given to flope_tf_create");
+  if (((uintptr_t)qkv_dev | (uintptr_t)out_dev) & (uintptr_t)(e->esz - 1))
+    return tf_fail(e, FLOPE_EINVAL, "flope_tf_attention: buffer not aligned to its element type");
+  TF_HIP(e, hipSetDevice(e->device));
+  hipStream_t st = (hipStream_t)stream;
+  if (e->dtype == FLOPE_DT_F32) return launch_attention<float>(e, qkv_dev, out_dev, batch, seq_len, st);
+  if (e->dtype == FLOPE_DT_F16) return launch_attention<f16_t>(e, qkv_dev, out_dev, batch, seq_len, st);
+  return launch_attention<bf16_t>(e, qkv_dev, out_dev, batch, seq_len, st);
 }
 
 // algorithmic FLOPs of one forward (2*MAC: linears + QK^T + PV)

@@ -27,7 +27,7 @@ def expected_keys(num_layers: int) -> list:
 
 class TransformerEncoder:
     def __init__(self, input_dim, model_dim, out_dim, num_heads, num_layers, ff_dim, dropout=0.1,
-                 dtype="f32", max_tokens=4096, device=None):
+                 dtype="f32", max_tokens=4096, device=None, attn_tiled=0):
         _require_gpu()
         self.lib = _lib.load()
         self.device = torch.device(device if device is not None else "cuda:0")
@@ -49,6 +49,12 @@ class TransformerEncoder:
             if rc < 0:
                 self.close()
                 raise RuntimeError(f"flope_tf_set_option(f32mfma) failed ({rc})")
+        self.last_attn_kernel = None             # FLOPE_TF_ATTN_* id of the last attention() launch
+        if attn_tiled:                           # 16-bit handles: MFMA attention for head_dim 32 .. 128 at any length (0 .. 2, include/flope_amd.h)
+            rc = self.lib.flope_tf_set_option(self.handle, b"attn_tiled", int(attn_tiled))
+            if rc < 0:
+                self.close()
+                raise ValueError(f"attn_tiled must be 0, 1 or 2 (got {attn_tiled!r})")
 
     def _check(self, rc):
         if rc:
@@ -98,6 +104,28 @@ class TransformerEncoder:
         return y
 
     __call__ = forward
+
+    def attention(self, qkv: torch.Tensor, out: torch.Tensor = None) -> torch.Tensor:
+        """softmax(q k^T / sqrt(head_dim)) v per head of qkv [B, L, 3 * model_dim] in the handle's dtype -> [B, L, model_dim], by
+        the kernel a forward of this (B, L) would launch under the current options; its id is kept in `last_attn_kernel`.  Needs no
+        weights.  `out`: a contiguous tensor of the result's shape and dtype to write into."""
+        tdt = {"f16": torch.float16, "bf16": torch.bfloat16}.get(self.dtype, torch.float32)
+        d = self.dims[1]
+        if not qkv.is_cuda or qkv.device != self.device:
+            raise RuntimeError(f"input must live on {self.device} (got {qkv.device}); no CPU path")
+        if qkv.dim() != 3 or qkv.shape[2] != 3 * d or qkv.dtype != tdt or not qkv.is_contiguous():
+            raise ValueError(f"expected a contiguous {tdt} tensor [B, L, {3 * d}], got {qkv.dtype} {tuple(qkv.shape)}")
+        B, L = qkv.shape[0], qkv.shape[1]
+        if out is None:
+            out = torch.empty((B, L, d), dtype=tdt, device=self.device)
+        elif out.shape != (B, L, d) or out.dtype != tdt or out.device != self.device or not out.is_contiguous():
+            raise ValueError(f"out must be a contiguous {tdt} tensor {(B, L, d)} on {self.device}")
+        rc = self.lib.flope_tf_attention(self.handle, qkv.data_ptr(), B, L, out.data_ptr(), _stream_ptr(self.device))
+        if rc < 0:
+            self._check(rc)
+        self.last_attn_kernel = rc
+        self._keep = qkv
+        return out
 
     def close(self):
         if getattr(self, "handle", None) and self.handle.value:

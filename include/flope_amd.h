@@ -290,7 +290,8 @@ int flope_frame_read_gaps(flope_frame_handle f, int slot, float* gap_host, int c
  *   no mask, no positional encoding) -> out_layer Linear.
  * dtype FLOPE_DT_F32: fp32 everywhere (any dimensions).  FLOPE_DT_F16 / BF16: 16-bit activations,
  * fp32 accumulation; linears with N % 128 == 0 and K % 64 == 0 and attention with head_dim 64
- * (seq_len <= 512) run on MFMA, everything else on generic kernels.
+ * (seq_len <= 512) run on MFMA, everything else on generic kernels.  With flope_tf_set_option(h, "attn_tiled", 1) attention with
+ * head_dim 32 / 64 / 96 / 128 runs on MFMA at any seq_len (tf_attn_tiled streams K and V through LDS in 64-key blocks).
  * FLOPE_DT_F32 with flope_tf_set_option(h, "f32mfma", 1): the same float32 buffers and launch sequence, every linear with
  * K % 4 == 0 and every attention with head_dim % 4 == 0, head_dim <= 128 and 16 score rows of seq_len floats within 160 KiB of LDS
  * on v_mfma_f32_16x16x4_f32 (exact float32 products and sums: differs from the strict mode in summation order only); the other
@@ -316,8 +317,19 @@ int flope_tf_forward(flope_tf_handle h, const float* x_dev, int batch, int seq_l
  *       (tf_linear_f32m, tf_attn_f32m) instead of the generic ones; may be flipped between forwards (flope_tf_load_weights on a
  *       float32 handle uploads both weight images).  Stored and ignored by FLOPE_DT_F16 / BF16 handles;
  *   "f32mlds" (default 0; 0 .. 160): KiB of untouched LDS every tf_linear_f32m launch reserves; more than 80 leaves one
- *       workgroup per CU (measurement knob: DESIGN.md 16). */
+ *       workgroup per CU (measurement knob: DESIGN.md 16);
+ *   "attn_tiled" (default 0; 0 .. 2, FLOPE_EINVAL outside): which 16-bit attention launches take the streaming MFMA kernel
+ *       tf_attn_tiled (head_dim % 32 == 0, head_dim <= 128, any seq_len).  0: none.  1: those that would otherwise run
+ *       the generic kernel; shapes the resident kernel takes (head_dim 64, seq_len <= 512) keep it.  2: every eligible launch, also in
+ *       place of the resident kernel (A/B and tests).  "generic" = 1 overrides it; buffers that are not 16-byte aligned run generic.
+ *       May be flipped between forwards.  Stored and ignored by FLOPE_DT_F32 handles. */
 int flope_tf_set_option(flope_tf_handle h, const char* name, int value);
+/* softmax(q k^T / sqrt(head_dim)) v per head on a caller's buffer: qkv_dev [batch, seq_len, 3*model_dim] and out_dev
+ * [batch, seq_len, model_dim] in the handle's dtype (float32 for FLOPE_DT_F32).  Launches exactly what flope_tf_forward
+ * would launch for this (batch, seq_len) under the handle's current options; needs no weights.  Returns the
+ * FLOPE_TF_ATTN_* id of the kernel launched (flope_amd/csrc/tf_attn_plan.h: 0 generic, 1 tf_attn_mfma, 2 tf_attn_tiled,
+ * 3 tf_attn_f32m), or < 0.  batch*seq_len <= max_tokens. */
+int flope_tf_attention(flope_tf_handle h, const void* qkv_dev, int batch, int seq_len, void* out_dev, void* stream);
 /* algorithmic FLOPs of one forward (2*MAC: linears + QK^T + PV) */
 double flope_tf_forward_flops(flope_tf_handle h, int batch, int seq_len);
 
