@@ -11,12 +11,13 @@ HARNESS_F32M_KSPLIT := tests/host_harness/libflope_host_f32m_ksplit.so
 HARNESS_GUARD := tests/host_harness/libflope_host_guard.so
 HARNESS_TF_F32M := tests/host_harness/libflope_host_tf_f32m.so
 HARNESS_TF_ATTN := tests/host_harness/libflope_host_tf_attn.so
+HARNESS_TF_VARLEN := tests/host_harness/libflope_host_tf_varlen.so
 SRCS     := $(wildcard $(CSRC)/*.hip)
 OBJS     := $(patsubst $(CSRC)/%.hip,$(OBJDIR)/%.o,$(SRCS))
 HDRS     := $(wildcard $(CSRC)/*.h) include/flope_amd.h
 HIPFLAGS := --offload-arch=$(ARCH) -O3 -fPIC -std=c++17 -Wno-unused-value -Iinclude
 
-all: $(LIB) $(HARNESS) $(HARNESS_F32M) $(HARNESS_F32M_KSPLIT) $(HARNESS_GUARD) $(HARNESS_TF_F32M) $(HARNESS_TF_ATTN)
+all: $(LIB) $(HARNESS) $(HARNESS_F32M) $(HARNESS_F32M_KSPLIT) $(HARNESS_GUARD) $(HARNESS_TF_F32M) $(HARNESS_TF_ATTN) $(HARNESS_TF_VARLEN)
 
 $(OBJDIR)/%.o: $(CSRC)/%.hip $(HDRS)
 	@mkdir -p $(OBJDIR)
@@ -47,6 +48,11 @@ $(HARNESS_TF_F32M): tests/host_harness/harness_tf_f32m.cpp $(CSRC)/host_pack.h
 $(HARNESS_TF_ATTN): tests/host_harness/harness_tf_attn.cpp $(CSRC)/tf_attn_plan.h include/flope_amd.h
 	g++ -O2 -fPIC -shared -std=c++17 -I$(CSRC) -o $@ $<
 
+# ragged-batch planner of the encoder: offsets, limits and the variable-length attention launches (tests/test_tf_varlen_host.py,
+# tests/test_gpu_tf_varlen.py)
+$(HARNESS_TF_VARLEN): tests/host_harness/harness_tf_varlen.cpp $(CSRC)/tf_attn_plan.h include/flope_amd.h
+	g++ -O2 -fPIC -shared -std=c++17 -I$(CSRC) -o $@ $<
+
 # conditioning figure and flag predicate of the guarded mode (tests/test_guard_host.py)
 $(HARNESS_GUARD): tests/host_harness/harness_guard.cpp $(CSRC)/pose_math.h
 	g++ -O2 -fPIC -shared -std=c++17 -I$(CSRC) -o $@ $<
@@ -72,7 +78,7 @@ dbg: $(DBGOBJS)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $(DBGDIR)/libflope_amd_dbg.so $(DBGOBJS)
 
 clean:
-	rm -rf build $(LIB) $(HARNESS) $(HARNESS_F32M) $(HARNESS_F32M_KSPLIT) $(HARNESS_GUARD) $(HARNESS_TF_F32M) $(HARNESS_TF_ATTN)
+	rm -rf build $(LIB) $(HARNESS) $(HARNESS_F32M) $(HARNESS_F32M_KSPLIT) $(HARNESS_GUARD) $(HARNESS_TF_F32M) $(HARNESS_TF_ATTN) $(HARNESS_TF_VARLEN)
 
 # stand-alone measurement programs used by tools/collect_profiles.sh and DESIGN.md section 9 (not part of the library)
 TOOLBINS := build/fetch_calib build/launch_floor build/loop_probe build/loop_probe32 build/dma_issue_probe

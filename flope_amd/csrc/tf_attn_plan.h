@@ -1,6 +1,8 @@
 // Which attention kernel one encoder launch takes, and the LDS bytes it is launched with -- plain integer arithmetic, no HIP,
 // shared by tf_encoder.hip (launch_attention: flope_tf_forward and flope_tf_attention) and tests/host_harness/harness_tf_attn.cpp
 // (tests/test_tf_attn_plan_host.py checks the table on the CPU, tests/test_gpu_tf_attn_tiled.py the device against it).
+// Below it, the planner of ragged batches (launch_attention_varlen and the flope_tf_*_varlen entry points;
+// tests/host_harness/harness_tf_varlen.cpp, tests/test_tf_varlen_host.py).
 #pragma once
 
 #include <stddef.h>
@@ -52,6 +54,67 @@ inline int tf_attn_pick(int dtype, int head_dim, int seq_len, int opt_generic, i
   if (head_dim == 64 && tf_attn_pad32(seq_len) <= kTfAttnMfma64MaxLp) pick = FLOPE_TF_ATTN_MFMA64;
   if (tf_attn_tiled_ok(head_dim) && (opt_tiled == 2 || (opt_tiled == 1 && pick == FLOPE_TF_ATTN_GENERIC))) pick = FLOPE_TF_ATTN_TILED;
   return pick;
+}
+
+// ---- ragged batches (flope_tf_forward_varlen / flope_tf_attention_varlen) ------------------------------------------
+// A batch of B sequences of lengths[b] tokens (1 <= lengths[b] <= L) lives in the handle as T = sum lengths packed rows;
+// sequence b starts at packed row off[b], off[B] = T.
+enum {
+  kTfVarlenOk = 0,
+  kTfVarlenBatch = -1,      // B <= 0 (or a NULL table)
+  kTfVarlenLength = -2,     // a length < 1 or > L; *bad = its index
+  kTfVarlenTokens = -3,     // T > max_tokens
+  kTfVarlenOverflow = -4    // T does not fit an int
+};
+
+// off: B + 1 ints.  On kTfVarlenOk: off, *T and *max_len are written; otherwise nothing but *bad (kTfVarlenLength) is.
+inline int tf_varlen_plan(const int* lengths, int B, int L, int max_tokens, int* off, int* T, int* max_len, int* bad) {
+  if (B <= 0 || !lengths || !off) return kTfVarlenBatch;
+  long long sum = 0;
+  int mx = 0;
+  for (int b = 0; b < B; ++b) {
+    if (lengths[b] < 1 || lengths[b] > L) {
+      if (bad) *bad = b;
+      return kTfVarlenLength;
+    }
+    sum += lengths[b];
+    if (lengths[b] > mx) mx = lengths[b];
+  }
+  if (sum > (long long)INT32_MAX) return kTfVarlenOverflow;
+  if (sum > (long long)max_tokens) return kTfVarlenTokens;
+  int run = 0;
+  for (int b = 0; b < B; ++b) { off[b] = run; run += lengths[b]; }
+  off[B] = run;
+  if (T) *T = run;
+  if (max_len) *max_len = mx;
+  return kTfVarlenOk;
+}
+
+// Grid, block and dynamic LDS of the variable-length launch of kernel `which` (FLOPE_TF_ATTN_*): sized by the longest sequence of
+// the batch; a workgroup past its own sequence's length leaves at once.
+struct TfAttnLaunch { unsigned grid_x, grid_y, block; size_t lds; };
+inline TfAttnLaunch tf_attn_varlen_launch(int which, int head_dim, int B, int H, int max_len) {
+  TfAttnLaunch l = {(unsigned)B * (unsigned)H, 1u, 256u, 0};
+  switch (which) {
+    case FLOPE_TF_ATTN_MFMA64:
+      l.block = (unsigned)(tf_attn_pad32(max_len) / 32 * 64);
+      l.lds = tf_attn_mfma64_lds(max_len);
+      break;
+    case FLOPE_TF_ATTN_TILED:
+      l.grid_y = (unsigned)((max_len + kTfAttnTiledQueries - 1) / kTfAttnTiledQueries);
+      l.lds = tf_attn_tiled_lds(head_dim);
+      break;
+    case FLOPE_TF_ATTN_F32M:
+      l.grid_y = (unsigned)((max_len + 15) / 16);
+      l.lds = tf_attn_f32m_lds(head_dim, max_len);
+      break;
+    default: {                                   // generic: four waves, one query each per trip, at most 64 workgroups per head
+      const int gy = (max_len + 3) / 4;
+      l.grid_y = (unsigned)(gy < 64 ? gy : 64);
+      l.lds = (size_t)4 * max_len * sizeof(float);
+    }
+  }
+  return l;
 }
 
 }  // namespace flope_tf_plan

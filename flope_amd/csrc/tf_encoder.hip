@@ -159,6 +159,30 @@ __global__ void tf_cast_pad(const float* X, T* Y, int M, int K, int Kp) {
   Y[idx] = from_f32<T>(k < K ? X[(size_t)m * K + k] : 0.f);
 }
 
+// Ragged batches (flope_tf_forward_varlen): rows i < off[b + 1] - off[b] of X [B][L][K] -> packed rows off[b] + i of Y [T][Kp]
+// (TO = float, Kp = K: a copy; TO 16-bit: tf_cast_pad's conversion and zero columns).  Rows behind a sequence are never read.
+template <typename TO>
+__global__ void tf_gather_rows(const float* X, TO* Y, const int* __restrict__ off, int L, int K, int Kp, size_t total) {
+  const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= total) return;
+  const size_t r = idx / Kp;
+  const int k = (int)(idx - r * Kp), b = (int)(r / L), i = (int)(r - (size_t)b * L);
+  const int o = off[b];
+  if (i >= off[b + 1] - o) return;
+  Y[(size_t)(o + i) * Kp + k] = from_f32<TO>(k < K ? X[r * K + k] : 0.f);
+}
+
+// ... and back: packed Yp [T][N] -> Y [B][L][N]; rows behind a sequence get the bias of out_layer (what the reference module
+// returns there: its eval path zeroes padded tokens behind the encoder stack, and out_layer(0) = bias).  Y is fully written.
+__global__ void tf_scatter_rows(const float* Yp, const float* __restrict__ bias, float* Y, const int* __restrict__ off, int L, int N, size_t total) {
+  const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= total) return;
+  const size_t r = idx / N;
+  const int c = (int)(idx - r * N), b = (int)(r / L), i = (int)(r - (size_t)b * L);
+  const int o = off[b];
+  Y[idx] = i < off[b + 1] - o ? Yp[(size_t)(o + i) * N + c] : bias[c];
+}
+
 // LayerNorm over the last dimension, one wave per row (eps 1e-5, biased variance)
 template <typename T>
 __global__ void tf_layernorm(const T* in, T* out, const float* w, const float* b, int M, int d) {
@@ -223,14 +247,20 @@ __global__ void tf_layernorm_vec(const T* in, T* out, const float* w, const floa
 }
 
 // softmax(q k^T / sqrt(dh)) v for one (batch, head) per blockIdx.x; one wave per query row.  Any L / dh.
-template <typename T>
-__global__ void tf_attn_generic(const T* qkv, T* out, int L, int d, int H) {
+// VARLEN (all four attention kernels): qkv and out are packed [T][.] rows of a ragged batch, sequence b is rows
+// off[b] .. off[b + 1] - 1 and the L argument is the longest length, which sized the grid and the LDS; the kernel takes its own
+// sequence's length for L, so every bound, mask and clamp below stays inside the sequence (row off[b] + L is the next sequence's
+// first key, not padding).  The fixed-length instantiations (VARLEN = false, off unused) compile from the source they had.
+template <typename T, bool VARLEN = false>
+__global__ void tf_attn_generic(const T* qkv, T* out, int L, int d, int H, const int* __restrict__ off) {
   extern __shared__ float sc[];                 // [waves][L]
   const int nw = blockDim.x >> 6, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int b = blockIdx.x / H, h = blockIdx.x - b * H, dh = d / H;
   const float scale = 1.f / sqrtf((float)dh);
+  size_t row0 = 0;                              // first row of this sequence
+  if constexpr (VARLEN) { row0 = (size_t)off[b]; L = off[b + 1] - off[b]; }
   float* s = sc + (size_t)wave * L;
-  const T* base = qkv + (size_t)b * L * 3 * d + h * dh;
+  const T* base = VARLEN ? qkv + row0 * 3 * d + h * dh : qkv + (size_t)b * L * 3 * d + h * dh;
   for (int i = blockIdx.y * nw + wave; i < L; i += gridDim.y * nw) {
     const T* q = base + (size_t)i * 3 * d;
     float mx = -INFINITY;
@@ -251,7 +281,7 @@ __global__ void tf_attn_generic(const T* qkv, T* out, int L, int d, int H) {
     for (int c = lane; c < dh; c += 64) {
       float o = 0.f;
       for (int j = 0; j < L; ++j) o = fmaf(s[j], to_f32<T>(base[(size_t)j * 3 * d + 2 * d + c]), o);
-      out[((size_t)b * L + i) * d + h * dh + c] = from_f32<T>(o * inv);
+      out[((VARLEN ? row0 : (size_t)b * L) + i) * d + h * dh + c] = from_f32<T>(o * inv);
     }
     __builtin_amdgcn_wave_barrier();
   }
@@ -400,14 +430,19 @@ __global__ __launch_bounds__(256, 2) void tf_gemm_mfma(const T* __restrict__ X, 
 typedef short s16x4 __attribute__((ext_vector_type(4)));
 typedef short s16x8 __attribute__((ext_vector_type(8)));
 
-template <typename T>
+// VARLEN: launched with pad32(longest) / 32 waves and that much LDS; L and Lp become the sequence's own (the V image starts behind
+// its own K image), a wave whose 32 queries lie past the sequence leaves behind the one __syncthreads (a whole wave: EXEC of the
+// others stays all ones for the transposed reads).
+template <typename T, bool VARLEN = false>
 __global__ __launch_bounds__(1024) void tf_attn_mfma(const T* __restrict__ qkv, T* __restrict__ out, int L, int d,
-                                                     int H, int Lp, float scale_log2e) {
+                                                     int H, int Lp, float scale_log2e, const int* __restrict__ off) {
   typedef typename Elem<T>::frag frag;
   extern __shared__ __attribute__((aligned(16))) char smem[];      // K image [Lp][128 B] | V image [Lp][128 B]
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, g = lane >> 4, li = lane & 15;
   const int b = blockIdx.x / H, h = blockIdx.x - b * H;
-  const T* base = qkv + (size_t)b * L * 3 * d + h * 64;
+  size_t row0 = 0;
+  if constexpr (VARLEN) { row0 = (size_t)off[b]; L = off[b + 1] - off[b]; Lp = (L + 31) / 32 * 32; }
+  const T* base = VARLEN ? qkv + row0 * 3 * d + h * 64 : qkv + (size_t)b * L * 3 * d + h * 64;
   char* Ki = smem;
   char* Vi = smem + (size_t)Lp * 128;
   for (int idx = tid; idx < Lp * 8; idx += blockDim.x) {
@@ -424,6 +459,7 @@ __global__ __launch_bounds__(1024) void tf_attn_mfma(const T* __restrict__ qkv, 
   __syncthreads();
 
   const int q0 = wave * 32;
+  if constexpr (VARLEN) { if (q0 >= L) return; }
   frag qf[2][2];
 #pragma unroll
   for (int qt = 0; qt < 2; ++qt) {
@@ -510,7 +546,7 @@ __global__ __launch_bounds__(1024) void tf_attn_mfma(const T* __restrict__ qkv, 
     const float inv = 1.f / lt;
     const int qi = q0 + qt * 16 + li;
     if (qi < L) {
-      T* dst = out + ((size_t)b * L + qi) * d + h * 64 + g * 4;
+      T* dst = out + ((VARLEN ? row0 : (size_t)b * L) + qi) * d + h * 64 + g * 4;
 #pragma unroll
       for (int dt = 0; dt < 4; ++dt) {
         u32x2 w2;
@@ -551,9 +587,12 @@ template <int HD32> __device__ __forceinline__ int tf_tiled_vswz(int r) {
   return (HD32 == 2 ? (r >> 1) & 3 : HD32 == 4 ? r & 7 : (r >> 2) & 1) << 1;
 }
 
-template <typename T, int HD32>
+// VARLEN: grid.y counts the query blocks of the longest sequence; a workgroup whose first query lies at or past its own sequence's
+// length leaves before its first load and barrier (all four waves: the condition is per workgroup), one with some valid queries
+// keeps all four waves in the barrier loop as above; nb, the step skip and the masks use the sequence's own L.
+template <typename T, int HD32, bool VARLEN = false>
 __global__ __launch_bounds__(256, 2) void tf_attn_tiled(const T* __restrict__ qkv, T* __restrict__ out, int L, int d, int H,
-                                                        float scale_log2e) {
+                                                        float scale_log2e, const int* __restrict__ off) {
   typedef typename Elem<T>::frag frag;
   constexpr int HD = 32 * HD32, RB = 64 * HD32, NCH = 4 * HD32;     // head_dim, bytes and 16-byte chunks of a row
   constexpr int KB = flope_tf_plan::kTfAttnTiledKB, BLK = KB * RB, STAGE = 2 * BLK;
@@ -561,7 +600,12 @@ __global__ __launch_bounds__(256, 2) void tf_attn_tiled(const T* __restrict__ qk
   extern __shared__ __attribute__((aligned(16))) char smem[];      // [2 stages][K block [64][RB] | V block [64][RB]]
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, g = lane >> 4, li = lane & 15;
   const int b = blockIdx.x / H, h = blockIdx.x - b * H;
-  const T* base = qkv + (size_t)b * L * 3 * d + h * HD;
+  size_t row0 = 0;
+  if constexpr (VARLEN) {
+    row0 = (size_t)off[b]; L = off[b + 1] - off[b];
+    if ((int)blockIdx.y * flope_tf_plan::kTfAttnTiledQueries >= L) return;
+  }
+  const T* base = VARLEN ? qkv + row0 * 3 * d + h * HD : qkv + (size_t)b * L * 3 * d + h * HD;
   const int nb = (L + KB - 1) / KB;
 
   // staging role: HD32 chunks of K and of V per thread and block
@@ -692,7 +736,7 @@ __global__ __launch_bounds__(256, 2) void tf_attn_tiled(const T* __restrict__ qk
     const float inv = 1.f / lt;
     const int qi = q0 + qt * 16 + li;
     if (qi < L) {
-      T* dst = out + ((size_t)b * L + qi) * d + h * HD + g * 4;
+      T* dst = out + ((VARLEN ? row0 : (size_t)b * L) + qi) * d + h * HD + g * 4;
 #pragma unroll
       for (int dt = 0; dt < 2 * HD32; ++dt) {
         u32x2 w2;
@@ -827,14 +871,22 @@ __global__ __launch_bounds__(256) void tf_linear_f32m(const float* __restrict__ 
 //      fourth group of 4 keys; the waves' partial sums are added in wave order through LDS).
 // Nothing depends on the sequence's position in the batch.  LDS: 16 (Lp + 4) + 3 NT 256 floats, at most kTfAttnLds.
 using flope_tf_plan::kTfAttnLds;
-template <int NT>
-__global__ __launch_bounds__(256) void tf_attn_f32m(const float* __restrict__ qkv, float* __restrict__ out, int L, int d, int H, float scale) {
+// VARLEN: grid.y and the LDS are those of the longest sequence; a workgroup whose 16 queries lie past its own sequence leaves before
+// the first barrier; Lp, the score pitch and the place of the partial sums behind the scores follow the sequence's own L.
+template <int NT, bool VARLEN = false>
+__global__ __launch_bounds__(256) void tf_attn_f32m(const float* __restrict__ qkv, float* __restrict__ out, int L, int d, int H, float scale,
+                                                    const int* __restrict__ off) {
   extern __shared__ __attribute__((aligned(16))) float Sm[];      // [16][pitch] scores / probabilities | [3][NT][64][4] partial outputs
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int kq = lane >> 4, c16 = lane & 15;
   const int b = blockIdx.x / H, h = blockIdx.x - b * H, dh = d / H, q0 = blockIdx.y * 16;
+  size_t row0 = 0;
+  if constexpr (VARLEN) {
+    row0 = (size_t)off[b]; L = off[b + 1] - off[b];
+    if (q0 >= L) return;
+  }
   const int Lp = (L + 15) & ~15, pitch = Lp + 4, ld = 3 * d;
-  const float* const base = qkv + (size_t)b * L * ld + h * dh;
+  const float* const base = VARLEN ? qkv + row0 * ld + h * dh : qkv + (size_t)b * L * ld + h * dh;
   float* const red = Sm + 16 * pitch;
   // 1. scores
   {
@@ -930,7 +982,7 @@ __global__ __launch_bounds__(256) void tf_attn_f32m(const float* __restrict__ qk
     }
   // lane (kq, c16): query c16, dims ct * 16 + 4 kq + r
   if (q0 + c16 < L) {
-    float* o = out + ((size_t)b * L + q0 + c16) * d + h * dh + 4 * kq;
+    float* o = out + ((VARLEN ? row0 : (size_t)b * L) + q0 + c16) * d + h * dh + 4 * kq;
 #pragma unroll
     for (int ct = 0; ct < NT; ++ct)
       if (ct * 16 + 4 * kq < dh) *(f32x4*)(o + ct * 16) = acc[ct];
@@ -960,6 +1012,11 @@ struct flope_tf_encoder {
   std::vector<TfLayer> layers;
   void *h = nullptr, *h2 = nullptr, *qkv = nullptr, *att = nullptr, *ffb = nullptr;
   void* xin = nullptr;                       // 16-bit zero-padded copy of the fp32 input [Mpad][roundup(in_dim, 64)]
+  // ragged batches (flope_tf_*_varlen): packed float32 input [Mpad][in_dim] and output [Mpad][out_dim], the offset table
+  // [max_tokens + 1] on the device and the pageable host copy it is uploaded from; all allocated in flope_tf_create
+  float *xpk = nullptr, *ypk = nullptr;
+  int* vl_off = nullptr;
+  std::vector<int> vl_host;
   std::vector<void*> allocs;
   std::string err;
 };
@@ -1075,11 +1132,11 @@ int launch_attention(flope_tf_encoder* e, const void* qkv, void* att, int B, int
     if (pick == FLOPE_TF_ATTN_MFMA64) {
       const int Lp = tf_attn_pad32(L);
       hipLaunchKernelGGL((tf_attn_mfma<T>), dim3(B * H), dim3(Lp / 32 * 64), tf_attn_mfma64_lds(L), st, (const T*)qkv, (T*)att, L, d, H, Lp,
-                         1.4426950408889634f / sqrtf(64.f));
+                         1.4426950408889634f / sqrtf(64.f), (const int*)nullptr);
     } else if (pick == FLOPE_TF_ATTN_TILED) {
       const dim3 grid(B * H, (L + kTfAttnTiledQueries - 1) / kTfAttnTiledQueries);
       const float scale_log2e = 1.4426950408889634f / sqrtf((float)dh);
-#define TF_ATT(HD32_) hipLaunchKernelGGL((tf_attn_tiled<T, HD32_>), grid, dim3(256), tf_attn_tiled_lds(dh), st, (const T*)qkv, (T*)att, L, d, H, scale_log2e)
+#define TF_ATT(HD32_) hipLaunchKernelGGL((tf_attn_tiled<T, HD32_>), grid, dim3(256), tf_attn_tiled_lds(dh), st, (const T*)qkv, (T*)att, L, d, H, scale_log2e, (const int*)nullptr)
       if (dh == 32) TF_ATT(1); else if (dh == 64) TF_ATT(2); else if (dh == 96) TF_ATT(3); else TF_ATT(4);
 #undef TF_ATT
     }
@@ -1090,27 +1147,97 @@ int launch_attention(flope_tf_encoder* e, const void* qkv, void* att, int B, int
       const size_t lds = tf_attn_f32m_lds(dh, L);
       const dim3 grid(B * H, (L + 15) / 16);
       const float scale = 1.f / sqrtf((float)dh);
-#define TF_ATT(NT_) hipLaunchKernelGGL((tf_attn_f32m<NT_>), grid, dim3(256), lds, st, (const float*)qkv, (float*)att, L, d, H, scale)
+#define TF_ATT(NT_) hipLaunchKernelGGL((tf_attn_f32m<NT_>), grid, dim3(256), lds, st, (const float*)qkv, (float*)att, L, d, H, scale, (const int*)nullptr)
       if (nt == 1) TF_ATT(1); else if (nt == 2) TF_ATT(2); else if (nt == 4) TF_ATT(4); else TF_ATT(8);
 #undef TF_ATT
     }
   }
   if (pick == FLOPE_TF_ATTN_GENERIC) {
     const int nw = 4, gy = (L + nw - 1) / nw < 64 ? (L + nw - 1) / nw : 64;
-    hipLaunchKernelGGL((tf_attn_generic<T>), dim3(B * H, gy), dim3(nw * 64), (size_t)nw * L * 4, st, (const T*)qkv, (T*)att, L, d, H);
+    hipLaunchKernelGGL((tf_attn_generic<T>), dim3(B * H, gy), dim3(nw * 64), (size_t)nw * L * 4, st, (const T*)qkv, (T*)att, L, d, H, (const int*)nullptr);
   }
   TF_HIP(e, hipGetLastError());
   return pick;
 }
 
+// The same for a ragged batch: packed qkv [T][3 d] -> att [T][d], sequence b = rows off[b] .. off[b + 1] - 1 (off: the handle's
+// device table).  One kernel for the whole batch, the one tf_attn_pick gives the longest sequence; grid, block and LDS from
+// tf_attn_varlen_launch.
 template <typename T>
-int run_forward(flope_tf_encoder* e, const float* x, int B, int L, float* y, hipStream_t st) {
-  const int M = B * L, d = e->d;
+int launch_attention_varlen(flope_tf_encoder* e, const void* qkv, void* att, int B, int max_len, const int* off, hipStream_t st) {
+  using namespace flope_tf_plan;
+  const int d = e->d, H = e->H, dh = d / H;
+  const int pick = tf_attn_pick(e->dtype, dh, max_len, e->opt_generic, e->opt_f32m, e->opt_tiled, !(((uintptr_t)qkv | (uintptr_t)att) & 15));
+  const TfAttnLaunch l = tf_attn_varlen_launch(pick, dh, B, H, max_len);
+  const dim3 grid(l.grid_x, l.grid_y), block(l.block);
+  if constexpr (!std::is_same<T, float>::value) {
+    if (pick == FLOPE_TF_ATTN_MFMA64) {
+      hipLaunchKernelGGL((tf_attn_mfma<T, true>), grid, block, l.lds, st, (const T*)qkv, (T*)att, max_len, d, H, tf_attn_pad32(max_len),
+                         1.4426950408889634f / sqrtf(64.f), off);
+    } else if (pick == FLOPE_TF_ATTN_TILED) {
+      const float scale_log2e = 1.4426950408889634f / sqrtf((float)dh);
+#define TF_ATT(HD32_) hipLaunchKernelGGL((tf_attn_tiled<T, HD32_, true>), grid, block, l.lds, st, (const T*)qkv, (T*)att, max_len, d, H, scale_log2e, off)
+      if (dh == 32) TF_ATT(1); else if (dh == 64) TF_ATT(2); else if (dh == 96) TF_ATT(3); else TF_ATT(4);
+#undef TF_ATT
+    }
+  }
+  if constexpr (std::is_same<T, float>::value) {
+    if (pick == FLOPE_TF_ATTN_F32M) {
+      const int nt = tf_attn_f32m_nt(dh);
+      const float scale = 1.f / sqrtf((float)dh);
+#define TF_ATT(NT_) hipLaunchKernelGGL((tf_attn_f32m<NT_, true>), grid, block, l.lds, st, (const float*)qkv, (float*)att, max_len, d, H, scale, off)
+      if (nt == 1) TF_ATT(1); else if (nt == 2) TF_ATT(2); else if (nt == 4) TF_ATT(4); else TF_ATT(8);
+#undef TF_ATT
+    }
+  }
+  if (pick == FLOPE_TF_ATTN_GENERIC)
+    hipLaunchKernelGGL((tf_attn_generic<T, true>), grid, block, l.lds, st, (const T*)qkv, (T*)att, max_len, d, H, off);
+  TF_HIP(e, hipGetLastError());
+  return pick;
+}
+
+// A ragged batch as flope_tf_forward_varlen / flope_tf_attention_varlen planned it: T packed tokens, the longest length; the
+// offsets are in e->vl_off by the time the first kernel runs (uploaded on the same stream).
+struct TfRagged { int T, max_len; };
+
+// Validates and plans a ragged batch into e->vl_host and enqueues the upload of its batch + 1 offsets.
+int tf_plan_ragged(flope_tf_encoder* e, const char* who, const int* lengths, int B, int L, hipStream_t st, TfRagged* rg) {
+  int bad = -1;
+  const int rc = flope_tf_plan::tf_varlen_plan(lengths, B, L, e->max_tokens, e->vl_host.data(), &rg->T, &rg->max_len, &bad);
+  const std::string w(who);
+  switch (rc) {
+    case flope_tf_plan::kTfVarlenOk: break;
+    case flope_tf_plan::kTfVarlenBatch: return tf_fail(e, FLOPE_EINVAL, w + ": batch must be positive and lengths_host non-NULL");
+    case flope_tf_plan::kTfVarlenLength:
+      return tf_fail(e, FLOPE_EINVAL, w + ": lengths[" + std::to_string(bad) + "] = " + std::to_string(lengths[bad]) + " is outside 1 .. " + std::to_string(L) +
+                                          (lengths[bad] == 0 ? " (an empty sequence has no softmax; drop it from the batch)" : ""));
+    case flope_tf_plan::kTfVarlenTokens: return tf_fail(e, FLOPE_EINVAL, w + ": the sum of lengths exceeds max_tokens given to flope_tf_create");
+    default: return tf_fail(e, FLOPE_EINVAL, w + ": the sum of lengths overflows int");
+  }
+  // pageable source: the runtime has staged it when the call returns, so the next call may overwrite vl_host
+  TF_HIP(e, hipMemcpyAsync(e->vl_off, e->vl_host.data(), (size_t)(B + 1) * sizeof(int), hipMemcpyHostToDevice, st));
+  return 0;
+}
+
+// rg == nullptr: the fixed-length forward, x [B][L][in] -> y [B][L][out].  Otherwise the ragged one: the valid rows of x are gathered
+// into rg->T packed rows, every linear and LayerNorm runs on those, attention per sequence, and the result is scattered into y.
+template <typename T>
+int run_forward(flope_tf_encoder* e, const float* x, int B, int L, float* y, hipStream_t st, const TfRagged* rg = nullptr) {
+  const int M = rg ? rg->T : B * L, d = e->d;
   int rc;
-  if ((rc = launch_linear<T>(e, e->emb, x, 1, nullptr, e->h, 0, M, 0, st))) return rc;
+  if (rg) {
+    const bool cast = !std::is_same<T, float>::value && e->emb.packed && !e->opt_generic;     // where launch_linear would run tf_cast_pad
+    const int Kp = cast ? e->emb.Kp : e->in_dim;
+    const size_t tot = (size_t)B * L * Kp;
+    const dim3 grid((unsigned)((tot + 255) / 256));
+    if (cast) hipLaunchKernelGGL((tf_gather_rows<T>), grid, dim3(256), 0, st, x, (T*)e->xin, e->vl_off, L, e->in_dim, Kp, tot);
+    else hipLaunchKernelGGL((tf_gather_rows<float>), grid, dim3(256), 0, st, x, e->xpk, e->vl_off, L, e->in_dim, Kp, tot);
+    TF_HIP(e, hipGetLastError());
+    if ((rc = launch_linear<T>(e, e->emb, cast ? (const void*)e->xin : (const void*)e->xpk, cast ? 0 : 1, nullptr, e->h, 0, M, 0, st))) return rc;
+  } else if ((rc = launch_linear<T>(e, e->emb, x, 1, nullptr, e->h, 0, M, 0, st))) return rc;
   for (TfLayer& ly : e->layers) {
     if ((rc = launch_linear<T>(e, ly.in_proj, e->h, 0, nullptr, e->qkv, 0, M, 0, st))) return rc;
-    if ((rc = launch_attention<T>(e, e->qkv, e->att, B, L, st)) < 0) return rc;
+    if ((rc = rg ? launch_attention_varlen<T>(e, e->qkv, e->att, B, rg->max_len, e->vl_off, st) : launch_attention<T>(e, e->qkv, e->att, B, L, st)) < 0) return rc;
     if ((rc = launch_linear<T>(e, ly.out_proj, e->att, 0, e->h, e->h2, 0, M, 0, st))) return rc;
     auto ln = [&](const void* in, void* out, const float* w, const float* b) {
       if constexpr (!std::is_same<T, float>::value) {
@@ -1127,7 +1254,13 @@ int run_forward(flope_tf_encoder* e, const float* x, int B, int L, float* y, hip
     ln(e->h2, e->h, ly.n2w, ly.n2b);
     TF_HIP(e, hipGetLastError());
   }
-  return launch_linear<T>(e, e->outl, e->h, 0, nullptr, y, 1, M, 0, st);
+  if (!rg) return launch_linear<T>(e, e->outl, e->h, 0, nullptr, y, 1, M, 0, st);
+  if ((rc = launch_linear<T>(e, e->outl, e->h, 0, nullptr, e->ypk, 1, M, 0, st))) return rc;
+  const size_t tot = (size_t)B * L * e->out_dim;
+  hipLaunchKernelGGL(tf_scatter_rows, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, (const float*)e->ypk, (const float*)e->outl.b, y, e->vl_off, L,
+                     e->out_dim, tot);
+  TF_HIP(e, hipGetLastError());
+  return 0;
 }
 
 }  // namespace
@@ -1164,9 +1297,21 @@ extern "C" int flope_tf_create(int device_id, int input_dim, int model_dim, int 
     e->allocs.push_back(*bf.p);
     if (hipMemset(*bf.p, 0, bytes) != hipSuccess) return fin(tf_fail(nullptr, FLOPE_EHIP, "flope_tf_create: hipMemset failed"));
   }
+  {                                                  // ragged batches: nothing is allocated in a forward
+    struct { void** p; size_t bytes; } vb[] = {{(void**)&e->xpk, (size_t)e->Mpad * input_dim * sizeof(float)}, {(void**)&e->ypk, (size_t)e->Mpad * out_dim * sizeof(float)},
+                                               {(void**)&e->vl_off, ((size_t)max_tokens + 1) * sizeof(int)}};
+    for (auto& bf : vb) {
+      if (hipMalloc(bf.p, bf.bytes) != hipSuccess) return fin(tf_fail(nullptr, FLOPE_EHIP, "flope_tf_create: hipMalloc failed"));
+      e->allocs.push_back(*bf.p);
+      if (hipMemset(*bf.p, 0, bf.bytes) != hipSuccess) return fin(tf_fail(nullptr, FLOPE_EHIP, "flope_tf_create: hipMemset failed"));
+    }
+    e->vl_host.assign((size_t)max_tokens + 1, 0);
+  }
   {                                                  // per create: the attribute is per device (a process-wide flag would leave a second GPU without it)
     hipFuncSetAttribute((const void*)tf_attn_mfma<f16_t>, hipFuncAttributeMaxDynamicSharedMemorySize, 131072);
     hipFuncSetAttribute((const void*)tf_attn_mfma<bf16_t>, hipFuncAttributeMaxDynamicSharedMemorySize, 131072);
+    hipFuncSetAttribute((const void*)tf_attn_mfma<f16_t, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 131072);
+    hipFuncSetAttribute((const void*)tf_attn_mfma<bf16_t, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 131072);
 #define TF_ATTR(T_, A_, B_) hipFuncSetAttribute((const void*)tf_gemm_mfma<T_, A_, B_>, hipFuncAttributeMaxDynamicSharedMemorySize, 65536)
     TF_ATTR(f16_t, false, false); TF_ATTR(f16_t, false, true); TF_ATTR(f16_t, true, false); TF_ATTR(f16_t, true, true);
     TF_ATTR(bf16_t, false, false); TF_ATTR(bf16_t, false, true); TF_ATTR(bf16_t, true, false); TF_ATTR(bf16_t, true, true);
@@ -1174,12 +1319,14 @@ extern "C" int flope_tf_create(int device_id, int input_dim, int model_dim, int 
     const void* const f32m[] = {(const void*)tf_linear_f32m<4, false, false>, (const void*)tf_linear_f32m<4, true, false>, (const void*)tf_linear_f32m<4, false, true>,
                                 (const void*)tf_linear_f32m<2, false, false>, (const void*)tf_linear_f32m<2, true, false>, (const void*)tf_linear_f32m<2, false, true>,
                                 (const void*)tf_linear_f32m<1, false, false>, (const void*)tf_linear_f32m<1, true, false>, (const void*)tf_linear_f32m<1, false, true>,
-                                (const void*)tf_attn_f32m<1>, (const void*)tf_attn_f32m<2>, (const void*)tf_attn_f32m<4>, (const void*)tf_attn_f32m<8>};
+                                (const void*)tf_attn_f32m<1>, (const void*)tf_attn_f32m<2>, (const void*)tf_attn_f32m<4>, (const void*)tf_attn_f32m<8>,
+                                (const void*)tf_attn_f32m<1, true>, (const void*)tf_attn_f32m<2, true>, (const void*)tf_attn_f32m<4, true>, (const void*)tf_attn_f32m<8, true>};
     for (const void* f : f32m)
       if (hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kTfAttnLds) != hipSuccess)
         return fin(tf_fail(nullptr, FLOPE_EHIP, "flope_tf_create: hipFuncSetAttribute failed"));
     // tf_attn_tiled: 16 / 32 / 48 / 64 KiB; the widest sits at the 64 KiB a launch gets without asking
-    const void* const tiled[] = {(const void*)tf_attn_tiled<f16_t, 4>, (const void*)tf_attn_tiled<bf16_t, 4>};
+    const void* const tiled[] = {(const void*)tf_attn_tiled<f16_t, 4>, (const void*)tf_attn_tiled<bf16_t, 4>,
+                                 (const void*)tf_attn_tiled<f16_t, 4, true>, (const void*)tf_attn_tiled<bf16_t, 4, true>};
     for (const void* f : tiled)
       if (hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)flope_tf_plan::tf_attn_tiled_lds(128)) != hipSuccess)
         return fin(tf_fail(nullptr, FLOPE_EHIP, "flope_tf_create: hipFuncSetAttribute failed"));
@@ -1311,12 +1458,60 @@ extern "C" int flope_tf_attention(flope_tf_handle e, const void* qkv_dev, int ba
   return launch_attention<bf16_t>(e, qkv_dev, out_dev, batch, seq_len, st);
 }
 
+extern "C" int flope_tf_forward_varlen(flope_tf_handle e, const float* x_dev, int batch, int seq_len, const int* lengths_host, float* y_dev, void* stream) {
+  if (!e) return tf_fail(nullptr, FLOPE_EINVAL, "flope_tf_forward_varlen: NULL handle");
+  if (!e->loaded) return tf_fail(e, FLOPE_ESTATE, "flope_tf_forward_varlen: weights not loaded");
+  if (!x_dev || !y_dev) return tf_fail(e, FLOPE_EINVAL, "flope_tf_forward_varlen: NULL buffer");
+  if (seq_len < 1) return tf_fail(e, FLOPE_EINVAL, "flope_tf_forward_varlen: non-positive seq_len");
+  const size_t widest = (size_t)(e->emb.Kp > e->out_dim ? e->emb.Kp : e->out_dim);
+  if (batch > 0 && (size_t)batch * seq_len > (size_t)INT32_MAX * 256 / widest)          // the row-copy kernels' grids
+    return tf_fail(e, FLOPE_EINVAL, "flope_tf_forward_varlen: batch*seq_len too large for one launch");
+  TF_HIP(e, hipSetDevice(e->device));
+  hipStream_t st = (hipStream_t)stream;
+  TfRagged rg;
+  int rc;
+  if ((rc = tf_plan_ragged(e, "flope_tf_forward_varlen", lengths_host, batch, seq_len, st, &rg))) return rc;
+  if (e->dtype == FLOPE_DT_F32) return run_forward<float>(e, x_dev, batch, seq_len, y_dev, st, &rg);
+  if (e->dtype == FLOPE_DT_F16) return run_forward<f16_t>(e, x_dev, batch, seq_len, y_dev, st, &rg);
+  return run_forward<bf16_t>(e, x_dev, batch, seq_len, y_dev, st, &rg);
+}
+
+extern "C" int flope_tf_attention_varlen(flope_tf_handle e, const void* qkv_dev, int batch, const int* lengths_host, void* out_dev, void* stream) {
+  if (!e) return tf_fail(nullptr, FLOPE_EINVAL, "flope_tf_attention_varlen: NULL handle");
+  if (!qkv_dev || !out_dev) return tf_fail(e, FLOPE_EINVAL, "flope_tf_attention_varlen: NULL buffer");
+  if (((uintptr_t)qkv_dev | (uintptr_t)out_dev) & (uintptr_t)(e->esz - 1))
+    return tf_fail(e, FLOPE_EINVAL, "flope_tf_attention_varlen: buffer not aligned to its element type");
+  TF_HIP(e, hipSetDevice(e->device));
+  hipStream_t st = (hipStream_t)stream;
+  TfRagged rg;
+  int rc;
+  if ((rc = tf_plan_ragged(e, "flope_tf_attention_varlen", lengths_host, batch, e->max_tokens, st, &rg))) return rc;   // no padded length here: a length is bounded by max_tokens
+  if (e->dtype == FLOPE_DT_F32) return launch_attention_varlen<float>(e, qkv_dev, out_dev, batch, rg.max_len, e->vl_off, st);
+  if (e->dtype == FLOPE_DT_F16) return launch_attention_varlen<f16_t>(e, qkv_dev, out_dev, batch, rg.max_len, e->vl_off, st);
+  return launch_attention_varlen<bf16_t>(e, qkv_dev, out_dev, batch, rg.max_len, e->vl_off, st);
+}
+
 // algorithmic FLOPs of one forward (2*MAC: linears + QK^T + PV)
 extern "C" double flope_tf_forward_flops(flope_tf_handle e, int batch, int seq_len) {
   if (!e) return 0.0;
   const double M = (double)batch * seq_len, d = e->d;
   double mac = M * e->in_dim * d + M * d * e->out_dim;
   mac += e->nl * (M * d * 3 * d + M * d * d + 2.0 * M * d * e->ff + 2.0 * M * seq_len * d);
+  return 2.0 * mac;
+}
+
+// algorithmic FLOPs of one ragged forward: the linears on T = sum lengths tokens, attention on sum lengths^2; 0 for an invalid batch
+extern "C" double flope_tf_forward_flops_varlen(flope_tf_handle e, int batch, const int* lengths_host) {
+  if (!e || batch < 1 || !lengths_host) return 0.0;
+  double M = 0.0, sq = 0.0;
+  for (int b = 0; b < batch; ++b) {
+    if (lengths_host[b] < 1) return 0.0;
+    M += lengths_host[b];
+    sq += (double)lengths_host[b] * lengths_host[b];
+  }
+  const double d = e->d;
+  double mac = M * e->in_dim * d + M * d * e->out_dim;
+  mac += e->nl * (M * d * 3 * d + M * d * d + 2.0 * M * d * e->ff + 2.0 * sq * d);
   return 2.0 * mac;
 }
 

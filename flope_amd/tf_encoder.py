@@ -1,6 +1,8 @@
 """Host-side mirror of the reference's `TransformerEncoder` (scripts/tf_encoder.py:5-27) over the
 C-ABI `flope_tf_*` (include/flope_amd.h).  Same constructor arguments, same state_dict names, same
-call: `enc(x)` with x float32 [B, L, input_dim] on the GPU -> float32 [B, L, out_dim].
+call: `enc(x)` with x float32 [B, L, input_dim] on the GPU -> float32 [B, L, out_dim].  Right-padded
+ragged batches take `lengths=` (or torch's `src_key_padding_mask=`): each sequence is encoded alone at
+its own length, rows behind it come back as `out_layer.bias`, as from the reference module.
 
 Eval-mode semantics only (dropout is identity), as everywhere in this package.  There is no CPU
 path: construction fails loudly without a HIP device or without the built library.
@@ -23,6 +25,34 @@ def expected_keys(num_layers: int) -> list:
                                  "self_attn.out_proj.bias", "linear1.weight", "linear1.bias", "linear2.weight",
                                  "linear2.bias", "norm1.weight", "norm1.bias", "norm2.weight", "norm2.bias")]
     return keys + ["out_layer.weight", "out_layer.bias"]
+
+
+def _host_lengths(lengths, batch):
+    """lengths (a sequence or a CPU integer tensor of `batch` values) -> a ctypes int array"""
+    if isinstance(lengths, torch.Tensor):
+        if lengths.is_cuda or lengths.dtype.is_floating_point or lengths.dtype == torch.bool:
+            raise ValueError("lengths must be a sequence or a CPU integer tensor (grid sizes are computed from it on the host)")
+        lengths = lengths.reshape(-1).tolist()
+    vals = [int(v) for v in lengths]
+    if len(vals) != batch:
+        raise ValueError(f"lengths has {len(vals)} values for a batch of {batch}")
+    if any(v < -2 ** 31 or v >= 2 ** 31 for v in vals):
+        raise ValueError("a length does not fit an int")
+    return (C.c_int * len(vals))(*vals)
+
+
+def _mask_to_lengths(mask, B, L):
+    """torch's src_key_padding_mask (bool [B, L], True = padding) -> lengths; only right padding has a packed form"""
+    mask = torch.as_tensor(mask)
+    if mask.dtype != torch.bool or tuple(mask.shape) != (B, L):
+        raise ValueError(f"src_key_padding_mask must be a bool tensor {(B, L)}, got {mask.dtype} {tuple(mask.shape)}")
+    valid = ~mask.cpu()
+    lengths = valid.sum(dim=1)
+    prefix = torch.arange(L)[None, :] < lengths[:, None]
+    wrong = ((valid != prefix).any(dim=1) | (lengths == 0)).nonzero().reshape(-1).tolist()
+    if wrong:
+        raise ValueError(f"src_key_padding_mask row {wrong[0]}: the valid entries must form a non-empty prefix of the row (right padding)")
+    return lengths.tolist()
 
 
 class TransformerEncoder:
@@ -88,31 +118,73 @@ class TransformerEncoder:
     def set_option(self, name: str, value: int) -> int:
         return self.lib.flope_tf_set_option(self.handle, name.encode(), int(value))
 
-    def flops(self, batch: int, seq_len: int) -> float:
-        return self.lib.flope_tf_forward_flops(self.handle, batch, seq_len)
+    def flops(self, batch: int, seq_len: int, lengths=None) -> float:
+        if lengths is None:
+            return self.lib.flope_tf_forward_flops(self.handle, batch, seq_len)
+        return self.lib.flope_tf_forward_flops_varlen(self.handle, batch, _host_lengths(lengths, batch))
 
-    def forward(self, x: torch.Tensor) -> torch.Tensor:
+    # The ragged entry points have a checker of their own, on purpose: a refused batch (FLOPE_EINVAL: a bad length, too many
+    # tokens) is the caller's argument and raises ValueError, where _check keeps raising RuntimeError for the fixed-length calls,
+    # whose behaviour stays as it was.  For the same reason only the ragged calls are wrapped in torch.cuda.device().
+    def _check_varlen(self, rc):
+        if rc < 0:
+            msg = self.lib.flope_tf_last_error(self.handle)
+            msg = msg.decode() if msg else ""
+            raise (ValueError if rc == _lib.EINVAL else RuntimeError)(f"flope_amd error {rc}: {msg}")
+
+    def forward(self, x: torch.Tensor, lengths=None, src_key_padding_mask=None) -> torch.Tensor:
+        """x [B, L, input_dim] -> [B, L, out_dim].  `lengths`: a sequence or CPU integer tensor of B values, 1 <= lengths[b] <= L --
+        sequence b is x[b, :lengths[b]], the rows behind it are padding (never read) and come back as out_layer.bias.
+        `src_key_padding_mask`: bool [B, L], True = padding (torch's convention); it must mask a suffix of every row and is turned
+        into lengths on the host.  With neither, every sequence has length L (the fixed-length path, unchanged)."""
         if not x.is_cuda or x.device != self.device:
             raise RuntimeError(f"input must live on {self.device} (got {x.device}); no CPU path")
         if x.dim() != 3 or x.shape[2] != self.dims[0]:
             raise ValueError(f"expected [B, L, {self.dims[0]}], got {tuple(x.shape)}")
+        if lengths is not None and src_key_padding_mask is not None:
+            raise ValueError("give lengths or src_key_padding_mask, not both")
         x = x.to(torch.float32).contiguous()
         B, L = x.shape[0], x.shape[1]
+        if src_key_padding_mask is not None:
+            lengths = _mask_to_lengths(src_key_padding_mask, B, L)
         y = torch.empty((B, L, self.dims[2]), dtype=torch.float32, device=self.device)
-        self._check(self.lib.flope_tf_forward(self.handle, x.data_ptr(), B, L, y.data_ptr(), _stream_ptr(self.device)))
+        if lengths is None:
+            self._check(self.lib.flope_tf_forward(self.handle, x.data_ptr(), B, L, y.data_ptr(), _stream_ptr(self.device)))
+        else:
+            with torch.cuda.device(self.device):
+                self._check_varlen(self.lib.flope_tf_forward_varlen(self.handle, x.data_ptr(), B, L, _host_lengths(lengths, B), y.data_ptr(),
+                                                                    _stream_ptr(self.device)))
         self._keep = x
         return y
 
     __call__ = forward
 
-    def attention(self, qkv: torch.Tensor, out: torch.Tensor = None) -> torch.Tensor:
+    def attention(self, qkv: torch.Tensor, lengths=None, out: torch.Tensor = None) -> torch.Tensor:
         """softmax(q k^T / sqrt(head_dim)) v per head of qkv [B, L, 3 * model_dim] in the handle's dtype -> [B, L, model_dim], by
         the kernel a forward of this (B, L) would launch under the current options; its id is kept in `last_attn_kernel`.  Needs no
-        weights.  `out`: a contiguous tensor of the result's shape and dtype to write into."""
+        weights.  `out`: a contiguous tensor of the result's shape and dtype to write into.
+        With `lengths` (B values), qkv is the packed 2-D [T, 3 * model_dim] of a ragged batch, T = sum(lengths), sequence b at rows
+        sum(lengths[:b]) onwards; the result is the packed [T, model_dim]."""
         tdt = {"f16": torch.float16, "bf16": torch.bfloat16}.get(self.dtype, torch.float32)
         d = self.dims[1]
         if not qkv.is_cuda or qkv.device != self.device:
             raise RuntimeError(f"input must live on {self.device} (got {qkv.device}); no CPU path")
+        if lengths is not None:
+            n = len(lengths)
+            lh = _host_lengths(lengths, n)
+            T = sum(int(v) for v in lh)
+            if qkv.dim() != 2 or qkv.shape[1] != 3 * d or qkv.dtype != tdt or not qkv.is_contiguous() or qkv.shape[0] != T:
+                raise ValueError(f"expected a contiguous {tdt} tensor [{T}, {3 * d}] (T = sum(lengths)), got {qkv.dtype} {tuple(qkv.shape)}")
+            if out is None:
+                out = torch.empty((T, d), dtype=tdt, device=self.device)
+            elif out.shape != (T, d) or out.dtype != tdt or out.device != self.device or not out.is_contiguous():
+                raise ValueError(f"out must be a contiguous {tdt} tensor {(T, d)} on {self.device}")
+            with torch.cuda.device(self.device):
+                rc = self.lib.flope_tf_attention_varlen(self.handle, qkv.data_ptr(), n, lh, out.data_ptr(), _stream_ptr(self.device))
+            self._check_varlen(rc)
+            self.last_attn_kernel = rc
+            self._keep = qkv
+            return out
         if qkv.dim() != 3 or qkv.shape[2] != 3 * d or qkv.dtype != tdt or not qkv.is_contiguous():
             raise ValueError(f"expected a contiguous {tdt} tensor [B, L, {3 * d}], got {qkv.dtype} {tuple(qkv.shape)}")
         B, L = qkv.shape[0], qkv.shape[1]

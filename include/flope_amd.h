@@ -296,7 +296,7 @@ int flope_frame_read_gaps(flope_frame_handle f, int slot, float* gap_host, int c
  * K % 4 == 0 and every attention with head_dim % 4 == 0, head_dim <= 128 and 16 score rows of seq_len floats within 160 KiB of LDS
  * on v_mfma_f32_16x16x4_f32 (exact float32 products and sums: differs from the strict mode in summation order only); the other
  * ops of the handle stay on the generic kernels, LayerNorm is unchanged.
- * max_tokens bounds batch*seq_len of any later forward.  Same ownership / error rules as above. */
+ * max_tokens bounds batch*seq_len of any later forward (the token count of a ragged one).  Same ownership / error rules as above. */
 typedef struct flope_tf_encoder* flope_tf_handle;
 int flope_tf_create(int device_id, int input_dim, int model_dim, int out_dim, int num_heads,
                     int num_layers, int ff_dim, int max_tokens, int dtype, flope_tf_handle* out);
@@ -332,6 +332,23 @@ int flope_tf_set_option(flope_tf_handle h, const char* name, int value);
 int flope_tf_attention(flope_tf_handle h, const void* qkv_dev, int batch, int seq_len, void* out_dev, void* stream);
 /* algorithmic FLOPs of one forward (2*MAC: linears + QK^T + PV) */
 double flope_tf_forward_flops(flope_tf_handle h, int batch, int seq_len);
+/* Ragged batches: x_dev float32 [batch, seq_len, input_dim] whose sequence b consists of rows 0 .. lengths_host[b] - 1,
+ * 1 <= lengths_host[b] <= seq_len (nn.TransformerEncoder's src_key_padding_mask for right-padded batches).  Rows behind a sequence are
+ * padding: never read, they may hold NaN.  y_dev float32 [batch, seq_len, out_dim] is fully written: rows < lengths_host[b] are the
+ * encoder applied to that sequence alone, bit for bit what flope_tf_forward gives it at (1, lengths_host[b]); rows behind them hold
+ * out_layer.bias (what the reference module returns there).  Inside the handle the batch is T = sum of lengths packed tokens:
+ * padding costs no FLOPs and no bytes behind the input gather, and the limit is T <= max_tokens (batch*seq_len may exceed it).
+ * lengths_host is a host array of batch ints (grid sizes and the kernel choice need its maximum and its sum); it is read before the
+ * call returns.  One attention kernel per launch, chosen for the longest sequence.  FLOPE_EINVAL for batch < 1, a length of 0 (torch
+ * returns NaN there; this library does not), a length > seq_len, or T > max_tokens.  All options keep their meaning. */
+int flope_tf_forward_varlen(flope_tf_handle h, const float* x_dev, int batch, int seq_len, const int* lengths_host, float* y_dev,
+                            void* stream);
+/* flope_tf_attention for a ragged batch: packed qkv_dev [T, 3*model_dim] -> packed out_dev [T, model_dim] in the handle's dtype,
+ * sequence b = rows sum(lengths_host[0 .. b-1]) onwards.  Launches exactly what flope_tf_forward_varlen would for these lengths under
+ * the handle's current options; needs no weights.  Returns the FLOPE_TF_ATTN_* id of the kernel launched, or < 0.  T <= max_tokens. */
+int flope_tf_attention_varlen(flope_tf_handle h, const void* qkv_dev, int batch, const int* lengths_host, void* out_dev, void* stream);
+/* algorithmic FLOPs of one ragged forward: the linears on T tokens, attention on the sum of lengths squared; 0 for an invalid batch */
+double flope_tf_forward_flops_varlen(flope_tf_handle h, int batch, const int* lengths_host);
 
 /* ---- YOLO11-seg detector front end ---------------------------------------------------
  * Replaces `self.yolo = YOLO(yolo_path)` (sunflower/predictor/fast_pose_predictor.py:36) and the
