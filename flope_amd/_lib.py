@@ -12,6 +12,8 @@ DT_BF16, DT_F16, DT_F32 = 0, 1, 2
 EINVAL = -1                                                                      # FLOPE_EINVAL of include/flope_amd.h
 IN_F32_NCHW, IN_BF16_NHWC, IN_F16_NHWC, IN_U8_NHWC = 0, 1, 2, 3
 TF_ATTN_GENERIC, TF_ATTN_MFMA64, TF_ATTN_TILED, TF_ATTN_F32M = 0, 1, 2, 3     # flope_tf_attention's return (tf_attn_plan.h)
+TF_LIN_GENERIC, TF_LIN_ROWWAVE, TF_LIN_ROWWAVE_VEC, TF_LIN_MFMA, TF_LIN_F32M = 0, 1, 2, 3, 4      # flope_tf_linear's return
+TF_LN_SCALAR, TF_LN_VEC = 0, 1                                                 # flope_tf_layernorm's return
 STAGE_STEM, STAGE_POOL, STAGE_FEAT, STAGE_HIDDEN = 0, 1, 10, 11
 
 
@@ -97,6 +99,8 @@ SIGNATURES = {
     "flope_tf_set_option": (_I, [_P, C.c_char_p, _I]),
     "flope_tf_forward_flops": (_D, [_P, _I, _I]),
     "flope_tf_attention": (_I, [_P, _P, _I, _I, _P, _P]),
+    "flope_tf_linear": (_I, [_P, C.c_char_p, _P, _I, _P, _P, _I, _I, _I, _P]),
+    "flope_tf_layernorm": (_I, [_P, _P, _P, _P, _P, _I, _P]),
     "flope_tf_forward_varlen": (_I, [_P, _P, _I, _I, C.POINTER(_I), _P, _P]),
     "flope_tf_attention_varlen": (_I, [_P, _P, _I, C.POINTER(_I), _P, _P]),
     "flope_tf_forward_flops_varlen": (_D, [_P, _I, C.POINTER(_I)]),

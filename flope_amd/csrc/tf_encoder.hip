@@ -1063,6 +1063,9 @@ template <typename V> int tf_upload(flope_tf_encoder* e, const V* src, size_t co
   return 0;
 }
 
+// One linear under the handle's options; returns the FLOPE_TF_LIN_* id of the kernel launched, or < 0.  The 16-bit vector paths
+// (tf_gemm_mfma, tf_linear_rowwave_vec) take X, R and Y 16-byte aligned and, tf_gemm_mfma, allocated for whole 128-row tiles: true of
+// the handle's own buffers, checked for a caller's by flope_tf_linear.
 template <typename T>
 int launch_linear(flope_tf_encoder* e, const TfLinear& l, const void* X, int x_f32, const void* R, void* Y, int y_f32,
                   int M, int relu, hipStream_t st) {
@@ -1079,7 +1082,7 @@ int launch_linear(flope_tf_encoder* e, const TfLinear& l, const void* X, int x_f
 #undef TF_GO2
 #undef TF_GO3
       TF_HIP(e, hipGetLastError());
-      return 0;
+      return FLOPE_TF_LIN_F32M;
     }
   }
   if (l.packed && !y_f32 && !e->opt_generic) {
@@ -1097,7 +1100,7 @@ int launch_linear(flope_tf_encoder* e, const TfLinear& l, const void* X, int x_f
       if (relu && R) TF_GO(true, true); else if (relu) TF_GO(true, false); else if (R) TF_GO(false, true); else TF_GO(false, false);
 #undef TF_GO
       TF_HIP(e, hipGetLastError());
-      return 0;
+      return FLOPE_TF_LIN_MFMA;
     }
   }
   if constexpr (!std::is_same<T, float>::value) {
@@ -1105,20 +1108,36 @@ int launch_linear(flope_tf_encoder* e, const TfLinear& l, const void* X, int x_f
       const int blocks = (M + 7) / 8 < 2048 ? (M + 7) / 8 : 2048;
       hipLaunchKernelGGL((tf_linear_rowwave_vec<T>), dim3(blocks), dim3(256), (size_t)l.N * l.K * 4, st, (const T*)X, l.w, l.b, Y, y_f32, M, l.K, l.N, relu);
       TF_HIP(e, hipGetLastError());
-      return 0;
+      return FLOPE_TF_LIN_ROWWAVE_VEC;
     }
   }
   if (l.N <= 16 && !R) {
     const int blocks = (M + 3) / 4 < 8192 ? (M + 3) / 4 : 8192;
     hipLaunchKernelGGL((tf_linear_rowwave<T>), dim3(blocks), dim3(256), 0, st, X, x_f32, l.w, l.b, Y, y_f32, M, l.K, l.N, relu);
     TF_HIP(e, hipGetLastError());
-    return 0;
+    return FLOPE_TF_LIN_ROWWAVE;
   }
   const size_t total = (size_t)M * l.N;
   hipLaunchKernelGGL((tf_linear_generic<T>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, X, x_f32, l.w, l.b,
                      R, Y, y_f32, M, l.K, l.N, relu);
   TF_HIP(e, hipGetLastError());
-  return 0;
+  return FLOPE_TF_LIN_GENERIC;
+}
+
+// LayerNorm over the last dimension of M rows of d (eps 1e-5, biased variance); returns the FLOPE_TF_LN_* id of the kernel, or < 0
+template <typename T>
+int launch_layernorm(flope_tf_encoder* e, const void* in, void* out, const float* w, const float* b, int M, hipStream_t st) {
+  const int d = e->d;
+  int id = FLOPE_TF_LN_SCALAR;
+  if constexpr (!std::is_same<T, float>::value) {
+    if (d % 8 == 0 && d <= 2048) id = FLOPE_TF_LN_VEC;
+  }
+  if constexpr (!std::is_same<T, float>::value) {
+    if (id == FLOPE_TF_LN_VEC) hipLaunchKernelGGL((tf_layernorm_vec<T>), dim3((M + 3) / 4), dim3(256), 0, st, (const T*)in, (T*)out, w, b, M, d);
+  }
+  if (id == FLOPE_TF_LN_SCALAR) hipLaunchKernelGGL((tf_layernorm<T>), dim3((M + 3) / 4), dim3(256), 0, st, (const T*)in, (T*)out, w, b, M, d);
+  TF_HIP(e, hipGetLastError());
+  return id;
 }
 
 // One attention launch: softmax(q k^T / sqrt(head_dim)) v per head, qkv [B][L][3 d] -> att [B][L][d].  The kernel is the one
@@ -1223,7 +1242,7 @@ int tf_plan_ragged(flope_tf_encoder* e, const char* who, const int* lengths, int
 // into rg->T packed rows, every linear and LayerNorm runs on those, attention per sequence, and the result is scattered into y.
 template <typename T>
 int run_forward(flope_tf_encoder* e, const float* x, int B, int L, float* y, hipStream_t st, const TfRagged* rg = nullptr) {
-  const int M = rg ? rg->T : B * L, d = e->d;
+  const int M = rg ? rg->T : B * L;
   int rc;
   if (rg) {
     const bool cast = !std::is_same<T, float>::value && e->emb.packed && !e->opt_generic;     // where launch_linear would run tf_cast_pad
@@ -1233,29 +1252,19 @@ int run_forward(flope_tf_encoder* e, const float* x, int B, int L, float* y, hip
     if (cast) hipLaunchKernelGGL((tf_gather_rows<T>), grid, dim3(256), 0, st, x, (T*)e->xin, e->vl_off, L, e->in_dim, Kp, tot);
     else hipLaunchKernelGGL((tf_gather_rows<float>), grid, dim3(256), 0, st, x, e->xpk, e->vl_off, L, e->in_dim, Kp, tot);
     TF_HIP(e, hipGetLastError());
-    if ((rc = launch_linear<T>(e, e->emb, cast ? (const void*)e->xin : (const void*)e->xpk, cast ? 0 : 1, nullptr, e->h, 0, M, 0, st))) return rc;
-  } else if ((rc = launch_linear<T>(e, e->emb, x, 1, nullptr, e->h, 0, M, 0, st))) return rc;
+    if ((rc = launch_linear<T>(e, e->emb, cast ? (const void*)e->xin : (const void*)e->xpk, cast ? 0 : 1, nullptr, e->h, 0, M, 0, st)) < 0) return rc;
+  } else if ((rc = launch_linear<T>(e, e->emb, x, 1, nullptr, e->h, 0, M, 0, st)) < 0) return rc;
   for (TfLayer& ly : e->layers) {
-    if ((rc = launch_linear<T>(e, ly.in_proj, e->h, 0, nullptr, e->qkv, 0, M, 0, st))) return rc;
+    if ((rc = launch_linear<T>(e, ly.in_proj, e->h, 0, nullptr, e->qkv, 0, M, 0, st)) < 0) return rc;
     if ((rc = rg ? launch_attention_varlen<T>(e, e->qkv, e->att, B, rg->max_len, e->vl_off, st) : launch_attention<T>(e, e->qkv, e->att, B, L, st)) < 0) return rc;
-    if ((rc = launch_linear<T>(e, ly.out_proj, e->att, 0, e->h, e->h2, 0, M, 0, st))) return rc;
-    auto ln = [&](const void* in, void* out, const float* w, const float* b) {
-      if constexpr (!std::is_same<T, float>::value) {
-        if (d % 8 == 0 && d <= 2048) {
-          hipLaunchKernelGGL((tf_layernorm_vec<T>), dim3((M + 3) / 4), dim3(256), 0, st, (const T*)in, (T*)out, w, b, M, d);
-          return;
-        }
-      }
-      hipLaunchKernelGGL((tf_layernorm<T>), dim3((M + 3) / 4), dim3(256), 0, st, (const T*)in, (T*)out, w, b, M, d);
-    };
-    ln(e->h2, e->h, ly.n1w, ly.n1b);
-    if ((rc = launch_linear<T>(e, ly.lin1, e->h, 0, nullptr, e->ffb, 0, M, 1, st))) return rc;
-    if ((rc = launch_linear<T>(e, ly.lin2, e->ffb, 0, e->h, e->h2, 0, M, 0, st))) return rc;
-    ln(e->h2, e->h, ly.n2w, ly.n2b);
-    TF_HIP(e, hipGetLastError());
+    if ((rc = launch_linear<T>(e, ly.out_proj, e->att, 0, e->h, e->h2, 0, M, 0, st)) < 0) return rc;
+    if ((rc = launch_layernorm<T>(e, e->h2, e->h, ly.n1w, ly.n1b, M, st)) < 0) return rc;
+    if ((rc = launch_linear<T>(e, ly.lin1, e->h, 0, nullptr, e->ffb, 0, M, 1, st)) < 0) return rc;
+    if ((rc = launch_linear<T>(e, ly.lin2, e->ffb, 0, e->h, e->h2, 0, M, 0, st)) < 0) return rc;
+    if ((rc = launch_layernorm<T>(e, e->h2, e->h, ly.n2w, ly.n2b, M, st)) < 0) return rc;
   }
-  if (!rg) return launch_linear<T>(e, e->outl, e->h, 0, nullptr, y, 1, M, 0, st);
-  if ((rc = launch_linear<T>(e, e->outl, e->h, 0, nullptr, e->ypk, 1, M, 0, st))) return rc;
+  if (!rg) return (rc = launch_linear<T>(e, e->outl, e->h, 0, nullptr, y, 1, M, 0, st)) < 0 ? rc : 0;
+  if ((rc = launch_linear<T>(e, e->outl, e->h, 0, nullptr, e->ypk, 1, M, 0, st)) < 0) return rc;
   const size_t tot = (size_t)B * L * e->out_dim;
   hipLaunchKernelGGL(tf_scatter_rows, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, (const float*)e->ypk, (const float*)e->outl.b, y, e->vl_off, L,
                      e->out_dim, tot);
@@ -1456,6 +1465,62 @@ extern "C" int flope_tf_attention(flope_tf_handle e, const void* qkv_dev, int ba
   if (e->dtype == FLOPE_DT_F32) return launch_attention<float>(e, qkv_dev, out_dev, batch, seq_len, st);
   if (e->dtype == FLOPE_DT_F16) return launch_attention<f16_t>(e, qkv_dev, out_dev, batch, seq_len, st);
   return launch_attention<bf16_t>(e, qkv_dev, out_dev, batch, seq_len, st);
+}
+
+extern "C" int flope_tf_linear(flope_tf_handle e, const char* name, const void* x_dev, int x_f32, const void* res_dev, void* y_dev, int y_f32, int rows,
+                               int relu, void* stream) {
+  if (!e) return tf_fail(nullptr, FLOPE_EINVAL, "flope_tf_linear: NULL handle");
+  if (!e->loaded) return tf_fail(e, FLOPE_ESTATE, "flope_tf_linear: weights not loaded");
+  if (!name || !x_dev || !y_dev) return tf_fail(e, FLOPE_EINVAL, "flope_tf_linear: NULL argument");
+  const TfLinear* l = nullptr;
+  const std::string nm(name);
+  if (nm == "embedding") l = &e->emb;
+  else if (nm == "out_layer") l = &e->outl;
+  else if (nm.compare(0, 7, "layers.") == 0) {
+    const size_t dot = nm.find('.', 7);
+    const std::string idx = dot == std::string::npos ? "" : nm.substr(7, dot - 7), op = dot == std::string::npos ? "" : nm.substr(dot + 1);
+    if (!idx.empty() && idx.size() <= 6 && idx.find_first_not_of("0123456789") == std::string::npos && std::stoi(idx) < e->nl) {
+      const TfLayer& ly = e->layers[std::stoi(idx)];
+      l = op == "in_proj" ? &ly.in_proj : op == "out_proj" ? &ly.out_proj : op == "linear1" ? &ly.lin1 : op == "linear2" ? &ly.lin2 : nullptr;
+    }
+  }
+  if (!l) return tf_fail(e, FLOPE_EINVAL, "flope_tf_linear: unknown linear " + nm + " (embedding, out_layer, layers.<i>.in_proj / out_proj / linear1 / linear2)");
+  if (rows < 1) return tf_fail(e, FLOPE_EINVAL, "flope_tf_linear: non-positive rows");
+  if (rows > e->max_tokens) return tf_fail(e, FLOPE_EINVAL, "flope_tf_linear: rows exceeds max_tokens given to flope_tf_create");
+  const uintptr_t bits = (uintptr_t)x_dev | (uintptr_t)res_dev | (uintptr_t)y_dev;
+  if (e->dtype == FLOPE_DT_F32) {
+    if (bits & 3) return tf_fail(e, FLOPE_EINVAL, "flope_tf_linear: buffer not aligned to its element type");
+  } else {
+    if (bits & 15) return tf_fail(e, FLOPE_EINVAL, "flope_tf_linear: 16-bit handles take x, res and y 16-byte aligned");
+    // tf_cast_pad writes rows of roundup(K, 64) into the handle's input copy, which is as wide as the embedding's
+    if (x_f32 && l != &e->emb && l->packed && !y_f32 && !e->opt_generic)
+      return tf_fail(e, FLOPE_EINVAL, "flope_tf_linear: a float32 input to the MFMA linear is the network input (embedding only)");
+    // ... and tf_gemm_mfma reads rows of roundup(K, 64): a 16-bit x_dev [rows, K] with K % 64 != 0 would be read past its rows
+    if (!x_f32 && l->packed && l->K != l->Kp && !y_f32 && !e->opt_generic)
+      return tf_fail(e, FLOPE_EINVAL, "flope_tf_linear: the MFMA linear with K % 64 != 0 takes its input as float32 (x_f32), which is zero-padded to roundup(K, 64) columns");
+  }
+  TF_HIP(e, hipSetDevice(e->device));
+  hipStream_t st = (hipStream_t)stream;
+  if (e->dtype == FLOPE_DT_F32) return launch_linear<float>(e, *l, x_dev, 1, res_dev, y_dev, 1, rows, relu ? 1 : 0, st);
+  if (e->dtype == FLOPE_DT_F16) return launch_linear<f16_t>(e, *l, x_dev, x_f32 ? 1 : 0, res_dev, y_dev, y_f32 ? 1 : 0, rows, relu ? 1 : 0, st);
+  return launch_linear<bf16_t>(e, *l, x_dev, x_f32 ? 1 : 0, res_dev, y_dev, y_f32 ? 1 : 0, rows, relu ? 1 : 0, st);
+}
+
+extern "C" int flope_tf_layernorm(flope_tf_handle e, const void* in_dev, void* out_dev, const float* gamma_dev, const float* beta_dev, int rows, void* stream) {
+  if (!e) return tf_fail(nullptr, FLOPE_EINVAL, "flope_tf_layernorm: NULL handle");
+  if (!in_dev || !out_dev || !gamma_dev || !beta_dev) return tf_fail(e, FLOPE_EINVAL, "flope_tf_layernorm: NULL buffer");
+  if (rows < 1) return tf_fail(e, FLOPE_EINVAL, "flope_tf_layernorm: non-positive rows");
+  if (rows > e->max_tokens) return tf_fail(e, FLOPE_EINVAL, "flope_tf_layernorm: rows exceeds max_tokens given to flope_tf_create");
+  if (((uintptr_t)gamma_dev | (uintptr_t)beta_dev) & 3) return tf_fail(e, FLOPE_EINVAL, "flope_tf_layernorm: gamma / beta not aligned to float");
+  const uintptr_t bits = (uintptr_t)in_dev | (uintptr_t)out_dev;
+  if (e->dtype == FLOPE_DT_F32 ? bits & 3 : bits & 15)
+    return tf_fail(e, FLOPE_EINVAL, e->dtype == FLOPE_DT_F32 ? "flope_tf_layernorm: buffer not aligned to its element type"
+                                                             : "flope_tf_layernorm: 16-bit handles take in and out 16-byte aligned");
+  TF_HIP(e, hipSetDevice(e->device));
+  hipStream_t st = (hipStream_t)stream;
+  if (e->dtype == FLOPE_DT_F32) return launch_layernorm<float>(e, in_dev, out_dev, gamma_dev, beta_dev, rows, st);
+  if (e->dtype == FLOPE_DT_F16) return launch_layernorm<f16_t>(e, in_dev, out_dev, gamma_dev, beta_dev, rows, st);
+  return launch_layernorm<bf16_t>(e, in_dev, out_dev, gamma_dev, beta_dev, rows, st);
 }
 
 extern "C" int flope_tf_forward_varlen(flope_tf_handle e, const float* x_dev, int batch, int seq_len, const int* lengths_host, float* y_dev, void* stream) {

@@ -80,6 +80,8 @@ class TransformerEncoder:
                 self.close()
                 raise RuntimeError(f"flope_tf_set_option(f32mfma) failed ({rc})")
         self.last_attn_kernel = None             # FLOPE_TF_ATTN_* id of the last attention() launch
+        self.last_linear_kernel = None           # FLOPE_TF_LIN_* id of the last linear() launch
+        self.last_ln_kernel = None               # FLOPE_TF_LN_* id of the last layernorm() launch
         if attn_tiled:                           # 16-bit handles: MFMA attention for head_dim 32 .. 128 at any length (0 .. 2, include/flope_amd.h)
             rc = self.lib.flope_tf_set_option(self.handle, b"attn_tiled", int(attn_tiled))
             if rc < 0:
@@ -123,10 +125,11 @@ class TransformerEncoder:
             return self.lib.flope_tf_forward_flops(self.handle, batch, seq_len)
         return self.lib.flope_tf_forward_flops_varlen(self.handle, batch, _host_lengths(lengths, batch))
 
-    # The ragged entry points have a checker of their own, on purpose: a refused batch (FLOPE_EINVAL: a bad length, too many
-    # tokens) is the caller's argument and raises ValueError, where _check keeps raising RuntimeError for the fixed-length calls,
-    # whose behaviour stays as it was.  For the same reason only the ragged calls are wrapped in torch.cuda.device().
-    def _check_varlen(self, rc):
+    # The entry points added after the fixed-length forward (the ragged calls, linear, layernorm) share this checker: a refused call
+    # (FLOPE_EINVAL: a bad length, too many tokens, a misaligned buffer, an unknown name) is the caller's argument and raises
+    # ValueError, and a result >= 0 (a kernel id) passes.  _check keeps raising RuntimeError for forward() and attention() without
+    # lengths, whose behaviour stays as it was.  For the same reason only the newer calls are wrapped in torch.cuda.device().
+    def _check_arg(self, rc):
         if rc < 0:
             msg = self.lib.flope_tf_last_error(self.handle)
             msg = msg.decode() if msg else ""
@@ -152,7 +155,7 @@ class TransformerEncoder:
             self._check(self.lib.flope_tf_forward(self.handle, x.data_ptr(), B, L, y.data_ptr(), _stream_ptr(self.device)))
         else:
             with torch.cuda.device(self.device):
-                self._check_varlen(self.lib.flope_tf_forward_varlen(self.handle, x.data_ptr(), B, L, _host_lengths(lengths, B), y.data_ptr(),
+                self._check_arg(self.lib.flope_tf_forward_varlen(self.handle, x.data_ptr(), B, L, _host_lengths(lengths, B), y.data_ptr(),
                                                                     _stream_ptr(self.device)))
         self._keep = x
         return y
@@ -181,7 +184,7 @@ class TransformerEncoder:
                 raise ValueError(f"out must be a contiguous {tdt} tensor {(T, d)} on {self.device}")
             with torch.cuda.device(self.device):
                 rc = self.lib.flope_tf_attention_varlen(self.handle, qkv.data_ptr(), n, lh, out.data_ptr(), _stream_ptr(self.device))
-            self._check_varlen(rc)
+            self._check_arg(rc)
             self.last_attn_kernel = rc
             self._keep = qkv
             return out
@@ -197,6 +200,98 @@ class TransformerEncoder:
             self._check(rc)
         self.last_attn_kernel = rc
         self._keep = qkv
+        return out
+
+    # ---- one operation of the forward on a caller's tensor (include/flope_amd.h: flope_tf_linear, flope_tf_layernorm) ----------
+    def _tdt(self):
+        return {"f16": torch.float16, "bf16": torch.bfloat16}.get(self.dtype, torch.float32)
+
+    def _padded(self, t, rows, cols, dt, what):
+        """`t` [rows, cols] as a tensor whose storage holds roundup(rows, 128) rows from its first element on (16-bit handles: the
+        MFMA linear reads and writes whole 128-row tiles).  A contiguous view with that much room behind it is used as it is,
+        anything else is copied to the head of a fresh padded allocation whose pad rows are zero."""
+        if t.device != self.device:
+            raise RuntimeError(f"{what} must live on {self.device} (got {t.device}); no CPU path")
+        if t.dim() != 2 or tuple(t.shape) != (rows, cols) or t.dtype != dt:
+            raise ValueError(f"{what}: expected a {dt} tensor [{rows}, {cols}], got {t.dtype} {tuple(t.shape)}")
+        if self.dtype in ("f32", "f32m"):
+            return t if t.is_contiguous() else t.contiguous()
+        need = (rows + 127) // 128 * 128 * cols
+        room = t.untyped_storage().nbytes() // t.element_size() - t.storage_offset()
+        if t.is_contiguous() and room >= need:
+            return t
+        big = torch.zeros(need, dtype=dt, device=self.device)
+        big[:rows * cols] = t.reshape(-1)
+        return big[:rows * cols].view(rows, cols)
+
+    def _linear_dims(self, name):
+        i, d, o, _, nl, ff = self.dims
+        if name == "embedding":
+            return d, i
+        if name == "out_layer":
+            return o, d
+        parts = name.split(".")
+        if len(parts) == 3 and parts[0] == "layers" and parts[1].isdigit() and int(parts[1]) < nl:
+            nk = {"in_proj": (3 * d, d), "out_proj": (d, d), "linear1": (ff, d), "linear2": (d, ff)}.get(parts[2])
+            if nk:
+                return nk
+        raise ValueError(f"unknown linear {name!r}: embedding, out_layer, layers.<i>.in_proj / out_proj / linear1 / linear2")
+
+    def linear(self, name, x, res=None, relu=False, out_f32=False, out=None):
+        """act(x W^T + b (+ res)) of the loaded linear `name` ("embedding", "out_layer", "layers.<i>.in_proj" / ".out_proj" /
+        ".linear1" / ".linear2") by the kernel a forward launches for it at this row count under the current options; its
+        FLOPE_TF_LIN_* id is kept in `last_linear_kernel`.  x [rows, K] in the handle's dtype, or float32 (the network input; the only form
+        an MFMA embedding with input_dim % 64 != 0 takes, since its kernel reads zero-padded rows: ValueError otherwise);
+        res [rows, N] in the handle's dtype; the result is [rows, N] in the handle's dtype, float32 with out_f32.
+        16-bit handles: x, res and the result live in storage of roundup(rows, 128) rows (the MFMA linear works on whole 128-row
+        tiles: pad rows of x and res may hold anything, those of the result are overwritten).  A tensor that is a view with that
+        much room behind it is used in place -- the result keeps its padded storage --, any other is copied into one.
+        `out`: a [rows, N] tensor to write into, under the same rule (never copied: too little room is an error)."""
+        tdt = self._tdt()
+        N, K = self._linear_dims(name)
+        if x.dim() != 2 or x.shape[1] != K:
+            raise ValueError(f"{name}: expected [rows, {K}], got {tuple(x.shape)}")
+        rows = x.shape[0]
+        f16h = self.dtype in ("f16", "bf16")
+        x_f32 = f16h and x.dtype == torch.float32
+        x = self._padded(x, rows, K, torch.float32 if x_f32 else tdt, "x")
+        if res is not None:
+            res = self._padded(res, rows, N, tdt, "res")
+        odt = torch.float32 if (out_f32 or not f16h) else tdt
+        if out is None:
+            rpad = (rows + 127) // 128 * 128 if f16h else rows
+            out = torch.empty((rpad, N), dtype=odt, device=self.device)[:rows]
+        elif self._padded(out, rows, N, odt, "out") is not out:
+            raise ValueError(f"out must be a contiguous {odt} tensor [{rows}, {N}] with storage for {(rows + 127) // 128 * 128} rows")
+        with torch.cuda.device(self.device):
+            rc = self.lib.flope_tf_linear(self.handle, name.encode(), x.data_ptr(), int(x_f32), res.data_ptr() if res is not None else None,
+                                          out.data_ptr(), int(odt == torch.float32), rows, int(bool(relu)), _stream_ptr(self.device))
+        self._check_arg(rc)
+        self.last_linear_kernel = rc
+        self._keep = (x, res)
+        return out
+
+    def layernorm(self, x, weight, bias, out=None):
+        """LayerNorm (eps 1e-5, biased variance) of x [rows, model_dim] in the handle's dtype with device float32 weight / bias
+        [model_dim], by the kernel a forward launches; its FLOPE_TF_LN_* id is kept in `last_ln_kernel`.  Needs no weights."""
+        tdt, d = self._tdt(), self.dims[1]
+        if x.device != self.device or weight.device != self.device or bias.device != self.device:
+            raise RuntimeError(f"x, weight and bias must live on {self.device}; no CPU path")
+        if x.dim() != 2 or x.shape[1] != d or x.dtype != tdt or not x.is_contiguous():
+            raise ValueError(f"expected a contiguous {tdt} tensor [rows, {d}], got {x.dtype} {tuple(x.shape)}")
+        for t in (weight, bias):
+            if tuple(t.shape) != (d,) or t.dtype != torch.float32 or not t.is_contiguous():
+                raise ValueError(f"weight and bias must be contiguous float32 [{d}]")
+        if out is None:
+            out = torch.empty_like(x)
+        elif out.shape != x.shape or out.dtype != tdt or out.device != self.device or not out.is_contiguous():
+            raise ValueError(f"out must be a contiguous {tdt} tensor {tuple(x.shape)} on {self.device}")
+        with torch.cuda.device(self.device):
+            rc = self.lib.flope_tf_layernorm(self.handle, x.data_ptr(), out.data_ptr(), weight.data_ptr(), bias.data_ptr(), x.shape[0],
+                                             _stream_ptr(self.device))
+        self._check_arg(rc)
+        self.last_ln_kernel = rc
+        self._keep = (x, weight, bias)
         return out
 
     def close(self):

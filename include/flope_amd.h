@@ -332,6 +332,36 @@ int flope_tf_set_option(flope_tf_handle h, const char* name, int value);
 int flope_tf_attention(flope_tf_handle h, const void* qkv_dev, int batch, int seq_len, void* out_dev, void* stream);
 /* algorithmic FLOPs of one forward (2*MAC: linears + QK^T + PV) */
 double flope_tf_forward_flops(flope_tf_handle h, int batch, int seq_len);
+/* One loaded linear on a caller's buffers: y = act(x W^T + b (+ res)), x_dev [rows, K] -> y_dev [rows, N], res_dev [rows, N] or NULL,
+ * relu != 0: ReLU behind the residual.  name: "embedding", "out_layer", "layers.<i>.in_proj", ".out_proj", ".linear1", ".linear2".
+ * Launches exactly what flope_tf_forward launches for that linear at this row count under the handle's current options and
+ * returns the FLOPE_TF_LIN_* id of the kernel, or < 0 and nothing launched.  Needs loaded weights (FLOPE_ESTATE) and
+ * rows <= max_tokens.  FLOPE_DT_F16 / BF16 handles: x_dev is float32 where x_f32 != 0 (the network input; with the MFMA linear only
+ * for "embedding", whose 16-bit copy the handle holds), y_dev is float32 where y_f32 != 0, res_dev is always 16-bit.  An MFMA linear
+ * with K % 64 != 0 (an "embedding" of such an input_dim) reads rows of roundup(K, 64) zero-padded columns, which only that copy
+ * has: it takes x_f32 != 0, a 16-bit x_dev is FLOPE_EINVAL.  Two contracts:
+ *   padded rows   tf_gemm_mfma (FLOPE_TF_LIN_MFMA) takes no row count: it reads x_dev and res_dev and writes y_dev in whole
+ *                 128-row tiles.  All three must be allocated for roundup(rows, 128) rows; rows >= `rows` of x_dev and res_dev may
+ *                 hold anything (NaN included) and never reach a row < `rows`; rows >= `rows` of y_dev are overwritten.  The
+ *                 library cannot check an allocation's size: the caller's duty (flope_amd.TransformerEncoder.linear does it).
+ *   alignment     x_dev, res_dev and y_dev 16-byte aligned, otherwise FLOPE_EINVAL (the 16-bit kernels load and store 16 bytes).
+ * FLOPE_DT_F32 handles: all buffers float32 (x_f32 / y_f32 ignored), aligned to 4 bytes; a pointer that is not 16-byte aligned is
+ * legal and sends an f32mfma linear to the generic kernel.  ReLU and residual together have no tf_linear_f32m form (FLOPE_EINVAL). */
+#define FLOPE_TF_LIN_GENERIC      0   /* tf_linear_generic: any shape */
+#define FLOPE_TF_LIN_ROWWAVE      1   /* tf_linear_rowwave: N <= 16, no residual */
+#define FLOPE_TF_LIN_ROWWAVE_VEC  2   /* tf_linear_rowwave_vec: 16-bit input, N <= 16, K % 8 == 0, N K floats within 48 KiB of LDS */
+#define FLOPE_TF_LIN_MFMA         3   /* tf_gemm_mfma: 16-bit, N % 128 == 0, K % 64 == 0 (embedding: K zero-padded) */
+#define FLOPE_TF_LIN_F32M         4   /* tf_linear_f32m: float32, option f32mfma, K % 4 == 0 */
+int flope_tf_linear(flope_tf_handle h, const char* name, const void* x_dev, int x_f32, const void* res_dev, void* y_dev, int y_f32,
+                    int rows, int relu, void* stream);
+/* The LayerNorm flope_tf_forward runs for this handle's dtype and model_dim (eps 1e-5, biased variance) on a caller's buffers:
+ * in_dev [rows, model_dim] -> out_dev [rows, model_dim] in the handle's dtype, gamma_dev / beta_dev device float32 [model_dim].
+ * Needs no weights.  Returns the FLOPE_TF_LN_* id of the kernel, or < 0 and nothing launched.  rows <= max_tokens; 16-bit handles
+ * take in_dev and out_dev 16-byte aligned (FLOPE_EINVAL otherwise), float32 handles 4-byte aligned.  Only `rows` rows are touched. */
+#define FLOPE_TF_LN_SCALAR        0   /* tf_layernorm: any model_dim, float32 handles always */
+#define FLOPE_TF_LN_VEC           1   /* tf_layernorm_vec: 16-bit, model_dim % 8 == 0 and <= 2048 */
+int flope_tf_layernorm(flope_tf_handle h, const void* in_dev, void* out_dev, const float* gamma_dev, const float* beta_dev, int rows,
+                       void* stream);
 /* Ragged batches: x_dev float32 [batch, seq_len, input_dim] whose sequence b consists of rows 0 .. lengths_host[b] - 1,
  * 1 <= lengths_host[b] <= seq_len (nn.TransformerEncoder's src_key_padding_mask for right-padded batches).  Rows behind a sequence are
  * padding: never read, they may hold NaN.  y_dev float32 [batch, seq_len, out_dim] is fully written: rows < lengths_host[b] are the
