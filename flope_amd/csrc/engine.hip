@@ -84,6 +84,7 @@ enum Image {
 // device side of conv i (its shape and plan: flope_engine::plan.shape[i] / .conv[i])
 struct ConvDev {
   int in_buf = -1, out_buf = -1, res_buf = -1;
+  int ip_in = -1, ip_out = -1, ip_res = -1;   // the same under option inplace (map_buffers)
   void* img[kImages] = {nullptr};
   Launch last;                                // what the last forward's last slice launched for it (flope_launch_info)
 };
@@ -108,6 +109,15 @@ struct flope_engine {
   int ds_buf[3] = {-1, -1, -1}, ds_conv[3] = {-1, -1, -1};   // FLOPE_STAGE_DS(li) - FLOPE_STAGE_DS(2) -> buffer / conv index
   bool last_ds_folded[3] = {false, false, false};            // the last forward computed that shortcut inside conv2
   int final_buf = -1;
+  // option inplace: the second set of buffer indices (ConvDev::ip_*, ip_final: map_buffers) and what flope_read_stage needs to serve
+  // the stages of a forward that ran under it
+  int ip_final = -1;
+  int stage_conv[10];                // FLOPE_STAGE_* (0..9) -> the conv that writes it (-1: stem, pool)
+  int mid_conv[8];                   // FLOPE_STAGE_MID(li, bi) - FLOPE_STAGE_MID(1, 0) -> conv index
+  std::vector<int> ip_last_writer;   // buffer -> the last conv of a forward under inplace that stores into it (-1: none)
+  bool ip_now = false;               // the map the forward being enqueued uses (run_trunk)
+  bool last_inplace = false;         // the last forward ran under inplace
+  std::vector<int> last_ip_out, last_ip_writer;   // ... with this map (ConvDev::ip_out, ip_last_writer at that time)
   float *feat = nullptr, *hidden = nullptr, *W1 = nullptr, *W1p = nullptr, *b1 = nullptr, *W2 = nullptr, *b2 = nullptr;
   float* r9_scratch = nullptr;
   bool weights_loaded = false;
@@ -158,6 +168,11 @@ __global__ void lag_kernel(int us) {
   while (__builtin_amdgcn_s_memrealtime() - t0 < (unsigned long long)us * 100ull) __builtin_amdgcn_s_sleep(32);
 }
 
+// the buffers of conv c under the map in force for the forward being enqueued
+int in_of(const flope_engine* e, const ConvDev& c) { return e->ip_now ? c.ip_in : c.in_buf; }
+int out_of(const flope_engine* e, const ConvDev& c) { return e->ip_now ? c.ip_out : c.out_buf; }
+int res_of(const flope_engine* e, const ConvDev& c) { return e->ip_now ? c.ip_res : c.res_buf; }
+
 // a slice's view of buffer bi: every tensor is batch-major, so images [start, ..) are an offset into the same buffer
 void* buf_at(const flope_engine* e, int bi, int start) {
   const Buf& b = e->bufs[bi];
@@ -171,8 +186,8 @@ void conv_params(const flope_engine* e, int i, const Launch& L, int start, int b
   const ConvDev& c = e->convs[i];
   const bool stag_image = L.family != kMfma && L.family != kS2r;      // conv_stag and the kernels that share its weight image
   memset(p, 0, sizeof(*p));
-  p->in = buf_at(e, c.in_buf, start); p->out = buf_at(e, c.out_buf, start);
-  p->res = c.res_buf >= 0 ? buf_at(e, c.res_buf, start) : nullptr;
+  p->in = buf_at(e, in_of(e, c), start); p->out = buf_at(e, out_of(e, c), start);
+  p->res = res_of(e, c) >= 0 ? buf_at(e, res_of(e, c), start) : nullptr;
   p->w = c.img[stag_image ? kWStag : kWPacked]; p->bias = (const float*)c.img[kBias];
   p->B = batch; p->Hip = s.hin + 2; p->Wip = s.win + 2; p->Cin = s.cin;
   p->Ho = s.hout; p->Wo = s.wout; p->Hop = s.hout + 2; p->Wop = s.wout + 2; p->Cout = s.cout;
@@ -188,7 +203,7 @@ void conv_params(const flope_engine* e, int i, const Launch& L, int start, int b
     const int di = e->plan.conv[i].ds_conv;
     const ConvShape& sd = e->plan.shape[di];
     p->res = nullptr; p->bias = (const float*)c.img[kBiasFused];
-    p->ds_in = buf_at(e, e->convs[di].in_buf, start); p->ds_w = e->convs[di].img[L.family == kS1r ? kWDsS1r : kWDsStag];
+    p->ds_in = buf_at(e, in_of(e, e->convs[di]), start); p->ds_w = e->convs[di].img[L.family == kS1r ? kWDsS1r : kWDsStag];
     p->ds_Hip = sd.hin + 2; p->ds_Wip = sd.win + 2; p->ds_Cin = sd.cin;
   }
   if (L.ksplit > 1) {
@@ -199,6 +214,61 @@ void conv_params(const flope_engine* e, int i, const Launch& L, int start, int b
   if (L.family == kR4 || L.family == kW4) fastdiv_magic((unsigned)(p->Wip + 2), &p->mg_pitch, &p->sh_pitch);
   if (L.stamps && e->split_ws)                 // diagnostic build: clock stamps of this launch (flope_debug_read_ws)
     p->split_ws = e->split_ws + (size_t)i * (kDbgRegion / 4);
+}
+
+// Option inplace: the second set of buffer indices.  Every buffer stays allocated; a forward under the option walks the same
+// launches and only names other buffers:
+//   conv2 whose residual buffer has the output's shape (the block input, or the materialised shortcut): stores over that residual
+//   conv2 behind a folded shortcut (no residual buffer; it reads the block input at stride 2): keeps its own buffer
+//   conv1 of block X.1: stores into block X.0's conv1 buffer (same shape; X.0's conv2, its only reader, is done in stream order)
+// so a layer touches two maps (three with a folded shortcut) instead of five, and every reuse distance is at most two maps.
+// The zero rings are never stored to, so maps of one shape share a buffer freely; maps of different shapes never do.
+// Depends on the plan (which shortcuts are folded): rebuilt after a replan.
+//
+// Only a conv2 aliases two of its own operands (res == out; its input is another buffer, so patch and halo reads never see a store
+// of the same launch).  That is safe in a kernel when (a) no two tiles store the same pixel, (b) a residual element is read only by
+// the tile that stores it, or read and discarded, and (c) every store depends on its residual load through data.  Per family:
+//   conv_r4<RES>        whole 8-row bands; a lane loads rb + oconst[pt] (+ 64) by inline asm and stores ob + oconst[pt] (+ 64) behind
+//                       the vmcnt(0) in front of sub-step 17; the next band's loads are issued after this band's stores (other pixels)
+//   conv_w4<RES>        disjoint pixel ranges [m0, mend); a lane's residual pieces (LDS-DMA into idle slots, or registers in a class
+//                       walk) are its own pixel's at ooff[pt]; the stores leave in line order -- another lane of the wave stores the
+//                       pixel -- but only after the owner added its residual and wrote the wave's line image; lanes past mend are
+//                       clamped to pixel mend - 1, which they read and never store (okl)
+//   conv_stag<RES>      flat tiles, 512 x 64 tiles, 8-row bands and their 64-column segments: a lane loads and stores at the same
+//                       out_off(pt); segments are disjoint in columns and lanes past Wo / mend are clamped, read and masked; the
+//                       bands prefetch the residual of this workgroup's own next tile (nobody else stores it), res_lds pieces are
+//                       the lane's own 16 bytes; the first tile's residual is loaded before anything is stored
+//   split-K             the main launch has no residual; conv_split_finalize / conv_f32m_finalize: one thread, one load and one
+//                       store at the same offset
+//   conv_s1r<RES>       whole 4-row bands; rbase and obase carry the same opix and the same per-tile offset
+//   conv_mfma, naive, conv_f32m   one lane / thread loads and stores the same elements, masked by m < mend / the grid bound
+//   conv_gstag, conv_s2r, folded shortcuts (conv_w4 / conv_stag / conv_s1r DSF)   no residual buffer: never in place
+// No kernel declares the residual or the output __restrict__ or loads the residual through a non-coherent path.  So every family
+// with a residual buffer runs in place and none is held back.
+void map_buffers(flope_engine* e) {
+  const Plan& pl = e->plan;
+  int cur = e->stage_buf[FLOPE_STAGE_POOL], mid = -1, ds = -1, mid0 = -1;
+  e->ip_last_writer.assign(e->bufs.size(), -1);
+  for (size_t i = 0; i < e->convs.size(); ++i) {
+    const ConvShape& s = pl.shape[i];
+    ConvDev& c = e->convs[i];
+    c.ip_res = -1;
+    if (s.role == kConv1) {
+      c.ip_in = cur;
+      if (s.bi == 0) mid0 = c.out_buf;
+      c.ip_out = mid = s.bi == 0 ? c.out_buf : mid0;
+    } else if (s.role == kShortcut) {
+      c.ip_in = cur; c.ip_out = ds = c.out_buf;
+    } else {
+      c.ip_in = mid;
+      const bool folded = pl.conv[i].ds_conv >= 0;
+      c.ip_res = s.res == 2 ? ds : cur;
+      c.ip_out = folded ? c.out_buf : c.ip_res;
+      cur = c.ip_out;
+    }
+    e->ip_last_writer[c.ip_out] = (int)i;
+  }
+  e->ip_final = cur;
 }
 
 template <typename V>
@@ -364,17 +434,20 @@ extern "C" int flope_create(int device_id, int height, int width, int max_batch,
     ConvDev c;
     c.out_buf = add_buf(s.cout, s.hout, s.wout);
     c.in_buf = s.role == kConv2 ? b_mid : cur;
-    if (s.role == kConv1) { b_mid = c.out_buf; e->mid_buf[(s.li - 1) * 2 + s.bi] = c.out_buf; }
+    if (s.role == kConv1) { b_mid = c.out_buf; e->mid_buf[(s.li - 1) * 2 + s.bi] = c.out_buf; e->mid_conv[(s.li - 1) * 2 + s.bi] = (int)e->convs.size(); }
     else if (s.role == kShortcut) {
       b_ds = c.out_buf;
       if (s.li >= 2) { e->ds_buf[s.li - 2] = c.out_buf; e->ds_conv[s.li - 2] = (int)e->convs.size(); }
     } else {
       c.res_buf = s.res == 2 ? b_ds : cur;
       e->stage_buf[FLOPE_STAGE_LAYER(s.li, s.bi)] = cur = c.out_buf;
+      e->stage_conv[FLOPE_STAGE_LAYER(s.li, s.bi)] = (int)e->convs.size();
     }
     e->convs.push_back(c);
   }
   e->final_buf = cur;
+  e->stage_conv[FLOPE_STAGE_STEM] = e->stage_conv[FLOPE_STAGE_POOL] = -1;
+  map_buffers(e);
   if (pl.shape.back().hout < 1 || pl.shape.back().wout < 1) { int rc = fail(nullptr, FLOPE_EINVAL, "flope_create: crop too small"); flope_destroy(e); return rc; }
   for (Buf& b : e->bufs) {
     CREATE_TRY(hipMalloc(&b.ptr, b.bytes));
@@ -445,7 +518,7 @@ extern "C" int flope_set_option(flope_handle e, const char* name, int value) {
   bool replans = false;
   const int prev = set_option(e->opt, name, value, &replans);
   if (d->member == &PlanOptions::profile) e->ev_n = 0;
-  if (replans) replan(e->plan, e->opt);
+  if (replans) { replan(e->plan, e->opt); map_buffers(e); }
   return prev;
 }
 
@@ -594,7 +667,8 @@ static int run_slice(flope_engine* e, const void* x_dev, int in_format, int star
   for (size_t i = 0; i < e->convs.size(); ++i) {
     ConvDev& c = e->convs[i];
     const ConvShape& s = pl.shape[i];
-    const Launch L = c.last = decide(o, pl, (int)i, x);
+    const Launch L = decide(o, pl, (int)i, x);
+    if (x.slice == x.slices - 1) c.last = L;           // (under inline0 the last slice is not the last one enqueued)
     ConvP p, pf;
     if (L.family != kFolded && L.family != kNaive && L.family != kF32m) conv_params(e, (int)i, L, start, batch, &p, &pf);
     if (L.family != kFolded) SMARK();
@@ -602,8 +676,8 @@ static int run_slice(flope_engine* e, const void* x_dev, int in_format, int star
       case kFolded: break;                           // computed inside the next launch (conv_stag DSF)
       case kNaive: {
         NaiveConvP q; memset(&q, 0, sizeof(q));
-        q.in = (const float*)buf_at(e, c.in_buf, start); q.out = (float*)buf_at(e, c.out_buf, start);
-        q.res = c.res_buf >= 0 ? (const float*)buf_at(e, c.res_buf, start) : nullptr;
+        q.in = (const float*)buf_at(e, in_of(e, c), start); q.out = (float*)buf_at(e, out_of(e, c), start);
+        q.res = res_of(e, c) >= 0 ? (const float*)buf_at(e, res_of(e, c), start) : nullptr;
         q.w = (const float*)c.img[kWNaive]; q.bias = (const float*)c.img[kBias];
         q.B = batch; q.Hip = s.hin + 2; q.Wip = s.win + 2; q.Cin_stored = s.cin; q.Cin = s.cin; q.Ho = s.hout; q.Wo = s.wout;
         q.Hop = s.hout + 2; q.Wop = s.wout + 2; q.Cout = s.cout; q.KH = s.k; q.KW = s.k; q.stride = s.stride;
@@ -613,8 +687,8 @@ static int run_slice(flope_engine* e, const void* x_dev, int in_format, int star
       }
       case kF32m: {
         F32mConvP q; memset(&q, 0, sizeof(q));
-        q.in = (const float*)buf_at(e, c.in_buf, start); q.out = (float*)buf_at(e, c.out_buf, start);
-        q.res = c.res_buf >= 0 ? (const float*)buf_at(e, c.res_buf, start) : nullptr;
+        q.in = (const float*)buf_at(e, in_of(e, c), start); q.out = (float*)buf_at(e, out_of(e, c), start);
+        q.res = res_of(e, c) >= 0 ? (const float*)buf_at(e, res_of(e, c), start) : nullptr;
         q.w = (const float*)c.img[kWF32m]; q.bias = (const float*)c.img[kBias];
         q.B = batch; q.Hip = s.hin + 2; q.Wip = s.win + 2; q.Cin_stored = s.cin; q.Cin = s.cin; q.Ho = s.hout; q.Wo = s.wout;
         q.Hop = s.hout + 2; q.Wop = s.wout + 2; q.Cout = s.cout; q.KH = s.k; q.KW = s.k; q.stride = s.stride;
@@ -638,9 +712,10 @@ static int run_slice(flope_engine* e, const void* x_dev, int in_format, int star
       case kMfma: K_TRY(e, conv_name(s).c_str(), flope_conv_mfma_launch(&p, dt, L.cfg, L.patch, L.nbuf, L.lds_bytes, stream)); break;
     }
   }
-  const Buf& bl = e->bufs[e->final_buf];
+  const int final_buf = e->ip_now ? e->ip_final : e->final_buf;
+  const Buf& bl = e->bufs[final_buf];
   SMARK();
-  K_TRY(e, "avgpool", flope_avgpool_launch(buf_at(e, e->final_buf, start), feat, batch, bl.h, bl.w, 512, dt, stream));
+  K_TRY(e, "avgpool", flope_avgpool_launch(buf_at(e, final_buf, start), feat, batch, bl.h, bl.w, 512, dt, stream));
   SMARK();
   K_TRY(e, "fc1", flope_fc1_launch(feat, e->W1, o.fc1_packed ? e->W1p : nullptr, e->b1, hidden, batch, 512, e->bod, stream));
   if (head) {
@@ -676,6 +751,12 @@ static int run_trunk(flope_engine* e, const void* x_dev, int in_format, int batc
   e->last_fused = e->opt.fuse_stem && e->dtype != FLOPE_DT_F32;
   e->last_batch = batch;
   for (int i = 0; i < 3; ++i) e->last_ds_folded[i] = e->ds_conv[i] >= 0 && e->plan.conv[e->ds_conv[i]].folded;
+  e->ip_now = e->last_inplace = e->opt.inplace != 0;
+  if (e->ip_now) {
+    e->last_ip_out.resize(e->convs.size());
+    for (size_t i = 0; i < e->convs.size(); ++i) e->last_ip_out[i] = e->convs[i].ip_out;
+    e->last_ip_writer = e->ip_last_writer;
+  }
   const Slices sl = slices(e->opt, batch, e->opt.profile);
   const int ns = sl.n;
   if (ns == 1) return run_slice(e, x_dev, in_format, 0, slice_ctx(sl, 0, batch, e->num_cus), stream, true, head, r9_dev, R_dev, po);
@@ -685,8 +766,15 @@ static int run_trunk(flope_engine* e, const void* x_dev, int in_format, int batc
   // each slice's whole sequence goes to its own stream; the hardware queues interleave them, and a slice's short tail round
   // overlaps another slice's next launch.  Time line (option profile = 2, tools/slice_timeline.py): the slices walk the same
   // layers side by side and finish within microseconds of each other.
-  int rc_all = FLOPE_OK, forked = 0;
-  for (int s = 0; s < ns && rc_all == FLOPE_OK; ++s) {
+  // Option inline0 (default): slice 0's sequence goes onto the caller's stream itself.  It starts without the hop from the caller's
+  // queue to a side queue (first launch eligible 12 us after the fork instead of 28), the side slices start one hop later -- the
+  // offset that option lag buys with a sleeping wave, which is therefore skipped -- and the join waits for one event fewer.  The
+  // side slices are enqueued first, so that their barrier is armed before slice 0's launches fill the caller's queue (the other
+  // order measured 0.3 - 0.6 % slower in three of four passes).  Same-run pairs, time lines: profiles/step_schedule_ab.txt, DESIGN.md 21.
+  const int first_side = e->opt.inline0 ? 1 : 0;
+  const bool marks = e->opt.profile == 2;
+  int rc_all = FLOPE_OK, forked = first_side;              // side slices [first_side, forked) were forked
+  for (int s = first_side; s < ns && rc_all == FLOPE_OK; ++s) {
     if (hipStreamWaitEvent(e->side[s], e->ev_fork, 0) != hipSuccess) { rc_all = fail(e, FLOPE_EHIP, "hipStreamWaitEvent(fork) failed"); break; }
 
     forked = s + 1;
@@ -694,16 +782,18 @@ static int run_trunk(flope_engine* e, const void* x_dev, int in_format, int batc
     // side by side, every pair of launches starting in the same microsecond -- i.e. their prologue fills and epilogue drains
     // coincide; a small offset is +0.7 .. +1.4 % on the step (5 .. 30 us all do; 80 us and more lose: profiles/r03_slice_lag.txt)
     // (measured at B = 256 x 224 x 224 only: applied from 192 crops up, where a step is >= 35 x the offset)
-    if (e->opt.lag && s == ns - 1 && batch >= 192) {
+    if (e->opt.lag && !e->opt.inline0 && s == ns - 1 && batch >= 192) {
       hipLaunchKernelGGL(lag_kernel, dim3(1), dim3(64), 0, e->side[s], e->opt.lag);
       if (hipGetLastError() != hipSuccess) { rc_all = fail(e, FLOPE_EHIP, "lag kernel launch failed"); break; }
     }
-    rc_all = run_slice(e, x_dev, in_format, sl.start[s], slice_ctx(sl, s, batch, e->num_cus), e->side[s], e->opt.profile == 2, head, r9_dev, R_dev, po);
+    rc_all = run_slice(e, x_dev, in_format, sl.start[s], slice_ctx(sl, s, batch, e->num_cus), e->side[s], marks, head, r9_dev, R_dev, po);
   }
+  if (e->opt.inline0 && rc_all == FLOPE_OK)
+    rc_all = run_slice(e, x_dev, in_format, sl.start[0], slice_ctx(sl, 0, batch, e->num_cus), user, marks, head, r9_dev, R_dev, po);
   // join every stream that was forked -- also after a failed launch, so that work already queued on the side
-  // streams stays ordered before the caller's next use of x / r9 / R / Rt
+  // streams stays ordered before the caller's next use of x / r9 / R / Rt (slice 0 under inline0 is on the caller's stream already)
   const std::string first_err = rc_all != FLOPE_OK ? e->err : std::string();
-  for (int s = 0; s < forked; ++s) {
+  for (int s = first_side; s < forked; ++s) {
     if (hipEventRecord(e->ev_join[s], e->side[s]) != hipSuccess || hipStreamWaitEvent(user, e->ev_join[s], 0) != hipSuccess) {
       hipStreamSynchronize(e->side[s]);
       if (rc_all == FLOPE_OK) rc_all = fail(e, FLOPE_EHIP, "joining the batch-slice streams failed");
@@ -761,6 +851,15 @@ extern "C" int flope_read_stage(flope_handle e, int stage, int batch, float* dst
     bi = e->ds_buf[stage - FLOPE_STAGE_DS(2)];
   }
   if (bi < 0) return fail(e, FLOPE_EINVAL, "flope_read_stage: unknown stage");
+  if (e->last_inplace) {           // the map of the last forward: a stage is where its conv stored it, if no later conv stored there too
+    int conv = -1;
+    if (stage >= 0 && stage <= 9) conv = e->stage_conv[stage];
+    else if (stage >= FLOPE_STAGE_MID(1, 0) && stage <= FLOPE_STAGE_MID(4, 1)) conv = e->mid_conv[stage - FLOPE_STAGE_MID(1, 0)];
+    else conv = e->ds_conv[stage - FLOPE_STAGE_DS(2)];
+    if (conv >= 0) bi = e->last_ip_out[conv];
+    if (e->last_ip_writer[bi] != conv)
+      return fail(e, FLOPE_ESTATE, "flope_read_stage: a later conv stored over this activation under option inplace (set option inplace=0)");
+  }
   if (stage == FLOPE_STAGE_STEM && e->last_fused)
     return fail(e, FLOPE_ESTATE, "flope_read_stage: the stem activation is not materialised by the fused stem+maxpool kernel (set option fuse_stem=0)");
   const Buf& b = e->bufs[bi];

@@ -34,7 +34,7 @@ struct PlanOptions {
   int split = 0;         // 0: default halves; 1..100: percent of the batch in slice 0; > 100: (value - 100) images
   int fc1_packed = 1;
   int w4mtlo = 0;        // smallest tile height the per-launch choice may take (0: 7 with two slices in flight, 5 alone)
-  int lag = 20;          // microseconds by which the last batch slice starts late (0 = off)
+  int lag = 20;          // inline0 = 0 only: microseconds by which the last batch slice starts late (0 = off)
   int w4mt = 0;          // conv_w4 tile height: 0 = per launch, 5..8 = 160..256 pixels (where the shape has that instantiation)
   int fc2_k4 = 1;        // fc_rot: K split over the four waves of a workgroup per image
   int ksplit = 1;        // 2: always the largest split
@@ -61,6 +61,8 @@ struct PlanOptions {
   int nbuf = 2;          // conv_mfma ring depth asked for (3 where the weight tile is 16 KB per step)
   int f32mfma = 0;       // FLOPE_DT_F32 only: 1 = stem and trunk convs on the exact-fp32 MFMA (conv_f32m.hip), 0 = naive_conv_kernel (the checker)
   int f32m_ksplit = 0;   // FLOPE_DT_F32 with f32mfma = 1 only: 0 = off, 1 = split-K per launch by the cost model of f32m_ksplit(), 2..32 = force that share count (rounded down to 2 / 4 / 8 / 16 / 32) wherever a split is allowed
+  int inline0 = 1;       // several batch slices: slice 0 runs on the caller's stream itself (no fork hop in front of it, one join fewer; the hop offsets the side slices, so lag's sleeping wave is skipped)
+  int inplace = 0;       // 1: a BasicBlock's conv2 writes over its residual input and block X.1's conv1 over block X.0's conv1 output (engine.hip: map_buffers)
   int profile = 0;       // 1: one slice, an event around every launch (flope_profile_read); 2: the slices as in production, events on every slice's stream (flope_profile_timeline)
 };
 
@@ -107,6 +109,8 @@ inline const std::vector<OptionDef>& option_table() {
       {"profile", &O::profile, kClamp, 0, 2, false},
       {"f32mfma", &O::f32mfma, kBool, 0, 1, false},
       {"f32m_ksplit", &O::f32m_ksplit, kClamp, 0, 32, false},
+      {"inline0", &O::inline0, kBool, 0, 1, false},
+      {"inplace", &O::inplace, kBool, 0, 1, false},
   };
   return t;
 }

@@ -191,7 +191,13 @@ class PoseEngine:
     # "split38" / "split716": slice 0 = 3/8 or 7/16 of the batch as an ABSOLUTE image count on a multiple of 8 (engine option
     # split = 100 + images), so that every layer's tiles stay whole in both slices -- a percentage would give 97 / 159 at B = 256
     # (ADVICE r4): resolved per batch by tune_candidates()
-    TUNE_CANDIDATES = ({}, {"w4cw": 4, "w4cwf": 1}, {"lag": 0}, {"split": "3/8"}, {"split": "7/16"})
+    # "inline0": 0 is the schedule before DESIGN.md 21 (both slices on side streams, the last one behind option lag's sleeping wave);
+    # it replaces the former {"lag": 0}, which is a no-op under the default inline0 = 1.  "inplace": 1 (block outputs over their
+    # residual input) won every same-run pair at B = 256; it is a candidate and not the default because read_stage
+    # then serves only the stages whose buffer still holds them -- autotune leaves it in force where it is faster, and a caller who
+    # reads stages afterwards sets it back to 0.
+    TUNE_CANDIDATES = ({}, {"w4cw": 4, "w4cwf": 1}, {"inline0": 0}, {"split": "3/8"}, {"split": "7/16"},
+                       {"inplace": 1})
 
     @classmethod
     def tune_candidates(cls, batch: int):

@@ -17,6 +17,8 @@ class FramePoses:
     def __init__(self, engine: PoseEngine | GuardedPoseEngine, frame_h: int, frame_w: int, max_boxes: int = 300, slots: int = 1):
         self.lib = _lib.load()
         self.engine = engine                     # kept alive: the handle borrows it
+        if hasattr(engine, "set_option"):        # (a bare view of an engine's handles keeps the engine's own setting)
+            engine.set_option("inplace", 1)      # the frame path never reads a stage: block outputs over their residual input
         self.device = engine.device
         self.frame_h, self.frame_w, self.max_boxes, self.slots = int(frame_h), int(frame_w), int(max_boxes), int(slots)
         h = C.c_void_p()

@@ -145,6 +145,7 @@ class FastPosePredictor:
         """The flope_frame handle behind this predictor's detector (csrc/frame.hip): rebuilt when the PoseResNet engine it
         borrows was rebuilt (larger batch) or when more slots are needed; parameters re-uploaded after load_state_dict."""
         eng = self.posenet.engine_for(self.device, (self.crop_size, self.crop_size))
+        eng.set_option("inplace", 1)               # no stage is read on this path: block outputs over their residual input (DESIGN.md 21)
         ctx = getattr(self, "_fctx", None)
         if ctx is None or ctx.engine is not eng or ctx.slots < slots:
             from flope_amd.frame import FramePoses

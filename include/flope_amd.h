@@ -159,7 +159,10 @@ int flope_depth_lift(const void* depth_dev, int depth_format, const uint8_t* mas
 /* ---- introspection (parity tests / DESIGN.md numbers) ----------------------- */
 /* Copy one internal activation of the LAST forward to float32: conv stages (STEM, POOL,
  * LAYER, MID, DS) as NCHW [B,C,h,w]; FEAT / HIDDEN as [B,n].  dims_out[4] receives the shape.
- * Every block owns its MID and DS buffers, so all taps of one forward can be read after it. */
+ * Every block owns its MID and DS buffers, so all taps of one forward can be read after it -- unless that forward ran under
+ * option "inplace": then only the stages whose buffer still holds them are served (STEM, every layer's last block output LAYER(l, 1)
+ * and last conv1 output MID(l, 1), FEAT, HIDDEN) and the others fail with FLOPE_ESTATE and a message that names the option.  What
+ * counts is the option's value during the last forward, not its value now. */
 int flope_read_stage(flope_handle h, int stage, int batch, float* dst_dev,
                      int64_t* dims_out, void* stream);
 /* runtime knobs (A/B variants inside one build); returns previous value or <0
@@ -173,7 +176,17 @@ int flope_read_stage(flope_handle h, int stage, int batch, float* dst_dev,
  *   "layer[split-K xS]" in flope_launch_info; flope_forward_launches counts the conv once (its finalize launch belongs to it).
  *   NOTE: with the option on, S depends on the batch, so a crop's bits depend on HOW MANY crops run with it -- not on its position
  *   in the batch, not on its neighbours, not on the run.  May be flipped between forwards.  Stored and ignored by FLOPE_DT_F16 /
- *   BF16 engines and by FLOPE_DT_F32 engines with "f32mfma" = 0. */
+ *   BF16 engines and by FLOPE_DT_F32 engines with "f32mfma" = 0.
+ *   "inline0" (default 1): where a forward runs as several batch slices, slice 0 is enqueued on the caller's stream itself and only
+ *   the other slices on internal streams forked from / joined to it.  Slice 0 starts without a cross-queue hop, the other slices
+ *   start one hop later (so option "lag"'s sleeping wave is skipped), and the join waits for one event fewer.  Slice 0's kernels
+ *   inherit what the caller's stream carries (priority, CU mask).  0 = every slice on an internal stream, the last one behind
+ *   "lag".  Same launches, same bits; no effect where the batch runs in one slice.  May be flipped between forwards.
+ *   "inplace" (default 0): a BasicBlock's second conv stores its output over its residual input (the block input, or the
+ *   materialised shortcut with "dsfuse" = 0; a conv2 with a folded shortcut keeps its own buffer), and the first conv of block X.1
+ *   stores into block X.0's conv1 buffer: a layer touches two activation maps instead of five, which keeps them resident in the
+ *   Infinity Cache.  Same launches, same bits; every buffer stays allocated, so the option may be flipped between forwards.
+ *   flope_read_stage then serves only part of the stages (see there). */
 int flope_set_option(flope_handle h, const char* name, int value);
 /* developer aid of diagnostic builds (-DFLOPE_STAG_DBG, option "dbg" = 64): in-kernel clock stamps that conv launch i of
  * the last forward left in the split-K workspace at byte offset i * 1048576 ({clk0, clk1, rt0, rt1} uint64 per workgroup and
@@ -194,7 +207,8 @@ int flope_forward_launches(flope_handle h);
 int flope_profile_read(flope_handle h, float* ms_out, int cap);
 /* option "profile" = 2: the last forward with its batch slices on their own streams, as in production, as a time line: event i was
  * recorded on slice slice_out[i]'s stream in front of that slice's next launch (behind its last one); ms_out[i] = milliseconds since the
- * fork (event 0).  Returns the number of events, < 0 on error.  Developer aid (tools/slice_timeline.py). */
+ * fork (event 0).  With "inline0" slice 0's events are recorded on the caller's stream, where that slice runs.  Returns the number of
+ * events, < 0 on error.  Developer aid (tools/slice_timeline.py). */
 int flope_profile_timeline(flope_handle h, float* ms_out, int* slice_out, int cap);
 int flope_launch_info(flope_handle h, int idx, int batch, char* name, int name_cap, double* flops);
 /* human-readable launch plan (one line per conv: tile config, patch/gather, LDS bytes) */
