@@ -12,10 +12,12 @@
 //     option attn_tiled   head_dim 32 / 64 / 96 / 128 at any length on the streaming form of that kernel (tf_attn_tiled);
 //                         everything else (embedding, out_layer, odd shapes) falls to the generic kernels.
 // Bias, residual add and ReLU live in the linear kernels' epilogues; LayerNorm is one wave per token row.
+// FLOPE_DT_F32 with option fused = 1: a forward whose longest sequence fits 64 KiB of LDS is ONE launch (tf_fused_f32), same bits.
 #include "../../include/flope_amd.h"
 #include "common.h"
 #include "host_pack.h"
 #include "tf_attn_plan.h"
+#include "tf_fused_plan.h"
 
 #include <math.h>
 #include <string.h>
@@ -61,6 +63,8 @@ __device__ __forceinline__ float wave_max(float v) {
 
 // ---- generic kernels (any shape; fp32 accumulate) ------------------------------------------------------------
 // Y[m][n] = act(sum_k X[m][k] * W[n][k] + b[n] (+ R[m][n]))        W fp32 [N][K] as stored in the checkpoint
+// TWIN: tf_fz_chain (tf_fused_f32) restates this kernel's float32 arithmetic and is held to its bits (tests/test_gpu_tf_fused.py):
+// change the order or an expression here and there together.
 template <typename T>
 __global__ void tf_linear_generic(const void* X, int x_f32, const float* W, const float* b, const void* R, void* Y,
                                   int y_f32, int M, int K, int N, int relu) {
@@ -76,6 +80,7 @@ __global__ void tf_linear_generic(const void* X, int x_f32, const float* W, cons
   st_any<T>(Y, idx, y_f32, acc);
 }
 
+// TWIN: tf_fz_rowwave (tf_fused_f32) restates this kernel's float32 arithmetic and is held to its bits: change both together.
 // Narrow outputs (N <= 16, e.g. out_layer): one wave per token row, lanes stride K (coalesced X and W reads), one
 // wave reduction per output feature.
 template <typename T>
@@ -184,6 +189,7 @@ __global__ void tf_scatter_rows(const float* Yp, const float* __restrict__ bias,
 }
 
 // LayerNorm over the last dimension, one wave per row (eps 1e-5, biased variance)
+// TWIN: tf_fz_ln (tf_fused_f32) restates the float instantiation's arithmetic and is held to its bits: change both together.
 template <typename T>
 __global__ void tf_layernorm(const T* in, T* out, const float* w, const float* b, int M, int d) {
   const int row = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6), lane = threadIdx.x & 63;
@@ -247,6 +253,7 @@ __global__ void tf_layernorm_vec(const T* in, T* out, const float* w, const floa
 }
 
 // softmax(q k^T / sqrt(dh)) v for one (batch, head) per blockIdx.x; one wave per query row.  Any L / dh.
+// TWIN: tf_fz_attn (tf_fused_f32) restates the float instantiation's arithmetic and is held to its bits: change both together.
 // VARLEN (all four attention kernels): qkv and out are packed [T][.] rows of a ragged batch, sequence b is rows
 // off[b] .. off[b + 1] - 1 and the L argument is the longest length, which sized the grid and the LDS; the kernel takes its own
 // sequence's length for L, so every bound, mask and clamp below stays inside the sequence (row off[b] + L is the next sequence's
@@ -989,6 +996,159 @@ __global__ __launch_bounds__(256) void tf_attn_f32m(const float* __restrict__ qk
   }
 }
 
+// ---- the whole float32 forward of one sequence in one workgroup (option fused) ---------------------------------
+// One launch per forward: workgroup b keeps every activation of sequence b in LDS at the offsets of tf_fused_plan.h and walks the
+// launch sequence of run_forward<float> phase by phase, a workgroup barrier where that sequence has a kernel boundary.  The result
+// is the launch sequence's, bit for bit: every generic float32 kernel computes an element in an order that does not depend on
+// which thread computes it, and the helpers below restate those orders expression by expression --
+//   tf_fz_chain    tf_linear_generic   one fmaf chain k = 0 .. K - 1 from 0.f, + b, + residual, ReLU
+//   tf_fz_rowwave  tf_linear_rowwave   (N <= 16, no residual) one wave per row, lane-strided k, wave_sum, + b, ReLU
+//   tf_fz_ln       tf_layernorm<float> one wave per row
+//   tf_fz_attn     tf_attn_generic     one wave per (head, query)
+// Weights, biases and LayerNorm parameters are read through L2 from the handle's float32 arrays; tab is the device table
+// flope_tf_load_weights builds: {embedding w, b, out_layer w, b}, then per layer {in_proj w, b, out_proj w, b, linear1 w, b,
+// linear2 w, b, norm1 w, b, norm2 w, b}.
+constexpr int kTfFusedTabHead = 4, kTfFusedTabLayer = 12;
+
+__device__ __forceinline__ void tf_fz_chain(const float* X, int xld, const float* __restrict__ W, const float* __restrict__ b,
+                                            const float* R, int rld, float* Y, int yld, int M, int K, int N, int relu) {
+  for (int idx = threadIdx.x; idx < M * N; idx += 256) {
+    const int m = idx / N, n = idx - m * N;
+    const float* w = W + (size_t)n * K;
+    const float* xr = X + m * xld;
+    float acc = 0.f;
+    for (int k = 0; k < K; ++k) acc = fmaf(xr[k], w[k], acc);
+    acc += b[n];
+    if (R) acc += R[m * rld + n];
+    if (relu) acc = fmaxf(acc, 0.f);
+    Y[(size_t)m * yld + n] = acc;
+  }
+}
+
+__device__ __forceinline__ void tf_fz_rowwave(const float* X, int xld, const float* __restrict__ W, const float* __restrict__ b, float* Y,
+                                              int yld, int M, int K, int N, int relu) {
+  const int lane = threadIdx.x & 63;
+  for (int m = threadIdx.x >> 6; m < M; m += 4) {
+    float acc[16];
+#pragma unroll
+    for (int n = 0; n < 16; ++n) acc[n] = 0.f;
+    for (int k = lane; k < K; k += 64) {
+      const float x = X[m * xld + k];
+#pragma unroll
+      for (int n = 0; n < 16; ++n)
+        if (n < N) acc[n] = fmaf(x, W[(size_t)n * K + k], acc[n]);
+    }
+#pragma unroll
+    for (int n = 0; n < 16; ++n)
+      if (n < N) {
+        float v = wave_sum(acc[n]) + b[n];
+        if (relu) v = fmaxf(v, 0.f);
+        if (lane == 0) Y[(size_t)m * yld + n] = v;
+      }
+  }
+}
+
+// the order launch_linear gives this linear in the float32 launch sequence
+__device__ __forceinline__ void tf_fz_linear(const float* X, int xld, const float* __restrict__ W, const float* __restrict__ b,
+                                             const float* R, int rld, float* Y, int yld, int M, int K, int N, int relu) {
+  if (flope_tf_plan::tf_fused_rowwave_order(N, R != nullptr)) tf_fz_rowwave(X, xld, W, b, Y, yld, M, K, N, relu);
+  else tf_fz_chain(X, xld, W, b, R, rld, Y, yld, M, K, N, relu);
+}
+
+__device__ __forceinline__ void tf_fz_ln(const float* in, float* out, const float* __restrict__ w, const float* __restrict__ b, int M, int d) {
+  const int lane = threadIdx.x & 63;
+  for (int row = threadIdx.x >> 6; row < M; row += 4) {
+    const float* x = in + row * d;
+    float s = 0.f;
+    for (int c = lane; c < d; c += 64) s += x[c];
+    const float mean = wave_sum(s) / d;
+    float v = 0.f;
+    for (int c = lane; c < d; c += 64) { const float t = x[c] - mean; v = fmaf(t, t, v); }
+    const float rstd = 1.f / sqrtf(wave_sum(v) / d + 1e-5f);
+    float* y = out + row * d;
+    for (int c = lane; c < d; c += 64) y[c] = (x[c] - mean) * rstd * w[c] + b[c];
+  }
+}
+
+// qkv rows of qld floats (q | k | v in the first 3 d), s: this wave's score row
+__device__ __forceinline__ void tf_fz_attn(const float* qkv, int qld, float* att, float* s, int L, int d, int H) {
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int dh = d / H;
+  const float scale = 1.f / sqrtf((float)dh);
+  for (int it = wave; it < H * L; it += 4) {
+    const int h = it / L, i = it - h * L;
+    const float* base = qkv + h * dh;
+    const float* q = base + i * qld;
+    float mx = -INFINITY;
+    for (int j = lane; j < L; j += 64) {
+      const float* k = base + j * qld + d;
+      float a = 0.f;
+      for (int c = 0; c < dh; ++c) a = fmaf(q[c], k[c], a);
+      a *= scale;
+      s[j] = a;
+      mx = fmaxf(mx, a);
+    }
+    mx = wave_max(mx);
+    float sum = 0.f;
+    for (int j = lane; j < L; j += 64) { const float p = expf(s[j] - mx); s[j] = p; sum += p; }
+    sum = wave_sum(sum);
+    __builtin_amdgcn_wave_barrier();
+    const float inv = 1.f / sum;
+    for (int c = lane; c < dh; c += 64) {
+      float o = 0.f;
+      for (int j = 0; j < L; ++j) o = fmaf(s[j], base[j * qld + 2 * d + c], o);
+      att[i * d + h * dh + c] = o * inv;
+    }
+    __builtin_amdgcn_wave_barrier();
+  }
+}
+
+// grid = batch, block = 256, dynamic LDS = lay.total (the layout of the longest sequence of the call).  x [batch][L][in_dim] ->
+// y [batch][L][out_dim]; off == nullptr: every sequence has L tokens; otherwise sequence b has off[b + 1] - off[b] <= the layout's L
+// tokens, rows behind it are not read and come back as out_layer.bias.
+__global__ __launch_bounds__(256) void tf_fused_f32(const float* __restrict__ x, float* __restrict__ y, const int* __restrict__ off,
+                                                    const float* const* __restrict__ tab, const flope_tf_plan::TfFusedLayout lay, int L,
+                                                    int in_dim, int d, int out_dim, int H, int nl, int ff) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int b = blockIdx.x;
+  const int len = off ? off[b + 1] - off[b] : L;
+  float* h = (float*)(smem + lay.h);
+  float* h2 = (float*)(smem + lay.h2);
+  float* xs = (float*)(smem + lay.x);
+  float* qkv = (float*)(smem + lay.qkv);
+  float* att = (float*)(smem + lay.att);
+  float* sc = (float*)(smem + lay.sc) + (threadIdx.x >> 6) * lay.sc_ld;
+  float* ffb = (float*)(smem + lay.ffb);
+  const int qld = (int)lay.qkv_ld;
+  const float* xb = x + (size_t)b * L * in_dim;
+  float* yb = y + (size_t)b * L * out_dim;
+  for (int i = threadIdx.x; i < len * in_dim; i += 256) xs[i] = xb[i];
+  __syncthreads();
+  tf_fz_linear(xs, in_dim, tab[0], tab[1], nullptr, 0, h, d, len, in_dim, d, 0);
+  __syncthreads();
+  for (int l = 0; l < nl; ++l) {
+    const float* const* t = tab + kTfFusedTabHead + l * kTfFusedTabLayer;
+    tf_fz_linear(h, d, t[0], t[1], nullptr, 0, qkv, qld, len, d, 3 * d, 0);
+    __syncthreads();
+    tf_fz_attn(qkv, qld, att, sc, len, d, H);
+    __syncthreads();
+    tf_fz_linear(att, d, t[2], t[3], h, d, h2, d, len, d, d, 0);
+    __syncthreads();
+    tf_fz_ln(h2, h, t[8], t[9], len, d);
+    __syncthreads();
+    tf_fz_linear(h, d, t[4], t[5], nullptr, 0, ffb, ff, len, d, ff, 1);
+    __syncthreads();
+    tf_fz_linear(ffb, ff, t[6], t[7], h, d, h2, d, len, ff, d, 0);
+    __syncthreads();
+    tf_fz_ln(h2, h, t[10], t[11], len, d);
+    __syncthreads();
+  }
+  tf_fz_linear(h, d, tab[2], tab[3], nullptr, 0, yb, out_dim, len, d, out_dim, 0);
+  const float* ob = tab[3];
+  float* pad = yb + (size_t)len * out_dim;
+  for (size_t i = threadIdx.x; i < (size_t)(L - len) * out_dim; i += 256) pad[i] = ob[i % out_dim];
+}
+
 }  // namespace
 
 // ---- handle ----------------------------------------------------------------------------------------------------
@@ -1005,6 +1165,9 @@ struct flope_tf_encoder {
   int opt_generic = 0;                       // 1: force the generic kernels (A/B checks)
   int opt_f32m = 0;                          // 1: FLOPE_DT_F32 linears and attention on v_mfma_f32_16x16x4_f32 where eligible (stored and ignored by 16-bit handles)
   int opt_tiled = 0;                         // 16-bit handles: 1 = tf_attn_tiled where the choice would be tf_attn_generic, 2 = also in place of tf_attn_mfma (stored and ignored by float32 handles)
+  int opt_fused = 0;                         // 1: a float32 forward that tf_fused_ok takes runs as one launch of tf_fused_f32 (stored and ignored by 16-bit handles and while opt_f32m)
+  int last_fwd = FLOPE_TF_FWD_LAUNCHES;       // what the last forward that enqueued anything ran (flope_tf_last_forward)
+  const float** fused_tab = nullptr;         // device table of the float32 weight arrays tf_fused_f32 reads (FLOPE_DT_F32 handles, built by flope_tf_load_weights)
   int opt_f32m_lds = 0;                      // KiB of untouched LDS a tf_linear_f32m launch reserves (> 80: one workgroup per CU)
   int cus = 256;
   bool loaded = false;
@@ -1219,10 +1382,10 @@ int launch_attention_varlen(flope_tf_encoder* e, const void* qkv, void* att, int
 // offsets are in e->vl_off by the time the first kernel runs (uploaded on the same stream).
 struct TfRagged { int T, max_len; };
 
-// Validates and plans a ragged batch into e->vl_host and enqueues the upload of its batch + 1 offsets.
-int tf_plan_ragged(flope_tf_encoder* e, const char* who, const int* lengths, int B, int L, hipStream_t st, TfRagged* rg) {
+// Validates and plans a ragged batch into off_host (batch + 1 ints); enqueues nothing.
+int tf_check_ragged(flope_tf_encoder* e, const char* who, const int* lengths, int B, int L, int* off_host, TfRagged* rg) {
   int bad = -1;
-  const int rc = flope_tf_plan::tf_varlen_plan(lengths, B, L, e->max_tokens, e->vl_host.data(), &rg->T, &rg->max_len, &bad);
+  const int rc = flope_tf_plan::tf_varlen_plan(lengths, B, L, e->max_tokens, off_host, &rg->T, &rg->max_len, &bad);
   const std::string w(who);
   switch (rc) {
     case flope_tf_plan::kTfVarlenOk: break;
@@ -1233,6 +1396,13 @@ int tf_plan_ragged(flope_tf_encoder* e, const char* who, const int* lengths, int
     case flope_tf_plan::kTfVarlenTokens: return tf_fail(e, FLOPE_EINVAL, w + ": the sum of lengths exceeds max_tokens given to flope_tf_create");
     default: return tf_fail(e, FLOPE_EINVAL, w + ": the sum of lengths overflows int");
   }
+  return 0;
+}
+
+// Validates and plans a ragged batch into e->vl_host and enqueues the upload of its batch + 1 offsets.
+int tf_plan_ragged(flope_tf_encoder* e, const char* who, const int* lengths, int B, int L, hipStream_t st, TfRagged* rg) {
+  int rc;
+  if ((rc = tf_check_ragged(e, who, lengths, B, L, e->vl_host.data(), rg))) return rc;
   // pageable source: the runtime has staged it when the call returns, so the next call may overwrite vl_host
   TF_HIP(e, hipMemcpyAsync(e->vl_off, e->vl_host.data(), (size_t)(B + 1) * sizeof(int), hipMemcpyHostToDevice, st));
   return 0;
@@ -1268,6 +1438,21 @@ int run_forward(flope_tf_encoder* e, const float* x, int B, int L, float* y, hip
   const size_t tot = (size_t)B * L * e->out_dim;
   hipLaunchKernelGGL(tf_scatter_rows, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, (const float*)e->ypk, (const float*)e->outl.b, y, e->vl_off, L,
                      e->out_dim, tot);
+  TF_HIP(e, hipGetLastError());
+  return 0;
+}
+
+// Option fused: whether a float32 forward whose longest sequence has Lmax tokens runs as the single launch
+bool tf_fused_pick(const flope_tf_encoder* e, int Lmax) {
+  return e->fused_tab && flope_tf_plan::tf_fused_ok(e->dtype, e->opt_fused, e->opt_f32m, e->in_dim, e->d, e->ff, Lmax);
+}
+
+// ... and that launch: x [B][L][in] -> y [B][L][out], one workgroup per sequence.  off == nullptr: every sequence has L = Lmax tokens;
+// otherwise the handle's device offset table of a ragged batch whose longest sequence has Lmax <= L tokens.
+int launch_fused(flope_tf_encoder* e, const float* x, int B, int L, int Lmax, const int* off, float* y, hipStream_t st) {
+  const flope_tf_plan::TfFusedLayout lay = flope_tf_plan::tf_fused_layout(e->in_dim, e->d, e->ff, Lmax);
+  hipLaunchKernelGGL(tf_fused_f32, dim3((unsigned)B), dim3(256), (size_t)lay.total, st, x, y, off, (const float* const*)e->fused_tab, lay, L, e->in_dim,
+                     e->d, e->out_dim, e->H, e->nl, e->ff);
   TF_HIP(e, hipGetLastError());
   return 0;
 }
@@ -1361,6 +1546,10 @@ extern "C" int flope_tf_set_option(flope_tf_handle e, const char* name, int valu
     if (value < 0 || value > 2) return tf_fail(e, FLOPE_EINVAL, "flope_tf_set_option: attn_tiled is 0, 1 or 2");
     const int old = e->opt_tiled; e->opt_tiled = value; return old;
   }
+  if (!strcmp(name, "fused")) {
+    if (value < 0 || value > 1) return tf_fail(e, FLOPE_EINVAL, "flope_tf_set_option: fused is 0 or 1");
+    const int old = e->opt_fused; e->opt_fused = value; return old;
+  }
   if (!strcmp(name, "f32mlds")) {
     if (value < 0 || value > 160) return tf_fail(e, FLOPE_EINVAL, "flope_tf_set_option: f32mlds is 0 .. 160 (KiB)");
     const int old = e->opt_f32m_lds; e->opt_f32m_lds = value; return old;
@@ -1432,6 +1621,21 @@ extern "C" int flope_tf_load_weights(flope_tf_handle e, int n, const char* const
       return rc;
   }
   if ((rc = linear("out_layer.weight", "out_layer.bias", e->out_dim, e->d, &e->outl))) return rc;
+  if (e->fused_tab) {                                  // a reload replaces the table (the weight arrays themselves stay until destroy, as before)
+    for (auto it = e->allocs.begin(); it != e->allocs.end(); ++it)
+      if (*it == (void*)e->fused_tab) { e->allocs.erase(it); break; }
+    hipFree((void*)e->fused_tab);
+    e->fused_tab = nullptr;
+  }
+  if (e->dtype == FLOPE_DT_F32) {                      // tf_fused_f32's table: 4 + 12 num_layers device pointers
+    std::vector<const float*> tab = {e->emb.w, e->emb.b, e->outl.w, e->outl.b};
+    for (const TfLayer& ly : e->layers)
+      for (const float* p : {(const float*)ly.in_proj.w, (const float*)ly.in_proj.b, (const float*)ly.out_proj.w, (const float*)ly.out_proj.b,
+                             (const float*)ly.lin1.w, (const float*)ly.lin1.b, (const float*)ly.lin2.w, (const float*)ly.lin2.b,
+                             (const float*)ly.n1w, (const float*)ly.n1b, (const float*)ly.n2w, (const float*)ly.n2b})
+        tab.push_back(p);
+    if ((rc = tf_upload(e, tab.data(), tab.size(), (void**)&e->fused_tab))) return rc;
+  }
   TF_HIP(e, hipDeviceSynchronize());
   e->loaded = true;
   return FLOPE_OK;
@@ -1447,6 +1651,12 @@ extern "C" int flope_tf_forward(flope_tf_handle e, const float* x_dev, int batch
     return tf_fail(e, FLOPE_EINVAL, "flope_tf_forward: batch*seq_len exceeds max_tokens given to flope_tf_create");
   TF_HIP(e, hipSetDevice(e->device));
   hipStream_t st = (hipStream_t)stream;
+  e->last_fwd = FLOPE_TF_FWD_LAUNCHES;
+  if (tf_fused_pick(e, seq_len)) {
+    const int rc = launch_fused(e, x_dev, batch, seq_len, seq_len, nullptr, y_dev, st);
+    if (!rc) e->last_fwd = FLOPE_TF_FWD_FUSED;
+    return rc;
+  }
   if (e->dtype == FLOPE_DT_F32) return run_forward<float>(e, x_dev, batch, seq_len, y_dev, st);
   if (e->dtype == FLOPE_DT_F16) return run_forward<f16_t>(e, x_dev, batch, seq_len, y_dev, st);
   return run_forward<bf16_t>(e, x_dev, batch, seq_len, y_dev, st);
@@ -1536,9 +1746,41 @@ extern "C" int flope_tf_forward_varlen(flope_tf_handle e, const float* x_dev, in
   TfRagged rg;
   int rc;
   if ((rc = tf_plan_ragged(e, "flope_tf_forward_varlen", lengths_host, batch, seq_len, st, &rg))) return rc;
+  e->last_fwd = FLOPE_TF_FWD_LAUNCHES;
+  if (tf_fused_pick(e, rg.max_len)) {
+    rc = launch_fused(e, x_dev, batch, seq_len, rg.max_len, e->vl_off, y_dev, st);
+    if (!rc) e->last_fwd = FLOPE_TF_FWD_FUSED;
+    return rc;
+  }
   if (e->dtype == FLOPE_DT_F32) return run_forward<float>(e, x_dev, batch, seq_len, y_dev, st, &rg);
   if (e->dtype == FLOPE_DT_F16) return run_forward<f16_t>(e, x_dev, batch, seq_len, y_dev, st, &rg);
   return run_forward<bf16_t>(e, x_dev, batch, seq_len, y_dev, st, &rg);
+}
+
+extern "C" int flope_tf_forward_plan(flope_tf_handle e, int batch, int seq_len, const int* lengths_host) {
+  if (!e) return tf_fail(nullptr, FLOPE_EINVAL, "flope_tf_forward_plan: NULL handle");
+  if (!e->loaded) return tf_fail(e, FLOPE_ESTATE, "flope_tf_forward_plan: weights not loaded");
+  if (!lengths_host) {                                               // flope_tf_forward's checks
+    if (batch < 0 || seq_len < 0) return tf_fail(e, FLOPE_EINVAL, "flope_tf_forward_plan: negative size");
+    if (batch == 0 || seq_len == 0) return FLOPE_TF_FWD_LAUNCHES;
+    if ((long long)batch * seq_len > e->max_tokens)
+      return tf_fail(e, FLOPE_EINVAL, "flope_tf_forward_plan: batch*seq_len exceeds max_tokens given to flope_tf_create");
+    return tf_fused_pick(e, seq_len) ? FLOPE_TF_FWD_FUSED : FLOPE_TF_FWD_LAUNCHES;
+  }
+  if (seq_len < 1) return tf_fail(e, FLOPE_EINVAL, "flope_tf_forward_plan: non-positive seq_len");      // flope_tf_forward_varlen's
+  const size_t widest = (size_t)(e->emb.Kp > e->out_dim ? e->emb.Kp : e->out_dim);
+  if (batch > 0 && (size_t)batch * seq_len > (size_t)INT32_MAX * 256 / widest)
+    return tf_fail(e, FLOPE_EINVAL, "flope_tf_forward_plan: batch*seq_len too large for one launch");
+  std::vector<int> off((size_t)(batch > 0 ? batch : 0) + 1);         // the handle's own table stays as the last forward left it
+  TfRagged rg;
+  int rc;
+  if ((rc = tf_check_ragged(e, "flope_tf_forward_plan", lengths_host, batch, seq_len, off.data(), &rg))) return rc;
+  return tf_fused_pick(e, rg.max_len) ? FLOPE_TF_FWD_FUSED : FLOPE_TF_FWD_LAUNCHES;
+}
+
+extern "C" int flope_tf_last_forward(flope_tf_handle e) {
+  if (!e) return tf_fail(nullptr, FLOPE_EINVAL, "flope_tf_last_forward: NULL handle");
+  return e->last_fwd;
 }
 
 extern "C" int flope_tf_attention_varlen(flope_tf_handle e, const void* qkv_dev, int batch, const int* lengths_host, void* out_dev, void* stream) {

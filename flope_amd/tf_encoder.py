@@ -57,7 +57,7 @@ def _mask_to_lengths(mask, B, L):
 
 class TransformerEncoder:
     def __init__(self, input_dim, model_dim, out_dim, num_heads, num_layers, ff_dim, dropout=0.1,
-                 dtype="f32", max_tokens=4096, device=None, attn_tiled=0):
+                 dtype="f32", max_tokens=4096, device=None, attn_tiled=0, fused=0):
         _require_gpu()
         self.lib = _lib.load()
         self.device = torch.device(device if device is not None else "cuda:0")
@@ -87,6 +87,12 @@ class TransformerEncoder:
             if rc < 0:
                 self.close()
                 raise ValueError(f"attn_tiled must be 0, 1 or 2 (got {attn_tiled!r})")
+        self.last_forward_fused = False          # whether the last forward() ran as the single launch of option "fused"
+        if fused:                                # float32 handles: one launch per forward where a sequence fits in LDS (0 or 1, include/flope_amd.h)
+            rc = self.lib.flope_tf_set_option(self.handle, b"fused", int(fused))
+            if rc < 0:
+                self.close()
+                raise ValueError(f"fused must be 0 or 1 (got {fused!r})")
 
     def _check(self, rc):
         if rc:
@@ -125,6 +131,14 @@ class TransformerEncoder:
             return self.lib.flope_tf_forward_flops(self.handle, batch, seq_len)
         return self.lib.flope_tf_forward_flops_varlen(self.handle, batch, _host_lengths(lengths, batch))
 
+    def forward_plan(self, batch: int, seq_len: int, lengths=None) -> str:
+        """"fused" or "launches": what forward() of x [batch, seq_len, input_dim] (with these `lengths`) would run under the current
+        options.  Enqueues nothing; a shape the forward refuses raises ValueError."""
+        with torch.cuda.device(self.device):
+            rc = self.lib.flope_tf_forward_plan(self.handle, int(batch), int(seq_len), None if lengths is None else _host_lengths(lengths, batch))
+        self._check_arg(rc)
+        return "fused" if rc == _lib.TF_FWD_FUSED else "launches"
+
     # The entry points added after the fixed-length forward (the ragged calls, linear, layernorm) share this checker: a refused call
     # (FLOPE_EINVAL: a bad length, too many tokens, a misaligned buffer, an unknown name) is the caller's argument and raises
     # ValueError, and a result >= 0 (a kernel id) passes.  _check keeps raising RuntimeError for forward() and attention() without
@@ -151,12 +165,14 @@ class TransformerEncoder:
         if src_key_padding_mask is not None:
             lengths = _mask_to_lengths(src_key_padding_mask, B, L)
         y = torch.empty((B, L, self.dims[2]), dtype=torch.float32, device=self.device)
+        lh = None if lengths is None else _host_lengths(lengths, B)
         if lengths is None:
             self._check(self.lib.flope_tf_forward(self.handle, x.data_ptr(), B, L, y.data_ptr(), _stream_ptr(self.device)))
         else:
             with torch.cuda.device(self.device):
-                self._check_arg(self.lib.flope_tf_forward_varlen(self.handle, x.data_ptr(), B, L, _host_lengths(lengths, B), y.data_ptr(),
+                self._check_arg(self.lib.flope_tf_forward_varlen(self.handle, x.data_ptr(), B, L, lh, y.data_ptr(),
                                                                     _stream_ptr(self.device)))
+        self.last_forward_fused = self.lib.flope_tf_last_forward(self.handle) == _lib.TF_FWD_FUSED      # what that forward recorded
         self._keep = x
         return y
 

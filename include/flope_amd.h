@@ -336,7 +336,11 @@ int flope_tf_forward(flope_tf_handle h, const float* x_dev, int batch, int seq_l
  *       tf_attn_tiled (head_dim % 32 == 0, head_dim <= 128, any seq_len).  0: none.  1: those that would otherwise run
  *       the generic kernel; shapes the resident kernel takes (head_dim 64, seq_len <= 512) keep it.  2: every eligible launch, also in
  *       place of the resident kernel (A/B and tests).  "generic" = 1 overrides it; buffers that are not 16-byte aligned run generic.
- *       May be flipped between forwards.  Stored and ignored by FLOPE_DT_F32 handles. */
+ *       May be flipped between forwards.  Stored and ignored by FLOPE_DT_F32 handles;
+ *   "fused" (default 0; 0 or 1, FLOPE_EINVAL outside): 1 = a FLOPE_DT_F32 forward whose longest sequence fits one workgroup's 64 KiB
+ *       of LDS (flope_amd/csrc/tf_fused_plan.h) runs as ONE launch, one sequence per workgroup (tf_fused_f32), and
+ *       returns the bits of the launch sequence; any other forward runs that sequence, silently.  Stored and ignored by 16-bit
+ *       handles and while "f32mfma" = 1; may be flipped between forwards; flope_tf_attention / _linear / _layernorm ignore it. */
 int flope_tf_set_option(flope_tf_handle h, const char* name, int value);
 /* softmax(q k^T / sqrt(head_dim)) v per head on a caller's buffer: qkv_dev [batch, seq_len, 3*model_dim] and out_dev
  * [batch, seq_len, model_dim] in the handle's dtype (float32 for FLOPE_DT_F32).  Launches exactly what flope_tf_forward
@@ -391,6 +395,16 @@ int flope_tf_forward_varlen(flope_tf_handle h, const float* x_dev, int batch, in
  * sequence b = rows sum(lengths_host[0 .. b-1]) onwards.  Launches exactly what flope_tf_forward_varlen would for these lengths under
  * the handle's current options; needs no weights.  Returns the FLOPE_TF_ATTN_* id of the kernel launched, or < 0.  T <= max_tokens. */
 int flope_tf_attention_varlen(flope_tf_handle h, const void* qkv_dev, int batch, const int* lengths_host, void* out_dev, void* stream);
+/* What flope_tf_forward (lengths_host NULL) or flope_tf_forward_varlen (lengths_host: batch ints) of this shape would run under the
+ * handle's current options: FLOPE_TF_FWD_LAUNCHES, the sequence of 2 + 7 num_layers kernels (also for an empty fixed-length batch,
+ * which runs nothing), or FLOPE_TF_FWD_FUSED, the single launch of option "fused".  < 0 for the argument errors the forward itself
+ * reports (buffers aside).  Enqueues nothing and leaves the handle's state alone. */
+#define FLOPE_TF_FWD_LAUNCHES     0
+#define FLOPE_TF_FWD_FUSED        1
+int flope_tf_forward_plan(flope_tf_handle h, int batch, int seq_len, const int* lengths_host);
+/* What the last flope_tf_forward / flope_tf_forward_varlen of this handle that passed its checks enqueued: FLOPE_TF_FWD_FUSED when the
+ * single launch ran, FLOPE_TF_FWD_LAUNCHES otherwise (also before any forward).  Recorded by the forward itself, not planned again. */
+int flope_tf_last_forward(flope_tf_handle h);
 /* algorithmic FLOPs of one ragged forward: the linears on T tokens, attention on the sum of lengths squared; 0 for an invalid batch */
 double flope_tf_forward_flops_varlen(flope_tf_handle h, int batch, const int* lengths_host);
 
