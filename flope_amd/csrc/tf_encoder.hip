@@ -62,49 +62,101 @@ __device__ __forceinline__ float wave_max(float v) {
 }
 
 // ---- generic kernels (any shape; fp32 accumulate) ------------------------------------------------------------
+// The float32 summation orders, one definition each: the generic kernels below and tf_fused_f32 (its float instantiations, on LDS
+// rows) call these, so a caller only decides which thread or wave takes which element or row.  Row strides are parameters.
+// One element of Y = act(X W^T + b (+ R)): one fmaf chain k = 0 .. K - 1 from 0.f, + b[n], + residual, ReLU
+template <typename T>
+__device__ __forceinline__ void tf_linear_elem(const void* X, int xld, int x_f32, const float* W, const float* b, const void* R, int rld,
+                                               void* Y, int yld, int y_f32, int m, int n, int K, int relu) {
+  const float* w = W + (size_t)n * K;
+  float acc = 0.f;
+  for (int k = 0; k < K; ++k) acc = fmaf(ld_any<T>(X, (size_t)m * xld + k, x_f32), w[k], acc);
+  acc += b[n];
+  if (R) acc += ld_any<T>(R, (size_t)m * rld + n, 0);
+  if (relu) acc = fmaxf(acc, 0.f);
+  st_any<T>(Y, (size_t)m * yld + n, y_f32, acc);
+}
+
+// One row of a narrow linear (N <= 16, no residual) on one wave: lanes stride K, one wave reduction per output feature, lane 0 stores
+template <typename T>
+__device__ __forceinline__ void tf_rowwave_row(const void* X, int xld, int x_f32, const float* W, const float* b, void* Y, int yld,
+                                               int y_f32, int m, int K, int N, int relu, int lane) {
+  float acc[16];
+#pragma unroll
+  for (int n = 0; n < 16; ++n) acc[n] = 0.f;
+  for (int k = lane; k < K; k += 64) {
+    const float x = ld_any<T>(X, (size_t)m * xld + k, x_f32);
+#pragma unroll
+    for (int n = 0; n < 16; ++n)
+      if (n < N) acc[n] = fmaf(x, W[(size_t)n * K + k], acc[n]);
+  }
+#pragma unroll
+  for (int n = 0; n < 16; ++n)
+    if (n < N) {
+      float v = wave_sum(acc[n]) + b[n];
+      if (relu) v = fmaxf(v, 0.f);
+      if (lane == 0) st_any<T>(Y, (size_t)m * yld + n, y_f32, v);
+    }
+}
+
+// LayerNorm of one row of d on one wave (eps 1e-5, biased variance)
+template <typename T>
+__device__ __forceinline__ void tf_layernorm_row(const T* x, T* y, const float* w, const float* b, int d, int lane) {
+  float s = 0.f;
+  for (int c = lane; c < d; c += 64) s += to_f32<T>(x[c]);
+  const float mean = wave_sum(s) / d;
+  float v = 0.f;
+  for (int c = lane; c < d; c += 64) { const float t = to_f32<T>(x[c]) - mean; v = fmaf(t, t, v); }
+  const float rstd = 1.f / sqrtf(wave_sum(v) / d + 1e-5f);
+  for (int c = lane; c < d; c += 64) y[c] = from_f32<T>((to_f32<T>(x[c]) - mean) * rstd * w[c] + b[c]);
+}
+
+// softmax(q k^T / sqrt(dh)) v for query i of one head on one wave.  base: the head's q columns of the sequence's first row, rows of
+// ld elements (q | k | v at 0, d, 2 d); s: this wave's score row (L floats of LDS); orow: the dh outputs of the query.
+template <typename T>
+__device__ __forceinline__ void tf_attn_row(const T* base, size_t ld, T* orow, float* s, int i, int L, int d, int dh, float scale, int lane) {
+  const T* q = base + (size_t)i * ld;
+  float mx = -INFINITY;
+  for (int j = lane; j < L; j += 64) {
+    const T* k = base + (size_t)j * ld + d;
+    float a = 0.f;
+    for (int c = 0; c < dh; ++c) a = fmaf(to_f32<T>(q[c]), to_f32<T>(k[c]), a);
+    a *= scale;
+    s[j] = a;
+    mx = fmaxf(mx, a);
+  }
+  mx = wave_max(mx);
+  float sum = 0.f;
+  for (int j = lane; j < L; j += 64) { const float p = expf(s[j] - mx); s[j] = p; sum += p; }
+  sum = wave_sum(sum);
+  __builtin_amdgcn_wave_barrier();
+  const float inv = 1.f / sum;
+  for (int c = lane; c < dh; c += 64) {
+    float o = 0.f;
+    for (int j = 0; j < L; ++j) o = fmaf(s[j], to_f32<T>(base[(size_t)j * ld + 2 * d + c]), o);
+    orow[c] = from_f32<T>(o * inv);
+  }
+  __builtin_amdgcn_wave_barrier();
+}
+
 // Y[m][n] = act(sum_k X[m][k] * W[n][k] + b[n] (+ R[m][n]))        W fp32 [N][K] as stored in the checkpoint
-// TWIN: tf_fz_chain (tf_fused_f32) restates this kernel's float32 arithmetic and is held to its bits (tests/test_gpu_tf_fused.py):
-// change the order or an expression here and there together.
 template <typename T>
 __global__ void tf_linear_generic(const void* X, int x_f32, const float* W, const float* b, const void* R, void* Y,
                                   int y_f32, int M, int K, int N, int relu) {
   const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (idx >= (size_t)M * N) return;
   const int m = (int)(idx / N), n = (int)(idx - (size_t)m * N);
-  const float* w = W + (size_t)n * K;
-  float acc = 0.f;
-  for (int k = 0; k < K; ++k) acc = fmaf(ld_any<T>(X, (size_t)m * K + k, x_f32), w[k], acc);
-  acc += b[n];
-  if (R) acc += ld_any<T>(R, idx, 0);
-  if (relu) acc = fmaxf(acc, 0.f);
-  st_any<T>(Y, idx, y_f32, acc);
+  tf_linear_elem<T>(X, K, x_f32, W, b, R, N, Y, N, y_f32, m, n, K, relu);
 }
 
-// TWIN: tf_fz_rowwave (tf_fused_f32) restates this kernel's float32 arithmetic and is held to its bits: change both together.
 // Narrow outputs (N <= 16, e.g. out_layer): one wave per token row, lanes stride K (coalesced X and W reads), one
 // wave reduction per output feature.
 template <typename T>
 __global__ void tf_linear_rowwave(const void* X, int x_f32, const float* W, const float* b, void* Y, int y_f32, int M,
                                   int K, int N, int relu) {
   const int lane = threadIdx.x & 63, nw = blockDim.x >> 6;
-  for (int m = blockIdx.x * nw + (threadIdx.x >> 6); m < M; m += gridDim.x * nw) {
-    float acc[16];
-#pragma unroll
-    for (int n = 0; n < 16; ++n) acc[n] = 0.f;
-    for (int k = lane; k < K; k += 64) {
-      const float x = ld_any<T>(X, (size_t)m * K + k, x_f32);
-#pragma unroll
-      for (int n = 0; n < 16; ++n)
-        if (n < N) acc[n] = fmaf(x, W[(size_t)n * K + k], acc[n]);
-    }
-#pragma unroll
-    for (int n = 0; n < 16; ++n)
-      if (n < N) {
-        float v = wave_sum(acc[n]) + b[n];
-        if (relu) v = fmaxf(v, 0.f);
-        if (lane == 0) st_any<T>(Y, (size_t)m * N + n, y_f32, v);
-      }
-  }
+  for (int m = blockIdx.x * nw + (threadIdx.x >> 6); m < M; m += gridDim.x * nw)
+    tf_rowwave_row<T>(X, K, x_f32, W, b, Y, N, y_f32, m, K, N, relu, lane);
 }
 
 // The same for 16-bit activations with K % 8 == 0 (r03: the kernel above took 184 us for the out_layer of the throughput shape --
@@ -188,21 +240,12 @@ __global__ void tf_scatter_rows(const float* Yp, const float* __restrict__ bias,
   Y[idx] = i < off[b + 1] - o ? Yp[(size_t)(o + i) * N + c] : bias[c];
 }
 
-// LayerNorm over the last dimension, one wave per row (eps 1e-5, biased variance)
-// TWIN: tf_fz_ln (tf_fused_f32) restates the float instantiation's arithmetic and is held to its bits: change both together.
+// LayerNorm over the last dimension, one wave per row
 template <typename T>
 __global__ void tf_layernorm(const T* in, T* out, const float* w, const float* b, int M, int d) {
   const int row = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6), lane = threadIdx.x & 63;
   if (row >= M) return;
-  const T* x = in + (size_t)row * d;
-  float s = 0.f;
-  for (int c = lane; c < d; c += 64) s += to_f32<T>(x[c]);
-  const float mean = wave_sum(s) / d;
-  float v = 0.f;
-  for (int c = lane; c < d; c += 64) { const float t = to_f32<T>(x[c]) - mean; v = fmaf(t, t, v); }
-  const float rstd = 1.f / sqrtf(wave_sum(v) / d + 1e-5f);
-  T* y = out + (size_t)row * d;
-  for (int c = lane; c < d; c += 64) y[c] = from_f32<T>((to_f32<T>(x[c]) - mean) * rstd * w[c] + b[c]);
+  tf_layernorm_row<T>(in + (size_t)row * d, out + (size_t)row * d, w, b, d, lane);
 }
 
 // 16-bit rows with d % 8 == 0 and d <= 2048: each lane keeps its 16-byte vectors in registers (one HBM read)
@@ -253,7 +296,6 @@ __global__ void tf_layernorm_vec(const T* in, T* out, const float* w, const floa
 }
 
 // softmax(q k^T / sqrt(dh)) v for one (batch, head) per blockIdx.x; one wave per query row.  Any L / dh.
-// TWIN: tf_fz_attn (tf_fused_f32) restates the float instantiation's arithmetic and is held to its bits: change both together.
 // VARLEN (all four attention kernels): qkv and out are packed [T][.] rows of a ragged batch, sequence b is rows
 // off[b] .. off[b + 1] - 1 and the L argument is the longest length, which sized the grid and the LDS; the kernel takes its own
 // sequence's length for L, so every bound, mask and clamp below stays inside the sequence (row off[b] + L is the next sequence's
@@ -268,30 +310,8 @@ __global__ void tf_attn_generic(const T* qkv, T* out, int L, int d, int H, const
   if constexpr (VARLEN) { row0 = (size_t)off[b]; L = off[b + 1] - off[b]; }
   float* s = sc + (size_t)wave * L;
   const T* base = VARLEN ? qkv + row0 * 3 * d + h * dh : qkv + (size_t)b * L * 3 * d + h * dh;
-  for (int i = blockIdx.y * nw + wave; i < L; i += gridDim.y * nw) {
-    const T* q = base + (size_t)i * 3 * d;
-    float mx = -INFINITY;
-    for (int j = lane; j < L; j += 64) {
-      const T* k = base + (size_t)j * 3 * d + d;
-      float a = 0.f;
-      for (int c = 0; c < dh; ++c) a = fmaf(to_f32<T>(q[c]), to_f32<T>(k[c]), a);
-      a *= scale;
-      s[j] = a;
-      mx = fmaxf(mx, a);
-    }
-    mx = wave_max(mx);
-    float sum = 0.f;
-    for (int j = lane; j < L; j += 64) { const float p = expf(s[j] - mx); s[j] = p; sum += p; }
-    sum = wave_sum(sum);
-    __builtin_amdgcn_wave_barrier();
-    const float inv = 1.f / sum;
-    for (int c = lane; c < dh; c += 64) {
-      float o = 0.f;
-      for (int j = 0; j < L; ++j) o = fmaf(s[j], to_f32<T>(base[(size_t)j * 3 * d + 2 * d + c]), o);
-      out[((VARLEN ? row0 : (size_t)b * L) + i) * d + h * dh + c] = from_f32<T>(o * inv);
-    }
-    __builtin_amdgcn_wave_barrier();
-  }
+  for (int i = blockIdx.y * nw + wave; i < L; i += gridDim.y * nw)
+    tf_attn_row<T>(base, (size_t)3 * d, out + ((VARLEN ? row0 : (size_t)b * L) + i) * d + h * dh, s, i, L, d, dh, scale, lane);
 }
 
 // ---- MFMA linear: Y[128-token tile][128-feature tile], K walked in 64-wide chunks ----------------------------
@@ -424,19 +444,146 @@ __global__ __launch_bounds__(256, 2) void tf_gemm_mfma(const T* __restrict__ X, 
 #endif
 }
 
-// ---- MFMA attention, head_dim 64 ------------------------------------------------------------------------------
-// One workgroup per (batch, head); K and V of that head are staged once into LDS (row-major [key][64], 128-byte
-// rows); each wave owns 32 queries and walks the keys 32 at a time:
+// ---- MFMA attention, 16-bit: head_dim 64 with the keys resident (tf_attn_mfma), head_dim 32 HD32 with the keys streamed (tf_attn_tiled) ----
+// A wave owns 32 queries of one (batch, head), Q fragments in registers, and walks the keys 32 at a time in ascending order, K and V
+// rows of the step in LDS images (row-major [key][head_dim], rows of RB = 64 HD32 bytes).  One 32-key step (tf_attn16_step):
 //   S^T[key][query] = K . Q^T        (A = K rows by ds_read_b128, B = Q fragments kept in registers)
 //   online softmax over keys         (in-lane over 8 values, then lanes +16 / +32 that share the query column)
 //   O^T[dh][query] += V^T . P^T      (B = P^T straight from the S^T accumulators: k-slot j of lane group g is key
 //                                     4g+j (j<4) or 16+4g+(j-4); A = V^T read with ds_read_b64_tr_b16 in the SAME
 //                                     permuted key order: two 4-row x 16-column transposed blocks per fragment)
-// K image swizzle: slot ^ ((row>>1)&7) (row reads); V image swizzle: slot ^ (((row>>1)&3)<<1) (keeps the 32-byte
-// column pairs of the transposed reads adjacent and spreads the 8 rows of a 32-lane half over all banks).
+// Both kernels call that one step, so at head_dim 64 their key loops give equal bits by construction; a kernel keeps how the images
+// get into LDS, its barriers and which steps it runs.  The epilogue (tf_attn16_store) is tf_attn_tiled's; tf_attn_mfma holds a copy.
+// ds_read_b64_tr_b16 needs EXEC all ones: the step has no lane-dependent branch and no early return, and its callers put none
+// around it; queries past L are clamped to L - 1 and not stored, keys at or past L hold zeros in the images and their scores become
+// -inf before the maximum.  The first step always holds key 0 < L, so every query's running maximum is finite from the first step
+// on, and exp2(-inf - max) is 0, never NaN.
+// LDS images (bank = (addr / 4) % 64 for ds_read_b128 and the transposed read; r = key row in its image, c = 16-byte chunk of the
+// row; both XORs stay inside an aligned group of four chunks, so rows of 12 chunks are safe; both depend on r & 15 or less, so an
+// image may start at any multiple of 16 rows):
+//   K rows, ds_read_b128 (a 16-lane group = 16 rows li, eight of them at chunk c0 and eight at c0 ^ 1):
+//     64-B and 192-B rows   c ^ (-(r >> 2) & 3)   rows r, r + 4, r + 8, r + 12 start on one slot quad and take its four slots
+//     128-B rows            c ^ ((r >> 1) & 7)
+//     256-B rows            c ^ (r & 15)
+//   V rows, transposed read (a 32-lane half = 8 rows x one 32-byte column pair p; the XOR moves whole pairs, which keeps the 32-byte
+//   column pairs of the transposed reads adjacent):
+//     64-B and 192-B rows   p ^ ((r >> 2) & 1)    128-B rows  p ^ ((r >> 1) & 3)    256-B rows  p ^ (r & 7)
+//   each makes the 8 rows of a half cover the 8 32-byte segments of the 256-byte bank row once.
 typedef short s16x4 __attribute__((ext_vector_type(4)));
 typedef short s16x8 __attribute__((ext_vector_type(8)));
 
+template <int HD32> __device__ __forceinline__ int tf_tiled_kswz(int r) {
+  return HD32 == 2 ? (r >> 1) & 7 : HD32 == 4 ? r & 15 : (-(r >> 2)) & 3;
+}
+template <int HD32> __device__ __forceinline__ int tf_tiled_vswz(int r) {
+  return (HD32 == 2 ? (r >> 1) & 3 : HD32 == 4 ? r & 7 : (r >> 2) & 1) << 1;
+}
+
+// A lane's role in every step: computed once per kernel, in front of the key loop
+struct TfAttn16Lane { int g, li, ksw, trp, vrow, vsw; };
+template <int HD32> __device__ __forceinline__ TfAttn16Lane tf_attn16_lane(int lane) {
+  TfAttn16Lane r;
+  r.g = lane >> 4; r.li = lane & 15;
+  r.ksw = tf_tiled_kswz<HD32>(r.li);             // K-image swizzle of this lane's key row (row = 16-aligned + li)
+  const int trq = r.li >> 2;                     // transposed-read role of this lane inside its 16-lane group
+  r.trp = r.li & 3;
+  r.vrow = r.g * 4 + trq;                        // ... its V row in a 32-key step (and vrow + 16); the swizzle sees vrow & 7
+  r.vsw = tf_tiled_vswz<HD32>(r.vrow);
+  return r;
+}
+
+// One 32-key step of a wave.  Ki, Vi: the K and V images; kl: the step's first row in them (a multiple of 32), kb: the key that row
+// holds; qf: the wave's Q fragments; mrun, lrun, o: running maximum, running sum and unnormalised output of its 2 x 16 queries.
+template <typename T, int HD32>
+__device__ __forceinline__ void tf_attn16_step(const char* Ki, const char* Vi, int kb, int kl, int L, float scale_log2e,
+                                               const TfAttn16Lane& ln, const typename Elem<T>::frag (&qf)[2][HD32], float (&mrun)[2],
+                                               float (&lrun)[2], f32x4 (&o)[2][2 * HD32]) {
+  typedef typename Elem<T>::frag frag;
+  constexpr int RB = 64 * HD32;
+  const int g = ln.g, li = ln.li, ksw = ln.ksw, trp = ln.trp, vrow = ln.vrow, vsw = ln.vsw;
+  f32x4 s[2][2];
+#pragma unroll
+  for (int u = 0; u < 2; ++u)
+#pragma unroll
+    for (int qt = 0; qt < 2; ++qt) s[u][qt] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int u = 0; u < 2; ++u)
+#pragma unroll
+    for (int ks = 0; ks < HD32; ++ks) {
+      const frag kf = *(const frag*)(Ki + (kl + u * 16 + li) * RB + (((ks * 4 + g) ^ ksw) << 4));
+#pragma unroll
+      for (int qt = 0; qt < 2; ++qt) s[u][qt] = Elem<T>::mfma(kf, qf[qt][ks], s[u][qt]);
+    }
+  frag pf[2];
+#pragma unroll
+  for (int qt = 0; qt < 2; ++qt) {
+    float v[8];
+    float mx = -INFINITY;
+#pragma unroll
+    for (int u = 0; u < 2; ++u)
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const int key = kb + u * 16 + g * 4 + q;
+        const float x = key < L ? s[u][qt][q] * scale_log2e : -INFINITY;
+        v[u * 4 + q] = x;
+        mx = fmaxf(mx, x);
+      }
+    mx = fmaxf(mx, __shfl_xor(mx, 16));
+    mx = fmaxf(mx, __shfl_xor(mx, 32));
+    const float mnew = fmaxf(mrun[qt], mx);
+    const float alpha = __builtin_amdgcn_exp2f(mrun[qt] - mnew);
+    float ps = 0.f;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) { v[i] = __builtin_amdgcn_exp2f(v[i] - mnew); ps += v[i]; }
+    lrun[qt] = lrun[qt] * alpha + ps;
+    mrun[qt] = mnew;
+#pragma unroll
+    for (int dt = 0; dt < 2 * HD32; ++dt) o[qt][dt] *= alpha;
+    u32x4 pk;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) pk[i] = pack2<T>(v[i * 2], v[i * 2 + 1]);
+    pf[qt] = __builtin_bit_cast(frag, pk);
+  }
+#pragma unroll
+  for (int dt = 0; dt < 2 * HD32; ++dt) {
+    const int a0 = (kl + vrow) * RB + (((dt * 2 + (trp >> 1)) ^ vsw) << 4) + (trp & 1) * 8;
+    const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(Vi + a0));
+    const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(Vi + a0 + 16 * RB));
+    const s16x8 v8 = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+    const frag vf = __builtin_bit_cast(frag, v8);
+#pragma unroll
+    for (int qt = 0; qt < 2; ++qt) o[qt][dt] = Elem<T>::mfma(vf, pf[qt], o[qt][dt]);
+  }
+}
+
+// ... and behind the last step: o / l of the wave's queries q0 .. q0 + 31 that lie inside the sequence, to columns hcol .. of rows
+// row0 + query of out [.][d]
+template <typename T, int HD32>
+__device__ __forceinline__ void tf_attn16_store(T* out, size_t row0, int d, int hcol, int q0, int L, int lane, const float (&lrun)[2],
+                                                const f32x4 (&o)[2][2 * HD32]) {
+  const int g = lane >> 4, li = lane & 15;
+#pragma unroll
+  for (int qt = 0; qt < 2; ++qt) {
+    float lt = lrun[qt];
+    lt += __shfl_xor(lt, 16);
+    lt += __shfl_xor(lt, 32);
+    const float inv = 1.f / lt;
+    const int qi = q0 + qt * 16 + li;
+    if (qi < L) {
+      T* dst = out + (row0 + qi) * d + hcol + g * 4;
+#pragma unroll
+      for (int dt = 0; dt < 2 * HD32; ++dt) {
+        u32x2 w2;
+        w2[0] = pack2<T>(o[qt][dt][0] * inv, o[qt][dt][1] * inv);
+        w2[1] = pack2<T>(o[qt][dt][2] * inv, o[qt][dt][3] * inv);
+        *(u32x2*)(dst + dt * 16) = w2;
+      }
+    }
+  }
+}
+
+// tf_attn_mfma: one workgroup per (batch, head); K and V of that head are staged once into LDS (128-byte rows), one __syncthreads,
+// then every wave walks all keys.
 // VARLEN: launched with pad32(longest) / 32 waves and that much LDS; L and Lp become the sequence's own (the V image starts behind
 // its own K image), a wave whose 32 queries lie past the sequence leaves behind the one __syncthreads (a whole wave: EXEC of the
 // others stays all ones for the transposed reads).
@@ -460,8 +607,8 @@ __global__ __launch_bounds__(1024) void tf_attn_mfma(const T* __restrict__ qkv, 
       kv = *(const u32x4*)(src + d);
       vv = *(const u32x4*)(src + 2 * d);
     }
-    *(u32x4*)(Ki + row * 128 + ((ch ^ ((row >> 1) & 7)) << 4)) = kv;
-    *(u32x4*)(Vi + row * 128 + ((ch ^ (((row >> 1) & 3) << 1)) << 4)) = vv;
+    *(u32x4*)(Ki + row * 128 + ((ch ^ tf_tiled_kswz<2>(row)) << 4)) = kv;
+    *(u32x4*)(Vi + row * 128 + ((ch ^ tf_tiled_vswz<2>(row)) << 4)) = vv;
   }
   __syncthreads();
 
@@ -482,69 +629,10 @@ __global__ __launch_bounds__(1024) void tf_attn_mfma(const T* __restrict__ qkv, 
 #pragma unroll
     for (int dt = 0; dt < 4; ++dt) o[qt][dt] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-  const int ksw = (li >> 1) & 7;                 // K-image swizzle of this lane's key row (row = 16-aligned + li)
-  const int trq = li >> 2, trp = li & 3;         // transposed-read role of this lane inside its 16-lane group
-
-  for (int kb = 0; kb < Lp; kb += 32) {
-    f32x4 s[2][2];
-#pragma unroll
-    for (int t = 0; t < 2; ++t)
-#pragma unroll
-      for (int qt = 0; qt < 2; ++qt) s[t][qt] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int t = 0; t < 2; ++t)
-#pragma unroll
-      for (int ks = 0; ks < 2; ++ks) {
-        const frag kf = *(const frag*)(Ki + (kb + t * 16 + li) * 128 + (((ks * 4 + g) ^ ksw) << 4));
-#pragma unroll
-        for (int qt = 0; qt < 2; ++qt) s[t][qt] = Elem<T>::mfma(kf, qf[qt][ks], s[t][qt]);
-      }
-    frag pf[2];
-#pragma unroll
-    for (int qt = 0; qt < 2; ++qt) {
-      float v[8];
-      float mx = -INFINITY;
-#pragma unroll
-      for (int t = 0; t < 2; ++t)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const int key = kb + t * 16 + g * 4 + q;
-          const float x = key < L ? s[t][qt][q] * scale_log2e : -INFINITY;
-          v[t * 4 + q] = x;
-          mx = fmaxf(mx, x);
-        }
-      mx = fmaxf(mx, __shfl_xor(mx, 16));
-      mx = fmaxf(mx, __shfl_xor(mx, 32));
-      const float mnew = fmaxf(mrun[qt], mx);
-      const float alpha = __builtin_amdgcn_exp2f(mrun[qt] - mnew);
-      float ps = 0.f;
-#pragma unroll
-      for (int i = 0; i < 8; ++i) { v[i] = __builtin_amdgcn_exp2f(v[i] - mnew); ps += v[i]; }
-      lrun[qt] = lrun[qt] * alpha + ps;
-      mrun[qt] = mnew;
-#pragma unroll
-      for (int dt = 0; dt < 4; ++dt) o[qt][dt] *= alpha;
-      u32x4 pk;
-#pragma unroll
-      for (int i = 0; i < 4; ++i) pk[i] = pack2<T>(v[i * 2], v[i * 2 + 1]);
-      pf[qt] = __builtin_bit_cast(frag, pk);
-    }
-#pragma unroll
-    for (int dt = 0; dt < 4; ++dt) {
-      s16x4 lo, hi;
-      {
-        const int r0 = kb + g * 4 + trq, r1 = r0 + 16;
-        const int a0 = r0 * 128 + (((dt * 2 + (trp >> 1)) ^ (((r0 >> 1) & 3) << 1)) << 4) + (trp & 1) * 8;
-        const int a1 = r1 * 128 + (((dt * 2 + (trp >> 1)) ^ (((r1 >> 1) & 3) << 1)) << 4) + (trp & 1) * 8;
-        lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(Vi + a0));
-        hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(Vi + a1));
-      }
-      const s16x8 v8 = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-      const frag vf = __builtin_bit_cast(frag, v8);
-#pragma unroll
-      for (int qt = 0; qt < 2; ++qt) o[qt][dt] = Elem<T>::mfma(vf, pf[qt], o[qt][dt]);
-    }
-  }
+  const TfAttn16Lane ln = tf_attn16_lane<2>(lane);
+  for (int kb = 0; kb < Lp; kb += 32) tf_attn16_step<T, 2>(Ki + kb * 128, Vi + kb * 128, kb, 0, L, scale_log2e, ln, qf, mrun, lrun, o);
+  // tf_attn16_store's body, kept as a copy: through the call this kernel allocates 98 VGPRs instead of 96 (5 -> 4 waves per SIMD).
+  // Change the expressions here and there together (test_head_dim_64_gives_the_bits_of_the_resident_kernel holds them to equal bits).
 #pragma unroll
   for (int qt = 0; qt < 2; ++qt) {
     float lt = lrun[qt];
@@ -565,35 +653,14 @@ __global__ __launch_bounds__(1024) void tf_attn_mfma(const T* __restrict__ qkv, 
   }
 }
 
-// ---- MFMA attention, head_dim 32 HD32 (32 .. 128), any sequence length (option attn_tiled) -------------------------
-// tf_attn_mfma's arithmetic -- the same lane-to-key map, 32-key steps in ascending key order, expression order -- with K and V
-// streamed instead of resident.  Workgroup = 128 queries of one (batch, head): four waves of 32 queries, Q fragments in registers;
-// grid (B H, ceil(L / 128)).  Keys arrive in blocks of kTfAttnTiledKB = 64 (two 32-key steps) through a ring of kTfAttnTiledRing = 2
-// LDS stages (K block | V block, rows of RB = 64 HD32 bytes).  Register staging: block t + 1 is loaded into VGPRs in front of the
-// barrier of block t, stays in flight under block t's MFMAs and is written to the other stage behind them.  One barrier per block:
-// it publishes the writes of stage t & 1 and tells that every wave is done reading stage (t + 1) & 1 (block t - 1).
+// tf_attn_tiled (option attn_tiled): K and V streamed instead of resident.  Workgroup = 128 queries of one
+// (batch, head): four waves of 32 queries; grid (B H, ceil(L / 128)).  Keys arrive in blocks of kTfAttnTiledKB = 64 (two 32-key
+// steps) through a ring of kTfAttnTiledRing = 2 LDS stages (K block | V block).  Register staging: block t + 1 is loaded into VGPRs
+// in front of the barrier of block t, stays in flight under block t's MFMAs and is written to the other stage behind them.  One
+// barrier per block: it publishes the writes of stage t & 1 and tells that every wave is done reading stage (t + 1) & 1 (block t - 1).
 // Keys at or past L: the lane loads row L - 1 instead (never a row past the sequence: the buffer may end at row B L) and writes
-// zeros to LDS; their scores become -inf before the maximum.  Block 0 always holds key 0 < L, so every query's running maximum is
-// finite from the first step on, and exp2(-inf - max) is 0, never NaN; a 32-key step that lies wholly past L is skipped by a
-// branch on the step index (the same for every lane).
-// ds_read_b64_tr_b16 needs EXEC all ones: no early return, no lane-dependent branch around the key loop; queries past L are clamped
-// to L - 1 and not stored.
-// LDS images (bank = (addr / 4) % 64 for ds_read_b128 and the transposed read; r = key row in its block, c = 16-byte chunk of the
-// row; both XORs stay inside an aligned group of four chunks, so rows of 12 chunks are safe):
-//   K rows, ds_read_b128 (a 16-lane group = 16 rows li, eight of them at chunk c0 and eight at c0 ^ 1):
-//     64-B and 192-B rows   c ^ (-(r >> 2) & 3)   rows r, r + 4, r + 8, r + 12 start on one slot quad and take its four slots
-//     128-B rows            c ^ ((r >> 1) & 7)    (tf_attn_mfma's)
-//     256-B rows            c ^ (r & 15)
-//   V rows, transposed read (a 32-lane half = 8 rows x one 32-byte column pair p; the XOR moves whole pairs):
-//     64-B and 192-B rows   p ^ ((r >> 2) & 1)    128-B rows  p ^ ((r >> 1) & 3)  (tf_attn_mfma's)    256-B rows  p ^ (r & 7)
-//   each makes the 8 rows of a half cover the 8 32-byte segments of the 256-byte bank row once.
-template <int HD32> __device__ __forceinline__ int tf_tiled_kswz(int r) {
-  return HD32 == 2 ? (r >> 1) & 7 : HD32 == 4 ? r & 15 : (-(r >> 2)) & 3;
-}
-template <int HD32> __device__ __forceinline__ int tf_tiled_vswz(int r) {
-  return (HD32 == 2 ? (r >> 1) & 3 : HD32 == 4 ? r & 7 : (r >> 2) & 1) << 1;
-}
-
+// zeros to LDS; a 32-key step that lies wholly past L is skipped by a branch on the step index (the same for every lane: EXEC stays
+// all ones, no early return, no lane-dependent branch around the key loop).
 // VARLEN: grid.y counts the query blocks of the longest sequence; a workgroup whose first query lies at or past its own sequence's
 // length leaves before its first load and barrier (all four waves: the condition is per workgroup), one with some valid queries
 // keeps all four waves in the barrier loop as above; nb, the step skip and the masks use the sequence's own L.
@@ -664,11 +731,7 @@ __global__ __launch_bounds__(256, 2) void tf_attn_tiled(const T* __restrict__ qk
 #pragma unroll
     for (int dt = 0; dt < 2 * HD32; ++dt) o[qt][dt] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-  const int ksw = tf_tiled_kswz<HD32>(li);       // K-image swizzle of this lane's key row (row = 16-aligned + li)
-  const int trq = li >> 2, trp = li & 3;         // transposed-read role of this lane inside its 16-lane group
-  const int vrow = g * 4 + trq;                  // ... its V row in a 32-key step (and vrow + 16); the swizzle sees vrow & 7
-  const int vsw = tf_tiled_vswz<HD32>(vrow);
-
+  const TfAttn16Lane ln = tf_attn16_lane<HD32>(lane);
   for (int t = 0; t < nb; ++t) {
     gload((t + 1) * KB);                         // (past the last block: row L - 1 again, zeros, a stage nobody reads)
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -679,80 +742,11 @@ __global__ __launch_bounds__(256, 2) void tf_attn_tiled(const T* __restrict__ qk
     for (int st = 0; st < KB / 32; ++st) {
       const int kl = st * 32, kb = t * KB + kl;
       if (kb >= L) continue;                     // uniform: EXEC stays all ones
-      f32x4 s[2][2];
-#pragma unroll
-      for (int u = 0; u < 2; ++u)
-#pragma unroll
-        for (int qt = 0; qt < 2; ++qt) s[u][qt] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int u = 0; u < 2; ++u)
-#pragma unroll
-        for (int ks = 0; ks < HD32; ++ks) {
-          const frag kf = *(const frag*)(Ki + (kl + u * 16 + li) * RB + (((ks * 4 + g) ^ ksw) << 4));
-#pragma unroll
-          for (int qt = 0; qt < 2; ++qt) s[u][qt] = Elem<T>::mfma(kf, qf[qt][ks], s[u][qt]);
-        }
-      frag pf[2];
-#pragma unroll
-      for (int qt = 0; qt < 2; ++qt) {
-        float v[8];
-        float mx = -INFINITY;
-#pragma unroll
-        for (int u = 0; u < 2; ++u)
-#pragma unroll
-          for (int q = 0; q < 4; ++q) {
-            const int key = kb + u * 16 + g * 4 + q;
-            const float x = key < L ? s[u][qt][q] * scale_log2e : -INFINITY;
-            v[u * 4 + q] = x;
-            mx = fmaxf(mx, x);
-          }
-        mx = fmaxf(mx, __shfl_xor(mx, 16));
-        mx = fmaxf(mx, __shfl_xor(mx, 32));
-        const float mnew = fmaxf(mrun[qt], mx);
-        const float alpha = __builtin_amdgcn_exp2f(mrun[qt] - mnew);
-        float ps = 0.f;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) { v[i] = __builtin_amdgcn_exp2f(v[i] - mnew); ps += v[i]; }
-        lrun[qt] = lrun[qt] * alpha + ps;
-        mrun[qt] = mnew;
-#pragma unroll
-        for (int dt = 0; dt < 2 * HD32; ++dt) o[qt][dt] *= alpha;
-        u32x4 pk;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) pk[i] = pack2<T>(v[i * 2], v[i * 2 + 1]);
-        pf[qt] = __builtin_bit_cast(frag, pk);
-      }
-#pragma unroll
-      for (int dt = 0; dt < 2 * HD32; ++dt) {
-        const int a0 = (kl + vrow) * RB + (((dt * 2 + (trp >> 1)) ^ vsw) << 4) + (trp & 1) * 8;
-        const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(Vi + a0));
-        const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(Vi + a0 + 16 * RB));
-        const s16x8 v8 = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-        const frag vf = __builtin_bit_cast(frag, v8);
-#pragma unroll
-        for (int qt = 0; qt < 2; ++qt) o[qt][dt] = Elem<T>::mfma(vf, pf[qt], o[qt][dt]);
-      }
+      tf_attn16_step<T, HD32>(Ki, Vi, kb, kl, L, scale_log2e, ln, qf, mrun, lrun, o);
     }
     lwrite((t + 1) & 1);
   }
-#pragma unroll
-  for (int qt = 0; qt < 2; ++qt) {
-    float lt = lrun[qt];
-    lt += __shfl_xor(lt, 16);
-    lt += __shfl_xor(lt, 32);
-    const float inv = 1.f / lt;
-    const int qi = q0 + qt * 16 + li;
-    if (qi < L) {
-      T* dst = out + ((VARLEN ? row0 : (size_t)b * L) + qi) * d + h * HD + g * 4;
-#pragma unroll
-      for (int dt = 0; dt < 2 * HD32; ++dt) {
-        u32x2 w2;
-        w2[0] = pack2<T>(o[qt][dt][0] * inv, o[qt][dt][1] * inv);
-        w2[1] = pack2<T>(o[qt][dt][2] * inv, o[qt][dt][3] * inv);
-        *(u32x2*)(dst + dt * 16) = w2;
-      }
-    }
-  }
+  tf_attn16_store<T, HD32>(out, VARLEN ? row0 : (size_t)b * L, d, h * HD, q0, L, lane, lrun, o);
 }
 
 // ---- float32 on the exact-fp32 matrix instruction (FLOPE_DT_F32 with option f32mfma = 1) ---------------------------------
@@ -1000,106 +994,40 @@ __global__ __launch_bounds__(256) void tf_attn_f32m(const float* __restrict__ qk
 // One launch per forward: workgroup b keeps every activation of sequence b in LDS at the offsets of tf_fused_plan.h and walks the
 // launch sequence of run_forward<float> phase by phase, a workgroup barrier where that sequence has a kernel boundary.  The result
 // is the launch sequence's, bit for bit: every generic float32 kernel computes an element in an order that does not depend on
-// which thread computes it, and the helpers below restate those orders expression by expression --
-//   tf_fz_chain    tf_linear_generic   one fmaf chain k = 0 .. K - 1 from 0.f, + b, + residual, ReLU
-//   tf_fz_rowwave  tf_linear_rowwave   (N <= 16, no residual) one wave per row, lane-strided k, wave_sum, + b, ReLU
-//   tf_fz_ln       tf_layernorm<float> one wave per row
-//   tf_fz_attn     tf_attn_generic     one wave per (head, query)
+// which thread computes it, and each phase below calls the definition its kernel calls, float instantiation, on LDS rows --
+//   linear with N > 16 or a residual   tf_linear_elem     (tf_linear_generic), elements strided over the 256 threads
+//   linear with N <= 16, no residual   tf_rowwave_row     (tf_linear_rowwave), rows strided over the four waves
+//   LayerNorm                          tf_layernorm_row   (tf_layernorm), rows strided over the four waves
+//   attention                          tf_attn_row        (tf_attn_generic), (head, query) pairs strided over the four waves
 // Weights, biases and LayerNorm parameters are read through L2 from the handle's float32 arrays; tab is the device table
 // flope_tf_load_weights builds: {embedding w, b, out_layer w, b}, then per layer {in_proj w, b, out_proj w, b, linear1 w, b,
 // linear2 w, b, norm1 w, b, norm2 w, b}.
 constexpr int kTfFusedTabHead = 4, kTfFusedTabLayer = 12;
 
-__device__ __forceinline__ void tf_fz_chain(const float* X, int xld, const float* __restrict__ W, const float* __restrict__ b,
-                                            const float* R, int rld, float* Y, int yld, int M, int K, int N, int relu) {
-  for (int idx = threadIdx.x; idx < M * N; idx += 256) {
-    const int m = idx / N, n = idx - m * N;
-    const float* w = W + (size_t)n * K;
-    const float* xr = X + m * xld;
-    float acc = 0.f;
-    for (int k = 0; k < K; ++k) acc = fmaf(xr[k], w[k], acc);
-    acc += b[n];
-    if (R) acc += R[m * rld + n];
-    if (relu) acc = fmaxf(acc, 0.f);
-    Y[(size_t)m * yld + n] = acc;
-  }
-}
-
-__device__ __forceinline__ void tf_fz_rowwave(const float* X, int xld, const float* __restrict__ W, const float* __restrict__ b, float* Y,
-                                              int yld, int M, int K, int N, int relu) {
-  const int lane = threadIdx.x & 63;
-  for (int m = threadIdx.x >> 6; m < M; m += 4) {
-    float acc[16];
-#pragma unroll
-    for (int n = 0; n < 16; ++n) acc[n] = 0.f;
-    for (int k = lane; k < K; k += 64) {
-      const float x = X[m * xld + k];
-#pragma unroll
-      for (int n = 0; n < 16; ++n)
-        if (n < N) acc[n] = fmaf(x, W[(size_t)n * K + k], acc[n]);
-    }
-#pragma unroll
-    for (int n = 0; n < 16; ++n)
-      if (n < N) {
-        float v = wave_sum(acc[n]) + b[n];
-        if (relu) v = fmaxf(v, 0.f);
-        if (lane == 0) Y[(size_t)m * yld + n] = v;
-      }
-  }
-}
-
 // the order launch_linear gives this linear in the float32 launch sequence
-__device__ __forceinline__ void tf_fz_linear(const float* X, int xld, const float* __restrict__ W, const float* __restrict__ b,
-                                             const float* R, int rld, float* Y, int yld, int M, int K, int N, int relu) {
-  if (flope_tf_plan::tf_fused_rowwave_order(N, R != nullptr)) tf_fz_rowwave(X, xld, W, b, Y, yld, M, K, N, relu);
-  else tf_fz_chain(X, xld, W, b, R, rld, Y, yld, M, K, N, relu);
+__device__ __forceinline__ void tf_fz_linear(const float* X, int xld, const float* W, const float* b, const float* R, int rld, float* Y,
+                                             int yld, int M, int K, int N, int relu) {
+  if (flope_tf_plan::tf_fused_rowwave_order(N, R != nullptr)) {
+    for (int m = threadIdx.x >> 6; m < M; m += 4) tf_rowwave_row<float>(X, xld, 1, W, b, Y, yld, 1, m, K, N, relu, threadIdx.x & 63);
+  } else {
+    for (int idx = threadIdx.x; idx < M * N; idx += 256) {
+      const int m = idx / N;
+      tf_linear_elem<float>(X, xld, 1, W, b, R, rld, Y, yld, 1, m, idx - m * N, K, relu);
+    }
+  }
 }
 
-__device__ __forceinline__ void tf_fz_ln(const float* in, float* out, const float* __restrict__ w, const float* __restrict__ b, int M, int d) {
-  const int lane = threadIdx.x & 63;
-  for (int row = threadIdx.x >> 6; row < M; row += 4) {
-    const float* x = in + row * d;
-    float s = 0.f;
-    for (int c = lane; c < d; c += 64) s += x[c];
-    const float mean = wave_sum(s) / d;
-    float v = 0.f;
-    for (int c = lane; c < d; c += 64) { const float t = x[c] - mean; v = fmaf(t, t, v); }
-    const float rstd = 1.f / sqrtf(wave_sum(v) / d + 1e-5f);
-    float* y = out + row * d;
-    for (int c = lane; c < d; c += 64) y[c] = (x[c] - mean) * rstd * w[c] + b[c];
-  }
+__device__ __forceinline__ void tf_fz_layernorm(const float* in, float* out, const float* w, const float* b, int M, int d) {
+  for (int row = threadIdx.x >> 6; row < M; row += 4) tf_layernorm_row<float>(in + row * d, out + row * d, w, b, d, threadIdx.x & 63);
 }
 
 // qkv rows of qld floats (q | k | v in the first 3 d), s: this wave's score row
-__device__ __forceinline__ void tf_fz_attn(const float* qkv, int qld, float* att, float* s, int L, int d, int H) {
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+__device__ __forceinline__ void tf_fz_attention(const float* qkv, int qld, float* att, float* s, int L, int d, int H) {
   const int dh = d / H;
   const float scale = 1.f / sqrtf((float)dh);
-  for (int it = wave; it < H * L; it += 4) {
+  for (int it = threadIdx.x >> 6; it < H * L; it += 4) {
     const int h = it / L, i = it - h * L;
-    const float* base = qkv + h * dh;
-    const float* q = base + i * qld;
-    float mx = -INFINITY;
-    for (int j = lane; j < L; j += 64) {
-      const float* k = base + j * qld + d;
-      float a = 0.f;
-      for (int c = 0; c < dh; ++c) a = fmaf(q[c], k[c], a);
-      a *= scale;
-      s[j] = a;
-      mx = fmaxf(mx, a);
-    }
-    mx = wave_max(mx);
-    float sum = 0.f;
-    for (int j = lane; j < L; j += 64) { const float p = expf(s[j] - mx); s[j] = p; sum += p; }
-    sum = wave_sum(sum);
-    __builtin_amdgcn_wave_barrier();
-    const float inv = 1.f / sum;
-    for (int c = lane; c < dh; c += 64) {
-      float o = 0.f;
-      for (int j = 0; j < L; ++j) o = fmaf(s[j], base[j * qld + 2 * d + c], o);
-      att[i * d + h * dh + c] = o * inv;
-    }
-    __builtin_amdgcn_wave_barrier();
+    tf_attn_row<float>(qkv + h * dh, (size_t)qld, att + i * d + h * dh, s, i, L, d, dh, scale, threadIdx.x & 63);
   }
 }
 
@@ -1130,17 +1058,17 @@ __global__ __launch_bounds__(256) void tf_fused_f32(const float* __restrict__ x,
     const float* const* t = tab + kTfFusedTabHead + l * kTfFusedTabLayer;
     tf_fz_linear(h, d, t[0], t[1], nullptr, 0, qkv, qld, len, d, 3 * d, 0);
     __syncthreads();
-    tf_fz_attn(qkv, qld, att, sc, len, d, H);
+    tf_fz_attention(qkv, qld, att, sc, len, d, H);
     __syncthreads();
     tf_fz_linear(att, d, t[2], t[3], h, d, h2, d, len, d, d, 0);
     __syncthreads();
-    tf_fz_ln(h2, h, t[8], t[9], len, d);
+    tf_fz_layernorm(h2, h, t[8], t[9], len, d);
     __syncthreads();
     tf_fz_linear(h, d, t[4], t[5], nullptr, 0, ffb, ff, len, d, ff, 1);
     __syncthreads();
     tf_fz_linear(ffb, ff, t[6], t[7], h, d, h2, d, len, ff, d, 0);
     __syncthreads();
-    tf_fz_ln(h2, h, t[10], t[11], len, d);
+    tf_fz_layernorm(h2, h, t[10], t[11], len, d);
     __syncthreads();
   }
   tf_fz_linear(h, d, tab[2], tab[3], nullptr, 0, yb, out_dim, len, d, out_dim, 0);
@@ -1196,6 +1124,14 @@ int tf_fail(flope_tf_encoder* e, int code, const std::string& msg) {
     hipError_t _s = (call);                                                                      \
     if (_s != hipSuccess) return tf_fail(e, FLOPE_EHIP, std::string(#call) + ": " + hipGetErrorString(_s)); \
   } while (0)
+
+// f(TfType<T>{}) for the element type T of the handle's dtype (in f: using T = typename decltype(tag)::type)
+template <typename T> struct TfType { using type = T; };
+template <typename F> int tf_by_dtype(const flope_tf_encoder* e, F&& f) {
+  if (e->dtype == FLOPE_DT_F32) return f(TfType<float>{});
+  if (e->dtype == FLOPE_DT_F16) return f(TfType<f16_t>{});
+  return f(TfType<bf16_t>{});
+}
 
 // [N][K] fp32 -> [N/128][K/64][128 rows][8 slots x 8 k] 16-bit, rows permuted so that MFMA row 4g+q of channel tile
 // ct is feature 16g + 4ct + q of the wave's 64-feature half, slots pre-swizzled (slot j holds chunk j ^ ((r>>1)&7)).
@@ -1303,77 +1239,43 @@ int launch_layernorm(flope_tf_encoder* e, const void* in, void* out, const float
   return id;
 }
 
-// One attention launch: softmax(q k^T / sqrt(head_dim)) v per head, qkv [B][L][3 d] -> att [B][L][d].  The kernel is the one
-// tf_attn_plan.h picks; returns its FLOPE_TF_ATTN_* id, or < 0.
+// One attention launch: softmax(q k^T / sqrt(head_dim)) v per head.  off == nullptr: qkv [B][L][3 d] -> att [B][L][d].  Otherwise a
+// ragged batch: packed qkv [T][3 d] -> att [T][d], sequence b = rows off[b] .. off[b + 1] - 1 (off: the handle's device table), L its
+// longest length, the VARLEN instantiations.  One kernel for the whole batch, the one tf_attn_plan.h picks for L; grid, block and LDS
+// from tf_attn_varlen_launch in both cases.  Returns the kernel's FLOPE_TF_ATTN_* id, or < 0.
 template <typename T>
-int launch_attention(flope_tf_encoder* e, const void* qkv, void* att, int B, int L, hipStream_t st) {
+int launch_attention(flope_tf_encoder* e, const void* qkv, void* att, int B, int L, const int* off, hipStream_t st) {
   using namespace flope_tf_plan;
   const int d = e->d, H = e->H, dh = d / H;
   const int pick = tf_attn_pick(e->dtype, dh, L, e->opt_generic, e->opt_f32m, e->opt_tiled, !(((uintptr_t)qkv | (uintptr_t)att) & 15));
-  if constexpr (!std::is_same<T, float>::value) {
-    if (pick == FLOPE_TF_ATTN_MFMA64) {
-      const int Lp = tf_attn_pad32(L);
-      hipLaunchKernelGGL((tf_attn_mfma<T>), dim3(B * H), dim3(Lp / 32 * 64), tf_attn_mfma64_lds(L), st, (const T*)qkv, (T*)att, L, d, H, Lp,
-                         1.4426950408889634f / sqrtf(64.f), (const int*)nullptr);
-    } else if (pick == FLOPE_TF_ATTN_TILED) {
-      const dim3 grid(B * H, (L + kTfAttnTiledQueries - 1) / kTfAttnTiledQueries);
-      const float scale_log2e = 1.4426950408889634f / sqrtf((float)dh);
-#define TF_ATT(HD32_) hipLaunchKernelGGL((tf_attn_tiled<T, HD32_>), grid, dim3(256), tf_attn_tiled_lds(dh), st, (const T*)qkv, (T*)att, L, d, H, scale_log2e, (const int*)nullptr)
-      if (dh == 32) TF_ATT(1); else if (dh == 64) TF_ATT(2); else if (dh == 96) TF_ATT(3); else TF_ATT(4);
-#undef TF_ATT
-    }
-  }
-  if constexpr (std::is_same<T, float>::value) {
-    if (pick == FLOPE_TF_ATTN_F32M) {
-      const int nt = tf_attn_f32m_nt(dh);
-      const size_t lds = tf_attn_f32m_lds(dh, L);
-      const dim3 grid(B * H, (L + 15) / 16);
-      const float scale = 1.f / sqrtf((float)dh);
-#define TF_ATT(NT_) hipLaunchKernelGGL((tf_attn_f32m<NT_>), grid, dim3(256), lds, st, (const float*)qkv, (float*)att, L, d, H, scale, (const int*)nullptr)
-      if (nt == 1) TF_ATT(1); else if (nt == 2) TF_ATT(2); else if (nt == 4) TF_ATT(4); else TF_ATT(8);
-#undef TF_ATT
-    }
-  }
-  if (pick == FLOPE_TF_ATTN_GENERIC) {
-    const int nw = 4, gy = (L + nw - 1) / nw < 64 ? (L + nw - 1) / nw : 64;
-    hipLaunchKernelGGL((tf_attn_generic<T>), dim3(B * H, gy), dim3(nw * 64), (size_t)nw * L * 4, st, (const T*)qkv, (T*)att, L, d, H, (const int*)nullptr);
-  }
-  TF_HIP(e, hipGetLastError());
-  return pick;
-}
-
-// The same for a ragged batch: packed qkv [T][3 d] -> att [T][d], sequence b = rows off[b] .. off[b + 1] - 1 (off: the handle's
-// device table).  One kernel for the whole batch, the one tf_attn_pick gives the longest sequence; grid, block and LDS from
-// tf_attn_varlen_launch.
-template <typename T>
-int launch_attention_varlen(flope_tf_encoder* e, const void* qkv, void* att, int B, int max_len, const int* off, hipStream_t st) {
-  using namespace flope_tf_plan;
-  const int d = e->d, H = e->H, dh = d / H;
-  const int pick = tf_attn_pick(e->dtype, dh, max_len, e->opt_generic, e->opt_f32m, e->opt_tiled, !(((uintptr_t)qkv | (uintptr_t)att) & 15));
-  const TfAttnLaunch l = tf_attn_varlen_launch(pick, dh, B, H, max_len);
+  const TfAttnLaunch l = tf_attn_varlen_launch(pick, dh, B, H, L);
   const dim3 grid(l.grid_x, l.grid_y), block(l.block);
-  if constexpr (!std::is_same<T, float>::value) {
-    if (pick == FLOPE_TF_ATTN_MFMA64) {
-      hipLaunchKernelGGL((tf_attn_mfma<T, true>), grid, block, l.lds, st, (const T*)qkv, (T*)att, max_len, d, H, tf_attn_pad32(max_len),
-                         1.4426950408889634f / sqrtf(64.f), off);
-    } else if (pick == FLOPE_TF_ATTN_TILED) {
-      const float scale_log2e = 1.4426950408889634f / sqrtf((float)dh);
-#define TF_ATT(HD32_) hipLaunchKernelGGL((tf_attn_tiled<T, HD32_, true>), grid, block, l.lds, st, (const T*)qkv, (T*)att, max_len, d, H, scale_log2e, off)
-      if (dh == 32) TF_ATT(1); else if (dh == 64) TF_ATT(2); else if (dh == 96) TF_ATT(3); else TF_ATT(4);
+  auto launch = [&](auto varlen) {
+    constexpr bool VL = decltype(varlen)::value;
+    if constexpr (!std::is_same<T, float>::value) {
+      if (pick == FLOPE_TF_ATTN_MFMA64) {
+        hipLaunchKernelGGL((tf_attn_mfma<T, VL>), grid, block, l.lds, st, (const T*)qkv, (T*)att, L, d, H, tf_attn_pad32(L),
+                           1.4426950408889634f / sqrtf(64.f), off);
+      } else if (pick == FLOPE_TF_ATTN_TILED) {
+        const float scale_log2e = 1.4426950408889634f / sqrtf((float)dh);
+#define TF_ATT(HD32_) hipLaunchKernelGGL((tf_attn_tiled<T, HD32_, VL>), grid, block, l.lds, st, (const T*)qkv, (T*)att, L, d, H, scale_log2e, off)
+        if (dh == 32) TF_ATT(1); else if (dh == 64) TF_ATT(2); else if (dh == 96) TF_ATT(3); else TF_ATT(4);
 #undef TF_ATT
+      }
     }
-  }
-  if constexpr (std::is_same<T, float>::value) {
-    if (pick == FLOPE_TF_ATTN_F32M) {
-      const int nt = tf_attn_f32m_nt(dh);
-      const float scale = 1.f / sqrtf((float)dh);
-#define TF_ATT(NT_) hipLaunchKernelGGL((tf_attn_f32m<NT_, true>), grid, block, l.lds, st, (const float*)qkv, (float*)att, max_len, d, H, scale, off)
-      if (nt == 1) TF_ATT(1); else if (nt == 2) TF_ATT(2); else if (nt == 4) TF_ATT(4); else TF_ATT(8);
+    if constexpr (std::is_same<T, float>::value) {
+      if (pick == FLOPE_TF_ATTN_F32M) {
+        const int nt = tf_attn_f32m_nt(dh);
+        const float scale = 1.f / sqrtf((float)dh);
+#define TF_ATT(NT_) hipLaunchKernelGGL((tf_attn_f32m<NT_, VL>), grid, block, l.lds, st, (const float*)qkv, (float*)att, L, d, H, scale, off)
+        if (nt == 1) TF_ATT(1); else if (nt == 2) TF_ATT(2); else if (nt == 4) TF_ATT(4); else TF_ATT(8);
 #undef TF_ATT
+      }
     }
-  }
-  if (pick == FLOPE_TF_ATTN_GENERIC)
-    hipLaunchKernelGGL((tf_attn_generic<T, true>), grid, block, l.lds, st, (const T*)qkv, (T*)att, max_len, d, H, off);
+    if (pick == FLOPE_TF_ATTN_GENERIC)
+      hipLaunchKernelGGL((tf_attn_generic<T, VL>), grid, block, l.lds, st, (const T*)qkv, (T*)att, L, d, H, off);
+  };
+  if (off) launch(std::true_type{}); else launch(std::false_type{});
   TF_HIP(e, hipGetLastError());
   return pick;
 }
@@ -1426,7 +1328,7 @@ int run_forward(flope_tf_encoder* e, const float* x, int B, int L, float* y, hip
   } else if ((rc = launch_linear<T>(e, e->emb, x, 1, nullptr, e->h, 0, M, 0, st)) < 0) return rc;
   for (TfLayer& ly : e->layers) {
     if ((rc = launch_linear<T>(e, ly.in_proj, e->h, 0, nullptr, e->qkv, 0, M, 0, st)) < 0) return rc;
-    if ((rc = rg ? launch_attention_varlen<T>(e, e->qkv, e->att, B, rg->max_len, e->vl_off, st) : launch_attention<T>(e, e->qkv, e->att, B, L, st)) < 0) return rc;
+    if ((rc = launch_attention<T>(e, e->qkv, e->att, B, rg ? rg->max_len : L, rg ? e->vl_off : nullptr, st)) < 0) return rc;
     if ((rc = launch_linear<T>(e, ly.out_proj, e->att, 0, e->h, e->h2, 0, M, 0, st)) < 0) return rc;
     if ((rc = launch_layernorm<T>(e, e->h2, e->h, ly.n1w, ly.n1b, M, st)) < 0) return rc;
     if ((rc = launch_linear<T>(e, ly.lin1, e->h, 0, nullptr, e->ffb, 0, M, 1, st)) < 0) return rc;
@@ -1454,6 +1356,45 @@ int launch_fused(flope_tf_encoder* e, const float* x, int B, int L, int Lmax, co
   hipLaunchKernelGGL(tf_fused_f32, dim3((unsigned)B), dim3(256), (size_t)lay.total, st, x, y, off, (const float* const*)e->fused_tab, lay, L, e->in_dim,
                      e->d, e->out_dim, e->H, e->nl, e->ff);
   TF_HIP(e, hipGetLastError());
+  return 0;
+}
+
+// One forward, fixed-length (rg == nullptr) or ragged: the single launch where tf_fused_pick takes it, the launch sequence otherwise;
+// last_fwd records which.
+int tf_forward(flope_tf_encoder* e, const float* x, int B, int L, float* y, hipStream_t st, const TfRagged* rg) {
+  const int Lmax = rg ? rg->max_len : L;
+  e->last_fwd = FLOPE_TF_FWD_LAUNCHES;
+  if (tf_fused_pick(e, Lmax)) {
+    const int rc = launch_fused(e, x, B, L, Lmax, rg ? e->vl_off : nullptr, y, st);
+    if (!rc) e->last_fwd = FLOPE_TF_FWD_FUSED;
+    return rc;
+  }
+  return tf_by_dtype(e, [&](auto tag) { return run_forward<typename decltype(tag)::type>(e, x, B, L, y, st, rg); });
+}
+
+// The argument checks of a fixed-length forward under the caller's name (flope_tf_forward, and flope_tf_forward_plan, which has no
+// buffers: bufs = true).  *empty: an empty batch, nothing to do.
+int tf_check_forward(flope_tf_encoder* e, const std::string& who, int batch, int seq_len, bool bufs, bool* empty) {
+  *empty = false;
+  if (!e) return tf_fail(nullptr, FLOPE_EINVAL, who + ": NULL handle");
+  if (!e->loaded) return tf_fail(e, FLOPE_ESTATE, who + ": weights not loaded");
+  if (batch < 0 || seq_len < 0) return tf_fail(e, FLOPE_EINVAL, who + ": negative size");
+  if (batch == 0 || seq_len == 0) { *empty = true; return 0; }     // buffers may be NULL
+  if (!bufs) return tf_fail(e, FLOPE_EINVAL, who + ": NULL buffer");
+  if ((long long)batch * seq_len > e->max_tokens)
+    return tf_fail(e, FLOPE_EINVAL, who + ": batch*seq_len exceeds max_tokens given to flope_tf_create");
+  return 0;
+}
+
+// ... and of a ragged one, up to the lengths (tf_check_ragged / tf_plan_ragged)
+int tf_check_forward_varlen(flope_tf_encoder* e, const std::string& who, int batch, int seq_len, bool bufs) {
+  if (!e) return tf_fail(nullptr, FLOPE_EINVAL, who + ": NULL handle");
+  if (!e->loaded) return tf_fail(e, FLOPE_ESTATE, who + ": weights not loaded");
+  if (!bufs) return tf_fail(e, FLOPE_EINVAL, who + ": NULL buffer");
+  if (seq_len < 1) return tf_fail(e, FLOPE_EINVAL, who + ": non-positive seq_len");
+  const size_t widest = (size_t)(e->emb.Kp > e->out_dim ? e->emb.Kp : e->out_dim);
+  if (batch > 0 && (size_t)batch * seq_len > (size_t)INT32_MAX * 256 / widest)          // the row-copy kernels' grids
+    return tf_fail(e, FLOPE_EINVAL, who + ": batch*seq_len too large for one launch");
   return 0;
 }
 
@@ -1642,24 +1583,11 @@ extern "C" int flope_tf_load_weights(flope_tf_handle e, int n, const char* const
 }
 
 extern "C" int flope_tf_forward(flope_tf_handle e, const float* x_dev, int batch, int seq_len, float* y_dev, void* stream) {
-  if (!e) return tf_fail(nullptr, FLOPE_EINVAL, "flope_tf_forward: NULL handle");
-  if (!e->loaded) return tf_fail(e, FLOPE_ESTATE, "flope_tf_forward: weights not loaded");
-  if (batch < 0 || seq_len < 0) return tf_fail(e, FLOPE_EINVAL, "flope_tf_forward: negative size");
-  if (batch == 0 || seq_len == 0) return FLOPE_OK;                 // empty batch: nothing to do, buffers may be NULL
-  if (!x_dev || !y_dev) return tf_fail(e, FLOPE_EINVAL, "flope_tf_forward: NULL buffer");
-  if ((long long)batch * seq_len > e->max_tokens)
-    return tf_fail(e, FLOPE_EINVAL, "flope_tf_forward: batch*seq_len exceeds max_tokens given to flope_tf_create");
+  bool empty;
+  int rc;
+  if ((rc = tf_check_forward(e, "flope_tf_forward", batch, seq_len, x_dev && y_dev, &empty)) || empty) return rc;
   TF_HIP(e, hipSetDevice(e->device));
-  hipStream_t st = (hipStream_t)stream;
-  e->last_fwd = FLOPE_TF_FWD_LAUNCHES;
-  if (tf_fused_pick(e, seq_len)) {
-    const int rc = launch_fused(e, x_dev, batch, seq_len, seq_len, nullptr, y_dev, st);
-    if (!rc) e->last_fwd = FLOPE_TF_FWD_FUSED;
-    return rc;
-  }
-  if (e->dtype == FLOPE_DT_F32) return run_forward<float>(e, x_dev, batch, seq_len, y_dev, st);
-  if (e->dtype == FLOPE_DT_F16) return run_forward<f16_t>(e, x_dev, batch, seq_len, y_dev, st);
-  return run_forward<bf16_t>(e, x_dev, batch, seq_len, y_dev, st);
+  return tf_forward(e, x_dev, batch, seq_len, y_dev, (hipStream_t)stream, nullptr);
 }
 
 extern "C" int flope_tf_attention(flope_tf_handle e, const void* qkv_dev, int batch, int seq_len, void* out_dev, void* stream) {
@@ -1671,10 +1599,9 @@ extern "C" int flope_tf_attention(flope_tf_handle e, const void* qkv_dev, int ba
   if (((uintptr_t)qkv_dev | (uintptr_t)out_dev) & (uintptr_t)(e->esz - 1))
     return tf_fail(e, FLOPE_EINVAL, "flope_tf_attention: buffer not aligned to its element type");
   TF_HIP(e, hipSetDevice(e->device));
-  hipStream_t st = (hipStream_t)stream;
-  if (e->dtype == FLOPE_DT_F32) return launch_attention<float>(e, qkv_dev, out_dev, batch, seq_len, st);
-  if (e->dtype == FLOPE_DT_F16) return launch_attention<f16_t>(e, qkv_dev, out_dev, batch, seq_len, st);
-  return launch_attention<bf16_t>(e, qkv_dev, out_dev, batch, seq_len, st);
+  return tf_by_dtype(e, [&](auto tag) {
+    return launch_attention<typename decltype(tag)::type>(e, qkv_dev, out_dev, batch, seq_len, nullptr, (hipStream_t)stream);
+  });
 }
 
 extern "C" int flope_tf_linear(flope_tf_handle e, const char* name, const void* x_dev, int x_f32, const void* res_dev, void* y_dev, int y_f32, int rows,
@@ -1710,10 +1637,11 @@ extern "C" int flope_tf_linear(flope_tf_handle e, const char* name, const void* 
       return tf_fail(e, FLOPE_EINVAL, "flope_tf_linear: the MFMA linear with K % 64 != 0 takes its input as float32 (x_f32), which is zero-padded to roundup(K, 64) columns");
   }
   TF_HIP(e, hipSetDevice(e->device));
-  hipStream_t st = (hipStream_t)stream;
-  if (e->dtype == FLOPE_DT_F32) return launch_linear<float>(e, *l, x_dev, 1, res_dev, y_dev, 1, rows, relu ? 1 : 0, st);
-  if (e->dtype == FLOPE_DT_F16) return launch_linear<f16_t>(e, *l, x_dev, x_f32 ? 1 : 0, res_dev, y_dev, y_f32 ? 1 : 0, rows, relu ? 1 : 0, st);
-  return launch_linear<bf16_t>(e, *l, x_dev, x_f32 ? 1 : 0, res_dev, y_dev, y_f32 ? 1 : 0, rows, relu ? 1 : 0, st);
+  return tf_by_dtype(e, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    constexpr bool f32 = std::is_same<T, float>::value;                // a float32 handle's buffers are float32 whatever the flags say
+    return launch_linear<T>(e, *l, x_dev, f32 || x_f32 ? 1 : 0, res_dev, y_dev, f32 || y_f32 ? 1 : 0, rows, relu ? 1 : 0, (hipStream_t)stream);
+  });
 }
 
 extern "C" int flope_tf_layernorm(flope_tf_handle e, const void* in_dev, void* out_dev, const float* gamma_dev, const float* beta_dev, int rows, void* stream) {
@@ -1727,53 +1655,31 @@ extern "C" int flope_tf_layernorm(flope_tf_handle e, const void* in_dev, void* o
     return tf_fail(e, FLOPE_EINVAL, e->dtype == FLOPE_DT_F32 ? "flope_tf_layernorm: buffer not aligned to its element type"
                                                              : "flope_tf_layernorm: 16-bit handles take in and out 16-byte aligned");
   TF_HIP(e, hipSetDevice(e->device));
-  hipStream_t st = (hipStream_t)stream;
-  if (e->dtype == FLOPE_DT_F32) return launch_layernorm<float>(e, in_dev, out_dev, gamma_dev, beta_dev, rows, st);
-  if (e->dtype == FLOPE_DT_F16) return launch_layernorm<f16_t>(e, in_dev, out_dev, gamma_dev, beta_dev, rows, st);
-  return launch_layernorm<bf16_t>(e, in_dev, out_dev, gamma_dev, beta_dev, rows, st);
+  return tf_by_dtype(e, [&](auto tag) {
+    return launch_layernorm<typename decltype(tag)::type>(e, in_dev, out_dev, gamma_dev, beta_dev, rows, (hipStream_t)stream);
+  });
 }
 
 extern "C" int flope_tf_forward_varlen(flope_tf_handle e, const float* x_dev, int batch, int seq_len, const int* lengths_host, float* y_dev, void* stream) {
-  if (!e) return tf_fail(nullptr, FLOPE_EINVAL, "flope_tf_forward_varlen: NULL handle");
-  if (!e->loaded) return tf_fail(e, FLOPE_ESTATE, "flope_tf_forward_varlen: weights not loaded");
-  if (!x_dev || !y_dev) return tf_fail(e, FLOPE_EINVAL, "flope_tf_forward_varlen: NULL buffer");
-  if (seq_len < 1) return tf_fail(e, FLOPE_EINVAL, "flope_tf_forward_varlen: non-positive seq_len");
-  const size_t widest = (size_t)(e->emb.Kp > e->out_dim ? e->emb.Kp : e->out_dim);
-  if (batch > 0 && (size_t)batch * seq_len > (size_t)INT32_MAX * 256 / widest)          // the row-copy kernels' grids
-    return tf_fail(e, FLOPE_EINVAL, "flope_tf_forward_varlen: batch*seq_len too large for one launch");
+  int rc;
+  if ((rc = tf_check_forward_varlen(e, "flope_tf_forward_varlen", batch, seq_len, x_dev && y_dev))) return rc;
   TF_HIP(e, hipSetDevice(e->device));
   hipStream_t st = (hipStream_t)stream;
   TfRagged rg;
-  int rc;
   if ((rc = tf_plan_ragged(e, "flope_tf_forward_varlen", lengths_host, batch, seq_len, st, &rg))) return rc;
-  e->last_fwd = FLOPE_TF_FWD_LAUNCHES;
-  if (tf_fused_pick(e, rg.max_len)) {
-    rc = launch_fused(e, x_dev, batch, seq_len, rg.max_len, e->vl_off, y_dev, st);
-    if (!rc) e->last_fwd = FLOPE_TF_FWD_FUSED;
-    return rc;
-  }
-  if (e->dtype == FLOPE_DT_F32) return run_forward<float>(e, x_dev, batch, seq_len, y_dev, st, &rg);
-  if (e->dtype == FLOPE_DT_F16) return run_forward<f16_t>(e, x_dev, batch, seq_len, y_dev, st, &rg);
-  return run_forward<bf16_t>(e, x_dev, batch, seq_len, y_dev, st, &rg);
+  return tf_forward(e, x_dev, batch, seq_len, y_dev, st, &rg);
 }
 
 extern "C" int flope_tf_forward_plan(flope_tf_handle e, int batch, int seq_len, const int* lengths_host) {
-  if (!e) return tf_fail(nullptr, FLOPE_EINVAL, "flope_tf_forward_plan: NULL handle");
-  if (!e->loaded) return tf_fail(e, FLOPE_ESTATE, "flope_tf_forward_plan: weights not loaded");
-  if (!lengths_host) {                                               // flope_tf_forward's checks
-    if (batch < 0 || seq_len < 0) return tf_fail(e, FLOPE_EINVAL, "flope_tf_forward_plan: negative size");
-    if (batch == 0 || seq_len == 0) return FLOPE_TF_FWD_LAUNCHES;
-    if ((long long)batch * seq_len > e->max_tokens)
-      return tf_fail(e, FLOPE_EINVAL, "flope_tf_forward_plan: batch*seq_len exceeds max_tokens given to flope_tf_create");
-    return tf_fused_pick(e, seq_len) ? FLOPE_TF_FWD_FUSED : FLOPE_TF_FWD_LAUNCHES;
+  int rc;
+  if (!lengths_host) {
+    bool empty;
+    if ((rc = tf_check_forward(e, "flope_tf_forward_plan", batch, seq_len, true, &empty))) return rc;
+    return !empty && tf_fused_pick(e, seq_len) ? FLOPE_TF_FWD_FUSED : FLOPE_TF_FWD_LAUNCHES;
   }
-  if (seq_len < 1) return tf_fail(e, FLOPE_EINVAL, "flope_tf_forward_plan: non-positive seq_len");      // flope_tf_forward_varlen's
-  const size_t widest = (size_t)(e->emb.Kp > e->out_dim ? e->emb.Kp : e->out_dim);
-  if (batch > 0 && (size_t)batch * seq_len > (size_t)INT32_MAX * 256 / widest)
-    return tf_fail(e, FLOPE_EINVAL, "flope_tf_forward_plan: batch*seq_len too large for one launch");
+  if ((rc = tf_check_forward_varlen(e, "flope_tf_forward_plan", batch, seq_len, true))) return rc;
   std::vector<int> off((size_t)(batch > 0 ? batch : 0) + 1);         // the handle's own table stays as the last forward left it
   TfRagged rg;
-  int rc;
   if ((rc = tf_check_ragged(e, "flope_tf_forward_plan", lengths_host, batch, seq_len, off.data(), &rg))) return rc;
   return tf_fused_pick(e, rg.max_len) ? FLOPE_TF_FWD_FUSED : FLOPE_TF_FWD_LAUNCHES;
 }
@@ -1793,9 +1699,9 @@ extern "C" int flope_tf_attention_varlen(flope_tf_handle e, const void* qkv_dev,
   TfRagged rg;
   int rc;
   if ((rc = tf_plan_ragged(e, "flope_tf_attention_varlen", lengths_host, batch, e->max_tokens, st, &rg))) return rc;   // no padded length here: a length is bounded by max_tokens
-  if (e->dtype == FLOPE_DT_F32) return launch_attention_varlen<float>(e, qkv_dev, out_dev, batch, rg.max_len, e->vl_off, st);
-  if (e->dtype == FLOPE_DT_F16) return launch_attention_varlen<f16_t>(e, qkv_dev, out_dev, batch, rg.max_len, e->vl_off, st);
-  return launch_attention_varlen<bf16_t>(e, qkv_dev, out_dev, batch, rg.max_len, e->vl_off, st);
+  return tf_by_dtype(e, [&](auto tag) {
+    return launch_attention<typename decltype(tag)::type>(e, qkv_dev, out_dev, batch, rg.max_len, e->vl_off, st);
+  });
 }
 
 // algorithmic FLOPs of one forward (2*MAC: linears + QK^T + PV)

@@ -26,7 +26,7 @@ void tf_varlen_launch(int which, int head_dim, int batch, int heads, int max_len
   out4[0] = l.grid_x; out4[1] = l.grid_y; out4[2] = l.block; out4[3] = (long)l.lds;
 }
 
-// the kernel a ragged batch runs: tf_attn_pick at the longest sequence (a pass-through: what launch_attention_varlen hands it is
+// the kernel a ragged batch runs: tf_attn_pick at the longest sequence (a pass-through: what launch_attention hands it for a ragged batch is
 // checked on the device, tests/test_gpu_tf_varlen.py)
 int tf_varlen_pick(int dtype, int head_dim, int max_len, int opt_generic, int opt_f32m, int opt_tiled, int aligned16) {
   return flope_tf_plan::tf_attn_pick(dtype, head_dim, max_len, opt_generic, opt_f32m, opt_tiled, aligned16);

@@ -1,7 +1,7 @@
 """The encoder's single-launch forward on the device (option fused: tf_fused_f32, one sequence per workgroup).
 
 The fused forward is held to BIT equality with the launch sequence of the same handle (fused = 0): every generic float32 kernel
-computes an element in an order that does not depend on the thread that computes it, and the fused kernel restates those orders.
+computes an element in an order that does not depend on the thread that computes it, and the fused kernel calls the definitions of those orders that the kernels call.
 
   1. the reference's toy fixture at the bound of test_toy_fp32_matches_the_reference_output;
   2. bits against the launch sequence and 1e-5 against the fp64 oracle at every eligible shape of tests/test_tf_fused_host.py

@@ -149,7 +149,7 @@ def test_grid_and_lds_of_the_four_launches(plan):
 
 def test_kernel_id_is_tf_attn_pick_at_the_longest_sequence(plan):
     """The harness's tf_varlen_pick hands the longest length to tf_attn_pick and nothing else, so this pins the rule's table (as
-    tests/test_tf_attn_plan_host.py does) at the lengths a ragged batch presents; it cannot notice launch_attention_varlen choosing by
+    tests/test_tf_attn_plan_host.py does) at the lengths a ragged batch presents; it cannot notice launch_attention choosing by
     something other than the maximum.  That is check (a) of tests/test_gpu_tf_varlen.py: the id the device call returns for a batch
     of mixed lengths against this function at max(lengths)."""
     seen = set()
