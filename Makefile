@@ -13,12 +13,13 @@ HARNESS_TF_F32M := tests/host_harness/libflope_host_tf_f32m.so
 HARNESS_TF_ATTN := tests/host_harness/libflope_host_tf_attn.so
 HARNESS_TF_VARLEN := tests/host_harness/libflope_host_tf_varlen.so
 HARNESS_TF_FUSED := tests/host_harness/libflope_host_tf_fused.so
+HARNESS_TF_CAUSAL := tests/host_harness/libflope_host_tf_causal.so
 SRCS     := $(wildcard $(CSRC)/*.hip)
 OBJS     := $(patsubst $(CSRC)/%.hip,$(OBJDIR)/%.o,$(SRCS))
 HDRS     := $(wildcard $(CSRC)/*.h) include/flope_amd.h
 HIPFLAGS := --offload-arch=$(ARCH) -O3 -fPIC -std=c++17 -Wno-unused-value -Iinclude
 
-all: $(LIB) $(HARNESS) $(HARNESS_F32M) $(HARNESS_F32M_KSPLIT) $(HARNESS_GUARD) $(HARNESS_TF_F32M) $(HARNESS_TF_ATTN) $(HARNESS_TF_VARLEN) $(HARNESS_TF_FUSED)
+all: $(LIB) $(HARNESS) $(HARNESS_F32M) $(HARNESS_F32M_KSPLIT) $(HARNESS_GUARD) $(HARNESS_TF_F32M) $(HARNESS_TF_ATTN) $(HARNESS_TF_VARLEN) $(HARNESS_TF_FUSED) $(HARNESS_TF_CAUSAL)
 
 $(OBJDIR)/%.o: $(CSRC)/%.hip $(HDRS)
 	@mkdir -p $(OBJDIR)
@@ -59,6 +60,11 @@ $(HARNESS_TF_VARLEN): tests/host_harness/harness_tf_varlen.cpp $(CSRC)/tf_attn_p
 $(HARNESS_TF_FUSED): tests/host_harness/harness_tf_fused.cpp $(CSRC)/tf_fused_plan.h include/flope_amd.h
 	g++ -O2 -fPIC -shared -std=c++17 -I$(CSRC) -o $@ $<
 
+# how far causal attention walks the keys: the planner's constexpr functions the four attention kernels call
+# (tests/test_tf_causal_host.py, tests/test_gpu_tf_causal.py)
+$(HARNESS_TF_CAUSAL): tests/host_harness/harness_tf_causal.cpp $(CSRC)/tf_attn_plan.h include/flope_amd.h
+	g++ -O2 -fPIC -shared -std=c++17 -I$(CSRC) -o $@ $<
+
 # conditioning figure and flag predicate of the guarded mode (tests/test_guard_host.py)
 $(HARNESS_GUARD): tests/host_harness/harness_guard.cpp $(CSRC)/pose_math.h
 	g++ -O2 -fPIC -shared -std=c++17 -I$(CSRC) -o $@ $<
@@ -84,7 +90,7 @@ dbg: $(DBGOBJS)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $(DBGDIR)/libflope_amd_dbg.so $(DBGOBJS)
 
 clean:
-	rm -rf build $(LIB) $(HARNESS) $(HARNESS_F32M) $(HARNESS_F32M_KSPLIT) $(HARNESS_GUARD) $(HARNESS_TF_F32M) $(HARNESS_TF_ATTN) $(HARNESS_TF_VARLEN) $(HARNESS_TF_FUSED)
+	rm -rf build $(LIB) $(HARNESS) $(HARNESS_F32M) $(HARNESS_F32M_KSPLIT) $(HARNESS_GUARD) $(HARNESS_TF_F32M) $(HARNESS_TF_ATTN) $(HARNESS_TF_VARLEN) $(HARNESS_TF_FUSED) $(HARNESS_TF_CAUSAL)
 
 # stand-alone measurement programs used by tools/collect_profiles.sh and DESIGN.md section 9 (not part of the library)
 TOOLBINS := build/fetch_calib build/launch_floor build/loop_probe build/loop_probe32 build/dma_issue_probe

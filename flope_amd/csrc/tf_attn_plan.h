@@ -56,6 +56,21 @@ inline int tf_attn_pick(int dtype, int head_dim, int seq_len, int opt_generic, i
   return pick;
 }
 
+// ---- causal attention (option "causal") ------------------------------------------------------------------------------
+// Query i attends to keys j <= i of its own sequence of L tokens.  Kernel choice, grid, block and LDS above and below do not depend on
+// the option; what depends on it is how far a query group walks the keys.  The kernels call these, and so does
+// tests/host_harness/harness_tf_causal.cpp (tests/test_tf_causal_host.py holds them against brute force).
+// Keys visible to the group of nq queries that starts at query q_first: keys 0 .. min(L, q_first + nq) - 1
+constexpr int tf_causal_keys(int q_first, int nq, int L) { return q_first + nq < L ? q_first + nq : L; }
+// tf_attn_tiled: 64-key blocks the workgroup of query block qblock walks (every wave of it: one trip count, one barrier count)
+constexpr int tf_causal_tiled_blocks(int qblock, int L) {
+  return (tf_causal_keys(qblock * kTfAttnTiledQueries, kTfAttnTiledQueries, L) + kTfAttnTiledKB - 1) / kTfAttnTiledKB;
+}
+// tf_attn_tiled / tf_attn_mfma: whether the wave whose 32 queries start at q0 takes the 32-key step that starts at key kb
+constexpr bool tf_causal_step_taken(int q0, int kb) { return kb <= q0 + 31; }
+// tf_attn_f32m: 16-key tiles the workgroup of queries q0 .. q0 + 15 walks in its score and value passes
+constexpr int tf_causal_f32m_tiles(int q0, int L) { return (tf_causal_keys(q0, 16, L) + 15) / 16; }
+
 // ---- ragged batches (flope_tf_forward_varlen / flope_tf_attention_varlen) ------------------------------------------
 // A batch of B sequences of lengths[b] tokens (1 <= lengths[b] <= L) lives in the handle as T = sum lengths packed rows;
 // sequence b starts at packed row off[b], off[B] = T.

@@ -13,6 +13,8 @@
 //                         everything else (embedding, out_layer, odd shapes) falls to the generic kernels.
 // Bias, residual add and ReLU live in the linear kernels' epilogues; LayerNorm is one wave per token row.
 // FLOPE_DT_F32 with option fused = 1: a forward whose longest sequence fits 64 KiB of LDS is ONE launch (tf_fused_f32), same bits.
+// Option causal = 1 (any dtype): query i attends to keys j <= i of its own sequence -- the CAUSAL instantiation of whichever attention
+// kernel the shape picks, and of tf_fused_f32; key blocks above the diagonal are skipped, not loaded and masked.
 #include "../../include/flope_amd.h"
 #include "common.h"
 #include "host_pack.h"
@@ -113,8 +115,11 @@ __device__ __forceinline__ void tf_layernorm_row(const T* x, T* y, const float* 
 
 // softmax(q k^T / sqrt(dh)) v for query i of one head on one wave.  base: the head's q columns of the sequence's first row, rows of
 // ld elements (q | k | v at 0, d, 2 d); s: this wave's score row (L floats of LDS); orow: the dh outputs of the query.
-template <typename T>
+// CAUSAL (all four attention kernels): query i attends to keys j <= i of its own sequence.  Here the three key loops end
+// at i + 1 instead of L: the keys above the diagonal are never loaded.
+template <typename T, bool CAUSAL = false>
 __device__ __forceinline__ void tf_attn_row(const T* base, size_t ld, T* orow, float* s, int i, int L, int d, int dh, float scale, int lane) {
+  if constexpr (CAUSAL) L = flope_tf_plan::tf_causal_keys(i, 1, L);      // kend = i + 1
   const T* q = base + (size_t)i * ld;
   float mx = -INFINITY;
   for (int j = lane; j < L; j += 64) {
@@ -300,7 +305,7 @@ __global__ void tf_layernorm_vec(const T* in, T* out, const float* w, const floa
 // off[b] .. off[b + 1] - 1 and the L argument is the longest length, which sized the grid and the LDS; the kernel takes its own
 // sequence's length for L, so every bound, mask and clamp below stays inside the sequence (row off[b] + L is the next sequence's
 // first key, not padding).  The fixed-length instantiations (VARLEN = false, off unused) compile from the source they had.
-template <typename T, bool VARLEN = false>
+template <typename T, bool VARLEN = false, bool CAUSAL = false>
 __global__ void tf_attn_generic(const T* qkv, T* out, int L, int d, int H, const int* __restrict__ off) {
   extern __shared__ float sc[];                 // [waves][L]
   const int nw = blockDim.x >> 6, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -311,7 +316,7 @@ __global__ void tf_attn_generic(const T* qkv, T* out, int L, int d, int H, const
   float* s = sc + (size_t)wave * L;
   const T* base = VARLEN ? qkv + row0 * 3 * d + h * dh : qkv + (size_t)b * L * 3 * d + h * dh;
   for (int i = blockIdx.y * nw + wave; i < L; i += gridDim.y * nw)
-    tf_attn_row<T>(base, (size_t)3 * d, out + ((VARLEN ? row0 : (size_t)b * L) + i) * d + h * dh, s, i, L, d, dh, scale, lane);
+    tf_attn_row<T, CAUSAL>(base, (size_t)3 * d, out + ((VARLEN ? row0 : (size_t)b * L) + i) * d + h * dh, s, i, L, d, dh, scale, lane);
 }
 
 // ---- MFMA linear: Y[128-token tile][128-feature tile], K walked in 64-wide chunks ----------------------------
@@ -494,8 +499,11 @@ template <int HD32> __device__ __forceinline__ TfAttn16Lane tf_attn16_lane(int l
 
 // One 32-key step of a wave.  Ki, Vi: the K and V images; kl: the step's first row in them (a multiple of 32), kb: the key that row
 // holds; qf: the wave's Q fragments; mrun, lrun, o: running maximum, running sum and unnormalised output of its 2 x 16 queries.
-template <typename T, int HD32>
-__device__ __forceinline__ void tf_attn16_step(const char* Ki, const char* Vi, int kb, int kl, int L, float scale_log2e,
+// CAUSAL: q0 is the wave's first query and a key also has to be <= the lane's own query q0 + qt * 16 + li, unclamped (a query past L
+// is never stored).  A wave starts at step 0, which holds key 0 <= every query: the running maximum is finite before any step that
+// is masked for a query tile as a whole, as above.  Which steps a wave takes is its kernel's business (tf_causal_step_taken).
+template <typename T, int HD32, bool CAUSAL = false>
+__device__ __forceinline__ void tf_attn16_step(const char* Ki, const char* Vi, int kb, int kl, int L, int q0, float scale_log2e,
                                                const TfAttn16Lane& ln, const typename Elem<T>::frag (&qf)[2][HD32], float (&mrun)[2],
                                                float (&lrun)[2], f32x4 (&o)[2][2 * HD32]) {
   typedef typename Elem<T>::frag frag;
@@ -524,7 +532,9 @@ __device__ __forceinline__ void tf_attn16_step(const char* Ki, const char* Vi, i
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
         const int key = kb + u * 16 + g * 4 + q;
-        const float x = key < L ? s[u][qt][q] * scale_log2e : -INFINITY;
+        bool seen = key < L;
+        if constexpr (CAUSAL) seen = seen && key <= q0 + qt * 16 + li;
+        const float x = seen ? s[u][qt][q] * scale_log2e : -INFINITY;
         v[u * 4 + q] = x;
         mx = fmaxf(mx, x);
       }
@@ -587,7 +597,9 @@ __device__ __forceinline__ void tf_attn16_store(T* out, size_t row0, int d, int 
 // VARLEN: launched with pad32(longest) / 32 waves and that much LDS; L and Lp become the sequence's own (the V image starts behind
 // its own K image), a wave whose 32 queries lie past the sequence leaves behind the one __syncthreads (a whole wave: EXEC of the
 // others stays all ones for the transposed reads).
-template <typename T, bool VARLEN = false>
+// CAUSAL: staging and the one __syncthreads as they are; a wave's step loop ends behind the step that holds its last query (the
+// bound is the wave's: EXEC stays all ones).
+template <typename T, bool VARLEN = false, bool CAUSAL = false>
 __global__ __launch_bounds__(1024) void tf_attn_mfma(const T* __restrict__ qkv, T* __restrict__ out, int L, int d,
                                                      int H, int Lp, float scale_log2e, const int* __restrict__ off) {
   typedef typename Elem<T>::frag frag;
@@ -630,7 +642,8 @@ __global__ __launch_bounds__(1024) void tf_attn_mfma(const T* __restrict__ qkv, 
     for (int dt = 0; dt < 4; ++dt) o[qt][dt] = f32x4{0.f, 0.f, 0.f, 0.f};
 
   const TfAttn16Lane ln = tf_attn16_lane<2>(lane);
-  for (int kb = 0; kb < Lp; kb += 32) tf_attn16_step<T, 2>(Ki + kb * 128, Vi + kb * 128, kb, 0, L, scale_log2e, ln, qf, mrun, lrun, o);
+  if constexpr (CAUSAL) Lp = flope_tf_plan::tf_causal_keys(q0, 32, Lp);      // min(Lp, q0 + 32): a multiple of 32
+  for (int kb = 0; kb < Lp; kb += 32) tf_attn16_step<T, 2, CAUSAL>(Ki + kb * 128, Vi + kb * 128, kb, 0, L, q0, scale_log2e, ln, qf, mrun, lrun, o);
   // tf_attn16_store's body, kept as a copy: through the call this kernel allocates 98 VGPRs instead of 96 (5 -> 4 waves per SIMD).
   // Change the expressions here and there together (test_head_dim_64_gives_the_bits_of_the_resident_kernel holds them to equal bits).
 #pragma unroll
@@ -664,7 +677,10 @@ __global__ __launch_bounds__(1024) void tf_attn_mfma(const T* __restrict__ qkv, 
 // VARLEN: grid.y counts the query blocks of the longest sequence; a workgroup whose first query lies at or past its own sequence's
 // length leaves before its first load and barrier (all four waves: the condition is per workgroup), one with some valid queries
 // keeps all four waves in the barrier loop as above; nb, the step skip and the masks use the sequence's own L.
-template <typename T, int HD32, bool VARLEN = false>
+// CAUSAL: the barrier loop runs the WORKGROUP's block count, the 64-key blocks up to its last query (tf_causal_tiled_blocks: all
+// four waves keep the same trips, loads, LDS writes and barriers); inside it a wave skips the 32-key steps that lie wholly above
+// its own last query (tf_causal_step_taken), by the same uniform `continue` as the steps past L.
+template <typename T, int HD32, bool VARLEN = false, bool CAUSAL = false>
 __global__ __launch_bounds__(256, 2) void tf_attn_tiled(const T* __restrict__ qkv, T* __restrict__ out, int L, int d, int H,
                                                         float scale_log2e, const int* __restrict__ off) {
   typedef typename Elem<T>::frag frag;
@@ -680,7 +696,7 @@ __global__ __launch_bounds__(256, 2) void tf_attn_tiled(const T* __restrict__ qk
     if ((int)blockIdx.y * flope_tf_plan::kTfAttnTiledQueries >= L) return;
   }
   const T* base = VARLEN ? qkv + row0 * 3 * d + h * HD : qkv + (size_t)b * L * 3 * d + h * HD;
-  const int nb = (L + KB - 1) / KB;
+  const int nb = CAUSAL ? flope_tf_plan::tf_causal_tiled_blocks((int)blockIdx.y, L) : (L + KB - 1) / KB;
 
   // staging role: HD32 chunks of K and of V per thread and block
   int srow[HD32], ssrc[HD32], sdk[HD32], sdv[HD32];
@@ -742,7 +758,8 @@ __global__ __launch_bounds__(256, 2) void tf_attn_tiled(const T* __restrict__ qk
     for (int st = 0; st < KB / 32; ++st) {
       const int kl = st * 32, kb = t * KB + kl;
       if (kb >= L) continue;                     // uniform: EXEC stays all ones
-      tf_attn16_step<T, HD32>(Ki, Vi, kb, kl, L, scale_log2e, ln, qf, mrun, lrun, o);
+      if constexpr (CAUSAL) { if (!flope_tf_plan::tf_causal_step_taken(q0, kb)) continue; }     // per wave, uniform
+      tf_attn16_step<T, HD32, CAUSAL>(Ki, Vi, kb, kl, L, q0, scale_log2e, ln, qf, mrun, lrun, o);
     }
     lwrite((t + 1) & 1);
   }
@@ -874,7 +891,10 @@ __global__ __launch_bounds__(256) void tf_linear_f32m(const float* __restrict__ 
 using flope_tf_plan::kTfAttnLds;
 // VARLEN: grid.y and the LDS are those of the longest sequence; a workgroup whose 16 queries lie past its own sequence leaves before
 // the first barrier; Lp, the score pitch and the place of the partial sums behind the scores follow the sequence's own L.
-template <int NT, bool VARLEN = false>
+// CAUSAL: a score also needs key <= its query; the score and value passes stop at the key tile that holds the workgroup's last query
+// (tf_causal_f32m_tiles; which wave takes a key stays a function of the key alone), the softmax of query q runs over
+// min(L, q + 1) keys and zeroes the rest of those tiles, as it does for keys past L.
+template <int NT, bool VARLEN = false, bool CAUSAL = false>
 __global__ __launch_bounds__(256) void tf_attn_f32m(const float* __restrict__ qkv, float* __restrict__ out, int L, int d, int H, float scale,
                                                     const int* __restrict__ off) {
   extern __shared__ __attribute__((aligned(16))) float Sm[];      // [16][pitch] scores / probabilities | [3][NT][64][4] partial outputs
@@ -889,6 +909,7 @@ __global__ __launch_bounds__(256) void tf_attn_f32m(const float* __restrict__ qk
   const int Lp = (L + 15) & ~15, pitch = Lp + 4, ld = 3 * d;
   const float* const base = VARLEN ? qkv + row0 * ld + h * dh : qkv + (size_t)b * L * ld + h * dh;
   float* const red = Sm + 16 * pitch;
+  const int Lw = CAUSAL ? flope_tf_plan::tf_causal_f32m_tiles(q0, L) * 16 : Lp;       // the keys this workgroup walks, whole tiles
   // 1. scores
   {
     f32x4 qf[NT];
@@ -901,7 +922,7 @@ __global__ __launch_bounds__(256) void tf_attn_f32m(const float* __restrict__ qk
       const f32x4 v = *(const f32x4*)(qp + dimc[st]);
       qf[st] = dim < dh ? v : f32x4{0.f, 0.f, 0.f, 0.f};
     }
-    const int ntile = Lp >> 4;
+    const int ntile = Lw >> 4;
     for (int kt = wave; kt < ntile; kt += 8) {
       const int kt1 = kt + 4;
       const float* kp0 = base + (size_t)min(kt * 16 + c16, L - 1) * ld + d;
@@ -918,13 +939,14 @@ __global__ __launch_bounds__(256) void tf_attn_f32m(const float* __restrict__ qk
           d1 = __builtin_amdgcn_mfma_f32_16x16x4f32(k1[st][s], qf[st][s], d1, 0, 0, 0);
         }
       // lane (kq, c16): keys tile * 16 + 4 kq + r of query c16
+      auto seen = [&](int key) { return CAUSAL ? key < L && key <= q0 + c16 : key < L; };
       f32x4 o;
 #pragma unroll
-      for (int r = 0; r < 4; ++r) o[r] = kt * 16 + 4 * kq + r < L ? d0[r] * scale : -3.0e38f;
+      for (int r = 0; r < 4; ++r) o[r] = seen(kt * 16 + 4 * kq + r) ? d0[r] * scale : -3.0e38f;
       *(f32x4*)(Sm + c16 * pitch + kt * 16 + 4 * kq) = o;
       if (kt1 < ntile) {
 #pragma unroll
-        for (int r = 0; r < 4; ++r) o[r] = kt1 * 16 + 4 * kq + r < L ? d1[r] * scale : -3.0e38f;
+        for (int r = 0; r < 4; ++r) o[r] = seen(kt1 * 16 + 4 * kq + r) ? d1[r] * scale : -3.0e38f;
         *(f32x4*)(Sm + c16 * pitch + kt1 * 16 + 4 * kq) = o;
       }
     }
@@ -934,16 +956,17 @@ __global__ __launch_bounds__(256) void tf_attn_f32m(const float* __restrict__ qk
   {
     const int kl = tid & 15;
     float* Sq = Sm + (tid >> 4) * pitch;
+    const int Lq = CAUSAL ? flope_tf_plan::tf_causal_keys(q0 + (tid >> 4), 1, L) : L;      // this query's keys: min(L, q + 1)
     float mx = -3.0e38f;
-    for (int j = kl; j < L; j += 16) mx = fmaxf(mx, Sq[j]);
+    for (int j = kl; j < Lq; j += 16) mx = fmaxf(mx, Sq[j]);
 #pragma unroll
     for (int o = 8; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 16));
     float l = 0.f;
-    for (int j = kl; j < L; j += 16) { const float e = expf(Sq[j] - mx); Sq[j] = e; l += e; }
+    for (int j = kl; j < Lq; j += 16) { const float e = expf(Sq[j] - mx); Sq[j] = e; l += e; }
 #pragma unroll
     for (int o = 8; o > 0; o >>= 1) l += __shfl_xor(l, o, 16);
     const float inv = 1.f / l;
-    for (int j = kl; j < Lp; j += 16) Sq[j] = j < L ? Sq[j] * inv : 0.f;
+    for (int j = kl; j < Lw; j += 16) Sq[j] = j < Lq ? Sq[j] * inv : 0.f;
   }
   __syncthreads();
   // 3. values: group g covers keys 4 g .. 4 g + 3; lane (kq, c16): A = V[4 g + kq][ct * 16 + c16], B = P[query c16][4 g + kq]
@@ -951,7 +974,7 @@ __global__ __launch_bounds__(256) void tf_attn_f32m(const float* __restrict__ qk
   int dimv[NT];
 #pragma unroll
   for (int ct = 0; ct < NT; ++ct) { acc[ct] = f32x4{0.f, 0.f, 0.f, 0.f}; dimv[ct] = min(ct * 16 + c16, dh - 1); }
-  const int ng = Lp >> 2;
+  const int ng = Lw >> 2;
   const float* const vb = base + 2 * d;
   for (int g0 = wave; g0 < ng; g0 += 16) {                 // four groups of this wave per trip
     float av[4][NT], bv[4];
@@ -1022,18 +1045,20 @@ __device__ __forceinline__ void tf_fz_layernorm(const float* in, float* out, con
 }
 
 // qkv rows of qld floats (q | k | v in the first 3 d), s: this wave's score row
+template <bool CAUSAL>
 __device__ __forceinline__ void tf_fz_attention(const float* qkv, int qld, float* att, float* s, int L, int d, int H) {
   const int dh = d / H;
   const float scale = 1.f / sqrtf((float)dh);
   for (int it = threadIdx.x >> 6; it < H * L; it += 4) {
     const int h = it / L, i = it - h * L;
-    tf_attn_row<float>(qkv + h * dh, (size_t)qld, att + i * d + h * dh, s, i, L, d, dh, scale, threadIdx.x & 63);
+    tf_attn_row<float, CAUSAL>(qkv + h * dh, (size_t)qld, att + i * d + h * dh, s, i, L, d, dh, scale, threadIdx.x & 63);
   }
 }
 
 // grid = batch, block = 256, dynamic LDS = lay.total (the layout of the longest sequence of the call).  x [batch][L][in_dim] ->
 // y [batch][L][out_dim]; off == nullptr: every sequence has L tokens; otherwise sequence b has off[b + 1] - off[b] <= the layout's L
-// tokens, rows behind it are not read and come back as out_layer.bias.
+// tokens, rows behind it are not read and come back as out_layer.bias.  CAUSAL: the attention phase calls tf_attn_row's causal form.
+template <bool CAUSAL = false>
 __global__ __launch_bounds__(256) void tf_fused_f32(const float* __restrict__ x, float* __restrict__ y, const int* __restrict__ off,
                                                     const float* const* __restrict__ tab, const flope_tf_plan::TfFusedLayout lay, int L,
                                                     int in_dim, int d, int out_dim, int H, int nl, int ff) {
@@ -1058,7 +1083,7 @@ __global__ __launch_bounds__(256) void tf_fused_f32(const float* __restrict__ x,
     const float* const* t = tab + kTfFusedTabHead + l * kTfFusedTabLayer;
     tf_fz_linear(h, d, t[0], t[1], nullptr, 0, qkv, qld, len, d, 3 * d, 0);
     __syncthreads();
-    tf_fz_attention(qkv, qld, att, sc, len, d, H);
+    tf_fz_attention<CAUSAL>(qkv, qld, att, sc, len, d, H);
     __syncthreads();
     tf_fz_linear(att, d, t[2], t[3], h, d, h2, d, len, d, d, 0);
     __syncthreads();
@@ -1094,6 +1119,7 @@ struct flope_tf_encoder {
   int opt_f32m = 0;                          // 1: FLOPE_DT_F32 linears and attention on v_mfma_f32_16x16x4_f32 where eligible (stored and ignored by 16-bit handles)
   int opt_tiled = 0;                         // 16-bit handles: 1 = tf_attn_tiled where the choice would be tf_attn_generic, 2 = also in place of tf_attn_mfma (stored and ignored by float32 handles)
   int opt_fused = 0;                         // 1: a float32 forward that tf_fused_ok takes runs as one launch of tf_fused_f32 (stored and ignored by 16-bit handles and while opt_f32m)
+  int opt_causal = 0;                        // 1: query i attends to keys j <= i of its own sequence, in every attention launch and in tf_fused_f32
   int last_fwd = FLOPE_TF_FWD_LAUNCHES;       // what the last forward that enqueued anything ran (flope_tf_last_forward)
   const float** fused_tab = nullptr;         // device table of the float32 weight arrays tf_fused_f32 reads (FLOPE_DT_F32 handles, built by flope_tf_load_weights)
   int opt_f32m_lds = 0;                      // KiB of untouched LDS a tf_linear_f32m launch reserves (> 80: one workgroup per CU)
@@ -1241,7 +1267,7 @@ int launch_layernorm(flope_tf_encoder* e, const void* in, void* out, const float
 
 // One attention launch: softmax(q k^T / sqrt(head_dim)) v per head.  off == nullptr: qkv [B][L][3 d] -> att [B][L][d].  Otherwise a
 // ragged batch: packed qkv [T][3 d] -> att [T][d], sequence b = rows off[b] .. off[b + 1] - 1 (off: the handle's device table), L its
-// longest length, the VARLEN instantiations.  One kernel for the whole batch, the one tf_attn_plan.h picks for L; grid, block and LDS
+// longest length, the VARLEN instantiations.  Option causal: the CAUSAL instantiations of the same pick.  One kernel for the whole batch, the one tf_attn_plan.h picks for L; grid, block and LDS
 // from tf_attn_varlen_launch in both cases.  Returns the kernel's FLOPE_TF_ATTN_* id, or < 0.
 template <typename T>
 int launch_attention(flope_tf_encoder* e, const void* qkv, void* att, int B, int L, const int* off, hipStream_t st) {
@@ -1250,15 +1276,15 @@ int launch_attention(flope_tf_encoder* e, const void* qkv, void* att, int B, int
   const int pick = tf_attn_pick(e->dtype, dh, L, e->opt_generic, e->opt_f32m, e->opt_tiled, !(((uintptr_t)qkv | (uintptr_t)att) & 15));
   const TfAttnLaunch l = tf_attn_varlen_launch(pick, dh, B, H, L);
   const dim3 grid(l.grid_x, l.grid_y), block(l.block);
-  auto launch = [&](auto varlen) {
-    constexpr bool VL = decltype(varlen)::value;
+  auto launch = [&](auto varlen, auto causal) {
+    constexpr bool VL = decltype(varlen)::value, CA = decltype(causal)::value;
     if constexpr (!std::is_same<T, float>::value) {
       if (pick == FLOPE_TF_ATTN_MFMA64) {
-        hipLaunchKernelGGL((tf_attn_mfma<T, VL>), grid, block, l.lds, st, (const T*)qkv, (T*)att, L, d, H, tf_attn_pad32(L),
+        hipLaunchKernelGGL((tf_attn_mfma<T, VL, CA>), grid, block, l.lds, st, (const T*)qkv, (T*)att, L, d, H, tf_attn_pad32(L),
                            1.4426950408889634f / sqrtf(64.f), off);
       } else if (pick == FLOPE_TF_ATTN_TILED) {
         const float scale_log2e = 1.4426950408889634f / sqrtf((float)dh);
-#define TF_ATT(HD32_) hipLaunchKernelGGL((tf_attn_tiled<T, HD32_, VL>), grid, block, l.lds, st, (const T*)qkv, (T*)att, L, d, H, scale_log2e, off)
+#define TF_ATT(HD32_) hipLaunchKernelGGL((tf_attn_tiled<T, HD32_, VL, CA>), grid, block, l.lds, st, (const T*)qkv, (T*)att, L, d, H, scale_log2e, off)
         if (dh == 32) TF_ATT(1); else if (dh == 64) TF_ATT(2); else if (dh == 96) TF_ATT(3); else TF_ATT(4);
 #undef TF_ATT
       }
@@ -1267,15 +1293,17 @@ int launch_attention(flope_tf_encoder* e, const void* qkv, void* att, int B, int
       if (pick == FLOPE_TF_ATTN_F32M) {
         const int nt = tf_attn_f32m_nt(dh);
         const float scale = 1.f / sqrtf((float)dh);
-#define TF_ATT(NT_) hipLaunchKernelGGL((tf_attn_f32m<NT_, VL>), grid, block, l.lds, st, (const float*)qkv, (float*)att, L, d, H, scale, off)
+#define TF_ATT(NT_) hipLaunchKernelGGL((tf_attn_f32m<NT_, VL, CA>), grid, block, l.lds, st, (const float*)qkv, (float*)att, L, d, H, scale, off)
         if (nt == 1) TF_ATT(1); else if (nt == 2) TF_ATT(2); else if (nt == 4) TF_ATT(4); else TF_ATT(8);
 #undef TF_ATT
       }
     }
     if (pick == FLOPE_TF_ATTN_GENERIC)
-      hipLaunchKernelGGL((tf_attn_generic<T, VL>), grid, block, l.lds, st, (const T*)qkv, (T*)att, L, d, H, off);
+      hipLaunchKernelGGL((tf_attn_generic<T, VL, CA>), grid, block, l.lds, st, (const T*)qkv, (T*)att, L, d, H, off);
   };
-  if (off) launch(std::true_type{}); else launch(std::false_type{});
+  if (e->opt_causal) {                           // kernel, grid, block and LDS are those of the option at 0
+    if (off) launch(std::true_type{}, std::true_type{}); else launch(std::false_type{}, std::true_type{});
+  } else if (off) launch(std::true_type{}, std::false_type{}); else launch(std::false_type{}, std::false_type{});
   TF_HIP(e, hipGetLastError());
   return pick;
 }
@@ -1353,8 +1381,10 @@ bool tf_fused_pick(const flope_tf_encoder* e, int Lmax) {
 // otherwise the handle's device offset table of a ragged batch whose longest sequence has Lmax <= L tokens.
 int launch_fused(flope_tf_encoder* e, const float* x, int B, int L, int Lmax, const int* off, float* y, hipStream_t st) {
   const flope_tf_plan::TfFusedLayout lay = flope_tf_plan::tf_fused_layout(e->in_dim, e->d, e->ff, Lmax);
-  hipLaunchKernelGGL(tf_fused_f32, dim3((unsigned)B), dim3(256), (size_t)lay.total, st, x, y, off, (const float* const*)e->fused_tab, lay, L, e->in_dim,
-                     e->d, e->out_dim, e->H, e->nl, e->ff);
+#define TF_FZ(CA_) hipLaunchKernelGGL((tf_fused_f32<CA_>), dim3((unsigned)B), dim3(256), (size_t)lay.total, st, x, y, off, (const float* const*)e->fused_tab, lay, L, \
+                                      e->in_dim, e->d, e->out_dim, e->H, e->nl, e->ff)
+  if (e->opt_causal) TF_FZ(true); else TF_FZ(false);
+#undef TF_FZ
   TF_HIP(e, hipGetLastError());
   return 0;
 }
@@ -1447,6 +1477,10 @@ extern "C" int flope_tf_create(int device_id, int input_dim, int model_dim, int 
     hipFuncSetAttribute((const void*)tf_attn_mfma<bf16_t>, hipFuncAttributeMaxDynamicSharedMemorySize, 131072);
     hipFuncSetAttribute((const void*)tf_attn_mfma<f16_t, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 131072);
     hipFuncSetAttribute((const void*)tf_attn_mfma<bf16_t, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 131072);
+    hipFuncSetAttribute((const void*)tf_attn_mfma<f16_t, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 131072);
+    hipFuncSetAttribute((const void*)tf_attn_mfma<bf16_t, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 131072);
+    hipFuncSetAttribute((const void*)tf_attn_mfma<f16_t, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 131072);
+    hipFuncSetAttribute((const void*)tf_attn_mfma<bf16_t, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 131072);
 #define TF_ATTR(T_, A_, B_) hipFuncSetAttribute((const void*)tf_gemm_mfma<T_, A_, B_>, hipFuncAttributeMaxDynamicSharedMemorySize, 65536)
     TF_ATTR(f16_t, false, false); TF_ATTR(f16_t, false, true); TF_ATTR(f16_t, true, false); TF_ATTR(f16_t, true, true);
     TF_ATTR(bf16_t, false, false); TF_ATTR(bf16_t, false, true); TF_ATTR(bf16_t, true, false); TF_ATTR(bf16_t, true, true);
@@ -1455,13 +1489,18 @@ extern "C" int flope_tf_create(int device_id, int input_dim, int model_dim, int 
                                 (const void*)tf_linear_f32m<2, false, false>, (const void*)tf_linear_f32m<2, true, false>, (const void*)tf_linear_f32m<2, false, true>,
                                 (const void*)tf_linear_f32m<1, false, false>, (const void*)tf_linear_f32m<1, true, false>, (const void*)tf_linear_f32m<1, false, true>,
                                 (const void*)tf_attn_f32m<1>, (const void*)tf_attn_f32m<2>, (const void*)tf_attn_f32m<4>, (const void*)tf_attn_f32m<8>,
-                                (const void*)tf_attn_f32m<1, true>, (const void*)tf_attn_f32m<2, true>, (const void*)tf_attn_f32m<4, true>, (const void*)tf_attn_f32m<8, true>};
+                                (const void*)tf_attn_f32m<1, true>, (const void*)tf_attn_f32m<2, true>, (const void*)tf_attn_f32m<4, true>, (const void*)tf_attn_f32m<8, true>,
+                                (const void*)tf_attn_f32m<1, false, true>, (const void*)tf_attn_f32m<2, false, true>, (const void*)tf_attn_f32m<4, false, true>,
+                                (const void*)tf_attn_f32m<8, false, true>, (const void*)tf_attn_f32m<1, true, true>, (const void*)tf_attn_f32m<2, true, true>,
+                                (const void*)tf_attn_f32m<4, true, true>, (const void*)tf_attn_f32m<8, true, true>};
     for (const void* f : f32m)
       if (hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kTfAttnLds) != hipSuccess)
         return fin(tf_fail(nullptr, FLOPE_EHIP, "flope_tf_create: hipFuncSetAttribute failed"));
     // tf_attn_tiled: 16 / 32 / 48 / 64 KiB; the widest sits at the 64 KiB a launch gets without asking
     const void* const tiled[] = {(const void*)tf_attn_tiled<f16_t, 4>, (const void*)tf_attn_tiled<bf16_t, 4>,
-                                 (const void*)tf_attn_tiled<f16_t, 4, true>, (const void*)tf_attn_tiled<bf16_t, 4, true>};
+                                 (const void*)tf_attn_tiled<f16_t, 4, true>, (const void*)tf_attn_tiled<bf16_t, 4, true>,
+                                 (const void*)tf_attn_tiled<f16_t, 4, false, true>, (const void*)tf_attn_tiled<bf16_t, 4, false, true>,
+                                 (const void*)tf_attn_tiled<f16_t, 4, true, true>, (const void*)tf_attn_tiled<bf16_t, 4, true, true>};
     for (const void* f : tiled)
       if (hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)flope_tf_plan::tf_attn_tiled_lds(128)) != hipSuccess)
         return fin(tf_fail(nullptr, FLOPE_EHIP, "flope_tf_create: hipFuncSetAttribute failed"));
@@ -1490,6 +1529,10 @@ extern "C" int flope_tf_set_option(flope_tf_handle e, const char* name, int valu
   if (!strcmp(name, "fused")) {
     if (value < 0 || value > 1) return tf_fail(e, FLOPE_EINVAL, "flope_tf_set_option: fused is 0 or 1");
     const int old = e->opt_fused; e->opt_fused = value; return old;
+  }
+  if (!strcmp(name, "causal")) {
+    if (value < 0 || value > 1) return tf_fail(e, FLOPE_EINVAL, "flope_tf_set_option: causal is 0 or 1");
+    const int old = e->opt_causal; e->opt_causal = value; return old;
   }
   if (!strcmp(name, "f32mlds")) {
     if (value < 0 || value > 160) return tf_fail(e, FLOPE_EINVAL, "flope_tf_set_option: f32mlds is 0 .. 160 (KiB)");
@@ -1704,16 +1747,18 @@ extern "C" int flope_tf_attention_varlen(flope_tf_handle e, const void* qkv_dev,
   });
 }
 
-// algorithmic FLOPs of one forward (2*MAC: linears + QK^T + PV)
+// algorithmic FLOPs of one forward (2*MAC: linears + QK^T + PV); option causal: a query of a sequence of len tokens meets
+// (len + 1) / 2 keys on average, d len (len + 1) MACs per sequence and layer instead of 2 d len^2
 extern "C" double flope_tf_forward_flops(flope_tf_handle e, int batch, int seq_len) {
   if (!e) return 0.0;
   const double M = (double)batch * seq_len, d = e->d;
   double mac = M * e->in_dim * d + M * d * e->out_dim;
-  mac += e->nl * (M * d * 3 * d + M * d * d + 2.0 * M * d * e->ff + 2.0 * M * seq_len * d);
+  mac += e->nl * (M * d * 3 * d + M * d * d + 2.0 * M * d * e->ff + (e->opt_causal ? M * (seq_len + 1.0) * d : 2.0 * M * seq_len * d));
   return 2.0 * mac;
 }
 
-// algorithmic FLOPs of one ragged forward: the linears on T = sum lengths tokens, attention on sum lengths^2; 0 for an invalid batch
+// algorithmic FLOPs of one ragged forward: the linears on T = sum lengths tokens, attention on sum lengths^2 (option causal: on
+// sum lengths (lengths + 1) / 2); 0 for an invalid batch
 extern "C" double flope_tf_forward_flops_varlen(flope_tf_handle e, int batch, const int* lengths_host) {
   if (!e || batch < 1 || !lengths_host) return 0.0;
   double M = 0.0, sq = 0.0;
@@ -1724,7 +1769,7 @@ extern "C" double flope_tf_forward_flops_varlen(flope_tf_handle e, int batch, co
   }
   const double d = e->d;
   double mac = M * e->in_dim * d + M * d * e->out_dim;
-  mac += e->nl * (M * d * 3 * d + M * d * d + 2.0 * M * d * e->ff + 2.0 * sq * d);
+  mac += e->nl * (M * d * 3 * d + M * d * d + 2.0 * M * d * e->ff + (e->opt_causal ? (sq + M) * d : 2.0 * sq * d));
   return 2.0 * mac;
 }
 

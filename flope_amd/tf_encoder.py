@@ -3,6 +3,8 @@ C-ABI `flope_tf_*` (include/flope_amd.h).  Same constructor arguments, same stat
 call: `enc(x)` with x float32 [B, L, input_dim] on the GPU -> float32 [B, L, out_dim].  Right-padded
 ragged batches take `lengths=` (or torch's `src_key_padding_mask=`): each sequence is encoded alone at
 its own length, rows behind it come back as `out_layer.bias`, as from the reference module.
+Causal attention takes `is_causal=True` or torch's `mask=` holding the causal mask: position t sees positions <= t of its own
+sequence, so a track is encoded once and every row is the answer the encoder gives when the track ends there.
 
 Eval-mode semantics only (dropout is identity), as everywhere in this package.  There is no CPU
 path: construction fails loudly without a HIP device or without the built library.
@@ -53,6 +55,32 @@ def _mask_to_lengths(mask, B, L):
     if wrong:
         raise ValueError(f"src_key_padding_mask row {wrong[0]}: the valid entries must form a non-empty prefix of the row (right padding)")
     return lengths.tolist()
+
+
+def _mask_is_causal(mask, L):
+    """torch's `mask` of nn.TransformerEncoder.forward -> True (the causal mask) or False (no mask).  Accepted: None; an all-False bool
+    or all-zero floating [L, L] (no mask); the causal [L, L] mask, bool with True exactly above the diagonal or floating with -inf
+    exactly above the diagonal and 0 elsewhere (generate_square_subsequent_mask).  Anything else has no kernel and raises ValueError
+    naming the first offending (row, col).  Checked on the host: a device mask is copied there."""
+    if mask is None:
+        return False
+    mask = torch.as_tensor(mask)
+    if tuple(mask.shape) != (L, L) or not (mask.dtype == torch.bool or mask.dtype.is_floating_point):
+        raise ValueError(f"mask must be a bool or floating tensor {(L, L)}, got {mask.dtype} {tuple(mask.shape)}")
+    m = mask.detach().cpu()
+    above = torch.ones(L, L, dtype=torch.bool).triu(1)
+    if m.dtype == torch.bool:
+        clear, causal = ~m, m == above
+    else:
+        m = m.double()
+        clear, causal = m == 0, torch.where(above, m == float("-inf"), m == 0)
+    if bool(clear.all()):
+        return False
+    if bool(causal.all()):
+        return True
+    r, c = (int(v) for v in (~causal).nonzero()[0])
+    raise ValueError(f"mask[{r}, {c}] = {mask[r, c].item()!r} is not the causal mask's entry ({'masked' if c > r else 'clear'}): only the "
+                     "causal mask (masked exactly above the diagonal) or an all-clear mask has a kernel")
 
 
 class TransformerEncoder:
@@ -126,14 +154,23 @@ class TransformerEncoder:
     def set_option(self, name: str, value: int) -> int:
         return self.lib.flope_tf_set_option(self.handle, name.encode(), int(value))
 
-    def flops(self, batch: int, seq_len: int, lengths=None) -> float:
+    def _state_causal(self, causal):
+        """Every call that runs or counts attention states the option first, so a plain call after a causal one is non-causal"""
+        rc = self.lib.flope_tf_set_option(self.handle, b"causal", int(bool(causal)))
+        if rc < 0:
+            raise RuntimeError(f"flope_tf_set_option(causal) failed ({rc})")
+
+    def flops(self, batch: int, seq_len: int, lengths=None, *, is_causal=False) -> float:
+        """Algorithmic FLOPs of one forward; `is_causal`: attention counted over the keys a causal forward meets."""
+        self._state_causal(is_causal)
         if lengths is None:
             return self.lib.flope_tf_forward_flops(self.handle, batch, seq_len)
         return self.lib.flope_tf_forward_flops_varlen(self.handle, batch, _host_lengths(lengths, batch))
 
-    def forward_plan(self, batch: int, seq_len: int, lengths=None) -> str:
-        """"fused" or "launches": what forward() of x [batch, seq_len, input_dim] (with these `lengths`) would run under the current
-        options.  Enqueues nothing; a shape the forward refuses raises ValueError."""
+    def forward_plan(self, batch: int, seq_len: int, lengths=None, *, is_causal=False) -> str:
+        """"fused" or "launches": what forward() of x [batch, seq_len, input_dim] (with these `lengths`, with `is_causal`) would run
+        under the current options.  Enqueues nothing; a shape the forward refuses raises ValueError."""
+        self._state_causal(is_causal)
         with torch.cuda.device(self.device):
             rc = self.lib.flope_tf_forward_plan(self.handle, int(batch), int(seq_len), None if lengths is None else _host_lengths(lengths, batch))
         self._check_arg(rc)
@@ -149,11 +186,18 @@ class TransformerEncoder:
             msg = msg.decode() if msg else ""
             raise (ValueError if rc == _lib.EINVAL else RuntimeError)(f"flope_amd error {rc}: {msg}")
 
-    def forward(self, x: torch.Tensor, lengths=None, src_key_padding_mask=None) -> torch.Tensor:
+    def forward(self, x: torch.Tensor, lengths=None, src_key_padding_mask=None, *, mask=None, is_causal=False) -> torch.Tensor:
         """x [B, L, input_dim] -> [B, L, out_dim].  `lengths`: a sequence or CPU integer tensor of B values, 1 <= lengths[b] <= L --
         sequence b is x[b, :lengths[b]], the rows behind it are padding (never read) and come back as out_layer.bias.
         `src_key_padding_mask`: bool [B, L], True = padding (torch's convention); it must mask a suffix of every row and is turned
-        into lengths on the host.  With neither, every sequence has length L (the fixed-length path, unchanged)."""
+        into lengths on the host.  With neither, every sequence has length L (the fixed-length path, unchanged).
+        `is_causal=True`, or `mask` = the [L, L] causal mask (torch's generate_square_subsequent_mask(L), or bool with True above the
+        diagonal): row t attends to rows <= t of its own sequence, so forward(x[:, :n], is_causal=True) is the first n rows of
+        forward(x, is_causal=True), bit for bit.  An all-clear `mask` means none; any other mask, or one that contradicts
+        `is_causal=True`, raises ValueError.  The mask is checked on the host: a device mask costs a copy, `is_causal=True` costs
+        nothing.  Two deliberate differences from torch: `is_causal=True` without a mask means causal here (torch ignores that hint
+        silently), and with `lengths` the rows behind a sequence still come back as out_layer.bias, never read (torch leaves its
+        nested-tensor path once a mask is given and computes something there)."""
         if not x.is_cuda or x.device != self.device:
             raise RuntimeError(f"input must live on {self.device} (got {x.device}); no CPU path")
         if x.dim() != 3 or x.shape[2] != self.dims[0]:
@@ -164,6 +208,10 @@ class TransformerEncoder:
         B, L = x.shape[0], x.shape[1]
         if src_key_padding_mask is not None:
             lengths = _mask_to_lengths(src_key_padding_mask, B, L)
+        causal = _mask_is_causal(mask, L)
+        if is_causal and mask is not None and not causal:
+            raise ValueError("is_causal=True with a mask that is not the causal mask")
+        self._state_causal(causal or is_causal)
         y = torch.empty((B, L, self.dims[2]), dtype=torch.float32, device=self.device)
         lh = None if lengths is None else _host_lengths(lengths, B)
         if lengths is None:
@@ -178,12 +226,14 @@ class TransformerEncoder:
 
     __call__ = forward
 
-    def attention(self, qkv: torch.Tensor, lengths=None, out: torch.Tensor = None) -> torch.Tensor:
+    def attention(self, qkv: torch.Tensor, lengths=None, out: torch.Tensor = None, *, is_causal=False) -> torch.Tensor:
         """softmax(q k^T / sqrt(head_dim)) v per head of qkv [B, L, 3 * model_dim] in the handle's dtype -> [B, L, model_dim], by
         the kernel a forward of this (B, L) would launch under the current options; its id is kept in `last_attn_kernel`.  Needs no
         weights.  `out`: a contiguous tensor of the result's shape and dtype to write into.
         With `lengths` (B values), qkv is the packed 2-D [T, 3 * model_dim] of a ragged batch, T = sum(lengths), sequence b at rows
-        sum(lengths[:b]) onwards; the result is the packed [T, model_dim]."""
+        sum(lengths[:b]) onwards; the result is the packed [T, model_dim].
+        `is_causal`: query i attends to keys <= i of its own sequence; the kernel is the one the shape picks without it."""
+        self._state_causal(is_causal)
         tdt = {"f16": torch.float16, "bf16": torch.bfloat16}.get(self.dtype, torch.float32)
         d = self.dims[1]
         if not qkv.is_cuda or qkv.device != self.device:

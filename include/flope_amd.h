@@ -340,7 +340,15 @@ int flope_tf_forward(flope_tf_handle h, const float* x_dev, int batch, int seq_l
  *   "fused" (default 0; 0 or 1, FLOPE_EINVAL outside): 1 = a FLOPE_DT_F32 forward whose longest sequence fits one workgroup's 64 KiB
  *       of LDS (flope_amd/csrc/tf_fused_plan.h) runs as ONE launch, one sequence per workgroup (tf_fused_f32), and
  *       returns the bits of the launch sequence; any other forward runs that sequence, silently.  Stored and ignored by 16-bit
- *       handles and while "f32mfma" = 1; may be flipped between forwards; flope_tf_attention / _linear / _layernorm ignore it. */
+ *       handles and while "f32mfma" = 1; may be flipped between forwards; flope_tf_attention / _linear / _layernorm ignore it;
+ *   "causal" (default 0; 0 or 1, FLOPE_EINVAL outside): 1 = query i attends to keys j <= i of its own sequence (torch's
+ *       mask = generate_square_subsequent_mask(seq_len)) in flope_tf_forward, _forward_varlen (causal inside each
+ *       sequence; rows behind a sequence still come back as out_layer.bias, never read -- torch computes something there once a mask
+ *       is given), _attention and _attention_varlen.  Every dtype and every attention kernel has the form, "fused" included; the
+ *       kernel a shape picks, its grid, block and LDS (and so flope_tf_forward_plan's answer) are those of the option at 0, and
+ *       keys above the diagonal are skipped, not loaded and masked.  flope_tf_forward_flops / _flops_varlen count attention as
+ *       num_layers model_dim sum len (len + 1) MACs under it.  Row i of a causal forward depends on rows <= i only: the forward of a
+ *       prefix is the prefix of the forward, bit for bit.  May be flipped between calls.  No other [L, L] mask has a form. */
 int flope_tf_set_option(flope_tf_handle h, const char* name, int value);
 /* softmax(q k^T / sqrt(head_dim)) v per head on a caller's buffer: qkv_dev [batch, seq_len, 3*model_dim] and out_dev
  * [batch, seq_len, model_dim] in the handle's dtype (float32 for FLOPE_DT_F32).  Launches exactly what flope_tf_forward
