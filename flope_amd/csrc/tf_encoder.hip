@@ -15,10 +15,14 @@
 // FLOPE_DT_F32 with option fused = 1: a forward whose longest sequence fits 64 KiB of LDS is ONE launch (tf_fused_f32), same bits.
 // Option causal = 1 (any dtype): query i attends to keys j <= i of its own sequence -- the CAUSAL instantiation of whichever attention
 // kernel the shape picks, and of tf_fused_f32; key blocks above the diagonal are skipped, not loaded and masked.
+// flope_tf_stream_* (any dtype): one new token per track instead of the causal forward again -- the same launch sequence at one row per
+// track, with tf_attn_step over a per-track cache of every layer's keys and values where the forward has its attention kernel
+// (the checks and launch shapes are in tf_encoder_stream.h).
 #include "../../include/flope_amd.h"
 #include "common.h"
 #include "host_pack.h"
 #include "tf_attn_plan.h"
+#include "tf_encoder_stream.h"
 #include "tf_fused_plan.h"
 
 #include <math.h>
@@ -317,6 +321,148 @@ __global__ void tf_attn_generic(const T* qkv, T* out, int L, int d, int H, const
   const T* base = VARLEN ? qkv + row0 * 3 * d + h * dh : qkv + (size_t)b * L * 3 * d + h * dh;
   for (int i = blockIdx.y * nw + wave; i < L; i += gridDim.y * nw)
     tf_attn_row<T, CAUSAL>(base, (size_t)3 * d, out + ((VARLEN ? row0 : (size_t)b * L) + i) * d + h * dh, s, i, L, d, dh, scale, lane);
+}
+
+// ---- streaming step (flope_tf_stream_*) ----------------------------------------------------------------------------
+// VE consecutive elements of a head slice as floats: one 16-byte load (VEC) or VE = 1 element
+template <typename T, bool VEC> struct TfSlice {
+  static constexpr int VE = VEC ? 16 / (int)sizeof(T) : 1;
+  float f[VE];
+  __device__ __forceinline__ void load(const T* p) {
+    if constexpr (!VEC) f[0] = to_f32<T>(p[0]);
+    else if constexpr (std::is_same<T, float>::value) {
+      const f32x4 v = *(const f32x4*)p;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) f[e] = v[e];
+    } else {
+      const u32x4 v = *(const u32x4*)p;
+#pragma unroll
+      for (int w = 0; w < 4; ++w) { f[2 * w] = unpack_lo<T>(v[w]); f[2 * w + 1] = unpack_hi<T>(v[w]); }
+    }
+  }
+  __device__ __forceinline__ void store(T* p) const {
+    if constexpr (!VEC) p[0] = from_f32<T>(f[0]);
+    else if constexpr (std::is_same<T, float>::value) *(f32x4*)p = f32x4{f[0], f[1], f[2], f[3]};
+    else {
+      // element-wise conversions, as tf_attn_row's store makes them
+      struct { T t[VE]; } w;
+#pragma unroll
+      for (int e = 0; e < VE; ++e) w.t[e] = from_f32<T>(f[e]);
+      *(u32x4*)p = __builtin_bit_cast(u32x4, w);
+    }
+  }
+};
+
+// tf_attn_row<T, true> for query pos, operation for operation, with the keys and values in two places: those of positions 0 .. pos - 1
+// in the track's cache rows (kv: the head's k columns of cache row 0, rows of ld elements, v at + d) and those of position pos in the
+// new token's qkv row (tok: its head's q columns, k at + d, v at + 2 d).  The order is tf_attn_row's -- per key one fmaf chain over
+// c = 0 .. dh - 1 from 0.f, * scale; lane j takes keys j, j + 64, ..; wave_max, expf, wave_sum; per output dim one fmaf chain over
+// j = 0 .. pos from 0.f; * (1 / sum) -- and so are the bits (tests/test_gpu_tf_stream.py holds the two definitions to that).  It is
+// a second definition, not a call, because what differs is the loops themselves: a key comes from one of two buffers, a lane reads
+// its key's slice as 16-byte vectors, and the value pass gives a lane VE output dims and keeps kTfStepUnroll keys' loads in flight
+// in front of their fmafs, where tf_attn_row has one scalar load per trip; each of these would change the loops tf_attn_generic
+// and tf_fused_f32 compile from.
+constexpr int kTfStepUnroll = 16;
+template <typename T, bool VEC>
+__device__ __forceinline__ void tf_attn_step_row(const T* tok, const T* kv, size_t ld, T* orow, float* s, int pos, int d, int dh, float scale,
+                                                 int lane) {
+  typedef TfSlice<T, VEC> Sl;
+  constexpr int VE = Sl::VE;
+  const int L = pos + 1;
+  float mx = -INFINITY;
+  for (int j = lane; j < L; j += 64) {
+    const T* k = j == pos ? tok + d : kv + (size_t)j * ld;
+    float a = 0.f;
+    for (int c = 0; c < dh; c += VE) {
+      Sl qv, kx;
+      qv.load(tok + c);
+      kx.load(k + c);
+#pragma unroll
+      for (int e = 0; e < VE; ++e) a = fmaf(qv.f[e], kx.f[e], a);
+    }
+    a *= scale;
+    s[j] = a;
+    mx = fmaxf(mx, a);
+  }
+  mx = wave_max(mx);
+  float sum = 0.f;
+  for (int j = lane; j < L; j += 64) { const float p = expf(s[j] - mx); s[j] = p; sum += p; }
+  sum = wave_sum(sum);
+  __builtin_amdgcn_wave_barrier();
+  const float inv = 1.f / sum;
+  for (int c = lane * VE; c < dh; c += 64 * VE) {
+    const T* v = kv + d + c;
+    float o[VE];
+#pragma unroll
+    for (int e = 0; e < VE; ++e) o[e] = 0.f;
+    int j = 0;
+    for (; j + kTfStepUnroll <= pos; j += kTfStepUnroll) {
+      Sl vv[kTfStepUnroll];
+#pragma unroll
+      for (int u = 0; u < kTfStepUnroll; ++u) vv[u].load(v + (size_t)(j + u) * ld);
+#pragma unroll
+      for (int u = 0; u < kTfStepUnroll; ++u) {
+        const float p = s[j + u];
+#pragma unroll
+        for (int e = 0; e < VE; ++e) o[e] = fmaf(p, vv[u].f[e], o[e]);
+      }
+    }
+    for (; j < pos; ++j) {
+      Sl vv;
+      vv.load(v + (size_t)j * ld);
+#pragma unroll
+      for (int e = 0; e < VE; ++e) o[e] = fmaf(s[j], vv.f[e], o[e]);
+    }
+    Sl vv;
+    vv.load(tok + 2 * d + c);                     // the value of position pos: from the qkv row, never from the cache row stored above
+#pragma unroll
+    for (int e = 0; e < VE; ++e) vv.f[e] = fmaf(s[pos], vv.f[e], o[e]) * inv;
+    vv.store(orow + c);
+  }
+  __builtin_amdgcn_wave_barrier();
+}
+
+// One new token per track: wave (row r, head h) takes q, k and v of the token from row r of qkv [n][3 d], stores that k | v slice
+// into row pos of its track in cache [tracks][capacity][2 d] (one layer's part; for later steps only) and writes
+// softmax(q K^T / sqrt(dh)) V over keys 0 .. pos to att [n][d].  tab: (track, pos) per row.  smax: floats of a wave's score row
+// (the call's largest pos + 1).  A row whose table entry is no track, no row of the cache or past the score row is left alone:
+// nothing is written outside the track's capacity rows, whatever the table holds.
+template <typename T, bool VEC>
+__global__ __launch_bounds__(256) void tf_attn_step(const T* __restrict__ qkv, T* cache, T* __restrict__ att, const int* __restrict__ tab, int n,
+                                                    int d, int H, int tracks, int capacity, int smax) {
+  extern __shared__ __attribute__((aligned(16))) float sc[];     // [waves][smax]
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int it = blockIdx.x * flope_tf_plan::kTfStepWaves + wave;
+  if (it >= n * H) return;
+  const int r = it / H, h = it - r * H, dh = d / H;
+  const int track = tab[2 * r], pos = tab[2 * r + 1];
+  if ((unsigned)track >= (unsigned)tracks || (unsigned)pos >= (unsigned)capacity || pos >= smax) return;
+  const float scale = 1.f / sqrtf((float)dh);
+  const size_t ld = (size_t)2 * d;
+  const T* tok = qkv + (size_t)r * 3 * d + h * dh;
+  T* kv = cache + (size_t)track * capacity * ld + h * dh;
+  constexpr int VE = TfSlice<T, VEC>::VE;
+  for (int c = lane * VE; c < 2 * dh; c += 64 * VE) {            // k slice | v slice of the token -> cache row pos
+    const int col = c < dh ? c : c - dh + d;
+    if constexpr (VEC) *(u32x4*)(kv + pos * ld + col) = *(const u32x4*)(tok + d + col);
+    else kv[pos * ld + col] = tok[d + col];
+  }
+  tf_attn_step_row<T, VEC>(tok, kv, ld, att + (size_t)r * d + h * dh, sc + (size_t)wave * smax, pos, d, dh, scale, lane);
+}
+
+// prefill: the k | v columns (d .. 3 d) of the valid packed rows of qkv [T][3 d] -> rows 0 .. len - 1 of each sequence's track in
+// cache [tracks][capacity][2 d].  off: the ragged batch's offsets; trk: the track of sequence b.  V: u32x4 (dv = d / elements per 16
+// bytes) or the element type (dv = d).  A sequence whose entry is no track, and rows past capacity, are skipped.
+template <typename V>
+__global__ void tf_cache_fill(const V* __restrict__ qkv, V* __restrict__ cache, const int* __restrict__ off, const int* __restrict__ trk,
+                              int max_len, int dv, int tracks, int capacity, size_t total) {
+  const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= total) return;
+  const size_t r = idx / (2 * dv);
+  const int c = (int)(idx - r * (2 * dv)), b = (int)(r / max_len), i = (int)(r - (size_t)b * max_len);
+  const int o = off[b], t = trk[b];
+  if (i >= off[b + 1] - o || i >= capacity || (unsigned)t >= (unsigned)tracks) return;
+  cache[((size_t)t * capacity + i) * 2 * dv + c] = qkv[(size_t)(o + i) * 3 * dv + dv + c];
 }
 
 // ---- MFMA linear: Y[128-token tile][128-feature tile], K walked in 64-wide chunks ----------------------------
@@ -1111,6 +1257,7 @@ struct TfLinear {
   float* pk32 = nullptr; float* bpad = nullptr;   // FLOPE_DT_F32, K % 4 == 0: pack_tf_f32m image and the bias padded to whole 64-feature blocks
   int N = 0, K = 0, Kp = 0;                  // Kp: K rounded up to 64 (the packed image's K)
 };
+struct flope_tf_stream_s;
 struct TfLayer { TfLinear in_proj, out_proj, lin1, lin2; float *n1w = nullptr, *n1b = nullptr, *n2w = nullptr, *n2b = nullptr; };
 
 struct flope_tf_encoder {
@@ -1135,7 +1282,19 @@ struct flope_tf_encoder {
   int* vl_off = nullptr;
   std::vector<int> vl_host;
   std::vector<void*> allocs;
+  std::vector<flope_tf_stream_s*> streams;   // the open stream states of this handle (flope_tf_stream_open); destroy orphans them
   std::string err;
+};
+
+// A stream state (flope_tf_stream_*): the keys and values of `tracks` tracks of up to `capacity` tokens per layer,
+// and how many tokens each track holds.  Positions live here, on the host; a call uploads the table of its rows.
+struct flope_tf_stream_s {
+  flope_tf_encoder* e = nullptr;             // nullptr once the handle is destroyed: every call but close then fails with FLOPE_ESTATE
+  int tracks = 0, capacity = 0;
+  void* cache = nullptr;                     // [num_layers][tracks][capacity][2 model_dim] in the handle's dtype, a row is k | v
+  int* tab = nullptr;                        // device table of one call: step (track, position) per row, prefill the track per sequence
+  std::vector<int> pos, tab_host;            // tokens held per track; the pageable copy tab is uploaded from
+  std::vector<char> seen;                    // scratch of the argument checks
 };
 
 namespace {
@@ -1330,19 +1489,24 @@ int tf_check_ragged(flope_tf_encoder* e, const char* who, const int* lengths, in
 }
 
 // Validates and plans a ragged batch into e->vl_host and enqueues the upload of its batch + 1 offsets.
-int tf_plan_ragged(flope_tf_encoder* e, const char* who, const int* lengths, int B, int L, hipStream_t st, TfRagged* rg) {
-  int rc;
-  if ((rc = tf_check_ragged(e, who, lengths, B, L, e->vl_host.data(), rg))) return rc;
+int tf_upload_ragged(flope_tf_encoder* e, int B, hipStream_t st) {
   // pageable source: the runtime has staged it when the call returns, so the next call may overwrite vl_host
   TF_HIP(e, hipMemcpyAsync(e->vl_off, e->vl_host.data(), (size_t)(B + 1) * sizeof(int), hipMemcpyHostToDevice, st));
   return 0;
 }
+int tf_plan_ragged(flope_tf_encoder* e, const char* who, const int* lengths, int B, int L, hipStream_t st, TfRagged* rg) {
+  int rc;
+  if ((rc = tf_check_ragged(e, who, lengths, B, L, e->vl_host.data(), rg))) return rc;
+  return tf_upload_ragged(e, B, st);
+}
 
 // rg == nullptr: the fixed-length forward, x [B][L][in] -> y [B][L][out].  Otherwise the ragged one: the valid rows of x are gathered
 // into rg->T packed rows, every linear and LayerNorm runs on those, attention per sequence, and the result is scattered into y.
-template <typename T>
-int run_forward(flope_tf_encoder* e, const float* x, int B, int L, float* y, hipStream_t st, const TfRagged* rg = nullptr) {
+// attention(li): what stands between in_proj and out_proj of layer li (qkv of the M rows in e->qkv -> e->att); < 0 ends the forward.
+template <typename T, typename ATT>
+int run_forward_with(flope_tf_encoder* e, const float* x, int B, int L, float* y, hipStream_t st, const TfRagged* rg, ATT&& attention) {
   const int M = rg ? rg->T : B * L;
+  int li = 0;
   int rc;
   if (rg) {
     const bool cast = !std::is_same<T, float>::value && e->emb.packed && !e->opt_generic;     // where launch_linear would run tf_cast_pad
@@ -1356,7 +1520,7 @@ int run_forward(flope_tf_encoder* e, const float* x, int B, int L, float* y, hip
   } else if ((rc = launch_linear<T>(e, e->emb, x, 1, nullptr, e->h, 0, M, 0, st)) < 0) return rc;
   for (TfLayer& ly : e->layers) {
     if ((rc = launch_linear<T>(e, ly.in_proj, e->h, 0, nullptr, e->qkv, 0, M, 0, st)) < 0) return rc;
-    if ((rc = launch_attention<T>(e, e->qkv, e->att, B, rg ? rg->max_len : L, rg ? e->vl_off : nullptr, st)) < 0) return rc;
+    if ((rc = attention(li++)) < 0) return rc;
     if ((rc = launch_linear<T>(e, ly.out_proj, e->att, 0, e->h, e->h2, 0, M, 0, st)) < 0) return rc;
     if ((rc = launch_layernorm<T>(e, e->h2, e->h, ly.n1w, ly.n1b, M, st)) < 0) return rc;
     if ((rc = launch_linear<T>(e, ly.lin1, e->h, 0, nullptr, e->ffb, 0, M, 1, st)) < 0) return rc;
@@ -1370,6 +1534,14 @@ int run_forward(flope_tf_encoder* e, const float* x, int B, int L, float* y, hip
                      e->out_dim, tot);
   TF_HIP(e, hipGetLastError());
   return 0;
+}
+
+// ... with launch_attention there: flope_tf_forward and flope_tf_forward_varlen
+template <typename T>
+int run_forward(flope_tf_encoder* e, const float* x, int B, int L, float* y, hipStream_t st, const TfRagged* rg = nullptr) {
+  return run_forward_with<T>(e, x, B, L, y, st, rg, [&](int) {
+    return launch_attention<T>(e, e->qkv, e->att, B, rg ? rg->max_len : L, rg ? e->vl_off : nullptr, st);
+  });
 }
 
 // Option fused: whether a float32 forward whose longest sequence has Lmax tokens runs as the single launch
@@ -1513,6 +1685,10 @@ extern "C" int flope_tf_create(int device_id, int input_dim, int model_dim, int 
 extern "C" int flope_tf_destroy(flope_tf_handle e) {
   if (!e) return FLOPE_OK;
   hipSetDevice(e->device);
+  for (flope_tf_stream_s* s : e->streams) {      // their device memory goes with the handle; the states stay until closed and refuse every call
+    hipFree(s->cache); hipFree(s->tab);
+    s->cache = nullptr; s->tab = nullptr; s->e = nullptr;
+  }
   for (void* p : e->allocs) hipFree(p);
   delete e;
   return FLOPE_OK;
@@ -1771,6 +1947,186 @@ extern "C" double flope_tf_forward_flops_varlen(flope_tf_handle e, int batch, co
   double mac = M * e->in_dim * d + M * d * e->out_dim;
   mac += e->nl * (M * d * 3 * d + M * d * d + 2.0 * M * d * e->ff + (e->opt_causal ? (sq + M) * d : 2.0 * sq * d));
   return 2.0 * mac;
+}
+
+// ---- streaming causal forward ---------------------------------------------------------------------------------------
+namespace {
+
+using flope_tf_plan::tf_stream_track;
+
+// the checks every call on a state starts with; *e: its handle
+int tf_stream_enter(flope_tf_stream_s* s, const std::string& who, flope_tf_encoder** e) {
+  if (!s) return tf_fail(nullptr, FLOPE_EINVAL, who + ": NULL stream state");
+  if (!s->e) return tf_fail(nullptr, FLOPE_ESTATE, who + ": the encoder handle of this stream state has been destroyed");
+  *e = s->e;
+  return 0;
+}
+
+// the refusals of tf_encoder_stream.h in words; bad: the index they name
+int tf_stream_refuse(flope_tf_stream_s* s, const std::string& who, int rc, int bad, int n, const int* rows, const int* lengths, int seq_len) {
+  using namespace flope_tf_plan;
+  flope_tf_encoder* e = s->e;
+  const std::string i = std::to_string(bad);
+  switch (rc) {
+    case kTfStreamCount:
+      return tf_fail(e, FLOPE_EINVAL, who + ": n = " + std::to_string(n) + " is outside 1 .. min(tracks = " + std::to_string(s->tracks) + ", max_tokens = " +
+                                          std::to_string(e->max_tokens) + ")" + (rows ? "" : ", or tracks_host is NULL and n is not the state's track count"));
+    case kTfStreamRange:
+      return tf_fail(e, FLOPE_EINVAL, who + ": tracks[" + i + "] = " + std::to_string(rows[bad]) + " is outside 0 .. " + std::to_string(s->tracks - 1));
+    case kTfStreamDuplicate:
+      return tf_fail(e, FLOPE_EINVAL, who + ": tracks[" + i + "] = " + std::to_string(rows[bad]) + " names a track an earlier row names (one token per track and call)");
+    case kTfStreamFull:
+      return tf_fail(e, FLOPE_EINVAL, who + ": row " + i + ": track " + std::to_string(tf_stream_track(rows, bad)) + " already holds capacity = " + std::to_string(s->capacity) +
+                                          " tokens (reset it, or open a state with more room)");
+    default:
+      return tf_fail(e, FLOPE_EINVAL, who + ": lengths[" + i + "] = " + std::to_string(lengths ? lengths[bad] : seq_len) + " exceeds capacity = " + std::to_string(s->capacity));
+  }
+}
+
+// the forward's launch sequence at M = n rows, tf_attn_step where it has launch_attention
+template <typename T>
+int run_step(flope_tf_stream_s* s, const float* x, int n, int max_pos, float* y, hipStream_t st) {
+  flope_tf_encoder* e = s->e;
+  const flope_tf_plan::TfStreamLaunch l = flope_tf_plan::tf_step_launch(n, e->H, max_pos);
+  const size_t layer = (size_t)s->tracks * s->capacity * 2 * e->d;
+  return run_forward_with<T>(e, x, n, 1, y, st, nullptr, [&](int li) {
+    T* cache = (T*)s->cache + (size_t)li * layer;
+    if (flope_tf_plan::tf_step_vec_ok(e->d / e->H, (int)sizeof(T)))
+      hipLaunchKernelGGL((tf_attn_step<T, true>), dim3(l.grid_x), dim3(l.block), l.lds, st, (const T*)e->qkv, cache, (T*)e->att, (const int*)s->tab, n, e->d, e->H,
+                         s->tracks, s->capacity, max_pos + 1);
+    else
+      hipLaunchKernelGGL((tf_attn_step<T, false>), dim3(l.grid_x), dim3(l.block), l.lds, st, (const T*)e->qkv, cache, (T*)e->att, (const int*)s->tab, n, e->d, e->H,
+                         s->tracks, s->capacity, max_pos + 1);
+    TF_HIP(e, hipGetLastError());
+    return 0;
+  });
+}
+
+// the causal ragged forward's launch sequence, each layer's k | v rows copied into the cache in front of its attention
+template <typename T>
+int run_prefill(flope_tf_stream_s* s, const float* x, int n, int L, const TfRagged& rg, float* y, hipStream_t st) {
+  flope_tf_encoder* e = s->e;
+  const size_t layer = (size_t)s->tracks * s->capacity * 2 * e->d;
+  const bool vec = flope_tf_plan::tf_cache_fill_vec_ok(e->d, (int)sizeof(T));
+  const int dv = vec ? e->d / flope_tf_plan::tf_stream_vec((int)sizeof(T)) : e->d;
+  const flope_tf_plan::TfStreamLaunch l = flope_tf_plan::tf_cache_fill_launch(n, rg.max_len, 2 * dv);
+  const size_t total = (size_t)n * rg.max_len * 2 * dv;
+  return run_forward_with<T>(e, x, n, L, y, st, &rg, [&](int li) {
+    T* cache = (T*)s->cache + (size_t)li * layer;
+    if (vec)
+      hipLaunchKernelGGL((tf_cache_fill<u32x4>), dim3(l.grid_x), dim3(l.block), 0, st, (const u32x4*)e->qkv, (u32x4*)cache, (const int*)e->vl_off, (const int*)s->tab,
+                         rg.max_len, dv, s->tracks, s->capacity, total);
+    else
+      hipLaunchKernelGGL((tf_cache_fill<T>), dim3(l.grid_x), dim3(l.block), 0, st, (const T*)e->qkv, cache, (const int*)e->vl_off, (const int*)s->tab, rg.max_len, dv,
+                         s->tracks, s->capacity, total);
+    TF_HIP(e, hipGetLastError());
+    return launch_attention<T>(e, e->qkv, e->att, n, rg.max_len, e->vl_off, st);
+  });
+}
+
+}  // namespace
+
+extern "C" int flope_tf_stream_open(flope_tf_handle e, int tracks, int capacity, flope_tf_stream* out) {
+  if (!out) return tf_fail(e, FLOPE_EINVAL, "flope_tf_stream_open: NULL out");
+  *out = nullptr;
+  if (!e) return tf_fail(nullptr, FLOPE_EINVAL, "flope_tf_stream_open: NULL handle");
+  if (flope_tf_plan::tf_stream_check_open(tracks, capacity))
+    return tf_fail(e, FLOPE_EINVAL, "flope_tf_stream_open: tracks must be positive and capacity 1 .. " + std::to_string(flope_tf_plan::kTfStreamMaxCapacity) +
+                                        " (the score rows of tf_attn_step live in 64 KiB of LDS)");
+  TF_HIP(e, hipSetDevice(e->device));
+  const size_t bytes = (size_t)e->nl * tracks * capacity * 2 * e->d * e->esz;
+  flope_tf_stream_s* s = new flope_tf_stream_s();
+  s->e = e; s->tracks = tracks; s->capacity = capacity;
+  // num_layers = 0 has no cache; the allocation keeps one row so that the pointer is a pointer
+  if (hipMalloc(&s->cache, bytes ? bytes : 16) != hipSuccess || hipMalloc((void**)&s->tab, (size_t)2 * tracks * sizeof(int)) != hipSuccess) {
+    (void)hipGetLastError();
+    hipFree(s->cache); hipFree(s->tab);
+    delete s;
+    return tf_fail(e, FLOPE_EHIP, "flope_tf_stream_open: hipMalloc failed for a cache of " + std::to_string(bytes) + " bytes (num_layers x tracks x capacity x 2 model_dim)");
+  }
+  s->pos.assign((size_t)tracks, 0);
+  s->tab_host.assign((size_t)2 * tracks, 0);
+  s->seen.assign((size_t)tracks, 0);
+  e->streams.push_back(s);
+  *out = s;
+  return FLOPE_OK;
+}
+
+extern "C" int flope_tf_stream_close(flope_tf_stream s) {
+  if (!s) return FLOPE_OK;
+  if (flope_tf_encoder* e = s->e) {
+    hipSetDevice(e->device);
+    hipFree(s->cache); hipFree(s->tab);
+    for (auto it = e->streams.begin(); it != e->streams.end(); ++it)
+      if (*it == s) { e->streams.erase(it); break; }
+  }
+  delete s;
+  return FLOPE_OK;
+}
+
+extern "C" int flope_tf_stream_reset(flope_tf_stream s, int n, const int* tracks_host) {
+  flope_tf_encoder* e;
+  int rc, bad = -1;
+  if ((rc = tf_stream_enter(s, "flope_tf_stream_reset", &e))) return rc;
+  if ((rc = flope_tf_plan::tf_stream_check_reset(s->tracks, n, tracks_host, &bad)))
+    return tf_stream_refuse(s, "flope_tf_stream_reset", rc, bad, n, tracks_host, nullptr, 0);
+  if (!tracks_host) s->pos.assign((size_t)s->tracks, 0);
+  else for (int r = 0; r < n; ++r) s->pos[(size_t)tracks_host[r]] = 0;
+  return FLOPE_OK;
+}
+
+extern "C" int flope_tf_stream_position(flope_tf_stream s, int track) {
+  flope_tf_encoder* e;
+  int rc;
+  if ((rc = tf_stream_enter(s, "flope_tf_stream_position", &e))) return rc;
+  if (track < 0 || track >= s->tracks)
+    return tf_fail(e, FLOPE_EINVAL, "flope_tf_stream_position: track " + std::to_string(track) + " is outside 0 .. " + std::to_string(s->tracks - 1));
+  return s->pos[(size_t)track];
+}
+
+extern "C" int flope_tf_stream_step(flope_tf_stream s, const float* x_dev, int n, const int* tracks_host, float* y_dev, void* stream) {
+  const std::string who = "flope_tf_stream_step";
+  flope_tf_encoder* e;
+  int rc, bad = -1, max_pos = 0;
+  if ((rc = tf_stream_enter(s, who, &e))) return rc;
+  if (!e->loaded) return tf_fail(e, FLOPE_ESTATE, who + ": weights not loaded");
+  if ((rc = flope_tf_plan::tf_stream_check_step(s->pos.data(), s->tracks, s->capacity, e->max_tokens, n, tracks_host, s->seen.data(), &bad, &max_pos)))
+    return tf_stream_refuse(s, who, rc, bad, n, tracks_host, nullptr, 0);
+  if (!x_dev || !y_dev) return tf_fail(e, FLOPE_EINVAL, who + ": NULL buffer");
+  TF_HIP(e, hipSetDevice(e->device));
+  hipStream_t st = (hipStream_t)stream;
+  flope_tf_plan::tf_stream_step_table(s->pos.data(), n, tracks_host, s->tab_host.data());
+  // pageable source, as the offsets of a ragged batch: staged when the call returns, so the next call may overwrite tab_host
+  TF_HIP(e, hipMemcpyAsync(s->tab, s->tab_host.data(), (size_t)2 * n * sizeof(int), hipMemcpyHostToDevice, st));
+  flope_tf_plan::tf_stream_advance(s->pos.data(), n, tracks_host);
+  return tf_by_dtype(e, [&](auto tag) { return run_step<typename decltype(tag)::type>(s, x_dev, n, max_pos, y_dev, st); });
+}
+
+extern "C" int flope_tf_stream_prefill(flope_tf_stream s, const float* x_dev, int n, int seq_len, const int* lengths_host, const int* tracks_host, float* y_dev,
+                                       void* stream) {
+  const std::string who = "flope_tf_stream_prefill";
+  flope_tf_encoder* e;
+  int rc, bad = -1;
+  if ((rc = tf_stream_enter(s, who, &e))) return rc;
+  if ((rc = tf_check_forward_varlen(e, who, n, seq_len, x_dev && y_dev))) return rc;
+  std::vector<int> full;                            // lengths_host NULL: every sequence has seq_len tokens
+  if (!lengths_host && n > 0) full.assign((size_t)n, seq_len);
+  const int* lengths = lengths_host ? lengths_host : full.data();
+  TfRagged rg;
+  if ((rc = tf_check_ragged(e, who.c_str(), lengths, n, seq_len, e->vl_host.data(), &rg))) return rc;
+  if ((rc = flope_tf_plan::tf_stream_check_prefill(s->tracks, s->capacity, n, seq_len, lengths, tracks_host, s->seen.data(), &bad)))
+    return tf_stream_refuse(s, who, rc, bad, n, tracks_host, lengths, seq_len);
+  TF_HIP(e, hipSetDevice(e->device));
+  hipStream_t st = (hipStream_t)stream;
+  if ((rc = tf_upload_ragged(e, n, st))) return rc;
+  for (int b = 0; b < n; ++b) s->tab_host[(size_t)b] = tf_stream_track(tracks_host, b);
+  TF_HIP(e, hipMemcpyAsync(s->tab, s->tab_host.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice, st));
+  flope_tf_plan::tf_stream_set_lengths(s->pos.data(), n, seq_len, lengths, tracks_host);
+  const int causal = e->opt_causal;                 // causal for these launches only; last_fwd is tf_forward's and stays
+  e->opt_causal = 1;
+  rc = tf_by_dtype(e, [&](auto tag) { return run_prefill<typename decltype(tag)::type>(s, x_dev, n, seq_len, rg, y_dev, st); });
+  e->opt_causal = causal;
+  return rc;
 }
 
 #ifdef FLOPE_STAG_DBG

@@ -1,0 +1,117 @@
+// The streaming causal forward of the encoder (flope_tf_stream_*) as far as it is plain integer arithmetic, no HIP:
+// the argument checks of step / prefill / reset over host arrays, the capacity limit, and grid, block and LDS of tf_attn_step and
+// tf_cache_fill.  Shared by tf_encoder.hip and tests/host_harness/harness_tf_stream.cpp (tests/test_tf_stream_host.py holds it
+// against brute force on the CPU, tests/test_gpu_tf_stream.py the device against it).
+#pragma once
+
+#include <stddef.h>
+#include <stdint.h>
+#include <string.h>
+
+namespace flope_tf_plan {
+
+// tf_attn_step: one wave per (row, head), four waves per workgroup; a wave's score row holds the keys 0 .. pos of its track, and a
+// launch sizes every row for the largest position of the call
+constexpr int kTfStepWaves = 4;
+constexpr size_t kTfStepLdsMax = 64 * 1024;          // what a launch gets without asking for more
+constexpr size_t tf_step_lds(int max_pos) { return (size_t)kTfStepWaves * ((size_t)max_pos + 1) * sizeof(float); }
+// the largest capacity whose last position (capacity - 1) still fits: 4096
+constexpr int kTfStreamMaxCapacity = (int)(kTfStepLdsMax / (kTfStepWaves * sizeof(float)));
+static_assert(tf_step_lds(kTfStreamMaxCapacity - 1) <= kTfStepLdsMax && tf_step_lds(kTfStreamMaxCapacity) > kTfStepLdsMax,
+              "kTfStreamMaxCapacity is the largest capacity whose score rows fit");
+static_assert(kTfStreamMaxCapacity >= 4096, "a track holds at least 4096 tokens");
+
+struct TfStreamLaunch { unsigned grid_x, block; size_t lds; };
+// n rows of H heads at positions <= max_pos
+inline TfStreamLaunch tf_step_launch(int n, int H, int max_pos) {
+  return {(unsigned)(((long long)n * H + kTfStepWaves - 1) / kTfStepWaves), 64u * kTfStepWaves, tf_step_lds(max_pos)};
+}
+// tf_cache_fill: one thread per unit (a 16-byte vector or one element) of the k | v columns of the n x max_len rows a ragged batch may
+// hold; units: those of the 2 model_dim columns of a cache row
+inline TfStreamLaunch tf_cache_fill_launch(int n, int max_len, int units) {
+  const size_t total = (size_t)n * max_len * units;
+  return {(unsigned)((total + 255) / 256), 256u, 0};
+}
+// elements per 16-byte vector of a cache of esz-byte elements, and whether a head slice (tf_attn_step) or the k | v columns
+// (tf_cache_fill) of a row move as whole vectors: the cache and the handle's qkv buffer are 16-byte aligned, rows are 2 and 3
+// model_dim elements, so what has to divide is the first column of the slice and its width
+constexpr int tf_stream_vec(int esz) { return 16 / esz; }
+constexpr bool tf_step_vec_ok(int head_dim, int esz) { return head_dim % tf_stream_vec(esz) == 0; }
+constexpr bool tf_cache_fill_vec_ok(int model_dim, int esz) { return model_dim % tf_stream_vec(esz) == 0; }
+
+enum {
+  kTfStreamOk = 0,
+  kTfStreamCount = -1,      // n < 1, n > the limit, or a NULL track list with n != tracks
+  kTfStreamRange = -2,      // rows[*bad] is no track
+  kTfStreamDuplicate = -3,  // rows[*bad] names a track an earlier row named
+  kTfStreamFull = -4,       // step: the track of row *bad already holds capacity tokens
+  kTfStreamLength = -5,     // prefill: lengths[*bad] > capacity
+  kTfStreamOpen = -6        // open: tracks < 1 or capacity outside 1 .. kTfStreamMaxCapacity
+};
+
+inline int tf_stream_check_open(int tracks, int capacity) {
+  return tracks >= 1 && capacity >= 1 && capacity <= kTfStreamMaxCapacity ? kTfStreamOk : kTfStreamOpen;
+}
+
+// The track of row r: rows[r], or r with a NULL list
+inline int tf_stream_track(const int* rows, int r) { return rows ? rows[r] : r; }
+
+// n rows name n distinct tracks of `tracks`; rows == NULL: n == tracks and row r is track r.  seen: scratch of `tracks` bytes.
+inline int tf_stream_check_rows(int tracks, int limit, int n, const int* rows, char* seen, int* bad) {
+  if (n < 1 || n > limit || n > tracks) return kTfStreamCount;
+  if (!rows) return n == tracks ? kTfStreamOk : kTfStreamCount;
+  memset(seen, 0, (size_t)tracks);
+  for (int r = 0; r < n; ++r) {
+    if (rows[r] < 0 || rows[r] >= tracks) { *bad = r; return kTfStreamRange; }
+    if (seen[rows[r]]) { *bad = r; return kTfStreamDuplicate; }
+    seen[rows[r]] = 1;
+  }
+  return kTfStreamOk;
+}
+
+// step: 1 <= n <= min(tracks, max_tokens), distinct tracks in range, none at capacity.  *max_pos: the largest position of the call
+// (the position a row's token takes is what its track holds).  Writes nothing but *bad / *max_pos and the scratch.
+inline int tf_stream_check_step(const int* pos, int tracks, int capacity, int max_tokens, int n, const int* rows, char* seen, int* bad,
+                                int* max_pos) {
+  const int rc = tf_stream_check_rows(tracks, max_tokens, n, rows, seen, bad);
+  if (rc) return rc;
+  int mx = 0;
+  for (int r = 0; r < n; ++r) {
+    const int p = pos[tf_stream_track(rows, r)];
+    if (p >= capacity) { *bad = r; return kTfStreamFull; }
+    if (p > mx) mx = p;
+  }
+  *max_pos = mx;
+  return kTfStreamOk;
+}
+// ... its device table, (track, position) per row, and the positions behind it
+inline void tf_stream_step_table(const int* pos, int n, const int* rows, int* tab) {
+  for (int r = 0; r < n; ++r) { tab[2 * r] = tf_stream_track(rows, r); tab[2 * r + 1] = pos[tf_stream_track(rows, r)]; }
+}
+inline void tf_stream_advance(int* pos, int n, const int* rows) {
+  for (int r = 0; r < n; ++r) ++pos[tf_stream_track(rows, r)];
+}
+
+// prefill: n sequences for n distinct tracks, every length (seq_len with a NULL list) within capacity; the limits of the ragged
+// forward itself (tf_varlen_plan) are checked by the caller in front of this
+inline int tf_stream_check_prefill(int tracks, int capacity, int n, int seq_len, const int* lengths, const int* rows, char* seen, int* bad) {
+  const int rc = tf_stream_check_rows(tracks, tracks, n, rows, seen, bad);
+  if (rc) return rc;
+  for (int b = 0; b < n; ++b)
+    if ((lengths ? lengths[b] : seq_len) > capacity) { *bad = b; return kTfStreamLength; }
+  return kTfStreamOk;
+}
+inline void tf_stream_set_lengths(int* pos, int n, int seq_len, const int* lengths, const int* rows) {
+  for (int b = 0; b < n; ++b) pos[tf_stream_track(rows, b)] = lengths ? lengths[b] : seq_len;
+}
+
+// reset: rows == NULL: every track (n is ignored); otherwise n >= 1 tracks in range.  A track named twice is reset once: harmless.
+inline int tf_stream_check_reset(int tracks, int n, const int* rows, int* bad) {
+  if (!rows) return kTfStreamOk;
+  if (n < 1) return kTfStreamCount;
+  for (int r = 0; r < n; ++r)
+    if (rows[r] < 0 || rows[r] >= tracks) { *bad = r; return kTfStreamRange; }
+  return kTfStreamOk;
+}
+
+}  // namespace flope_tf_plan

@@ -360,10 +360,137 @@ class TransformerEncoder:
         self._keep = (x, weight, bias)
         return out
 
+    def open_stream(self, tracks: int, capacity: int) -> "TransformerEncoderStream":
+        """A stream state for `tracks` live tracks of up to `capacity` tokens each (TransformerEncoderStream): feed one new token per
+        track with step() and get the row a causal forward of the whole track would end with, without running it again."""
+        return TransformerEncoderStream(self, tracks, capacity)
+
     def close(self):
         if getattr(self, "handle", None) and self.handle.value:
             self.lib.flope_tf_destroy(self.handle)
             self.handle = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _host_tracks(tracks):
+    """tracks (None, a sequence or a CPU integer tensor) -> (count or None, a ctypes int array or None)"""
+    if tracks is None:
+        return None, None
+    if isinstance(tracks, torch.Tensor):
+        if tracks.is_cuda or tracks.dtype.is_floating_point or tracks.dtype == torch.bool:
+            raise ValueError("tracks must be a sequence or a CPU integer tensor (positions are kept on the host)")
+        tracks = tracks.reshape(-1).tolist()
+    vals = [int(v) for v in tracks]
+    if any(v < -2 ** 31 or v >= 2 ** 31 for v in vals):
+        raise ValueError("a track index does not fit an int")
+    return len(vals), (C.c_int * len(vals))(*vals)
+
+
+class TransformerEncoderStream:
+    """The encoder run live over `tracks` tracks (include/flope_amd.h: flope_tf_stream_*).  The state keeps every
+    layer's keys and values of each track's tokens so far, up to `capacity` per track, and the number of tokens each track holds
+    (`positions`).  step() takes one new token per track and returns the encoder's output for it: the row enc(track, is_causal=True)
+    would end with -- in bits where that forward's attention runs the generic kernel, within the attention kernels' tolerances
+    elsewhere.  prefill() loads whole histories in one causal forward.  The calls on one state run on the current stream in
+    program order; keep them on one stream.  The state keeps its encoder alive; after enc.close() its calls raise RuntimeError."""
+
+    def __init__(self, enc: TransformerEncoder, tracks: int, capacity: int):
+        self.enc = enc
+        self.state = C.c_void_p()
+        self.tracks, self.capacity = int(tracks), int(capacity)
+        self._handle()
+        with torch.cuda.device(enc.device):
+            rc = enc.lib.flope_tf_stream_open(enc.handle, self.tracks, self.capacity, C.byref(self.state))
+        enc._check_arg(rc)
+
+    def _handle(self):
+        if not self.enc.handle.value:
+            raise RuntimeError("the encoder of this stream has been closed")
+
+    def _live(self):
+        self._handle()
+        if not self.state.value:
+            raise RuntimeError("the stream has been closed")
+
+    def _check_x(self, x, dims):
+        enc = self.enc
+        if not x.is_cuda or x.device != enc.device:
+            raise RuntimeError(f"input must live on {enc.device} (got {x.device}); no CPU path")
+        if x.dim() != dims or x.shape[-1] != enc.dims[0]:
+            want = "[n, L, {}]" if dims == 3 else "[n, {}]"
+            raise ValueError(f"expected {want.format(enc.dims[0])}, got {tuple(x.shape)}")
+        return x.to(torch.float32).contiguous()
+
+    def step(self, x: torch.Tensor, tracks=None, out: torch.Tensor = None) -> torch.Tensor:
+        """x [n, input_dim]: row r is the next token of track tracks[r] (None: n == the state's track count, row r is track r) ->
+        [n, out_dim].  Tracks must be distinct and none at capacity (ValueError names the offending row; nothing has moved then).
+        `out`: a float32 [n, out_dim] tensor with contiguous rows to write into."""
+        self._live()
+        enc = self.enc
+        x = self._check_x(x, 2)
+        n = x.shape[0]
+        cnt, th = _host_tracks(tracks)
+        if cnt is not None and cnt != n:
+            raise ValueError(f"tracks has {cnt} values for {n} rows")
+        y = self._out(out, (n, enc.dims[2]))
+        with torch.cuda.device(enc.device):
+            rc = enc.lib.flope_tf_stream_step(self.state, x.data_ptr(), n, th, y.data_ptr(), _stream_ptr(enc.device))
+        enc._check_arg(rc)
+        self._keep = x
+        return y
+
+    def prefill(self, x: torch.Tensor, lengths=None, tracks=None, out: torch.Tensor = None) -> torch.Tensor:
+        """x [n, L, input_dim], sequence b the history of track tracks[b] (None as in step), `lengths` as in forward() -> the causal
+        forward enc(x, lengths=lengths, is_causal=True) [n, L, out_dim], bit for bit; the tracks then hold their lengths' tokens
+        (whatever they held before is overwritten) and the next step() continues them."""
+        self._live()
+        enc = self.enc
+        x = self._check_x(x, 3)
+        n, L = x.shape[0], x.shape[1]
+        cnt, th = _host_tracks(tracks)
+        if cnt is not None and cnt != n:
+            raise ValueError(f"tracks has {cnt} values for {n} sequences")
+        lh = None if lengths is None else _host_lengths(lengths, n)
+        y = self._out(out, (n, L, enc.dims[2]))
+        with torch.cuda.device(enc.device):
+            rc = enc.lib.flope_tf_stream_prefill(self.state, x.data_ptr(), n, L, lh, th, y.data_ptr(), _stream_ptr(enc.device))
+        enc._check_arg(rc)
+        self._keep = x
+        return y
+
+    def _out(self, out, shape):
+        if out is None:
+            return torch.empty(shape, dtype=torch.float32, device=self.enc.device)
+        if tuple(out.shape) != tuple(shape) or out.dtype != torch.float32 or out.device != self.enc.device or not out.is_contiguous():
+            raise ValueError(f"out must be a contiguous float32 tensor {tuple(shape)} on {self.enc.device}")
+        return out
+
+    def reset(self, tracks=None) -> None:
+        """The given tracks (None: all) hold nothing again; their stale cache rows are never read.  Enqueues nothing."""
+        self._live()
+        cnt, th = _host_tracks(tracks)
+        self.enc._check_arg(self.enc.lib.flope_tf_stream_reset(self.state, cnt or 0, th))
+
+    def position(self, track: int) -> int:
+        """tokens track `track` holds"""
+        self._live()
+        rc = self.enc.lib.flope_tf_stream_position(self.state, int(track))
+        self.enc._check_arg(rc)
+        return rc
+
+    @property
+    def positions(self) -> list:
+        return [self.position(t) for t in range(self.tracks)]
+
+    def close(self):
+        if getattr(self, "state", None) and self.state.value:
+            self.enc.lib.flope_tf_stream_close(self.state)      # after enc.close() this frees the host part only: the cache went with the handle
+            self.state = C.c_void_p()
 
     def __del__(self):
         try:

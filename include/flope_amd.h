@@ -415,6 +415,42 @@ int flope_tf_forward_plan(flope_tf_handle h, int batch, int seq_len, const int* 
 int flope_tf_last_forward(flope_tf_handle h);
 /* algorithmic FLOPs of one ragged forward: the linears on T tokens, attention on the sum of lengths squared; 0 for an invalid batch */
 double flope_tf_forward_flops_varlen(flope_tf_handle h, int batch, const int* lengths_host);
+/* Streaming causal forward: one new token per track and call instead of the whole track again.  A stream state owns
+ * the keys and values every layer has seen of `tracks` tracks, up to `capacity` tokens each: ONE device allocation
+ * [num_layers][tracks][capacity][2*model_dim] in the handle's dtype (float for FLOPE_DT_F32, with or without "f32mfma"), a row being
+ * k followed by v.  capacity <= 4096 (kTfStreamMaxCapacity of flope_amd/csrc/tf_encoder_stream.h: the step kernel keeps one score per
+ * key in 64 KiB of LDS); outside that, or tracks < 1: FLOPE_EINVAL.  A failed allocation is FLOPE_EHIP and the message names the
+ * size.  A handle may have several states, each with its own cache; they share the handle's scratch buffers, as forwards do, and
+ * end with the handle: after flope_tf_destroy every call on a state but _close returns FLOPE_ESTATE.
+ * How many tokens a track holds (its position) lives on the host, in the state: _step and _prefill check it there and advance it
+ * when they enqueue, _reset only clears it (stale cache rows are never read), _position returns it.  So the CALLS ON ONE STATE MUST
+ * BE ORDERED ON ONE STREAM BY THE CALLER, and forwards of the handle that run between them on that stream or a synchronised one.
+ *   _step     x_dev float32 [n, input_dim] -> y_dev float32 [n, out_dim]: row r is the next token of track tracks_host[r] (NULL: n ==
+ *             tracks and row r is track r) and comes back as the encoder's output at that token, which attends to the track's tokens so
+ *             far and itself.  Tracks distinct and in range, 1 <= n <= min(tracks, max_tokens), no track already at capacity:
+ *             otherwise FLOPE_EINVAL with the offending index in the message, nothing enqueued and no position advanced.  Launches
+ *             what flope_tf_forward launches for n rows under the handle's options (the same linear and LayerNorm kernels), with
+ *             tf_attn_step in place of the attention kernel: one wave per (row, head) computes tf_attn_generic's causal row over
+ *             the cache in that kernel's summation order and appends the token's k and v.  Where the forward's attention is
+ *             FLOPE_TF_ATTN_GENERIC for the track's length, y_dev's row is, bit for bit, row `position` of the causal forward of the
+ *             track so far; elsewhere (tf_attn_f32m, tf_attn_mfma, tf_attn_tiled) the attention order differs and the rows agree
+ *             within those kernels' tolerances.  Neither reads nor writes option "causal" or what flope_tf_last_forward reports.
+ *   _prefill  loads n tracks' histories: the causal ragged forward of x_dev [n, seq_len, input_dim] with lengths_host (NULL: all
+ *             seq_len) -> y_dev [n, seq_len, out_dim], the bits of flope_tf_forward_varlen under "causal" = 1 (always as the
+ *             launch sequence; "fused" gives the same bits), which also copies every layer's k and v of the valid rows into cache
+ *             rows 0 .. length - 1 of track tracks_host[b] (NULL as above) and sets those tracks' positions to their lengths,
+ *             whatever they held.  Limits of flope_tf_forward_varlen, lengths <= capacity, tracks as for _step.  Option "causal"
+ *             is as it was when the call returns.
+ *   _reset    positions of the n tracks of tracks_host (NULL: every track, n ignored) back to 0; enqueues nothing. */
+typedef struct flope_tf_stream_s* flope_tf_stream;
+int flope_tf_stream_open(flope_tf_handle h, int tracks, int capacity, flope_tf_stream* out);
+int flope_tf_stream_close(flope_tf_stream s);
+int flope_tf_stream_reset(flope_tf_stream s, int n, const int* tracks_host);
+/* tokens held by `track`, or < 0 */
+int flope_tf_stream_position(flope_tf_stream s, int track);
+int flope_tf_stream_step(flope_tf_stream s, const float* x_dev, int n, const int* tracks_host, float* y_dev, void* stream);
+int flope_tf_stream_prefill(flope_tf_stream s, const float* x_dev, int n, int seq_len, const int* lengths_host, const int* tracks_host,
+                            float* y_dev, void* stream);
 
 /* ---- YOLO11-seg detector front end ---------------------------------------------------
  * Replaces `self.yolo = YOLO(yolo_path)` (sunflower/predictor/fast_pose_predictor.py:36) and the
