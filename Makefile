@@ -15,12 +15,13 @@ HARNESS_TF_VARLEN := tests/host_harness/libflope_host_tf_varlen.so
 HARNESS_TF_FUSED := tests/host_harness/libflope_host_tf_fused.so
 HARNESS_TF_CAUSAL := tests/host_harness/libflope_host_tf_causal.so
 HARNESS_TF_STREAM := tests/host_harness/libflope_host_tf_stream.so
+HARNESS_TF_WINDOW := tests/host_harness/libflope_host_tf_window.so
 SRCS     := $(wildcard $(CSRC)/*.hip)
 OBJS     := $(patsubst $(CSRC)/%.hip,$(OBJDIR)/%.o,$(SRCS))
 HDRS     := $(wildcard $(CSRC)/*.h) include/flope_amd.h
 HIPFLAGS := --offload-arch=$(ARCH) -O3 -fPIC -std=c++17 -Wno-unused-value -Iinclude
 
-all: $(LIB) $(HARNESS) $(HARNESS_F32M) $(HARNESS_F32M_KSPLIT) $(HARNESS_GUARD) $(HARNESS_TF_F32M) $(HARNESS_TF_ATTN) $(HARNESS_TF_VARLEN) $(HARNESS_TF_FUSED) $(HARNESS_TF_CAUSAL) $(HARNESS_TF_STREAM)
+all: $(LIB) $(HARNESS) $(HARNESS_F32M) $(HARNESS_F32M_KSPLIT) $(HARNESS_GUARD) $(HARNESS_TF_F32M) $(HARNESS_TF_ATTN) $(HARNESS_TF_VARLEN) $(HARNESS_TF_FUSED) $(HARNESS_TF_CAUSAL) $(HARNESS_TF_STREAM) $(HARNESS_TF_WINDOW)
 
 $(OBJDIR)/%.o: $(CSRC)/%.hip $(HDRS)
 	@mkdir -p $(OBJDIR)
@@ -68,7 +69,12 @@ $(HARNESS_TF_CAUSAL): tests/host_harness/harness_tf_causal.cpp $(CSRC)/tf_attn_p
 
 # the streaming forward's planner: argument checks of step / prefill / reset, the capacity limit, the launches of tf_attn_step and
 # tf_cache_fill (tests/test_tf_stream_host.py, tests/test_gpu_tf_stream.py)
-$(HARNESS_TF_STREAM): tests/host_harness/harness_tf_stream.cpp $(CSRC)/tf_encoder_stream.h
+$(HARNESS_TF_STREAM): tests/host_harness/harness_tf_stream.cpp $(CSRC)/tf_encoder_stream.h $(CSRC)/tf_attn_plan.h include/flope_amd.h
+	g++ -O2 -fPIC -shared -std=c++17 -I$(CSRC) -o $@ $<
+
+# sliding-window causal attention and the ring cache of a windowed stream state: the first visible key, the slot of a position, the
+# row runs of a step, the rows a fill writes, the windowed checks (tests/test_tf_window_host.py, tests/test_gpu_tf_window.py)
+$(HARNESS_TF_WINDOW): tests/host_harness/harness_tf_window.cpp $(CSRC)/tf_encoder_stream.h $(CSRC)/tf_attn_plan.h include/flope_amd.h
 	g++ -O2 -fPIC -shared -std=c++17 -I$(CSRC) -o $@ $<
 
 # conditioning figure and flag predicate of the guarded mode (tests/test_guard_host.py)
@@ -96,7 +102,7 @@ dbg: $(DBGOBJS)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $(DBGDIR)/libflope_amd_dbg.so $(DBGOBJS)
 
 clean:
-	rm -rf build $(LIB) $(HARNESS) $(HARNESS_F32M) $(HARNESS_F32M_KSPLIT) $(HARNESS_GUARD) $(HARNESS_TF_F32M) $(HARNESS_TF_ATTN) $(HARNESS_TF_VARLEN) $(HARNESS_TF_FUSED) $(HARNESS_TF_CAUSAL) $(HARNESS_TF_STREAM)
+	rm -rf build $(LIB) $(HARNESS) $(HARNESS_F32M) $(HARNESS_F32M_KSPLIT) $(HARNESS_GUARD) $(HARNESS_TF_F32M) $(HARNESS_TF_ATTN) $(HARNESS_TF_VARLEN) $(HARNESS_TF_FUSED) $(HARNESS_TF_CAUSAL) $(HARNESS_TF_STREAM) $(HARNESS_TF_WINDOW)
 
 # stand-alone measurement programs used by tools/collect_profiles.sh and DESIGN.md section 9 (not part of the library)
 TOOLBINS := build/fetch_calib build/launch_floor build/loop_probe build/loop_probe32 build/dma_issue_probe

@@ -108,6 +108,7 @@ SIGNATURES = {
     "flope_tf_forward_plan": (_I, [_P, _I, _I, C.POINTER(_I)]),
     "flope_tf_last_forward": (_I, [_P]),
     "flope_tf_stream_open": (_I, [_P, _I, _I, C.POINTER(_P)]),
+    "flope_tf_stream_open_window": (_I, [_P, _I, _I, _I, C.POINTER(_P)]),
     "flope_tf_stream_close": (_I, [_P]),
     "flope_tf_stream_reset": (_I, [_P, _I, C.POINTER(_I)]),
     "flope_tf_stream_position": (_I, [_P, _I]),

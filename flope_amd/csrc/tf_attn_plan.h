@@ -71,6 +71,14 @@ constexpr bool tf_causal_step_taken(int q0, int kb) { return kb <= q0 + 31; }
 // tf_attn_f32m: 16-key tiles the workgroup of queries q0 .. q0 + 15 walks in its score and value passes
 constexpr int tf_causal_f32m_tiles(int q0, int L) { return (tf_causal_keys(q0, 16, L) + 15) / 16; }
 
+// ---- sliding-window causal attention (option "window") ------------------------------------------------------------------
+// With causal and a window W >= 1, query i attends to keys i - W < j <= i of its own sequence; W = 0: no window.  First visible key
+// of query i: max(0, i + 1 - W).  tf_attn_row, tf_attn_step_row and tests/host_harness/harness_tf_window.cpp call this
+// (tests/test_tf_window_host.py holds it against brute force); the last visible key stays tf_causal_keys(i, 1, L) - 1 = i.
+constexpr int tf_window_lo(int i, int W) { return W > 0 && i >= W ? i - W + 1 : 0; }
+// ... and how many keys that is: min(i + 1, W), i + 1 without a window
+constexpr int tf_window_keys(int i, int W) { return i - tf_window_lo(i, W) + 1; }
+
 // ---- ragged batches (flope_tf_forward_varlen / flope_tf_attention_varlen) ------------------------------------------
 // A batch of B sequences of lengths[b] tokens (1 <= lengths[b] <= L) lives in the handle as T = sum lengths packed rows;
 // sequence b starts at packed row off[b], off[B] = T.

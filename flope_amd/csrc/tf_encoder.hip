@@ -15,9 +15,12 @@
 // FLOPE_DT_F32 with option fused = 1: a forward whose longest sequence fits 64 KiB of LDS is ONE launch (tf_fused_f32), same bits.
 // Option causal = 1 (any dtype): query i attends to keys j <= i of its own sequence -- the CAUSAL instantiation of whichever attention
 // kernel the shape picks, and of tf_fused_f32; key blocks above the diagonal are skipped, not loaded and masked.
+// Option window = W > 0 (with causal, any dtype): query i attends to keys i - W < j <= i -- tf_attn_generic's WINDOW instantiation for every
+// shape, the keys below the window not loaded either; never the single launch.
 // flope_tf_stream_* (any dtype): one new token per track instead of the causal forward again -- the same launch sequence at one row per
 // track, with tf_attn_step over a per-track cache of every layer's keys and values where the forward has its attention kernel
-// (the checks and launch shapes are in tf_encoder_stream.h).
+// (the checks and launch shapes are in tf_encoder_stream.h).  flope_tf_stream_open_window: the same over a ring cache
+// with sliding-window attention, never full.
 #include "../../include/flope_amd.h"
 #include "common.h"
 #include "host_pack.h"
@@ -121,12 +124,19 @@ __device__ __forceinline__ void tf_layernorm_row(const T* x, T* y, const float* 
 // ld elements (q | k | v at 0, d, 2 d); s: this wave's score row (L floats of LDS); orow: the dh outputs of the query.
 // CAUSAL (all four attention kernels): query i attends to keys j <= i of its own sequence.  Here the three key loops end
 // at i + 1 instead of L: the keys above the diagonal are never loaded.
-template <typename T, bool CAUSAL = false>
-__device__ __forceinline__ void tf_attn_row(const T* base, size_t ld, T* orow, float* s, int i, int L, int d, int dh, float scale, int lane) {
+// WINDOW (with CAUSAL, tf_attn_generic only): query i attends to keys lo .. i, lo = tf_window_lo(i, W) = max(0, i + 1 - W);
+// the three key loops start at lo, so the keys below the window are never loaded either.  The order, fixed here once: lane l takes keys
+// lo + l, lo + l + 64, ..; the value chain runs j = lo .. i from 0.f.  With lo = 0 (no window, or i < W) that is the order above.
+template <typename T, bool CAUSAL = false, bool WINDOW = false>
+__device__ __forceinline__ void tf_attn_row(const T* base, size_t ld, T* orow, float* s, int i, int L, int d, int dh, float scale, int lane,
+                                            int W = 0) {
+  static_assert(CAUSAL || !WINDOW, "a window without causal has no meaning");
   if constexpr (CAUSAL) L = flope_tf_plan::tf_causal_keys(i, 1, L);      // kend = i + 1
+  int lo = 0;
+  if constexpr (WINDOW) lo = flope_tf_plan::tf_window_lo(i, W);
   const T* q = base + (size_t)i * ld;
   float mx = -INFINITY;
-  for (int j = lane; j < L; j += 64) {
+  for (int j = lo + lane; j < L; j += 64) {
     const T* k = base + (size_t)j * ld + d;
     float a = 0.f;
     for (int c = 0; c < dh; ++c) a = fmaf(to_f32<T>(q[c]), to_f32<T>(k[c]), a);
@@ -136,13 +146,13 @@ __device__ __forceinline__ void tf_attn_row(const T* base, size_t ld, T* orow, f
   }
   mx = wave_max(mx);
   float sum = 0.f;
-  for (int j = lane; j < L; j += 64) { const float p = expf(s[j] - mx); s[j] = p; sum += p; }
+  for (int j = lo + lane; j < L; j += 64) { const float p = expf(s[j] - mx); s[j] = p; sum += p; }
   sum = wave_sum(sum);
   __builtin_amdgcn_wave_barrier();
   const float inv = 1.f / sum;
   for (int c = lane; c < dh; c += 64) {
     float o = 0.f;
-    for (int j = 0; j < L; ++j) o = fmaf(s[j], to_f32<T>(base[(size_t)j * ld + 2 * d + c]), o);
+    for (int j = lo; j < L; ++j) o = fmaf(s[j], to_f32<T>(base[(size_t)j * ld + 2 * d + c]), o);
     orow[c] = from_f32<T>(o * inv);
   }
   __builtin_amdgcn_wave_barrier();
@@ -309,8 +319,10 @@ __global__ void tf_layernorm_vec(const T* in, T* out, const float* w, const floa
 // off[b] .. off[b + 1] - 1 and the L argument is the longest length, which sized the grid and the LDS; the kernel takes its own
 // sequence's length for L, so every bound, mask and clamp below stays inside the sequence (row off[b] + L is the next sequence's
 // first key, not padding).  The fixed-length instantiations (VARLEN = false, off unused) compile from the source they had.
-template <typename T, bool VARLEN = false, bool CAUSAL = false>
-__global__ void tf_attn_generic(const T* qkv, T* out, int L, int d, int H, const int* __restrict__ off) {
+// WINDOW (this kernel only): keys i - W < j <= i; W is read by those instantiations alone and sits where the argument
+// block had four bytes of padding, so every other argument keeps its offset.
+template <typename T, bool VARLEN = false, bool CAUSAL = false, bool WINDOW = false>
+__global__ void tf_attn_generic(const T* qkv, T* out, int L, int d, int H, int W, const int* __restrict__ off) {
   extern __shared__ float sc[];                 // [waves][L]
   const int nw = blockDim.x >> 6, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int b = blockIdx.x / H, h = blockIdx.x - b * H, dh = d / H;
@@ -320,7 +332,7 @@ __global__ void tf_attn_generic(const T* qkv, T* out, int L, int d, int H, const
   float* s = sc + (size_t)wave * L;
   const T* base = VARLEN ? qkv + row0 * 3 * d + h * dh : qkv + (size_t)b * L * 3 * d + h * dh;
   for (int i = blockIdx.y * nw + wave; i < L; i += gridDim.y * nw)
-    tf_attn_row<T, CAUSAL>(base, (size_t)3 * d, out + ((VARLEN ? row0 : (size_t)b * L) + i) * d + h * dh, s, i, L, d, dh, scale, lane);
+    tf_attn_row<T, CAUSAL, WINDOW>(base, (size_t)3 * d, out + ((VARLEN ? row0 : (size_t)b * L) + i) * d + h * dh, s, i, L, d, dh, scale, lane, W);
 }
 
 // ---- streaming step (flope_tf_stream_*) ----------------------------------------------------------------------------
@@ -363,15 +375,34 @@ template <typename T, bool VEC> struct TfSlice {
 // in front of their fmafs, where tf_attn_row has one scalar load per trip; each of these would change the loops tf_attn_generic
 // and tf_fused_f32 compile from.
 constexpr int kTfStepUnroll = 16;
-template <typename T, bool VEC>
+// (float16)(a * b) in ONE rounding, as bits: what the compiler makes of tf_attn_row's `from_f32<f16_t>(o * inv)`, one v_fma_mixlo_f16.
+// A packed store of two such products (v_mul_f32, then v_cvt_pk_f16_f32) rounds to float32 first and to float16 second, and the two
+// roundings differ from the one in the last bit of about one element in 2^13 -- which is what the VEC float16 store of tf_attn_step_row
+// compiled to, against DESIGN.md 25's bit contract with tf_attn_row (no test there had a shape that showed it).  That store spells the
+// instruction out, so that its bits do not hang on which of the two forms the compiler picks.
+__device__ __forceinline__ unsigned tf_mul_f16_bits(float a, float b) {
+  unsigned r = 0;
+  asm("v_fma_mixlo_f16 %0, %1, %2, 0" : "+v"(r) : "v"(a), "v"(b));
+  return r & 0xffffu;
+}
+// WINDOW (a windowed state): tf_attn_row<T, true, true> for query pos instead -- keys lo .. pos, lo = tf_window_lo(pos, W),
+// lane l takes keys lo + l, lo + l + 64, .., the value chain runs j = lo .. pos from 0.f -- over a ring: key j < pos lives in cache
+// row j % capacity, the score of key j in s[j - lo] (at most W floats; the loops below count j from key lo).  The pos - lo cached keys are consecutive rows from lo % capacity
+// on that wrap at most once (pos - lo < W <= capacity), so a key's row is one add and one conditional subtract in the score pass,
+// and the value pass walks two contiguous runs of rows, each as the unrolled loop below; no modulo per key.
+template <typename T, bool VEC, bool WINDOW = false>
 __device__ __forceinline__ void tf_attn_step_row(const T* tok, const T* kv, size_t ld, T* orow, float* s, int pos, int d, int dh, float scale,
-                                                 int lane) {
+                                                 int lane, int capacity = 0, int W = 0) {
   typedef TfSlice<T, VEC> Sl;
   constexpr int VE = Sl::VE;
-  const int L = pos + 1;
+  int lo = 0, slo = 0;                            // first visible key and its cache row
+  if constexpr (WINDOW) { lo = flope_tf_plan::tf_window_lo(pos, W); slo = flope_tf_plan::tf_stream_slot(lo, capacity); }
+  const int nk = pos - lo, L = nk + 1;            // cached keys, visible keys; j below counts from key lo (an absolute pos may be near INT_MAX)
   float mx = -INFINITY;
   for (int j = lane; j < L; j += 64) {
-    const T* k = j == pos ? tok + d : kv + (size_t)j * ld;
+    int row = j;
+    if constexpr (WINDOW) { row = slo + j; if (row >= capacity) row -= capacity; }
+    const T* k = j == nk ? tok + d : kv + (size_t)row * ld;
     float a = 0.f;
     for (int c = 0; c < dh; c += VE) {
       Sl qv, kx;
@@ -395,29 +426,64 @@ __device__ __forceinline__ void tf_attn_step_row(const T* tok, const T* kv, size
     float o[VE];
 #pragma unroll
     for (int e = 0; e < VE; ++e) o[e] = 0.f;
-    int j = 0;
-    for (; j + kTfStepUnroll <= pos; j += kTfStepUnroll) {
-      Sl vv[kTfStepUnroll];
+    // cnt consecutive cache rows from vr on, their probabilities from sp on, kTfStepUnroll loads in flight: the chain goes on in key order
+    auto run = [&](const T* vr, const float* sp, int cnt) {
+      int j = 0;
+      for (; j + kTfStepUnroll <= cnt; j += kTfStepUnroll) {
+        Sl vv[kTfStepUnroll];
 #pragma unroll
-      for (int u = 0; u < kTfStepUnroll; ++u) vv[u].load(v + (size_t)(j + u) * ld);
+        for (int u = 0; u < kTfStepUnroll; ++u) vv[u].load(vr + (size_t)(j + u) * ld);
 #pragma unroll
-      for (int u = 0; u < kTfStepUnroll; ++u) {
-        const float p = s[j + u];
+        for (int u = 0; u < kTfStepUnroll; ++u) {
+          const float p = sp[j + u];
 #pragma unroll
-        for (int e = 0; e < VE; ++e) o[e] = fmaf(p, vv[u].f[e], o[e]);
+          for (int e = 0; e < VE; ++e) o[e] = fmaf(p, vv[u].f[e], o[e]);
+        }
       }
-    }
-    for (; j < pos; ++j) {
-      Sl vv;
-      vv.load(v + (size_t)j * ld);
+      for (; j < cnt; ++j) {
+        Sl vv;
+        vv.load(vr + (size_t)j * ld);
 #pragma unroll
-      for (int e = 0; e < VE; ++e) o[e] = fmaf(s[j], vv.f[e], o[e]);
+        for (int e = 0; e < VE; ++e) o[e] = fmaf(sp[j], vv.f[e], o[e]);
+      }
+    };
+    if constexpr (WINDOW) {
+      const int first = flope_tf_plan::tf_stream_run0(slo, nk, capacity);      // keys lo .. pos - 1: rows slo .., then rows 0 ..
+      run(v + (size_t)slo * ld, s, first);
+      run(v, s + first, nk - first);
+    } else {                                      // one run of rows 0 .. pos - 1, spelled out: these instantiations compile from the source they had
+      int j = 0;
+      for (; j + kTfStepUnroll <= pos; j += kTfStepUnroll) {
+        Sl vv[kTfStepUnroll];
+#pragma unroll
+        for (int u = 0; u < kTfStepUnroll; ++u) vv[u].load(v + (size_t)(j + u) * ld);
+#pragma unroll
+        for (int u = 0; u < kTfStepUnroll; ++u) {
+          const float p = s[j + u];
+#pragma unroll
+          for (int e = 0; e < VE; ++e) o[e] = fmaf(p, vv[u].f[e], o[e]);
+        }
+      }
+      for (; j < pos; ++j) {
+        Sl vv;
+        vv.load(v + (size_t)j * ld);
+#pragma unroll
+        for (int e = 0; e < VE; ++e) o[e] = fmaf(s[j], vv.f[e], o[e]);
+      }
     }
     Sl vv;
     vv.load(tok + 2 * d + c);                     // the value of position pos: from the qkv row, never from the cache row stored above
+    if constexpr (VEC && std::is_same<T, f16_t>::value) {      // one rounding per element, as tf_attn_row's store (tf_mul_f16_bits)
+      u32x4 w;
 #pragma unroll
-    for (int e = 0; e < VE; ++e) vv.f[e] = fmaf(s[pos], vv.f[e], o[e]) * inv;
-    vv.store(orow + c);
+      for (int e = 0; e < VE; e += 2)
+        w[e / 2] = tf_mul_f16_bits(fmaf(s[nk], vv.f[e], o[e]), inv) | (tf_mul_f16_bits(fmaf(s[nk], vv.f[e + 1], o[e + 1]), inv) << 16);
+      *(u32x4*)(orow + c) = w;
+    } else {
+#pragma unroll
+      for (int e = 0; e < VE; ++e) vv.f[e] = fmaf(s[nk], vv.f[e], o[e]) * inv;
+      vv.store(orow + c);
+    }
   }
   __builtin_amdgcn_wave_barrier();
 }
@@ -427,33 +493,46 @@ __device__ __forceinline__ void tf_attn_step_row(const T* tok, const T* kv, size
 // softmax(q K^T / sqrt(dh)) V over keys 0 .. pos to att [n][d].  tab: (track, pos) per row.  smax: floats of a wave's score row
 // (the call's largest pos + 1).  A row whose table entry is no track, no row of the cache or past the score row is left alone:
 // nothing is written outside the track's capacity rows, whatever the table holds.
-template <typename T, bool VEC>
+// WINDOW: pos is absolute and unbounded, the cache a ring -- the slice goes to row pos % capacity, attention is over keys
+// tf_window_lo(pos, W) .. pos, smax the call's largest visible key count (<= W).  The overwrite is safe: row pos % capacity held key
+// pos - capacity <= pos - W, which is outside every window that includes pos, so no wave of this launch reads it (the launch's rows
+// are distinct tracks, and the heads of one row touch distinct columns).  Left alone: a row whose track is out of range, whose pos is
+// negative or whose visible keys exceed the score row; pos % capacity is a row of the track whatever else the table holds.
+template <typename T, bool VEC, bool WINDOW = false>
 __global__ __launch_bounds__(256) void tf_attn_step(const T* __restrict__ qkv, T* cache, T* __restrict__ att, const int* __restrict__ tab, int n,
-                                                    int d, int H, int tracks, int capacity, int smax) {
+                                                    int d, int H, int tracks, int capacity, int smax, int W) {
   extern __shared__ __attribute__((aligned(16))) float sc[];     // [waves][smax]
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int it = blockIdx.x * flope_tf_plan::kTfStepWaves + wave;
   if (it >= n * H) return;
   const int r = it / H, h = it - r * H, dh = d / H;
   const int track = tab[2 * r], pos = tab[2 * r + 1];
-  if ((unsigned)track >= (unsigned)tracks || (unsigned)pos >= (unsigned)capacity || pos >= smax) return;
+  int slot = pos;                                                // the cache row of the token
+  if constexpr (WINDOW) {
+    if ((unsigned)track >= (unsigned)tracks || pos < 0 || W < 1 || W > capacity || flope_tf_plan::tf_window_keys(pos, W) > smax) return;
+    slot = flope_tf_plan::tf_stream_slot(pos, capacity);
+  } else {
+    if ((unsigned)track >= (unsigned)tracks || (unsigned)pos >= (unsigned)capacity || pos >= smax) return;
+  }
   const float scale = 1.f / sqrtf((float)dh);
   const size_t ld = (size_t)2 * d;
   const T* tok = qkv + (size_t)r * 3 * d + h * dh;
   T* kv = cache + (size_t)track * capacity * ld + h * dh;
   constexpr int VE = TfSlice<T, VEC>::VE;
-  for (int c = lane * VE; c < 2 * dh; c += 64 * VE) {            // k slice | v slice of the token -> cache row pos
+  for (int c = lane * VE; c < 2 * dh; c += 64 * VE) {            // k slice | v slice of the token -> cache row pos (WINDOW: pos % capacity)
     const int col = c < dh ? c : c - dh + d;
-    if constexpr (VEC) *(u32x4*)(kv + pos * ld + col) = *(const u32x4*)(tok + d + col);
-    else kv[pos * ld + col] = tok[d + col];
+    if constexpr (VEC) *(u32x4*)(kv + slot * ld + col) = *(const u32x4*)(tok + d + col);
+    else kv[slot * ld + col] = tok[d + col];
   }
-  tf_attn_step_row<T, VEC>(tok, kv, ld, att + (size_t)r * d + h * dh, sc + (size_t)wave * smax, pos, d, dh, scale, lane);
+  tf_attn_step_row<T, VEC, WINDOW>(tok, kv, ld, att + (size_t)r * d + h * dh, sc + (size_t)wave * smax, pos, d, dh, scale, lane, capacity, W);
 }
 
 // prefill: the k | v columns (d .. 3 d) of the valid packed rows of qkv [T][3 d] -> rows 0 .. len - 1 of each sequence's track in
 // cache [tracks][capacity][2 d].  off: the ragged batch's offsets; trk: the track of sequence b.  V: u32x4 (dv = d / elements per 16
 // bytes) or the element type (dv = d).  A sequence whose entry is no track, and rows past capacity, are skipped.
-template <typename V>
+// WINDOW (a ring): token i of a sequence of len tokens goes to row i % capacity, and only the last min(len, capacity) tokens go
+// (tf_stream_fill_writes) -- the earlier ones share their rows with those, and two threads would write one address.
+template <typename V, bool WINDOW = false>
 __global__ void tf_cache_fill(const V* __restrict__ qkv, V* __restrict__ cache, const int* __restrict__ off, const int* __restrict__ trk,
                               int max_len, int dv, int tracks, int capacity, size_t total) {
   const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -461,8 +540,14 @@ __global__ void tf_cache_fill(const V* __restrict__ qkv, V* __restrict__ cache, 
   const size_t r = idx / (2 * dv);
   const int c = (int)(idx - r * (2 * dv)), b = (int)(r / max_len), i = (int)(r - (size_t)b * max_len);
   const int o = off[b], t = trk[b];
-  if (i >= off[b + 1] - o || i >= capacity || (unsigned)t >= (unsigned)tracks) return;
-  cache[((size_t)t * capacity + i) * 2 * dv + c] = qkv[(size_t)(o + i) * 3 * dv + dv + c];
+  if constexpr (WINDOW) {
+    const int len = off[b + 1] - o;
+    if (i >= len || !flope_tf_plan::tf_stream_fill_writes(i, len, capacity) || (unsigned)t >= (unsigned)tracks) return;
+    cache[((size_t)t * capacity + flope_tf_plan::tf_stream_slot(i, capacity)) * 2 * dv + c] = qkv[(size_t)(o + i) * 3 * dv + dv + c];
+  } else {
+    if (i >= off[b + 1] - o || i >= capacity || (unsigned)t >= (unsigned)tracks) return;
+    cache[((size_t)t * capacity + i) * 2 * dv + c] = qkv[(size_t)(o + i) * 3 * dv + dv + c];
+  }
 }
 
 // ---- MFMA linear: Y[128-token tile][128-feature tile], K walked in 64-wide chunks ----------------------------
@@ -1267,6 +1352,7 @@ struct flope_tf_encoder {
   int opt_tiled = 0;                         // 16-bit handles: 1 = tf_attn_tiled where the choice would be tf_attn_generic, 2 = also in place of tf_attn_mfma (stored and ignored by float32 handles)
   int opt_fused = 0;                         // 1: a float32 forward that tf_fused_ok takes runs as one launch of tf_fused_f32 (stored and ignored by 16-bit handles and while opt_f32m)
   int opt_causal = 0;                        // 1: query i attends to keys j <= i of its own sequence, in every attention launch and in tf_fused_f32
+  int opt_window = 0;                        // W > 0 (honoured with opt_causal = 1, refused without): keys i - W < j <= i, always on tf_attn_generic, never tf_fused_f32
   int last_fwd = FLOPE_TF_FWD_LAUNCHES;       // what the last forward that enqueued anything ran (flope_tf_last_forward)
   const float** fused_tab = nullptr;         // device table of the float32 weight arrays tf_fused_f32 reads (FLOPE_DT_F32 handles, built by flope_tf_load_weights)
   int opt_f32m_lds = 0;                      // KiB of untouched LDS a tf_linear_f32m launch reserves (> 80: one workgroup per CU)
@@ -1291,6 +1377,7 @@ struct flope_tf_encoder {
 struct flope_tf_stream_s {
   flope_tf_encoder* e = nullptr;             // nullptr once the handle is destroyed: every call but close then fails with FLOPE_ESTATE
   int tracks = 0, capacity = 0;
+  int window = 0;                            // 0: a linear cache, full at capacity; W >= 1: a ring, row p % capacity, keys p - W < j <= p
   void* cache = nullptr;                     // [num_layers][tracks][capacity][2 model_dim] in the handle's dtype, a row is k | v
   int* tab = nullptr;                        // device table of one call: step (track, position) per row, prefill the track per sequence
   std::vector<int> pos, tab_host;            // tokens held per track; the pageable copy tab is uploaded from
@@ -1427,14 +1514,23 @@ int launch_layernorm(flope_tf_encoder* e, const void* in, void* out, const float
 // One attention launch: softmax(q k^T / sqrt(head_dim)) v per head.  off == nullptr: qkv [B][L][3 d] -> att [B][L][d].  Otherwise a
 // ragged batch: packed qkv [T][3 d] -> att [T][d], sequence b = rows off[b] .. off[b + 1] - 1 (off: the handle's device table), L its
 // longest length, the VARLEN instantiations.  Option causal: the CAUSAL instantiations of the same pick.  One kernel for the whole batch, the one tf_attn_plan.h picks for L; grid, block and LDS
-// from tf_attn_varlen_launch in both cases.  Returns the kernel's FLOPE_TF_ATTN_* id, or < 0.
+// from tf_attn_varlen_launch in both cases.  Option window (with causal): the override sits here -- tf_attn_generic's WINDOW
+// instantiation whatever tf_attn_pick would say, launched as the generic kernel always is.  Returns the kernel's FLOPE_TF_ATTN_* id, or < 0.
 template <typename T>
 int launch_attention(flope_tf_encoder* e, const void* qkv, void* att, int B, int L, const int* off, hipStream_t st) {
   using namespace flope_tf_plan;
   const int d = e->d, H = e->H, dh = d / H;
-  const int pick = tf_attn_pick(e->dtype, dh, L, e->opt_generic, e->opt_f32m, e->opt_tiled, !(((uintptr_t)qkv | (uintptr_t)att) & 15));
+  const bool window = e->opt_causal && e->opt_window > 0;
+  const int pick = window ? (int)FLOPE_TF_ATTN_GENERIC
+                          : tf_attn_pick(e->dtype, dh, L, e->opt_generic, e->opt_f32m, e->opt_tiled, !(((uintptr_t)qkv | (uintptr_t)att) & 15));
   const TfAttnLaunch l = tf_attn_varlen_launch(pick, dh, B, H, L);
   const dim3 grid(l.grid_x, l.grid_y), block(l.block);
+  if (window) {
+    if (off) hipLaunchKernelGGL((tf_attn_generic<T, true, true, true>), grid, block, l.lds, st, (const T*)qkv, (T*)att, L, d, H, e->opt_window, off);
+    else hipLaunchKernelGGL((tf_attn_generic<T, false, true, true>), grid, block, l.lds, st, (const T*)qkv, (T*)att, L, d, H, e->opt_window, off);
+    TF_HIP(e, hipGetLastError());
+    return pick;
+  }
   auto launch = [&](auto varlen, auto causal) {
     constexpr bool VL = decltype(varlen)::value, CA = decltype(causal)::value;
     if constexpr (!std::is_same<T, float>::value) {
@@ -1458,7 +1554,7 @@ int launch_attention(flope_tf_encoder* e, const void* qkv, void* att, int B, int
       }
     }
     if (pick == FLOPE_TF_ATTN_GENERIC)
-      hipLaunchKernelGGL((tf_attn_generic<T, VL, CA>), grid, block, l.lds, st, (const T*)qkv, (T*)att, L, d, H, off);
+      hipLaunchKernelGGL((tf_attn_generic<T, VL, CA>), grid, block, l.lds, st, (const T*)qkv, (T*)att, L, d, H, 0, off);
   };
   if (e->opt_causal) {                           // kernel, grid, block and LDS are those of the option at 0
     if (off) launch(std::true_type{}, std::true_type{}); else launch(std::false_type{}, std::true_type{});
@@ -1544,9 +1640,9 @@ int run_forward(flope_tf_encoder* e, const float* x, int B, int L, float* y, hip
   });
 }
 
-// Option fused: whether a float32 forward whose longest sequence has Lmax tokens runs as the single launch
+// Option fused: whether a float32 forward whose longest sequence has Lmax tokens runs as the single launch (never under option window)
 bool tf_fused_pick(const flope_tf_encoder* e, int Lmax) {
-  return e->fused_tab && flope_tf_plan::tf_fused_ok(e->dtype, e->opt_fused, e->opt_f32m, e->in_dim, e->d, e->ff, Lmax);
+  return e->fused_tab && e->opt_window == 0 && flope_tf_plan::tf_fused_ok(e->dtype, e->opt_fused, e->opt_f32m, e->in_dim, e->d, e->ff, Lmax);
 }
 
 // ... and that launch: x [B][L][in] -> y [B][L][out], one workgroup per sequence.  off == nullptr: every sequence has L = Lmax tokens;
@@ -1572,6 +1668,13 @@ int tf_forward(flope_tf_encoder* e, const float* x, int B, int L, float* y, hipS
     return rc;
   }
   return tf_by_dtype(e, [&](auto tag) { return run_forward<typename decltype(tag)::type>(e, x, B, L, y, st, rg); });
+}
+
+// Option window is honoured with causal only: every entry point that runs or plans a forward or an attention of the handle's options refuses the pair (window > 0, causal = 0)
+int tf_check_window(flope_tf_encoder* e, const std::string& who) {
+  if (e->opt_window > 0 && !e->opt_causal)
+    return tf_fail(e, FLOPE_EINVAL, who + ": option window = " + std::to_string(e->opt_window) + " needs option causal = 1 (a window without causal is refused)");
+  return 0;
 }
 
 // The argument checks of a fixed-length forward under the caller's name (flope_tf_forward, and flope_tf_forward_plan, which has no
@@ -1710,6 +1813,10 @@ extern "C" int flope_tf_set_option(flope_tf_handle e, const char* name, int valu
     if (value < 0 || value > 1) return tf_fail(e, FLOPE_EINVAL, "flope_tf_set_option: causal is 0 or 1");
     const int old = e->opt_causal; e->opt_causal = value; return old;
   }
+  if (!strcmp(name, "window")) {
+    if (value < 0) return tf_fail(e, FLOPE_EINVAL, "flope_tf_set_option: window is 0 (none) or a positive key count");
+    const int old = e->opt_window; e->opt_window = value; return old;
+  }
   if (!strcmp(name, "f32mlds")) {
     if (value < 0 || value > 160) return tf_fail(e, FLOPE_EINVAL, "flope_tf_set_option: f32mlds is 0 .. 160 (KiB)");
     const int old = e->opt_f32m_lds; e->opt_f32m_lds = value; return old;
@@ -1805,12 +1912,14 @@ extern "C" int flope_tf_forward(flope_tf_handle e, const float* x_dev, int batch
   bool empty;
   int rc;
   if ((rc = tf_check_forward(e, "flope_tf_forward", batch, seq_len, x_dev && y_dev, &empty)) || empty) return rc;
+  if ((rc = tf_check_window(e, "flope_tf_forward"))) return rc;
   TF_HIP(e, hipSetDevice(e->device));
   return tf_forward(e, x_dev, batch, seq_len, y_dev, (hipStream_t)stream, nullptr);
 }
 
 extern "C" int flope_tf_attention(flope_tf_handle e, const void* qkv_dev, int batch, int seq_len, void* out_dev, void* stream) {
   if (!e) return tf_fail(nullptr, FLOPE_EINVAL, "flope_tf_attention: NULL handle");
+  if (int rc = tf_check_window(e, "flope_tf_attention")) return rc;
   if (batch < 1 || seq_len < 1) return tf_fail(e, FLOPE_EINVAL, "flope_tf_attention: non-positive size");
   if (!qkv_dev || !out_dev) return tf_fail(e, FLOPE_EINVAL, "flope_tf_attention: NULL buffer");
   if ((long long)batch * seq_len > e->max_tokens)
@@ -1882,6 +1991,7 @@ extern "C" int flope_tf_layernorm(flope_tf_handle e, const void* in_dev, void* o
 extern "C" int flope_tf_forward_varlen(flope_tf_handle e, const float* x_dev, int batch, int seq_len, const int* lengths_host, float* y_dev, void* stream) {
   int rc;
   if ((rc = tf_check_forward_varlen(e, "flope_tf_forward_varlen", batch, seq_len, x_dev && y_dev))) return rc;
+  if ((rc = tf_check_window(e, "flope_tf_forward_varlen"))) return rc;
   TF_HIP(e, hipSetDevice(e->device));
   hipStream_t st = (hipStream_t)stream;
   TfRagged rg;
@@ -1894,9 +2004,10 @@ extern "C" int flope_tf_forward_plan(flope_tf_handle e, int batch, int seq_len, 
   if (!lengths_host) {
     bool empty;
     if ((rc = tf_check_forward(e, "flope_tf_forward_plan", batch, seq_len, true, &empty))) return rc;
+    if ((rc = tf_check_window(e, "flope_tf_forward_plan"))) return rc;
     return !empty && tf_fused_pick(e, seq_len) ? FLOPE_TF_FWD_FUSED : FLOPE_TF_FWD_LAUNCHES;
   }
-  if ((rc = tf_check_forward_varlen(e, "flope_tf_forward_plan", batch, seq_len, true))) return rc;
+  if ((rc = tf_check_forward_varlen(e, "flope_tf_forward_plan", batch, seq_len, true)) || (rc = tf_check_window(e, "flope_tf_forward_plan"))) return rc;
   std::vector<int> off((size_t)(batch > 0 ? batch : 0) + 1);         // the handle's own table stays as the last forward left it
   TfRagged rg;
   if ((rc = tf_check_ragged(e, "flope_tf_forward_plan", lengths_host, batch, seq_len, off.data(), &rg))) return rc;
@@ -1910,6 +2021,7 @@ extern "C" int flope_tf_last_forward(flope_tf_handle e) {
 
 extern "C" int flope_tf_attention_varlen(flope_tf_handle e, const void* qkv_dev, int batch, const int* lengths_host, void* out_dev, void* stream) {
   if (!e) return tf_fail(nullptr, FLOPE_EINVAL, "flope_tf_attention_varlen: NULL handle");
+  if (int rc = tf_check_window(e, "flope_tf_attention_varlen")) return rc;
   if (!qkv_dev || !out_dev) return tf_fail(e, FLOPE_EINVAL, "flope_tf_attention_varlen: NULL buffer");
   if (((uintptr_t)qkv_dev | (uintptr_t)out_dev) & (uintptr_t)(e->esz - 1))
     return tf_fail(e, FLOPE_EINVAL, "flope_tf_attention_varlen: buffer not aligned to its element type");
@@ -1923,29 +2035,41 @@ extern "C" int flope_tf_attention_varlen(flope_tf_handle e, const void* qkv_dev,
   });
 }
 
+namespace {
+// (query, key) pairs of one sequence of len tokens under the handle's options: len^2, causal len (len + 1) / 2, causal with window W
+// sum_t min(t + 1, W) = W (W + 1) / 2 + (len - W) W for W < len
+double tf_attn_pairs(const flope_tf_encoder* e, double len) {
+  if (!e->opt_causal) return len * len;
+  const double W = e->opt_window;
+  if (W > 0 && W < len) return W * (W + 1.0) / 2.0 + (len - W) * W;
+  return len * (len + 1.0) / 2.0;
+}
+}  // namespace
+
 // algorithmic FLOPs of one forward (2*MAC: linears + QK^T + PV); option causal: a query of a sequence of len tokens meets
-// (len + 1) / 2 keys on average, d len (len + 1) MACs per sequence and layer instead of 2 d len^2
+// (len + 1) / 2 keys on average, d len (len + 1) MACs per sequence and layer instead of 2 d len^2; with option window W query t
+// meets min(t + 1, W) keys
 extern "C" double flope_tf_forward_flops(flope_tf_handle e, int batch, int seq_len) {
   if (!e) return 0.0;
   const double M = (double)batch * seq_len, d = e->d;
   double mac = M * e->in_dim * d + M * d * e->out_dim;
-  mac += e->nl * (M * d * 3 * d + M * d * d + 2.0 * M * d * e->ff + (e->opt_causal ? M * (seq_len + 1.0) * d : 2.0 * M * seq_len * d));
+  mac += e->nl * (M * d * 3 * d + M * d * d + 2.0 * M * d * e->ff + 2.0 * batch * tf_attn_pairs(e, seq_len) * d);
   return 2.0 * mac;
 }
 
 // algorithmic FLOPs of one ragged forward: the linears on T = sum lengths tokens, attention on sum lengths^2 (option causal: on
-// sum lengths (lengths + 1) / 2); 0 for an invalid batch
+// sum lengths (lengths + 1) / 2, with option window on sum_t min(t + 1, W) per sequence); 0 for an invalid batch
 extern "C" double flope_tf_forward_flops_varlen(flope_tf_handle e, int batch, const int* lengths_host) {
   if (!e || batch < 1 || !lengths_host) return 0.0;
   double M = 0.0, sq = 0.0;
   for (int b = 0; b < batch; ++b) {
     if (lengths_host[b] < 1) return 0.0;
     M += lengths_host[b];
-    sq += (double)lengths_host[b] * lengths_host[b];
+    sq += tf_attn_pairs(e, lengths_host[b]);
   }
   const double d = e->d;
   double mac = M * e->in_dim * d + M * d * e->out_dim;
-  mac += e->nl * (M * d * 3 * d + M * d * d + 2.0 * M * d * e->ff + (e->opt_causal ? (sq + M) * d : 2.0 * sq * d));
+  mac += e->nl * (M * d * 3 * d + M * d * d + 2.0 * M * d * e->ff + 2.0 * sq * d);
   return 2.0 * mac;
 }
 
@@ -1976,6 +2100,9 @@ int tf_stream_refuse(flope_tf_stream_s* s, const std::string& who, int rc, int b
     case kTfStreamDuplicate:
       return tf_fail(e, FLOPE_EINVAL, who + ": tracks[" + i + "] = " + std::to_string(rows[bad]) + " names a track an earlier row names (one token per track and call)");
     case kTfStreamFull:
+      if (s->window)
+        return tf_fail(e, FLOPE_EINVAL, who + ": row " + i + ": track " + std::to_string(tf_stream_track(rows, bad)) + " holds INT_MAX = " + std::to_string(INT_MAX) +
+                                            " tokens, the last position an int counts (a windowed state is full only there; reset the track)");
       return tf_fail(e, FLOPE_EINVAL, who + ": row " + i + ": track " + std::to_string(tf_stream_track(rows, bad)) + " already holds capacity = " + std::to_string(s->capacity) +
                                           " tokens (reset it, or open a state with more room)");
     default:
@@ -1983,7 +2110,8 @@ int tf_stream_refuse(flope_tf_stream_s* s, const std::string& who, int rc, int b
   }
 }
 
-// the forward's launch sequence at M = n rows, tf_attn_step where it has launch_attention
+// the forward's launch sequence at M = n rows, tf_attn_step where it has launch_attention.  max_pos: the call's largest position; a
+// windowed state: its largest visible key count - 1 (tf_stream_check_step_window)
 template <typename T>
 int run_step(flope_tf_stream_s* s, const float* x, int n, int max_pos, float* y, hipStream_t st) {
   flope_tf_encoder* e = s->e;
@@ -1991,18 +2119,18 @@ int run_step(flope_tf_stream_s* s, const float* x, int n, int max_pos, float* y,
   const size_t layer = (size_t)s->tracks * s->capacity * 2 * e->d;
   return run_forward_with<T>(e, x, n, 1, y, st, nullptr, [&](int li) {
     T* cache = (T*)s->cache + (size_t)li * layer;
-    if (flope_tf_plan::tf_step_vec_ok(e->d / e->H, (int)sizeof(T)))
-      hipLaunchKernelGGL((tf_attn_step<T, true>), dim3(l.grid_x), dim3(l.block), l.lds, st, (const T*)e->qkv, cache, (T*)e->att, (const int*)s->tab, n, e->d, e->H,
-                         s->tracks, s->capacity, max_pos + 1);
-    else
-      hipLaunchKernelGGL((tf_attn_step<T, false>), dim3(l.grid_x), dim3(l.block), l.lds, st, (const T*)e->qkv, cache, (T*)e->att, (const int*)s->tab, n, e->d, e->H,
-                         s->tracks, s->capacity, max_pos + 1);
+#define TF_STEP(VEC_, WIN_) hipLaunchKernelGGL((tf_attn_step<T, VEC_, WIN_>), dim3(l.grid_x), dim3(l.block), l.lds, st, (const T*)e->qkv, cache, (T*)e->att, \
+                                              (const int*)s->tab, n, e->d, e->H, s->tracks, s->capacity, max_pos + 1, s->window)
+    if (flope_tf_plan::tf_step_vec_ok(e->d / e->H, (int)sizeof(T))) { if (s->window) TF_STEP(true, true); else TF_STEP(true, false); }
+    else { if (s->window) TF_STEP(false, true); else TF_STEP(false, false); }
+#undef TF_STEP
     TF_HIP(e, hipGetLastError());
     return 0;
   });
 }
 
-// the causal ragged forward's launch sequence, each layer's k | v rows copied into the cache in front of its attention
+// the causal ragged forward's launch sequence, each layer's k | v rows copied into the cache in front of its attention (a windowed
+// state: the last min(len, capacity) rows of a sequence, into the ring)
 template <typename T>
 int run_prefill(flope_tf_stream_s* s, const float* x, int n, int L, const TfRagged& rg, float* y, hipStream_t st) {
   flope_tf_encoder* e = s->e;
@@ -2013,12 +2141,11 @@ int run_prefill(flope_tf_stream_s* s, const float* x, int n, int L, const TfRagg
   const size_t total = (size_t)n * rg.max_len * 2 * dv;
   return run_forward_with<T>(e, x, n, L, y, st, &rg, [&](int li) {
     T* cache = (T*)s->cache + (size_t)li * layer;
-    if (vec)
-      hipLaunchKernelGGL((tf_cache_fill<u32x4>), dim3(l.grid_x), dim3(l.block), 0, st, (const u32x4*)e->qkv, (u32x4*)cache, (const int*)e->vl_off, (const int*)s->tab,
-                         rg.max_len, dv, s->tracks, s->capacity, total);
-    else
-      hipLaunchKernelGGL((tf_cache_fill<T>), dim3(l.grid_x), dim3(l.block), 0, st, (const T*)e->qkv, cache, (const int*)e->vl_off, (const int*)s->tab, rg.max_len, dv,
-                         s->tracks, s->capacity, total);
+#define TF_FILL(V_, WIN_) hipLaunchKernelGGL((tf_cache_fill<V_, WIN_>), dim3(l.grid_x), dim3(l.block), 0, st, (const V_*)e->qkv, (V_*)cache, (const int*)e->vl_off, \
+                                            (const int*)s->tab, rg.max_len, dv, s->tracks, s->capacity, total)
+    if (vec) { if (s->window) TF_FILL(u32x4, true); else TF_FILL(u32x4, false); }
+    else { if (s->window) TF_FILL(T, true); else TF_FILL(T, false); }
+#undef TF_FILL
     TF_HIP(e, hipGetLastError());
     return launch_attention<T>(e, e->qkv, e->att, n, rg.max_len, e->vl_off, st);
   });
@@ -2026,23 +2153,28 @@ int run_prefill(flope_tf_stream_s* s, const float* x, int n, int L, const TfRagg
 
 }  // namespace
 
-extern "C" int flope_tf_stream_open(flope_tf_handle e, int tracks, int capacity, flope_tf_stream* out) {
-  if (!out) return tf_fail(e, FLOPE_EINVAL, "flope_tf_stream_open: NULL out");
+namespace {
+// window = 0: flope_tf_stream_open, the linear cache; window >= 1: flope_tf_stream_open_window, the ring
+int tf_stream_open(flope_tf_handle e, const std::string& who, int tracks, int capacity, int window, flope_tf_stream* out) {
+  if (!out) return tf_fail(e, FLOPE_EINVAL, who + ": NULL out");
   *out = nullptr;
-  if (!e) return tf_fail(nullptr, FLOPE_EINVAL, "flope_tf_stream_open: NULL handle");
+  if (!e) return tf_fail(nullptr, FLOPE_EINVAL, who + ": NULL handle");
   if (flope_tf_plan::tf_stream_check_open(tracks, capacity))
-    return tf_fail(e, FLOPE_EINVAL, "flope_tf_stream_open: tracks must be positive and capacity 1 .. " + std::to_string(flope_tf_plan::kTfStreamMaxCapacity) +
+    return tf_fail(e, FLOPE_EINVAL, who + ": tracks must be positive and capacity 1 .. " + std::to_string(flope_tf_plan::kTfStreamMaxCapacity) +
                                         " (the score rows of tf_attn_step live in 64 KiB of LDS)");
+  if (window && flope_tf_plan::tf_stream_check_open_window(tracks, capacity, window))
+    return tf_fail(e, FLOPE_EINVAL, who + ": window = " + std::to_string(window) + " is outside 1 .. capacity = " + std::to_string(capacity) +
+                                        " (the ring must hold every key of a window)");
   TF_HIP(e, hipSetDevice(e->device));
   const size_t bytes = (size_t)e->nl * tracks * capacity * 2 * e->d * e->esz;
   flope_tf_stream_s* s = new flope_tf_stream_s();
-  s->e = e; s->tracks = tracks; s->capacity = capacity;
+  s->e = e; s->tracks = tracks; s->capacity = capacity; s->window = window;
   // num_layers = 0 has no cache; the allocation keeps one row so that the pointer is a pointer
   if (hipMalloc(&s->cache, bytes ? bytes : 16) != hipSuccess || hipMalloc((void**)&s->tab, (size_t)2 * tracks * sizeof(int)) != hipSuccess) {
     (void)hipGetLastError();
     hipFree(s->cache); hipFree(s->tab);
     delete s;
-    return tf_fail(e, FLOPE_EHIP, "flope_tf_stream_open: hipMalloc failed for a cache of " + std::to_string(bytes) + " bytes (num_layers x tracks x capacity x 2 model_dim)");
+    return tf_fail(e, FLOPE_EHIP, who + ": hipMalloc failed for a cache of " + std::to_string(bytes) + " bytes (num_layers x tracks x capacity x 2 model_dim)");
   }
   s->pos.assign((size_t)tracks, 0);
   s->tab_host.assign((size_t)2 * tracks, 0);
@@ -2050,6 +2182,19 @@ extern "C" int flope_tf_stream_open(flope_tf_handle e, int tracks, int capacity,
   e->streams.push_back(s);
   *out = s;
   return FLOPE_OK;
+}
+}  // namespace
+
+extern "C" int flope_tf_stream_open(flope_tf_handle e, int tracks, int capacity, flope_tf_stream* out) {
+  return tf_stream_open(e, "flope_tf_stream_open", tracks, capacity, 0, out);
+}
+
+extern "C" int flope_tf_stream_open_window(flope_tf_handle e, int tracks, int capacity, int window, flope_tf_stream* out) {
+  if (out && e && window < 1) {
+    *out = nullptr;
+    return tf_fail(e, FLOPE_EINVAL, "flope_tf_stream_open_window: window = " + std::to_string(window) + " is outside 1 .. capacity (flope_tf_stream_open is the state without a window)");
+  }
+  return tf_stream_open(e, "flope_tf_stream_open_window", tracks, capacity, window, out);
 }
 
 extern "C" int flope_tf_stream_close(flope_tf_stream s) {
@@ -2090,7 +2235,9 @@ extern "C" int flope_tf_stream_step(flope_tf_stream s, const float* x_dev, int n
   int rc, bad = -1, max_pos = 0;
   if ((rc = tf_stream_enter(s, who, &e))) return rc;
   if (!e->loaded) return tf_fail(e, FLOPE_ESTATE, who + ": weights not loaded");
-  if ((rc = flope_tf_plan::tf_stream_check_step(s->pos.data(), s->tracks, s->capacity, e->max_tokens, n, tracks_host, s->seen.data(), &bad, &max_pos)))
+  rc = s->window ? flope_tf_plan::tf_stream_check_step_window(s->pos.data(), s->tracks, s->window, e->max_tokens, n, tracks_host, s->seen.data(), &bad, &max_pos)
+                 : flope_tf_plan::tf_stream_check_step(s->pos.data(), s->tracks, s->capacity, e->max_tokens, n, tracks_host, s->seen.data(), &bad, &max_pos);
+  if (rc)
     return tf_stream_refuse(s, who, rc, bad, n, tracks_host, nullptr, 0);
   if (!x_dev || !y_dev) return tf_fail(e, FLOPE_EINVAL, who + ": NULL buffer");
   TF_HIP(e, hipSetDevice(e->device));
@@ -2114,7 +2261,9 @@ extern "C" int flope_tf_stream_prefill(flope_tf_stream s, const float* x_dev, in
   const int* lengths = lengths_host ? lengths_host : full.data();
   TfRagged rg;
   if ((rc = tf_check_ragged(e, who.c_str(), lengths, n, seq_len, e->vl_host.data(), &rg))) return rc;
-  if ((rc = flope_tf_plan::tf_stream_check_prefill(s->tracks, s->capacity, n, seq_len, lengths, tracks_host, s->seen.data(), &bad)))
+  rc = s->window ? flope_tf_plan::tf_stream_check_prefill_window(s->tracks, n, tracks_host, s->seen.data(), &bad)
+                 : flope_tf_plan::tf_stream_check_prefill(s->tracks, s->capacity, n, seq_len, lengths, tracks_host, s->seen.data(), &bad);
+  if (rc)
     return tf_stream_refuse(s, who, rc, bad, n, tracks_host, lengths, seq_len);
   TF_HIP(e, hipSetDevice(e->device));
   hipStream_t st = (hipStream_t)stream;
@@ -2122,10 +2271,12 @@ extern "C" int flope_tf_stream_prefill(flope_tf_stream s, const float* x_dev, in
   for (int b = 0; b < n; ++b) s->tab_host[(size_t)b] = tf_stream_track(tracks_host, b);
   TF_HIP(e, hipMemcpyAsync(s->tab, s->tab_host.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice, st));
   flope_tf_plan::tf_stream_set_lengths(s->pos.data(), n, seq_len, lengths, tracks_host);
-  const int causal = e->opt_causal;                 // causal for these launches only; last_fwd is tf_forward's and stays
+  const int causal = e->opt_causal, window = e->opt_window;       // causal and the state's window for these launches only; last_fwd is tf_forward's and stays
   e->opt_causal = 1;
+  e->opt_window = s->window;
   rc = tf_by_dtype(e, [&](auto tag) { return run_prefill<typename decltype(tag)::type>(s, x_dev, n, seq_len, rg, y_dev, st); });
   e->opt_causal = causal;
+  e->opt_window = window;
   return rc;
 }
 

@@ -2,11 +2,16 @@
 // the argument checks of step / prefill / reset over host arrays, the capacity limit, and grid, block and LDS of tf_attn_step and
 // tf_cache_fill.  Shared by tf_encoder.hip and tests/host_harness/harness_tf_stream.cpp (tests/test_tf_stream_host.py holds it
 // against brute force on the CPU, tests/test_gpu_tf_stream.py the device against it).
+// Below them, the same for a windowed state (flope_tf_stream_open_window): a ring cache, absolute positions, keys
+// tf_window_lo(p, W) .. p -- new functions beside the old ones (tests/host_harness/harness_tf_window.cpp, tests/test_tf_window_host.py).
 #pragma once
 
+#include <limits.h>
 #include <stddef.h>
 #include <stdint.h>
 #include <string.h>
+
+#include "tf_attn_plan.h"
 
 namespace flope_tf_plan {
 
@@ -113,5 +118,45 @@ inline int tf_stream_check_reset(int tracks, int n, const int* rows, int* bad) {
     if (rows[r] < 0 || rows[r] >= tracks) { *bad = r; return kTfStreamRange; }
   return kTfStreamOk;
 }
+
+// ---- a windowed state: sliding-window causal attention over a ring cache -------------------------------------------
+// The cache keeps its shape [tracks][capacity][2 d]; the token at absolute position p lives in row p % capacity, and a step at
+// position p attends to keys tf_window_lo(p, W) .. p, W <= capacity.  Positions are absolute and never wrap: a track is full only at
+// INT_MAX tokens.
+constexpr int tf_stream_slot(int p, int capacity) { return p % capacity; }
+
+// The pos - lo cached keys of a step are nk consecutive ring rows from slo = lo % capacity on; they wrap at most once (nk < W <=
+// capacity), so tf_attn_step_row's value pass walks two contiguous runs: tf_stream_run0 rows from slo, the rest from row 0
+constexpr int tf_stream_run0(int slo, int nk, int capacity) { return nk < capacity - slo ? nk : capacity - slo; }
+
+inline int tf_stream_check_open_window(int tracks, int capacity, int window) {
+  return tf_stream_check_open(tracks, capacity) == kTfStreamOk && window >= 1 && window <= capacity ? kTfStreamOk : kTfStreamOpen;
+}
+
+// step: as tf_stream_check_step, with kTfStreamFull only for a track that holds INT_MAX tokens.  *max_pos: the largest visible key
+// count of the call - 1, min(p, W - 1) over its rows; tf_step_launch(n, H, *max_pos) sizes the score rows, *max_pos + 1 is smax.
+inline int tf_stream_check_step_window(const int* pos, int tracks, int window, int max_tokens, int n, const int* rows, char* seen, int* bad,
+                                       int* max_pos) {
+  const int rc = tf_stream_check_rows(tracks, max_tokens, n, rows, seen, bad);
+  if (rc) return rc;
+  int mx = 0;
+  for (int r = 0; r < n; ++r) {
+    const int p = pos[tf_stream_track(rows, r)];
+    if (p == INT_MAX) { *bad = r; return kTfStreamFull; }
+    const int vis = tf_window_keys(p, window) - 1;
+    if (vis > mx) mx = vis;
+  }
+  *max_pos = mx;
+  return kTfStreamOk;
+}
+
+// prefill: n sequences for n distinct tracks; a length is limited by the ragged forward alone (tf_varlen_plan, checked by the caller
+// in front of this), not by capacity: the ring keeps the last min(len, capacity) tokens, which hold every key a later step sees
+inline int tf_stream_check_prefill_window(int tracks, int n, const int* rows, char* seen, int* bad) {
+  return tf_stream_check_rows(tracks, tracks, n, rows, seen, bad);
+}
+// ... and which tokens tf_cache_fill writes: token i of len goes to row i % capacity only if no later token of the sequence takes
+// that row, so every row is written at most once
+constexpr bool tf_stream_fill_writes(int i, int len, int capacity) { return i >= 0 && i < len && i >= len - capacity; }
 
 }  // namespace flope_tf_plan

@@ -5,6 +5,8 @@ ragged batches take `lengths=` (or torch's `src_key_padding_mask=`): each sequen
 its own length, rows behind it come back as `out_layer.bias`, as from the reference module.
 Causal attention takes `is_causal=True` or torch's `mask=` holding the causal mask: position t sees positions <= t of its own
 sequence, so a track is encoded once and every row is the answer the encoder gives when the track ends there.
+Sliding-window causal attention takes `window=W` beside it (or `mask=` holding the banded causal mask): position t sees positions
+t - W < j <= t; `enc.open_stream(tracks, capacity, window=W)` is the same live, over a ring cache that is never full.
 
 Eval-mode semantics only (dropout is identity), as everywhere in this package.  There is no CPU
 path: construction fails loudly without a HIP device or without the built library.
@@ -81,6 +83,45 @@ def _mask_is_causal(mask, L):
     r, c = (int(v) for v in (~causal).nonzero()[0])
     raise ValueError(f"mask[{r}, {c}] = {mask[r, c].item()!r} is not the causal mask's entry ({'masked' if c > r else 'clear'}): only the "
                      "causal mask (masked exactly above the diagonal) or an all-clear mask has a kernel")
+
+
+def _mask_window(mask, L):
+    """torch's `mask` of nn.TransformerEncoder.forward -> (causal, W).  Accepts everything _mask_is_causal accepts -- None or an
+    all-clear [L, L] mask: (False, 0); the causal mask: (True, 0) -- and the banded causal mask: masked exactly where j > i or
+    j <= i - W for one W in 1 .. L - 1, bool (True = masked) or floating (-inf / 0): (True, W).  Anything else has no kernel and raises
+    ValueError naming the first offending (row, col): the first entry that is not the causal mask's, unless that entry is a masked
+    [W, 0] -- then the mask is held to the band of window W and the first entry off that band is named.  Checked on the host."""
+    if mask is None:
+        return False, 0
+    mask = torch.as_tensor(mask)
+    if tuple(mask.shape) != (L, L) or not (mask.dtype == torch.bool or mask.dtype.is_floating_point):
+        raise ValueError(f"mask must be a bool or floating tensor {(L, L)}, got {mask.dtype} {tuple(mask.shape)}")
+    m = mask.detach().cpu()
+    if m.dtype == torch.bool:
+        clear, masked = ~m, m
+    else:
+        m = m.double()
+        clear, masked = m == 0, m == float("-inf")
+    if bool(clear.all()):
+        return False, 0
+    i, j = torch.arange(L)[:, None], torch.arange(L)[None, :]
+    above = j > i
+    causal = torch.where(above, masked, clear)
+    if bool(causal.all()):
+        return True, 0
+    r, c = (int(v) for v in (~causal).nonzero()[0])
+    if c == 0 and r >= 1 and bool(masked[r, c]):             # the first masked entry below the diagonal of a band of window r
+        band = torch.where(above | (j <= i - r), masked, clear)
+        if bool(band.all()):
+            return True, r
+        r2, c2 = (int(v) for v in (~band).nonzero()[0])
+        want = "masked" if c2 > r2 or c2 <= r2 - r else "clear"
+        raise ValueError(f"mask[{r2}, {c2}] = {mask[r2, c2].item()!r} is not the entry of the banded causal mask of window {r} ({want}), "
+                         f"which mask[{r}, 0] starts: only the causal mask, a banded causal mask (masked exactly where col > row or "
+                         "col <= row - W) or an all-clear mask has a kernel")
+    raise ValueError(f"mask[{r}, {c}] = {mask[r, c].item()!r} is not the causal mask's entry ({'masked' if c > r else 'clear'}): only the "
+                     "causal mask (masked exactly above the diagonal), a banded causal mask (also masked where col <= row - W) or an "
+                     "all-clear mask has a kernel")
 
 
 class TransformerEncoder:
@@ -160,17 +201,31 @@ class TransformerEncoder:
         if rc < 0:
             raise RuntimeError(f"flope_tf_set_option(causal) failed ({rc})")
 
-    def flops(self, batch: int, seq_len: int, lengths=None, *, is_causal=False) -> float:
-        """Algorithmic FLOPs of one forward; `is_causal`: attention counted over the keys a causal forward meets."""
-        self._state_causal(is_causal)
+    def _state_window(self, causal, window):
+        """... and the window beside it: `window` > 0 needs causal (ValueError), anything else is stated as it is"""
+        window = int(window)
+        if window < 0:
+            raise ValueError(f"window must be 0 (none) or a positive number of keys, got {window}")
+        if window > 0 and not causal:
+            raise ValueError(f"window={window} needs is_causal=True or a causal / banded mask: a window without causal has no kernel")
+        self._state_causal(causal)
+        rc = self.lib.flope_tf_set_option(self.handle, b"window", window)
+        if rc < 0:
+            raise RuntimeError(f"flope_tf_set_option(window) failed ({rc})")
+
+    def flops(self, batch: int, seq_len: int, lengths=None, *, is_causal=False, window=0) -> float:
+        """Algorithmic FLOPs of one forward; `is_causal`: attention counted over the keys a causal forward meets, `window`: over
+        the min(t + 1, window) keys query t meets under a window."""
+        self._state_window(is_causal, window)
         if lengths is None:
             return self.lib.flope_tf_forward_flops(self.handle, batch, seq_len)
         return self.lib.flope_tf_forward_flops_varlen(self.handle, batch, _host_lengths(lengths, batch))
 
-    def forward_plan(self, batch: int, seq_len: int, lengths=None, *, is_causal=False) -> str:
-        """"fused" or "launches": what forward() of x [batch, seq_len, input_dim] (with these `lengths`, with `is_causal`) would run
-        under the current options.  Enqueues nothing; a shape the forward refuses raises ValueError."""
-        self._state_causal(is_causal)
+    def forward_plan(self, batch: int, seq_len: int, lengths=None, *, is_causal=False, window=0) -> str:
+        """"fused" or "launches": what forward() of x [batch, seq_len, input_dim] (with these `lengths`, with `is_causal`, with
+        `window`: always "launches") would run under the current options.  Enqueues nothing; a shape the forward refuses raises
+        ValueError."""
+        self._state_window(is_causal, window)
         with torch.cuda.device(self.device):
             rc = self.lib.flope_tf_forward_plan(self.handle, int(batch), int(seq_len), None if lengths is None else _host_lengths(lengths, batch))
         self._check_arg(rc)
@@ -186,7 +241,7 @@ class TransformerEncoder:
             msg = msg.decode() if msg else ""
             raise (ValueError if rc == _lib.EINVAL else RuntimeError)(f"flope_amd error {rc}: {msg}")
 
-    def forward(self, x: torch.Tensor, lengths=None, src_key_padding_mask=None, *, mask=None, is_causal=False) -> torch.Tensor:
+    def forward(self, x: torch.Tensor, lengths=None, src_key_padding_mask=None, *, mask=None, is_causal=False, window=0) -> torch.Tensor:
         """x [B, L, input_dim] -> [B, L, out_dim].  `lengths`: a sequence or CPU integer tensor of B values, 1 <= lengths[b] <= L --
         sequence b is x[b, :lengths[b]], the rows behind it are padding (never read) and come back as out_layer.bias.
         `src_key_padding_mask`: bool [B, L], True = padding (torch's convention); it must mask a suffix of every row and is turned
@@ -197,7 +252,12 @@ class TransformerEncoder:
         `is_causal=True`, raises ValueError.  The mask is checked on the host: a device mask costs a copy, `is_causal=True` costs
         nothing.  Two deliberate differences from torch: `is_causal=True` without a mask means causal here (torch ignores that hint
         silently), and with `lengths` the rows behind a sequence still come back as out_layer.bias, never read (torch leaves its
-        nested-tensor path once a mask is given and computes something there)."""
+        nested-tensor path once a mask is given and computes something there).
+        `window=W` (W >= 1, with `is_causal=True` or such a mask; ValueError without), or `mask` = the banded causal [L, L] mask
+        (masked exactly where col > row or col <= row - W, bool or -inf / 0): row t attends to rows t - W < j <= t of its own sequence
+        (inside each sequence with `lengths`).  Attention then runs the generic kernel for every dtype and shape and the forward is
+        never the single launch; W >= L gives the generic causal kernel's bits.  A banded mask together with another `window` raises
+        ValueError.  The option is stated per call: a plain call after a windowed one has no window."""
         if not x.is_cuda or x.device != self.device:
             raise RuntimeError(f"input must live on {self.device} (got {x.device}); no CPU path")
         if x.dim() != 3 or x.shape[2] != self.dims[0]:
@@ -208,10 +268,13 @@ class TransformerEncoder:
         B, L = x.shape[0], x.shape[1]
         if src_key_padding_mask is not None:
             lengths = _mask_to_lengths(src_key_padding_mask, B, L)
-        causal = _mask_is_causal(mask, L)
+        causal, band = _mask_window(mask, L)
         if is_causal and mask is not None and not causal:
             raise ValueError("is_causal=True with a mask that is not the causal mask")
-        self._state_causal(causal or is_causal)
+        window = int(window)
+        if band and window and window != band:
+            raise ValueError(f"window={window} with a banded mask of window {band}")
+        self._state_window(causal or is_causal, window or band)
         y = torch.empty((B, L, self.dims[2]), dtype=torch.float32, device=self.device)
         lh = None if lengths is None else _host_lengths(lengths, B)
         if lengths is None:
@@ -226,14 +289,15 @@ class TransformerEncoder:
 
     __call__ = forward
 
-    def attention(self, qkv: torch.Tensor, lengths=None, out: torch.Tensor = None, *, is_causal=False) -> torch.Tensor:
+    def attention(self, qkv: torch.Tensor, lengths=None, out: torch.Tensor = None, *, is_causal=False, window=0) -> torch.Tensor:
         """softmax(q k^T / sqrt(head_dim)) v per head of qkv [B, L, 3 * model_dim] in the handle's dtype -> [B, L, model_dim], by
         the kernel a forward of this (B, L) would launch under the current options; its id is kept in `last_attn_kernel`.  Needs no
         weights.  `out`: a contiguous tensor of the result's shape and dtype to write into.
         With `lengths` (B values), qkv is the packed 2-D [T, 3 * model_dim] of a ragged batch, T = sum(lengths), sequence b at rows
         sum(lengths[:b]) onwards; the result is the packed [T, model_dim].
-        `is_causal`: query i attends to keys <= i of its own sequence; the kernel is the one the shape picks without it."""
-        self._state_causal(is_causal)
+        `is_causal`: query i attends to keys <= i of its own sequence; the kernel is the one the shape picks without it.
+        `window=W` (with `is_causal=True`): keys i - W < j <= i, always by the generic kernel."""
+        self._state_window(is_causal, window)
         tdt = {"f16": torch.float16, "bf16": torch.bfloat16}.get(self.dtype, torch.float32)
         d = self.dims[1]
         if not qkv.is_cuda or qkv.device != self.device:
@@ -360,10 +424,12 @@ class TransformerEncoder:
         self._keep = (x, weight, bias)
         return out
 
-    def open_stream(self, tracks: int, capacity: int) -> "TransformerEncoderStream":
+    def open_stream(self, tracks: int, capacity: int, window: int = 0) -> "TransformerEncoderStream":
         """A stream state for `tracks` live tracks of up to `capacity` tokens each (TransformerEncoderStream): feed one new token per
-        track with step() and get the row a causal forward of the whole track would end with, without running it again."""
-        return TransformerEncoderStream(self, tracks, capacity)
+        track with step() and get the row a causal forward of the whole track would end with, without running it again.
+        `window=W` (1 <= W <= capacity): sliding-window attention over a ring cache -- a track is never full, positions are absolute,
+        and step() at position t returns row t of enc(track[: t + 1], is_causal=True, window=W), bit for bit."""
+        return TransformerEncoderStream(self, tracks, capacity, window)
 
     def close(self):
         if getattr(self, "handle", None) and self.handle.value:
@@ -397,15 +463,25 @@ class TransformerEncoderStream:
     (`positions`).  step() takes one new token per track and returns the encoder's output for it: the row enc(track, is_causal=True)
     would end with -- in bits where that forward's attention runs the generic kernel, within the attention kernels' tolerances
     elsewhere.  prefill() loads whole histories in one causal forward.  The calls on one state run on the current stream in
-    program order; keep them on one stream.  The state keeps its encoder alive; after enc.close() its calls raise RuntimeError."""
+    program order; keep them on one stream.  The state keeps its encoder alive; after enc.close() its calls raise RuntimeError.
+    With `window` = W >= 1 (1 <= W <= capacity, ValueError outside) the cache is a ring and the state is never full:
+    positions are absolute and unbounded, the token at position t attends to positions max(0, t + 1 - W) .. t, and step() returns row
+    t of enc(track[: t + 1], is_causal=True, window=W) in bits for every dtype, alone or behind a prefill(), for any capacity >= W.
+    prefill() is then enc(x, lengths=lengths, is_causal=True, window=W) in bits, takes sequences longer than `capacity` (the ring
+    keeps their last `capacity` tokens) and leaves the tracks at their lengths."""
 
-    def __init__(self, enc: TransformerEncoder, tracks: int, capacity: int):
+    def __init__(self, enc: TransformerEncoder, tracks: int, capacity: int, window: int = 0):
         self.enc = enc
         self.state = C.c_void_p()
-        self.tracks, self.capacity = int(tracks), int(capacity)
+        self.tracks, self.capacity, self.window = int(tracks), int(capacity), int(window)
         self._handle()
+        if self.window < 0:
+            raise ValueError(f"window must be 0 (a linear cache) or 1 .. capacity, got {self.window}")
         with torch.cuda.device(enc.device):
-            rc = enc.lib.flope_tf_stream_open(enc.handle, self.tracks, self.capacity, C.byref(self.state))
+            if self.window:
+                rc = enc.lib.flope_tf_stream_open_window(enc.handle, self.tracks, self.capacity, self.window, C.byref(self.state))
+            else:
+                rc = enc.lib.flope_tf_stream_open(enc.handle, self.tracks, self.capacity, C.byref(self.state))
         enc._check_arg(rc)
 
     def _handle(self):
@@ -428,7 +504,8 @@ class TransformerEncoderStream:
 
     def step(self, x: torch.Tensor, tracks=None, out: torch.Tensor = None) -> torch.Tensor:
         """x [n, input_dim]: row r is the next token of track tracks[r] (None: n == the state's track count, row r is track r) ->
-        [n, out_dim].  Tracks must be distinct and none at capacity (ValueError names the offending row; nothing has moved then).
+        [n, out_dim].  Tracks must be distinct and none at capacity (ValueError names the offending row; nothing has moved then);
+        a windowed state has no such limit.
         `out`: a float32 [n, out_dim] tensor with contiguous rows to write into."""
         self._live()
         enc = self.enc
@@ -447,7 +524,8 @@ class TransformerEncoderStream:
     def prefill(self, x: torch.Tensor, lengths=None, tracks=None, out: torch.Tensor = None) -> torch.Tensor:
         """x [n, L, input_dim], sequence b the history of track tracks[b] (None as in step), `lengths` as in forward() -> the causal
         forward enc(x, lengths=lengths, is_causal=True) [n, L, out_dim], bit for bit; the tracks then hold their lengths' tokens
-        (whatever they held before is overwritten) and the next step() continues them."""
+        (whatever they held before is overwritten) and the next step() continues them.  A windowed state: the forward is the one
+        with window=W, and L may exceed the capacity."""
         self._live()
         enc = self.enc
         x = self._check_x(x, 3)

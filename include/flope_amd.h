@@ -348,7 +348,18 @@ int flope_tf_forward(flope_tf_handle h, const float* x_dev, int batch, int seq_l
  *       kernel a shape picks, its grid, block and LDS (and so flope_tf_forward_plan's answer) are those of the option at 0, and
  *       keys above the diagonal are skipped, not loaded and masked.  flope_tf_forward_flops / _flops_varlen count attention as
  *       num_layers model_dim sum len (len + 1) MACs under it.  Row i of a causal forward depends on rows <= i only: the forward of a
- *       prefix is the prefix of the forward, bit for bit.  May be flipped between calls.  No other [L, L] mask has a form. */
+ *       prefix is the prefix of the forward, bit for bit.  May be flipped between calls.  The only other [L, L] mask with a form
+ *       is the banded causal one of "window";
+ *   "window" (default 0; FLOPE_EINVAL below 0; returns the old value, as the others do): W >= 1 together with "causal" = 1 is
+ *       sliding-window causal attention: query i attends to keys j of its own sequence with i - W < j <= i, torch's
+ *       banded [L, L] mask.  0 = no window.  Honoured only with "causal" = 1: with "causal" = 0 and W > 0, flope_tf_forward,
+ *       _forward_varlen, _forward_plan, _attention and _attention_varlen return FLOPE_EINVAL with a message (a window without causal
+ *       is refused).  With lengths the window lies inside each packed sequence; rows behind a sequence keep coming back as
+ *       out_layer.bias.  Under a window EVERY attention launch is tf_attn_generic (its WINDOW instantiation, whatever the dtype and
+ *       shape: flope_tf_attention* return FLOPE_TF_ATTN_GENERIC), keys outside the window are not loaded, the forward is always the
+ *       launch sequence (flope_tf_forward_plan answers FLOPE_TF_FWD_LAUNCHES, "fused" is not taken), and flope_tf_forward_flops /
+ *       _flops_varlen count attention over sum_t min(t + 1, W) keys per sequence.  W >= seq_len gives the bits of the generic causal
+ *       kernel.  Windows inside tf_attn_mfma, tf_attn_tiled, tf_attn_f32m and tf_fused_f32 are a follow-up. */
 int flope_tf_set_option(flope_tf_handle h, const char* name, int value);
 /* softmax(q k^T / sqrt(head_dim)) v per head on a caller's buffer: qkv_dev [batch, seq_len, 3*model_dim] and out_dev
  * [batch, seq_len, model_dim] in the handle's dtype (float32 for FLOPE_DT_F32).  Launches exactly what flope_tf_forward
@@ -356,7 +367,7 @@ int flope_tf_set_option(flope_tf_handle h, const char* name, int value);
  * FLOPE_TF_ATTN_* id of the kernel launched (flope_amd/csrc/tf_attn_plan.h: 0 generic, 1 tf_attn_mfma, 2 tf_attn_tiled,
  * 3 tf_attn_f32m), or < 0.  batch*seq_len <= max_tokens. */
 int flope_tf_attention(flope_tf_handle h, const void* qkv_dev, int batch, int seq_len, void* out_dev, void* stream);
-/* algorithmic FLOPs of one forward (2*MAC: linears + QK^T + PV) */
+/* algorithmic FLOPs of one forward (2*MAC: linears + QK^T + PV), attention counted over the keys options "causal" / "window" leave */
 double flope_tf_forward_flops(flope_tf_handle h, int batch, int seq_len);
 /* One loaded linear on a caller's buffers: y = act(x W^T + b (+ res)), x_dev [rows, K] -> y_dev [rows, N], res_dev [rows, N] or NULL,
  * relu != 0: ReLU behind the residual.  name: "embedding", "out_layer", "layers.<i>.in_proj", ".out_proj", ".linear1", ".linear2".
@@ -441,9 +452,23 @@ double flope_tf_forward_flops_varlen(flope_tf_handle h, int batch, const int* le
  *             rows 0 .. length - 1 of track tracks_host[b] (NULL as above) and sets those tracks' positions to their lengths,
  *             whatever they held.  Limits of flope_tf_forward_varlen, lengths <= capacity, tracks as for _step.  Option "causal"
  *             is as it was when the call returns.
- *   _reset    positions of the n tracks of tracks_host (NULL: every track, n ignored) back to 0; enqueues nothing. */
+ *   _reset    positions of the n tracks of tracks_host (NULL: every track, n ignored) back to 0; enqueues nothing.
+ * flope_tf_stream_open_window: a state that is never full -- sliding-window causal attention over a RING cache.
+ * 1 <= window <= capacity <= 4096 (FLOPE_EINVAL outside, the message names the figure); the allocation has the same shape, and the
+ * token at absolute position p lives in row p % capacity.  Positions are absolute and unbounded: _step refuses a track only once it
+ * holds INT_MAX tokens (the message says so), and _position returns the absolute count.  Everything above holds with these changes:
+ *   _step     the token at position p attends to keys max(0, p + 1 - window) .. p; its k and v overwrite row p % capacity, which held
+ *             key p - capacity, outside every window that includes p.  LDS and time are bounded by `window`, not by the track's age.
+ *             y_dev's row is, bit for bit and for every dtype, row p of the forward of the track so far under "causal" = 1,
+ *             "window" = window (whose attention is tf_attn_generic by construction) -- alone or behind a _prefill, for any capacity
+ *             >= window; while p < window also the row of a state opened without a window.
+ *   _prefill  the ragged forward under "causal" = 1 and "window" = window, in bits; lengths are limited by flope_tf_forward_varlen
+ *             alone, not by capacity: of a sequence of len tokens the last min(len, capacity) go to the ring (token i to row
+ *             i % capacity), and the track is left at position len.  Options "causal" and "window" are as they were on return.
+ * flope_tf_stream_open is window = 0: the linear cache and the refusals above. */
 typedef struct flope_tf_stream_s* flope_tf_stream;
 int flope_tf_stream_open(flope_tf_handle h, int tracks, int capacity, flope_tf_stream* out);
+int flope_tf_stream_open_window(flope_tf_handle h, int tracks, int capacity, int window, flope_tf_stream* out);
 int flope_tf_stream_close(flope_tf_stream s);
 int flope_tf_stream_reset(flope_tf_stream s, int n, const int* tracks_host);
 /* tokens held by `track`, or < 0 */
