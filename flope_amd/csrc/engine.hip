@@ -40,7 +40,7 @@ extern "C" int flope_conv_w4_init();
 extern "C" int flope_conv_r4_init();
 extern "C" int flope_conv_r4_launch(const ConvP* p, int dtype, int grid_blocks, void* stream);
 extern "C" int flope_conv_s1r_init();
-extern "C" int flope_conv_s1r_launch(const ConvP* p, const void* w, int dtype, int grid, void* stream);
+extern "C" int flope_conv_s1r_launch(const ConvP* p, const void* w, int dtype, int grid, int yw, void* stream);
 extern "C" int flope_conv_s2r_init();
 extern "C" int flope_conv_s2r_launch(const ConvP* p, const void* w, int dtype, int grid, void* stream);
 extern "C" int flope_conv_w4_launch(const ConvP* p, int dtype, int grid_blocks, int mt, void* stream);
@@ -701,7 +701,7 @@ static int run_slice(flope_engine* e, const void* x_dev, int in_format, int star
         break;
       }
       case kGstag: K_TRY(e, conv_name(s).c_str(), flope_conv_gstag_launch(&p, dt, stream)); break;
-      case kS1r: K_TRY(e, conv_name(s).c_str(), flope_conv_s1r_launch(&p, c.img[kWS1r], dt, L.grid, stream)); break;
+      case kS1r: K_TRY(e, conv_name(s).c_str(), flope_conv_s1r_launch(&p, c.img[kWS1r], dt, L.grid, o.coldyw, stream)); break;
       case kR4: K_TRY(e, conv_name(s).c_str(), flope_conv_r4_launch(&p, dt, L.grid, stream)); break;
       case kW4: K_TRY(e, conv_name(s).c_str(), flope_conv_w4_launch(&p, dt, L.grid, L.mt, stream)); break;
       case kStagFlat: case kStag512x64: case kStagBands:

@@ -63,6 +63,7 @@ struct PlanOptions {
   int f32m_ksplit = 0;   // FLOPE_DT_F32 with f32mfma = 1 only: 0 = off, 1 = split-K per launch by the cost model of f32m_ksplit(), 2..32 = force that share count (rounded down to 2 / 4 / 8 / 16 / 32) wherever a split is allowed
   int inline0 = 1;       // several batch slices: slice 0 runs on the caller's stream itself (no fork hop in front of it, one join fewer; the hop offsets the side slices, so lag's sleeping wave is skipped)
   int inplace = 0;       // 1: a BasicBlock's conv2 writes over its residual input and block X.1's conv1 over block X.0's conv1 output (engine.hip: map_buffers)
+  int coldyw = 2;        // conv_s1r: 1 = the next band's LDS-DMA pieces are issued by the SIMD's younger waves (4-7) alone, at the head of their sub-tile; 2 = that, and the first band runs while the weights arrive (loaded four steps ahead in its step stream); 0 = pieces by all eight waves in their first three steps, all weights in front of the first band
   int profile = 0;       // 1: one slice, an event around every launch (flope_profile_read); 2: the slices as in production, events on every slice's stream (flope_profile_timeline)
 };
 
@@ -111,6 +112,7 @@ inline const std::vector<OptionDef>& option_table() {
       {"f32m_ksplit", &O::f32m_ksplit, kClamp, 0, 32, false},
       {"inline0", &O::inline0, kBool, 0, 1, false},
       {"inplace", &O::inplace, kBool, 0, 1, false},
+      {"coldyw", &O::coldyw, kClamp, 0, 2, false},
   };
   return t;
 }

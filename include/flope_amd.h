@@ -186,7 +186,11 @@ int flope_read_stage(flope_handle h, int stage, int batch, float* dst_dev,
  *   materialised shortcut with "dsfuse" = 0; a conv2 with a folded shortcut keeps its own buffer), and the first conv of block X.1
  *   stores into block X.0's conv1 buffer: a layer touches two activation maps instead of five, which keeps them resident in the
  *   Infinity Cache.  Same launches, same bits; every buffer stays allocated, so the option may be flipped between forwards.
- *   flope_read_stage then serves only part of the stages (see there). */
+ *   flope_read_stage then serves only part of the stages (see there).
+ *   "coldyw" (default 2): conv_s1r (layer 2's three 128 -> 128 convs on 224 x 224 crops).  1 = the look-ahead LDS-DMA pieces of
+ *   the next band are issued by the SIMD's younger waves (4 - 7) alone, where they wait for the matrix pipe anyway; 2 = that, and
+ *   the first band of a workgroup runs while its weights arrive instead of behind them; 0 = the schedule before both.  Same
+ *   launches, same bits; may be flipped between forwards. */
 int flope_set_option(flope_handle h, const char* name, int value);
 /* developer aid of diagnostic builds (-DFLOPE_STAG_DBG, option "dbg" = 64): in-kernel clock stamps that conv launch i of
  * the last forward left in the split-K workspace at byte offset i * 1048576 ({clk0, clk1, rt0, rt1} uint64 per workgroup and

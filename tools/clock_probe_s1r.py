@@ -1,4 +1,4 @@
-"""conv_s1r band timeline (diagnostic build): cycles between the stamps of each workgroup's second band, wave 0.
+"""conv_s1r band timeline (diagnostic build): cycles between the stamps of each workgroup's second band, wave 0 and wave 4.
     make dbg && FLOPE_AMD_LIB=build/dbg/libflope_amd_dbg.so python tools/clock_probe_s1r.py [streams] [opts]"""
 import ctypes as C
 import os
@@ -32,7 +32,7 @@ while time.time() - t0 < 2.0:
 buf = np.zeros(256 * 16, dtype=np.uint64)
 names = ["sub-tile A: 18 steps x 8 MFMAs (+ 6 pieces)", "A: swap write, residual issue, wait", "A: barrier", "A: swap read + epilogue (2 tiles)", "(gap)",
          "sub-tile B: 18 steps x 6 MFMAs", "B: swap write, residual issue, waits", "B: barrier", "B: swap read + epilogue"]
-for ci in (6, 7):       # layer2.1.conv1, layer2.1.conv2 in the engine's conv list
+for ci in (6, 7):       # layer2.0.conv2 (+ folded shortcut), layer2.1.conv1 in the engine's conv list
     rc = e.lib.flope_debug_read_ws(e.handle, buf.ctypes.data_as(C.c_void_p), C.c_size_t(ci * 1048576), C.c_size_t(buf.nbytes))
     assert rc == 0
     r = buf.reshape(-1, 16).astype(np.int64)
@@ -49,6 +49,12 @@ for ci in (6, 7):       # layer2.1.conv1, layer2.1.conv2 in the engine's conv li
     t0_ = d[:, 13].min()
     print(f"  workgroup lifetime {np.median(life):.0f} cycles = {np.median(d[:, 14] - d[:, 13]) / 100:.1f} us (clock {np.median(clk):.2f} GHz); entry -> loop start {np.median(pro):.0f} cycles; "
           f"entries spread over {(d[:, 13].max() - t0_) / 100:.1f} us; first entry -> last exit {(d[:, 14].max() - t0_) / 100:.1f} us")
+    yb = np.zeros(256 * 16, dtype=np.uint64)      # wave 4 (the younger wave of SIMD 0): the same stamps
+    rc = e.lib.flope_debug_read_ws(e.handle, yb.ctypes.data_as(C.c_void_p), C.c_size_t(ci * 1048576 + 16384 * 8), C.c_size_t(yb.nbytes))
+    assert rc == 0
+    y = yb.reshape(-1, 16).astype(np.int64)[ok]
+    print("  wave 4, same phases: " + " ".join(f"{np.median(y[:, k + 1] - y[:, k]):.0f}" for k in range(9)) + f"; band {np.median(y[:, 9] - y[:, 0]):.0f}; "
+          f"starts {np.median(y[:, 0] - d[:, 0]):.0f} after wave 0")
     wb = np.zeros(256 * 16, dtype=np.uint64)
     rc = e.lib.flope_debug_read_ws(e.handle, wb.ctypes.data_as(C.c_void_p), C.c_size_t(ci * 1048576 + 8192 * 8), C.c_size_t(wb.nbytes))
     assert rc == 0
