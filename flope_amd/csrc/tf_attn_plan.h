@@ -79,6 +79,26 @@ constexpr int tf_window_lo(int i, int W) { return W > 0 && i >= W ? i - W + 1 : 
 // ... and how many keys that is: min(i + 1, W), i + 1 without a window
 constexpr int tf_window_keys(int i, int W) { return i - tf_window_lo(i, W) + 1; }
 
+// ---- the window on the 16-bit MFMA kernels (option "window_mfma") ---------------------------------------------------------
+// tf_attn_mfma / tf_attn_tiled walk 32-key steps; under a window a wave also leaves out the steps that lie wholly below the window of
+// its FIRST query (the lowest window of the wave).  The kernels call these, and so does tests/host_harness/harness_tf_window16.cpp
+// (tests/test_tf_window16_host.py holds them against brute force).
+// First 32-key step the wave of queries q0 .. q0 + 31 takes: the one that holds the first visible key of query q0; 0 for W = 0
+constexpr int tf_window_first_step(int q0, int W) { return tf_window_lo(q0, W) & ~31; }
+// ... whether that wave takes the step that starts at key kb: not above its last query, not wholly below its first query's window
+constexpr bool tf_window_step_taken(int q0, int kb, int W) { return tf_causal_step_taken(q0, kb) && kb + 31 >= tf_window_lo(q0, W); }
+// tf_attn_tiled: first 64-key block the workgroup of query block qblock loads (its first wave's first step lies in it); the last
+// stays tf_causal_tiled_blocks(qblock, L) - 1
+constexpr int tf_window_tiled_first_block(int qblock, int W) { return tf_window_lo(qblock * kTfAttnTiledQueries, W) / kTfAttnTiledKB; }
+// The pick under causal with a window: tf_attn_pick's where the option is set and that kernel has a WINDOW instantiation
+// (tf_attn_mfma, tf_attn_tiled), the generic kernel otherwise -- option 0, float32 (tf_attn_f32m has none), misaligned pointers
+inline int tf_attn_pick_window(int dtype, int head_dim, int seq_len, int opt_generic, int opt_f32m, int opt_tiled, int opt_window_mfma,
+                               int aligned16) {
+  if (!opt_window_mfma) return FLOPE_TF_ATTN_GENERIC;
+  const int pick = tf_attn_pick(dtype, head_dim, seq_len, opt_generic, opt_f32m, opt_tiled, aligned16);
+  return pick == FLOPE_TF_ATTN_MFMA64 || pick == FLOPE_TF_ATTN_TILED ? pick : (int)FLOPE_TF_ATTN_GENERIC;
+}
+
 // ---- ragged batches (flope_tf_forward_varlen / flope_tf_attention_varlen) ------------------------------------------
 // A batch of B sequences of lengths[b] tokens (1 <= lengths[b] <= L) lives in the handle as T = sum lengths packed rows;
 // sequence b starts at packed row off[b], off[B] = T.

@@ -16,7 +16,8 @@
 // Option causal = 1 (any dtype): query i attends to keys j <= i of its own sequence -- the CAUSAL instantiation of whichever attention
 // kernel the shape picks, and of tf_fused_f32; key blocks above the diagonal are skipped, not loaded and masked.
 // Option window = W > 0 (with causal, any dtype): query i attends to keys i - W < j <= i -- tf_attn_generic's WINDOW instantiation for every
-// shape, the keys below the window not loaded either; never the single launch.
+// shape, the keys below the window not loaded either; never the single launch.  Option window_mfma = 1: a 16-bit launch
+// keeps tf_attn_mfma / tf_attn_tiled under a window, their WINDOW instantiations.
 // flope_tf_stream_* (any dtype): one new token per track instead of the causal forward again -- the same launch sequence at one row per
 // track, with tf_attn_step over a per-track cache of every layer's keys and values where the forward has its attention kernel
 // (the checks and launch shapes are in tf_encoder_stream.h).  flope_tf_stream_open_window: the same over a ring cache
@@ -124,7 +125,7 @@ __device__ __forceinline__ void tf_layernorm_row(const T* x, T* y, const float* 
 // ld elements (q | k | v at 0, d, 2 d); s: this wave's score row (L floats of LDS); orow: the dh outputs of the query.
 // CAUSAL (all four attention kernels): query i attends to keys j <= i of its own sequence.  Here the three key loops end
 // at i + 1 instead of L: the keys above the diagonal are never loaded.
-// WINDOW (with CAUSAL, tf_attn_generic only): query i attends to keys lo .. i, lo = tf_window_lo(i, W) = max(0, i + 1 - W);
+// WINDOW (with CAUSAL; the 16-bit MFMA kernels have their own form): query i attends to keys lo .. i, lo = tf_window_lo(i, W) = max(0, i + 1 - W);
 // the three key loops start at lo, so the keys below the window are never loaded either.  The order, fixed here once: lane l takes keys
 // lo + l, lo + l + 64, ..; the value chain runs j = lo .. i from 0.f.  With lo = 0 (no window, or i < W) that is the order above.
 template <typename T, bool CAUSAL = false, bool WINDOW = false>
@@ -319,7 +320,7 @@ __global__ void tf_layernorm_vec(const T* in, T* out, const float* w, const floa
 // off[b] .. off[b + 1] - 1 and the L argument is the longest length, which sized the grid and the LDS; the kernel takes its own
 // sequence's length for L, so every bound, mask and clamp below stays inside the sequence (row off[b] + L is the next sequence's
 // first key, not padding).  The fixed-length instantiations (VARLEN = false, off unused) compile from the source they had.
-// WINDOW (this kernel only): keys i - W < j <= i; W is read by those instantiations alone and sits where the argument
+// WINDOW (every launch under a window unless option window_mfma keeps a 16-bit MFMA kernel): keys i - W < j <= i; W is read by those instantiations alone and sits where the argument
 // block had four bytes of padding, so every other argument keeps its offset.
 template <typename T, bool VARLEN = false, bool CAUSAL = false, bool WINDOW = false>
 __global__ void tf_attn_generic(const T* qkv, T* out, int L, int d, int H, int W, const int* __restrict__ off) {
@@ -692,8 +693,10 @@ __global__ __launch_bounds__(256, 2) void tf_gemm_mfma(const T* __restrict__ X, 
 // get into LDS, its barriers and which steps it runs.  The epilogue (tf_attn16_store) is tf_attn_tiled's; tf_attn_mfma holds a copy.
 // ds_read_b64_tr_b16 needs EXEC all ones: the step has no lane-dependent branch and no early return, and its callers put none
 // around it; queries past L are clamped to L - 1 and not stored, keys at or past L hold zeros in the images and their scores become
-// -inf before the maximum.  The first step always holds key 0 < L, so every query's running maximum is finite from the first step
-// on, and exp2(-inf - max) is 0, never NaN.
+// -inf before the maximum.  Without WINDOW the first step always holds key 0 < L, so every query's running maximum is finite from
+// the first step on, and exp2(-inf - max) is 0, never NaN.  With WINDOW a wave starts at the step that holds the first
+// visible key of its FIRST query, and a later query of the wave may see no key of that step: its maximum stays -inf across it, and
+// the step subtracts 0 instead of that maximum (msafe below), which keeps its sum and output at exactly 0 until its first own key.
 // LDS images (bank = (addr / 4) % 64 for ds_read_b128 and the transposed read; r = key row in its image, c = 16-byte chunk of the
 // row; both XORs stay inside an aligned group of four chunks, so rows of 12 chunks are safe; both depend on r & 15 or less, so an
 // image may start at any multiple of 16 rows):
@@ -733,10 +736,20 @@ template <int HD32> __device__ __forceinline__ TfAttn16Lane tf_attn16_lane(int l
 // CAUSAL: q0 is the wave's first query and a key also has to be <= the lane's own query q0 + qt * 16 + li, unclamped (a query past L
 // is never stored).  A wave starts at step 0, which holds key 0 <= every query: the running maximum is finite before any step that
 // is masked for a query tile as a whole, as above.  Which steps a wave takes is its kernel's business (tf_causal_step_taken).
-template <typename T, int HD32, bool CAUSAL = false>
+// WINDOW (with CAUSAL): a key also has to be > the lane's own query - W, the unclamped query again.  The wave's first
+// step is tf_window_first_step(q0, W), not 0, so a query whose window starts behind that step sees none of its keys: mx, mrun and
+// mnew are all -inf, and exp2(-inf - -inf) would be NaN for good.  The step therefore subtracts msafe = (mnew == -inf ? 0 : mnew) in
+// alpha and in the eight exponentials and still keeps mrun = mnew: a query that has seen nothing gets alpha = exp2(-inf) = 0 and
+// eight zeros, so lrun = 0 and o = 0 exactly; the first step that holds one of its keys then is a first step (alpha = 0 on zeros);
+// where mnew is finite msafe == mnew and no value changes.  Every query below L sees its own key on the diagonal, in a step its wave
+// takes, so lrun > 0 at the store for every stored query.  A query at or past L is clamped for its Q rows only, its mask uses the
+// unclamped index: all its visible keys may lie at or past L and it may end with lrun = 0 and 1 / lrun = inf -- it is not stored
+// (tf_attn16_store's qi < L) and must stay unstored.
+template <typename T, int HD32, bool CAUSAL = false, bool WINDOW = false>
 __device__ __forceinline__ void tf_attn16_step(const char* Ki, const char* Vi, int kb, int kl, int L, int q0, float scale_log2e,
                                                const TfAttn16Lane& ln, const typename Elem<T>::frag (&qf)[2][HD32], float (&mrun)[2],
-                                               float (&lrun)[2], f32x4 (&o)[2][2 * HD32]) {
+                                               float (&lrun)[2], f32x4 (&o)[2][2 * HD32], int W = 0) {
+  static_assert(CAUSAL || !WINDOW, "a window without causal has no meaning");
   typedef typename Elem<T>::frag frag;
   constexpr int RB = 64 * HD32;
   const int g = ln.g, li = ln.li, ksw = ln.ksw, trp = ln.trp, vrow = ln.vrow, vsw = ln.vsw;
@@ -765,6 +778,7 @@ __device__ __forceinline__ void tf_attn16_step(const char* Ki, const char* Vi, i
         const int key = kb + u * 16 + g * 4 + q;
         bool seen = key < L;
         if constexpr (CAUSAL) seen = seen && key <= q0 + qt * 16 + li;
+        if constexpr (WINDOW) seen = seen && key > q0 + qt * 16 + li - W;      // key + W > query, without the overflow of a huge W
         const float x = seen ? s[u][qt][q] * scale_log2e : -INFINITY;
         v[u * 4 + q] = x;
         mx = fmaxf(mx, x);
@@ -772,10 +786,12 @@ __device__ __forceinline__ void tf_attn16_step(const char* Ki, const char* Vi, i
     mx = fmaxf(mx, __shfl_xor(mx, 16));
     mx = fmaxf(mx, __shfl_xor(mx, 32));
     const float mnew = fmaxf(mrun[qt], mx);
-    const float alpha = __builtin_amdgcn_exp2f(mrun[qt] - mnew);
+    float msafe = mnew;
+    if constexpr (WINDOW) msafe = mnew == -INFINITY ? 0.f : mnew;
+    const float alpha = __builtin_amdgcn_exp2f(mrun[qt] - msafe);
     float ps = 0.f;
 #pragma unroll
-    for (int i = 0; i < 8; ++i) { v[i] = __builtin_amdgcn_exp2f(v[i] - mnew); ps += v[i]; }
+    for (int i = 0; i < 8; ++i) { v[i] = __builtin_amdgcn_exp2f(v[i] - msafe); ps += v[i]; }
     lrun[qt] = lrun[qt] * alpha + ps;
     mrun[qt] = mnew;
 #pragma unroll
@@ -830,9 +846,14 @@ __device__ __forceinline__ void tf_attn16_store(T* out, size_t row0, int d, int 
 // others stays all ones for the transposed reads).
 // CAUSAL: staging and the one __syncthreads as they are; a wave's step loop ends behind the step that holds its last query (the
 // bound is the wave's: EXEC stays all ones).
-template <typename T, bool VARLEN = false, bool CAUSAL = false>
+// WINDOW (with CAUSAL, option window_mfma): staging and the one __syncthreads as they are (the image holds every key;
+// its staging is shared by all waves); a wave's step loop starts at tf_window_first_step(q0, W) instead of 0, the wave's bound
+// again.  Only the WINDOW instantiations read W; it sits where the argument block had four bytes of padding, so every other
+// argument, the hidden ones behind them included (blockDim.x of the staging loop), keeps its offset.
+template <typename T, bool VARLEN = false, bool CAUSAL = false, bool WINDOW = false>
 __global__ __launch_bounds__(1024) void tf_attn_mfma(const T* __restrict__ qkv, T* __restrict__ out, int L, int d,
-                                                     int H, int Lp, float scale_log2e, const int* __restrict__ off) {
+                                                     int H, int Lp, float scale_log2e, int W, const int* __restrict__ off) {
+  static_assert(CAUSAL || !WINDOW, "a window without causal has no meaning");
   typedef typename Elem<T>::frag frag;
   extern __shared__ __attribute__((aligned(16))) char smem[];      // K image [Lp][128 B] | V image [Lp][128 B]
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, g = lane >> 4, li = lane & 15;
@@ -874,6 +895,10 @@ __global__ __launch_bounds__(1024) void tf_attn_mfma(const T* __restrict__ qkv, 
 
   const TfAttn16Lane ln = tf_attn16_lane<2>(lane);
   if constexpr (CAUSAL) Lp = flope_tf_plan::tf_causal_keys(q0, 32, Lp);      // min(Lp, q0 + 32): a multiple of 32
+  if constexpr (WINDOW) {
+    for (int kb = flope_tf_plan::tf_window_first_step(q0, W); kb < Lp; kb += 32)
+      tf_attn16_step<T, 2, true, true>(Ki + kb * 128, Vi + kb * 128, kb, 0, L, q0, scale_log2e, ln, qf, mrun, lrun, o, W);
+  } else
   for (int kb = 0; kb < Lp; kb += 32) tf_attn16_step<T, 2, CAUSAL>(Ki + kb * 128, Vi + kb * 128, kb, 0, L, q0, scale_log2e, ln, qf, mrun, lrun, o);
   // tf_attn16_store's body, kept as a copy: through the call this kernel allocates 98 VGPRs instead of 96 (5 -> 4 waves per SIMD).
   // Change the expressions here and there together (test_head_dim_64_gives_the_bits_of_the_resident_kernel holds them to equal bits).
@@ -911,9 +936,15 @@ __global__ __launch_bounds__(1024) void tf_attn_mfma(const T* __restrict__ qkv, 
 // CAUSAL: the barrier loop runs the WORKGROUP's block count, the 64-key blocks up to its last query (tf_causal_tiled_blocks: all
 // four waves keep the same trips, loads, LDS writes and barriers); inside it a wave skips the 32-key steps that lie wholly above
 // its own last query (tf_causal_step_taken), by the same uniform `continue` as the steps past L.
-template <typename T, int HD32, bool VARLEN = false, bool CAUSAL = false>
+// WINDOW (with CAUSAL, option window_mfma): the barrier loop runs blocks t0 = tf_window_tiled_first_block .. nb - 1,
+// the WORKGROUP's range again (one trip, load and barrier count for its four waves); the blocks below t0 are not loaded.  The loads
+// in front of the loop fetch block t0 into stage t0 & 1, so a block's stage is t & 1 from the first block on, as without a window.
+// Inside the loop a wave skips the steps outside tf_window_step_taken, the same uniform `continue`.  W is the last argument, behind
+// every offset the other instantiations read, and only the WINDOW instantiations read it.
+template <typename T, int HD32, bool VARLEN = false, bool CAUSAL = false, bool WINDOW = false>
 __global__ __launch_bounds__(256, 2) void tf_attn_tiled(const T* __restrict__ qkv, T* __restrict__ out, int L, int d, int H,
-                                                        float scale_log2e, const int* __restrict__ off) {
+                                                        float scale_log2e, const int* __restrict__ off, int W) {
+  static_assert(CAUSAL || !WINDOW, "a window without causal has no meaning");
   typedef typename Elem<T>::frag frag;
   constexpr int HD = 32 * HD32, RB = 64 * HD32, NCH = 4 * HD32;     // head_dim, bytes and 16-byte chunks of a row
   constexpr int KB = flope_tf_plan::kTfAttnTiledKB, BLK = KB * RB, STAGE = 2 * BLK;
@@ -959,8 +990,10 @@ __global__ __launch_bounds__(256, 2) void tf_attn_tiled(const T* __restrict__ qk
       *(u32x4*)(s + sdv[i]) = vr[i];
     }
   };
-  gload(0);
-  lwrite(0);
+  int t0 = 0;
+  if constexpr (WINDOW) t0 = flope_tf_plan::tf_window_tiled_first_block((int)blockIdx.y, W);
+  if constexpr (WINDOW) { gload(t0 * KB); lwrite(t0 & 1); }
+  else { gload(0); lwrite(0); }
 
   const int q0 = blockIdx.y * flope_tf_plan::kTfAttnTiledQueries + wave * 32;
   frag qf[2][HD32];
@@ -979,7 +1012,7 @@ __global__ __launch_bounds__(256, 2) void tf_attn_tiled(const T* __restrict__ qk
     for (int dt = 0; dt < 2 * HD32; ++dt) o[qt][dt] = f32x4{0.f, 0.f, 0.f, 0.f};
 
   const TfAttn16Lane ln = tf_attn16_lane<HD32>(lane);
-  for (int t = 0; t < nb; ++t) {
+  for (int t = t0; t < nb; ++t) {
     gload((t + 1) * KB);                         // (past the last block: row L - 1 again, zeros, a stage nobody reads)
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     BLOCK_BARRIER();
@@ -990,6 +1023,10 @@ __global__ __launch_bounds__(256, 2) void tf_attn_tiled(const T* __restrict__ qk
       const int kl = st * 32, kb = t * KB + kl;
       if (kb >= L) continue;                     // uniform: EXEC stays all ones
       if constexpr (CAUSAL) { if (!flope_tf_plan::tf_causal_step_taken(q0, kb)) continue; }     // per wave, uniform
+      if constexpr (WINDOW) {
+        if (!flope_tf_plan::tf_window_step_taken(q0, kb, W)) continue;                           // per wave, uniform
+        tf_attn16_step<T, HD32, true, true>(Ki, Vi, kb, kl, L, q0, scale_log2e, ln, qf, mrun, lrun, o, W);
+      } else
       tf_attn16_step<T, HD32, CAUSAL>(Ki, Vi, kb, kl, L, q0, scale_log2e, ln, qf, mrun, lrun, o);
     }
     lwrite((t + 1) & 1);
@@ -1352,7 +1389,8 @@ struct flope_tf_encoder {
   int opt_tiled = 0;                         // 16-bit handles: 1 = tf_attn_tiled where the choice would be tf_attn_generic, 2 = also in place of tf_attn_mfma (stored and ignored by float32 handles)
   int opt_fused = 0;                         // 1: a float32 forward that tf_fused_ok takes runs as one launch of tf_fused_f32 (stored and ignored by 16-bit handles and while opt_f32m)
   int opt_causal = 0;                        // 1: query i attends to keys j <= i of its own sequence, in every attention launch and in tf_fused_f32
-  int opt_window = 0;                        // W > 0 (honoured with opt_causal = 1, refused without): keys i - W < j <= i, always on tf_attn_generic, never tf_fused_f32
+  int opt_window = 0;                        // W > 0 (honoured with opt_causal = 1, refused without): keys i - W < j <= i, on tf_attn_generic unless opt_window_mfma, never tf_fused_f32
+  int opt_window_mfma = 0;                   // 1: under causal with a window a 16-bit launch keeps tf_attn_pick's tf_attn_mfma / tf_attn_tiled, their WINDOW instantiations (stored and ignored by float32 handles)
   int last_fwd = FLOPE_TF_FWD_LAUNCHES;       // what the last forward that enqueued anything ran (flope_tf_last_forward)
   const float** fused_tab = nullptr;         // device table of the float32 weight arrays tf_fused_f32 reads (FLOPE_DT_F32 handles, built by flope_tf_load_weights)
   int opt_f32m_lds = 0;                      // KiB of untouched LDS a tf_linear_f32m launch reserves (> 80: one workgroup per CU)
@@ -1514,20 +1552,37 @@ int launch_layernorm(flope_tf_encoder* e, const void* in, void* out, const float
 // One attention launch: softmax(q k^T / sqrt(head_dim)) v per head.  off == nullptr: qkv [B][L][3 d] -> att [B][L][d].  Otherwise a
 // ragged batch: packed qkv [T][3 d] -> att [T][d], sequence b = rows off[b] .. off[b + 1] - 1 (off: the handle's device table), L its
 // longest length, the VARLEN instantiations.  Option causal: the CAUSAL instantiations of the same pick.  One kernel for the whole batch, the one tf_attn_plan.h picks for L; grid, block and LDS
-// from tf_attn_varlen_launch in both cases.  Option window (with causal): the override sits here -- tf_attn_generic's WINDOW
-// instantiation whatever tf_attn_pick would say, launched as the generic kernel always is.  Returns the kernel's FLOPE_TF_ATTN_* id, or < 0.
+// from tf_attn_varlen_launch in both cases.  Option window (with causal): the override sits here -- tf_attn_pick_window's answer:
+// tf_attn_generic's WINDOW instantiation whatever tf_attn_pick would say, launched as the generic kernel always is, unless option
+// window_mfma keeps tf_attn_pick's tf_attn_mfma / tf_attn_tiled, then their WINDOW instantiations.  Returns the kernel's FLOPE_TF_ATTN_* id, or < 0.
 template <typename T>
 int launch_attention(flope_tf_encoder* e, const void* qkv, void* att, int B, int L, const int* off, hipStream_t st) {
   using namespace flope_tf_plan;
   const int d = e->d, H = e->H, dh = d / H;
   const bool window = e->opt_causal && e->opt_window > 0;
-  const int pick = window ? (int)FLOPE_TF_ATTN_GENERIC
-                          : tf_attn_pick(e->dtype, dh, L, e->opt_generic, e->opt_f32m, e->opt_tiled, !(((uintptr_t)qkv | (uintptr_t)att) & 15));
+  const int aligned16 = !(((uintptr_t)qkv | (uintptr_t)att) & 15);
+  const int pick = window ? tf_attn_pick_window(e->dtype, dh, L, e->opt_generic, e->opt_f32m, e->opt_tiled, e->opt_window_mfma, aligned16)
+                          : tf_attn_pick(e->dtype, dh, L, e->opt_generic, e->opt_f32m, e->opt_tiled, aligned16);
   const TfAttnLaunch l = tf_attn_varlen_launch(pick, dh, B, H, L);
   const dim3 grid(l.grid_x, l.grid_y), block(l.block);
   if (window) {
-    if (off) hipLaunchKernelGGL((tf_attn_generic<T, true, true, true>), grid, block, l.lds, st, (const T*)qkv, (T*)att, L, d, H, e->opt_window, off);
-    else hipLaunchKernelGGL((tf_attn_generic<T, false, true, true>), grid, block, l.lds, st, (const T*)qkv, (T*)att, L, d, H, e->opt_window, off);
+    auto launch_w = [&](auto varlen) {
+      constexpr bool VL = decltype(varlen)::value;
+      if constexpr (!std::is_same<T, float>::value) {
+        if (pick == FLOPE_TF_ATTN_MFMA64) {
+          hipLaunchKernelGGL((tf_attn_mfma<T, VL, true, true>), grid, block, l.lds, st, (const T*)qkv, (T*)att, L, d, H, tf_attn_pad32(L),
+                             1.4426950408889634f / sqrtf(64.f), e->opt_window, off);
+        } else if (pick == FLOPE_TF_ATTN_TILED) {
+          const float scale_log2e = 1.4426950408889634f / sqrtf((float)dh);
+#define TF_ATT(HD32_) hipLaunchKernelGGL((tf_attn_tiled<T, HD32_, VL, true, true>), grid, block, l.lds, st, (const T*)qkv, (T*)att, L, d, H, scale_log2e, off, e->opt_window)
+          if (dh == 32) TF_ATT(1); else if (dh == 64) TF_ATT(2); else if (dh == 96) TF_ATT(3); else TF_ATT(4);
+#undef TF_ATT
+        }
+      }
+      if (pick == FLOPE_TF_ATTN_GENERIC)
+        hipLaunchKernelGGL((tf_attn_generic<T, VL, true, true>), grid, block, l.lds, st, (const T*)qkv, (T*)att, L, d, H, e->opt_window, off);
+    };
+    if (off) launch_w(std::true_type{}); else launch_w(std::false_type{});
     TF_HIP(e, hipGetLastError());
     return pick;
   }
@@ -1536,10 +1591,10 @@ int launch_attention(flope_tf_encoder* e, const void* qkv, void* att, int B, int
     if constexpr (!std::is_same<T, float>::value) {
       if (pick == FLOPE_TF_ATTN_MFMA64) {
         hipLaunchKernelGGL((tf_attn_mfma<T, VL, CA>), grid, block, l.lds, st, (const T*)qkv, (T*)att, L, d, H, tf_attn_pad32(L),
-                           1.4426950408889634f / sqrtf(64.f), off);
+                           1.4426950408889634f / sqrtf(64.f), 0, off);
       } else if (pick == FLOPE_TF_ATTN_TILED) {
         const float scale_log2e = 1.4426950408889634f / sqrtf((float)dh);
-#define TF_ATT(HD32_) hipLaunchKernelGGL((tf_attn_tiled<T, HD32_, VL, CA>), grid, block, l.lds, st, (const T*)qkv, (T*)att, L, d, H, scale_log2e, off)
+#define TF_ATT(HD32_) hipLaunchKernelGGL((tf_attn_tiled<T, HD32_, VL, CA>), grid, block, l.lds, st, (const T*)qkv, (T*)att, L, d, H, scale_log2e, off, 0)
         if (dh == 32) TF_ATT(1); else if (dh == 64) TF_ATT(2); else if (dh == 96) TF_ATT(3); else TF_ATT(4);
 #undef TF_ATT
       }
@@ -1756,6 +1811,10 @@ extern "C" int flope_tf_create(int device_id, int input_dim, int model_dim, int 
     hipFuncSetAttribute((const void*)tf_attn_mfma<bf16_t, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 131072);
     hipFuncSetAttribute((const void*)tf_attn_mfma<f16_t, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 131072);
     hipFuncSetAttribute((const void*)tf_attn_mfma<bf16_t, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 131072);
+    hipFuncSetAttribute((const void*)tf_attn_mfma<f16_t, false, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 131072);
+    hipFuncSetAttribute((const void*)tf_attn_mfma<bf16_t, false, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 131072);
+    hipFuncSetAttribute((const void*)tf_attn_mfma<f16_t, true, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 131072);
+    hipFuncSetAttribute((const void*)tf_attn_mfma<bf16_t, true, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 131072);
 #define TF_ATTR(T_, A_, B_) hipFuncSetAttribute((const void*)tf_gemm_mfma<T_, A_, B_>, hipFuncAttributeMaxDynamicSharedMemorySize, 65536)
     TF_ATTR(f16_t, false, false); TF_ATTR(f16_t, false, true); TF_ATTR(f16_t, true, false); TF_ATTR(f16_t, true, true);
     TF_ATTR(bf16_t, false, false); TF_ATTR(bf16_t, false, true); TF_ATTR(bf16_t, true, false); TF_ATTR(bf16_t, true, true);
@@ -1775,7 +1834,9 @@ extern "C" int flope_tf_create(int device_id, int input_dim, int model_dim, int 
     const void* const tiled[] = {(const void*)tf_attn_tiled<f16_t, 4>, (const void*)tf_attn_tiled<bf16_t, 4>,
                                  (const void*)tf_attn_tiled<f16_t, 4, true>, (const void*)tf_attn_tiled<bf16_t, 4, true>,
                                  (const void*)tf_attn_tiled<f16_t, 4, false, true>, (const void*)tf_attn_tiled<bf16_t, 4, false, true>,
-                                 (const void*)tf_attn_tiled<f16_t, 4, true, true>, (const void*)tf_attn_tiled<bf16_t, 4, true, true>};
+                                 (const void*)tf_attn_tiled<f16_t, 4, true, true>, (const void*)tf_attn_tiled<bf16_t, 4, true, true>,
+                                 (const void*)tf_attn_tiled<f16_t, 4, false, true, true>, (const void*)tf_attn_tiled<bf16_t, 4, false, true, true>,
+                                 (const void*)tf_attn_tiled<f16_t, 4, true, true, true>, (const void*)tf_attn_tiled<bf16_t, 4, true, true, true>};
     for (const void* f : tiled)
       if (hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)flope_tf_plan::tf_attn_tiled_lds(128)) != hipSuccess)
         return fin(tf_fail(nullptr, FLOPE_EHIP, "flope_tf_create: hipFuncSetAttribute failed"));
@@ -1816,6 +1877,10 @@ extern "C" int flope_tf_set_option(flope_tf_handle e, const char* name, int valu
   if (!strcmp(name, "window")) {
     if (value < 0) return tf_fail(e, FLOPE_EINVAL, "flope_tf_set_option: window is 0 (none) or a positive key count");
     const int old = e->opt_window; e->opt_window = value; return old;
+  }
+  if (!strcmp(name, "window_mfma")) {
+    if (value < 0 || value > 1) return tf_fail(e, FLOPE_EINVAL, "flope_tf_set_option: window_mfma is 0 or 1");
+    const int old = e->opt_window_mfma; e->opt_window_mfma = value; return old;
   }
   if (!strcmp(name, "f32mlds")) {
     if (value < 0 || value > 160) return tf_fail(e, FLOPE_EINVAL, "flope_tf_set_option: f32mlds is 0 .. 160 (KiB)");

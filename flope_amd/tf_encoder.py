@@ -7,6 +7,7 @@ Causal attention takes `is_causal=True` or torch's `mask=` holding the causal ma
 sequence, so a track is encoded once and every row is the answer the encoder gives when the track ends there.
 Sliding-window causal attention takes `window=W` beside it (or `mask=` holding the banded causal mask): position t sees positions
 t - W < j <= t; `enc.open_stream(tracks, capacity, window=W)` is the same live, over a ring cache that is never full.
+A 16-bit encoder made with `window_mfma=1` keeps its MFMA attention kernels under a window.
 
 Eval-mode semantics only (dropout is identity), as everywhere in this package.  There is no CPU
 path: construction fails loudly without a HIP device or without the built library.
@@ -126,7 +127,7 @@ def _mask_window(mask, L):
 
 class TransformerEncoder:
     def __init__(self, input_dim, model_dim, out_dim, num_heads, num_layers, ff_dim, dropout=0.1,
-                 dtype="f32", max_tokens=4096, device=None, attn_tiled=0, fused=0):
+                 dtype="f32", max_tokens=4096, device=None, attn_tiled=0, fused=0, window_mfma=0):
         _require_gpu()
         self.lib = _lib.load()
         self.device = torch.device(device if device is not None else "cuda:0")
@@ -162,6 +163,11 @@ class TransformerEncoder:
             if rc < 0:
                 self.close()
                 raise ValueError(f"fused must be 0 or 1 (got {fused!r})")
+        if window_mfma:                          # 16-bit handles: a windowed attention keeps its MFMA kernel (0 or 1, include/flope_amd.h)
+            rc = self.lib.flope_tf_set_option(self.handle, b"window_mfma", int(window_mfma))
+            if rc < 0:
+                self.close()
+                raise ValueError(f"window_mfma must be 0 or 1 (got {window_mfma!r})")
 
     def _check(self, rc):
         if rc:
@@ -255,8 +261,10 @@ class TransformerEncoder:
         nested-tensor path once a mask is given and computes something there).
         `window=W` (W >= 1, with `is_causal=True` or such a mask; ValueError without), or `mask` = the banded causal [L, L] mask
         (masked exactly where col > row or col <= row - W, bool or -inf / 0): row t attends to rows t - W < j <= t of its own sequence
-        (inside each sequence with `lengths`).  Attention then runs the generic kernel for every dtype and shape and the forward is
-        never the single launch; W >= L gives the generic causal kernel's bits.  A banded mask together with another `window` raises
+        (inside each sequence with `lengths`).  With `window_mfma=0` attention then runs the generic kernel for every dtype and shape,
+        and W >= L gives the generic causal kernel's bits; on a handle made with `window_mfma=1` a 16-bit forward keeps the MFMA
+        kernel it would run without a window, and W >= L gives that kernel's causal bits.  The forward is never the
+        single launch.  A banded mask together with another `window` raises
         ValueError.  The option is stated per call: a plain call after a windowed one has no window."""
         if not x.is_cuda or x.device != self.device:
             raise RuntimeError(f"input must live on {self.device} (got {x.device}); no CPU path")
@@ -296,7 +304,8 @@ class TransformerEncoder:
         With `lengths` (B values), qkv is the packed 2-D [T, 3 * model_dim] of a ragged batch, T = sum(lengths), sequence b at rows
         sum(lengths[:b]) onwards; the result is the packed [T, model_dim].
         `is_causal`: query i attends to keys <= i of its own sequence; the kernel is the one the shape picks without it.
-        `window=W` (with `is_causal=True`): keys i - W < j <= i, always by the generic kernel."""
+        `window=W` (with `is_causal=True`): keys i - W < j <= i, by the generic kernel with `window_mfma=0`, by the 16-bit MFMA
+        kernel the call would take without a window on a handle made with `window_mfma=1`."""
         self._state_window(is_causal, window)
         tdt = {"f16": torch.float16, "bf16": torch.bfloat16}.get(self.dtype, torch.float32)
         d = self.dims[1]
@@ -428,7 +437,9 @@ class TransformerEncoder:
         """A stream state for `tracks` live tracks of up to `capacity` tokens each (TransformerEncoderStream): feed one new token per
         track with step() and get the row a causal forward of the whole track would end with, without running it again.
         `window=W` (1 <= W <= capacity): sliding-window attention over a ring cache -- a track is never full, positions are absolute,
-        and step() at position t returns row t of enc(track[: t + 1], is_causal=True, window=W), bit for bit."""
+        and step() at position t returns row t of enc(track[: t + 1], is_causal=True, window=W), bit for bit with `window_mfma=0`
+        (with `window_mfma=1`: in bits where that forward's attention is the generic kernel, within the attention kernels'
+        tolerances elsewhere)."""
         return TransformerEncoderStream(self, tracks, capacity, window)
 
     def close(self):
@@ -466,9 +477,11 @@ class TransformerEncoderStream:
     program order; keep them on one stream.  The state keeps its encoder alive; after enc.close() its calls raise RuntimeError.
     With `window` = W >= 1 (1 <= W <= capacity, ValueError outside) the cache is a ring and the state is never full:
     positions are absolute and unbounded, the token at position t attends to positions max(0, t + 1 - W) .. t, and step() returns row
-    t of enc(track[: t + 1], is_causal=True, window=W) in bits for every dtype, alone or behind a prefill(), for any capacity >= W.
-    prefill() is then enc(x, lengths=lengths, is_causal=True, window=W) in bits, takes sequences longer than `capacity` (the ring
-    keeps their last `capacity` tokens) and leaves the tracks at their lengths."""
+    t of enc(track[: t + 1], is_causal=True, window=W), alone or behind a prefill(), for any capacity >= W -- with `window_mfma=0`
+    in bits for every dtype; on an encoder made with `window_mfma=1` in bits where that forward's attention is the generic kernel,
+    within the attention kernels' tolerances elsewhere (step() itself is always the generic order).
+    prefill() is then enc(x, lengths=lengths, is_causal=True, window=W) in bits under either value, takes sequences longer than
+    `capacity` (the ring keeps their last `capacity` tokens) and leaves the tracks at their lengths."""
 
     def __init__(self, enc: TransformerEncoder, tracks: int, capacity: int, window: int = 0):
         self.enc = enc

@@ -359,11 +359,20 @@ int flope_tf_forward(flope_tf_handle h, const float* x_dev, int batch, int seq_l
  *       banded [L, L] mask.  0 = no window.  Honoured only with "causal" = 1: with "causal" = 0 and W > 0, flope_tf_forward,
  *       _forward_varlen, _forward_plan, _attention and _attention_varlen return FLOPE_EINVAL with a message (a window without causal
  *       is refused).  With lengths the window lies inside each packed sequence; rows behind a sequence keep coming back as
- *       out_layer.bias.  Under a window EVERY attention launch is tf_attn_generic (its WINDOW instantiation, whatever the dtype and
- *       shape: flope_tf_attention* return FLOPE_TF_ATTN_GENERIC), keys outside the window are not loaded, the forward is always the
+ *       out_layer.bias.  Under a window, with "window_mfma" = 0, EVERY attention launch is tf_attn_generic (its WINDOW instantiation,
+ *       whatever the dtype and shape: flope_tf_attention* return FLOPE_TF_ATTN_GENERIC), keys outside the window are not loaded, the forward is always the
  *       launch sequence (flope_tf_forward_plan answers FLOPE_TF_FWD_LAUNCHES, "fused" is not taken), and flope_tf_forward_flops /
  *       _flops_varlen count attention over sum_t min(t + 1, W) keys per sequence.  W >= seq_len gives the bits of the generic causal
- *       kernel.  Windows inside tf_attn_mfma, tf_attn_tiled, tf_attn_f32m and tf_fused_f32 are a follow-up. */
+ *       kernel.  Windows inside tf_attn_f32m and tf_fused_f32 are a follow-up;
+ *   "window_mfma" (default 0; 0 or 1, FLOPE_EINVAL outside; returns the old value; stored and ignored by float32 handles, as
+ *       "attn_tiled" is): 1 = under "causal" = 1 and "window" > 0 a 16-bit launch whose pick without a window is tf_attn_mfma or
+ *       tf_attn_tiled stays on that kernel, its WINDOW instantiation: same grid, block and LDS, a wave starts at the
+ *       32-key step that holds its first query's first visible key, tf_attn_tiled does not load the 64-key blocks below the
+ *       workgroup's window, and flope_tf_attention* return FLOPE_TF_ATTN_MFMA64 / _TILED.  Every other launch under a window
+ *       (float32, option "generic", head dims without such a kernel, misaligned buffers) stays tf_attn_generic.  W >= seq_len gives
+ *       the bits of the same kernel under "causal" alone.  flope_tf_stream_step is untouched (tf_attn_step, the generic order), so
+ *       its rows equal the windowed forward's in bits where that forward's attention is tf_attn_generic and within the MFMA
+ *       kernels' tolerances elsewhere; _prefill stays the ragged windowed forward in bits.  With 0 every launch is as above. */
 int flope_tf_set_option(flope_tf_handle h, const char* name, int value);
 /* softmax(q k^T / sqrt(head_dim)) v per head on a caller's buffer: qkv_dev [batch, seq_len, 3*model_dim] and out_dev
  * [batch, seq_len, model_dim] in the handle's dtype (float32 for FLOPE_DT_F32).  Launches exactly what flope_tf_forward
