@@ -114,6 +114,7 @@ SIGNATURES = {
     "flope_tf_stream_position": (_I, [_P, _I]),
     "flope_tf_stream_step": (_I, [_P, _P, _I, C.POINTER(_I), _P, _P]),
     "flope_tf_stream_prefill": (_I, [_P, _P, _I, _I, C.POINTER(_I), C.POINTER(_I), _P, _P]),
+    "flope_tf_stream_extend": (_I, [_P, _P, _I, _I, C.POINTER(_I), C.POINTER(_I), _P, _P]),
 }
 
 _lib = None

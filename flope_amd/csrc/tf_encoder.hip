@@ -22,6 +22,8 @@
 // track, with tf_attn_step over a per-track cache of every layer's keys and values where the forward has its attention kernel
 // (the checks and launch shapes are in tf_encoder_stream.h).  flope_tf_stream_open_window: the same over a ring cache
 // with sliding-window attention, never full.
+// flope_tf_stream_extend: several tokens per track and call behind what the track holds -- the ragged launch sequence over the packed
+// chunks with tf_attn_extend over cache and chunk, tf_cache_append behind it in every layer; the bits of the same steps.
 #include "../../include/flope_amd.h"
 #include "common.h"
 #include "host_pack.h"
@@ -549,6 +551,158 @@ __global__ void tf_cache_fill(const V* __restrict__ qkv, V* __restrict__ cache, 
     if (i >= off[b + 1] - o || i >= capacity || (unsigned)t >= (unsigned)tracks) return;
     cache[((size_t)t * capacity + i) * 2 * dv + c] = qkv[(size_t)(o + i) * 3 * dv + dv + c];
   }
+}
+
+// ---- extend: several tokens per track and call (flope_tf_stream_extend) ----------------------------------------------
+// tf_attn_row<T, true(, true)> for the query at chunk row i of a sequence whose track holds pos0 tokens -- position p = pos0 + i, keys
+// lo .. p -- operation for operation, as tf_attn_step_row is: per key one fmaf chain over c = 0 .. dh - 1 from 0.f, * scale; lane l
+// takes keys lo + l, lo + l + 64, ..; wave_max, expf, wave_sum; per output dim one fmaf chain over j = lo .. p from 0.f; * (1 / sum),
+// float16 in one rounding (tf_mul_f16_bits).  The keys lie in up to three contiguous runs of rows: the cached keys lo .. pos0 - 1 in
+// rows slo .. of the track's cache and, where a ring wraps, from row 0 on (tf_stream_run0), then keys max(lo, pos0) .. p in the
+// chunk's own packed qkv rows, the query's among them -- never in a cache row this call writes (tf_cache_append runs behind this
+// kernel).  chunk: the head's q columns of the sequence's first packed row (rows of 3 d: q | k | v); kv: the head's k columns of
+// cache row 0 of the track (rows of 2 d: k | v); s: the wave's score row, key j at s[j - lo].
+template <typename T, bool VEC, bool WINDOW>
+__device__ __forceinline__ void tf_attn_extend_row(const T* chunk, const T* kv, T* orow, float* s, int pos0, int i, int d, int dh, float scale,
+                                                   int lane, int capacity, int W) {
+  typedef TfSlice<T, VEC> Sl;
+  constexpr int VE = Sl::VE;
+  const size_t ld = (size_t)2 * d, ldc = (size_t)3 * d;
+  const int p = pos0 + i;
+  int lo = 0, slo = 0;                            // first visible key and, where it is a cached one, its cache row
+  if constexpr (WINDOW) { lo = flope_tf_plan::tf_window_lo(p, W); slo = flope_tf_plan::tf_stream_slot(lo, capacity); }
+  const int nc = flope_tf_plan::tf_extend_cached(pos0, lo), c0 = flope_tf_plan::tf_extend_chunk0(pos0, lo);
+  const int L = p - lo + 1;                       // visible keys: nc cached ones, then chunk rows c0 .. i
+  const T* q = chunk + (size_t)i * ldc;
+  float mx = -INFINITY;
+  for (int j = lane; j < L; j += 64) {
+    const T* k;
+    if (j < nc) {
+      int row = j;
+      if constexpr (WINDOW) { row = slo + j; if (row >= capacity) row -= capacity; }
+      k = kv + (size_t)row * ld;
+    } else k = chunk + (size_t)(c0 + j - nc) * ldc + d;
+    float a = 0.f;
+    for (int c = 0; c < dh; c += VE) {
+      Sl qv, kx;
+      qv.load(q + c);
+      kx.load(k + c);
+#pragma unroll
+      for (int e = 0; e < VE; ++e) a = fmaf(qv.f[e], kx.f[e], a);
+    }
+    a *= scale;
+    s[j] = a;
+    mx = fmaxf(mx, a);
+  }
+  mx = wave_max(mx);
+  float sum = 0.f;
+  for (int j = lane; j < L; j += 64) { const float pr = expf(s[j] - mx); s[j] = pr; sum += pr; }
+  sum = wave_sum(sum);
+  __builtin_amdgcn_wave_barrier();
+  const float inv = 1.f / sum;
+  for (int c = lane * VE; c < dh; c += 64 * VE) {
+    float o[VE];
+#pragma unroll
+    for (int e = 0; e < VE; ++e) o[e] = 0.f;
+    // cnt consecutive rows of ldr elements from vr on, their probabilities from sp on, kTfStepUnroll loads in flight: the chain goes on in key order
+    auto run = [&](const T* vr, size_t ldr, const float* sp, int cnt) {
+      int j = 0;
+      for (; j + kTfStepUnroll <= cnt; j += kTfStepUnroll) {
+        Sl vv[kTfStepUnroll];
+#pragma unroll
+        for (int u = 0; u < kTfStepUnroll; ++u) vv[u].load(vr + (size_t)(j + u) * ldr);
+#pragma unroll
+        for (int u = 0; u < kTfStepUnroll; ++u) {
+          const float pr = sp[j + u];
+#pragma unroll
+          for (int e = 0; e < VE; ++e) o[e] = fmaf(pr, vv[u].f[e], o[e]);
+        }
+      }
+      for (; j < cnt; ++j) {
+        Sl vv;
+        vv.load(vr + (size_t)j * ldr);
+#pragma unroll
+        for (int e = 0; e < VE; ++e) o[e] = fmaf(sp[j], vv.f[e], o[e]);
+      }
+    };
+    const T* v = kv + d + c;
+    if constexpr (WINDOW) {
+      const int first = flope_tf_plan::tf_stream_run0(slo, nc, capacity);      // keys lo .. pos0 - 1: rows slo .., then rows 0 ..
+      run(v + (size_t)slo * ld, ld, s, first);
+      run(v, ld, s + first, nc - first);
+    } else run(v, ld, s, nc);                                                  // rows 0 .. pos0 - 1
+    run(chunk + (size_t)c0 * ldc + 2 * d + c, ldc, s + nc, L - nc);            // chunk rows c0 .. i
+    if constexpr (std::is_same<T, f16_t>::value) {      // one rounding per element, as tf_attn_row's store
+      if constexpr (VEC) {
+        u32x4 w;
+#pragma unroll
+        for (int e = 0; e < VE; e += 2) w[e / 2] = tf_mul_f16_bits(o[e], inv) | (tf_mul_f16_bits(o[e + 1], inv) << 16);
+        *(u32x4*)(orow + c) = w;
+      } else *(unsigned short*)(orow + c) = (unsigned short)tf_mul_f16_bits(o[0], inv);
+    } else {
+      Sl vv;
+#pragma unroll
+      for (int e = 0; e < VE; ++e) vv.f[e] = o[e] * inv;
+      vv.store(orow + c);
+    }
+  }
+  __builtin_amdgcn_wave_barrier();
+}
+
+// n sequences of a ragged batch (qkv: packed rows, sequence b = rows off[b] .. off[b + 1] - 1), each the next tokens of one track.
+// Workgroup (b, h) x blockIdx.y: its four waves take consecutive queries of that sequence and head, as tf_attn_generic<.., VARLEN>
+// does, so they stream the same cache rows -- in tf_attn_step every wave walks another track.  tab: (track, pos0) per sequence.
+// smax: floats of a wave's score row, the call's largest visible key count.  Reads the cache, writes att alone; a workgroup whose
+// table entry is no track, whose positions leave the cache (linear: pos0 + len > capacity; a ring: past INT_MAX, or a window that is
+// none of this cache's) or whose keys exceed the score row exits before it stores anything (tf_attn_step's rule).
+template <typename T, bool VEC, bool WINDOW>
+__global__ __launch_bounds__(256) void tf_attn_extend(const T* __restrict__ qkv, const T* __restrict__ cache, T* __restrict__ att,
+                                                      const int* __restrict__ tab, const int* __restrict__ off, int n, int d, int H, int tracks,
+                                                      int capacity, int smax, int W) {
+  extern __shared__ __attribute__((aligned(16))) float sc[];     // [waves][smax]
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int b = blockIdx.x / H, h = blockIdx.x - b * H, dh = d / H;
+  if (b >= n) return;
+  const int track = tab[2 * b], pos0 = tab[2 * b + 1];
+  const int o = off[b], len = off[b + 1] - o;
+  if ((unsigned)track >= (unsigned)tracks || pos0 < 0 || len < 1) return;
+  if constexpr (WINDOW) {
+    if (W < 1 || W > capacity || pos0 > INT_MAX - len || flope_tf_plan::tf_extend_keys(pos0, len, W) > smax) return;
+  } else {
+    if (pos0 > capacity - len || pos0 + len > smax) return;
+  }
+  const float scale = 1.f / sqrtf((float)dh);
+  const T* chunk = qkv + (size_t)o * 3 * d + h * dh;
+  const T* kv = cache + (size_t)track * capacity * 2 * d + h * dh;
+  float* s = sc + (size_t)wave * smax;
+  for (int i = blockIdx.y * flope_tf_plan::kTfStepWaves + wave; i < len; i += gridDim.y * flope_tf_plan::kTfStepWaves)
+    tf_attn_extend_row<T, VEC, WINDOW>(chunk, kv, att + (size_t)(o + i) * d + h * dh, s, pos0, i, d, dh, scale, lane, capacity, W);
+}
+
+// ... and the append behind it: the k | v columns of chunk row i of sequence b -> cache row pos0 + i of its track (a ring: row
+// (pos0 + i) % capacity, the chunk's last min(len, capacity) tokens only, tf_stream_append_writes -- every row once).  tf_cache_fill
+// with a start position per sequence: tab is tf_attn_extend's table, V and dv as there.  It runs BEHIND the layer's tf_attn_extend:
+// on a ring the token at p takes the row of key p - capacity, which an earlier query of the same chunk still sees once
+// len >= capacity - W + 2 (at capacity == W: every chunk of two tokens).  A sequence whose entry is no track or whose rows leave the
+// cache is skipped.
+template <typename V, bool WINDOW>
+__global__ void tf_cache_append(const V* __restrict__ qkv, V* __restrict__ cache, const int* __restrict__ off, const int* __restrict__ tab,
+                                int max_len, int dv, int tracks, int capacity, size_t total) {
+  const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= total) return;
+  const size_t r = idx / (2 * dv);
+  const int c = (int)(idx - r * (2 * dv)), b = (int)(r / max_len), i = (int)(r - (size_t)b * max_len);
+  const int o = off[b], len = off[b + 1] - o, t = tab[2 * b], pos0 = tab[2 * b + 1];
+  if (i >= len || (unsigned)t >= (unsigned)tracks || pos0 < 0) return;
+  int row;
+  if constexpr (WINDOW) {
+    if (pos0 > INT_MAX - len || !flope_tf_plan::tf_stream_append_writes(i, len, capacity)) return;
+    row = flope_tf_plan::tf_stream_append_slot(pos0, i, capacity);
+  } else {
+    if (pos0 > capacity - len) return;
+    row = pos0 + i;
+  }
+  cache[((size_t)t * capacity + row) * 2 * dv + c] = qkv[(size_t)(o + i) * 3 * dv + dv + c];
 }
 
 // ---- MFMA linear: Y[128-token tile][128-feature tile], K walked in 64-wide chunks ----------------------------
@@ -2216,6 +2370,36 @@ int run_prefill(flope_tf_stream_s* s, const float* x, int n, int L, const TfRagg
   });
 }
 
+// the ragged forward's launch sequence over the packed chunks, tf_attn_extend where it has launch_attention and each layer's k | v rows
+// appended to the cache BEHIND that attention (on a ring the append takes rows whose keys the chunk's earlier queries still read;
+// tf_encoder_stream.h).  smax: the call's largest visible key count (tf_stream_check_extend)
+template <typename T>
+int run_extend(flope_tf_stream_s* s, const float* x, int n, int L, const TfRagged& rg, int smax, float* y, hipStream_t st) {
+  flope_tf_encoder* e = s->e;
+  const size_t layer = (size_t)s->tracks * s->capacity * 2 * e->d;
+  const flope_tf_plan::TfExtendLaunch la = flope_tf_plan::tf_extend_launch(n, e->H, rg.max_len, smax);
+  const bool vec = flope_tf_plan::tf_cache_fill_vec_ok(e->d, (int)sizeof(T));
+  const int dv = vec ? e->d / flope_tf_plan::tf_stream_vec((int)sizeof(T)) : e->d;
+  const flope_tf_plan::TfStreamLaunch lc = flope_tf_plan::tf_cache_append_launch(n, rg.max_len, 2 * dv);
+  const size_t total = (size_t)n * rg.max_len * 2 * dv;
+  return run_forward_with<T>(e, x, n, L, y, st, &rg, [&](int li) {
+    T* cache = (T*)s->cache + (size_t)li * layer;
+#define TF_EXT(VEC_, WIN_) hipLaunchKernelGGL((tf_attn_extend<T, VEC_, WIN_>), dim3(la.grid_x, la.grid_y), dim3(la.block), la.lds, st, (const T*)e->qkv, (const T*)cache, \
+                                             (T*)e->att, (const int*)s->tab, (const int*)e->vl_off, n, e->d, e->H, s->tracks, s->capacity, smax, s->window)
+    if (flope_tf_plan::tf_step_vec_ok(e->d / e->H, (int)sizeof(T))) { if (s->window) TF_EXT(true, true); else TF_EXT(true, false); }
+    else { if (s->window) TF_EXT(false, true); else TF_EXT(false, false); }
+#undef TF_EXT
+    TF_HIP(e, hipGetLastError());
+#define TF_APP(V_, WIN_) hipLaunchKernelGGL((tf_cache_append<V_, WIN_>), dim3(lc.grid_x), dim3(lc.block), 0, st, (const V_*)e->qkv, (V_*)cache, (const int*)e->vl_off, \
+                                           (const int*)s->tab, rg.max_len, dv, s->tracks, s->capacity, total)
+    if (vec) { if (s->window) TF_APP(u32x4, true); else TF_APP(u32x4, false); }
+    else { if (s->window) TF_APP(T, true); else TF_APP(T, false); }
+#undef TF_APP
+    TF_HIP(e, hipGetLastError());
+    return 0;
+  });
+}
+
 }  // namespace
 
 namespace {
@@ -2343,6 +2527,45 @@ extern "C" int flope_tf_stream_prefill(flope_tf_stream s, const float* x_dev, in
   e->opt_causal = causal;
   e->opt_window = window;
   return rc;
+}
+
+extern "C" int flope_tf_stream_extend(flope_tf_stream s, const float* x_dev, int n, int seq_len, const int* lengths_host, const int* tracks_host, float* y_dev,
+                                      void* stream) {
+  const std::string who = "flope_tf_stream_extend";
+  flope_tf_encoder* e;
+  int rc, bad = -1, smax = 0;
+  if ((rc = tf_stream_enter(s, who, &e))) return rc;
+  if ((rc = tf_check_forward_varlen(e, who, n, seq_len, x_dev && y_dev))) return rc;
+  std::vector<int> full;                            // lengths_host NULL: every chunk has seq_len tokens
+  if (!lengths_host && n > 0) full.assign((size_t)n, seq_len);
+  const int* lengths = lengths_host ? lengths_host : full.data();
+  TfRagged rg;
+  if ((rc = tf_check_ragged(e, who.c_str(), lengths, n, seq_len, e->vl_host.data(), &rg))) return rc;
+  if ((rc = flope_tf_plan::tf_stream_check_extend(s->pos.data(), s->tracks, s->capacity, s->window, n, lengths, tracks_host, s->seen.data(), &bad, &smax))) {
+    if (rc == flope_tf_plan::kTfStreamRoom || rc == flope_tf_plan::kTfStreamFull) {
+      const int t = tf_stream_track(tracks_host, bad);
+      const std::string head = who + ": lengths[" + std::to_string(bad) + "] = " + std::to_string(lengths[bad]) + ": track " + std::to_string(t) + " holds " +
+                               std::to_string(s->pos[(size_t)t]) + " tokens, ";
+      if (rc == flope_tf_plan::kTfStreamRoom)
+        return tf_fail(e, FLOPE_EINVAL, head + "and the chunk would pass capacity = " + std::to_string(s->capacity) + " (reset the track, or open a state with more room)");
+      return tf_fail(e, FLOPE_EINVAL, head + "and the chunk would pass INT_MAX = " + std::to_string(INT_MAX) + ", the last position an int counts (reset the track)");
+    }
+    if (rc == flope_tf_plan::kTfStreamDuplicate)
+      return tf_fail(e, FLOPE_EINVAL, who + ": tracks[" + std::to_string(bad) + "] = " + std::to_string(tracks_host[bad]) +
+                                          " names a track an earlier sequence names (one sequence per track and call)");
+    return tf_stream_refuse(s, who, rc, bad, n, tracks_host, lengths, seq_len);
+  }
+  TF_HIP(e, hipSetDevice(e->device));
+  hipStream_t st = (hipStream_t)stream;
+  if ((rc = tf_upload_ragged(e, n, st))) return rc;
+  flope_tf_plan::tf_stream_extend_table(s->pos.data(), n, tracks_host, s->tab_host.data());
+  TF_HIP(e, hipMemcpyAsync(s->tab, s->tab_host.data(), (size_t)2 * n * sizeof(int), hipMemcpyHostToDevice, st));
+  // the positions move only once every launch is enqueued: a call that fails on the way (FLOPE_EHIP) leaves the tracks where they were.
+  // On a linear state the rows it may have written lie behind the positions, where nothing reads them; on a ring they may have taken
+  // the rows of keys a later window still holds, so reset the call's tracks after such a failure
+  if ((rc = tf_by_dtype(e, [&](auto tag) { return run_extend<typename decltype(tag)::type>(s, x_dev, n, seq_len, rg, smax, y_dev, st); }))) return rc;
+  flope_tf_plan::tf_stream_extend_advance(s->pos.data(), n, lengths, tracks_host);
+  return FLOPE_OK;
 }
 
 #ifdef FLOPE_STAG_DBG

@@ -4,6 +4,9 @@
 // against brute force on the CPU, tests/test_gpu_tf_stream.py the device against it).
 // Below them, the same for a windowed state (flope_tf_stream_open_window): a ring cache, absolute positions, keys
 // tf_window_lo(p, W) .. p -- new functions beside the old ones (tests/host_harness/harness_tf_window.cpp, tests/test_tf_window_host.py).
+// Below those, flope_tf_stream_extend: its checks, table, smax and advance for both kinds of state, the launches of
+// tf_attn_extend and tf_cache_append, where a chunk query's keys lie and which rows the append writes
+// (tests/host_harness/harness_tf_extend.cpp, tests/test_tf_extend_host.py).
 #pragma once
 
 #include <limits.h>
@@ -158,5 +161,65 @@ inline int tf_stream_check_prefill_window(int tracks, int n, const int* rows, ch
 // ... and which tokens tf_cache_fill writes: token i of len goes to row i % capacity only if no later token of the sequence takes
 // that row, so every row is written at most once
 constexpr bool tf_stream_fill_writes(int i, int len, int capacity) { return i >= 0 && i < len && i >= len - capacity; }
+
+// ---- extend: several tokens per track in one call, behind what the track holds ----------------------------------------
+// Sequence b of the call is the next len tokens of its track, which holds pos0: the token at chunk row i takes position p = pos0 + i
+// and attends to keys lo .. p, lo = tf_window_lo(p, W) (W = 0: a linear state, lo = 0).  Keys lo .. pos0 - 1 lie in the cache (rows j,
+// or j % capacity of a ring), keys max(lo, pos0) .. p in the chunk's own packed qkv rows -- the query's own key among them.
+// How many of query p's keys are cached ones, and the chunk row of its first key that is not
+constexpr int tf_extend_cached(int pos0, int lo) { return lo < pos0 ? pos0 - lo : 0; }
+constexpr int tf_extend_chunk0(int pos0, int lo) { return lo > pos0 ? lo - pos0 : 0; }
+// ... and the largest visible key count of a sequence (its last query's), which sizes the score rows: tf_step_lds(smax - 1) bytes
+constexpr int tf_extend_keys(int pos0, int len, int W) { return tf_window_keys(pos0 + len - 1, W); }
+
+// tf_attn_extend: workgroup (sequence b, head h) x a slice of the queries, one query per wave and trip -- grid (n H, min(ceil(max_len
+// / 4), 64)), so the four waves of a workgroup walk the same cache rows
+constexpr int kTfExtendGridY = 64;
+struct TfExtendLaunch { unsigned grid_x, grid_y, block; size_t lds; };
+inline TfExtendLaunch tf_extend_launch(int n, int H, int max_len, int smax) {
+  const int gy = (max_len + kTfStepWaves - 1) / kTfStepWaves;
+  return {(unsigned)n * (unsigned)H, (unsigned)(gy < kTfExtendGridY ? gy : kTfExtendGridY), 64u * kTfStepWaves, tf_step_lds(smax - 1)};
+}
+// tf_cache_append: tf_cache_fill's geometry, one thread per unit of the k | v columns of the n x max_len rows the chunks may hold
+inline TfStreamLaunch tf_cache_append_launch(int n, int max_len, int units) { return tf_cache_fill_launch(n, max_len, units); }
+
+// Which chunk tokens the append writes, and where: tf_stream_fill_writes with a start position.  Token i of a chunk of len tokens at
+// pos0 goes to row (pos0 + i) % capacity only if no later token of the chunk takes that row -- the last min(len, capacity) tokens --
+// so every row is written at most once; pos0 = 0 is the prefill's rule.  A linear state writes every token, to row pos0 + i (the check
+// below keeps that below capacity, where the two rules are one).
+// THE APPEND RUNS BEHIND THE LAYER'S ATTENTION, never in front of it as the prefill's fill does: on a ring the chunk's token at p takes
+// the row of key p - capacity, and query q < p of the same chunk still sees that key when p - capacity >= tf_window_lo(q, W) -- with
+// q = pos0 and p = pos0 + len - 1 that is len >= capacity - W + 2, every chunk of two tokens at capacity == W.
+constexpr bool tf_stream_append_writes(int i, int len, int capacity) { return tf_stream_fill_writes(i, len, capacity); }
+constexpr int tf_stream_append_slot(int pos0, int i, int capacity) { return tf_stream_slot(pos0 + i, capacity); }
+
+enum {
+  kTfStreamRoom = -7        // extend, linear state: the track of sequence *bad holds pos and pos + lengths[*bad] > capacity
+};
+
+// extend: n sequences for n distinct tracks (tf_stream_check_rows as for prefill); lengths are 1 .. seq_len and sum to <= max_tokens
+// by tf_varlen_plan, which the caller runs in front of this.  window = 0: every track has room for its chunk (kTfStreamRoom
+// otherwise); a windowed state: pos + len stays an int (kTfStreamFull otherwise) -- a chunk may be longer than the capacity.
+// *smax: the call's largest visible key count.  Writes nothing but *bad / *smax and the scratch.
+inline int tf_stream_check_extend(const int* pos, int tracks, int capacity, int window, int n, const int* lengths, const int* rows, char* seen,
+                                  int* bad, int* smax) {
+  const int rc = tf_stream_check_rows(tracks, tracks, n, rows, seen, bad);
+  if (rc) return rc;
+  int mx = 0;
+  for (int b = 0; b < n; ++b) {
+    const int p = pos[tf_stream_track(rows, b)], len = lengths[b];
+    if (window) { if (p > INT_MAX - len) { *bad = b; return kTfStreamFull; } }
+    else if (p > capacity - len) { *bad = b; return kTfStreamRoom; }
+    const int vis = tf_extend_keys(p, len, window);
+    if (vis > mx) mx = vis;
+  }
+  *smax = mx;
+  return kTfStreamOk;
+}
+// ... its device table, (track, pos0) per sequence, and the positions behind it
+inline void tf_stream_extend_table(const int* pos, int n, const int* rows, int* tab) { tf_stream_step_table(pos, n, rows, tab); }
+inline void tf_stream_extend_advance(int* pos, int n, const int* lengths, const int* rows) {
+  for (int b = 0; b < n; ++b) pos[tf_stream_track(rows, b)] += lengths[b];
+}
 
 }  // namespace flope_tf_plan

@@ -435,7 +435,8 @@ class TransformerEncoder:
 
     def open_stream(self, tracks: int, capacity: int, window: int = 0) -> "TransformerEncoderStream":
         """A stream state for `tracks` live tracks of up to `capacity` tokens each (TransformerEncoderStream): feed one new token per
-        track with step() and get the row a causal forward of the whole track would end with, without running it again.
+        track with step() and get the row a causal forward of the whole track would end with, without running it again;
+        extend() appends several tokens per track in one call, with the bits of those steps.
         `window=W` (1 <= W <= capacity): sliding-window attention over a ring cache -- a track is never full, positions are absolute,
         and step() at position t returns row t of enc(track[: t + 1], is_causal=True, window=W), bit for bit with `window_mfma=0`
         (with `window_mfma=1`: in bits where that forward's attention is the generic kernel, within the attention kernels'
@@ -473,7 +474,9 @@ class TransformerEncoderStream:
     layer's keys and values of each track's tokens so far, up to `capacity` per track, and the number of tokens each track holds
     (`positions`).  step() takes one new token per track and returns the encoder's output for it: the row enc(track, is_causal=True)
     would end with -- in bits where that forward's attention runs the generic kernel, within the attention kernels' tolerances
-    elsewhere.  prefill() loads whole histories in one causal forward.  The calls on one state run on the current stream in
+    elsewhere.  prefill() loads whole histories in one causal forward.  extend() appends several tokens per track behind what the
+    track holds, in one ragged launch sequence: its rows and the cache it leaves are, in bits, those of the same tokens
+    fed by step() one at a time, in every dtype, on linear and windowed states alike.  The calls on one state run on the current stream in
     program order; keep them on one stream.  The state keeps its encoder alive; after enc.close() its calls raise RuntimeError.
     With `window` = W >= 1 (1 <= W <= capacity, ValueError outside) the cache is a ring and the state is never full:
     positions are absolute and unbounded, the token at position t attends to positions max(0, t + 1 - W) .. t, and step() returns row
@@ -550,6 +553,30 @@ class TransformerEncoderStream:
         y = self._out(out, (n, L, enc.dims[2]))
         with torch.cuda.device(enc.device):
             rc = enc.lib.flope_tf_stream_prefill(self.state, x.data_ptr(), n, L, lh, th, y.data_ptr(), _stream_ptr(enc.device))
+        enc._check_arg(rc)
+        self._keep = x
+        return y
+
+    def extend(self, x: torch.Tensor, lengths=None, tracks=None, out: torch.Tensor = None) -> torch.Tensor:
+        """Appends several tokens per track in one call.  x [n, L, input_dim], sequence b the NEXT lengths[b] tokens
+        (1 .. L, right-padded; None: all L) of track tracks[b] (None as in step), behind whatever the track holds -> [n, L, out_dim]:
+        row i of sequence b is what step() would return for that token, bit for bit in every dtype and under every option, and the
+        tracks end as the same steps would leave them, so any split of a track into extend() / step() calls gives the same bits.
+        Rows behind a length are out_layer.bias.  Tracks must be distinct; on a linear state position + length must stay within the
+        capacity (ValueError names the offending index; nothing has moved then), a windowed state takes chunks of any length (the
+        ring keeps the last `capacity` tokens).
+        `out`: a float32 [n, L, out_dim] contiguous tensor to write into."""
+        self._live()
+        enc = self.enc
+        x = self._check_x(x, 3)
+        n, L = x.shape[0], x.shape[1]
+        cnt, th = _host_tracks(tracks)
+        if cnt is not None and cnt != n:
+            raise ValueError(f"tracks has {cnt} values for {n} sequences")
+        lh = None if lengths is None else _host_lengths(lengths, n)
+        y = self._out(out, (n, L, enc.dims[2]))
+        with torch.cuda.device(enc.device):
+            rc = enc.lib.flope_tf_stream_extend(self.state, x.data_ptr(), n, L, lh, th, y.data_ptr(), _stream_ptr(enc.device))
         enc._check_arg(rc)
         self._keep = x
         return y

@@ -478,7 +478,27 @@ double flope_tf_forward_flops_varlen(flope_tf_handle h, int batch, const int* le
  *   _prefill  the ragged forward under "causal" = 1 and "window" = window, in bits; lengths are limited by flope_tf_forward_varlen
  *             alone, not by capacity: of a sequence of len tokens the last min(len, capacity) go to the ring (token i to row
  *             i % capacity), and the track is left at position len.  Options "causal" and "window" are as they were on return.
- * flope_tf_stream_open is window = 0: the linear cache and the refusals above. */
+ * flope_tf_stream_open is window = 0: the linear cache and the refusals above.
+ *   _extend    appends SEVERAL tokens per track in one call, behind what the track holds: x_dev float32 [n, seq_len,
+ *             input_dim] -> y_dev [n, seq_len, out_dim], sequence b being the next lengths_host[b] tokens (1 .. seq_len, right-padded;
+ *             NULL: all seq_len) of track tracks_host[b] (NULL as above).  The token at chunk row i takes position p = position + i and
+ *             attends to keys 0 .. p of its track (a windowed state: max(0, p + 1 - window) .. p): those below the track's position
+ *             from the cache, the chunk's own -- the query's among them -- from the call's packed qkv rows, never from a cache row the
+ *             call writes.  The chunks run packed as one ragged launch sequence: the linears, LayerNorms, gather and scatter of
+ *             flope_tf_forward_varlen at sum(lengths) rows, tf_attn_extend in place of the attention kernel (one wave per query, the
+ *             four waves of a workgroup on consecutive queries of one sequence and head, tf_attn_generic's causal order), and behind
+ *             it in every layer tf_cache_append, which copies the chunk's k and v to rows position + i (a ring: (position + i) %
+ *             capacity, the chunk's last min(length, capacity) tokens).  Afterwards the track holds position + length tokens and a
+ *             later _step or _extend continues it.  y_dev's valid rows are, bit for bit, for every dtype and option, what _step
+ *             returns for the same tokens fed one call at a time, and so is the cache; any split of a track into chunks gives the same
+ *             bits; hence they are rows position .. position + length - 1 of the causal (windowed) forward of the track wherever _step's
+ *             are.  Rows behind a length come back as out_layer's bias, as from flope_tf_forward_varlen.  Refused with FLOPE_EINVAL,
+ *             before anything is enqueued or any position moves, the offending index in the message: n outside 1 .. tracks (or
+ *             tracks_host NULL with n != tracks), a track out of range or named twice, a length outside 1 .. seq_len, sum(lengths) >
+ *             max_tokens, NULL buffers; a linear state: position + length > capacity; a windowed state: position + length > INT_MAX
+ *             (a chunk may be longer than capacity: the ring keeps its last capacity tokens).  FLOPE_ESTATE without weights or after
+ *             flope_tf_destroy.  Neither reads nor writes options "causal" / "window" or what flope_tf_last_forward reports, and
+ *             never runs the single launch of option "fused". */
 typedef struct flope_tf_stream_s* flope_tf_stream;
 int flope_tf_stream_open(flope_tf_handle h, int tracks, int capacity, flope_tf_stream* out);
 int flope_tf_stream_open_window(flope_tf_handle h, int tracks, int capacity, int window, flope_tf_stream* out);
@@ -489,6 +509,8 @@ int flope_tf_stream_position(flope_tf_stream s, int track);
 int flope_tf_stream_step(flope_tf_stream s, const float* x_dev, int n, const int* tracks_host, float* y_dev, void* stream);
 int flope_tf_stream_prefill(flope_tf_stream s, const float* x_dev, int n, int seq_len, const int* lengths_host, const int* tracks_host,
                             float* y_dev, void* stream);
+int flope_tf_stream_extend(flope_tf_stream s, const float* x_dev, int n, int seq_len, const int* lengths_host, const int* tracks_host,
+                           float* y_dev, void* stream);
 
 /* ---- YOLO11-seg detector front end ---------------------------------------------------
  * Replaces `self.yolo = YOLO(yolo_path)` (sunflower/predictor/fast_pose_predictor.py:36) and the
