@@ -88,6 +88,9 @@ SIGNATURES = {
     "flope_yolo_forward": (_I, [_P, _P, _P]),
     "flope_yolo_read_tensor": (_I, [_P, C.c_char_p, _P, C.POINTER(C.c_int64), _P]),
     "flope_yolo_set_option": (_I, [_P, C.c_char_p, _I]),
+    "flope_yolo_op_count": (_I, [_P]),
+    "flope_yolo_op_info": (_I, [_P, _I, C.c_char_p, _I]),
+    "flope_yolo_forward_ops": (_I, [_P, _P, _I, _P]),
     "flope_yolo_profile": (_I, [_P, _P, _I, C.c_char_p, _I, _P]),
     "flope_yolo_flops": (_D, [_P]),
     "flope_yolo_launches": (_I, [_P]),

@@ -19,6 +19,7 @@
 #include "host_pack.h"
 
 #include <algorithm>
+#include <stdio.h>
 
 namespace {
 
@@ -1434,6 +1435,15 @@ extern "C" int flope_yconv_launch(const YConvP* p, int dtype, int nt, int tile, 
   return (int)hipGetLastError();
 }
 
+// test hook (flope_yolo_op_info): the form flope_yconv_launch gives this conv, from the same geometry
+extern "C" int flope_yconv_path(const YConvP* p, int nt, int tile, char* text, int cap) {
+  bool splitk; int nbx, nby, lds;
+  YConvP q;
+  if (!yconv_geometry(p, nt, tile, &q, &splitk, &nbx, &nby, &lds)) return (int)hipErrorInvalidValue;
+  snprintf(text, (size_t)cap, "nt%d.%s.%s.mode%d", nt, p->k == 3 ? "3x3" : "1x1", splitk ? "splitk" : q.tile ? "tile" : "plain", p->out_mode);
+  return 0;
+}
+
 // ---- several independent ops in one grid (ymulti_kernel) ---------------------------------------------------------
 extern "C" int flope_ymulti_add_conv(YMultiP* m, const YConvP* p, int nt, int tile) {
   bool splitk; int nbx, nby, lds;
@@ -1486,6 +1496,15 @@ extern "C" int flope_ybneck_launch(const YConvP* c1, int nt1, const YConvP* c2, 
   if (dtype == 0) ybneck_go<bf16_t>(b, code, tiles, lds, (hipStream_t)stream); else ybneck_go<f16_t>(b, code, tiles, lds, (hipStream_t)stream);
   return (int)hipGetLastError();
 }
+// test hook: the instantiation and tile height flope_ybneck_launch takes
+extern "C" int flope_ybneck_path(const YConvP* c1, int nt1, const YConvP* c2, int nt2, char* text, int cap) {
+  int lds, tiles;
+  const int code = ybneck_code(c1, nt1, c2, nt2, &lds, &tiles);
+  if (code < 0) return (int)hipErrorInvalidValue;
+  YBneckP b; ybneck_fill(&b, c1, c2);
+  snprintf(text, (size_t)cap, "bneck.code%d.th%d", code, b.th);
+  return 0;
+}
 extern "C" int flope_ymulti_add_bneck(YMultiP* m, const YConvP* c1, int nt1, const YConvP* c2, int nt2) {
   int lds, tiles;
   const int code = ybneck_code(c1, nt1, c2, nt2, &lds, &tiles);
@@ -1521,11 +1540,14 @@ extern "C" int flope_ydw_launch(const YDwP* p, int dtype, void* stream) {
 }
 
 constexpr size_t kYSppfLdsMax = 144 * 1024;
+static size_t ypool_lds_bytes(const YPoolP* p) { return (size_t)2 * p->H * p->W * 16; }
+static bool ypool_in_lds(const YPoolP* p, int use_lds) { return use_lds && ypool_lds_bytes(p) <= kYSppfLdsMax; }
+extern "C" int flope_ypool_path(const YPoolP* p, int use_lds) { return ypool_in_lds(p, use_lds) ? 1 : 0; }   // test hook: 1 = LDS kernel, 0 = ring
 // use_lds = 0: the ring kernel for every map (the reference path of the LDS kernel)
 extern "C" int flope_ypool_launch(const YPoolP* p, int dtype, int use_lds, void* stream) {
   if (p->C % 8 || p->n < 1 || p->n > 3) return (int)hipErrorInvalidValue;
-  const size_t lds = (size_t)2 * p->H * p->W * 16;
-  if (use_lds && lds <= kYSppfLdsMax) {
+  const size_t lds = ypool_lds_bytes(p);
+  if (ypool_in_lds(p, use_lds)) {
     YDISPATCH(dtype, ysppf_lds_kernel, dim3(p->C / 8), dim3(256), lds, (hipStream_t)stream, *p);
     return (int)hipGetLastError();
   }
@@ -1560,12 +1582,14 @@ extern "C" int flope_yattn_init() {
   return (int)e;
 }
 
+static size_t yattn_mfma_lds(const YAttnP* p) { return (size_t)64 * ((p->N + 31) / 32 * 64 + 16); }
+static bool yattn_is_mfma(const YAttnP* p, int variant) { return variant == 0 && yattn_mfma_lds(p) <= 160 * 1024; }
+extern "C" int flope_yattn_path(const YAttnP* p, int variant) { return yattn_is_mfma(p, variant) ? 1 : 0; }   // test hook: 1 = MFMA kernel, 0 = generic
 // variant: 0 = automatic (MFMA kernel while the head's V^T fits LDS, N <= 1280), 1 = force the generic fp32 kernel
 extern "C" int flope_yattn_launch(const YAttnP* p, int dtype, int variant, void* stream) {
   if (p->N < 1) return (int)hipErrorInvalidValue;
-  const int NB = (p->N + 31) / 32;
-  const size_t lds_m = (size_t)64 * (NB * 64 + 16);
-  if (variant == 0 && lds_m <= 160 * 1024) {
+  const size_t lds_m = yattn_mfma_lds(p);
+  if (yattn_is_mfma(p, variant)) {
     YDISPATCH(dtype, yattn_mfma_kernel, dim3((p->N + 63) / 64, p->heads), dim3(256), lds_m, (hipStream_t)stream, *p);
     return (int)hipGetLastError();
   }

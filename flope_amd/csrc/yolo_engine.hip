@@ -55,6 +55,14 @@ extern "C" int flope_y32_pool_init();
 extern "C" int flope_y32_attn_launch(const YAttnP* p, void* stream);
 extern "C" int flope_y32m_attn_launch(const YAttnP* p, void* stream);
 extern "C" int flope_y32_letter_launch(const YLetterP* p, void* stream);
+// test hooks beside the launchers: the kernel form a launch takes, from the launcher's own geometry (flope_yolo_op_info)
+extern "C" int flope_yconv_path(const YConvP* p, int nt, int tile, char* text, int cap);
+extern "C" int flope_ybneck_path(const YConvP* c1, int nt1, const YConvP* c2, int nt2, char* text, int cap);
+extern "C" int flope_ypool_path(const YPoolP* p, int use_lds);
+extern "C" int flope_yattn_path(const YAttnP* p, int variant);
+extern "C" int flope_y32m_conv_path(const YConvP* p, char* text, int cap);
+extern "C" int flope_y32_pool_path(const YPoolP* p);
+extern "C" int flope_y32m_attn_path(const YAttnP* p);
 
 using namespace flope_host;
 
@@ -72,6 +80,7 @@ struct Rng { int t, c0, c1; };                 // what an op touches: channels [
 struct Op {
   enum Kind { CONV, DW, POOL, UP, ATTN, BNECK } kind;     // BNECK: Bottleneck cv1 -> cv2 (conv, conv2), one fused launch
   int nt = 4, nt2 = 4;
+  int cin_w = 0, cin_w2 = 0;      // input channels the weight tensor really has (model.0: 3 of the 8 stored)
   int level = 0;                  // longest dependency chain before this op (ops of one level are independent)
   YConvP conv, conv2; YDwP dw; YPoolP pool; YUpP up; YAttnP attn;
   std::vector<Rng> reads, writes;
@@ -273,7 +282,7 @@ struct Builder {
 
   void emit_conv(const std::string& p, const std::vector<float>& wf, const std::vector<float>& bf, int co, int cin, int k,
                  const View& in, const View& out, int stride, int act, const View* res, int out_mode, float* f32_out, int f32_ld) {
-    Op op; op.kind = Op::CONV; op.name = p;
+    Op op; op.kind = Op::CONV; op.name = p; op.cin_w = cin;
     const int rows = out_mode == 2 ? 4 * (co / 4) : co;
     op.nt = pick_nt(out_mode == 2 ? co / 4 : co);
     YConvP& c = op.conv; memset(&c, 0, sizeof c);
@@ -386,6 +395,7 @@ struct Builder {
     const Op& o1 = e->ops[e->ops.size() - 2];
     if (f32() || o1.kind != Op::CONV || o2.kind != Op::CONV || !flope_ybneck_fusable(&o1.conv, o1.nt, &o2.conv, o2.nt)) return;
     Op f; f.kind = Op::BNECK; f.name = p; f.conv = o1.conv; f.conv2 = o2.conv; f.nt = o1.nt; f.nt2 = o2.nt;
+    f.cin_w = o1.cin_w; f.cin_w2 = o2.cin_w;
     f.reads = o1.reads;                                   // the intermediate map never leaves the workgroup
     for (const Rng& r : o2.reads)
       if (r.t != t) f.reads.push_back(r);
@@ -459,10 +469,13 @@ struct Builder {
   }
 };
 
+// float32 mode: does this conv run on the MFMA kernel?  (a shape it does not take, or f32mfma = 0: the plain kernel)
+inline bool conv32_on_mfma(const flope_yolo* e, const YConvP& c) { return e->opt_f32mfma && flope_y32m_conv_ok(&c); }
+
 int launch_op(flope_yolo* e, const Op& op, hipStream_t st) {
   if (e->dtype == FLOPE_DT_F32) {
     switch (op.kind) {
-      case Op::CONV: return (e->opt_f32mfma && flope_y32m_conv_ok(&op.conv)) ? flope_y32m_conv_launch(&op.conv, st) : flope_y32_conv_launch(&op.conv, st);   // (a shape the MFMA kernel does not take: the plain kernel)
+      case Op::CONV: return conv32_on_mfma(e, op.conv) ? flope_y32m_conv_launch(&op.conv, st) : flope_y32_conv_launch(&op.conv, st);   // (a shape the MFMA kernel does not take: the plain kernel)
       case Op::DW: return flope_y32_dw_launch(&op.dw, st);
       case Op::POOL: return flope_y32_pool_launch(&op.pool, st);
       case Op::UP: return flope_y32_up_launch(&op.up, st);
@@ -857,12 +870,144 @@ extern "C" int flope_yolo_detect(flope_yolo_handle e, const uint8_t* frame_dev, 
   return FLOPE_OK;
 }
 
+// ---- per-op test hook: every op's views as taps, its launch form as text, and a forward that stops after n ops -----------
+namespace {
+
+// "op<i>.in" / ".res" (conv residual) / ".add" (depthwise addend) / ".mid" (fused Bottleneck: cv1's own output map, written only
+// with bneck = 0) / ".out" -> the view, from the launch parameters themselves
+bool op_tap(const flope_yolo* e, const char* name, Tap* t) {
+  int i = -1, used = 0;
+  if (sscanf(name, "op%d.%n", &i, &used) != 1 || used == 0 || i < 0 || i >= (int)e->ops.size()) return false;
+  const std::string what = name + used;
+  const Op& op = e->ops[i];
+  const int f32 = e->dtype == FLOPE_DT_F32 ? 1 : 0;
+  auto set = [&](const void* ptr, int H, int W, int C, int ld, int is_f32) { t->ptr = ptr; t->H = H; t->W = W; t->C = C; t->ld = ld; t->is_f32 = is_f32; return ptr != nullptr; };
+  auto conv_out = [&](const YConvP& c) {
+    if (c.out_mode == 1) return set(c.out, c.Ho, c.Wo, c.Cout, c.ldo, 1);          // the float32 slice of the prediction rows
+    if (c.out_mode == 2) return set(c.out, 2 * c.Ho, 2 * c.Wo, c.dc, c.ldo, f32);
+    return set(c.out, c.Ho, c.Wo, c.Cout, c.ldo, f32);
+  };
+  switch (op.kind) {
+    case Op::CONV: case Op::BNECK: {
+      const YConvP& last = op.kind == Op::BNECK ? op.conv2 : op.conv;
+      if (what == "in") return set(op.conv.in, op.conv.Hi, op.conv.Wi, op.conv.Cin, op.conv.ldi, f32);
+      if (what == "res") return set(last.res, last.Ho, last.Wo, last.Cout, last.ldr, f32);
+      if (what == "mid" && op.kind == Op::BNECK) return conv_out(op.conv);
+      if (what == "out") return conv_out(last);
+      return false;
+    }
+    case Op::DW: {
+      const YDwP& d = op.dw;
+      if (what == "in") return set(d.in, d.H, d.W, d.blk ? (d.C / d.blk) * d.blk_stride : d.C, d.ldi, f32);
+      if (what == "add") return set(d.add, d.H, d.W, d.C, d.lda, f32);
+      if (what == "out") return set(d.out, d.H, d.W, d.C, d.ldo, f32);
+      return false;
+    }
+    case Op::POOL:
+      if (what == "in") return set(op.pool.in, op.pool.H, op.pool.W, op.pool.C, op.pool.ldi, f32);
+      if (what == "out") return set(op.pool.out, op.pool.H, op.pool.W, op.pool.n * op.pool.C, op.pool.ldo, f32);
+      return false;
+    case Op::UP:
+      if (what == "in") return set(op.up.in, op.up.H, op.up.W, op.up.C, op.up.ldi, f32);
+      if (what == "out") return set(op.up.out, 2 * op.up.H, 2 * op.up.W, op.up.C, op.up.ldo, f32);
+      return false;
+    case Op::ATTN:
+      if (what == "in") return set(op.attn.qkv, 1, op.attn.N, op.attn.heads * 128, op.attn.ld, f32);
+      if (what == "out") return set(op.attn.out, 1, op.attn.N, op.attn.heads * 64, op.attn.ldo, f32);
+      return false;
+  }
+  return false;
+}
+
+std::string conv_text(const YConvP& c, int cin_w) {
+  char b[256];
+  snprintf(b, sizeof b, "k=%d s=%d act=%d Hi=%d Wi=%d Cin=%d cin_w=%d Ho=%d Wo=%d Cout=%d mode=%d dc=%d res=%d", c.k, c.stride, c.act, c.Hi, c.Wi, c.Cin,
+           cin_w, c.Ho, c.Wo, c.Cout, c.out_mode, c.dc, c.res ? 1 : 0);
+  return b;
+}
+
+// the kernel form launch_op gives a 16-bit / float32 conv, in the launchers' own words
+std::string conv_path(const flope_yolo* e, const YConvP& c, int nt) {
+  char b[96] = "invalid";
+  if (e->dtype != FLOPE_DT_F32) { flope_yconv_path(&c, nt, e->opt_tile, b, sizeof b); return b; }
+  if (conv32_on_mfma(e, c)) { flope_y32m_conv_path(&c, b, sizeof b); return b; }
+  snprintf(b, sizeof b, "y32.%s.mode%d", e->opt_f32mfma ? "fallback" : "plain", c.out_mode);
+  return b;
+}
+
+}  // namespace
+
+extern "C" int flope_yolo_op_count(flope_yolo_handle e) { return e && e->loaded ? (int)e->ops.size() : 0; }
+
+extern "C" int flope_yolo_op_info(flope_yolo_handle e, int i, char* text, int cap) {
+  if (!e || !text || cap < 64) return yfail(e, FLOPE_EINVAL, "flope_yolo_op_info: bad argument");
+  if (!e->loaded) return yfail(e, FLOPE_ESTATE, "flope_yolo_op_info before flope_yolo_load_weights");
+  if (i < 0 || i >= (int)e->ops.size()) return yfail(e, FLOPE_EINVAL, "flope_yolo_op_info: op index out of range");
+  const Op& op = e->ops[i];
+  const bool f32 = e->dtype == FLOPE_DT_F32;
+  std::string t, path;
+  char b[256];
+  switch (op.kind) {
+    case Op::CONV:
+      t = "kind=conv name=" + op.name + " " + conv_text(op.conv, op.cin_w);
+      path = conv_path(e, op.conv, op.nt);
+      break;
+    case Op::BNECK: {
+      t = "kind=bneck name=" + op.name + " " + conv_text(op.conv, op.cin_w) + " | " + conv_text(op.conv2, op.cin_w2);
+      if (e->opt_bneck) { char pb[96] = "invalid"; flope_ybneck_path(&op.conv, op.nt, &op.conv2, op.nt2, pb, sizeof pb); path = pb; }
+      else path = conv_path(e, op.conv, op.nt) + "+" + conv_path(e, op.conv2, op.nt2);     // launch_op: two conv launches
+      break;
+    }
+    case Op::DW:
+      snprintf(b, sizeof b, "H=%d W=%d C=%d act=%d add=%d blk=%d blk_stride=%d blk_off=%d", op.dw.H, op.dw.W, op.dw.C, op.dw.act, op.dw.add ? 1 : 0,
+               op.dw.blk, op.dw.blk_stride, op.dw.blk_off);
+      t = "kind=dw name=" + op.name + " " + b;
+      path = f32 ? "y32.dw" : "dw";
+      break;
+    case Op::POOL:
+      snprintf(b, sizeof b, "H=%d W=%d C=%d n=%d", op.pool.H, op.pool.W, op.pool.C, op.pool.n);
+      t = std::string("kind=pool name=maxpool5 ") + b;
+      path = f32 ? (flope_y32_pool_path(&op.pool) ? "y32.pool.lds" : "y32.pool.sweep") : (flope_ypool_path(&op.pool, e->opt_pool_lds) ? "pool.lds" : "pool.ring");
+      break;
+    case Op::UP:
+      snprintf(b, sizeof b, "H=%d W=%d C=%d", op.up.H, op.up.W, op.up.C);
+      t = std::string("kind=up name=upsample2x ") + b;
+      path = f32 ? "y32.up" : "up";
+      break;
+    case Op::ATTN:
+      snprintf(b, sizeof b, "N=%d heads=%d scale=%.9g", op.attn.N, op.attn.heads, (double)op.attn.scale);
+      t = "kind=attn name=" + op.name + " " + b;
+      path = f32 ? (!e->opt_f32mfma ? "y32.attn" : flope_y32m_attn_path(&op.attn) ? "y32m.attn" : "y32.attn.fallback") : (flope_yattn_path(&op.attn, e->opt_generic_attn) ? "attn.mfma" : "attn.generic");
+      break;
+  }
+  t += " path=" + path;
+  if ((int)t.size() + 1 > cap) return yfail(e, FLOPE_EINVAL, "flope_yolo_op_info: text buffer too small");
+  snprintf(text, (size_t)cap, "%s", t.c_str());
+  return FLOPE_OK;
+}
+
+extern "C" int flope_yolo_forward_ops(flope_yolo_handle e, const uint8_t* frame_dev, int n, void* stream) {
+  if (!e) return yfail(nullptr, FLOPE_EINVAL, "flope_yolo_forward_ops: NULL handle");
+  if (!e->loaded) return yfail(e, FLOPE_ESTATE, "flope_yolo_forward_ops before flope_yolo_load_weights");
+  if (!frame_dev || n < 0 || n > (int)e->ops.size()) return yfail(e, FLOPE_EINVAL, "flope_yolo_forward_ops: bad argument");
+  Y_TRY(e, hipSetDevice(e->device));
+  YLetterP L = e->letter; L.frame = frame_dev;
+  int s = e->dtype == FLOPE_DT_F32 ? flope_y32_letter_launch(&L, stream) : flope_yletter_launch(&L, e->dtype, stream);
+  if (s) return yfail(e, FLOPE_EHIP, std::string("letterbox: ") + hipGetErrorString((hipError_t)s));
+  for (int i = 0; i < n; ++i) {
+    s = launch_one(e, e->sched[0][i], (hipStream_t)stream);
+    if (s) return yfail(e, FLOPE_EHIP, launch_name(e, e->sched[0][i]) + ": " + hipGetErrorString((hipError_t)s));
+  }
+  return FLOPE_OK;
+}
+
 extern "C" int flope_yolo_read_tensor(flope_yolo_handle e, const char* name, float* dst_dev, int64_t* dims_out, void* stream) {
   if (!e || !name || !dims_out) return yfail(e, FLOPE_EINVAL, "flope_yolo_read_tensor: NULL argument");
   if (!e->loaded) return yfail(e, FLOPE_ESTATE, "flope_yolo_read_tensor before flope_yolo_load_weights");
+  Tap op_view;
   auto it = e->taps.find(name);
-  if (it == e->taps.end()) return yfail(e, FLOPE_EINVAL, std::string("flope_yolo_read_tensor: unknown tensor ") + name);
-  const Tap& t = it->second;
+  if (it == e->taps.end() && !op_tap(e, name, &op_view)) return yfail(e, FLOPE_EINVAL, std::string("flope_yolo_read_tensor: unknown tensor ") + name);
+  const Tap& t = it != e->taps.end() ? it->second : op_view;
   dims_out[0] = t.C; dims_out[1] = t.H; dims_out[2] = t.W;
   if (!dst_dev) return FLOPE_OK;                   // size query
   Y_TRY(e, hipSetDevice(e->device));

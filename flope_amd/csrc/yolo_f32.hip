@@ -13,6 +13,8 @@
 #include "common.h"
 #include "yolo.h"
 
+#include <stdio.h>
+
 namespace {
 
 __device__ __forceinline__ float silu32(float v) { return __fdiv_rn(v, 1.f + expf(-v)); }
@@ -299,11 +301,16 @@ extern "C" int flope_y32_pool_init() {
   if (e == hipSuccess) e = hipFuncSetAttribute((const void*)y32_pool_lds_kernel<3>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
   return (int)e;
 }
+static size_t y32_pool_lds_bytes(const YPoolP* p) { return (size_t)4 * p->H * p->W * 4 * sizeof(float); }
+static bool y32_pool_in_lds(const YPoolP* p) {                                                 // (the LDS form reads float32x4 pixels)
+  return y32_pool_lds_bytes(p) <= 160 * 1024 && p->C % 4 == 0 && p->ldi % 4 == 0 && !((uintptr_t)p->in & 15);
+}
+extern "C" int flope_y32_pool_path(const YPoolP* p) { return y32_pool_in_lds(p) ? 1 : 0; }    // test hook: 1 = LDS kernel, 0 = the sweep
 extern "C" int flope_y32_pool_launch(const YPoolP* p, void* stream) {
   if (p->n < 1 || p->n > 3) return (int)hipErrorInvalidValue;
-  const size_t lds = (size_t)4 * p->H * p->W * 4 * sizeof(float);
+  const size_t lds = y32_pool_lds_bytes(p);
   hipStream_t st = (hipStream_t)stream;
-  if (lds <= 160 * 1024 && p->C % 4 == 0 && p->ldi % 4 == 0 && !((uintptr_t)p->in & 15)) {   // (the LDS form reads float32x4 pixels)
+  if (y32_pool_in_lds(p)) {
     if (p->n == 1) hipLaunchKernelGGL(y32_pool_lds_kernel<1>, dim3(p->C / 4), dim3(1024), lds, st, *p);
     else if (p->n == 2) hipLaunchKernelGGL(y32_pool_lds_kernel<2>, dim3(p->C / 4), dim3(1024), lds, st, *p);
     else hipLaunchKernelGGL(y32_pool_lds_kernel<3>, dim3(p->C / 4), dim3(1024), lds, st, *p);
@@ -423,9 +430,12 @@ extern "C" int flope_y32_attn_launch(const YAttnP* p, void* stream) {
   hipLaunchKernelGGL(y32_attn_kernel, dim3((p->N + 15) / 16, p->heads), dim3(256), lds, (hipStream_t)stream, *p);
   return (int)hipGetLastError();
 }
+static size_t y32m_attn_lds(const YAttnP* p) { return ((size_t)16 * (((p->N + 15) & ~15) + 4) + 3 * 4 * 64 * 4) * sizeof(float); }
+static bool y32m_attn_ok(const YAttnP* p) { return p->N >= 1 && y32m_attn_lds(p) <= 160 * 1024 && p->ld % 4 == 0 && p->ldo % 4 == 0; }
+extern "C" int flope_y32m_attn_path(const YAttnP* p) { return y32m_attn_ok(p) ? 1 : 0; }     // test hook: 1 = MFMA kernel, 0 = falls back to the plain one
 extern "C" int flope_y32m_attn_launch(const YAttnP* p, void* stream) {
-  const size_t lds = ((size_t)16 * (((p->N + 15) & ~15) + 4) + 3 * 4 * 64 * 4) * sizeof(float);
-  if (p->N < 1 || lds > 160 * 1024 || p->ld % 4 || p->ldo % 4) return flope_y32_attn_launch(p, stream);
+  const size_t lds = y32m_attn_lds(p);
+  if (!y32m_attn_ok(p)) return flope_y32_attn_launch(p, stream);
   hipLaunchKernelGGL(y32m_attn_kernel, dim3((p->N + 15) / 16, p->heads), dim3(256), lds, (hipStream_t)stream, *p);
   return (int)hipGetLastError();
 }
@@ -642,6 +652,14 @@ static bool y32m_geometry(const YConvP* p, bool* splitk, int* mp, int* nbx, int*
 extern "C" int flope_y32m_conv_ok(const YConvP* p) {
   bool splitk; int mp, nbx, nby;
   return y32m_geometry(p, &splitk, &mp, &nbx, &nby) ? 1 : 0;
+}
+
+// test hook (flope_yolo_op_info): the instantiation flope_y32m_conv_launch takes
+extern "C" int flope_y32m_conv_path(const YConvP* p, char* text, int cap) {
+  bool splitk; int mp, nbx, nby;
+  if (!y32m_geometry(p, &splitk, &mp, &nbx, &nby)) return (int)hipErrorInvalidValue;
+  snprintf(text, (size_t)cap, "y32m.nt%d.mp%d.%s.mode%d", p->nt32m, mp, splitk ? "splitk" : "plain", p->out_mode);
+  return 0;
 }
 
 // float32 detector convolution on the matrix cores; p->w32m / bias32m / k16steps / nt32m from the builder (yolo_engine.hip pack)

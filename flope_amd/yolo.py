@@ -53,6 +53,26 @@ def load_yolo_checkpoint(path: str, allow_pickle: bool = False):
     return sd, imgsz
 
 
+def parse_op_info(line: str) -> dict:
+    """one flope_yolo_op_info line -> dict; integers where they are integers; the words behind " | " (cv2 of a fused
+    Bottleneck) under "cv2" """
+    def words(text):
+        d = {}
+        for w in text.split():
+            k, _, v = w.partition("=")
+            try:
+                d[k] = int(v)
+            except ValueError:
+                d[k] = float(v) if k == "scale" else v
+        return d
+    head, sep, tail = line.partition(" | ")
+    d = words(head)
+    if sep:
+        d["cv2"] = words(tail)
+        d["path"] = d["cv2"].pop("path")
+    return d
+
+
 class YoloSeg:
     def __init__(self, frame_h: int, frame_w: int, imgsz: int = 1280, dtype: str = "f16", device=None):
         if not torch.cuda.is_available():
@@ -126,6 +146,22 @@ class YoloSeg:
         f = self._frame(frame)
         with torch.cuda.device(self.device):
             self._check(self.lib.flope_yolo_forward(self.handle, f.data_ptr(), self._stream()))
+
+    def ops(self) -> list:
+        """test hook: one dict per op of the program-order list (flope_yolo_op_info's key=value words; a fused Bottleneck's
+        second conv under "cv2"), with the kernel path the launcher takes under the current options"""
+        out = []
+        buf = C.create_string_buffer(1024)
+        for i in range(int(self.lib.flope_yolo_op_count(self.handle))):
+            self._check(self.lib.flope_yolo_op_info(self.handle, i, buf, len(buf)))
+            out.append(parse_op_info(buf.value.decode()))
+        return out
+
+    def forward_ops(self, frame, n: int) -> None:
+        """test hook: letterbox + the first n ops in program order, one launch per op"""
+        f = self._frame(frame)
+        with torch.cuda.device(self.device):
+            self._check(self.lib.flope_yolo_forward_ops(self.handle, f.data_ptr(), int(n), self._stream()))
 
     def new_outputs(self):
         """a private (det, count, mask) buffer set for detect_device(out=...): several frames in flight"""

@@ -567,6 +567,18 @@ int flope_yolo_read_tensor(flope_yolo_handle h, const char* name, float* dst_dev
  *   "pool_lds" (default 1): SPPF's cascaded max-pools in LDS where the map fits; 0: the 13 x 13 ring kernel.
  * "bneck", "tile" and "pool_lds" rebuild this handle's schedules and drop its captured graphs when they change. */
 int flope_yolo_set_option(flope_yolo_handle h, const char* name, int value);
+/* Test hooks (per-op element-wise checks); nothing flope_yolo_forward / flope_yolo_detect launch depends on them.
+ * flope_yolo_op_count: ops of the program-order list.  flope_yolo_op_info: one line of `key=value` words for op i -- kind (conv,
+ * bneck, dw, pool, up, attn), state_dict name, geometry (a fused Bottleneck: cv1's words, " | ", cv2's), and `path=`: the kernel
+ * form the launcher takes under the handle's current options, as reported by the launchers' own geometry functions.
+ * Op i's views are tensors of flope_yolo_read_tensor: "op<i>.in", "op<i>.res" (conv residual), "op<i>.add" (depthwise addend),
+ * "op<i>.mid" (a Bottleneck's cv1 output, written with bneck = 0 only), "op<i>.out" (out_mode 1: its float32 columns of the
+ * prediction rows; pool: all n * C channels; attention: [C, 1, N]).
+ * flope_yolo_forward_ops: the letterbox and the first n ops in program order, one launch per op (C2PSA updates a map in place,
+ * so an op's inputs are only intact before it ran). */
+int flope_yolo_op_count(flope_yolo_handle h);
+int flope_yolo_op_info(flope_yolo_handle h, int i, char* text, int cap);
+int flope_yolo_forward_ops(flope_yolo_handle h, const uint8_t* frame_dev, int n, void* stream);
 /* developer aid: `iters` forwards with a HIP event pair around every launch of the graph; writes a text table (mean
  * microseconds per launch, kind, geometry, state_dict name) into text_out[cap] */
 int flope_yolo_profile(flope_yolo_handle h, const uint8_t* frame_dev, int iters, char* text_out, int cap, void* stream);

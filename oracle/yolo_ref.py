@@ -138,6 +138,20 @@ def forward_layers(sd: dict, x: torch.Tensor, emulate=None) -> dict:
         _EMU = None
 
 
+def c2psa_qkv(sd: dict, x: torch.Tensor, emulate=None) -> torch.Tensor:
+    """The qkv map the first attention block of C2PSA (model.10.m.0) is fed with, [1, heads * 128, H / 32, W / 32]: the forward up to
+    SPPF, model.10.cv1, the second half of its output through attn.qkv.  emulate: as forward_layers."""
+    global _EMU
+    _EMU = emulate
+    try:
+        sdf = {k: v.float() for k, v in sd.items() if v.is_floating_point()}
+        o9 = _forward_layers(sdf, x)[9]
+        c = sdf["model.10.cv1.conv.weight"].shape[0] // 2
+        return conv(sdf, "model.10.m.0.attn.qkv", conv(sdf, "model.10.cv1", o9)[:, c:], act=False)
+    finally:
+        _EMU = None
+
+
 def _forward_layers(sd: dict, x: torch.Tensor) -> dict:
     sd = {k: v.float() for k, v in sd.items() if v.is_floating_point()}
     o = {}
