@@ -18,12 +18,13 @@ HARNESS_TF_STREAM := tests/host_harness/libflope_host_tf_stream.so
 HARNESS_TF_WINDOW := tests/host_harness/libflope_host_tf_window.so
 HARNESS_TF_WINDOW16 := tests/host_harness/libflope_host_tf_window16.so
 HARNESS_TF_EXTEND := tests/host_harness/libflope_host_tf_extend.so
+HARNESS_TF_SPLIT := tests/host_harness/libflope_host_tf_split.so
 SRCS     := $(wildcard $(CSRC)/*.hip)
 OBJS     := $(patsubst $(CSRC)/%.hip,$(OBJDIR)/%.o,$(SRCS))
 HDRS     := $(wildcard $(CSRC)/*.h) include/flope_amd.h
 HIPFLAGS := --offload-arch=$(ARCH) -O3 -fPIC -std=c++17 -Wno-unused-value -Iinclude
 
-all: $(LIB) $(HARNESS) $(HARNESS_F32M) $(HARNESS_F32M_KSPLIT) $(HARNESS_GUARD) $(HARNESS_TF_F32M) $(HARNESS_TF_ATTN) $(HARNESS_TF_VARLEN) $(HARNESS_TF_FUSED) $(HARNESS_TF_CAUSAL) $(HARNESS_TF_STREAM) $(HARNESS_TF_WINDOW) $(HARNESS_TF_WINDOW16) $(HARNESS_TF_EXTEND)
+all: $(LIB) $(HARNESS) $(HARNESS_F32M) $(HARNESS_F32M_KSPLIT) $(HARNESS_GUARD) $(HARNESS_TF_F32M) $(HARNESS_TF_ATTN) $(HARNESS_TF_VARLEN) $(HARNESS_TF_FUSED) $(HARNESS_TF_CAUSAL) $(HARNESS_TF_STREAM) $(HARNESS_TF_WINDOW) $(HARNESS_TF_WINDOW16) $(HARNESS_TF_EXTEND) $(HARNESS_TF_SPLIT)
 
 $(OBJDIR)/%.o: $(CSRC)/%.hip $(HDRS)
 	@mkdir -p $(OBJDIR)
@@ -90,6 +91,12 @@ $(HARNESS_TF_WINDOW16): tests/host_harness/harness_tf_window16.cpp $(CSRC)/tf_at
 $(HARNESS_TF_EXTEND): tests/host_harness/harness_tf_extend.cpp $(CSRC)/tf_encoder_stream.h $(CSRC)/tf_attn_plan.h include/flope_amd.h
 	g++ -O2 -fPIC -shared -std=c++17 -I$(CSRC) -o $@ $<
 
+# the planner of option step_split: the partition of a token's visible keys over waves, blocks and lanes, the LDS bytes, both launches,
+# the eligibility rule, where a key lies, the checks of flope_tf_stream_attention (tests/test_tf_step_split_host.py,
+# tests/test_gpu_tf_step_split.py)
+$(HARNESS_TF_SPLIT): tests/host_harness/harness_tf_split.cpp $(CSRC)/tf_encoder_stream.h $(CSRC)/tf_attn_plan.h include/flope_amd.h
+	g++ -O2 -fPIC -shared -std=c++17 -I$(CSRC) -o $@ $<
+
 # conditioning figure and flag predicate of the guarded mode (tests/test_guard_host.py)
 $(HARNESS_GUARD): tests/host_harness/harness_guard.cpp $(CSRC)/pose_math.h
 	g++ -O2 -fPIC -shared -std=c++17 -I$(CSRC) -o $@ $<
@@ -115,7 +122,7 @@ dbg: $(DBGOBJS)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $(DBGDIR)/libflope_amd_dbg.so $(DBGOBJS)
 
 clean:
-	rm -rf build $(LIB) $(HARNESS) $(HARNESS_F32M) $(HARNESS_F32M_KSPLIT) $(HARNESS_GUARD) $(HARNESS_TF_F32M) $(HARNESS_TF_ATTN) $(HARNESS_TF_VARLEN) $(HARNESS_TF_FUSED) $(HARNESS_TF_CAUSAL) $(HARNESS_TF_STREAM) $(HARNESS_TF_WINDOW) $(HARNESS_TF_WINDOW16) $(HARNESS_TF_EXTEND)
+	rm -rf build $(LIB) $(HARNESS) $(HARNESS_F32M) $(HARNESS_F32M_KSPLIT) $(HARNESS_GUARD) $(HARNESS_TF_F32M) $(HARNESS_TF_ATTN) $(HARNESS_TF_VARLEN) $(HARNESS_TF_FUSED) $(HARNESS_TF_CAUSAL) $(HARNESS_TF_STREAM) $(HARNESS_TF_WINDOW) $(HARNESS_TF_WINDOW16) $(HARNESS_TF_EXTEND) $(HARNESS_TF_SPLIT)
 
 # stand-alone measurement programs used by tools/collect_profiles.sh and DESIGN.md section 9 (not part of the library)
 TOOLBINS := build/fetch_calib build/launch_floor build/loop_probe build/loop_probe32 build/dma_issue_probe

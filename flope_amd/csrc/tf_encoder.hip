@@ -24,6 +24,9 @@
 // with sliding-window attention, never full.
 // flope_tf_stream_extend: several tokens per track and call behind what the track holds -- the ragged launch sequence over the packed
 // chunks with tf_attn_extend over cache and chunk, tf_cache_append behind it in every layer; the bits of the same steps.
+// Option step_split = 1 (any dtype): _step and _extend run tf_attn_step_split / tf_attn_extend_split where tf_step_split_ok --
+// one workgroup per token and head, its visible keys split over the four waves, partial softmax states merged in a fixed order; not the
+// forward's bits, element-wise within a derived bound of fp64.  flope_tf_stream_attention runs the step's attention launch alone.
 #include "../../include/flope_amd.h"
 #include "common.h"
 #include "host_pack.h"
@@ -703,6 +706,194 @@ __global__ void tf_cache_append(const V* __restrict__ qkv, V* __restrict__ cache
     row = pos0 + i;
   }
   cache[((size_t)t * capacity + row) * 2 * dv + c] = qkv[(size_t)(o + i) * 3 * dv + dv + c];
+}
+
+// ---- step_split: a token's visible keys over the four waves of a workgroup (option "step_split") -----------------------
+// Where the L visible keys of a query lie, counted k = 0 .. L - 1 from its first visible key: the first nc in the track's cache (kv: the
+// head's k columns of cache row 0, rows of ld elements; a ring: row (slo + k) % capacity), the others in rows of ldo elements from
+// `own` on (the head's k columns of the token's qkv row, or of chunk row tf_extend_chunk0 of an extend).  In both places a row's v
+// columns lie d elements behind its k columns.
+template <typename T, bool WINDOW> struct TfSplitKeys {
+  const T* kv; size_t ld; int nc, slo, capacity;
+  const T* own; size_t ldo;
+  __device__ __forceinline__ const T* key(int k) const {
+    if (k >= nc) return own + (size_t)(k - nc) * ldo;
+    int row = k;
+    if constexpr (WINDOW) row = flope_tf_plan::tf_split_cache_row(k, slo, capacity);
+    return kv + (size_t)row * ld;
+  }
+};
+
+// softmax(q K^T / sqrt(dh)) V over the L >= 1 keys of `keys` on the four waves of a workgroup, every thread of which calls this with
+// the same arguments.  The order, fixed here once for the step and the extend:
+//   wave w walks blocks b = w, w + 4, .. of 64 keys (tf_split_wave) in ascending order.  In a block lane l scores key 64 b + l -- one
+//   fmaf chain over c = 0 .. dh - 1 from 0.f, * scale, as tf_attn_step_row -- the block maximum goes across the wave, the running
+//   (m, l, o) is rescaled by expf(m - m'), p = expf(score - m') is added to the lane's own l, and the 64 p go to the wave's LDS row.
+//   Value pass: the lanes form G = 64 / LPS groups of LPS = dh / VE lanes; group g adds keys g, g + G, .. of the block to its partial
+//   o (lane s of the group: dims s VE .. s VE + VE - 1), one 16-byte load per lane and key, the block's loads in flight before their
+//   fmafs (at most kTfSplitUnroll at a time).  Behind its last block the wave adds the groups' o by a butterfly (xor 32, 16, .., LPS)
+//   and the lanes' l by wave_sum, and leaves (m, l, o) in LDS.
+//   Merge, after one workgroup barrier, by lanes 0 .. LPS - 1 of wave 0: M = max of the m of the waves that had a block
+//   (tf_split_wave_blocks > 0; the others are skipped by that rule), l and o summed in wave order 0 .. 3 with expf(m_w - M) from 0.f,
+//   o * (1 / l), float16 in one rounding (tf_mul_f16_bits), one 16-byte store per lane.
+// lds: tf_split_lds(dh) bytes.  Ends with a workgroup barrier, so a caller may call it again.
+constexpr int kTfSplitUnroll = 8;
+template <typename T, bool WINDOW>
+__device__ __forceinline__ void tf_attn_split_row(const TfSplitKeys<T, WINDOW>& keys, const T* q, T* orow, float* lds, int L, int d, int dh, float scale) {
+  typedef TfSlice<T, true> Sl;
+  constexpr int VE = Sl::VE, KB = flope_tf_plan::kTfSplitBlock, NW = flope_tf_plan::kTfSplitWaves;
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int LPS = dh / VE, G = 64 / LPS, g = lane / LPS, c = (lane - g * LPS) * VE;
+  float* ps = lds + wave * KB;                      // the block's probabilities
+  float* part = lds + NW * KB;                      // [wave][2 + dh]: m, l, o
+  const int stride = 2 + dh;
+  float m = -INFINITY, l = 0.f, o[VE];
+#pragma unroll
+  for (int e = 0; e < VE; ++e) o[e] = 0.f;
+  const int nb = flope_tf_plan::tf_split_blocks(L);
+  for (int b = wave; b < nb; b += NW) {
+    const int k0 = b * KB, cnt = L - k0 < KB ? L - k0 : KB;      // keys of this block
+    float a = -INFINITY;
+    if (lane < cnt) {
+      const T* k = keys.key(k0 + lane);
+      a = 0.f;
+      for (int cc = 0; cc < dh; cc += VE) {
+        Sl qv, kx;
+        qv.load(q + cc);
+        kx.load(k + cc);
+#pragma unroll
+        for (int e = 0; e < VE; ++e) a = fmaf(qv.f[e], kx.f[e], a);
+      }
+      a *= scale;
+    }
+    const float mn = fmaxf(m, wave_max(a));
+    const float alpha = expf(m - mn);                // the wave's first block: expf(-inf) = 0 on l = 0, o = 0
+    const float p = lane < cnt ? expf(a - mn) : 0.f;
+    m = mn;
+    l = fmaf(l, alpha, p);
+#pragma unroll
+    for (int e = 0; e < VE; ++e) o[e] *= alpha;
+    ps[lane] = p;
+    __builtin_amdgcn_wave_barrier();
+    for (int t = g; t < cnt; t += G * kTfSplitUnroll) {          // keys t, t + G, ..: kTfSplitUnroll loads, then their fmafs
+      Sl vv[kTfSplitUnroll];
+#pragma unroll
+      for (int u = 0; u < kTfSplitUnroll; ++u)
+        if (t + u * G < cnt) vv[u].load(keys.key(k0 + t + u * G) + d + c);
+#pragma unroll
+      for (int u = 0; u < kTfSplitUnroll; ++u)
+        if (t + u * G < cnt) {
+          const float pr = ps[t + u * G];
+#pragma unroll
+          for (int e = 0; e < VE; ++e) o[e] = fmaf(pr, vv[u].f[e], o[e]);
+        }
+    }
+    __builtin_amdgcn_wave_barrier();
+  }
+  if (wave < nb) {                                   // uniform per wave
+    for (int off = 32; off >= LPS; off >>= 1) {
+#pragma unroll
+      for (int e = 0; e < VE; ++e) o[e] += __shfl_xor(o[e], off);
+    }
+    l = wave_sum(l);
+    float* pw = part + wave * stride;
+    if (lane == 0) { pw[0] = m; pw[1] = l; }
+    if (lane < LPS) {
+#pragma unroll
+      for (int e = 0; e < VE; ++e) pw[2 + c + e] = o[e];
+    }
+  }
+  __syncthreads();
+  if (threadIdx.x < LPS) {                           // wave 0, group 0: lane s merges dims s VE ..
+    const int waves = nb < NW ? nb : NW;
+    float M = part[0];
+    for (int w = 1; w < waves; ++w) M = fmaxf(M, part[w * stride]);
+    float ls = 0.f, os[VE];
+#pragma unroll
+    for (int e = 0; e < VE; ++e) os[e] = 0.f;
+    for (int w = 0; w < waves; ++w) {
+      const float* pw = part + w * stride;
+      const float f = expf(pw[0] - M);
+      ls = fmaf(f, pw[1], ls);
+#pragma unroll
+      for (int e = 0; e < VE; ++e) os[e] = fmaf(f, pw[2 + c + e], os[e]);
+    }
+    const float inv = 1.f / ls;
+    if constexpr (std::is_same<T, f16_t>::value) {
+      u32x4 w;
+#pragma unroll
+      for (int e = 0; e < VE; e += 2) w[e / 2] = tf_mul_f16_bits(os[e], inv) | (tf_mul_f16_bits(os[e + 1], inv) << 16);
+      *(u32x4*)(orow + c) = w;
+    } else {
+      Sl r;
+#pragma unroll
+      for (int e = 0; e < VE; ++e) r.f[e] = os[e] * inv;
+      r.store(orow + c);
+    }
+  }
+  __syncthreads();
+}
+
+// tf_attn_step with the row above: workgroup (row r, head h).  The slice store, the table and the memory-safety exits are
+// tf_attn_step's (no score row, so no smax); every exit depends on the workgroup's table entry alone, so a workgroup leaves as one,
+// before its first store and before any barrier.  The token's own key and value come from its qkv row, never from the cache row
+// stored here.
+template <typename T, bool WINDOW>
+__global__ __launch_bounds__(256) void tf_attn_step_split(const T* __restrict__ qkv, T* cache, T* __restrict__ att, const int* __restrict__ tab, int n,
+                                                          int d, int H, int tracks, int capacity, int W) {
+  extern __shared__ __attribute__((aligned(16))) float sc[];     // tf_split_lds(dh)
+  const int r = blockIdx.x / H, h = blockIdx.x - r * H, dh = d / H;
+  if (r >= n) return;
+  const int track = tab[2 * r], pos = tab[2 * r + 1];
+  int slot = pos, lo = 0;
+  if constexpr (WINDOW) {
+    if ((unsigned)track >= (unsigned)tracks || pos < 0 || W < 1 || W > capacity) return;
+    slot = flope_tf_plan::tf_stream_slot(pos, capacity);
+    lo = flope_tf_plan::tf_window_lo(pos, W);
+  } else {
+    if ((unsigned)track >= (unsigned)tracks || (unsigned)pos >= (unsigned)capacity) return;
+  }
+  const float scale = 1.f / sqrtf((float)dh);
+  const size_t ld = (size_t)2 * d;
+  const T* tok = qkv + (size_t)r * 3 * d + h * dh;
+  T* kv = cache + (size_t)track * capacity * ld + h * dh;
+  constexpr int VE = TfSlice<T, true>::VE;
+  for (int c = threadIdx.x * VE; c < 2 * dh; c += 256 * VE) {    // k slice | v slice of the token -> cache row pos (WINDOW: pos % capacity)
+    const int col = c < dh ? c : c - dh + d;
+    *(u32x4*)(kv + slot * ld + col) = *(const u32x4*)(tok + d + col);
+  }
+  const TfSplitKeys<T, WINDOW> keys = {kv, ld, pos - lo, WINDOW ? flope_tf_plan::tf_stream_slot(lo, capacity) : 0, capacity, tok + d, (size_t)3 * d};
+  tf_attn_split_row<T, WINDOW>(keys, tok, att + (size_t)r * d + h * dh, sc, pos - lo + 1, d, dh, scale);
+}
+
+// tf_attn_extend with the row above: workgroup (sequence b, head h) x blockIdx.y takes queries blockIdx.y, + gridDim.y, .. of the
+// sequence, one at a time on its four waves.  Reads the cache, writes att alone (tf_cache_append runs behind it); the exits are
+// tf_attn_extend's and uniform for the workgroup, as is the trip count.
+template <typename T, bool WINDOW>
+__global__ __launch_bounds__(256) void tf_attn_extend_split(const T* __restrict__ qkv, const T* __restrict__ cache, T* __restrict__ att,
+                                                            const int* __restrict__ tab, const int* __restrict__ off, int n, int d, int H, int tracks,
+                                                            int capacity, int W) {
+  extern __shared__ __attribute__((aligned(16))) float sc[];     // tf_split_lds(dh)
+  const int b = blockIdx.x / H, h = blockIdx.x - b * H, dh = d / H;
+  if (b >= n) return;
+  const int track = tab[2 * b], pos0 = tab[2 * b + 1];
+  const int o = off[b], len = off[b + 1] - o;
+  if ((unsigned)track >= (unsigned)tracks || pos0 < 0 || len < 1) return;
+  if constexpr (WINDOW) {
+    if (W < 1 || W > capacity || pos0 > INT_MAX - len) return;
+  } else {
+    if (pos0 > capacity - len) return;
+  }
+  const float scale = 1.f / sqrtf((float)dh);
+  const size_t ld = (size_t)2 * d, ldc = (size_t)3 * d;
+  const T* chunk = qkv + (size_t)o * ldc + h * dh;
+  const T* kv = cache + (size_t)track * capacity * ld + h * dh;
+  for (int i = blockIdx.y; i < len; i += gridDim.y) {
+    const int p = pos0 + i, lo = WINDOW ? flope_tf_plan::tf_window_lo(p, W) : 0;
+    const TfSplitKeys<T, WINDOW> keys = {kv, ld, flope_tf_plan::tf_extend_cached(pos0, lo), WINDOW ? flope_tf_plan::tf_stream_slot(lo, capacity) : 0, capacity,
+                                         chunk + (size_t)flope_tf_plan::tf_extend_chunk0(pos0, lo) * ldc + d, ldc};
+    tf_attn_split_row<T, WINDOW>(keys, chunk + (size_t)i * ldc, att + (size_t)(o + i) * d + h * dh, sc, p - lo + 1, d, dh, scale);
+  }
 }
 
 // ---- MFMA linear: Y[128-token tile][128-feature tile], K walked in 64-wide chunks ----------------------------
@@ -1545,6 +1736,7 @@ struct flope_tf_encoder {
   int opt_causal = 0;                        // 1: query i attends to keys j <= i of its own sequence, in every attention launch and in tf_fused_f32
   int opt_window = 0;                        // W > 0 (honoured with opt_causal = 1, refused without): keys i - W < j <= i, on tf_attn_generic unless opt_window_mfma, never tf_fused_f32
   int opt_window_mfma = 0;                   // 1: under causal with a window a 16-bit launch keeps tf_attn_pick's tf_attn_mfma / tf_attn_tiled, their WINDOW instantiations (stored and ignored by float32 handles)
+  int opt_step_split = 0;                    // 1: flope_tf_stream_step / _extend split a token's keys over the four waves of a workgroup where tf_step_split_ok (every dtype)
   int last_fwd = FLOPE_TF_FWD_LAUNCHES;       // what the last forward that enqueued anything ran (flope_tf_last_forward)
   const float** fused_tab = nullptr;         // device table of the float32 weight arrays tf_fused_f32 reads (FLOPE_DT_F32 handles, built by flope_tf_load_weights)
   int opt_f32m_lds = 0;                      // KiB of untouched LDS a tf_linear_f32m launch reserves (> 80: one workgroup per CU)
@@ -1571,7 +1763,7 @@ struct flope_tf_stream_s {
   int tracks = 0, capacity = 0;
   int window = 0;                            // 0: a linear cache, full at capacity; W >= 1: a ring, row p % capacity, keys p - W < j <= p
   void* cache = nullptr;                     // [num_layers][tracks][capacity][2 model_dim] in the handle's dtype, a row is k | v
-  int* tab = nullptr;                        // device table of one call: step (track, position) per row, prefill the track per sequence
+  int* tab = nullptr;                        // device table of one call (4 ints per track): step (track, position) per row, prefill the track per sequence, attention both and its fills' offsets
   std::vector<int> pos, tab_host;            // tokens held per track; the pageable copy tab is uploaded from
   std::vector<char> seen;                    // scratch of the argument checks
 };
@@ -2036,6 +2228,10 @@ extern "C" int flope_tf_set_option(flope_tf_handle e, const char* name, int valu
     if (value < 0 || value > 1) return tf_fail(e, FLOPE_EINVAL, "flope_tf_set_option: window_mfma is 0 or 1");
     const int old = e->opt_window_mfma; e->opt_window_mfma = value; return old;
   }
+  if (!strcmp(name, "step_split")) {
+    if (value < 0 || value > 1) return tf_fail(e, FLOPE_EINVAL, "flope_tf_set_option: step_split is 0 or 1");
+    const int old = e->opt_step_split; e->opt_step_split = value; return old;
+  }
   if (!strcmp(name, "f32mlds")) {
     if (value < 0 || value > 160) return tf_fail(e, FLOPE_EINVAL, "flope_tf_set_option: f32mlds is 0 .. 160 (KiB)");
     const int old = e->opt_f32m_lds; e->opt_f32m_lds = value; return old;
@@ -2329,22 +2525,44 @@ int tf_stream_refuse(flope_tf_stream_s* s, const std::string& who, int rc, int b
   }
 }
 
-// the forward's launch sequence at M = n rows, tf_attn_step where it has launch_attention.  max_pos: the call's largest position; a
-// windowed state: its largest visible key count - 1 (tf_stream_check_step_window)
+// which of FLOPE_TF_STEP_ROW / _SPLIT a step or extend of this state launches now
+template <typename T> int tf_step_plan(const flope_tf_encoder* e) {
+  return e->opt_step_split && flope_tf_plan::tf_step_split_ok(e->d / e->H, (int)sizeof(T)) ? FLOPE_TF_STEP_SPLIT : FLOPE_TF_STEP_ROW;
+}
+
+// the attention launch of a step: n rows of qkv [n][3 d] against one layer's part of the cache -> att [n][d]; the table is s->tab.
+// Returns the kernel's id or < 0
 template <typename T>
-int run_step(flope_tf_stream_s* s, const float* x, int n, int max_pos, float* y, hipStream_t st) {
+int launch_step_attn(flope_tf_stream_s* s, const T* qkv, T* cache, T* att, int n, int max_pos, hipStream_t st) {
   flope_tf_encoder* e = s->e;
-  const flope_tf_plan::TfStreamLaunch l = flope_tf_plan::tf_step_launch(n, e->H, max_pos);
-  const size_t layer = (size_t)s->tracks * s->capacity * 2 * e->d;
-  return run_forward_with<T>(e, x, n, 1, y, st, nullptr, [&](int li) {
-    T* cache = (T*)s->cache + (size_t)li * layer;
-#define TF_STEP(VEC_, WIN_) hipLaunchKernelGGL((tf_attn_step<T, VEC_, WIN_>), dim3(l.grid_x), dim3(l.block), l.lds, st, (const T*)e->qkv, cache, (T*)e->att, \
+  const int plan = tf_step_plan<T>(e);
+  if (plan == FLOPE_TF_STEP_SPLIT) {
+    const flope_tf_plan::TfStreamLaunch l = flope_tf_plan::tf_step_split_launch(n, e->H, e->d / e->H);
+#define TF_SPLIT(WIN_) hipLaunchKernelGGL((tf_attn_step_split<T, WIN_>), dim3(l.grid_x), dim3(l.block), l.lds, st, qkv, cache, att, (const int*)s->tab, n, e->d, \
+                                          e->H, s->tracks, s->capacity, s->window)
+    if (s->window) TF_SPLIT(true); else TF_SPLIT(false);
+#undef TF_SPLIT
+  } else {
+    const flope_tf_plan::TfStreamLaunch l = flope_tf_plan::tf_step_launch(n, e->H, max_pos);
+#define TF_STEP(VEC_, WIN_) hipLaunchKernelGGL((tf_attn_step<T, VEC_, WIN_>), dim3(l.grid_x), dim3(l.block), l.lds, st, qkv, cache, att, \
                                               (const int*)s->tab, n, e->d, e->H, s->tracks, s->capacity, max_pos + 1, s->window)
     if (flope_tf_plan::tf_step_vec_ok(e->d / e->H, (int)sizeof(T))) { if (s->window) TF_STEP(true, true); else TF_STEP(true, false); }
     else { if (s->window) TF_STEP(false, true); else TF_STEP(false, false); }
 #undef TF_STEP
-    TF_HIP(e, hipGetLastError());
-    return 0;
+  }
+  TF_HIP(e, hipGetLastError());
+  return plan;
+}
+
+// the forward's launch sequence at M = n rows, tf_attn_step (option step_split: tf_attn_step_split) where it has launch_attention.
+// max_pos: the call's largest position; a windowed state: its largest visible key count - 1 (tf_stream_check_step_window)
+template <typename T>
+int run_step(flope_tf_stream_s* s, const float* x, int n, int max_pos, float* y, hipStream_t st) {
+  flope_tf_encoder* e = s->e;
+  const size_t layer = (size_t)s->tracks * s->capacity * 2 * e->d;
+  return run_forward_with<T>(e, x, n, 1, y, st, nullptr, [&](int li) {
+    const int rc = launch_step_attn<T>(s, (const T*)e->qkv, (T*)s->cache + (size_t)li * layer, (T*)e->att, n, max_pos, st);
+    return rc < 0 ? rc : 0;
   });
 }
 
@@ -2378,6 +2596,8 @@ int run_extend(flope_tf_stream_s* s, const float* x, int n, int L, const TfRagge
   flope_tf_encoder* e = s->e;
   const size_t layer = (size_t)s->tracks * s->capacity * 2 * e->d;
   const flope_tf_plan::TfExtendLaunch la = flope_tf_plan::tf_extend_launch(n, e->H, rg.max_len, smax);
+  const bool split = tf_step_plan<T>(e) == FLOPE_TF_STEP_SPLIT;       // option step_split: tf_attn_extend_split, the bits of the split steps
+  const flope_tf_plan::TfExtendLaunch ls = flope_tf_plan::tf_extend_split_launch(n, e->H, rg.max_len, e->d / e->H);
   const bool vec = flope_tf_plan::tf_cache_fill_vec_ok(e->d, (int)sizeof(T));
   const int dv = vec ? e->d / flope_tf_plan::tf_stream_vec((int)sizeof(T)) : e->d;
   const flope_tf_plan::TfStreamLaunch lc = flope_tf_plan::tf_cache_append_launch(n, rg.max_len, 2 * dv);
@@ -2386,8 +2606,12 @@ int run_extend(flope_tf_stream_s* s, const float* x, int n, int L, const TfRagge
     T* cache = (T*)s->cache + (size_t)li * layer;
 #define TF_EXT(VEC_, WIN_) hipLaunchKernelGGL((tf_attn_extend<T, VEC_, WIN_>), dim3(la.grid_x, la.grid_y), dim3(la.block), la.lds, st, (const T*)e->qkv, (const T*)cache, \
                                              (T*)e->att, (const int*)s->tab, (const int*)e->vl_off, n, e->d, e->H, s->tracks, s->capacity, smax, s->window)
-    if (flope_tf_plan::tf_step_vec_ok(e->d / e->H, (int)sizeof(T))) { if (s->window) TF_EXT(true, true); else TF_EXT(true, false); }
+#define TF_EXTS(WIN_) hipLaunchKernelGGL((tf_attn_extend_split<T, WIN_>), dim3(ls.grid_x, ls.grid_y), dim3(ls.block), ls.lds, st, (const T*)e->qkv, (const T*)cache, \
+                                        (T*)e->att, (const int*)s->tab, (const int*)e->vl_off, n, e->d, e->H, s->tracks, s->capacity, s->window)
+    if (split) { if (s->window) TF_EXTS(true); else TF_EXTS(false); }
+    else if (flope_tf_plan::tf_step_vec_ok(e->d / e->H, (int)sizeof(T))) { if (s->window) TF_EXT(true, true); else TF_EXT(true, false); }
     else { if (s->window) TF_EXT(false, true); else TF_EXT(false, false); }
+#undef TF_EXTS
 #undef TF_EXT
     TF_HIP(e, hipGetLastError());
 #define TF_APP(V_, WIN_) hipLaunchKernelGGL((tf_cache_append<V_, WIN_>), dim3(lc.grid_x), dim3(lc.block), 0, st, (const V_*)e->qkv, (V_*)cache, (const int*)e->vl_off, \
@@ -2419,14 +2643,14 @@ int tf_stream_open(flope_tf_handle e, const std::string& who, int tracks, int ca
   flope_tf_stream_s* s = new flope_tf_stream_s();
   s->e = e; s->tracks = tracks; s->capacity = capacity; s->window = window;
   // num_layers = 0 has no cache; the allocation keeps one row so that the pointer is a pointer
-  if (hipMalloc(&s->cache, bytes ? bytes : 16) != hipSuccess || hipMalloc((void**)&s->tab, (size_t)2 * tracks * sizeof(int)) != hipSuccess) {
+  if (hipMalloc(&s->cache, bytes ? bytes : 16) != hipSuccess || hipMalloc((void**)&s->tab, (size_t)4 * tracks * sizeof(int)) != hipSuccess) {
     (void)hipGetLastError();
     hipFree(s->cache); hipFree(s->tab);
     delete s;
     return tf_fail(e, FLOPE_EHIP, who + ": hipMalloc failed for a cache of " + std::to_string(bytes) + " bytes (num_layers x tracks x capacity x 2 model_dim)");
   }
   s->pos.assign((size_t)tracks, 0);
-  s->tab_host.assign((size_t)2 * tracks, 0);
+  s->tab_host.assign((size_t)4 * tracks, 0);
   s->seen.assign((size_t)tracks, 0);
   e->streams.push_back(s);
   *out = s;
@@ -2566,6 +2790,73 @@ extern "C" int flope_tf_stream_extend(flope_tf_stream s, const float* x_dev, int
   if ((rc = tf_by_dtype(e, [&](auto tag) { return run_extend<typename decltype(tag)::type>(s, x_dev, n, seq_len, rg, smax, y_dev, st); }))) return rc;
   flope_tf_plan::tf_stream_extend_advance(s->pos.data(), n, lengths, tracks_host);
   return FLOPE_OK;
+}
+
+extern "C" int flope_tf_stream_step_plan(flope_tf_stream s) {
+  flope_tf_encoder* e;
+  int rc;
+  if ((rc = tf_stream_enter(s, "flope_tf_stream_step_plan", &e))) return rc;
+  return tf_by_dtype(e, [&](auto tag) { return tf_step_plan<typename decltype(tag)::type>(e); });
+}
+
+namespace {
+// flope_tf_stream_attention behind its checks: per sequence the k | v columns of rows 0 .. len - 2 into layer 0's part of track b
+// (tf_cache_fill, one launch per sequence: the batch is padded, not packed), row len - 1 into the handle's qkv buffer, then the step's
+// attention launch.  Table (s->tab, 4 n ints): (track b, position len - 1) per row, then (0, len - 1) per sequence, the offsets of its fill
+template <typename T>
+int run_stream_attention(flope_tf_stream_s* s, const T* qkv, int n, int L, const int* lengths, T* att, int max_pos, hipStream_t st) {
+  flope_tf_encoder* e = s->e;
+  const bool vec = flope_tf_plan::tf_cache_fill_vec_ok(e->d, (int)sizeof(T));
+  const int dv = vec ? e->d / flope_tf_plan::tf_stream_vec((int)sizeof(T)) : e->d;
+  const int* tab = (const int*)s->tab;
+  for (int b = 0; b < n; ++b) {
+    const int len = lengths ? lengths[b] : L;
+    const T* seq = qkv + (size_t)b * L * 3 * e->d;
+    TF_HIP(e, hipMemcpyAsync((T*)e->qkv + (size_t)b * 3 * e->d, seq + (size_t)(len - 1) * 3 * e->d, (size_t)3 * e->d * sizeof(T), hipMemcpyDeviceToDevice, st));
+    if (len < 2) continue;
+    const flope_tf_plan::TfStreamLaunch l = flope_tf_plan::tf_cache_fill_launch(1, len - 1, 2 * dv);
+    const size_t total = (size_t)(len - 1) * 2 * dv;
+#define TF_FILL(V_, WIN_) hipLaunchKernelGGL((tf_cache_fill<V_, WIN_>), dim3(l.grid_x), dim3(l.block), 0, st, (const V_*)seq, (V_*)s->cache, tab + 2 * n + 2 * b, \
+                                            tab + 2 * b, len - 1, dv, s->tracks, s->capacity, total)
+    if (vec) { if (s->window) TF_FILL(u32x4, true); else TF_FILL(u32x4, false); }
+    else { if (s->window) TF_FILL(T, true); else TF_FILL(T, false); }
+#undef TF_FILL
+    TF_HIP(e, hipGetLastError());
+  }
+  return launch_step_attn<T>(s, (const T*)e->qkv, (T*)s->cache, att, n, max_pos, st);
+}
+}  // namespace
+
+extern "C" int flope_tf_stream_attention(flope_tf_stream s, const void* qkv_dev, int n, int seq_len, const int* lengths_host, void* att_dev, void* stream) {
+  const std::string who = "flope_tf_stream_attention";
+  flope_tf_encoder* e;
+  int rc, bad = -1, max_pos = 0;
+  if ((rc = tf_stream_enter(s, who, &e))) return rc;
+  if (e->nl < 1) return tf_fail(e, FLOPE_EINVAL, who + ": an encoder without layers has no cache");
+  if ((rc = flope_tf_plan::tf_stream_check_attention(s->tracks, s->capacity, s->window, e->max_tokens, n, seq_len, lengths_host, &bad, &max_pos))) {
+    if (rc == flope_tf_plan::kTfStreamLength)
+      return tf_fail(e, FLOPE_EINVAL, who + ": lengths[" + std::to_string(bad) + "] = " + std::to_string(lengths_host ? lengths_host[bad] : seq_len) + " is outside 1 .. seq_len = " +
+                                          std::to_string(seq_len) + (s->window ? "" : ", or above capacity = " + std::to_string(s->capacity)));
+    return tf_fail(e, FLOPE_EINVAL, who + ": n = " + std::to_string(n) + " is outside 1 .. min(tracks = " + std::to_string(s->tracks) + ", max_tokens = " +
+                                        std::to_string(e->max_tokens) + "), or seq_len < 1");
+  }
+  if (!qkv_dev || !att_dev) return tf_fail(e, FLOPE_EINVAL, who + ": NULL buffer");
+  if (((uintptr_t)qkv_dev | (uintptr_t)att_dev) & 15) return tf_fail(e, FLOPE_EINVAL, who + ": buffer not aligned to 16 bytes");
+  TF_HIP(e, hipSetDevice(e->device));
+  hipStream_t st = (hipStream_t)stream;
+  for (int b = 0; b < n; ++b) {
+    const int len = lengths_host ? lengths_host[b] : seq_len;
+    s->tab_host[(size_t)2 * b] = b;
+    s->tab_host[(size_t)2 * b + 1] = len - 1;
+    s->tab_host[(size_t)2 * n + 2 * b] = 0;
+    s->tab_host[(size_t)2 * n + 2 * b + 1] = len - 1;
+    s->pos[(size_t)b] = 0;                             // a test hook: the rows it loads are no history of the track
+  }
+  TF_HIP(e, hipMemcpyAsync(s->tab, s->tab_host.data(), (size_t)4 * n * sizeof(int), hipMemcpyHostToDevice, st));
+  return tf_by_dtype(e, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    return run_stream_attention<T>(s, (const T*)qkv_dev, n, seq_len, lengths_host, (T*)att_dev, max_pos, st);
+  });
 }
 
 #ifdef FLOPE_STAG_DBG

@@ -7,6 +7,9 @@
 // Below those, flope_tf_stream_extend: its checks, table, smax and advance for both kinds of state, the launches of
 // tf_attn_extend and tf_cache_append, where a chunk query's keys lie and which rows the append writes
 // (tests/host_harness/harness_tf_extend.cpp, tests/test_tf_extend_host.py).
+// Below those, option step_split: the partition of a token's visible keys over the waves, blocks and lanes of a workgroup,
+// the LDS and launches of tf_attn_step_split / tf_attn_extend_split, the eligibility rule, and the checks of flope_tf_stream_attention
+// (tests/host_harness/harness_tf_split.cpp, tests/test_tf_step_split_host.py).
 #pragma once
 
 #include <limits.h>
@@ -220,6 +223,60 @@ inline int tf_stream_check_extend(const int* pos, int tracks, int capacity, int 
 inline void tf_stream_extend_table(const int* pos, int n, const int* rows, int* tab) { tf_stream_step_table(pos, n, rows, tab); }
 inline void tf_stream_extend_advance(int* pos, int n, const int* lengths, const int* rows) {
   for (int b = 0; b < n; ++b) pos[tf_stream_track(rows, b)] += lengths[b];
+}
+
+// ---- step_split: a token's visible keys split over the four waves of a workgroup (option "step_split") -----------------
+// The visible key with index k, counted from the first visible key lo (k = 0 .. L - 1, the token's own key is k = L - 1), lies in block
+// k / kTfSplitBlock; block b belongs to wave b % kTfSplitWaves, a wave walks its blocks in ascending order, and lane l of the wave scores
+// key kTfSplitBlock b + l.  Counting from lo, not from the absolute position, is what makes a ring's capacity and the cached / chunk
+// boundary of an extend invisible to the arithmetic.  tf_attn_split_row is built from these, and so is
+// tests/host_harness/harness_tf_split.cpp (tests/test_tf_step_split_host.py holds them against brute force).
+constexpr int kTfSplitWaves = 4;
+constexpr int kTfSplitBlock = 64;
+constexpr int tf_split_block(int k) { return k / kTfSplitBlock; }
+constexpr int tf_split_lane(int k) { return k % kTfSplitBlock; }
+constexpr int tf_split_wave(int block) { return block % kTfSplitWaves; }
+// blocks of L visible keys, and how many of them wave w walks: blocks w, w + 4, .. (0: the wave has no part in the merge, by this rule)
+constexpr int tf_split_blocks(int L) { return (L + kTfSplitBlock - 1) / kTfSplitBlock; }
+constexpr int tf_split_wave_blocks(int L, int wave) { return (tf_split_blocks(L) - wave + kTfSplitWaves - 1) / kTfSplitWaves; }
+// The value pass: a head slice is tf_split_lanes 16-byte vectors, one per lane; the wave's 64 lanes form 64 / tf_split_lanes groups,
+// group g = lane / tf_split_lanes takes the block's keys g, g + groups, .. -- every lane loads
+constexpr int tf_split_lanes(int head_dim, int esz) { return head_dim / tf_stream_vec(esz); }
+// The rule: the head slice moves as whole 16-byte vectors (tf_step_vec_ok) and their count is a power of two <= 64
+constexpr bool tf_step_split_ok(int head_dim, int esz) {
+  return head_dim > 0 && tf_step_vec_ok(head_dim, esz) && tf_split_lanes(head_dim, esz) <= 64 &&
+         (tf_split_lanes(head_dim, esz) & (tf_split_lanes(head_dim, esz) - 1)) == 0;
+}
+// LDS of a workgroup: per wave one block's probabilities, then the partial state m, l, o[head_dim].  No position, no smax.
+constexpr size_t tf_split_lds(int head_dim) { return (size_t)kTfSplitWaves * (kTfSplitBlock + 2 + (size_t)head_dim) * sizeof(float); }
+// tf_attn_step_split: one workgroup per (row, head)
+inline TfStreamLaunch tf_step_split_launch(int n, int H, int head_dim) {
+  return {(unsigned)n * (unsigned)H, 64u * kTfSplitWaves, tf_split_lds(head_dim)};
+}
+// tf_attn_extend_split: workgroup (sequence b, head h) x blockIdx.y takes queries blockIdx.y, blockIdx.y + grid_y, .. of the sequence
+constexpr int kTfSplitGridY = 256;
+inline TfExtendLaunch tf_extend_split_launch(int n, int H, int max_len, int head_dim) {
+  return {(unsigned)n * (unsigned)H, (unsigned)(max_len < kTfSplitGridY ? max_len : kTfSplitGridY), 64u * kTfSplitWaves, tf_split_lds(head_dim)};
+}
+// Where visible key k of a query lies: the first nc keys are cached ones, cache row k (a ring: (slo + k) % capacity, slo = lo %
+// capacity -- they wrap at most once), the others rows k - nc, .. behind the first own row (step: the token's qkv row; extend: chunk
+// row tf_extend_chunk0 onwards)
+constexpr int tf_split_cache_row(int k, int slo, int capacity) { return slo + k >= capacity ? slo + k - capacity : slo + k; }
+
+// flope_tf_stream_attention: n sequences of a padded [n][seq_len] batch for tracks 0 .. n - 1; a length is 1 .. seq_len and, on a linear
+// state (window = 0), at most capacity.  *max_pos: the largest visible key count - 1, as the step checks give it.
+inline int tf_stream_check_attention(int tracks, int capacity, int window, int max_tokens, int n, int seq_len, const int* lengths, int* bad,
+                                     int* max_pos) {
+  if (n < 1 || n > tracks || n > max_tokens || seq_len < 1) return kTfStreamCount;
+  int mx = 0;
+  for (int b = 0; b < n; ++b) {
+    const int len = lengths ? lengths[b] : seq_len;
+    if (len < 1 || len > seq_len || (!window && len > capacity)) { *bad = b; return kTfStreamLength; }
+    const int vis = tf_window_keys(len - 1, window) - 1;
+    if (vis > mx) mx = vis;
+  }
+  *max_pos = mx;
+  return kTfStreamOk;
 }
 
 }  // namespace flope_tf_plan

@@ -8,6 +8,7 @@ sequence, so a track is encoded once and every row is the answer the encoder giv
 Sliding-window causal attention takes `window=W` beside it (or `mask=` holding the banded causal mask): position t sees positions
 t - W < j <= t; `enc.open_stream(tracks, capacity, window=W)` is the same live, over a ring cache that is never full.
 A 16-bit encoder made with `window_mfma=1` keeps its MFMA attention kernels under a window.
+An encoder made with `step_split=1` splits the keys of a stream's step() / extend() over the four waves of a workgroup.
 
 Eval-mode semantics only (dropout is identity), as everywhere in this package.  There is no CPU
 path: construction fails loudly without a HIP device or without the built library.
@@ -127,7 +128,7 @@ def _mask_window(mask, L):
 
 class TransformerEncoder:
     def __init__(self, input_dim, model_dim, out_dim, num_heads, num_layers, ff_dim, dropout=0.1,
-                 dtype="f32", max_tokens=4096, device=None, attn_tiled=0, fused=0, window_mfma=0):
+                 dtype="f32", max_tokens=4096, device=None, attn_tiled=0, fused=0, window_mfma=0, step_split=0):
         _require_gpu()
         self.lib = _lib.load()
         self.device = torch.device(device if device is not None else "cuda:0")
@@ -168,6 +169,11 @@ class TransformerEncoder:
             if rc < 0:
                 self.close()
                 raise ValueError(f"window_mfma must be 0 or 1 (got {window_mfma!r})")
+        if step_split:                           # every dtype: a stream's step / extend split a token's keys over four waves (0 or 1, include/flope_amd.h)
+            rc = self.lib.flope_tf_set_option(self.handle, b"step_split", int(step_split))
+            if rc < 0:
+                self.close()
+                raise ValueError(f"step_split must be 0 or 1 (got {step_split!r})")
 
     def _check(self, rc):
         if rc:
@@ -199,6 +205,10 @@ class TransformerEncoder:
             self._check(self.lib.flope_tf_load_weights(self.handle, n, names, ptrs, ndims, shapes))
 
     def set_option(self, name: str, value: int) -> int:
+        if name == "step_split":                 # the newer option raises on a refused value (the others keep returning the code)
+            rc = self.lib.flope_tf_set_option(self.handle, b"step_split", int(value))
+            self._check_arg(rc)
+            return rc
         return self.lib.flope_tf_set_option(self.handle, name.encode(), int(value))
 
     def _state_causal(self, causal):
@@ -484,12 +494,18 @@ class TransformerEncoderStream:
     in bits for every dtype; on an encoder made with `window_mfma=1` in bits where that forward's attention is the generic kernel,
     within the attention kernels' tolerances elsewhere (step() itself is always the generic order).
     prefill() is then enc(x, lengths=lengths, is_causal=True, window=W) in bits under either value, takes sequences longer than
-    `capacity` (the ring keeps their last `capacity` tokens) and leaves the tracks at their lengths."""
+    `capacity` (the ring keeps their last `capacity` tokens) and leaves the tracks at their lengths.
+    On an encoder with option `step_split` = 1 (`enc.set_option("step_split", v)` may flip it between calls) step() and
+    extend() run the split-key attention kernel where `step_plan` says "split": their rows are then no longer the causal forward's
+    bits but a deterministic function of the track's own keys, element-wise within a derived bound of fp64, and everything above that
+    is stated in bits among step(), extend(), ring capacities and the other tracks of a call still holds in bits.  prefill() and the
+    forwards are untouched by it."""
 
     def __init__(self, enc: TransformerEncoder, tracks: int, capacity: int, window: int = 0):
         self.enc = enc
         self.state = C.c_void_p()
         self.tracks, self.capacity, self.window = int(tracks), int(capacity), int(window)
+        self.last_attn_kernel = None             # FLOPE_TF_STEP_* id of the last attention() launch
         self._handle()
         if self.window < 0:
             raise ValueError(f"window must be 0 (a linear cache) or 1 .. capacity, got {self.window}")
@@ -580,6 +596,42 @@ class TransformerEncoderStream:
         enc._check_arg(rc)
         self._keep = x
         return y
+
+    @property
+    def step_plan(self) -> str:
+        """"row" or "split": the attention kernel a step() / extend() of this state would launch now -- "split" under the encoder's
+        option `step_split` where the head slice is a power-of-two count of 16-byte vectors.  Enqueues nothing."""
+        self._live()
+        rc = self.enc.lib.flope_tf_stream_step_plan(self.state)
+        self.enc._check_arg(rc)
+        return "split" if rc == _lib.TF_STEP_SPLIT else "row"
+
+    def attention(self, qkv: torch.Tensor, lengths=None, out: torch.Tensor = None) -> torch.Tensor:
+        """A test hook: the attention launch of step() alone, on a caller's tensor.  qkv [n, L, 3 * model_dim] in the handle's dtype
+        -> [n, model_dim]: row b is what step()'s attention writes for a token whose q | k | v is row lengths[b] - 1 (None: L - 1) of
+        sequence b, on a track that holds the k | v columns of the rows in front of it (a windowed state: the ring keeps the last
+        `capacity` of them), by the kernel step() would run now; its id is kept in `last_attn_kernel` (0 row, 1 split).  It
+        overwrites layer 0's cache rows of tracks 0 .. n - 1 and leaves those tracks at position 0.  Needs no weights.
+        ValueError: n outside 1 .. tracks, a length outside 1 .. L or, on a linear state, above the capacity."""
+        self._live()
+        enc = self.enc
+        tdt, d = enc._tdt(), enc.dims[1]
+        if not qkv.is_cuda or qkv.device != enc.device:
+            raise RuntimeError(f"input must live on {enc.device} (got {qkv.device}); no CPU path")
+        if qkv.dim() != 3 or qkv.shape[2] != 3 * d or qkv.dtype != tdt or not qkv.is_contiguous():
+            raise ValueError(f"expected a contiguous {tdt} tensor [n, L, {3 * d}], got {qkv.dtype} {tuple(qkv.shape)}")
+        n, L = qkv.shape[0], qkv.shape[1]
+        lh = None if lengths is None else _host_lengths(lengths, n)
+        if out is None:
+            out = torch.empty((n, d), dtype=tdt, device=enc.device)
+        elif tuple(out.shape) != (n, d) or out.dtype != tdt or out.device != enc.device or not out.is_contiguous():
+            raise ValueError(f"out must be a contiguous {tdt} tensor {(n, d)} on {enc.device}")
+        with torch.cuda.device(enc.device):
+            rc = enc.lib.flope_tf_stream_attention(self.state, qkv.data_ptr(), n, L, lh, out.data_ptr(), _stream_ptr(enc.device))
+        enc._check_arg(rc)
+        self.last_attn_kernel = rc
+        self._keep = qkv
+        return out
 
     def _out(self, out, shape):
         if out is None:

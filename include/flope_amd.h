@@ -372,7 +372,15 @@ int flope_tf_forward(flope_tf_handle h, const float* x_dev, int batch, int seq_l
  *       (float32, option "generic", head dims without such a kernel, misaligned buffers) stays tf_attn_generic.  W >= seq_len gives
  *       the bits of the same kernel under "causal" alone.  flope_tf_stream_step is untouched (tf_attn_step, the generic order), so
  *       its rows equal the windowed forward's in bits where that forward's attention is tf_attn_generic and within the MFMA
- *       kernels' tolerances elsewhere; _prefill stays the ragged windowed forward in bits.  With 0 every launch is as above. */
+ *       kernels' tolerances elsewhere; _prefill stays the ragged windowed forward in bits.  With 0 every launch is as above;
+ *   "step_split" (default 0; 0 or 1, FLOPE_EINVAL outside; returns the old value; honoured by every dtype): 1 =
+ *       flope_tf_stream_step and _extend compute a token's attention with its visible keys split over the four waves of a workgroup
+ *       (tf_attn_step_split / tf_attn_extend_split) where the head slice is a power-of-two count of 16-byte vectors
+ *       (tf_step_split_ok: head_dim 8, 32, 64, 128 in every dtype); other shapes keep tf_attn_step / tf_attn_extend and their bits.
+ *       The result is then NOT the causal forward's bits: it is a deterministic function of the track's own keys, element-wise
+ *       within a derived bound of fp64, and every invariant among _step, _extend, ring capacity and the call's other tracks stays
+ *       bit-exact.  Read when a call enqueues, so it may be flipped between calls on one state (the cache layout is the same).
+ *       _prefill, the forwards, flope_tf_attention and option "fused" neither read nor are changed by it. */
 int flope_tf_set_option(flope_tf_handle h, const char* name, int value);
 /* softmax(q k^T / sqrt(head_dim)) v per head on a caller's buffer: qkv_dev [batch, seq_len, 3*model_dim] and out_dev
  * [batch, seq_len, model_dim] in the handle's dtype (float32 for FLOPE_DT_F32).  Launches exactly what flope_tf_forward
@@ -498,7 +506,22 @@ double flope_tf_forward_flops_varlen(flope_tf_handle h, int batch, const int* le
  *             max_tokens, NULL buffers; a linear state: position + length > capacity; a windowed state: position + length > INT_MAX
  *             (a chunk may be longer than capacity: the ring keeps its last capacity tokens).  FLOPE_ESTATE without weights or after
  *             flope_tf_destroy.  Neither reads nor writes options "causal" / "window" or what flope_tf_last_forward reports, and
- *             never runs the single launch of option "fused". */
+ *             never runs the single launch of option "fused".
+ * Option "step_split" (flope_tf_set_option) picks the attention kernel of _step and _extend:
+ *   _step_plan: FLOPE_TF_STEP_ROW (tf_attn_step / tf_attn_extend, one wave per token and head, the causal forward's bits) or
+ *             FLOPE_TF_STEP_SPLIT (tf_attn_step_split / tf_attn_extend_split, one workgroup per token and head), whichever a _step or
+ *             _extend of this state would launch now.  Enqueues nothing; FLOPE_ESTATE after flope_tf_destroy.
+ *   _attention: A TEST HOOK, in the spirit of flope_tf_linear: the step's attention launch alone on a caller's tensor.  qkv_dev
+ *             [n, seq_len, 3 model_dim] and att_dev [n, model_dim] in the handle's dtype (float for FLOPE_DT_F32), both 16-byte
+ *             aligned.  For sequence b of length len = lengths_host[b] (NULL: seq_len), row b of att_dev is what _step's attention
+ *             launch writes for a token whose q | k | v is row len - 1, on a track that holds the k | v columns of rows 0 .. len - 2:
+ *             those are loaded with tf_cache_fill into layer 0's part of tracks 0 .. n - 1 (a windowed state: the ring keeps the last
+ *             `capacity` of them), then the kernel _step would run runs: the handle's option, the state's window.  Returns its
+ *             FLOPE_TF_STEP_* id or < 0.  It OVERWRITES those cache rows and leaves tracks 0 .. n - 1 at position 0; needs no weights.
+ *             Refused with FLOPE_EINVAL, nothing enqueued: n outside 1 .. min(tracks, max_tokens), a length outside 1 .. seq_len, on
+ *             a linear state a length above capacity, NULL or misaligned buffers, a handle with num_layers = 0. */
+#define FLOPE_TF_STEP_ROW         0
+#define FLOPE_TF_STEP_SPLIT       1
 typedef struct flope_tf_stream_s* flope_tf_stream;
 int flope_tf_stream_open(flope_tf_handle h, int tracks, int capacity, flope_tf_stream* out);
 int flope_tf_stream_open_window(flope_tf_handle h, int tracks, int capacity, int window, flope_tf_stream* out);
@@ -511,6 +534,8 @@ int flope_tf_stream_prefill(flope_tf_stream s, const float* x_dev, int n, int se
                             float* y_dev, void* stream);
 int flope_tf_stream_extend(flope_tf_stream s, const float* x_dev, int n, int seq_len, const int* lengths_host, const int* tracks_host,
                            float* y_dev, void* stream);
+int flope_tf_stream_step_plan(flope_tf_stream s);
+int flope_tf_stream_attention(flope_tf_stream s, const void* qkv_dev, int n, int seq_len, const int* lengths_host, void* att_dev, void* stream);
 
 /* ---- YOLO11-seg detector front end ---------------------------------------------------
  * Replaces `self.yolo = YOLO(yolo_path)` (sunflower/predictor/fast_pose_predictor.py:36) and the
