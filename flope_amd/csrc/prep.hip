@@ -6,6 +6,7 @@
 //     scripts/generate_metrics_utils.py:17-35)
 //   * depth statistics + back-projection (image_manipulation.py:21-96, mvg.py:387-408)
 #include "common.h"
+#include "depth_plan.h"
 
 // ---------------------------------------------------------------------------
 template <typename T> __device__ __forceinline__ void store4(void* dst, float a, float b, float c);
@@ -284,16 +285,15 @@ extern "C" int flope_crop_resize_mask(const uint8_t* frame_dev, const uint8_t* m
 // ---------------------------------------------------------------------------
 // Depth: valid = (near < d < far) & (mask > 128); eroded by cv2's 10x10 MORPH_ELLIPSE
 // (anchor (5,5), out-of-frame taps ignored = erode's default +inf constant border).
-// Element rows (OpenCV getStructuringElement: dx = round(c * sqrt(1 - dy^2/r^2)), r=c=5):
-//   i: 0 -> col 5 | 1,9 -> 2..8 | 2,8 -> 1..9 | 3..7 -> 0..9
-__constant__ signed char kEllipseLo[10] = {5, 2, 1, 0, 0, 0, 0, 0, 1, 2};
-__constant__ signed char kEllipseHi[10] = {5, 8, 9, 9, 9, 9, 9, 9, 9, 8};
+// The element rows, the strips of a box, the validity tile and the scratch layout are stated in depth_plan.h.
+__constant__ signed char kEllipseLo[kDepthElem] = DEPTH_ELLIPSE_LO;
+__constant__ signed char kEllipseHi[kDepthElem] = DEPTH_ELLIPSE_HI;
 
 // Masked mean of depth over eroded-valid pixels.  A box is cut into kDepthStrips horizontal strips, one workgroup
 // each (one workgroup per box kept 16 CUs busy for 1.9 ms on a 1080p frame with 16 flowers); the strip partials
 // (double sum, count) are combined in strip order by depth_box_final_kernel, so the result does not depend on timing.
-constexpr int kDepthStrips = 32;
 struct DepthPartial { double sum; int cnt; int pad; };
+static_assert(sizeof(DepthPartial) == kDepthPartialBytes, "depth_plan.h states the scratch layout");
 
 // valid = (near < d < far) & (mask > 128) straight from the inputs (out-of-frame = "valid": erode's default border)
 template <typename DT>
@@ -305,27 +305,24 @@ __device__ __forceinline__ unsigned char depth_is_valid(const DT* depth, const u
   return (d > nearp && d < farp && mask[i] > 128) ? 1 : 0;
 }
 
-constexpr int kDepthLds = 48 * 1024;            // validity tile of one strip (+5 halo) when it fits
-
 template <typename DT>
 __global__ __launch_bounds__(256) void depth_box_kernel(const DT* depth, const unsigned char* mask, int FH, int FW,
                                                         float div, float nearp, float farp, const int* boxes,
                                                         DepthPartial* part) {
-  __shared__ unsigned char vt[kDepthLds];
+  __shared__ unsigned char vt[kDepthLds];            // validity tile of one strip (+5 / +4 halo) when it fits
   const int b = blockIdx.x, strip = blockIdx.y;
-  const int x0 = boxes[b * 4], y0 = boxes[b * 4 + 1], x1 = boxes[b * 4 + 2], y1 = boxes[b * 4 + 3];
   // numpy slicing semantics of depth[hmin:hmax, wmin:wmax] for in-frame, non-negative boxes
-  const int xs = max(x0, 0), ys = max(y0, 0), xe = min(x1, FW), ye = min(y1, FH);
-  const int bw = max(xe - xs, 0), bh = max(ye - ys, 0);
-  const int r0 = (int)((long)bh * strip / kDepthStrips), r1 = (int)((long)bh * (strip + 1) / kDepthStrips);
-  const int nr = r1 - r0;
+  const DepthExtent e = depth_box_extent(boxes[b * 4], boxes[b * 4 + 1], boxes[b * 4 + 2], boxes[b * 4 + 3], FH, FW);
+  const int xs = e.xs, ys = e.ys, bw = e.bw;
+  const DepthRows rows = depth_strip_rows(e.bh, strip);
+  const int r0 = rows.r0, nr = rows.r1 - rows.r0;
   // validity of the strip and its 10 x 10 neighbourhood: rows ys+r0-5 .. ys+r1+3, columns xs-5 .. xe+3
-  const int tw = bw + 9, th = nr + 9;
-  const bool tiled = nr > 0 && bw > 0 && (long)tw * th <= kDepthLds;
+  const int tw = depth_tile_w(bw), th = depth_tile_h(nr);
+  const bool tiled = depth_strip_is_tiled(bw, nr);
   if (tiled) {
     for (int i = threadIdx.x; i < tw * th; i += 256) {
       const int ty = i / tw, tx = i - ty * tw;
-      vt[i] = depth_is_valid(depth, mask, FH, FW, ys + r0 - 5 + ty, xs - 5 + tx, div, nearp, farp);
+      vt[i] = depth_is_valid(depth, mask, FH, FW, ys + r0 - kDepthAnchor + ty, xs - kDepthAnchor + tx, div, nearp, farp);
     }
   }
   __syncthreads();
@@ -336,20 +333,20 @@ __global__ __launch_bounds__(256) void depth_box_kernel(const DT* depth, const u
     const int x = xs + px, y = ys + r0 + py;
     bool ok = true;
     if (tiled) {
-      // all 76 taps unconditionally (fully unrolled, no early exit): independent LDS reads pipeline, whereas a
+      // all 83 taps unconditionally (fully unrolled, no early exit): independent LDS reads pipeline, whereas a
       // break-on-first-hole loop serialises one LDS latency per tap (60 us of an 80 us launch)
-      constexpr int LO[10] = {5, 2, 1, 0, 0, 0, 0, 0, 1, 2}, HI[10] = {5, 8, 9, 9, 9, 9, 9, 9, 9, 8};
+      constexpr int LO[kDepthElem] = DEPTH_ELLIPSE_LO, HI[kDepthElem] = DEPTH_ELLIPSE_HI;
       unsigned allv = 1;
       const unsigned char* t0 = vt + py * tw + px;
 #pragma unroll
-      for (int ey = 0; ey < 10; ++ey)
+      for (int ey = 0; ey < kDepthElem; ++ey)
 #pragma unroll
         for (int ex = LO[ey]; ex <= HI[ey]; ++ex) allv &= t0[ey * tw + ex];
       ok = allv != 0;
     } else {
-      for (int ey = 0; ey < 10 && ok; ++ey)
+      for (int ey = 0; ey < kDepthElem && ok; ++ey)
         for (int ex = kEllipseLo[ey]; ex <= kEllipseHi[ey]; ++ex)
-          if (!depth_is_valid(depth, mask, FH, FW, y + ey - 5, x + ex - 5, div, nearp, farp)) { ok = false; break; }
+          if (!depth_is_valid(depth, mask, FH, FW, y + ey - kDepthAnchor, x + ex - kDepthAnchor, div, nearp, farp)) { ok = false; break; }
     }
     if (ok) {
       const float dm = (float)depth[(size_t)y * FW + x] / div;   // metres, float32 like the reference
@@ -377,7 +374,7 @@ __global__ void depth_box_final_kernel(const DepthPartial* part, const int* boxe
   for (int k = 0; k < kDepthStrips; ++k) { s += part[b * kDepthStrips + k].sum; c += part[b * kDepthStrips + k].cnt; }
   const double dv = c > 0 ? (s / c) / 1000.0 : 0.0;
   depth_val[b] = (float)dv;
-  reliable[b] = c >= 50 ? 1 : 0;
+  reliable[b] = c >= kDepthMinCount ? 1 : 0;
   // uv = centre of the (un-squared) box; depth is the ray length (mvg.py:387-408)
   const int x0 = boxes[b * 4], y0 = boxes[b * 4 + 1], x1 = boxes[b * 4 + 2], y1 = boxes[b * 4 + 3];
   const double u = (x0 + x1) * 0.5, v = (y0 + y1) * 0.5;
@@ -396,7 +393,7 @@ extern "C" int flope_depth_lift(const void* depth_dev, int depth_format, const u
   const size_t npix = (size_t)frame_h * frame_w;
   hipStream_t st = (hipStream_t)stream;
   // scratch: [H*W bytes, unused since the validity map became an LDS tile][16-byte aligned n * kDepthStrips partials]
-  DepthPartial* part = (DepthPartial*)(scratch_dev + ((npix + 15) & ~(size_t)15));
+  DepthPartial* part = (DepthPartial*)(scratch_dev + depth_partials_offset(npix));
   if (depth_format == 0)
     hipLaunchKernelGGL(depth_box_kernel<unsigned short>, dim3(n, kDepthStrips), dim3(256), 0, st, (const unsigned short*)depth_dev,
                        mask_dev, frame_h, frame_w, depth_div, near_plane, far_plane, boxes_dev, part);

@@ -235,6 +235,23 @@ def get_depth_value(bbox, depth, seg_mask, scale=None, near_plane=0.1, far_plane
     return np.array(vals) / 1000, np.array(rel)
 
 
+def depth_stats64(bbox, depth_m_f32, mask, near, far):
+    """What get_depth_value decides from, made visible: per box the number of eroded-valid pixels and the mean (metres) of
+    their float32 millimetre values taken in float64.  Same validity rule (float32 depth against float32 planes, both strict,
+    mask > 128), same erosion, same numpy slicing of the boxes.  -> (count int64 [N], mean_m float64 [N]); mean 0 where count 0."""
+    depth = np.asarray(depth_m_f32, dtype=np.float32)
+    good = np.logical_and(depth > np.float32(near), depth < np.float32(far))
+    m = erode(np.logical_and(np.asarray(mask) > 128, good), 10)
+    with np.errstate(invalid="ignore", over="ignore"):
+        mm = depth * np.float32(1000)                                   # float32, as the reference's `depth *= 1000`
+    count, mean = [], []
+    for wmin, hmin, wmax, hmax in np.asarray(bbox).reshape(-1, 4).tolist():
+        g = mm[hmin:hmax, wmin:wmax][m[hmin:hmax, wmin:wmax]].astype(np.float64)
+        count.append(g.shape[0])
+        mean.append(float(g.sum() / g.shape[0]) / 1000 if g.shape[0] else 0.0)
+    return np.array(count, dtype=np.int64), np.array(mean, dtype=np.float64)
+
+
 # ---- predictors --------------------------------------------------------------------------
 
 def crop_batch(rgb, mask, sq_bb, size=512):

@@ -643,7 +643,7 @@ def test_depth_lift_vs_oracle():
     assert rel.cpu().numpy().tolist() == rel_ref.tolist() and rel_ref.any() and not rel_ref.all()
     np.testing.assert_allclose(dv.cpu().numpy(), dv_ref, atol=1e-5)
     uv = np.stack([(good[:, 0] + good[:, 2]) / 2, (good[:, 1] + good[:, 3]) / 2], 1)
-    np.testing.assert_allclose(xyz.cpu().numpy()[rel_ref], P.get_points3d(uv, dv_ref, K)[rel_ref], atol=1e-5)
+    np.testing.assert_allclose(xyz.cpu().numpy(), P.get_points3d(uv, dv_ref, K), atol=1e-5)       # every row, unreliable ones too
     # numpy-signature mirror
     from sunflower.utils.image_manipulation import get_depth_value
     d2, r2, _ = get_depth_value(good, depth.astype(np.float32) / 1000, mask, near_plane=0.1, far_plane=2.5)
@@ -666,6 +666,14 @@ def test_depth_val_file_rows_vs_oracle(tmp_path):
     # float32 metre depth (the script's 'npy' branch) gives the same numbers
     rows_f = depth_val_rows(depth.astype(np.float32) / 1000, mask, boxes, near=0.1, far=3.0)
     np.testing.assert_allclose(rows_f[0], dv_ref, atol=1e-5)
+    # the points the same launch lifts from those depths, on every row (the rows file drops them; unreliable rows included)
+    from flope_amd import engine as E
+    K = np.array([[600.0, 0, 320], [0, 600.0, 240], [0, 0, 1]])
+    dv, rel, xyz = E.depth_lift(torch.from_numpy(depth.view(np.int16)).cuda(), torch.from_numpy(mask).cuda(),
+                                torch.from_numpy(boxes.astype(np.int32)).cuda(), (600.0, 600.0, 320.0, 240.0), 1000.0, 0.1, 3.0)
+    assert not rel_ref.all() and rel.cpu().numpy().tolist() == rel_ref.tolist()
+    uv = np.stack([(boxes[:, 0] + boxes[:, 2]) / 2, (boxes[:, 1] + boxes[:, 3]) / 2], 1)
+    np.testing.assert_allclose(xyz.cpu().numpy(), P.get_points3d(uv, dv_ref, K), atol=1e-5)
 
 
 def test_fast_pose_predictor_end_to_end_vs_oracle(state_dict, tmp_path):
