@@ -14,6 +14,7 @@ IN_F32_NCHW, IN_BF16_NHWC, IN_F16_NHWC, IN_U8_NHWC = 0, 1, 2, 3
 TF_ATTN_GENERIC, TF_ATTN_MFMA64, TF_ATTN_TILED, TF_ATTN_F32M = 0, 1, 2, 3     # flope_tf_attention's return (tf_attn_plan.h)
 TF_LIN_GENERIC, TF_LIN_ROWWAVE, TF_LIN_ROWWAVE_VEC, TF_LIN_MFMA, TF_LIN_F32M = 0, 1, 2, 3, 4      # flope_tf_linear's return
 TF_FWD_LAUNCHES, TF_FWD_FUSED = 0, 1                                           # flope_tf_forward_plan's return
+TF_EXTEND_ROW, TF_EXTEND_SPLIT, TF_EXTEND_MFMA = 0, 1, 2                         # flope_tf_stream_extend_plan's / _attention_extend's return
 TF_STEP_ROW, TF_STEP_SPLIT = 0, 1                                              # flope_tf_stream_step_plan's / _attention's return
 TF_LN_SCALAR, TF_LN_VEC = 0, 1                                                 # flope_tf_layernorm's return
 STAGE_STEM, STAGE_POOL, STAGE_FEAT, STAGE_HIDDEN = 0, 1, 10, 11
@@ -121,6 +122,8 @@ SIGNATURES = {
     "flope_tf_stream_extend": (_I, [_P, _P, _I, _I, C.POINTER(_I), C.POINTER(_I), _P, _P]),
     "flope_tf_stream_step_plan": (_I, [_P]),
     "flope_tf_stream_attention": (_I, [_P, _P, _I, _I, C.POINTER(_I), _P, _P]),
+    "flope_tf_stream_extend_plan": (_I, [_P]),
+    "flope_tf_stream_attention_extend": (_I, [_P, _P, _I, _I, C.POINTER(_I), C.POINTER(_I), _P, _P]),
 }
 
 _lib = None

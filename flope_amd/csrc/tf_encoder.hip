@@ -27,6 +27,9 @@
 // Option step_split = 1 (any dtype): _step and _extend run tf_attn_step_split / tf_attn_extend_split where tf_step_split_ok --
 // one workgroup per token and head, its visible keys split over the four waves, partial softmax states merged in a fixed order; not the
 // forward's bits, element-wise within a derived bound of fp64.  flope_tf_stream_attention runs the step's attention launch alone.
+// Option extend_mfma = 1 (16-bit handles): _extend runs tf_attn16_extend where tf_extend_mfma_ok -- tf_attn_tiled's ring and
+// 32-key step over the track's cache and the call's chunk, in absolute key blocks: the bits of the MFMA forward's rows.  It wins over
+// step_split for _extend alone; _step, _prefill and the forwards do not read it.  flope_tf_stream_attention_extend runs that launch alone.
 #include "../../include/flope_amd.h"
 #include "common.h"
 #include "host_pack.h"
@@ -1379,6 +1382,116 @@ __global__ __launch_bounds__(256, 2) void tf_attn_tiled(const T* __restrict__ qk
   tf_attn16_store<T, HD32>(out, VARLEN ? row0 : (size_t)b * L, d, h * HD, q0, L, lane, lrun, o);
 }
 
+// tf_attn16_extend (option extend_mfma): flope_tf_stream_extend's attention on tf_attn_tiled's ring and step.  Workgroup
+// (sequence b, head h) x blockIdx.y = 128 chunk rows of that sequence, four waves of 32; the query at chunk row i has the ABSOLUTE
+// position pos0 + i (tab: (track, pos0) per sequence; off: the packed offsets), so a wave's q0 = pos0 + 128 y + 32 wave is no multiple
+// of 32.  Keys are the track's, in absolute 64-key blocks: block t = keys 64 t .. 64 t + 63, from the block that holds lo_wg (the first
+// key the workgroup's first query sees; key 0 without a window) to the block that holds its last query.  Staging, swizzles, the one
+// barrier per block and the step call are tf_attn_tiled's; what differs is where a key row is loaded from
+// (flope_tf_plan::tf_extend_mfma_key): keys >= pos0 from the chunk's packed qkv rows (k at d, v at 2 d of a 3 d row) -- the token's own
+// among them, never its cache slot --, keys lo_wg .. pos0 - 1 from the track's cache (k at 0, v at d of a 2 d row; a ring: row
+// j % capacity), every other key of a block as ZEROS: a stale cache row may hold NaN, the score mask gives p = 0 there, and 0 x NaN
+// in the PV product would be NaN.  The lane then loads chunk row 0, which always exists, and selects zeros, as tf_attn_tiled's gload.
+// A query's state in tf_attn16_step depends on its own row alone, a step that is masked for it as a whole leaves it unchanged and
+// under WINDOW it stays at exactly 0 until the query's first own key: so the same absolute steps give a chunk row the bits tf_attn_tiled
+// / tf_attn_mfma give row pos0 + i of the whole track, whichever queries share its wave.
+// Exits, all per workgroup and in front of the first load, store and barrier: tf_attn_extend's (no track, positions that leave the
+// cache, a window that is none of this cache's), positions past kTfExtendMfmaPosMax, and a query block behind the chunk.  A workgroup
+// with some valid queries keeps all four waves in the barrier loop; queries behind the chunk are clamped for their Q rows and not
+// stored.  Reads the cache, writes att alone: tf_cache_append stays behind it (tf_encoder_stream.h).
+template <typename T, int HD32, bool WINDOW>
+__global__ __launch_bounds__(256, 2) void tf_attn16_extend(const T* __restrict__ qkv, const T* __restrict__ cache, T* __restrict__ att,
+                                                           const int* __restrict__ tab, const int* __restrict__ off, int n, int d, int H,
+                                                           int tracks, int capacity, float scale_log2e, int W) {
+  typedef typename Elem<T>::frag frag;
+  constexpr int HD = 32 * HD32, RB = 64 * HD32, NCH = 4 * HD32;
+  constexpr int KB = flope_tf_plan::kTfAttnTiledKB, BLK = KB * RB, STAGE = 2 * BLK;
+  static_assert(flope_tf_plan::kTfAttnTiledRing == 2 && KB == 64, "the loop below is written for two stages of two 32-key steps");
+  extern __shared__ __attribute__((aligned(16))) char smem[];      // [2 stages][K block [64][RB] | V block [64][RB]]
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, g = lane >> 4, li = lane & 15;
+  const int b = blockIdx.x / H, h = blockIdx.x - b * H, y = (int)blockIdx.y;
+  if (b >= n) return;
+  const int track = tab[2 * b], pos0 = tab[2 * b + 1];
+  const int ob = off[b], len = off[b + 1] - ob;
+  if ((unsigned)track >= (unsigned)tracks || !flope_tf_plan::tf_extend_mfma_positions_ok(pos0, len)) return;
+  if constexpr (WINDOW) { if (W < 1 || W > capacity) return; }
+  else { if (pos0 > capacity - len) return; }
+  if (!flope_tf_plan::tf_extend_mfma_block_live(len, y)) return;
+  const int Wk = WINDOW ? W : 0, Labs = pos0 + len;
+  const T* chunk = qkv + (size_t)ob * 3 * d + h * HD;                        // chunk row i: k at + d, v at + 2 d
+  const T* kv = cache + (size_t)track * capacity * 2 * d + h * HD;           // cache row r: k at + 0, v at + d
+  const int t0 = flope_tf_plan::tf_extend_mfma_first_block(pos0, y, Wk), t1 = flope_tf_plan::tf_extend_mfma_last_block(pos0, len, y);
+
+  // staging role: HD32 chunks of K and of V per thread and block
+  int srow[HD32], ssrc[HD32], sdk[HD32], sdv[HD32];
+#pragma unroll
+  for (int i = 0; i < HD32; ++i) {
+    const int idx = tid + i * 256, row = idx / NCH, ch = idx - row * NCH;
+    srow[i] = row;
+    ssrc[i] = ch * 8;
+    sdk[i] = row * RB + ((ch ^ tf_tiled_kswz<HD32>(row)) << 4);
+    sdv[i] = BLK + row * RB + ((ch ^ tf_tiled_vswz<HD32>(row)) << 4);
+  }
+  u32x4 kr[HD32], vr[HD32];
+  auto gload = [&](int kb0) {
+#pragma unroll
+    for (int i = 0; i < HD32; ++i) {
+      const flope_tf_plan::TfExtendKey key = flope_tf_plan::tf_extend_mfma_key(kb0 + srow[i], pos0, len, capacity, Wk, y);
+      const bool cached = key.kind == flope_tf_plan::kTfExtendKeyCache;
+      const T* src = (cached ? kv + (size_t)key.row * 2 * d : chunk + (size_t)key.row * 3 * d + d) + ssrc[i];
+      const u32x4 kv4 = *(const u32x4*)src, vv4 = *(const u32x4*)(src + d);
+      const u32x4 z = {0, 0, 0, 0};
+      kr[i] = key.kind == flope_tf_plan::kTfExtendKeyZero ? z : kv4;
+      vr[i] = key.kind == flope_tf_plan::kTfExtendKeyZero ? z : vv4;
+    }
+  };
+  auto lwrite = [&](int stage) {
+    char* s = smem + stage * STAGE;
+#pragma unroll
+    for (int i = 0; i < HD32; ++i) {
+      *(u32x4*)(s + sdk[i]) = kr[i];
+      *(u32x4*)(s + sdv[i]) = vr[i];
+    }
+  };
+  gload(t0 * KB);
+  lwrite(t0 & 1);
+
+  const int q0 = flope_tf_plan::tf_extend_mfma_q0(pos0, y, wave);
+  frag qf[2][HD32];
+#pragma unroll
+  for (int qt = 0; qt < 2; ++qt) {
+    int qi = q0 - pos0 + qt * 16 + li;                                       // the chunk row
+    qi = qi < len ? qi : len - 1;
+#pragma unroll
+    for (int ks = 0; ks < HD32; ++ks) qf[qt][ks] = *(const frag*)(chunk + (size_t)qi * 3 * d + (ks * 4 + g) * 8);
+  }
+  float mrun[2] = {-INFINITY, -INFINITY}, lrun[2] = {0.f, 0.f};
+  f32x4 o[2][2 * HD32];
+#pragma unroll
+  for (int qt = 0; qt < 2; ++qt)
+#pragma unroll
+    for (int dt = 0; dt < 2 * HD32; ++dt) o[qt][dt] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+  const TfAttn16Lane ln = tf_attn16_lane<HD32>(lane);
+  for (int t = t0; t <= t1; ++t) {
+    gload((t + 1) * KB);                         // (behind the last block: rows nobody reads, zeros or chunk rows that exist)
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    BLOCK_BARRIER();
+    const char* Ki = smem + (t & 1) * STAGE;
+    const char* Vi = Ki + BLK;
+#pragma unroll
+    for (int st = 0; st < KB / 32; ++st) {
+      const int kl = st * 32, kb = t * KB + kl;
+      if (!flope_tf_plan::tf_extend_mfma_step_taken(q0, kb, Labs, Wk)) continue;                // per wave, uniform: EXEC stays all ones
+      if constexpr (WINDOW) tf_attn16_step<T, HD32, true, true>(Ki, Vi, kb, kl, Labs, q0, scale_log2e, ln, qf, mrun, lrun, o, W);
+      else tf_attn16_step<T, HD32, true>(Ki, Vi, kb, kl, Labs, q0, scale_log2e, ln, qf, mrun, lrun, o);
+    }
+    lwrite((t + 1) & 1);
+  }
+  // the store's row of query qi is row0 + qi: row0 = ob - pos0 in size_t arithmetic (flope_tf_plan::tf_extend_mfma_out_row)
+  tf_attn16_store<T, HD32>(att, (size_t)ob - (size_t)pos0, d, h * HD, q0, Labs, lane, lrun, o);
+}
+
 // ---- float32 on the exact-fp32 matrix instruction (FLOPE_DT_F32 with option f32mfma = 1) ---------------------------------
 // v_mfma_f32_16x16x4_f32 takes float32 operands and accumulates in float32: every product-sum is an fmaf chain, so these kernels
 // differ from tf_linear_generic / tf_attn_generic (option 0, the checker) in summation order only.
@@ -1737,6 +1850,7 @@ struct flope_tf_encoder {
   int opt_window = 0;                        // W > 0 (honoured with opt_causal = 1, refused without): keys i - W < j <= i, on tf_attn_generic unless opt_window_mfma, never tf_fused_f32
   int opt_window_mfma = 0;                   // 1: under causal with a window a 16-bit launch keeps tf_attn_pick's tf_attn_mfma / tf_attn_tiled, their WINDOW instantiations (stored and ignored by float32 handles)
   int opt_step_split = 0;                    // 1: flope_tf_stream_step / _extend split a token's keys over the four waves of a workgroup where tf_step_split_ok (every dtype)
+  int opt_extend_mfma = 0;                   // 1: flope_tf_stream_extend's attention is tf_attn16_extend where tf_extend_mfma_ok (stored and ignored by float32 handles); wins over opt_step_split for _extend only
   int last_fwd = FLOPE_TF_FWD_LAUNCHES;       // what the last forward that enqueued anything ran (flope_tf_last_forward)
   const float** fused_tab = nullptr;         // device table of the float32 weight arrays tf_fused_f32 reads (FLOPE_DT_F32 handles, built by flope_tf_load_weights)
   int opt_f32m_lds = 0;                      // KiB of untouched LDS a tf_linear_f32m launch reserves (> 80: one workgroup per CU)
@@ -2186,6 +2300,11 @@ extern "C" int flope_tf_create(int device_id, int input_dim, int model_dim, int 
     for (const void* f : tiled)
       if (hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)flope_tf_plan::tf_attn_tiled_lds(128)) != hipSuccess)
         return fin(tf_fail(nullptr, FLOPE_EHIP, "flope_tf_create: hipFuncSetAttribute failed"));
+    const void* const ext16[] = {(const void*)tf_attn16_extend<f16_t, 4, false>, (const void*)tf_attn16_extend<bf16_t, 4, false>,
+                                 (const void*)tf_attn16_extend<f16_t, 4, true>, (const void*)tf_attn16_extend<bf16_t, 4, true>};
+    for (const void* f : ext16)
+      if (hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)flope_tf_plan::tf_attn_tiled_lds(128)) != hipSuccess)
+        return fin(tf_fail(nullptr, FLOPE_EHIP, "flope_tf_create: hipFuncSetAttribute failed"));
     if (hipDeviceGetAttribute(&e->cus, hipDeviceAttributeMultiprocessorCount, device_id) != hipSuccess || e->cus < 1) e->cus = 256;
   }
   *out = e;
@@ -2231,6 +2350,10 @@ extern "C" int flope_tf_set_option(flope_tf_handle e, const char* name, int valu
   if (!strcmp(name, "step_split")) {
     if (value < 0 || value > 1) return tf_fail(e, FLOPE_EINVAL, "flope_tf_set_option: step_split is 0 or 1");
     const int old = e->opt_step_split; e->opt_step_split = value; return old;
+  }
+  if (!strcmp(name, "extend_mfma")) {
+    if (value < 0 || value > 1) return tf_fail(e, FLOPE_EINVAL, "flope_tf_set_option: extend_mfma is 0 or 1");
+    const int old = e->opt_extend_mfma; e->opt_extend_mfma = value; return old;
   }
   if (!strcmp(name, "f32mlds")) {
     if (value < 0 || value > 160) return tf_fail(e, FLOPE_EINVAL, "flope_tf_set_option: f32mlds is 0 .. 160 (KiB)");
@@ -2591,29 +2714,70 @@ int run_prefill(flope_tf_stream_s* s, const float* x, int n, int L, const TfRagg
 // the ragged forward's launch sequence over the packed chunks, tf_attn_extend where it has launch_attention and each layer's k | v rows
 // appended to the cache BEHIND that attention (on a ring the append takes rows whose keys the chunk's earlier queries still read;
 // tf_encoder_stream.h).  smax: the call's largest visible key count (tf_stream_check_extend)
+// which of FLOPE_TF_EXTEND_ROW / _SPLIT / _MFMA an extend of this state launches now: option extend_mfma where tf_extend_mfma_ok, in
+// front of option step_split.  pos_ok: every chunk of the call stays below kTfExtendMfmaPosMax (a plan without a call: true)
+template <typename T> int tf_extend_plan(const flope_tf_encoder* e, bool pos_ok = true) {
+  if (e->opt_extend_mfma && pos_ok && flope_tf_plan::tf_extend_mfma_ok(e->dtype, e->d / e->H, e->d)) return FLOPE_TF_EXTEND_MFMA;
+  return tf_step_plan<T>(e) == FLOPE_TF_STEP_SPLIT ? FLOPE_TF_EXTEND_SPLIT : FLOPE_TF_EXTEND_ROW;
+}
+
+// the attention launch of an extend: the packed chunks in qkv [T][3 d] (offsets e->vl_off, table s->tab) against one layer's part of
+// the cache -> att [T][d].  plan: tf_extend_plan's answer for the call.  Returns it, or < 0
 template <typename T>
-int run_extend(flope_tf_stream_s* s, const float* x, int n, int L, const TfRagged& rg, int smax, float* y, hipStream_t st) {
+int launch_extend_attn(flope_tf_stream_s* s, int plan, const T* qkv, const T* cache, T* att, int n, int max_len, int smax, hipStream_t st) {
+  flope_tf_encoder* e = s->e;
+  if (plan == FLOPE_TF_EXTEND_MFMA) {
+    if constexpr (!std::is_same<T, float>::value) {
+      const int dh = e->d / e->H;
+      const flope_tf_plan::TfExtendLaunch lm = flope_tf_plan::tf_extend_mfma_launch(n, e->H, max_len, dh);
+      const float scale_log2e = 1.4426950408889634f / sqrtf((float)dh);
+#define TF_EXTM(HD32_, WIN_) hipLaunchKernelGGL((tf_attn16_extend<T, HD32_, WIN_>), dim3(lm.grid_x, lm.grid_y), dim3(lm.block), lm.lds, st, qkv, cache, att, \
+                                               (const int*)s->tab, (const int*)e->vl_off, n, e->d, e->H, s->tracks, s->capacity, scale_log2e, s->window)
+#define TF_EXTM2(HD32_) do { if (s->window) TF_EXTM(HD32_, true); else TF_EXTM(HD32_, false); } while (0)
+      if (dh == 32) TF_EXTM2(1); else if (dh == 64) TF_EXTM2(2); else if (dh == 96) TF_EXTM2(3); else TF_EXTM2(4);
+#undef TF_EXTM2
+#undef TF_EXTM
+    } else {
+      return tf_fail(e, FLOPE_EINVAL, "tf_attn16_extend has no float32 form");
+    }
+    TF_HIP(e, hipGetLastError());
+    return plan;
+  }
+  const flope_tf_plan::TfExtendLaunch la = flope_tf_plan::tf_extend_launch(n, e->H, max_len, smax);
+  const flope_tf_plan::TfExtendLaunch ls = flope_tf_plan::tf_extend_split_launch(n, e->H, max_len, e->d / e->H);
+#define TF_EXT(VEC_, WIN_) hipLaunchKernelGGL((tf_attn_extend<T, VEC_, WIN_>), dim3(la.grid_x, la.grid_y), dim3(la.block), la.lds, st, qkv, cache, \
+                                             att, (const int*)s->tab, (const int*)e->vl_off, n, e->d, e->H, s->tracks, s->capacity, smax, s->window)
+#define TF_EXTS(WIN_) hipLaunchKernelGGL((tf_attn_extend_split<T, WIN_>), dim3(ls.grid_x, ls.grid_y), dim3(ls.block), ls.lds, st, qkv, cache, \
+                                        att, (const int*)s->tab, (const int*)e->vl_off, n, e->d, e->H, s->tracks, s->capacity, s->window)
+  if (plan == FLOPE_TF_EXTEND_SPLIT) { if (s->window) TF_EXTS(true); else TF_EXTS(false); }   // option step_split: tf_attn_extend_split, the bits of the split steps
+  else if (flope_tf_plan::tf_step_vec_ok(e->d / e->H, (int)sizeof(T))) { if (s->window) TF_EXT(true, true); else TF_EXT(true, false); }
+  else { if (s->window) TF_EXT(false, true); else TF_EXT(false, false); }
+#undef TF_EXTS
+#undef TF_EXT
+  TF_HIP(e, hipGetLastError());
+  return plan;
+}
+
+// whether every chunk of the call whose table is in s->tab_host stays where tf_attn16_extend's int arithmetic holds
+inline bool tf_extend_positions_ok(const flope_tf_stream_s* s, int n, const int* lengths) {
+  for (int b = 0; b < n; ++b)
+    if (!flope_tf_plan::tf_extend_mfma_positions_ok(s->tab_host[(size_t)2 * b + 1], lengths[b])) return false;
+  return true;
+}
+
+template <typename T>
+int run_extend(flope_tf_stream_s* s, const float* x, int n, int L, const TfRagged& rg, const int* lengths, int smax, float* y, hipStream_t st) {
   flope_tf_encoder* e = s->e;
   const size_t layer = (size_t)s->tracks * s->capacity * 2 * e->d;
-  const flope_tf_plan::TfExtendLaunch la = flope_tf_plan::tf_extend_launch(n, e->H, rg.max_len, smax);
-  const bool split = tf_step_plan<T>(e) == FLOPE_TF_STEP_SPLIT;       // option step_split: tf_attn_extend_split, the bits of the split steps
-  const flope_tf_plan::TfExtendLaunch ls = flope_tf_plan::tf_extend_split_launch(n, e->H, rg.max_len, e->d / e->H);
+  const int plan = tf_extend_plan<T>(e, tf_extend_positions_ok(s, n, lengths));
   const bool vec = flope_tf_plan::tf_cache_fill_vec_ok(e->d, (int)sizeof(T));
   const int dv = vec ? e->d / flope_tf_plan::tf_stream_vec((int)sizeof(T)) : e->d;
   const flope_tf_plan::TfStreamLaunch lc = flope_tf_plan::tf_cache_append_launch(n, rg.max_len, 2 * dv);
   const size_t total = (size_t)n * rg.max_len * 2 * dv;
   return run_forward_with<T>(e, x, n, L, y, st, &rg, [&](int li) {
     T* cache = (T*)s->cache + (size_t)li * layer;
-#define TF_EXT(VEC_, WIN_) hipLaunchKernelGGL((tf_attn_extend<T, VEC_, WIN_>), dim3(la.grid_x, la.grid_y), dim3(la.block), la.lds, st, (const T*)e->qkv, (const T*)cache, \
-                                             (T*)e->att, (const int*)s->tab, (const int*)e->vl_off, n, e->d, e->H, s->tracks, s->capacity, smax, s->window)
-#define TF_EXTS(WIN_) hipLaunchKernelGGL((tf_attn_extend_split<T, WIN_>), dim3(ls.grid_x, ls.grid_y), dim3(ls.block), ls.lds, st, (const T*)e->qkv, (const T*)cache, \
-                                        (T*)e->att, (const int*)s->tab, (const int*)e->vl_off, n, e->d, e->H, s->tracks, s->capacity, s->window)
-    if (split) { if (s->window) TF_EXTS(true); else TF_EXTS(false); }
-    else if (flope_tf_plan::tf_step_vec_ok(e->d / e->H, (int)sizeof(T))) { if (s->window) TF_EXT(true, true); else TF_EXT(true, false); }
-    else { if (s->window) TF_EXT(false, true); else TF_EXT(false, false); }
-#undef TF_EXTS
-#undef TF_EXT
-    TF_HIP(e, hipGetLastError());
+    const int rc = launch_extend_attn<T>(s, plan, (const T*)e->qkv, (const T*)cache, (T*)e->att, n, rg.max_len, smax, st);
+    if (rc < 0) return rc;
 #define TF_APP(V_, WIN_) hipLaunchKernelGGL((tf_cache_append<V_, WIN_>), dim3(lc.grid_x), dim3(lc.block), 0, st, (const V_*)e->qkv, (V_*)cache, (const int*)e->vl_off, \
                                            (const int*)s->tab, rg.max_len, dv, s->tracks, s->capacity, total)
     if (vec) { if (s->window) TF_APP(u32x4, true); else TF_APP(u32x4, false); }
@@ -2787,7 +2951,7 @@ extern "C" int flope_tf_stream_extend(flope_tf_stream s, const float* x_dev, int
   // the positions move only once every launch is enqueued: a call that fails on the way (FLOPE_EHIP) leaves the tracks where they were.
   // On a linear state the rows it may have written lie behind the positions, where nothing reads them; on a ring they may have taken
   // the rows of keys a later window still holds, so reset the call's tracks after such a failure
-  if ((rc = tf_by_dtype(e, [&](auto tag) { return run_extend<typename decltype(tag)::type>(s, x_dev, n, seq_len, rg, smax, y_dev, st); }))) return rc;
+  if ((rc = tf_by_dtype(e, [&](auto tag) { return run_extend<typename decltype(tag)::type>(s, x_dev, n, seq_len, rg, lengths, smax, y_dev, st); }))) return rc;
   flope_tf_plan::tf_stream_extend_advance(s->pos.data(), n, lengths, tracks_host);
   return FLOPE_OK;
 }
@@ -2856,6 +3020,94 @@ extern "C" int flope_tf_stream_attention(flope_tf_stream s, const void* qkv_dev,
   return tf_by_dtype(e, [&](auto tag) {
     using T = typename decltype(tag)::type;
     return run_stream_attention<T>(s, (const T*)qkv_dev, n, seq_len, lengths_host, (T*)att_dev, max_pos, st);
+  });
+}
+
+extern "C" int flope_tf_stream_extend_plan(flope_tf_stream s) {
+  flope_tf_encoder* e;
+  int rc;
+  if ((rc = tf_stream_enter(s, "flope_tf_stream_extend_plan", &e))) return rc;
+  return tf_by_dtype(e, [&](auto tag) { return tf_extend_plan<typename decltype(tag)::type>(e); });
+}
+
+namespace {
+// flope_tf_stream_attention_extend behind its checks: per sequence the k | v columns of rows 0 .. cached - 1 into layer 0's part of
+// track b (tf_cache_fill, one launch per sequence: the batch is padded), rows cached .. len - 1 packed into the handle's qkv buffer,
+// the extend's attention launch over them, and the packed rows of the handle's att buffer back to their places in att.
+// Table (s->tab, 4 n ints): (track b, cached) per sequence, then (0, cached) per sequence, the offsets of its fill
+template <typename T>
+int run_stream_attention_extend(flope_tf_stream_s* s, const T* qkv, int n, int L, const int* lengths, const int* cached, T* att, int smax, int max_len,
+                                hipStream_t st) {
+  flope_tf_encoder* e = s->e;
+  const int d = e->d;
+  const bool vec = flope_tf_plan::tf_cache_fill_vec_ok(d, (int)sizeof(T));
+  const int dv = vec ? d / flope_tf_plan::tf_stream_vec((int)sizeof(T)) : d;
+  const int* tab = (const int*)s->tab;
+  for (int b = 0; b < n; ++b) {
+    const T* seq = qkv + (size_t)b * L * 3 * d;
+    const int nc = cached[b], len = lengths[b] - nc;
+    TF_HIP(e, hipMemcpyAsync((T*)e->qkv + (size_t)e->vl_host[(size_t)b] * 3 * d, seq + (size_t)nc * 3 * d, (size_t)len * 3 * d * sizeof(T), hipMemcpyDeviceToDevice, st));
+    if (nc < 1) continue;
+    const flope_tf_plan::TfStreamLaunch l = flope_tf_plan::tf_cache_fill_launch(1, nc, 2 * dv);
+    const size_t total = (size_t)nc * 2 * dv;
+#define TF_FILL(V_, WIN_) hipLaunchKernelGGL((tf_cache_fill<V_, WIN_>), dim3(l.grid_x), dim3(l.block), 0, st, (const V_*)seq, (V_*)s->cache, tab + 2 * n + 2 * b, \
+                                            tab + 2 * b, nc, dv, s->tracks, s->capacity, total)
+    if (vec) { if (s->window) TF_FILL(u32x4, true); else TF_FILL(u32x4, false); }
+    else { if (s->window) TF_FILL(T, true); else TF_FILL(T, false); }
+#undef TF_FILL
+    TF_HIP(e, hipGetLastError());
+  }
+  std::vector<int> chunk((size_t)n);
+  for (int b = 0; b < n; ++b) chunk[(size_t)b] = lengths[b] - cached[b];
+  const int plan = tf_extend_plan<T>(e, tf_extend_positions_ok(s, n, chunk.data()));
+  const int rc = launch_extend_attn<T>(s, plan, (const T*)e->qkv, (const T*)s->cache, (T*)e->att, n, max_len, smax, st);
+  if (rc < 0) return rc;
+  for (int b = 0; b < n; ++b)
+    TF_HIP(e, hipMemcpyAsync(att + ((size_t)b * L + cached[b]) * d, (const T*)e->att + (size_t)e->vl_host[(size_t)b] * d, (size_t)chunk[(size_t)b] * d * sizeof(T),
+                             hipMemcpyDeviceToDevice, st));
+  return rc;
+}
+}  // namespace
+
+extern "C" int flope_tf_stream_attention_extend(flope_tf_stream s, const void* qkv_dev, int n, int seq_len, const int* lengths_host, const int* cached_host,
+                                                void* att_dev, void* stream) {
+  using namespace flope_tf_plan;
+  const std::string who = "flope_tf_stream_attention_extend";
+  flope_tf_encoder* e;
+  int rc, bad = -1, smax = 0, max_len = 0, total = 0;
+  if ((rc = tf_stream_enter(s, who, &e))) return rc;
+  if (e->nl < 1) return tf_fail(e, FLOPE_EINVAL, who + ": an encoder without layers has no cache");
+  if ((rc = tf_stream_check_attention_extend(s->tracks, s->capacity, s->window, e->max_tokens, n, seq_len, lengths_host, cached_host, &bad, &smax, &max_len, &total))) {
+    if (rc == kTfStreamLength)
+      return tf_fail(e, FLOPE_EINVAL, who + ": lengths[" + std::to_string(bad) + "] = " + std::to_string(lengths_host[bad]) + " is outside 1 .. seq_len = " +
+                                          std::to_string(seq_len) + (s->window ? "" : ", or above capacity = " + std::to_string(s->capacity)));
+    if (rc == kTfStreamCached)
+      return tf_fail(e, FLOPE_EINVAL, who + ": cached[" + std::to_string(bad) + "] = " + std::to_string(cached_host[bad]) + " is outside 0 .. lengths[" + std::to_string(bad) +
+                                          "] - 1 = " + std::to_string(lengths_host[bad] - 1));
+    if (rc == kTfStreamTokens) return tf_fail(e, FLOPE_EINVAL, who + ": the chunks together exceed max_tokens given to flope_tf_create");
+    return tf_fail(e, FLOPE_EINVAL, who + ": n = " + std::to_string(n) + " is outside 1 .. min(tracks = " + std::to_string(s->tracks) + ", max_tokens = " +
+                                        std::to_string(e->max_tokens) + "), seq_len < 1, or lengths_host / cached_host is NULL");
+  }
+  if (!qkv_dev || !att_dev) return tf_fail(e, FLOPE_EINVAL, who + ": NULL buffer");
+  if (((uintptr_t)qkv_dev | (uintptr_t)att_dev) & 15) return tf_fail(e, FLOPE_EINVAL, who + ": buffer not aligned to 16 bytes");
+  TF_HIP(e, hipSetDevice(e->device));
+  hipStream_t st = (hipStream_t)stream;
+  int run = 0;
+  for (int b = 0; b < n; ++b) {
+    e->vl_host[(size_t)b] = run;
+    run += lengths_host[b] - cached_host[b];
+    s->tab_host[(size_t)2 * b] = b;
+    s->tab_host[(size_t)2 * b + 1] = cached_host[b];
+    s->tab_host[(size_t)2 * n + 2 * b] = 0;
+    s->tab_host[(size_t)2 * n + 2 * b + 1] = cached_host[b];
+    s->pos[(size_t)b] = 0;                             // a test hook: the rows it loads are no history of the track
+  }
+  e->vl_host[(size_t)n] = run;
+  if ((rc = tf_upload_ragged(e, n, st))) return rc;
+  TF_HIP(e, hipMemcpyAsync(s->tab, s->tab_host.data(), (size_t)4 * n * sizeof(int), hipMemcpyHostToDevice, st));
+  return tf_by_dtype(e, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    return run_stream_attention_extend<T>(s, (const T*)qkv_dev, n, seq_len, lengths_host, cached_host, (T*)att_dev, smax, max_len, st);
   });
 }
 

@@ -10,6 +10,9 @@
 // Below those, option step_split: the partition of a token's visible keys over the waves, blocks and lanes of a workgroup,
 // the LDS and launches of tf_attn_step_split / tf_attn_extend_split, the eligibility rule, and the checks of flope_tf_stream_attention
 // (tests/host_harness/harness_tf_split.cpp, tests/test_tf_step_split_host.py).
+// Below those, option extend_mfma: which 64-key blocks a workgroup of tf_attn16_extend loads, where key j of a block comes
+// from (zeros, a cache row, a chunk row), the output row of a query, the launch, the eligibility rule, and the checks of
+// flope_tf_stream_attention_extend (tests/host_harness/harness_tf_extend16.cpp, tests/test_tf_extend_mfma_host.py).
 #pragma once
 
 #include <limits.h>
@@ -276,6 +279,79 @@ inline int tf_stream_check_attention(int tracks, int capacity, int window, int m
     if (vis > mx) mx = vis;
   }
   *max_pos = mx;
+  return kTfStreamOk;
+}
+
+// ---- extend_mfma: extend's attention on the 16-bit MFMA step (option "extend_mfma") -------------------------------------
+// tf_attn16_extend: workgroup (sequence b, head h, query block y) takes chunk rows 128 y .. 128 y + 127 of its sequence, wave w the 32
+// from 128 y + 32 w on; the query at chunk row i has the absolute position pos0 + i, and the wave's first query q0 = pos0 + 128 y + 32 w
+// is NOT a multiple of 32.  Keys are walked in ABSOLUTE 64-key blocks (block t = keys 64 t .. 64 t + 63, two 32-key steps), the blocks
+// and steps of tf_attn_tiled on the whole track: tf_causal_step_taken / tf_window_step_taken decide per wave, for any q0.
+// A 16-bit dtype, a head_dim tf_attn_tiled has (32 / 64 / 96 / 128), and head slices that start on 16 bytes in a qkv row (3 model_dim
+// elements) and in a cache row (2 model_dim elements)
+inline bool tf_extend_mfma_ok(int dtype, int head_dim, int model_dim) {
+  return (dtype == FLOPE_DT_F16 || dtype == FLOPE_DT_BF16) && tf_attn_tiled_ok(head_dim) && head_dim % 8 == 0 && model_dim > 0 && model_dim % 8 == 0;
+}
+// Positions the kernel's int arithmetic is written for: a wave's q0 + 31 and the block one behind the last stay ints while
+// pos0 + len <= kTfExtendMfmaPosMax.  A call that passes it keeps the other kernels (tf_extend_mfma_positions_ok), and the kernel
+// itself exits there.
+constexpr int kTfExtendMfmaPosMax = INT_MAX - 2 * kTfAttnTiledQueries;
+constexpr bool tf_extend_mfma_positions_ok(int pos0, int len) { return pos0 >= 0 && len >= 1 && pos0 <= kTfExtendMfmaPosMax - len; }
+// the chunk rows of query block y, and whether it has any
+constexpr bool tf_extend_mfma_block_live(int len, int y) { return y >= 0 && y < (len + kTfAttnTiledQueries - 1) / kTfAttnTiledQueries; }
+// lo_wg: the first key any query of the workgroup sees -- its first query's (W = 0: key 0)
+constexpr int tf_extend_mfma_lo(int pos0, int y, int W) { return tf_window_lo(pos0 + kTfAttnTiledQueries * y, W); }
+// first and last 64-key block the workgroup loads: the one that holds lo_wg .. the one that holds its last query
+constexpr int tf_extend_mfma_first_block(int pos0, int y, int W) { return tf_extend_mfma_lo(pos0, y, W) / kTfAttnTiledKB; }
+constexpr int tf_extend_mfma_last_query(int pos0, int len, int y) {
+  return pos0 + (kTfAttnTiledQueries * y + kTfAttnTiledQueries - 1 < len - 1 ? kTfAttnTiledQueries * y + kTfAttnTiledQueries - 1 : len - 1);
+}
+constexpr int tf_extend_mfma_last_block(int pos0, int len, int y) { return tf_extend_mfma_last_query(pos0, len, y) / kTfAttnTiledKB; }
+// a wave's first absolute query
+constexpr int tf_extend_mfma_q0(int pos0, int y, int wave) { return pos0 + kTfAttnTiledQueries * y + 32 * wave; }
+// whether that wave takes the 32-key step that starts at key kb (a multiple of 32) of a sequence that ends at Labs = pos0 + len
+constexpr bool tf_extend_mfma_step_taken(int q0, int kb, int Labs, int W) {
+  return kb < Labs && (W > 0 ? tf_window_step_taken(q0, kb, W) : tf_causal_step_taken(q0, kb));
+}
+// Where the LDS row of key j comes from, for the workgroup y of a chunk (pos0, len):
+//   j >= pos0 + len or j < lo_wg    zeros (never the contents of a row that holds no visible key: 0 x NaN is NaN in the PV product)
+//   pos0 <= j                       the chunk's packed qkv row j - pos0 -- the token's own key among them, never its cache slot
+//   lo_wg <= j < pos0               cache row j of the track, row j % capacity of a ring (lo_wg > pos0 - capacity: the ring holds it)
+enum { kTfExtendKeyZero = 0, kTfExtendKeyCache = 1, kTfExtendKeyChunk = 2 };
+struct TfExtendKey { int kind, row; };
+constexpr TfExtendKey tf_extend_mfma_key(int j, int pos0, int len, int capacity, int W, int y) {
+  if (j < tf_extend_mfma_lo(pos0, y, W) || j >= pos0 + len) return {kTfExtendKeyZero, 0};
+  if (j >= pos0) return {kTfExtendKeyChunk, j - pos0};
+  return {kTfExtendKeyCache, W > 0 ? tf_stream_slot(j, capacity) : j};
+}
+// the packed row of att the query at absolute position qi of sequence b (first packed row off_b) is stored to
+constexpr long long tf_extend_mfma_out_row(int off_b, int pos0, int qi) { return (long long)off_b + (qi - pos0); }
+// grid (n H, ceil(max_len / 128)), 256 threads, tf_attn_tiled's ring of two stages
+inline TfExtendLaunch tf_extend_mfma_launch(int n, int H, int max_len, int head_dim) {
+  return {(unsigned)n * (unsigned)H, (unsigned)((max_len + kTfAttnTiledQueries - 1) / kTfAttnTiledQueries), 256u, tf_attn_tiled_lds(head_dim)};
+}
+
+// flope_tf_stream_attention_extend: n sequences of a padded [n][seq_len] batch for tracks 0 .. n - 1; rows 0 .. cached[b] - 1 are the
+// track's history, rows cached[b] .. lengths[b] - 1 the chunk.  A length is 1 .. seq_len and, on a linear state, at most capacity;
+// cached[b] is 0 .. lengths[b] - 1; the chunks together are at most max_tokens rows.  *smax: the call's largest visible key count,
+// *max_len the longest chunk, *total the chunks' rows.  kTfStreamCached names a cached[] outside its range, kTfStreamTokens the sum.
+enum { kTfStreamCached = -8, kTfStreamTokens = -9 };
+inline int tf_stream_check_attention_extend(int tracks, int capacity, int window, int max_tokens, int n, int seq_len, const int* lengths,
+                                            const int* cached, int* bad, int* smax, int* max_len, int* total) {
+  if (n < 1 || n > tracks || n > max_tokens || seq_len < 1 || !lengths || !cached) return kTfStreamCount;
+  int mx = 0, ml = 0;
+  long long sum = 0;
+  for (int b = 0; b < n; ++b) {
+    const int len = lengths[b];
+    if (len < 1 || len > seq_len || (!window && len > capacity)) { *bad = b; return kTfStreamLength; }
+    if (cached[b] < 0 || cached[b] > len - 1) { *bad = b; return kTfStreamCached; }
+    const int vis = tf_extend_keys(cached[b], len - cached[b], window);
+    if (vis > mx) mx = vis;
+    if (len - cached[b] > ml) ml = len - cached[b];
+    sum += len - cached[b];
+  }
+  if (sum > (long long)max_tokens) return kTfStreamTokens;
+  *smax = mx; *max_len = ml; *total = (int)sum;
   return kTfStreamOk;
 }
 

@@ -9,6 +9,7 @@ Sliding-window causal attention takes `window=W` beside it (or `mask=` holding t
 t - W < j <= t; `enc.open_stream(tracks, capacity, window=W)` is the same live, over a ring cache that is never full.
 A 16-bit encoder made with `window_mfma=1` keeps its MFMA attention kernels under a window.
 An encoder made with `step_split=1` splits the keys of a stream's step() / extend() over the four waves of a workgroup.
+A 16-bit encoder made with `extend_mfma=1` runs a stream's extend() on the MFMA attention step: the MFMA forward's rows in bits.
 
 Eval-mode semantics only (dropout is identity), as everywhere in this package.  There is no CPU
 path: construction fails loudly without a HIP device or without the built library.
@@ -128,7 +129,7 @@ def _mask_window(mask, L):
 
 class TransformerEncoder:
     def __init__(self, input_dim, model_dim, out_dim, num_heads, num_layers, ff_dim, dropout=0.1,
-                 dtype="f32", max_tokens=4096, device=None, attn_tiled=0, fused=0, window_mfma=0, step_split=0):
+                 dtype="f32", max_tokens=4096, device=None, attn_tiled=0, fused=0, window_mfma=0, step_split=0, extend_mfma=0):
         _require_gpu()
         self.lib = _lib.load()
         self.device = torch.device(device if device is not None else "cuda:0")
@@ -174,6 +175,11 @@ class TransformerEncoder:
             if rc < 0:
                 self.close()
                 raise ValueError(f"step_split must be 0 or 1 (got {step_split!r})")
+        if extend_mfma:                          # 16-bit handles: a stream's extend runs its attention on the MFMA step (0 or 1, include/flope_amd.h)
+            rc = self.lib.flope_tf_set_option(self.handle, b"extend_mfma", int(extend_mfma))
+            if rc < 0:
+                self.close()
+                raise ValueError(f"extend_mfma must be 0 or 1 (got {extend_mfma!r})")
 
     def _check(self, rc):
         if rc:
@@ -205,8 +211,8 @@ class TransformerEncoder:
             self._check(self.lib.flope_tf_load_weights(self.handle, n, names, ptrs, ndims, shapes))
 
     def set_option(self, name: str, value: int) -> int:
-        if name == "step_split":                 # the newer option raises on a refused value (the others keep returning the code)
-            rc = self.lib.flope_tf_set_option(self.handle, b"step_split", int(value))
+        if name in ("step_split", "extend_mfma"):    # the newer options raise on a refused value (the others keep returning the code)
+            rc = self.lib.flope_tf_set_option(self.handle, name.encode(), int(value))
             self._check_arg(rc)
             return rc
         return self.lib.flope_tf_set_option(self.handle, name.encode(), int(value))
@@ -499,13 +505,17 @@ class TransformerEncoderStream:
     extend() run the split-key attention kernel where `step_plan` says "split": their rows are then no longer the causal forward's
     bits but a deterministic function of the track's own keys, element-wise within a derived bound of fp64, and everything above that
     is stated in bits among step(), extend(), ring capacities and the other tracks of a call still holds in bits.  prefill() and the
-    forwards are untouched by it."""
+    forwards are untouched by it.
+    On a 16-bit encoder with option `extend_mfma` = 1 (it may be flipped between calls too) extend() runs its attention on
+    the MFMA step where `extend_plan()` says "mfma" (head_dim 32 / 64 / 96 / 128): its rows are then, in bits, the rows of
+    enc(track, is_causal=True[, window=W]) where that forward's attention is an MFMA kernel, whatever the split into chunks, and the
+    cache it leaves is prefill()'s.  It wins over `step_split` for extend() alone; step(), prefill() and the forwards do not read it."""
 
     def __init__(self, enc: TransformerEncoder, tracks: int, capacity: int, window: int = 0):
         self.enc = enc
         self.state = C.c_void_p()
         self.tracks, self.capacity, self.window = int(tracks), int(capacity), int(window)
-        self.last_attn_kernel = None             # FLOPE_TF_STEP_* id of the last attention() launch
+        self.last_attn_kernel = None             # FLOPE_TF_STEP_* id of the last attention() launch, FLOPE_TF_EXTEND_* of the last attention_extend()
         self._handle()
         if self.window < 0:
             raise ValueError(f"window must be 0 (a linear cache) or 1 .. capacity, got {self.window}")
@@ -628,6 +638,44 @@ class TransformerEncoderStream:
             raise ValueError(f"out must be a contiguous {tdt} tensor {(n, d)} on {enc.device}")
         with torch.cuda.device(enc.device):
             rc = enc.lib.flope_tf_stream_attention(self.state, qkv.data_ptr(), n, L, lh, out.data_ptr(), _stream_ptr(enc.device))
+        enc._check_arg(rc)
+        self.last_attn_kernel = rc
+        self._keep = qkv
+        return out
+
+    def extend_plan(self) -> str:
+        """"row", "split" or "mfma": the attention kernel an extend() of this state would launch now -- "mfma" under the encoder's option
+        `extend_mfma` on a 16-bit handle with head_dim 32 / 64 / 96 / 128, otherwise what `step_plan` says.  Enqueues
+        nothing."""
+        self._live()
+        rc = self.enc.lib.flope_tf_stream_extend_plan(self.state)
+        self.enc._check_arg(rc)
+        return {_lib.TF_EXTEND_MFMA: "mfma", _lib.TF_EXTEND_SPLIT: "split"}.get(rc, "row")
+
+    def attention_extend(self, qkv: torch.Tensor, lengths, cached, out: torch.Tensor = None) -> torch.Tensor:
+        """A test hook: the attention launch of extend() alone, on a caller's tensor.  qkv [n, L, 3 * model_dim] in the handle's dtype
+        -> [n, L, model_dim]: of sequence b, rows 0 .. cached[b] - 1 are loaded into track b as its history (k | v columns; a windowed
+        state: the ring keeps the last `capacity` of them), rows cached[b] .. lengths[b] - 1 are the chunk, and those rows of the
+        result are what extend()'s attention writes for them, by the kernel extend() would run now; its id is kept in
+        `last_attn_kernel` (0 row, 1 split, 2 mfma).  Every other row of `out` is left as it is (a fresh result: zeros).  It
+        overwrites layer 0's cache rows of tracks 0 .. n - 1 and leaves those tracks at position 0.  Needs no weights.
+        ValueError: n outside 1 .. tracks, a length outside 1 .. L or, on a linear state, above the capacity, cached[b] outside
+        0 .. lengths[b] - 1, chunks of more than max_tokens rows together."""
+        self._live()
+        enc = self.enc
+        tdt, d = enc._tdt(), enc.dims[1]
+        if not qkv.is_cuda or qkv.device != enc.device:
+            raise RuntimeError(f"input must live on {enc.device} (got {qkv.device}); no CPU path")
+        if qkv.dim() != 3 or qkv.shape[2] != 3 * d or qkv.dtype != tdt or not qkv.is_contiguous():
+            raise ValueError(f"expected a contiguous {tdt} tensor [n, L, {3 * d}], got {qkv.dtype} {tuple(qkv.shape)}")
+        n, L = qkv.shape[0], qkv.shape[1]
+        lh, ch = _host_lengths(lengths, n), _host_lengths(cached, n)
+        if out is None:
+            out = torch.zeros((n, L, d), dtype=tdt, device=enc.device)
+        elif tuple(out.shape) != (n, L, d) or out.dtype != tdt or out.device != enc.device or not out.is_contiguous():
+            raise ValueError(f"out must be a contiguous {tdt} tensor {(n, L, d)} on {enc.device}")
+        with torch.cuda.device(enc.device):
+            rc = enc.lib.flope_tf_stream_attention_extend(self.state, qkv.data_ptr(), n, L, lh, ch, out.data_ptr(), _stream_ptr(enc.device))
         enc._check_arg(rc)
         self.last_attn_kernel = rc
         self._keep = qkv

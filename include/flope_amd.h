@@ -380,7 +380,22 @@ int flope_tf_forward(flope_tf_handle h, const float* x_dev, int batch, int seq_l
  *       The result is then NOT the causal forward's bits: it is a deterministic function of the track's own keys, element-wise
  *       within a derived bound of fp64, and every invariant among _step, _extend, ring capacity and the call's other tracks stays
  *       bit-exact.  Read when a call enqueues, so it may be flipped between calls on one state (the cache layout is the same).
- *       _prefill, the forwards, flope_tf_attention and option "fused" neither read nor are changed by it. */
+ *       _prefill, the forwards, flope_tf_attention and option "fused" neither read nor are changed by it;
+ *   "extend_mfma" (default 0; 0 or 1, FLOPE_EINVAL outside; returns the old value; stored and ignored by float32 handles): 1 =
+ *       flope_tf_stream_extend computes its attention with tf_attn16_extend where tf_extend_mfma_ok: a 16-bit dtype and
+ *       head_dim 32 / 64 / 96 / 128 -- tf_attn_tiled's LDS ring and 32-key MFMA step over the track's cache and then the call's chunk,
+ *       in the absolute 32-key steps of the whole track, on linear and windowed states alike.  Its rows are then, bit for bit, rows
+ *       position .. position + length - 1 of the causal (windowed) forward of the track where that forward's attention is
+ *       tf_attn_mfma / tf_attn_tiled (under a window: with "window_mfma" = 1), for any split of the track into chunks, and the cache
+ *       it leaves is _prefill's.  Other shapes keep the choice below it ("step_split"'s kernel, or tf_attn_extend) and their bits; it
+ *       takes precedence over "step_split" for _extend only.  Read when a call enqueues, so it may be flipped between calls on one
+ *       state (the cache layout is the same).  _step, _prefill, the forwards, flope_tf_attention and flope_tf_stream_attention
+ *       neither read nor are changed by it.  Stale cache rows are still never read (NaN included).  A NaN the caller FEEDS as a token
+ *       is a real key, and in a matrix product a masked probability of 0 does not hide it: a query is NaN when such a key lies in
+ *       one of the 32-key steps its wave of 32 chunk rows takes (those from the step of the wave's first query's first visible key
+ *       to the step of its last query), at or above the first key its workgroup of 128 chunk rows sees and below position + length
+ *       -- a key below the query's own window, or a later token of the same chunk, included.  Fed one token per call, a ring
+ *       forgets NaN tokens as fast as under option 0. */
 int flope_tf_set_option(flope_tf_handle h, const char* name, int value);
 /* softmax(q k^T / sqrt(head_dim)) v per head on a caller's buffer: qkv_dev [batch, seq_len, 3*model_dim] and out_dev
  * [batch, seq_len, model_dim] in the handle's dtype (float32 for FLOPE_DT_F32).  Launches exactly what flope_tf_forward
@@ -519,9 +534,27 @@ double flope_tf_forward_flops_varlen(flope_tf_handle h, int batch, const int* le
  *             `capacity` of them), then the kernel _step would run runs: the handle's option, the state's window.  Returns its
  *             FLOPE_TF_STEP_* id or < 0.  It OVERWRITES those cache rows and leaves tracks 0 .. n - 1 at position 0; needs no weights.
  *             Refused with FLOPE_EINVAL, nothing enqueued: n outside 1 .. min(tracks, max_tokens), a length outside 1 .. seq_len, on
- *             a linear state a length above capacity, NULL or misaligned buffers, a handle with num_layers = 0. */
+ *             a linear state a length above capacity, NULL or misaligned buffers, a handle with num_layers = 0.
+ * Option "extend_mfma" (flope_tf_set_option) picks the attention kernel of _extend in front of "step_split":
+ *   _extend_plan: FLOPE_TF_EXTEND_ROW (tf_attn_extend), FLOPE_TF_EXTEND_SPLIT (tf_attn_extend_split) or FLOPE_TF_EXTEND_MFMA
+ *             (tf_attn16_extend), whichever an _extend of this state would launch now (a call that would carry a track within 256
+ *             positions of INT_MAX keeps the other two).  Enqueues nothing; FLOPE_ESTATE after flope_tf_destroy.
+ *   _attention_extend: A TEST HOOK, as _attention is: the extend's attention launch alone on a caller's tensor.  qkv_dev [n, seq_len,
+ *             3 model_dim] and att_dev [n, seq_len, model_dim] in the handle's dtype, both 16-byte aligned; lengths_host and
+ *             cached_host: n ints each.  Of sequence b, rows 0 .. cached[b] - 1 are a track's history: their k | v columns are loaded
+ *             with tf_cache_fill into layer 0's part of track b (a windowed state: the ring keeps the last `capacity` of them); rows
+ *             cached[b] .. lengths[b] - 1 are the chunk, packed into the handle's buffers.  Then the kernel _extend would run now
+ *             runs once over all n chunks (the handle's options, the state's window) and rows cached[b] .. lengths[b] - 1 of att_dev
+ *             are written; every other row of att_dev is left untouched.  Returns the FLOPE_TF_EXTEND_* id or < 0.  It OVERWRITES
+ *             those cache rows and the handle's scratch buffers and leaves tracks 0 .. n - 1 at position 0; needs no weights.
+ *             Refused with FLOPE_EINVAL, nothing enqueued: n outside 1 .. min(tracks, max_tokens), NULL lengths_host / cached_host,
+ *             a length outside 1 .. seq_len, cached[b] outside 0 .. lengths[b] - 1, on a linear state a length above capacity, chunks
+ *             of more than max_tokens rows together, NULL or misaligned buffers, a handle with num_layers = 0. */
 #define FLOPE_TF_STEP_ROW         0
 #define FLOPE_TF_STEP_SPLIT       1
+#define FLOPE_TF_EXTEND_ROW       0
+#define FLOPE_TF_EXTEND_SPLIT     1
+#define FLOPE_TF_EXTEND_MFMA      2
 typedef struct flope_tf_stream_s* flope_tf_stream;
 int flope_tf_stream_open(flope_tf_handle h, int tracks, int capacity, flope_tf_stream* out);
 int flope_tf_stream_open_window(flope_tf_handle h, int tracks, int capacity, int window, flope_tf_stream* out);
@@ -536,6 +569,9 @@ int flope_tf_stream_extend(flope_tf_stream s, const float* x_dev, int n, int seq
                            float* y_dev, void* stream);
 int flope_tf_stream_step_plan(flope_tf_stream s);
 int flope_tf_stream_attention(flope_tf_stream s, const void* qkv_dev, int n, int seq_len, const int* lengths_host, void* att_dev, void* stream);
+int flope_tf_stream_extend_plan(flope_tf_stream s);
+int flope_tf_stream_attention_extend(flope_tf_stream s, const void* qkv_dev, int n, int seq_len, const int* lengths_host, const int* cached_host,
+                                     void* att_dev, void* stream);
 
 /* ---- YOLO11-seg detector front end ---------------------------------------------------
  * Replaces `self.yolo = YOLO(yolo_path)` (sunflower/predictor/fast_pose_predictor.py:36) and the
