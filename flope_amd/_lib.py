@@ -88,6 +88,7 @@ SIGNATURES = {
     "flope_yolo_load_weights": (_I, [_P, _I, C.POINTER(C.c_char_p), C.POINTER(_P), C.POINTER(_I), C.POINTER(_P)]),
     "flope_yolo_detect": (_I, [_P, _P, _F, _F, _I, _P, _P, _P, _P]),
     "flope_yolo_forward": (_I, [_P, _P, _P]),
+    "flope_yolo_postprocess": (_I, [_P, _P, _P, _F, _F, _I, _P, _P, _P, _P]),
     "flope_yolo_read_tensor": (_I, [_P, C.c_char_p, _P, C.POINTER(C.c_int64), _P]),
     "flope_yolo_set_option": (_I, [_P, C.c_char_p, _I]),
     "flope_yolo_op_count": (_I, [_P]),

@@ -808,10 +808,9 @@ extern "C" int flope_yolo_forward(flope_yolo_handle e, const uint8_t* frame_dev,
   return run_ops(e, stream);
 }
 
-static int detect_body(flope_yolo* e, const uint8_t* frame_dev, float conf, float iou, int max_det, float* det_dev,
-                       int32_t* count_dev, uint8_t* mask_dev, void* stream) {
-  int rc = flope_yolo_forward(e, frame_dev, stream);
-  if (rc) return rc;
+// the post-processing tail: decode, NMS (+ box scaling), masks, resize -- from e->pred and the proto map, wherever they came from
+static int detect_tail(flope_yolo* e, float conf, float iou, int max_det, float* det_dev, int32_t* count_dev, uint8_t* mask_dev,
+                       void* stream) {
   YDecodeP d = e->dec; d.conf = conf;
   int s = flope_ydecode_launch(&d, stream);
   YNmsP q = e->nms; q.conf = conf; q.iou = iou; q.max_det = max_det; q.det = det_dev; q.det_count = count_dev;
@@ -821,6 +820,29 @@ static int detect_body(flope_yolo* e, const uint8_t* frame_dev, float conf, floa
   if (!s) s = flope_resize_linear_u8_launch(e->merged, e->h, e->w, mask_dev, e->H, e->W, stream);
   if (s) return yfail(e, FLOPE_EHIP, std::string("post-processing: ") + hipGetErrorString((hipError_t)s));
   return FLOPE_OK;
+}
+
+static int detect_body(flope_yolo* e, const uint8_t* frame_dev, float conf, float iou, int max_det, float* det_dev,
+                       int32_t* count_dev, uint8_t* mask_dev, void* stream) {
+  int rc = flope_yolo_forward(e, frame_dev, stream);
+  if (rc) return rc;
+  return detect_tail(e, conf, iou, max_det, det_dev, count_dev, mask_dev, stream);
+}
+
+// Test hook: the tail of flope_yolo_detect on given head rows and a given proto map (no network forward).  Always eager.
+extern "C" int flope_yolo_postprocess(flope_yolo_handle e, const float* rows_dev, const void* proto_dev, float conf, float iou,
+                                      int max_det, float* det_dev, int32_t* count_dev, uint8_t* mask_dev, void* stream) {
+  if (!e) return yfail(nullptr, FLOPE_EINVAL, "flope_yolo_postprocess: NULL handle");
+  if (!e->loaded) return yfail(e, FLOPE_ESTATE, "postprocess before flope_yolo_load_weights");
+  if (!rows_dev || !proto_dev || !det_dev || !count_dev || !mask_dev) return yfail(e, FLOPE_EINVAL, "flope_yolo_postprocess: NULL argument");
+  if (max_det < 1 || max_det > kMaxDet) return yfail(e, FLOPE_EINVAL, "flope_yolo_postprocess: max_det must be within 1..300");
+  if (!(conf >= 0.f && conf < 1.f) || !(iou > 0.f && iou <= 1.f)) return yfail(e, FLOPE_EINVAL, "flope_yolo_postprocess: bad thresholds");
+  Y_TRY(e, hipSetDevice(e->device));
+  hipStream_t st = (hipStream_t)stream;
+  Y_TRY(e, hipMemcpyAsync(e->pred, rows_dev, (size_t)e->A * e->no * sizeof(float), hipMemcpyDeviceToDevice, st));
+  const size_t esz = e->dtype == FLOPE_DT_F32 ? 4 : 2;
+  Y_TRY(e, hipMemcpyAsync(const_cast<void*>(e->mask.proto), proto_dev, (size_t)e->mask.mh * e->mask.mw * kNm * esz, hipMemcpyDeviceToDevice, st));
+  return detect_tail(e, conf, iou, max_det, det_dev, count_dev, mask_dev, stream);
 }
 
 // "graph" option: the launch sequence of one (frame buffer, thresholds, output buffers) tuple is captured once into a

@@ -205,6 +205,35 @@ class YoloSeg:
         d = det[:n].cpu().numpy()
         return d[:, :4].copy(), d[:, 4].copy(), d[:, 5].astype(np.int64), d[:, 6].astype(np.int64), mask.cpu().numpy()
 
+    def head_dims(self):
+        """-> (A, no, nc, mh, mw): anchors, floats per head row (64 DFL + nc + 32), classes, proto map size"""
+        dims = (C.c_int64 * 3)()
+        self._check(self.lib.flope_yolo_read_tensor(self.handle, b"cand_conf", None, dims, None))
+        a = int(dims[2])
+        self._check(self.lib.flope_yolo_read_tensor(self.handle, b"cls0", None, dims, None))
+        nc = int(dims[0])
+        self._check(self.lib.flope_yolo_read_tensor(self.handle, b"proto", None, dims, None))
+        return a, 64 + nc + 32, nc, int(dims[1]), int(dims[2])
+
+    def postprocess(self, rows, proto, conf: float = 0.25, iou: float = 0.7, max_det: int = MAX_DET):
+        """test hook: detect()'s post-processing tail (decode, NMS, box scaling, masks, resize) on given head rows.
+        rows float32 [A, no] (64 DFL logits, nc class logits, 32 coefficients per anchor), proto float32 [32, mh, mw]
+        (cast here to the engine's map type and layout).  No network forward; -> the same tuple as detect()."""
+        a, no, _, mh, mw = self.head_dims()
+        rows = torch.as_tensor(rows, dtype=torch.float32)
+        proto = torch.as_tensor(proto, dtype=torch.float32)
+        if tuple(rows.shape) != (a, no) or tuple(proto.shape) != (32, mh, mw):
+            raise ValueError(f"expected rows [{a},{no}] and proto [32,{mh},{mw}], got {tuple(rows.shape)} and {tuple(proto.shape)}")
+        mt = {"f16": torch.float16, "bf16": torch.bfloat16, "f32": torch.float32}[self.dtype]
+        rows = rows.to(self.device).contiguous()
+        proto = proto.to(self.device).permute(1, 2, 0).to(mt).contiguous()
+        with torch.cuda.device(self.device):
+            self._check(self.lib.flope_yolo_postprocess(self.handle, rows.data_ptr(), proto.data_ptr(), float(conf), float(iou), int(max_det),
+                                                        self._det.data_ptr(), self._count.data_ptr(), self._mask.data_ptr(), self._stream()))
+        n = int(self._count.item())           # synchronises: rows / proto stay alive until their copies have run
+        d = self._det[:n].cpu().numpy()
+        return d[:, :4].copy(), d[:, 4].copy(), d[:, 5].astype(np.int64), d[:, 6].astype(np.int64), self._mask.cpu().numpy()
+
     def get_bbox_mask(self, image, conf: float = 0.25, iou: float = 0.7):
         """fast_pose_predictor.py:44-57: -> (bbox int16 [N,4] xyxy, mask uint8 [H,W])."""
         boxes, _, _, _, mask = self.detect(image, conf, iou)

@@ -640,6 +640,14 @@ int flope_yolo_set_option(flope_yolo_handle h, const char* name, int value);
 int flope_yolo_op_count(flope_yolo_handle h);
 int flope_yolo_op_info(flope_yolo_handle h, int i, char* text, int cap);
 int flope_yolo_forward_ops(flope_yolo_handle h, const uint8_t* frame_dev, int n, void* stream);
+/* Test hook: the post-processing tail of flope_yolo_detect (decode, NMS with box scaling, masks, resize: the same launch
+ * sequence, one function) on GIVEN head rows instead of the network's.  rows_dev: float32 [A][no], a row = 64 DFL logits, nc
+ * class logits, 32 mask coefficients (A = W of "cand_conf", no = 64 + nc + 32); proto_dev: [mh][mw][32] in the handle's own map
+ * type (16-bit or float32; mh, mw = H, W of "proto").  Both are copied device to device into the handle's own buffers, so
+ * flope_yolo_read_tensor serves "cand_*", "mask_lb", "box*" / "cls*" / "coef*" and "proto" afterwards as after flope_yolo_detect.
+ * Runs eagerly whatever the "graph" option says; thresholds and outputs as flope_yolo_detect. */
+int flope_yolo_postprocess(flope_yolo_handle h, const float* rows_dev, const void* proto_dev, float conf, float iou, int max_det,
+                           float* det_dev, int32_t* count_dev, uint8_t* mask_dev, void* stream);
 /* developer aid: `iters` forwards with a HIP event pair around every launch of the graph; writes a text table (mean
  * microseconds per launch, kind, geometry, state_dict name) into text_out[cap] */
 int flope_yolo_profile(flope_yolo_handle h, const uint8_t* frame_dev, int iters, char* text_out, int cap, void* stream);
