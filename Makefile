@@ -21,12 +21,13 @@ HARNESS_TF_EXTEND := tests/host_harness/libflope_host_tf_extend.so
 HARNESS_TF_SPLIT := tests/host_harness/libflope_host_tf_split.so
 HARNESS_TF_EXTEND16 := tests/host_harness/libflope_host_tf_extend16.so
 HARNESS_DEPTH := tests/host_harness/libflope_host_depth.so
+HARNESS_CROP := tests/host_harness/libflope_host_crop.so
 SRCS     := $(wildcard $(CSRC)/*.hip)
 OBJS     := $(patsubst $(CSRC)/%.hip,$(OBJDIR)/%.o,$(SRCS))
 HDRS     := $(wildcard $(CSRC)/*.h) include/flope_amd.h
 HIPFLAGS := --offload-arch=$(ARCH) -O3 -fPIC -std=c++17 -Wno-unused-value -Iinclude
 
-all: $(LIB) $(HARNESS) $(HARNESS_F32M) $(HARNESS_F32M_KSPLIT) $(HARNESS_GUARD) $(HARNESS_TF_F32M) $(HARNESS_TF_ATTN) $(HARNESS_TF_VARLEN) $(HARNESS_TF_FUSED) $(HARNESS_TF_CAUSAL) $(HARNESS_TF_STREAM) $(HARNESS_TF_WINDOW) $(HARNESS_TF_WINDOW16) $(HARNESS_TF_EXTEND) $(HARNESS_TF_SPLIT) $(HARNESS_TF_EXTEND16) $(HARNESS_DEPTH)
+all: $(LIB) $(HARNESS) $(HARNESS_F32M) $(HARNESS_F32M_KSPLIT) $(HARNESS_GUARD) $(HARNESS_TF_F32M) $(HARNESS_TF_ATTN) $(HARNESS_TF_VARLEN) $(HARNESS_TF_FUSED) $(HARNESS_TF_CAUSAL) $(HARNESS_TF_STREAM) $(HARNESS_TF_WINDOW) $(HARNESS_TF_WINDOW16) $(HARNESS_TF_EXTEND) $(HARNESS_TF_SPLIT) $(HARNESS_TF_EXTEND16) $(HARNESS_DEPTH) $(HARNESS_CROP)
 
 $(OBJDIR)/%.o: $(CSRC)/%.hip $(HDRS)
 	@mkdir -p $(OBJDIR)
@@ -114,6 +115,11 @@ $(HARNESS_GUARD): tests/host_harness/harness_guard.cpp $(CSRC)/pose_math.h
 $(HARNESS_DEPTH): tests/host_harness/harness_depth.cpp $(CSRC)/depth_plan.h
 	g++ -O2 -fPIC -shared -std=c++17 -I$(CSRC) -o $@ $<
 
+# tile plan of the crop + Lanczos-4 resize kernel: tile edge, LDS window, rows a tile touches, separable or direct path
+# (tests/crop_cases.py, tests/test_crop_cases.py, tests/test_gpu_crop_cases.py)
+$(HARNESS_CROP): tests/host_harness/harness_crop.cpp $(CSRC)/crop_plan.h
+	g++ -O2 -fPIC -shared -std=c++17 -I$(CSRC) -o $@ $<
+
 # the same host code under AddressSanitizer + UBSan (sanitizers run on the CPU build only):
 #   make asan-test      (builds the sanitized harness and runs tests/test_host.py against it; leak detection is off because the
 #                        interpreter's own libcrypto allocations are reported as leaks at exit)
@@ -135,7 +141,7 @@ dbg: $(DBGOBJS)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $(DBGDIR)/libflope_amd_dbg.so $(DBGOBJS)
 
 clean:
-	rm -rf build $(LIB) $(HARNESS) $(HARNESS_F32M) $(HARNESS_F32M_KSPLIT) $(HARNESS_GUARD) $(HARNESS_TF_F32M) $(HARNESS_TF_ATTN) $(HARNESS_TF_VARLEN) $(HARNESS_TF_FUSED) $(HARNESS_TF_CAUSAL) $(HARNESS_TF_STREAM) $(HARNESS_TF_WINDOW) $(HARNESS_TF_WINDOW16) $(HARNESS_TF_EXTEND) $(HARNESS_TF_SPLIT) $(HARNESS_TF_EXTEND16) $(HARNESS_DEPTH)
+	rm -rf build $(LIB) $(HARNESS) $(HARNESS_F32M) $(HARNESS_F32M_KSPLIT) $(HARNESS_GUARD) $(HARNESS_TF_F32M) $(HARNESS_TF_ATTN) $(HARNESS_TF_VARLEN) $(HARNESS_TF_FUSED) $(HARNESS_TF_CAUSAL) $(HARNESS_TF_STREAM) $(HARNESS_TF_WINDOW) $(HARNESS_TF_WINDOW16) $(HARNESS_TF_EXTEND) $(HARNESS_TF_SPLIT) $(HARNESS_TF_EXTEND16) $(HARNESS_DEPTH) $(HARNESS_CROP)
 
 # stand-alone measurement programs used by tools/collect_profiles.sh and DESIGN.md section 9 (not part of the library)
 TOOLBINS := build/fetch_calib build/launch_floor build/loop_probe build/loop_probe32 build/dma_issue_probe

@@ -6,6 +6,7 @@
 //     scripts/generate_metrics_utils.py:17-35)
 //   * depth statistics + back-projection (image_manipulation.py:21-96, mvg.py:387-408)
 #include "common.h"
+#include "crop_plan.h"
 #include "depth_plan.h"
 
 // ---------------------------------------------------------------------------
@@ -172,15 +173,17 @@ __device__ __forceinline__ float masked_unit(int img, int m) {
 //      double-precision sin/cos -- per output pixel: that, not the taps, was its cost: 225 us for 16 crops of 512 x 512);
 //   2. horizontal pass: for every source row the tile touches, the 16 output columns x (3 channels + mask) -> LDS int32;
 //   3. vertical pass from LDS, rounding, mask multiply, store.
-// Tiles that would need more than kCropRows source rows (down-scaling by more than ~3.5x) use the direct kernel.
-constexpr int kCropRows = 64;
+// Tiles that would need more than kCropRows source rows (down-scaling by more than ~3.5x) use the direct kernel.  The tile edge,
+// kCropRows and the rows a tile touches are stated in crop_plan.h.  A box with cw <= 0 or ch <= 0 reads nothing and writes zeros.
+static_assert(kCropTile == 16 && kCropTaps == 8,
+              "the thread-to-pixel mapping below (tid & 15, tid >> 4) and the tap loops are written for 16 and 8");
 __global__ __launch_bounds__(256) void crop_resize_mask_tiled_kernel(const unsigned char* __restrict__ frame,
                                                                      const unsigned char* __restrict__ mask, int FH,
                                                                      int FW, const int* __restrict__ boxes, int S,
                                                                      int tiles_x, int out_format, void* out) {
-  __shared__ short cx[16][8], cy[16][8];
-  __shared__ int sxs[16], sys_[16];
-  __shared__ int hor[kCropRows][16][4];
+  __shared__ short cx[kCropTile][kCropTaps], cy[kCropTile][kCropTaps];
+  __shared__ int sxs[kCropTile], sys_[kCropTile];
+  __shared__ int hor[kCropRows][kCropTile][4];
   const int b = blockIdx.y, ty = blockIdx.x / tiles_x, tx = blockIdx.x - ty * tiles_x;
   const int xmin = boxes[b * 4], ymin = boxes[b * 4 + 1], xmax = boxes[b * 4 + 2], ymax = boxes[b * 4 + 3];
   const int cw = xmax - xmin, ch = ymax - ymin;
@@ -198,9 +201,9 @@ __global__ __launch_bounds__(256) void crop_resize_mask_tiled_kernel(const unsig
   __syncthreads();
   float o0 = 0.f, o1 = 0.f, o2 = 0.f;
   if (live) {
-    const int r0 = sys_[0] - 3;                                     // first (unclamped) source row of the tile
-    const int R = sys_[15] + 4 - r0 + 1;                            // rows touched (uniform over the workgroup)
-    if (R <= kCropRows) {
+    const int r0 = crop_tile_first_row(sys_[0]);                    // first (unclamped) source row of the tile
+    const int R = crop_tile_rows(sys_[0], sys_[kCropTile - 1]);     // rows touched (uniform over the workgroup)
+    if (crop_tile_is_separable(R)) {
       for (int it = tid; it < R * 16; it += 256) {
         const int rr = it >> 4, c = it & 15;
         int yy = r0 + rr;
@@ -276,7 +279,7 @@ extern "C" int flope_crop_resize_mask(const uint8_t* frame_dev, const uint8_t* m
   if (n < 0 || size <= 0 || frame_h <= 0 || frame_w <= 0 || out_format < 0 || out_format > 2) return -1;
   if (n == 0) return 0;
   if (!frame_dev || !mask_dev || !boxes_dev || !out_dev) return -1;
-  const int tiles = (size + 15) / 16;
+  const int tiles = crop_tiles(size);
   hipLaunchKernelGGL(crop_resize_mask_tiled_kernel, dim3(tiles * tiles, n), dim3(256), 0, (hipStream_t)stream, frame_dev,
                      mask_dev, frame_h, frame_w, boxes_dev, size, tiles, out_format, out_dev);
   return hipGetLastError() == hipSuccess ? 0 : -2;
