@@ -74,7 +74,7 @@ $(HARNESS_TF_CAUSAL): tests/host_harness/harness_tf_causal.cpp $(CSRC)/tf_attn_p
 	g++ -O2 -fPIC -shared -std=c++17 -I$(CSRC) -o $@ $<
 
 # the streaming forward's planner: argument checks of step / prefill / reset, the capacity limit, the launches of tf_attn_step and
-# tf_cache_fill (tests/test_tf_stream_host.py, tests/test_gpu_tf_stream.py)
+# tf_cache_append (tests/test_tf_stream_host.py, tests/test_gpu_tf_stream.py)
 $(HARNESS_TF_STREAM): tests/host_harness/harness_tf_stream.cpp $(CSRC)/tf_encoder_stream.h $(CSRC)/tf_attn_plan.h include/flope_amd.h
 	g++ -O2 -fPIC -shared -std=c++17 -I$(CSRC) -o $@ $<
 

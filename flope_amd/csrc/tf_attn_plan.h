@@ -73,7 +73,7 @@ constexpr int tf_causal_f32m_tiles(int q0, int L) { return (tf_causal_keys(q0, 1
 
 // ---- sliding-window causal attention (option "window") ------------------------------------------------------------------
 // With causal and a window W >= 1, query i attends to keys i - W < j <= i of its own sequence; W = 0: no window.  First visible key
-// of query i: max(0, i + 1 - W).  tf_attn_row, tf_attn_step_row and tests/host_harness/harness_tf_window.cpp call this
+// of query i: max(0, i + 1 - W).  tf_attn_row, tf_attn_stream_row and tests/host_harness/harness_tf_window.cpp call this
 // (tests/test_tf_window_host.py holds it against brute force); the last visible key stays tf_causal_keys(i, 1, L) - 1 = i.
 constexpr int tf_window_lo(int i, int W) { return W > 0 && i >= W ? i - W + 1 : 0; }
 // ... and how many keys that is: min(i + 1, W), i + 1 without a window

@@ -374,202 +374,38 @@ template <typename T, bool VEC> struct TfSlice {
   }
 };
 
-// tf_attn_row<T, true> for query pos, operation for operation, with the keys and values in two places: those of positions 0 .. pos - 1
-// in the track's cache rows (kv: the head's k columns of cache row 0, rows of ld elements, v at + d) and those of position pos in the
-// new token's qkv row (tok: its head's q columns, k at + d, v at + 2 d).  The order is tf_attn_row's -- per key one fmaf chain over
-// c = 0 .. dh - 1 from 0.f, * scale; lane j takes keys j, j + 64, ..; wave_max, expf, wave_sum; per output dim one fmaf chain over
-// j = 0 .. pos from 0.f; * (1 / sum) -- and so are the bits (tests/test_gpu_tf_stream.py holds the two definitions to that).  It is
-// a second definition, not a call, because what differs is the loops themselves: a key comes from one of two buffers, a lane reads
-// its key's slice as 16-byte vectors, and the value pass gives a lane VE output dims and keeps kTfStepUnroll keys' loads in flight
-// in front of their fmafs, where tf_attn_row has one scalar load per trip; each of these would change the loops tf_attn_generic
-// and tf_fused_f32 compile from.
+// The streamed attention row, one definition for the step and the extend: tf_attn_row<T, true> (WINDOW:
+// <T, true, true>) for the query at chunk row i of a sequence whose track holds pos0 tokens -- position p = pos0 + i, keys lo .. p,
+// lo = tf_window_lo(p, W) under WINDOW and 0 otherwise -- operation for operation.  The order is tf_attn_row's: per key one fmaf chain
+// over c = 0 .. dh - 1 from 0.f, * scale; lane l takes keys lo + l, lo + l + 64, ..; wave_max, expf, wave_sum; per output dim one fmaf
+// chain over j = lo .. p from 0.f; * (1 / sum), float16 in one rounding (tf_mul_f16_bits) -- and so are the bits: the tests of
+// tests/test_gpu_tf_stream.py, _window.py and _extend.py hold step, extend and tf_attn_row to that.  It is a second definition beside
+// tf_attn_row, not a call, because what differs is the loops themselves: a key comes from one of two buffers, a lane reads its key's
+// slice as 16-byte vectors, and the value pass gives a lane VE output dims and keeps kTfStepUnroll keys' loads in flight in front of
+// their fmafs, where tf_attn_row has one scalar load per trip; each of these would change the loops tf_attn_generic and tf_fused_f32
+// compile from.
+// The keys lie in up to three contiguous runs of rows.  The nc = tf_extend_cached cached keys lo .. pos0 - 1 are cache rows lo .. (kv:
+// the head's k columns of cache row 0 of the track, rows of 2 d: k | v); on a ring key j lives in row j % capacity, the nc keys are
+// consecutive rows from slo = lo % capacity on that wrap at most once (nc < W <= capacity), so a key's row is one add and one
+// conditional subtract in the score pass and the value pass walks two runs (tf_stream_run0), no modulo per key.  Keys max(lo, pos0)
+// .. p are the chunk's own packed qkv rows c0 = tf_extend_chunk0 .. i (chunk: the head's q columns of the sequence's first packed
+// row, rows of 3 d: q | k | v), the query's own among them -- never a cache row the same call writes.  s: the wave's score row, key j
+// at s[j - lo] (the loops count from key lo: an absolute position may be near INT_MAX).
+// ONE: the caller's promise that the chunk is the single row `chunk` (i = 0), which is what a step is: then nc = p - lo, c0 = 0 and
+// the last run is one row.  Without it the compiler cannot see that and unrolls the last run again.
 constexpr int kTfStepUnroll = 16;
 // (float16)(a * b) in ONE rounding, as bits: what the compiler makes of tf_attn_row's `from_f32<f16_t>(o * inv)`, one v_fma_mixlo_f16.
 // A packed store of two such products (v_mul_f32, then v_cvt_pk_f16_f32) rounds to float32 first and to float16 second, and the two
-// roundings differ from the one in the last bit of about one element in 2^13 -- which is what the VEC float16 store of tf_attn_step_row
-// compiled to, against DESIGN.md 25's bit contract with tf_attn_row (no test there had a shape that showed it).  That store spells the
+// roundings differ from the one in the last bit of about one element in 2^13 -- which is what the VEC float16 store of the step row
+// once compiled to, against DESIGN.md 25's bit contract with tf_attn_row (no test there had a shape that showed it).  That store spells the
 // instruction out, so that its bits do not hang on which of the two forms the compiler picks.
 __device__ __forceinline__ unsigned tf_mul_f16_bits(float a, float b) {
   unsigned r = 0;
   asm("v_fma_mixlo_f16 %0, %1, %2, 0" : "+v"(r) : "v"(a), "v"(b));
   return r & 0xffffu;
 }
-// WINDOW (a windowed state): tf_attn_row<T, true, true> for query pos instead -- keys lo .. pos, lo = tf_window_lo(pos, W),
-// lane l takes keys lo + l, lo + l + 64, .., the value chain runs j = lo .. pos from 0.f -- over a ring: key j < pos lives in cache
-// row j % capacity, the score of key j in s[j - lo] (at most W floats; the loops below count j from key lo).  The pos - lo cached keys are consecutive rows from lo % capacity
-// on that wrap at most once (pos - lo < W <= capacity), so a key's row is one add and one conditional subtract in the score pass,
-// and the value pass walks two contiguous runs of rows, each as the unrolled loop below; no modulo per key.
-template <typename T, bool VEC, bool WINDOW = false>
-__device__ __forceinline__ void tf_attn_step_row(const T* tok, const T* kv, size_t ld, T* orow, float* s, int pos, int d, int dh, float scale,
-                                                 int lane, int capacity = 0, int W = 0) {
-  typedef TfSlice<T, VEC> Sl;
-  constexpr int VE = Sl::VE;
-  int lo = 0, slo = 0;                            // first visible key and its cache row
-  if constexpr (WINDOW) { lo = flope_tf_plan::tf_window_lo(pos, W); slo = flope_tf_plan::tf_stream_slot(lo, capacity); }
-  const int nk = pos - lo, L = nk + 1;            // cached keys, visible keys; j below counts from key lo (an absolute pos may be near INT_MAX)
-  float mx = -INFINITY;
-  for (int j = lane; j < L; j += 64) {
-    int row = j;
-    if constexpr (WINDOW) { row = slo + j; if (row >= capacity) row -= capacity; }
-    const T* k = j == nk ? tok + d : kv + (size_t)row * ld;
-    float a = 0.f;
-    for (int c = 0; c < dh; c += VE) {
-      Sl qv, kx;
-      qv.load(tok + c);
-      kx.load(k + c);
-#pragma unroll
-      for (int e = 0; e < VE; ++e) a = fmaf(qv.f[e], kx.f[e], a);
-    }
-    a *= scale;
-    s[j] = a;
-    mx = fmaxf(mx, a);
-  }
-  mx = wave_max(mx);
-  float sum = 0.f;
-  for (int j = lane; j < L; j += 64) { const float p = expf(s[j] - mx); s[j] = p; sum += p; }
-  sum = wave_sum(sum);
-  __builtin_amdgcn_wave_barrier();
-  const float inv = 1.f / sum;
-  for (int c = lane * VE; c < dh; c += 64 * VE) {
-    const T* v = kv + d + c;
-    float o[VE];
-#pragma unroll
-    for (int e = 0; e < VE; ++e) o[e] = 0.f;
-    // cnt consecutive cache rows from vr on, their probabilities from sp on, kTfStepUnroll loads in flight: the chain goes on in key order
-    auto run = [&](const T* vr, const float* sp, int cnt) {
-      int j = 0;
-      for (; j + kTfStepUnroll <= cnt; j += kTfStepUnroll) {
-        Sl vv[kTfStepUnroll];
-#pragma unroll
-        for (int u = 0; u < kTfStepUnroll; ++u) vv[u].load(vr + (size_t)(j + u) * ld);
-#pragma unroll
-        for (int u = 0; u < kTfStepUnroll; ++u) {
-          const float p = sp[j + u];
-#pragma unroll
-          for (int e = 0; e < VE; ++e) o[e] = fmaf(p, vv[u].f[e], o[e]);
-        }
-      }
-      for (; j < cnt; ++j) {
-        Sl vv;
-        vv.load(vr + (size_t)j * ld);
-#pragma unroll
-        for (int e = 0; e < VE; ++e) o[e] = fmaf(sp[j], vv.f[e], o[e]);
-      }
-    };
-    if constexpr (WINDOW) {
-      const int first = flope_tf_plan::tf_stream_run0(slo, nk, capacity);      // keys lo .. pos - 1: rows slo .., then rows 0 ..
-      run(v + (size_t)slo * ld, s, first);
-      run(v, s + first, nk - first);
-    } else {                                      // one run of rows 0 .. pos - 1, spelled out: these instantiations compile from the source they had
-      int j = 0;
-      for (; j + kTfStepUnroll <= pos; j += kTfStepUnroll) {
-        Sl vv[kTfStepUnroll];
-#pragma unroll
-        for (int u = 0; u < kTfStepUnroll; ++u) vv[u].load(v + (size_t)(j + u) * ld);
-#pragma unroll
-        for (int u = 0; u < kTfStepUnroll; ++u) {
-          const float p = s[j + u];
-#pragma unroll
-          for (int e = 0; e < VE; ++e) o[e] = fmaf(p, vv[u].f[e], o[e]);
-        }
-      }
-      for (; j < pos; ++j) {
-        Sl vv;
-        vv.load(v + (size_t)j * ld);
-#pragma unroll
-        for (int e = 0; e < VE; ++e) o[e] = fmaf(s[j], vv.f[e], o[e]);
-      }
-    }
-    Sl vv;
-    vv.load(tok + 2 * d + c);                     // the value of position pos: from the qkv row, never from the cache row stored above
-    if constexpr (VEC && std::is_same<T, f16_t>::value) {      // one rounding per element, as tf_attn_row's store (tf_mul_f16_bits)
-      u32x4 w;
-#pragma unroll
-      for (int e = 0; e < VE; e += 2)
-        w[e / 2] = tf_mul_f16_bits(fmaf(s[nk], vv.f[e], o[e]), inv) | (tf_mul_f16_bits(fmaf(s[nk], vv.f[e + 1], o[e + 1]), inv) << 16);
-      *(u32x4*)(orow + c) = w;
-    } else {
-#pragma unroll
-      for (int e = 0; e < VE; ++e) vv.f[e] = fmaf(s[nk], vv.f[e], o[e]) * inv;
-      vv.store(orow + c);
-    }
-  }
-  __builtin_amdgcn_wave_barrier();
-}
-
-// One new token per track: wave (row r, head h) takes q, k and v of the token from row r of qkv [n][3 d], stores that k | v slice
-// into row pos of its track in cache [tracks][capacity][2 d] (one layer's part; for later steps only) and writes
-// softmax(q K^T / sqrt(dh)) V over keys 0 .. pos to att [n][d].  tab: (track, pos) per row.  smax: floats of a wave's score row
-// (the call's largest pos + 1).  A row whose table entry is no track, no row of the cache or past the score row is left alone:
-// nothing is written outside the track's capacity rows, whatever the table holds.
-// WINDOW: pos is absolute and unbounded, the cache a ring -- the slice goes to row pos % capacity, attention is over keys
-// tf_window_lo(pos, W) .. pos, smax the call's largest visible key count (<= W).  The overwrite is safe: row pos % capacity held key
-// pos - capacity <= pos - W, which is outside every window that includes pos, so no wave of this launch reads it (the launch's rows
-// are distinct tracks, and the heads of one row touch distinct columns).  Left alone: a row whose track is out of range, whose pos is
-// negative or whose visible keys exceed the score row; pos % capacity is a row of the track whatever else the table holds.
-template <typename T, bool VEC, bool WINDOW = false>
-__global__ __launch_bounds__(256) void tf_attn_step(const T* __restrict__ qkv, T* cache, T* __restrict__ att, const int* __restrict__ tab, int n,
-                                                    int d, int H, int tracks, int capacity, int smax, int W) {
-  extern __shared__ __attribute__((aligned(16))) float sc[];     // [waves][smax]
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int it = blockIdx.x * flope_tf_plan::kTfStepWaves + wave;
-  if (it >= n * H) return;
-  const int r = it / H, h = it - r * H, dh = d / H;
-  const int track = tab[2 * r], pos = tab[2 * r + 1];
-  int slot = pos;                                                // the cache row of the token
-  if constexpr (WINDOW) {
-    if ((unsigned)track >= (unsigned)tracks || pos < 0 || W < 1 || W > capacity || flope_tf_plan::tf_window_keys(pos, W) > smax) return;
-    slot = flope_tf_plan::tf_stream_slot(pos, capacity);
-  } else {
-    if ((unsigned)track >= (unsigned)tracks || (unsigned)pos >= (unsigned)capacity || pos >= smax) return;
-  }
-  const float scale = 1.f / sqrtf((float)dh);
-  const size_t ld = (size_t)2 * d;
-  const T* tok = qkv + (size_t)r * 3 * d + h * dh;
-  T* kv = cache + (size_t)track * capacity * ld + h * dh;
-  constexpr int VE = TfSlice<T, VEC>::VE;
-  for (int c = lane * VE; c < 2 * dh; c += 64 * VE) {            // k slice | v slice of the token -> cache row pos (WINDOW: pos % capacity)
-    const int col = c < dh ? c : c - dh + d;
-    if constexpr (VEC) *(u32x4*)(kv + slot * ld + col) = *(const u32x4*)(tok + d + col);
-    else kv[slot * ld + col] = tok[d + col];
-  }
-  tf_attn_step_row<T, VEC, WINDOW>(tok, kv, ld, att + (size_t)r * d + h * dh, sc + (size_t)wave * smax, pos, d, dh, scale, lane, capacity, W);
-}
-
-// prefill: the k | v columns (d .. 3 d) of the valid packed rows of qkv [T][3 d] -> rows 0 .. len - 1 of each sequence's track in
-// cache [tracks][capacity][2 d].  off: the ragged batch's offsets; trk: the track of sequence b.  V: u32x4 (dv = d / elements per 16
-// bytes) or the element type (dv = d).  A sequence whose entry is no track, and rows past capacity, are skipped.
-// WINDOW (a ring): token i of a sequence of len tokens goes to row i % capacity, and only the last min(len, capacity) tokens go
-// (tf_stream_fill_writes) -- the earlier ones share their rows with those, and two threads would write one address.
-template <typename V, bool WINDOW = false>
-__global__ void tf_cache_fill(const V* __restrict__ qkv, V* __restrict__ cache, const int* __restrict__ off, const int* __restrict__ trk,
-                              int max_len, int dv, int tracks, int capacity, size_t total) {
-  const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (idx >= total) return;
-  const size_t r = idx / (2 * dv);
-  const int c = (int)(idx - r * (2 * dv)), b = (int)(r / max_len), i = (int)(r - (size_t)b * max_len);
-  const int o = off[b], t = trk[b];
-  if constexpr (WINDOW) {
-    const int len = off[b + 1] - o;
-    if (i >= len || !flope_tf_plan::tf_stream_fill_writes(i, len, capacity) || (unsigned)t >= (unsigned)tracks) return;
-    cache[((size_t)t * capacity + flope_tf_plan::tf_stream_slot(i, capacity)) * 2 * dv + c] = qkv[(size_t)(o + i) * 3 * dv + dv + c];
-  } else {
-    if (i >= off[b + 1] - o || i >= capacity || (unsigned)t >= (unsigned)tracks) return;
-    cache[((size_t)t * capacity + i) * 2 * dv + c] = qkv[(size_t)(o + i) * 3 * dv + dv + c];
-  }
-}
-
-// ---- extend: several tokens per track and call (flope_tf_stream_extend; DESIGN.md 29) ----------------------------------------------
-// tf_attn_row<T, true(, true)> for the query at chunk row i of a sequence whose track holds pos0 tokens -- position p = pos0 + i, keys
-// lo .. p -- operation for operation, as tf_attn_step_row is: per key one fmaf chain over c = 0 .. dh - 1 from 0.f, * scale; lane l
-// takes keys lo + l, lo + l + 64, ..; wave_max, expf, wave_sum; per output dim one fmaf chain over j = lo .. p from 0.f; * (1 / sum),
-// float16 in one rounding (tf_mul_f16_bits).  The keys lie in up to three contiguous runs of rows: the cached keys lo .. pos0 - 1 in
-// rows slo .. of the track's cache and, where a ring wraps, from row 0 on (tf_stream_run0), then keys max(lo, pos0) .. p in the
-// chunk's own packed qkv rows, the query's among them -- never in a cache row this call writes (tf_cache_append runs behind this
-// kernel).  chunk: the head's q columns of the sequence's first packed row (rows of 3 d: q | k | v); kv: the head's k columns of
-// cache row 0 of the track (rows of 2 d: k | v); s: the wave's score row, key j at s[j - lo].
-template <typename T, bool VEC, bool WINDOW>
-__device__ __forceinline__ void tf_attn_extend_row(const T* chunk, const T* kv, T* orow, float* s, int pos0, int i, int d, int dh, float scale,
+template <typename T, bool VEC, bool WINDOW, bool ONE>
+__device__ __forceinline__ void tf_attn_stream_row(const T* chunk, const T* kv, T* orow, float* s, int pos0, int i, int d, int dh, float scale,
                                                    int lane, int capacity, int W) {
   typedef TfSlice<T, VEC> Sl;
   constexpr int VE = Sl::VE;
@@ -577,8 +413,8 @@ __device__ __forceinline__ void tf_attn_extend_row(const T* chunk, const T* kv, 
   const int p = pos0 + i;
   int lo = 0, slo = 0;                            // first visible key and, where it is a cached one, its cache row
   if constexpr (WINDOW) { lo = flope_tf_plan::tf_window_lo(p, W); slo = flope_tf_plan::tf_stream_slot(lo, capacity); }
-  const int nc = flope_tf_plan::tf_extend_cached(pos0, lo), c0 = flope_tf_plan::tf_extend_chunk0(pos0, lo);
-  const int L = p - lo + 1;                       // visible keys: nc cached ones, then chunk rows c0 .. i
+  const int nc = ONE ? p - lo : flope_tf_plan::tf_extend_cached(pos0, lo), c0 = ONE ? 0 : flope_tf_plan::tf_extend_chunk0(pos0, lo);
+  const int L = p - lo + 1, own = ONE ? 1 : L - nc;   // visible keys: nc cached ones, then the `own` chunk rows c0 .. i
   const T* q = chunk + (size_t)i * ldc;
   float mx = -INFINITY;
   for (int j = lane; j < L; j += 64) {
@@ -587,7 +423,7 @@ __device__ __forceinline__ void tf_attn_extend_row(const T* chunk, const T* kv, 
       int row = j;
       if constexpr (WINDOW) { row = slo + j; if (row >= capacity) row -= capacity; }
       k = kv + (size_t)row * ld;
-    } else k = chunk + (size_t)(c0 + j - nc) * ldc + d;
+    } else k = chunk + (ONE ? 0 : (size_t)(c0 + j - nc) * ldc) + d;
     float a = 0.f;
     for (int c = 0; c < dh; c += VE) {
       Sl qv, kx;
@@ -610,7 +446,8 @@ __device__ __forceinline__ void tf_attn_extend_row(const T* chunk, const T* kv, 
     float o[VE];
 #pragma unroll
     for (int e = 0; e < VE; ++e) o[e] = 0.f;
-    // cnt consecutive rows of ldr elements from vr on, their probabilities from sp on, kTfStepUnroll loads in flight: the chain goes on in key order
+    // cnt consecutive rows of ldr elements from vr on, their probabilities from sp on, kTfStepUnroll loads in flight: the chain goes on
+    // in key order.  (tf_attn_split_row's value loop is strided by lane group and predicated per key: another loop, not a copy of this.)
     auto run = [&](const T* vr, size_t ldr, const float* sp, int cnt) {
       int j = 0;
       for (; j + kTfStepUnroll <= cnt; j += kTfStepUnroll) {
@@ -637,7 +474,7 @@ __device__ __forceinline__ void tf_attn_extend_row(const T* chunk, const T* kv, 
       run(v + (size_t)slo * ld, ld, s, first);
       run(v, ld, s + first, nc - first);
     } else run(v, ld, s, nc);                                                  // rows 0 .. pos0 - 1
-    run(chunk + (size_t)c0 * ldc + 2 * d + c, ldc, s + nc, L - nc);            // chunk rows c0 .. i
+    run(chunk + (size_t)c0 * ldc + 2 * d + c, ldc, s + nc, own);               // chunk rows c0 .. i
     if constexpr (std::is_same<T, f16_t>::value) {      // one rounding per element, as tf_attn_row's store
       if constexpr (VEC) {
         u32x4 w;
@@ -655,12 +492,66 @@ __device__ __forceinline__ void tf_attn_extend_row(const T* chunk, const T* kv, 
   __builtin_amdgcn_wave_barrier();
 }
 
+// Whether the table entry (track, pos0) of a step (len = 1) or of a chunk of len tokens may touch its track's cache: the track is one,
+// the chunk has a token, and its positions pos0 .. pos0 + len - 1 are rows of a linear cache, or ints over a ring whose window W is
+// one this cache can hold.  Every stream kernel leaves on `false` before its first load from or store to the cache; the two with a
+// score row test smax beside it.  What each had of its own before this was one function:
+//   tf_attn_step, tf_attn_step_split, linear: `(unsigned)pos >= (unsigned)capacity` is pos0 < 0 || pos0 > capacity - 1, the last line
+//     at len = 1 (that one-compare form is kept: with two signed compares the f16 step measured 0.3 - 0.5 % slower);  WINDOW: track, pos < 0, W < 1, W > capacity -- and now pos0 == INT_MAX too, which the host refuses (kTfStreamFull)
+//   tf_attn_extend, tf_attn_extend_split: these very tests (linear: pos0 < 0 || pos0 > capacity - len, with len <= capacity in front
+//     so that capacity - len is no negative number turned large)
+//   tf_attn16_extend: tf_extend_mfma_positions_ok is pos0 >= 0, len >= 1 and a bound below INT_MAX - len; it stays at the call
+//   tf_cache_append (W = capacity: it has no window to test): track, pos0 < 0, the two position tests; i < len gives len >= 1
+template <bool WINDOW>
+__device__ __forceinline__ bool tf_stream_entry_ok(int track, int pos0, int len, int tracks, int capacity, int W) {
+  if ((unsigned)track >= (unsigned)tracks || len < 1) return false;
+  if constexpr (WINDOW) return pos0 >= 0 && W >= 1 && W <= capacity && pos0 <= INT_MAX - len;
+  else return len <= capacity && (unsigned)pos0 <= (unsigned)(capacity - len);     // 0 <= pos0 <= capacity - len in one compare
+}
+
+// One new token per track: wave (row r, head h) takes q, k and v of the token from row r of qkv [n][3 d], stores that k | v slice
+// into row pos of its track in cache [tracks][capacity][2 d] (one layer's part; for later steps only) and writes
+// softmax(q K^T / sqrt(dh)) V over keys 0 .. pos to att [n][d].  tab: (track, pos) per row.  smax: floats of a wave's score row
+// (the call's largest pos + 1).  A row whose table entry is no track, no row of the cache or past the score row is left alone:
+// nothing is written outside the track's capacity rows, whatever the table holds.
+// WINDOW: pos is absolute and unbounded, the cache a ring -- the slice goes to row pos % capacity, attention is over keys
+// tf_window_lo(pos, W) .. pos, smax the call's largest visible key count (<= W).  The overwrite is safe: row pos % capacity held key
+// pos - capacity <= pos - W, which is outside every window that includes pos, so no wave of this launch reads it (the launch's rows
+// are distinct tracks, and the heads of one row touch distinct columns).  Left alone: a row whose track is out of range, whose pos is
+// negative or whose visible keys exceed the score row; pos % capacity is a row of the track whatever else the table holds.
+template <typename T, bool VEC, bool WINDOW = false>
+__global__ __launch_bounds__(256) void tf_attn_step(const T* __restrict__ qkv, T* cache, T* __restrict__ att, const int* __restrict__ tab, int n,
+                                                    int d, int H, int tracks, int capacity, int smax, int W) {
+  extern __shared__ __attribute__((aligned(16))) float sc[];     // [waves][smax]
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int it = blockIdx.x * flope_tf_plan::kTfStepWaves + wave;
+  if (it >= n * H) return;
+  const int r = it / H, h = it - r * H, dh = d / H;
+  const int track = tab[2 * r], pos = tab[2 * r + 1];
+  if (!tf_stream_entry_ok<WINDOW>(track, pos, 1, tracks, capacity, W) || flope_tf_plan::tf_window_keys(pos, WINDOW ? W : 0) > smax) return;
+  const int slot = WINDOW ? flope_tf_plan::tf_stream_slot(pos, capacity) : pos;      // the cache row of the token
+  const float scale = 1.f / sqrtf((float)dh);
+  const size_t ld = (size_t)2 * d;
+  const T* tok = qkv + (size_t)r * 3 * d + h * dh;
+  T* kv = cache + (size_t)track * capacity * ld + h * dh;
+  constexpr int VE = TfSlice<T, VEC>::VE;
+  for (int c = lane * VE; c < 2 * dh; c += 64 * VE) {            // k slice | v slice of the token -> cache row pos (WINDOW: pos % capacity)
+    const int col = c < dh ? c : c - dh + d;
+    if constexpr (VEC) *(u32x4*)(kv + slot * ld + col) = *(const u32x4*)(tok + d + col);
+    else kv[slot * ld + col] = tok[d + col];
+  }
+  // a step is an extend of one row: chunk = the token's row, pos0 = pos, i = 0
+  tf_attn_stream_row<T, VEC, WINDOW, true>(tok, kv, att + (size_t)r * d + h * dh, sc + (size_t)wave * smax, pos, 0, d, dh, scale, lane, capacity, W);
+}
+
+// ---- extend: several tokens per track and call (flope_tf_stream_extend; DESIGN.md 29) ----------------------------------------------
+
 // n sequences of a ragged batch (qkv: packed rows, sequence b = rows off[b] .. off[b + 1] - 1), each the next tokens of one track.
 // Workgroup (b, h) x blockIdx.y: its four waves take consecutive queries of that sequence and head, as tf_attn_generic<.., VARLEN>
 // does, so they stream the same cache rows -- in tf_attn_step every wave walks another track.  tab: (track, pos0) per sequence.
 // smax: floats of a wave's score row, the call's largest visible key count.  Reads the cache, writes att alone; a workgroup whose
 // table entry is no track, whose positions leave the cache (linear: pos0 + len > capacity; a ring: past INT_MAX, or a window that is
-// none of this cache's) or whose keys exceed the score row exits before it stores anything (tf_attn_step's rule).
+// none of this cache's) or whose keys exceed the score row exits before it stores anything (tf_stream_entry_ok, and smax).
 template <typename T, bool VEC, bool WINDOW>
 __global__ __launch_bounds__(256) void tf_attn_extend(const T* __restrict__ qkv, const T* __restrict__ cache, T* __restrict__ att,
                                                       const int* __restrict__ tab, const int* __restrict__ off, int n, int d, int H, int tracks,
@@ -671,26 +562,24 @@ __global__ __launch_bounds__(256) void tf_attn_extend(const T* __restrict__ qkv,
   if (b >= n) return;
   const int track = tab[2 * b], pos0 = tab[2 * b + 1];
   const int o = off[b], len = off[b + 1] - o;
-  if ((unsigned)track >= (unsigned)tracks || pos0 < 0 || len < 1) return;
-  if constexpr (WINDOW) {
-    if (W < 1 || W > capacity || pos0 > INT_MAX - len || flope_tf_plan::tf_extend_keys(pos0, len, W) > smax) return;
-  } else {
-    if (pos0 > capacity - len || pos0 + len > smax) return;
-  }
+  if (!tf_stream_entry_ok<WINDOW>(track, pos0, len, tracks, capacity, W) || flope_tf_plan::tf_extend_keys(pos0, len, WINDOW ? W : 0) > smax) return;
   const float scale = 1.f / sqrtf((float)dh);
   const T* chunk = qkv + (size_t)o * 3 * d + h * dh;
   const T* kv = cache + (size_t)track * capacity * 2 * d + h * dh;
   float* s = sc + (size_t)wave * smax;
   for (int i = blockIdx.y * flope_tf_plan::kTfStepWaves + wave; i < len; i += gridDim.y * flope_tf_plan::kTfStepWaves)
-    tf_attn_extend_row<T, VEC, WINDOW>(chunk, kv, att + (size_t)(o + i) * d + h * dh, s, pos0, i, d, dh, scale, lane, capacity, W);
+    tf_attn_stream_row<T, VEC, WINDOW, false>(chunk, kv, att + (size_t)(o + i) * d + h * dh, s, pos0, i, d, dh, scale, lane, capacity, W);
 }
 
-// ... and the append behind it: the k | v columns of chunk row i of sequence b -> cache row pos0 + i of its track (a ring: row
-// (pos0 + i) % capacity, the chunk's last min(len, capacity) tokens only, tf_stream_append_writes -- every row once).  tf_cache_fill
-// with a start position per sequence: tab is tf_attn_extend's table, V and dv as there.  It runs BEHIND the layer's tf_attn_extend:
-// on a ring the token at p takes the row of key p - capacity, which an earlier query of the same chunk still sees once
-// len >= capacity - W + 2 (at capacity == W: every chunk of two tokens).  A sequence whose entry is no track or whose rows leave the
-// cache is skipped.
+// The one cache copy: the k | v columns (d .. 3 d) of the valid packed rows of qkv [T][3 d] -> the cache [tracks][capacity][2 d]: row
+// i of sequence b goes to cache row pos0 + i of its track (a ring: row (pos0 + i) % capacity, and only the sequence's last min(len,
+// capacity) tokens go, tf_stream_append_writes -- the earlier ones share their rows with those, and two threads would write one
+// address).  off: the ragged batch's offsets; tab: (track, pos0) per sequence -- tf_attn_extend's table for the append of an extend,
+// (track, 0) for a prefill.  V: u32x4 (dv = d / elements per 16 bytes) or the element type (dv = d).  A sequence whose entry is no
+// track or whose rows leave the cache is skipped as a whole (tf_stream_entry_ok).
+// An extend runs it BEHIND the layer's tf_attn_extend: on a ring the token at p takes the row of key p - capacity, which an earlier
+// query of the same chunk still sees once len >= capacity - W + 2 (at capacity == W: every chunk of two tokens).  A prefill runs it
+// in front of the layer's attention, which reads the packed rows and not the cache.
 template <typename V, bool WINDOW>
 __global__ void tf_cache_append(const V* __restrict__ qkv, V* __restrict__ cache, const int* __restrict__ off, const int* __restrict__ tab,
                                 int max_len, int dv, int tracks, int capacity, size_t total) {
@@ -699,14 +588,11 @@ __global__ void tf_cache_append(const V* __restrict__ qkv, V* __restrict__ cache
   const size_t r = idx / (2 * dv);
   const int c = (int)(idx - r * (2 * dv)), b = (int)(r / max_len), i = (int)(r - (size_t)b * max_len);
   const int o = off[b], len = off[b + 1] - o, t = tab[2 * b], pos0 = tab[2 * b + 1];
-  if (i >= len || (unsigned)t >= (unsigned)tracks || pos0 < 0) return;
-  int row;
+  if (i >= len || !tf_stream_entry_ok<WINDOW>(t, pos0, len, tracks, capacity, capacity)) return;
+  int row = pos0 + i;
   if constexpr (WINDOW) {
-    if (pos0 > INT_MAX - len || !flope_tf_plan::tf_stream_append_writes(i, len, capacity)) return;
+    if (!flope_tf_plan::tf_stream_append_writes(i, len, capacity)) return;
     row = flope_tf_plan::tf_stream_append_slot(pos0, i, capacity);
-  } else {
-    if (pos0 > capacity - len) return;
-    row = pos0 + i;
   }
   cache[((size_t)t * capacity + row) * 2 * dv + c] = qkv[(size_t)(o + i) * 3 * dv + dv + c];
 }
@@ -730,7 +616,7 @@ template <typename T, bool WINDOW> struct TfSplitKeys {
 // softmax(q K^T / sqrt(dh)) V over the L >= 1 keys of `keys` on the four waves of a workgroup, every thread of which calls this with
 // the same arguments.  The order, fixed here once for the step and the extend:
 //   wave w walks blocks b = w, w + 4, .. of 64 keys (tf_split_wave) in ascending order.  In a block lane l scores key 64 b + l -- one
-//   fmaf chain over c = 0 .. dh - 1 from 0.f, * scale, as tf_attn_step_row -- the block maximum goes across the wave, the running
+//   fmaf chain over c = 0 .. dh - 1 from 0.f, * scale, as tf_attn_stream_row -- the block maximum goes across the wave, the running
 //   (m, l, o) is rescaled by expf(m - m'), p = expf(score - m') is added to the lane's own l, and the 64 p go to the wave's LDS row.
 //   Value pass: the lanes form G = 64 / LPS groups of LPS = dh / VE lanes; group g adds keys g, g + G, .. of the block to its partial
 //   o (lane s of the group: dims s VE .. s VE + VE - 1), one 16-byte load per lane and key, the block's loads in flight before their
@@ -837,8 +723,8 @@ __device__ __forceinline__ void tf_attn_split_row(const TfSplitKeys<T, WINDOW>& 
   __syncthreads();
 }
 
-// tf_attn_step with the row above: workgroup (row r, head h).  The slice store, the table and the memory-safety exits are
-// tf_attn_step's (no score row, so no smax); every exit depends on the workgroup's table entry alone, so a workgroup leaves as one,
+// tf_attn_step with the row above: workgroup (row r, head h).  The slice store, the table and the memory-safety exit
+// (tf_stream_entry_ok; no score row, so no smax) are tf_attn_step's; the exit depends on the workgroup's table entry alone, so a workgroup leaves as one,
 // before its first store and before any barrier.  The token's own key and value come from its qkv row, never from the cache row
 // stored here.
 template <typename T, bool WINDOW>
@@ -848,14 +734,8 @@ __global__ __launch_bounds__(256) void tf_attn_step_split(const T* __restrict__ 
   const int r = blockIdx.x / H, h = blockIdx.x - r * H, dh = d / H;
   if (r >= n) return;
   const int track = tab[2 * r], pos = tab[2 * r + 1];
-  int slot = pos, lo = 0;
-  if constexpr (WINDOW) {
-    if ((unsigned)track >= (unsigned)tracks || pos < 0 || W < 1 || W > capacity) return;
-    slot = flope_tf_plan::tf_stream_slot(pos, capacity);
-    lo = flope_tf_plan::tf_window_lo(pos, W);
-  } else {
-    if ((unsigned)track >= (unsigned)tracks || (unsigned)pos >= (unsigned)capacity) return;
-  }
+  if (!tf_stream_entry_ok<WINDOW>(track, pos, 1, tracks, capacity, W)) return;
+  const int slot = WINDOW ? flope_tf_plan::tf_stream_slot(pos, capacity) : pos, lo = WINDOW ? flope_tf_plan::tf_window_lo(pos, W) : 0;
   const float scale = 1.f / sqrtf((float)dh);
   const size_t ld = (size_t)2 * d;
   const T* tok = qkv + (size_t)r * 3 * d + h * dh;
@@ -870,8 +750,8 @@ __global__ __launch_bounds__(256) void tf_attn_step_split(const T* __restrict__ 
 }
 
 // tf_attn_extend with the row above: workgroup (sequence b, head h) x blockIdx.y takes queries blockIdx.y, + gridDim.y, .. of the
-// sequence, one at a time on its four waves.  Reads the cache, writes att alone (tf_cache_append runs behind it); the exits are
-// tf_attn_extend's and uniform for the workgroup, as is the trip count.
+// sequence, one at a time on its four waves.  Reads the cache, writes att alone (tf_cache_append runs behind it); the exit is
+// tf_stream_entry_ok's and uniform for the workgroup, as is the trip count.
 template <typename T, bool WINDOW>
 __global__ __launch_bounds__(256) void tf_attn_extend_split(const T* __restrict__ qkv, const T* __restrict__ cache, T* __restrict__ att,
                                                             const int* __restrict__ tab, const int* __restrict__ off, int n, int d, int H, int tracks,
@@ -881,12 +761,7 @@ __global__ __launch_bounds__(256) void tf_attn_extend_split(const T* __restrict_
   if (b >= n) return;
   const int track = tab[2 * b], pos0 = tab[2 * b + 1];
   const int o = off[b], len = off[b + 1] - o;
-  if ((unsigned)track >= (unsigned)tracks || pos0 < 0 || len < 1) return;
-  if constexpr (WINDOW) {
-    if (W < 1 || W > capacity || pos0 > INT_MAX - len) return;
-  } else {
-    if (pos0 > capacity - len) return;
-  }
+  if (!tf_stream_entry_ok<WINDOW>(track, pos0, len, tracks, capacity, W)) return;
   const float scale = 1.f / sqrtf((float)dh);
   const size_t ld = (size_t)2 * d, ldc = (size_t)3 * d;
   const T* chunk = qkv + (size_t)o * ldc + h * dh;
@@ -1395,7 +1270,7 @@ __global__ __launch_bounds__(256, 2) void tf_attn_tiled(const T* __restrict__ qk
 // A query's state in tf_attn16_step depends on its own row alone, a step that is masked for it as a whole leaves it unchanged and
 // under WINDOW it stays at exactly 0 until the query's first own key: so the same absolute steps give a chunk row the bits tf_attn_tiled
 // / tf_attn_mfma give row pos0 + i of the whole track, whichever queries share its wave.
-// Exits, all per workgroup and in front of the first load, store and barrier: tf_attn_extend's (no track, positions that leave the
+// Exits, all per workgroup and in front of the first load, store and barrier: tf_stream_entry_ok's (no track, positions that leave the
 // cache, a window that is none of this cache's), positions past kTfExtendMfmaPosMax, and a query block behind the chunk.  A workgroup
 // with some valid queries keeps all four waves in the barrier loop; queries behind the chunk are clamped for their Q rows and not
 // stored.  Reads the cache, writes att alone: tf_cache_append stays behind it (tf_encoder_stream.h).
@@ -1413,9 +1288,7 @@ __global__ __launch_bounds__(256, 2) void tf_attn16_extend(const T* __restrict__
   if (b >= n) return;
   const int track = tab[2 * b], pos0 = tab[2 * b + 1];
   const int ob = off[b], len = off[b + 1] - ob;
-  if ((unsigned)track >= (unsigned)tracks || !flope_tf_plan::tf_extend_mfma_positions_ok(pos0, len)) return;
-  if constexpr (WINDOW) { if (W < 1 || W > capacity) return; }
-  else { if (pos0 > capacity - len) return; }
+  if (!tf_stream_entry_ok<WINDOW>(track, pos0, len, tracks, capacity, W) || !flope_tf_plan::tf_extend_mfma_positions_ok(pos0, len)) return;
   if (!flope_tf_plan::tf_extend_mfma_block_live(len, y)) return;
   const int Wk = WINDOW ? W : 0, Labs = pos0 + len;
   const T* chunk = qkv + (size_t)ob * 3 * d + h * HD;                        // chunk row i: k at + d, v at + 2 d
@@ -2648,9 +2521,13 @@ int tf_stream_refuse(flope_tf_stream_s* s, const std::string& who, int rc, int b
   }
 }
 
+// what the step's and the extend's launches both ask: the head_dim, and whether the row kernels move a head slice as 16-byte vectors
+inline int tf_head_dim(const flope_tf_encoder* e) { return e->d / e->H; }
+template <typename T> bool tf_row_vec(const flope_tf_encoder* e) { return flope_tf_plan::tf_step_vec_ok(tf_head_dim(e), (int)sizeof(T)); }
+
 // which of FLOPE_TF_STEP_ROW / _SPLIT a step or extend of this state launches now
 template <typename T> int tf_step_plan(const flope_tf_encoder* e) {
-  return e->opt_step_split && flope_tf_plan::tf_step_split_ok(e->d / e->H, (int)sizeof(T)) ? FLOPE_TF_STEP_SPLIT : FLOPE_TF_STEP_ROW;
+  return e->opt_step_split && flope_tf_plan::tf_step_split_ok(tf_head_dim(e), (int)sizeof(T)) ? FLOPE_TF_STEP_SPLIT : FLOPE_TF_STEP_ROW;
 }
 
 // the attention launch of a step: n rows of qkv [n][3 d] against one layer's part of the cache -> att [n][d]; the table is s->tab.
@@ -2660,7 +2537,7 @@ int launch_step_attn(flope_tf_stream_s* s, const T* qkv, T* cache, T* att, int n
   flope_tf_encoder* e = s->e;
   const int plan = tf_step_plan<T>(e);
   if (plan == FLOPE_TF_STEP_SPLIT) {
-    const flope_tf_plan::TfStreamLaunch l = flope_tf_plan::tf_step_split_launch(n, e->H, e->d / e->H);
+    const flope_tf_plan::TfStreamLaunch l = flope_tf_plan::tf_step_split_launch(n, e->H, tf_head_dim(e));
 #define TF_SPLIT(WIN_) hipLaunchKernelGGL((tf_attn_step_split<T, WIN_>), dim3(l.grid_x), dim3(l.block), l.lds, st, qkv, cache, att, (const int*)s->tab, n, e->d, \
                                           e->H, s->tracks, s->capacity, s->window)
     if (s->window) TF_SPLIT(true); else TF_SPLIT(false);
@@ -2669,7 +2546,7 @@ int launch_step_attn(flope_tf_stream_s* s, const T* qkv, T* cache, T* att, int n
     const flope_tf_plan::TfStreamLaunch l = flope_tf_plan::tf_step_launch(n, e->H, max_pos);
 #define TF_STEP(VEC_, WIN_) hipLaunchKernelGGL((tf_attn_step<T, VEC_, WIN_>), dim3(l.grid_x), dim3(l.block), l.lds, st, qkv, cache, att, \
                                               (const int*)s->tab, n, e->d, e->H, s->tracks, s->capacity, max_pos + 1, s->window)
-    if (flope_tf_plan::tf_step_vec_ok(e->d / e->H, (int)sizeof(T))) { if (s->window) TF_STEP(true, true); else TF_STEP(true, false); }
+    if (tf_row_vec<T>(e)) { if (s->window) TF_STEP(true, true); else TF_STEP(true, false); }
     else { if (s->window) TF_STEP(false, true); else TF_STEP(false, false); }
 #undef TF_STEP
   }
@@ -2689,24 +2566,33 @@ int run_step(flope_tf_stream_s* s, const float* x, int n, int max_pos, float* y,
   });
 }
 
+// the one launch of tf_cache_append: the k | v columns of the n sequences of src_qkv (rows of 3 d; offsets `off`, at most max_len rows
+// each) into one layer's part of the cache, at the (track, pos0) of `tab`.  16-byte vectors where a row's columns are whole ones.
+template <typename T>
+int launch_cache_copy(flope_tf_stream_s* s, const T* src_qkv, T* cache, const int* off, const int* tab, int n, int max_len, hipStream_t st) {
+  flope_tf_encoder* e = s->e;
+  const bool vec = flope_tf_plan::tf_cache_fill_vec_ok(e->d, (int)sizeof(T));
+  const int dv = vec ? e->d / flope_tf_plan::tf_stream_vec((int)sizeof(T)) : e->d;
+  const flope_tf_plan::TfStreamLaunch l = flope_tf_plan::tf_cache_append_launch(n, max_len, 2 * dv);
+  const size_t total = (size_t)n * max_len * 2 * dv;
+#define TF_COPY(V_, WIN_) hipLaunchKernelGGL((tf_cache_append<V_, WIN_>), dim3(l.grid_x), dim3(l.block), 0, st, (const V_*)src_qkv, (V_*)cache, off, tab, max_len, dv, \
+                                            s->tracks, s->capacity, total)
+  if (vec) { if (s->window) TF_COPY(u32x4, true); else TF_COPY(u32x4, false); }
+  else { if (s->window) TF_COPY(T, true); else TF_COPY(T, false); }
+#undef TF_COPY
+  TF_HIP(e, hipGetLastError());
+  return 0;
+}
+
 // the causal ragged forward's launch sequence, each layer's k | v rows copied into the cache in front of its attention (a windowed
-// state: the last min(len, capacity) rows of a sequence, into the ring)
+// state: the last min(len, capacity) rows of a sequence, into the ring).  s->tab: (track, 0) per sequence
 template <typename T>
 int run_prefill(flope_tf_stream_s* s, const float* x, int n, int L, const TfRagged& rg, float* y, hipStream_t st) {
   flope_tf_encoder* e = s->e;
   const size_t layer = (size_t)s->tracks * s->capacity * 2 * e->d;
-  const bool vec = flope_tf_plan::tf_cache_fill_vec_ok(e->d, (int)sizeof(T));
-  const int dv = vec ? e->d / flope_tf_plan::tf_stream_vec((int)sizeof(T)) : e->d;
-  const flope_tf_plan::TfStreamLaunch l = flope_tf_plan::tf_cache_fill_launch(n, rg.max_len, 2 * dv);
-  const size_t total = (size_t)n * rg.max_len * 2 * dv;
   return run_forward_with<T>(e, x, n, L, y, st, &rg, [&](int li) {
-    T* cache = (T*)s->cache + (size_t)li * layer;
-#define TF_FILL(V_, WIN_) hipLaunchKernelGGL((tf_cache_fill<V_, WIN_>), dim3(l.grid_x), dim3(l.block), 0, st, (const V_*)e->qkv, (V_*)cache, (const int*)e->vl_off, \
-                                            (const int*)s->tab, rg.max_len, dv, s->tracks, s->capacity, total)
-    if (vec) { if (s->window) TF_FILL(u32x4, true); else TF_FILL(u32x4, false); }
-    else { if (s->window) TF_FILL(T, true); else TF_FILL(T, false); }
-#undef TF_FILL
-    TF_HIP(e, hipGetLastError());
+    const int rc = launch_cache_copy<T>(s, (const T*)e->qkv, (T*)s->cache + (size_t)li * layer, (const int*)e->vl_off, (const int*)s->tab, n, rg.max_len, st);
+    if (rc) return rc;
     return launch_attention<T>(e, e->qkv, e->att, n, rg.max_len, e->vl_off, st);
   });
 }
@@ -2717,7 +2603,7 @@ int run_prefill(flope_tf_stream_s* s, const float* x, int n, int L, const TfRagg
 // which of FLOPE_TF_EXTEND_ROW / _SPLIT / _MFMA an extend of this state launches now: option extend_mfma where tf_extend_mfma_ok, in
 // front of option step_split.  pos_ok: every chunk of the call stays below kTfExtendMfmaPosMax (a plan without a call: true)
 template <typename T> int tf_extend_plan(const flope_tf_encoder* e, bool pos_ok = true) {
-  if (e->opt_extend_mfma && pos_ok && flope_tf_plan::tf_extend_mfma_ok(e->dtype, e->d / e->H, e->d)) return FLOPE_TF_EXTEND_MFMA;
+  if (e->opt_extend_mfma && pos_ok && flope_tf_plan::tf_extend_mfma_ok(e->dtype, tf_head_dim(e), e->d)) return FLOPE_TF_EXTEND_MFMA;
   return tf_step_plan<T>(e) == FLOPE_TF_STEP_SPLIT ? FLOPE_TF_EXTEND_SPLIT : FLOPE_TF_EXTEND_ROW;
 }
 
@@ -2728,7 +2614,7 @@ int launch_extend_attn(flope_tf_stream_s* s, int plan, const T* qkv, const T* ca
   flope_tf_encoder* e = s->e;
   if (plan == FLOPE_TF_EXTEND_MFMA) {
     if constexpr (!std::is_same<T, float>::value) {
-      const int dh = e->d / e->H;
+      const int dh = tf_head_dim(e);
       const flope_tf_plan::TfExtendLaunch lm = flope_tf_plan::tf_extend_mfma_launch(n, e->H, max_len, dh);
       const float scale_log2e = 1.4426950408889634f / sqrtf((float)dh);
 #define TF_EXTM(HD32_, WIN_) hipLaunchKernelGGL((tf_attn16_extend<T, HD32_, WIN_>), dim3(lm.grid_x, lm.grid_y), dim3(lm.block), lm.lds, st, qkv, cache, att, \
@@ -2744,13 +2630,13 @@ int launch_extend_attn(flope_tf_stream_s* s, int plan, const T* qkv, const T* ca
     return plan;
   }
   const flope_tf_plan::TfExtendLaunch la = flope_tf_plan::tf_extend_launch(n, e->H, max_len, smax);
-  const flope_tf_plan::TfExtendLaunch ls = flope_tf_plan::tf_extend_split_launch(n, e->H, max_len, e->d / e->H);
+  const flope_tf_plan::TfExtendLaunch ls = flope_tf_plan::tf_extend_split_launch(n, e->H, max_len, tf_head_dim(e));
 #define TF_EXT(VEC_, WIN_) hipLaunchKernelGGL((tf_attn_extend<T, VEC_, WIN_>), dim3(la.grid_x, la.grid_y), dim3(la.block), la.lds, st, qkv, cache, \
                                              att, (const int*)s->tab, (const int*)e->vl_off, n, e->d, e->H, s->tracks, s->capacity, smax, s->window)
 #define TF_EXTS(WIN_) hipLaunchKernelGGL((tf_attn_extend_split<T, WIN_>), dim3(ls.grid_x, ls.grid_y), dim3(ls.block), ls.lds, st, qkv, cache, \
                                         att, (const int*)s->tab, (const int*)e->vl_off, n, e->d, e->H, s->tracks, s->capacity, s->window)
   if (plan == FLOPE_TF_EXTEND_SPLIT) { if (s->window) TF_EXTS(true); else TF_EXTS(false); }   // option step_split: tf_attn_extend_split, the bits of the split steps
-  else if (flope_tf_plan::tf_step_vec_ok(e->d / e->H, (int)sizeof(T))) { if (s->window) TF_EXT(true, true); else TF_EXT(true, false); }
+  else if (tf_row_vec<T>(e)) { if (s->window) TF_EXT(true, true); else TF_EXT(true, false); }
   else { if (s->window) TF_EXT(false, true); else TF_EXT(false, false); }
 #undef TF_EXTS
 #undef TF_EXT
@@ -2770,21 +2656,11 @@ int run_extend(flope_tf_stream_s* s, const float* x, int n, int L, const TfRagge
   flope_tf_encoder* e = s->e;
   const size_t layer = (size_t)s->tracks * s->capacity * 2 * e->d;
   const int plan = tf_extend_plan<T>(e, tf_extend_positions_ok(s, n, lengths));
-  const bool vec = flope_tf_plan::tf_cache_fill_vec_ok(e->d, (int)sizeof(T));
-  const int dv = vec ? e->d / flope_tf_plan::tf_stream_vec((int)sizeof(T)) : e->d;
-  const flope_tf_plan::TfStreamLaunch lc = flope_tf_plan::tf_cache_append_launch(n, rg.max_len, 2 * dv);
-  const size_t total = (size_t)n * rg.max_len * 2 * dv;
   return run_forward_with<T>(e, x, n, L, y, st, &rg, [&](int li) {
     T* cache = (T*)s->cache + (size_t)li * layer;
     const int rc = launch_extend_attn<T>(s, plan, (const T*)e->qkv, (const T*)cache, (T*)e->att, n, rg.max_len, smax, st);
     if (rc < 0) return rc;
-#define TF_APP(V_, WIN_) hipLaunchKernelGGL((tf_cache_append<V_, WIN_>), dim3(lc.grid_x), dim3(lc.block), 0, st, (const V_*)e->qkv, (V_*)cache, (const int*)e->vl_off, \
-                                           (const int*)s->tab, rg.max_len, dv, s->tracks, s->capacity, total)
-    if (vec) { if (s->window) TF_APP(u32x4, true); else TF_APP(u32x4, false); }
-    else { if (s->window) TF_APP(T, true); else TF_APP(T, false); }
-#undef TF_APP
-    TF_HIP(e, hipGetLastError());
-    return 0;
+    return launch_cache_copy<T>(s, (const T*)e->qkv, cache, (const int*)e->vl_off, (const int*)s->tab, n, rg.max_len, st);
   });
 }
 
@@ -2807,14 +2683,14 @@ int tf_stream_open(flope_tf_handle e, const std::string& who, int tracks, int ca
   flope_tf_stream_s* s = new flope_tf_stream_s();
   s->e = e; s->tracks = tracks; s->capacity = capacity; s->window = window;
   // num_layers = 0 has no cache; the allocation keeps one row so that the pointer is a pointer
-  if (hipMalloc(&s->cache, bytes ? bytes : 16) != hipSuccess || hipMalloc((void**)&s->tab, (size_t)4 * tracks * sizeof(int)) != hipSuccess) {
+  if (hipMalloc(&s->cache, bytes ? bytes : 16) != hipSuccess || hipMalloc((void**)&s->tab, (size_t)5 * tracks * sizeof(int)) != hipSuccess) {
     (void)hipGetLastError();
     hipFree(s->cache); hipFree(s->tab);
     delete s;
     return tf_fail(e, FLOPE_EHIP, who + ": hipMalloc failed for a cache of " + std::to_string(bytes) + " bytes (num_layers x tracks x capacity x 2 model_dim)");
   }
   s->pos.assign((size_t)tracks, 0);
-  s->tab_host.assign((size_t)4 * tracks, 0);
+  s->tab_host.assign((size_t)5 * tracks, 0);
   s->seen.assign((size_t)tracks, 0);
   e->streams.push_back(s);
   *out = s;
@@ -2905,8 +2781,8 @@ extern "C" int flope_tf_stream_prefill(flope_tf_stream s, const float* x_dev, in
   TF_HIP(e, hipSetDevice(e->device));
   hipStream_t st = (hipStream_t)stream;
   if ((rc = tf_upload_ragged(e, n, st))) return rc;
-  for (int b = 0; b < n; ++b) s->tab_host[(size_t)b] = tf_stream_track(tracks_host, b);
-  TF_HIP(e, hipMemcpyAsync(s->tab, s->tab_host.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice, st));
+  for (int b = 0; b < n; ++b) { s->tab_host[(size_t)2 * b] = tf_stream_track(tracks_host, b); s->tab_host[(size_t)2 * b + 1] = 0; }   // every sequence starts its track
+  TF_HIP(e, hipMemcpyAsync(s->tab, s->tab_host.data(), (size_t)2 * n * sizeof(int), hipMemcpyHostToDevice, st));
   flope_tf_plan::tf_stream_set_lengths(s->pos.data(), n, seq_len, lengths, tracks_host);
   const int causal = e->opt_causal, window = e->opt_window;       // causal and the state's window for these launches only; last_fwd is tf_forward's and stays
   e->opt_causal = 1;
@@ -2946,7 +2822,7 @@ extern "C" int flope_tf_stream_extend(flope_tf_stream s, const float* x_dev, int
   TF_HIP(e, hipSetDevice(e->device));
   hipStream_t st = (hipStream_t)stream;
   if ((rc = tf_upload_ragged(e, n, st))) return rc;
-  flope_tf_plan::tf_stream_extend_table(s->pos.data(), n, tracks_host, s->tab_host.data());
+  flope_tf_plan::tf_stream_step_table(s->pos.data(), n, tracks_host, s->tab_host.data());
   TF_HIP(e, hipMemcpyAsync(s->tab, s->tab_host.data(), (size_t)2 * n * sizeof(int), hipMemcpyHostToDevice, st));
   // the positions move only once every launch is enqueued: a call that fails on the way (FLOPE_EHIP) leaves the tracks where they were.
   // On a linear state the rows it may have written lie behind the positions, where nothing reads them; on a ring they may have taken
@@ -2964,28 +2840,45 @@ extern "C" int flope_tf_stream_step_plan(flope_tf_stream s) {
 }
 
 namespace {
-// flope_tf_stream_attention behind its checks: per sequence the k | v columns of rows 0 .. len - 2 into layer 0's part of track b
-// (tf_cache_fill, one launch per sequence: the batch is padded, not packed), row len - 1 into the handle's qkv buffer, then the step's
-// attention launch.  Table (s->tab, 4 n ints): (track b, position len - 1) per row, then (0, len - 1) per sequence, the offsets of its fill
+// What the two test hooks (flope_tf_stream_attention, flope_tf_stream_attention_extend) share.  Sequence b of their padded batch
+// [n][seq_len] is for track b: its first `hist` rows are the track's history, the `own` rows behind them the step's token or the
+// extend's chunk.  The table (s->tab, 5 n ints): (b, hist) per sequence -- the table of the attention launch -- then (b, 0, hist) per
+// sequence: (b, 0) is the one-entry table of that sequence's cache copy and (0, hist) its offsets.
+void tf_hook_table_entry(flope_tf_stream_s* s, int n, int b, int hist) {
+  int* t = s->tab_host.data();
+  t[2 * b] = b; t[2 * b + 1] = hist;
+  t[2 * n + 3 * b] = b; t[2 * n + 3 * b + 1] = 0; t[2 * n + 3 * b + 2] = hist;
+  s->pos[(size_t)b] = 0;                               // a test hook: the rows it loads are no history of the track
+}
+// ... and the staging of sequence b (seq: its first row): the k | v columns of the history into layer 0's part of track b
+// (tf_cache_append, one launch per sequence: the batch is padded, not packed), the own rows into the handle's qkv buffer from row dst on
+template <typename T>
+int tf_hook_stage(flope_tf_stream_s* s, const T* seq, int n, int b, int hist, int own, int dst, hipStream_t st) {
+  flope_tf_encoder* e = s->e;
+  const size_t row = (size_t)3 * e->d;
+  TF_HIP(e, hipMemcpyAsync((T*)e->qkv + (size_t)dst * row, seq + (size_t)hist * row, (size_t)own * row * sizeof(T), hipMemcpyDeviceToDevice, st));
+  if (hist < 1) return 0;
+  const int* tab = (const int*)s->tab + 2 * n + 3 * b;
+  return launch_cache_copy<T>(s, seq, (T*)s->cache, tab + 1, tab, 1, hist, st);
+}
+// ... and the refusals both make in the same words
+int tf_hook_refuse(flope_tf_stream_s* s, const std::string& who, int rc, int bad, int n, int seq_len, const int* lengths, const char* or_else) {
+  flope_tf_encoder* e = s->e;
+  if (rc == flope_tf_plan::kTfStreamLength)
+    return tf_fail(e, FLOPE_EINVAL, who + ": lengths[" + std::to_string(bad) + "] = " + std::to_string(lengths ? lengths[bad] : seq_len) + " is outside 1 .. seq_len = " +
+                                        std::to_string(seq_len) + (s->window ? "" : ", or above capacity = " + std::to_string(s->capacity)));
+  return tf_fail(e, FLOPE_EINVAL, who + ": n = " + std::to_string(n) + " is outside 1 .. min(tracks = " + std::to_string(s->tracks) + ", max_tokens = " +
+                                      std::to_string(e->max_tokens) + ")" + or_else);
+}
+
+// flope_tf_stream_attention behind its checks: per sequence rows 0 .. len - 2 are the history and row len - 1 the token (row b of the
+// handle's qkv buffer), then the step's attention launch
 template <typename T>
 int run_stream_attention(flope_tf_stream_s* s, const T* qkv, int n, int L, const int* lengths, T* att, int max_pos, hipStream_t st) {
   flope_tf_encoder* e = s->e;
-  const bool vec = flope_tf_plan::tf_cache_fill_vec_ok(e->d, (int)sizeof(T));
-  const int dv = vec ? e->d / flope_tf_plan::tf_stream_vec((int)sizeof(T)) : e->d;
-  const int* tab = (const int*)s->tab;
   for (int b = 0; b < n; ++b) {
-    const int len = lengths ? lengths[b] : L;
-    const T* seq = qkv + (size_t)b * L * 3 * e->d;
-    TF_HIP(e, hipMemcpyAsync((T*)e->qkv + (size_t)b * 3 * e->d, seq + (size_t)(len - 1) * 3 * e->d, (size_t)3 * e->d * sizeof(T), hipMemcpyDeviceToDevice, st));
-    if (len < 2) continue;
-    const flope_tf_plan::TfStreamLaunch l = flope_tf_plan::tf_cache_fill_launch(1, len - 1, 2 * dv);
-    const size_t total = (size_t)(len - 1) * 2 * dv;
-#define TF_FILL(V_, WIN_) hipLaunchKernelGGL((tf_cache_fill<V_, WIN_>), dim3(l.grid_x), dim3(l.block), 0, st, (const V_*)seq, (V_*)s->cache, tab + 2 * n + 2 * b, \
-                                            tab + 2 * b, len - 1, dv, s->tracks, s->capacity, total)
-    if (vec) { if (s->window) TF_FILL(u32x4, true); else TF_FILL(u32x4, false); }
-    else { if (s->window) TF_FILL(T, true); else TF_FILL(T, false); }
-#undef TF_FILL
-    TF_HIP(e, hipGetLastError());
+    const int rc = tf_hook_stage<T>(s, qkv + (size_t)b * L * 3 * e->d, n, b, (lengths ? lengths[b] : L) - 1, 1, b, st);
+    if (rc) return rc;
   }
   return launch_step_attn<T>(s, (const T*)e->qkv, (T*)s->cache, att, n, max_pos, st);
 }
@@ -2997,26 +2890,14 @@ extern "C" int flope_tf_stream_attention(flope_tf_stream s, const void* qkv_dev,
   int rc, bad = -1, max_pos = 0;
   if ((rc = tf_stream_enter(s, who, &e))) return rc;
   if (e->nl < 1) return tf_fail(e, FLOPE_EINVAL, who + ": an encoder without layers has no cache");
-  if ((rc = flope_tf_plan::tf_stream_check_attention(s->tracks, s->capacity, s->window, e->max_tokens, n, seq_len, lengths_host, &bad, &max_pos))) {
-    if (rc == flope_tf_plan::kTfStreamLength)
-      return tf_fail(e, FLOPE_EINVAL, who + ": lengths[" + std::to_string(bad) + "] = " + std::to_string(lengths_host ? lengths_host[bad] : seq_len) + " is outside 1 .. seq_len = " +
-                                          std::to_string(seq_len) + (s->window ? "" : ", or above capacity = " + std::to_string(s->capacity)));
-    return tf_fail(e, FLOPE_EINVAL, who + ": n = " + std::to_string(n) + " is outside 1 .. min(tracks = " + std::to_string(s->tracks) + ", max_tokens = " +
-                                        std::to_string(e->max_tokens) + "), or seq_len < 1");
-  }
+  if ((rc = flope_tf_plan::tf_stream_check_attention(s->tracks, s->capacity, s->window, e->max_tokens, n, seq_len, lengths_host, &bad, &max_pos)))
+    return tf_hook_refuse(s, who, rc, bad, n, seq_len, lengths_host, ", or seq_len < 1");
   if (!qkv_dev || !att_dev) return tf_fail(e, FLOPE_EINVAL, who + ": NULL buffer");
   if (((uintptr_t)qkv_dev | (uintptr_t)att_dev) & 15) return tf_fail(e, FLOPE_EINVAL, who + ": buffer not aligned to 16 bytes");
   TF_HIP(e, hipSetDevice(e->device));
   hipStream_t st = (hipStream_t)stream;
-  for (int b = 0; b < n; ++b) {
-    const int len = lengths_host ? lengths_host[b] : seq_len;
-    s->tab_host[(size_t)2 * b] = b;
-    s->tab_host[(size_t)2 * b + 1] = len - 1;
-    s->tab_host[(size_t)2 * n + 2 * b] = 0;
-    s->tab_host[(size_t)2 * n + 2 * b + 1] = len - 1;
-    s->pos[(size_t)b] = 0;                             // a test hook: the rows it loads are no history of the track
-  }
-  TF_HIP(e, hipMemcpyAsync(s->tab, s->tab_host.data(), (size_t)4 * n * sizeof(int), hipMemcpyHostToDevice, st));
+  for (int b = 0; b < n; ++b) tf_hook_table_entry(s, n, b, (lengths_host ? lengths_host[b] : seq_len) - 1);
+  TF_HIP(e, hipMemcpyAsync(s->tab, s->tab_host.data(), (size_t)5 * n * sizeof(int), hipMemcpyHostToDevice, st));
   return tf_by_dtype(e, [&](auto tag) {
     using T = typename decltype(tag)::type;
     return run_stream_attention<T>(s, (const T*)qkv_dev, n, seq_len, lengths_host, (T*)att_dev, max_pos, st);
@@ -3031,31 +2912,17 @@ extern "C" int flope_tf_stream_extend_plan(flope_tf_stream s) {
 }
 
 namespace {
-// flope_tf_stream_attention_extend behind its checks: per sequence the k | v columns of rows 0 .. cached - 1 into layer 0's part of
-// track b (tf_cache_fill, one launch per sequence: the batch is padded), rows cached .. len - 1 packed into the handle's qkv buffer,
-// the extend's attention launch over them, and the packed rows of the handle's att buffer back to their places in att.
-// Table (s->tab, 4 n ints): (track b, cached) per sequence, then (0, cached) per sequence, the offsets of its fill
+// flope_tf_stream_attention_extend behind its checks: per sequence rows 0 .. cached - 1 are the history and rows cached .. len - 1 the
+// chunk, packed into the handle's qkv buffer; the extend's attention launch over them, and the packed rows of the handle's att buffer
+// back to their places in att
 template <typename T>
 int run_stream_attention_extend(flope_tf_stream_s* s, const T* qkv, int n, int L, const int* lengths, const int* cached, T* att, int smax, int max_len,
                                 hipStream_t st) {
   flope_tf_encoder* e = s->e;
   const int d = e->d;
-  const bool vec = flope_tf_plan::tf_cache_fill_vec_ok(d, (int)sizeof(T));
-  const int dv = vec ? d / flope_tf_plan::tf_stream_vec((int)sizeof(T)) : d;
-  const int* tab = (const int*)s->tab;
   for (int b = 0; b < n; ++b) {
-    const T* seq = qkv + (size_t)b * L * 3 * d;
-    const int nc = cached[b], len = lengths[b] - nc;
-    TF_HIP(e, hipMemcpyAsync((T*)e->qkv + (size_t)e->vl_host[(size_t)b] * 3 * d, seq + (size_t)nc * 3 * d, (size_t)len * 3 * d * sizeof(T), hipMemcpyDeviceToDevice, st));
-    if (nc < 1) continue;
-    const flope_tf_plan::TfStreamLaunch l = flope_tf_plan::tf_cache_fill_launch(1, nc, 2 * dv);
-    const size_t total = (size_t)nc * 2 * dv;
-#define TF_FILL(V_, WIN_) hipLaunchKernelGGL((tf_cache_fill<V_, WIN_>), dim3(l.grid_x), dim3(l.block), 0, st, (const V_*)seq, (V_*)s->cache, tab + 2 * n + 2 * b, \
-                                            tab + 2 * b, nc, dv, s->tracks, s->capacity, total)
-    if (vec) { if (s->window) TF_FILL(u32x4, true); else TF_FILL(u32x4, false); }
-    else { if (s->window) TF_FILL(T, true); else TF_FILL(T, false); }
-#undef TF_FILL
-    TF_HIP(e, hipGetLastError());
+    const int rc = tf_hook_stage<T>(s, qkv + (size_t)b * L * 3 * d, n, b, cached[b], lengths[b] - cached[b], e->vl_host[(size_t)b], st);
+    if (rc) return rc;
   }
   std::vector<int> chunk((size_t)n);
   for (int b = 0; b < n; ++b) chunk[(size_t)b] = lengths[b] - cached[b];
@@ -3078,15 +2945,11 @@ extern "C" int flope_tf_stream_attention_extend(flope_tf_stream s, const void* q
   if ((rc = tf_stream_enter(s, who, &e))) return rc;
   if (e->nl < 1) return tf_fail(e, FLOPE_EINVAL, who + ": an encoder without layers has no cache");
   if ((rc = tf_stream_check_attention_extend(s->tracks, s->capacity, s->window, e->max_tokens, n, seq_len, lengths_host, cached_host, &bad, &smax, &max_len, &total))) {
-    if (rc == kTfStreamLength)
-      return tf_fail(e, FLOPE_EINVAL, who + ": lengths[" + std::to_string(bad) + "] = " + std::to_string(lengths_host[bad]) + " is outside 1 .. seq_len = " +
-                                          std::to_string(seq_len) + (s->window ? "" : ", or above capacity = " + std::to_string(s->capacity)));
     if (rc == kTfStreamCached)
       return tf_fail(e, FLOPE_EINVAL, who + ": cached[" + std::to_string(bad) + "] = " + std::to_string(cached_host[bad]) + " is outside 0 .. lengths[" + std::to_string(bad) +
                                           "] - 1 = " + std::to_string(lengths_host[bad] - 1));
     if (rc == kTfStreamTokens) return tf_fail(e, FLOPE_EINVAL, who + ": the chunks together exceed max_tokens given to flope_tf_create");
-    return tf_fail(e, FLOPE_EINVAL, who + ": n = " + std::to_string(n) + " is outside 1 .. min(tracks = " + std::to_string(s->tracks) + ", max_tokens = " +
-                                        std::to_string(e->max_tokens) + "), seq_len < 1, or lengths_host / cached_host is NULL");
+    return tf_hook_refuse(s, who, rc, bad, n, seq_len, lengths_host, ", seq_len < 1, or lengths_host / cached_host is NULL");
   }
   if (!qkv_dev || !att_dev) return tf_fail(e, FLOPE_EINVAL, who + ": NULL buffer");
   if (((uintptr_t)qkv_dev | (uintptr_t)att_dev) & 15) return tf_fail(e, FLOPE_EINVAL, who + ": buffer not aligned to 16 bytes");
@@ -3096,15 +2959,11 @@ extern "C" int flope_tf_stream_attention_extend(flope_tf_stream s, const void* q
   for (int b = 0; b < n; ++b) {
     e->vl_host[(size_t)b] = run;
     run += lengths_host[b] - cached_host[b];
-    s->tab_host[(size_t)2 * b] = b;
-    s->tab_host[(size_t)2 * b + 1] = cached_host[b];
-    s->tab_host[(size_t)2 * n + 2 * b] = 0;
-    s->tab_host[(size_t)2 * n + 2 * b + 1] = cached_host[b];
-    s->pos[(size_t)b] = 0;                             // a test hook: the rows it loads are no history of the track
+    tf_hook_table_entry(s, n, b, cached_host[b]);
   }
   e->vl_host[(size_t)n] = run;
   if ((rc = tf_upload_ragged(e, n, st))) return rc;
-  TF_HIP(e, hipMemcpyAsync(s->tab, s->tab_host.data(), (size_t)4 * n * sizeof(int), hipMemcpyHostToDevice, st));
+  TF_HIP(e, hipMemcpyAsync(s->tab, s->tab_host.data(), (size_t)5 * n * sizeof(int), hipMemcpyHostToDevice, st));
   return tf_by_dtype(e, [&](auto tag) {
     using T = typename decltype(tag)::type;
     return run_stream_attention_extend<T>(s, (const T*)qkv_dev, n, seq_len, lengths_host, cached_host, (T*)att_dev, smax, max_len, st);

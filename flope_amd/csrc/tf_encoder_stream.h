@@ -1,11 +1,14 @@
 // The streaming causal forward of the encoder (flope_tf_stream_*) as far as it is plain integer arithmetic, no HIP:
 // the argument checks of step / prefill / reset over host arrays, the capacity limit, and grid, block and LDS of tf_attn_step and
-// tf_cache_fill.  Shared by tf_encoder.hip and tests/host_harness/harness_tf_stream.cpp (tests/test_tf_stream_host.py holds it
+// of the one cache copy, tf_cache_append.  Shared by tf_encoder.hip and tests/host_harness/harness_tf_stream.cpp (tests/test_tf_stream_host.py holds it
 // against brute force on the CPU, tests/test_gpu_tf_stream.py the device against it).
 // Below them, the same for a windowed state (flope_tf_stream_open_window): a ring cache, absolute positions, keys
 // tf_window_lo(p, W) .. p -- new functions beside the old ones (tests/host_harness/harness_tf_window.cpp, tests/test_tf_window_host.py).
 // Below those, flope_tf_stream_extend: its checks, table, smax and advance for both kinds of state, the launches of
-// tf_attn_extend and tf_cache_append, where a chunk query's keys lie and which rows the append writes
+// tf_attn_extend, where a chunk query's keys lie and which rows tf_cache_append writes and where -- the prefill's copy is the append
+// at pos0 = 0, and a step's table is an extend's: where two names below mean one function (tf_cache_fill_launch and
+// tf_cache_append_launch, tf_stream_fill_writes and tf_stream_append_writes, tf_stream_step_table and tf_stream_extend_table), both
+// stay because the host harnesses of the stream, window and extend planners are built against them by name
 // (tests/host_harness/harness_tf_extend.cpp, tests/test_tf_extend_host.py).
 // Below those, option step_split: the partition of a token's visible keys over the waves, blocks and lanes of a workgroup,
 // the LDS and launches of tf_attn_step_split / tf_attn_extend_split, the eligibility rule, and the checks of flope_tf_stream_attention
@@ -40,14 +43,14 @@ struct TfStreamLaunch { unsigned grid_x, block; size_t lds; };
 inline TfStreamLaunch tf_step_launch(int n, int H, int max_pos) {
   return {(unsigned)(((long long)n * H + kTfStepWaves - 1) / kTfStepWaves), 64u * kTfStepWaves, tf_step_lds(max_pos)};
 }
-// tf_cache_fill: one thread per unit (a 16-byte vector or one element) of the k | v columns of the n x max_len rows a ragged batch may
-// hold; units: those of the 2 model_dim columns of a cache row
+// tf_cache_append (the prefill's copy and the extend's append): one thread per unit (a 16-byte vector or one element) of the k | v
+// columns of the n x max_len rows a ragged batch may hold; units: those of the 2 model_dim columns of a cache row
 inline TfStreamLaunch tf_cache_fill_launch(int n, int max_len, int units) {
   const size_t total = (size_t)n * max_len * units;
   return {(unsigned)((total + 255) / 256), 256u, 0};
 }
 // elements per 16-byte vector of a cache of esz-byte elements, and whether a head slice (tf_attn_step) or the k | v columns
-// (tf_cache_fill) of a row move as whole vectors: the cache and the handle's qkv buffer are 16-byte aligned, rows are 2 and 3
+// (tf_cache_append) of a row move as whole vectors: the cache and the handle's qkv buffer are 16-byte aligned, rows are 2 and 3
 // model_dim elements, so what has to divide is the first column of the slice and its width
 constexpr int tf_stream_vec(int esz) { return 16 / esz; }
 constexpr bool tf_step_vec_ok(int head_dim, int esz) { return head_dim % tf_stream_vec(esz) == 0; }
@@ -98,7 +101,7 @@ inline int tf_stream_check_step(const int* pos, int tracks, int capacity, int ma
   *max_pos = mx;
   return kTfStreamOk;
 }
-// ... its device table, (track, position) per row, and the positions behind it
+// ... its device table, (track, position) per row -- an extend's too, (track, pos0) per sequence -- and the positions behind it
 inline void tf_stream_step_table(const int* pos, int n, const int* rows, int* tab) {
   for (int r = 0; r < n; ++r) { tab[2 * r] = tf_stream_track(rows, r); tab[2 * r + 1] = pos[tf_stream_track(rows, r)]; }
 }
@@ -135,7 +138,7 @@ inline int tf_stream_check_reset(int tracks, int n, const int* rows, int* bad) {
 constexpr int tf_stream_slot(int p, int capacity) { return p % capacity; }
 
 // The pos - lo cached keys of a step are nk consecutive ring rows from slo = lo % capacity on; they wrap at most once (nk < W <=
-// capacity), so tf_attn_step_row's value pass walks two contiguous runs: tf_stream_run0 rows from slo, the rest from row 0
+// capacity), so tf_attn_stream_row's value pass walks two contiguous runs: tf_stream_run0 rows from slo, the rest from row 0
 constexpr int tf_stream_run0(int slo, int nk, int capacity) { return nk < capacity - slo ? nk : capacity - slo; }
 
 inline int tf_stream_check_open_window(int tracks, int capacity, int window) {
@@ -164,8 +167,8 @@ inline int tf_stream_check_step_window(const int* pos, int tracks, int window, i
 inline int tf_stream_check_prefill_window(int tracks, int n, const int* rows, char* seen, int* bad) {
   return tf_stream_check_rows(tracks, tracks, n, rows, seen, bad);
 }
-// ... and which tokens tf_cache_fill writes: token i of len goes to row i % capacity only if no later token of the sequence takes
-// that row, so every row is written at most once
+// ... and which tokens tf_cache_append writes into a ring (tf_stream_append_writes below is this function): token i of len only if no later token of the sequence takes its row -- the
+// last min(len, capacity) -- so every row is written at most once (where they go: tf_stream_append_slot below)
 constexpr bool tf_stream_fill_writes(int i, int len, int capacity) { return i >= 0 && i < len && i >= len - capacity; }
 
 // ---- extend: several tokens per track in one call, behind what the track holds ----------------------------------------
@@ -186,17 +189,15 @@ inline TfExtendLaunch tf_extend_launch(int n, int H, int max_len, int smax) {
   const int gy = (max_len + kTfStepWaves - 1) / kTfStepWaves;
   return {(unsigned)n * (unsigned)H, (unsigned)(gy < kTfExtendGridY ? gy : kTfExtendGridY), 64u * kTfStepWaves, tf_step_lds(smax - 1)};
 }
-// tf_cache_append: tf_cache_fill's geometry, one thread per unit of the k | v columns of the n x max_len rows the chunks may hold
+// The append: the prefill's copy by its other name, and the same tokens
 inline TfStreamLaunch tf_cache_append_launch(int n, int max_len, int units) { return tf_cache_fill_launch(n, max_len, units); }
-
-// Which chunk tokens the append writes, and where: tf_stream_fill_writes with a start position.  Token i of a chunk of len tokens at
-// pos0 goes to row (pos0 + i) % capacity only if no later token of the chunk takes that row -- the last min(len, capacity) tokens --
-// so every row is written at most once; pos0 = 0 is the prefill's rule.  A linear state writes every token, to row pos0 + i (the check
-// below keeps that below capacity, where the two rules are one).
+constexpr bool tf_stream_append_writes(int i, int len, int capacity) { return tf_stream_fill_writes(i, len, capacity); }
+// Where the tokens tf_stream_append_writes names go: token i of a chunk at pos0 to row
+// (pos0 + i) % capacity; pos0 = 0 is the prefill.  A linear state writes every token, to row pos0 + i (the check below keeps that
+// below capacity, where the two rules are one).
 // THE APPEND RUNS BEHIND THE LAYER'S ATTENTION, never in front of it as the prefill's fill does: on a ring the chunk's token at p takes
 // the row of key p - capacity, and query q < p of the same chunk still sees that key when p - capacity >= tf_window_lo(q, W) -- with
 // q = pos0 and p = pos0 + len - 1 that is len >= capacity - W + 2, every chunk of two tokens at capacity == W.
-constexpr bool tf_stream_append_writes(int i, int len, int capacity) { return tf_stream_fill_writes(i, len, capacity); }
 constexpr int tf_stream_append_slot(int pos0, int i, int capacity) { return tf_stream_slot(pos0 + i, capacity); }
 
 enum {
@@ -222,7 +223,7 @@ inline int tf_stream_check_extend(const int* pos, int tracks, int capacity, int 
   *smax = mx;
   return kTfStreamOk;
 }
-// ... its device table, (track, pos0) per sequence, and the positions behind it
+// ... its device table is tf_stream_step_table's, (track, pos0) per sequence; the positions behind it
 inline void tf_stream_extend_table(const int* pos, int n, const int* rows, int* tab) { tf_stream_step_table(pos, n, rows, tab); }
 inline void tf_stream_extend_advance(int* pos, int n, const int* lengths, const int* rows) {
   for (int b = 0; b < n; ++b) pos[tf_stream_track(rows, b)] += lengths[b];

@@ -530,7 +530,7 @@ double flope_tf_forward_flops_varlen(flope_tf_handle h, int batch, const int* le
  *             [n, seq_len, 3 model_dim] and att_dev [n, model_dim] in the handle's dtype (float for FLOPE_DT_F32), both 16-byte
  *             aligned.  For sequence b of length len = lengths_host[b] (NULL: seq_len), row b of att_dev is what _step's attention
  *             launch writes for a token whose q | k | v is row len - 1, on a track that holds the k | v columns of rows 0 .. len - 2:
- *             those are loaded with tf_cache_fill into layer 0's part of tracks 0 .. n - 1 (a windowed state: the ring keeps the last
+ *             those are loaded with tf_cache_append into layer 0's part of tracks 0 .. n - 1 (a windowed state: the ring keeps the last
  *             `capacity` of them), then the kernel _step would run runs: the handle's option, the state's window.  Returns its
  *             FLOPE_TF_STEP_* id or < 0.  It OVERWRITES those cache rows and leaves tracks 0 .. n - 1 at position 0; needs no weights.
  *             Refused with FLOPE_EINVAL, nothing enqueued: n outside 1 .. min(tracks, max_tokens), a length outside 1 .. seq_len, on
@@ -542,7 +542,7 @@ double flope_tf_forward_flops_varlen(flope_tf_handle h, int batch, const int* le
  *   _attention_extend: A TEST HOOK, as _attention is: the extend's attention launch alone on a caller's tensor.  qkv_dev [n, seq_len,
  *             3 model_dim] and att_dev [n, seq_len, model_dim] in the handle's dtype, both 16-byte aligned; lengths_host and
  *             cached_host: n ints each.  Of sequence b, rows 0 .. cached[b] - 1 are a track's history: their k | v columns are loaded
- *             with tf_cache_fill into layer 0's part of track b (a windowed state: the ring keeps the last `capacity` of them); rows
+ *             with tf_cache_append into layer 0's part of track b (a windowed state: the ring keeps the last `capacity` of them); rows
  *             cached[b] .. lengths[b] - 1 are the chunk, packed into the handle's buffers.  Then the kernel _extend would run now
  *             runs once over all n chunks (the handle's options, the state's window) and rows cached[b] .. lengths[b] - 1 of att_dev
  *             are written; every other row of att_dev is left untouched.  Returns the FLOPE_TF_EXTEND_* id or < 0.  It OVERWRITES

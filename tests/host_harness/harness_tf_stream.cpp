@@ -1,5 +1,5 @@
 // CPU-only test harness of the streaming forward's planner (flope_amd/csrc/tf_encoder_stream.h): the argument checks of
-// flope_tf_stream_step / _prefill / _reset over host arrays, the capacity limit and the launches of tf_attn_step and tf_cache_fill.
+// flope_tf_stream_step / _prefill / _reset over host arrays, the capacity limit and the launches of tf_attn_step and tf_cache_append.
 // tests/test_tf_stream_host.py holds them against brute force without a GPU and runs tfs_selfcheck once in a stand-alone program
 // built with -DTF_STREAM_MAIN under AddressSanitizer + UBSan.  Not part of the product.
 #include "tf_encoder_stream.h"

@@ -1,5 +1,5 @@
 // CPU-only test harness of sliding-window causal attention and the ring cache of a windowed stream state: the first
-// visible key (flope_amd/csrc/tf_attn_plan.h: tf_window_lo, which tf_attn_row and tf_attn_step_row call) and the host rules of
+// visible key (flope_amd/csrc/tf_attn_plan.h: tf_window_lo, which tf_attn_row and tf_attn_stream_row call) and the host rules of
 // flope_amd/csrc/tf_encoder_stream.h -- the open check, the windowed step and prefill checks, the slot of a position, the two row runs
 // a step's value pass walks, and which tokens a fill writes.  tests/test_tf_window_host.py holds them against brute force without a
 // GPU and runs tfw_selfcheck once in a stand-alone program built with -DTF_WINDOW_MAIN under AddressSanitizer + UBSan.  Not part of
@@ -30,7 +30,7 @@ int tfw_check_reset(int tracks, int n, const int* rows, int* bad) {
 void tfw_lo_table(int L, int W, int* lo, int* keys) {
   for (int i = 0; i < L; ++i) { lo[i] = flope_tf_plan::tf_window_lo(i, W); keys[i] = flope_tf_plan::tf_window_keys(i, W); }
 }
-// row[i]: the ring row tf_cache_fill writes token i of a sequence of len tokens to, -1 where it writes none
+// row[i]: the ring row tf_cache_append writes token i of a sequence of len tokens to, -1 where it writes none
 void tfw_fill_table(int len, int capacity, int* row) {
   for (int i = 0; i < len; ++i) row[i] = flope_tf_plan::tf_stream_fill_writes(i, len, capacity) ? flope_tf_plan::tf_stream_slot(i, capacity) : -1;
 }
@@ -58,7 +58,7 @@ int tfw_prefill(int* pos, int tracks, int n, int seq_len, const int* lengths, co
   return rc;
 }
 
-// The cache rows the step at position p reads, in the order tf_attn_step_row's value pass walks them (two runs), without the token's
+// The cache rows the step at position p reads, in the order tf_attn_stream_row's value pass walks them (two runs), without the token's
 // own: out gets tf_window_keys(p, W) - 1 rows; returns that count.  Every index is formed as the kernel forms it.
 int tfw_step_rows(int p, int W, int capacity, int* out) {
   using namespace flope_tf_plan;

@@ -12,6 +12,8 @@ last_attn_kernel, not guessed) those are rows pos .. pos + len - 1 of enc(track,
   3. a mixed call                                  8. refusals (the INT_MAX refusal of a ring needs 2^31 tokens: tests/test_tf_extend_host.py)
   4. long: three trips of the key loop             9. sentinels around y, the rows behind a length
   5. windowed states, the ring wraps in a chunk   10. nothing else of the handle moves
+ 11. an extend of ONE token == a step at the same position: both are tf_attn_stream_row, the step with the promise that the chunk is
+     one row
 """
 import ctypes as C
 import os
@@ -33,6 +35,7 @@ TOY = (16, 32, 9, 4, 2, 64)
 WIDE = (16, 128, 9, 2, 2, 256)
 ODD = (5, 30, 3, 5, 1, 20)           # head_dim 6: element-wise loads in float32 and in 16 bits, and in tf_cache_append
 MID = (5, 24, 3, 2, 1, 20)           # head_dim 12: three 16-byte vectors in float32, element-wise in 16 bits
+HD16 = (5, 32, 3, 2, 1, 20)          # head_dim 16: whole 16-byte vectors in all three dtypes
 MODES = [("f32", 0, 2e-4), ("f32m", 0, 2e-4), ("f16", 0, 1.5e-2), ("f16", 1, 1.5e-2), ("bf16", 0, 1.2e-1), ("bf16", 1, 1.2e-1)]
 
 
@@ -475,3 +478,52 @@ def test_two_states_extended_alternately(shapes):
     for s in (sa, sb, s1, s2):
         s.close()
     enc.close()
+
+
+# ---- 11. an extend of one token is a step ---------------------------------------------------------------------------------------------
+def _wrapping_positions(capacity, W, last, run):
+    """positions <= last of a full window whose W - 1 cached keys wrap in the ring with at least `run` rows on each side of the wrap"""
+    out = []
+    for p in range(W, last + 1):
+        first = min(W - 1, capacity - (p - W + 1) % capacity)          # rows from the first visible key's row to the end of the ring
+        if first >= run and W - 1 - first >= run:
+            out.append(p)
+    return out
+
+
+ONE_TOKEN_STATES = {
+    # no trip of the unrolled value loop (16 keys a trip), one trip, two trips and a tail, the score pass's second trip (64 keys a trip)
+    "linear": (72, 0, [0, 1, 15, 16, 17, 33, 63, 64, 65]),
+    # both runs of cached rows short, the wrap met at every phase
+    "ringA": (8, 5, list(range(21))),
+    # an unrolled trip in both runs of cached rows, and the positions around them up to 90
+    "ringB": (40, 36, sorted(set([35, 55, 60, 79, 90] + _wrapping_positions(40, 36, 90, 16)))),
+}
+
+
+@pytest.mark.parametrize("state", list(ONE_TOKEN_STATES))
+@pytest.mark.parametrize("dims", [ODD, HD16], ids=["hd6", "hd16"])
+@pytest.mark.parametrize("dtype", ["f32", "f16", "bf16"])
+def test_extend_of_one_token_equals_a_step(dims, dtype, state):
+    """one track per position, filled by a prefill; then ONE step() of every track on one state and ONE extend() of one token per
+    track on the other: the same raw bits, and the same cache behind them (a further step of every track)"""
+    from oracle import tf_encoder_ref as T
+    capacity, W, positions = ONE_TOKEN_STATES[state]
+    if state == "ringB":
+        assert _wrapping_positions(40, 36, 90, 16) == [56, 57, 58, 59]
+    sd = T.synthetic_state_dict(dims[0], dims[1], dims[2], dims[4], dims[5], seed=7)
+    n, L = len(positions), max(positions)
+    enc = _encoder(dims, sd, dtype, sum(positions) + n)
+    x = torch.randn(n, L + 2, dims[0], generator=torch.Generator().manual_seed(11)).cuda()
+    held = [t for t in range(n) if positions[t] > 0]
+    a, s = enc.open_stream(n, capacity, window=W), enc.open_stream(n, capacity, window=W)
+    for st in (a, s):
+        st.prefill(x[held, :L].contiguous(), lengths=[positions[t] for t in held], tracks=held)
+        assert st.positions == positions
+    for k in range(2):                                                  # the token at each track's position, then the one behind it
+        tok = torch.stack([x[t, positions[t] + k] for t in range(n)])
+        ys, ya = s.step(tok), a.extend(tok[:, None].contiguous())[:, 0]
+        bad = [positions[t] + k for t in range(n) if not torch.equal(_bits(ys[t]), _bits(ya[t]))]
+        assert not bad, f"{dtype} head_dim {dims[1] // dims[3]} {state}: extend of one token differs from the step at positions {bad}"
+    assert a.positions == s.positions == [p + 2 for p in positions]
+    a.close(); s.close(); enc.close()

@@ -154,7 +154,7 @@ def emulate(qkv, H, dtype, lengths=None, window=0, capacity=None, mutation=None)
         lo = max(0, ln - window) if window else 0
         Lv, nc = ln - lo, ln - 1 - lo
         cap = capacity if capacity is not None else max(ln, 1)
-        # the cache as tf_cache_fill leaves it: token i of rows 0 .. ln - 2 in row i % cap (a ring) or i; zeros behind the track
+        # the cache as tf_cache_append leaves it: token i of rows 0 .. ln - 2 in row i % cap (a ring) or i; zeros behind the track
         cache = torch.zeros(2 * cap + Lv, 2 * d)
         for i in range(max(0, ln - 1 - cap) if window else 0, ln - 1):
             cache[i % cap if window else i] = qkv[b, i, d:].float()
