@@ -12,6 +12,7 @@ DT_BF16, DT_F16, DT_F32 = 0, 1, 2
 EINVAL = -1                                                                      # FLOPE_EINVAL of include/flope_amd.h
 IN_F32_NCHW, IN_BF16_NHWC, IN_F16_NHWC, IN_U8_NHWC = 0, 1, 2, 3
 TF_ATTN_GENERIC, TF_ATTN_MFMA64, TF_ATTN_TILED, TF_ATTN_F32M = 0, 1, 2, 3     # flope_tf_attention's return (tf_attn_plan.h)
+TF_ATTN_MASKED = 4                                                             # flope_tf_attention_masked's return
 TF_LIN_GENERIC, TF_LIN_ROWWAVE, TF_LIN_ROWWAVE_VEC, TF_LIN_MFMA, TF_LIN_F32M = 0, 1, 2, 3, 4      # flope_tf_linear's return
 TF_FWD_LAUNCHES, TF_FWD_FUSED = 0, 1                                           # flope_tf_forward_plan's return
 TF_EXTEND_ROW, TF_EXTEND_SPLIT, TF_EXTEND_MFMA = 0, 1, 2                         # flope_tf_stream_extend_plan's / _attention_extend's return
@@ -125,6 +126,13 @@ SIGNATURES = {
     "flope_tf_stream_attention": (_I, [_P, _P, _I, _I, C.POINTER(_I), _P, _P]),
     "flope_tf_stream_extend_plan": (_I, [_P]),
     "flope_tf_stream_attention_extend": (_I, [_P, _P, _I, _I, C.POINTER(_I), C.POINTER(_I), _P, _P]),
+    # scripts/tf_encoder.py: nn.TransformerEncoder.forward(mask=) for any [L, L] mask, compiled once
+    "flope_tf_mask_create": (_I, [_P, _I, C.POINTER(C.c_uint32), C.POINTER(_P)]),
+    "flope_tf_mask_destroy": (_I, [_P]),
+    "flope_tf_mask_info": (_I, [_P, C.POINTER(_I), C.POINTER(C.c_longlong)]),
+    "flope_tf_forward_masked": (_I, [_P, _P, _I, _I, C.POINTER(_I), _P, _P, _P]),
+    "flope_tf_attention_masked": (_I, [_P, _P, _I, _I, C.POINTER(_I), _P, _P, _P]),
+    "flope_tf_forward_flops_masked": (_D, [_P, _I, C.POINTER(_I), _P]),
 }
 
 _lib = None

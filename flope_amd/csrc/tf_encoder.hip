@@ -30,10 +30,15 @@
 // Option extend_mfma = 1 (16-bit handles): _extend runs tf_attn16_extend where tf_extend_mfma_ok -- tf_attn_tiled's ring and
 // 32-key step over the track's cache and the call's chunk, in absolute key blocks: the bits of the MFMA forward's rows.  It wins over
 // step_split for _extend alone; _step, _prefill and the forwards do not read it.  flope_tf_stream_attention_extend runs that launch alone.
+// flope_tf_mask_* / flope_tf_forward_masked (any dtype): any [L, L] mask compiled once to bits on the device -- the launch
+// sequence with tf_attn_masked where the forward has its attention kernel, for every shape: a softmax over exactly the allowed keys in the
+// generic kernel's order, a masked key never loaded; never the single launch, options causal / window neither read nor written (the host
+// side is tf_attn_mask.h).
 #include "../../include/flope_amd.h"
 #include "common.h"
 #include "host_pack.h"
 #include "tf_attn_plan.h"
+#include "tf_attn_mask.h"
 #include "tf_encoder_stream.h"
 #include "tf_fused_plan.h"
 
@@ -490,6 +495,117 @@ __device__ __forceinline__ void tf_attn_stream_row(const T* chunk, const T* kv, 
     }
   }
   __builtin_amdgcn_wave_barrier();
+}
+
+// ---- attention under a compiled mask (flope_tf_*_masked; the host side is tf_attn_mask.h) ---------------------------------
+// softmax(q k^T / sqrt(dh)) v for query i of one head on one wave, over exactly the keys the mask allows it: bit j % 32 of mw[j / 32]
+// (mw: this wave's copy of row i's mask words in LDS).  first / last: the first and last allowed key of the row, last already clamped
+// to the sequence's last token.  The order, fixed here once:
+//   score pass  lane l takes keys first + l, first + l + 64, .. up to last.  An allowed key gets tf_attn_row's fmaf chain over
+//               c = 0 .. dh - 1 from 0.f, then * scale, into s[j] and the maximum.  A masked key is skipped: no load, no store to the
+//               score row, not in the maximum.  A 64-key trip in which no lane has an allowed key (one wave-wide vote) issues nothing.
+//   sum pass    the same lane walk: expf(s - max) and sum += p over allowed keys only, then wave_sum.
+//   value pass  per output dim one fmaf chain from 0.f over the allowed keys in ascending j -- a walk over the set bits of the words
+//               first / 32 .. last / 32, kTfMaskUnroll keys' loads in flight in front of their fmafs, no test per j -- then
+//               * (1 / sum) and the store as tf_attn_row makes them: float16 in ONE rounding (tf_mul_f16_bits).
+// Where the allowed keys of a row are the contiguous range lo .. hi this is tf_attn_row's order for that range, operation for
+// operation, and so are the bits (tests/test_gpu_tf_mask.py: all-clear, causal, bands and block-diagonal masks against tf_attn_generic's
+// instantiations).  It is a second definition beside tf_attn_row, not a flag on it, for tf_attn_stream_row's reason: what differs is
+// the loops themselves (a vote per trip, a predicate per key, a bit walk in place of the counted value loop), and each would change
+// the loops tf_attn_generic and tf_fused_f32 compile from.
+// A masked key is never addressed, so NaN or Inf in a key that no query allows reaches no output.
+constexpr int kTfMaskUnroll = 8;
+template <typename T>
+__device__ __forceinline__ void tf_attn_masked_row(const T* base, size_t ld, T* orow, float* s, const uint32_t* mw, int i, int first, int last, int d,
+                                                   int dh, float scale, int lane) {
+  const T* q = base + (size_t)i * ld;
+  float mx = -INFINITY;
+  for (int j0 = first; j0 <= last; j0 += 64) {
+    const int j = j0 + lane;
+    const bool on = j <= last && ((mw[j >> 5] >> (j & 31)) & 1u);
+    if (!__builtin_amdgcn_ballot_w64(on)) continue;
+    if (on) {
+      const T* k = base + (size_t)j * ld + d;
+      float a = 0.f;
+      for (int c = 0; c < dh; ++c) a = fmaf(to_f32<T>(q[c]), to_f32<T>(k[c]), a);
+      a *= scale;
+      s[j] = a;
+      mx = fmaxf(mx, a);
+    }
+  }
+  mx = wave_max(mx);
+  float sum = 0.f;
+  for (int j0 = first; j0 <= last; j0 += 64) {
+    const int j = j0 + lane;
+    const bool on = j <= last && ((mw[j >> 5] >> (j & 31)) & 1u);
+    if (on) { const float p = expf(s[j] - mx); s[j] = p; sum += p; }
+  }
+  sum = wave_sum(sum);
+  __builtin_amdgcn_wave_barrier();
+  const float inv = 1.f / sum;
+  const int w0 = first >> 5, w1 = last >> 5;
+  for (int c = lane; c < dh; c += 64) {
+    const T* v = base + 2 * d + c;
+    float o = 0.f;
+    for (int w = w0; w <= w1; ++w) {
+      uint32_t m = __builtin_amdgcn_readfirstlane(mw[w]);
+      if (w == w0) m &= ~0u << (first & 31);                     // nothing below first, nothing above last: whatever the words hold,
+      if (w == w1) m &= (2u << (last & 31)) - 1u;                // no key outside first .. last is addressed
+      const int jb = w * 32;
+      while (__builtin_popcount(m) >= kTfMaskUnroll) {
+        int js[kTfMaskUnroll];
+        float vv[kTfMaskUnroll];
+#pragma unroll
+        for (int u = 0; u < kTfMaskUnroll; ++u) { js[u] = jb + __builtin_ctz(m); m &= m - 1u; }
+#pragma unroll
+        for (int u = 0; u < kTfMaskUnroll; ++u) vv[u] = to_f32<T>(v[(size_t)js[u] * ld]);
+#pragma unroll
+        for (int u = 0; u < kTfMaskUnroll; ++u) o = fmaf(s[js[u]], vv[u], o);
+      }
+      while (m) {
+        const int j = jb + __builtin_ctz(m);
+        m &= m - 1u;
+        o = fmaf(s[j], to_f32<T>(v[(size_t)j * ld]), o);
+      }
+    }
+    if constexpr (std::is_same<T, f16_t>::value) *(unsigned short*)(orow + c) = (unsigned short)tf_mul_f16_bits(o, inv);
+    else orow[c] = from_f32<T>(o * inv);
+  }
+  __builtin_amdgcn_wave_barrier();
+}
+
+// Workgroup (b, h) x blockIdx.y, one wave per query row, as tf_attn_generic; L: the sequence length (VARLEN: the longest of the batch),
+// which sized the grid and the score rows.  Lm: the mask's sequence length; bits [Lm][ceil(Lm / 32)], first / last [Lm]: the compiled
+// mask's device tables.  LDS: [4][L] floats of score rows, behind them [4][ceil(Lm / 32)] mask words (tf_mask_launch).
+// Memory safety does not hang on the tables' contents: a sequence has n <= min(L, Lm) tokens here whatever `off` says about it, row
+// i < n reads the words first / 32 .. last / 32 of its own mask row only, last is clamped to n - 1, and a row whose first is not inside
+// its sequence leaves before its first store (the host refuses such a call: tf_mask_length_row).
+template <typename T, bool VARLEN>
+__global__ void tf_attn_masked(const T* qkv, T* out, int L, int d, int H, int Lm, const uint32_t* __restrict__ bits, const int* __restrict__ first,
+                               const int* __restrict__ last, const int* __restrict__ off) {
+  extern __shared__ float sc[];                 // [waves][L] | [waves][words]
+  const int nw = blockDim.x >> 6, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int b = blockIdx.x / H, h = blockIdx.x - b * H, dh = d / H;
+  const int words = flope_tf_plan::tf_mask_words(Lm);
+  const float scale = 1.f / sqrtf((float)dh);
+  size_t row0 = 0;                              // first row of this sequence
+  int n = L;
+  if constexpr (VARLEN) { row0 = (size_t)off[b]; n = off[b + 1] - off[b]; }
+  if (n > L) n = L;
+  if (n > Lm) n = Lm;
+  float* s = sc + (size_t)wave * L;
+  uint32_t* mw = (uint32_t*)(sc + (size_t)nw * L) + (size_t)wave * words;
+  const T* base = VARLEN ? qkv + row0 * 3 * d + h * dh : qkv + (size_t)b * L * 3 * d + h * dh;
+  for (int i = blockIdx.y * nw + wave; i < n; i += gridDim.y * nw) {
+    const int fi = __builtin_amdgcn_readfirstlane(first[i]);
+    int la = __builtin_amdgcn_readfirstlane(last[i]);
+    if ((unsigned)fi >= (unsigned)n) continue;
+    if (la > n - 1) la = n - 1;
+    if (la < fi) continue;
+    for (int w = (fi >> 5) + lane; w <= (la >> 5); w += 64) mw[w] = bits[(size_t)i * words + w];
+    __builtin_amdgcn_wave_barrier();
+    tf_attn_masked_row<T>(base, (size_t)3 * d, out + ((VARLEN ? row0 : (size_t)b * L) + i) * d + h * dh, s, mw, i, fi, la, d, dh, scale, lane);
+  }
 }
 
 // Whether the table entry (track, pos0) of a step (len = 1) or of a chunk of len tokens may touch its track's cache: the track is one,
@@ -1711,6 +1827,7 @@ struct TfLinear {
   int N = 0, K = 0, Kp = 0;                  // Kp: K rounded up to 64 (the packed image's K)
 };
 struct flope_tf_stream_s;
+struct flope_tf_mask;
 struct TfLayer { TfLinear in_proj, out_proj, lin1, lin2; float *n1w = nullptr, *n1b = nullptr, *n2w = nullptr, *n2b = nullptr; };
 
 struct flope_tf_encoder {
@@ -1740,6 +1857,7 @@ struct flope_tf_encoder {
   std::vector<int> vl_host;
   std::vector<void*> allocs;
   std::vector<flope_tf_stream_s*> streams;   // the open stream states of this handle (flope_tf_stream_open); destroy orphans them
+  std::vector<flope_tf_mask*> masks;         // the compiled masks of this handle (flope_tf_mask_create); destroy orphans them
   std::string err;
 };
 
@@ -1753,6 +1871,20 @@ struct flope_tf_stream_s {
   int* tab = nullptr;                        // device table of one call (4 ints per track): step (track, position) per row, prefill the track per sequence, attention both and its fills' offsets
   std::vector<int> pos, tab_host;            // tokens held per track; the pageable copy tab is uploaded from
   std::vector<char> seen;                    // scratch of the argument checks
+};
+
+// A compiled attention mask (flope_tf_mask_*; tf_attn_mask.h): one device allocation bits | first | last, and the host
+// copies the per-call checks and the FLOP count read.
+struct flope_tf_mask {
+  flope_tf_encoder* e = nullptr;             // nullptr once the handle is destroyed: every call but destroy then fails with FLOPE_ESTATE
+  int L = 0;
+  long long pairs = 0;
+  void* dev = nullptr;                       // uint32 bits [L][words] | int first [L] | int last [L]
+  std::vector<uint32_t> bits;
+  std::vector<int> first, last;
+  const uint32_t* bits_dev() const { return (const uint32_t*)dev; }
+  const int* first_dev() const { return (const int*)(bits_dev() + bits.size()); }
+  const int* last_dev() const { return first_dev() + L; }
 };
 
 namespace {
@@ -2178,6 +2310,11 @@ extern "C" int flope_tf_create(int device_id, int input_dim, int model_dim, int 
     for (const void* f : ext16)
       if (hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)flope_tf_plan::tf_attn_tiled_lds(128)) != hipSuccess)
         return fin(tf_fail(nullptr, FLOPE_EHIP, "flope_tf_create: hipFuncSetAttribute failed"));
+    const void* const masked[] = {(const void*)tf_attn_masked<float, false>, (const void*)tf_attn_masked<float, true>, (const void*)tf_attn_masked<f16_t, false>,
+                                  (const void*)tf_attn_masked<f16_t, true>, (const void*)tf_attn_masked<bf16_t, false>, (const void*)tf_attn_masked<bf16_t, true>};
+    for (const void* f : masked)                     // four score rows of up to max_tokens floats and the mask words behind them
+      if (hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kTfAttnLds) != hipSuccess)
+        return fin(tf_fail(nullptr, FLOPE_EHIP, "flope_tf_create: hipFuncSetAttribute failed"));
     if (hipDeviceGetAttribute(&e->cus, hipDeviceAttributeMultiprocessorCount, device_id) != hipSuccess || e->cus < 1) e->cus = 256;
   }
   *out = e;
@@ -2190,6 +2327,10 @@ extern "C" int flope_tf_destroy(flope_tf_handle e) {
   for (flope_tf_stream_s* s : e->streams) {      // their device memory goes with the handle; the states stay until closed and refuse every call
     hipFree(s->cache); hipFree(s->tab);
     s->cache = nullptr; s->tab = nullptr; s->e = nullptr;
+  }
+  for (flope_tf_mask* m : e->masks) {            // the same for the compiled masks
+    hipFree(m->dev);
+    m->dev = nullptr; m->e = nullptr;
   }
   for (void* p : e->allocs) hipFree(p);
   delete e;
@@ -2481,6 +2622,167 @@ extern "C" double flope_tf_forward_flops_varlen(flope_tf_handle e, int batch, co
   const double d = e->d;
   double mac = M * e->in_dim * d + M * d * e->out_dim;
   mac += e->nl * (M * d * 3 * d + M * d * d + 2.0 * M * d * e->ff + 2.0 * sq * d);
+  return 2.0 * mac;
+}
+
+// ---- attention under a compiled mask ------------------------------------------------------------------------------------
+namespace {
+
+// The masked attention launch: tf_attn_masked for every dtype and head_dim, launched as the generic kernel always is plus the mask rows
+// in LDS (tf_mask_launch).  off == nullptr: qkv [B][L][3 d], L == m->L; otherwise the packed rows of a ragged batch, L its longest length.
+template <typename T>
+int launch_attention_masked(flope_tf_encoder* e, const flope_tf_mask* m, const void* qkv, void* att, int B, int L, const int* off, hipStream_t st) {
+  const flope_tf_plan::TfAttnLaunch l = flope_tf_plan::tf_mask_launch(e->d / e->H, B, e->H, L, m->L);
+  const dim3 grid(l.grid_x, l.grid_y), block(l.block);
+  if (off)
+    hipLaunchKernelGGL((tf_attn_masked<T, true>), grid, block, l.lds, st, (const T*)qkv, (T*)att, L, e->d, e->H, m->L, m->bits_dev(), m->first_dev(), m->last_dev(), off);
+  else
+    hipLaunchKernelGGL((tf_attn_masked<T, false>), grid, block, l.lds, st, (const T*)qkv, (T*)att, L, e->d, e->H, m->L, m->bits_dev(), m->first_dev(), m->last_dev(), off);
+  TF_HIP(e, hipGetLastError());
+  return FLOPE_TF_ATTN_MASKED;
+}
+
+// The checks every masked call starts with, before anything is enqueued.  lengths == NULL: a fixed-length batch of `batch` sequences of
+// seq_len tokens.  Otherwise the ragged batch is planned into off_host (batch + 1 ints) and *rg, and every length n is held against
+// the mask's n x n corner.
+int tf_masked_check(flope_tf_encoder* e, const std::string& who, const flope_tf_mask* m, int batch, int seq_len, const int* lengths, int* off_host,
+                    TfRagged* rg) {
+  if (!e) return tf_fail(nullptr, FLOPE_EINVAL, who + ": NULL handle");
+  if (!m) return tf_fail(e, FLOPE_EINVAL, who + ": NULL mask");
+  if (!m->e) return tf_fail(e, FLOPE_ESTATE, who + ": the encoder handle of this mask has been destroyed");
+  if (m->e != e) return tf_fail(e, FLOPE_EINVAL, who + ": the mask was created on another handle");
+  if (batch < 1) return tf_fail(e, FLOPE_EINVAL, who + ": batch must be positive");
+  if (seq_len != m->L)
+    return tf_fail(e, FLOPE_EINVAL, who + ": seq_len = " + std::to_string(seq_len) + " differs from the mask's seq_len = " + std::to_string(m->L));
+  int max_len = seq_len;
+  if (!lengths) {
+    if ((long long)batch * seq_len > e->max_tokens) return tf_fail(e, FLOPE_EINVAL, who + ": batch*seq_len exceeds max_tokens given to flope_tf_create");
+  } else {
+    if (int rc = tf_check_ragged(e, who.c_str(), lengths, batch, seq_len, off_host, rg)) return rc;
+    for (int b = 0; b < batch; ++b) {
+      const int row = flope_tf_plan::tf_mask_length_row(m->first.data(), m->L, lengths[b]);
+      if (row >= 0)
+        return tf_fail(e, FLOPE_EINVAL, who + ": lengths[" + std::to_string(b) + "] = " + std::to_string(lengths[b]) + ": b = " + std::to_string(b) + ", row " +
+                                            std::to_string(row) + " has no allowed key below " + std::to_string(lengths[b]) + " (a softmax over nothing)");
+    }
+    max_len = rg->max_len;
+  }
+  if (flope_tf_plan::tf_mask_launch(e->d / e->H, batch, e->H, max_len, m->L).lds > flope_tf_plan::kTfAttnLds)
+    return tf_fail(e, FLOPE_EINVAL, who + ": seq_len too long for the score rows of one workgroup");
+  return 0;
+}
+
+}  // namespace
+
+extern "C" int flope_tf_mask_create(flope_tf_handle e, int seq_len, const uint32_t* allow_bits_host, flope_tf_mask_handle* out) {
+  using namespace flope_tf_plan;
+  const std::string who = "flope_tf_mask_create";
+  if (out) *out = nullptr;
+  if (!e) return tf_fail(nullptr, FLOPE_EINVAL, who + ": NULL handle");
+  if (!out || !allow_bits_host) return tf_fail(e, FLOPE_EINVAL, who + ": NULL argument");
+  if (seq_len < 1 || seq_len > e->max_tokens)
+    return tf_fail(e, FLOPE_EINVAL, who + ": seq_len = " + std::to_string(seq_len) + " is outside 1 .. max_tokens = " + std::to_string(e->max_tokens));
+  int row = -1;
+  const int col = tf_mask_padding_bit(allow_bits_host, seq_len, &row);
+  if (col >= 0)
+    return tf_fail(e, FLOPE_EINVAL, who + ": padding bit set in row " + std::to_string(row) + ", column " + std::to_string(col) + " (columns >= seq_len must be zero)");
+  row = tf_mask_empty_row(allow_bits_host, seq_len);
+  if (row >= 0) return tf_fail(e, FLOPE_EINVAL, who + ": row " + std::to_string(row) + " has no allowed key (a softmax over nothing; the reference returns NaN there)");
+  flope_tf_mask* m = new flope_tf_mask();
+  m->L = seq_len;
+  m->bits.assign(allow_bits_host, allow_bits_host + (size_t)seq_len * tf_mask_words(seq_len));
+  m->first.resize(seq_len);
+  m->last.resize(seq_len);
+  tf_mask_first_last(m->bits.data(), seq_len, m->first.data(), m->last.data());
+  m->pairs = tf_mask_pairs(m->bits.data(), seq_len);
+  const size_t nb = m->bits.size() * sizeof(uint32_t), nt = (size_t)seq_len * sizeof(int);
+  auto fin = [&](const std::string& what) { hipFree(m->dev); delete m; return tf_fail(e, FLOPE_EHIP, who + ": " + what); };
+  if (hipSetDevice(e->device) != hipSuccess) return fin("hipSetDevice failed");
+  if (hipMalloc(&m->dev, nb + 2 * nt) != hipSuccess) { m->dev = nullptr; return fin("hipMalloc of " + std::to_string(nb + 2 * nt) + " bytes failed"); }
+  if (hipMemcpy(m->dev, m->bits.data(), nb, hipMemcpyHostToDevice) != hipSuccess ||
+      hipMemcpy((char*)m->dev + nb, m->first.data(), nt, hipMemcpyHostToDevice) != hipSuccess ||
+      hipMemcpy((char*)m->dev + nb + nt, m->last.data(), nt, hipMemcpyHostToDevice) != hipSuccess)
+    return fin("hipMemcpy failed");
+  m->e = e;
+  e->masks.push_back(m);
+  *out = m;
+  return FLOPE_OK;
+}
+
+extern "C" int flope_tf_mask_destroy(flope_tf_mask_handle m) {
+  if (!m) return FLOPE_OK;
+  if (flope_tf_encoder* e = m->e) {                // after flope_tf_destroy the device memory is gone already
+    hipSetDevice(e->device);
+    hipFree(m->dev);
+    for (size_t i = 0; i < e->masks.size(); ++i)
+      if (e->masks[i] == m) { e->masks.erase(e->masks.begin() + (long)i); break; }
+  }
+  delete m;
+  return FLOPE_OK;
+}
+
+extern "C" int flope_tf_mask_info(flope_tf_mask_handle m, int* seq_len, long long* allowed_pairs) {
+  if (!m) return tf_fail(nullptr, FLOPE_EINVAL, "flope_tf_mask_info: NULL mask");
+  if (!m->e) return tf_fail(nullptr, FLOPE_ESTATE, "flope_tf_mask_info: the encoder handle of this mask has been destroyed");
+  if (seq_len) *seq_len = m->L;
+  if (allowed_pairs) *allowed_pairs = m->pairs;
+  return FLOPE_OK;
+}
+
+extern "C" int flope_tf_forward_masked(flope_tf_handle e, const float* x_dev, int batch, int seq_len, const int* lengths_host, flope_tf_mask_handle m,
+                                       float* y_dev, void* stream) {
+  const std::string who = "flope_tf_forward_masked";
+  if (!e) return tf_fail(nullptr, FLOPE_EINVAL, who + ": NULL handle");
+  if (!x_dev || !y_dev) return tf_fail(e, FLOPE_EINVAL, who + ": NULL buffer");
+  TfRagged rg;
+  int rc;
+  if ((rc = tf_masked_check(e, who, m, batch, seq_len, lengths_host, e->vl_host.data(), &rg))) return rc;
+  if (!e->loaded) return tf_fail(e, FLOPE_ESTATE, who + ": weights not loaded");
+  if (lengths_host && (rc = tf_check_forward_varlen(e, who, batch, seq_len, true))) return rc;
+  TF_HIP(e, hipSetDevice(e->device));
+  hipStream_t st = (hipStream_t)stream;
+  if (lengths_host && (rc = tf_upload_ragged(e, batch, st))) return rc;
+  e->last_fwd = FLOPE_TF_FWD_LAUNCHES;              // never the single launch
+  const TfRagged* rgp = lengths_host ? &rg : nullptr;
+  return tf_by_dtype(e, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    return run_forward_with<T>(e, x_dev, batch, seq_len, y_dev, st, rgp, [&](int) {
+      return launch_attention_masked<T>(e, m, e->qkv, e->att, batch, rgp ? rg.max_len : seq_len, rgp ? e->vl_off : nullptr, st);
+    });
+  });
+}
+
+extern "C" int flope_tf_attention_masked(flope_tf_handle e, const void* qkv_dev, int batch, int seq_len, const int* lengths_host, flope_tf_mask_handle m,
+                                         void* out_dev, void* stream) {
+  const std::string who = "flope_tf_attention_masked";
+  if (!e) return tf_fail(nullptr, FLOPE_EINVAL, who + ": NULL handle");
+  if (!qkv_dev || !out_dev) return tf_fail(e, FLOPE_EINVAL, who + ": NULL buffer");
+  if (((uintptr_t)qkv_dev | (uintptr_t)out_dev) & (uintptr_t)(e->esz - 1)) return tf_fail(e, FLOPE_EINVAL, who + ": buffer not aligned to its element type");
+  TfRagged rg;
+  int rc;
+  if ((rc = tf_masked_check(e, who, m, batch, seq_len, lengths_host, e->vl_host.data(), &rg))) return rc;
+  TF_HIP(e, hipSetDevice(e->device));
+  hipStream_t st = (hipStream_t)stream;
+  if (lengths_host && (rc = tf_upload_ragged(e, batch, st))) return rc;
+  return tf_by_dtype(e, [&](auto tag) {
+    return launch_attention_masked<typename decltype(tag)::type>(e, m, qkv_dev, out_dev, batch, lengths_host ? rg.max_len : seq_len,
+                                                                 lengths_host ? e->vl_off : nullptr, st);
+  });
+}
+
+// algorithmic FLOPs of one masked forward: the linears on every token, attention on the allowed pairs (lengths: of each length's corner)
+extern "C" double flope_tf_forward_flops_masked(flope_tf_handle e, int batch, const int* lengths_host, flope_tf_mask_handle m) {
+  if (!e || !m || m->e != e || batch < 1) return 0.0;
+  double M = 0.0, pairs = 0.0;
+  for (int b = 0; b < batch; ++b) {
+    const int n = lengths_host ? lengths_host[b] : m->L;
+    if (n < 1 || n > m->L) return 0.0;
+    M += n;
+    pairs += n == m->L ? (double)m->pairs : (double)flope_tf_plan::tf_mask_pairs_len(m->bits.data(), m->L, n);
+  }
+  const double d = e->d;
+  double mac = M * e->in_dim * d + M * d * e->out_dim;
+  mac += e->nl * (M * d * 3 * d + M * d * d + 2.0 * M * d * e->ff + 2.0 * pairs * d);
   return 2.0 * mac;
 }
 

@@ -10,6 +10,9 @@ t - W < j <= t; `enc.open_stream(tracks, capacity, window=W)` is the same live, 
 A 16-bit encoder made with `window_mfma=1` keeps its MFMA attention kernels under a window.
 An encoder made with `step_split=1` splits the keys of a stream's step() / extend() over the four waves of a workgroup.
 A 16-bit encoder made with `extend_mfma=1` runs a stream's extend() on the MFMA attention step: the MFMA forward's rows in bits.
+Any other [L, L] mask is compiled once with `enc.make_mask(mask)` and passed as `mask=` to any number of calls: query i is a softmax over
+exactly its allowed keys, a masked key is never loaded, and a sequence of a ragged batch is encoded under the mask's top-left corner
+(DESIGN.md 37).
 
 Eval-mode semantics only (dropout is identity), as everywhere in this package.  There is no CPU
 path: construction fails loudly without a HIP device or without the built library.
@@ -127,6 +130,35 @@ def _mask_window(mask, L):
                      "all-clear mask has a kernel")
 
 
+def _mask_allowed(mask):
+    """torch's `mask` of nn.TransformerEncoder.forward, any square one -> the bool [L, L] CPU tensor of ALLOWED pairs.  bool: True =
+    masked (torch's convention); floating: -inf = masked, 0 = allowed, anything else raises ValueError naming the first such entry.
+    No pattern is looked for."""
+    mask = torch.as_tensor(mask)
+    if mask.dim() != 2 or mask.shape[0] != mask.shape[1] or mask.shape[0] < 1 or not (mask.dtype == torch.bool or mask.dtype.is_floating_point):
+        raise ValueError(f"mask must be a bool or floating tensor [L, L] with L >= 1, got {mask.dtype} {tuple(mask.shape)}")
+    m = mask.detach().cpu()
+    if m.dtype == torch.bool:
+        return ~m
+    m = m.double()
+    allowed, masked = m == 0, m == float("-inf")
+    wrong = ~(allowed | masked)
+    if bool(wrong.any()):
+        r, c = (int(v) for v in wrong.nonzero()[0])
+        raise ValueError(f"mask[{r}, {c}] = {mask[r, c].item()!r}: a floating mask holds -inf (masked) or 0 (allowed); additive biases have no kernel")
+    return allowed
+
+
+def _pack_allowed(allowed):
+    """bool [L, L] of allowed pairs -> the uint32 words [L][ceil(L / 32)] flope_tf_mask_create takes (bit j % 32 of word j / 32)"""
+    L = allowed.shape[0]
+    words = (L + 31) // 32
+    a = torch.zeros(L, words * 32, dtype=torch.int64)
+    a[:, :L] = allowed.to(torch.int64)
+    packed = (a.view(L, words, 32) << torch.arange(32, dtype=torch.int64)).sum(dim=2)
+    return (C.c_uint32 * (L * words))(*packed.reshape(-1).tolist())
+
+
 class TransformerEncoder:
     def __init__(self, input_dim, model_dim, out_dim, num_heads, num_layers, ff_dim, dropout=0.1,
                  dtype="f32", max_tokens=4096, device=None, attn_tiled=0, fused=0, window_mfma=0, step_split=0, extend_mfma=0):
@@ -235,18 +267,41 @@ class TransformerEncoder:
         if rc < 0:
             raise RuntimeError(f"flope_tf_set_option(window) failed ({rc})")
 
-    def flops(self, batch: int, seq_len: int, lengths=None, *, is_causal=False, window=0) -> float:
+    def make_mask(self, mask) -> "TransformerEncoderMask":
+        """Compiles any [L, L] attention mask -- bool (True = masked, torch's convention) or floating (-inf / 0), on any device -- into
+        a device-resident TransformerEncoderMask that forward(), attention(), flops() and forward_plan() take as `mask=` (DESIGN.md
+        37).  No pattern is recognised: a causal tensor compiled this way runs the masked kernel.  ValueError: another shape, dtype or
+        value (the first offending entry is named), a row without an allowed key (the reference returns NaN there), L > max_tokens."""
+        return TransformerEncoderMask(self, mask)
+
+    def _compiled(self, mask, seq_len, is_causal, window):
+        """The checks every call that takes a compiled mask starts with"""
+        if mask.enc is not self:
+            raise ValueError("the mask was compiled by another encoder")
+        mask._live()
+        if is_causal or int(window) != 0:
+            raise ValueError("a compiled mask together with is_causal=True or window != 0: say it in the mask")
+        if seq_len is not None and int(seq_len) != mask.L:
+            raise ValueError(f"the mask was compiled for sequences of {mask.L} tokens, this call has {int(seq_len)}")
+
+    def flops(self, batch: int, seq_len: int, lengths=None, *, is_causal=False, window=0, mask=None) -> float:
         """Algorithmic FLOPs of one forward; `is_causal`: attention counted over the keys a causal forward meets, `window`: over
-        the min(t + 1, window) keys query t meets under a window."""
+        the min(t + 1, window) keys query t meets under a window, `mask` (a compiled one): over its allowed pairs."""
+        if isinstance(mask, TransformerEncoderMask):
+            self._compiled(mask, seq_len, is_causal, window)
+            return self.lib.flope_tf_forward_flops_masked(self.handle, int(batch), None if lengths is None else _host_lengths(lengths, batch), mask.handle)
         self._state_window(is_causal, window)
         if lengths is None:
             return self.lib.flope_tf_forward_flops(self.handle, batch, seq_len)
         return self.lib.flope_tf_forward_flops_varlen(self.handle, batch, _host_lengths(lengths, batch))
 
-    def forward_plan(self, batch: int, seq_len: int, lengths=None, *, is_causal=False, window=0) -> str:
+    def forward_plan(self, batch: int, seq_len: int, lengths=None, *, is_causal=False, window=0, mask=None) -> str:
         """"fused" or "launches": what forward() of x [batch, seq_len, input_dim] (with these `lengths`, with `is_causal`, with
-        `window`: always "launches") would run under the current options.  Enqueues nothing; a shape the forward refuses raises
-        ValueError."""
+        `window`: always "launches", with a compiled `mask`: always "launches") would run under the current options.  Enqueues
+        nothing; a shape the forward refuses raises ValueError."""
+        if isinstance(mask, TransformerEncoderMask):
+            self._compiled(mask, seq_len, is_causal, window)
+            return "launches"
         self._state_window(is_causal, window)
         with torch.cuda.device(self.device):
             rc = self.lib.flope_tf_forward_plan(self.handle, int(batch), int(seq_len), None if lengths is None else _host_lengths(lengths, batch))
@@ -281,7 +336,9 @@ class TransformerEncoder:
         and W >= L gives the generic causal kernel's bits; on a handle made with `window_mfma=1` a 16-bit forward keeps the MFMA
         kernel it would run without a window, and W >= L gives that kernel's causal bits.  The forward is never the
         single launch.  A banded mask together with another `window` raises
-        ValueError.  The option is stated per call: a plain call after a windowed one has no window."""
+        ValueError.  The option is stated per call: a plain call after a windowed one has no window.
+        `mask` = a TransformerEncoderMask (make_mask): any set of allowed (query, key) pairs, see there; with `is_causal=True` or a
+        `window` it raises ValueError."""
         if not x.is_cuda or x.device != self.device:
             raise RuntimeError(f"input must live on {self.device} (got {x.device}); no CPU path")
         if x.dim() != 3 or x.shape[2] != self.dims[0]:
@@ -292,6 +349,18 @@ class TransformerEncoder:
         B, L = x.shape[0], x.shape[1]
         if src_key_padding_mask is not None:
             lengths = _mask_to_lengths(src_key_padding_mask, B, L)
+        if isinstance(mask, TransformerEncoderMask):
+            # a compiled mask (make_mask): any [L, L] set of allowed pairs.  Sequence b of a ragged batch is encoded
+            # alone under the mask's top-left lengths[b] x lengths[b] corner.  Always the launch sequence; options "causal" and
+            # "window" are neither read nor written.
+            self._compiled(mask, L, is_causal, window)
+            y = torch.empty((B, L, self.dims[2]), dtype=torch.float32, device=self.device)
+            lh = None if lengths is None else _host_lengths(lengths, B)
+            with torch.cuda.device(self.device):
+                self._check_arg(self.lib.flope_tf_forward_masked(self.handle, x.data_ptr(), B, L, lh, mask.handle, y.data_ptr(), _stream_ptr(self.device)))
+            self.last_forward_fused = False
+            self._keep = x
+            return y
         causal, band = _mask_window(mask, L)
         if is_causal and mask is not None and not causal:
             raise ValueError("is_causal=True with a mask that is not the causal mask")
@@ -313,7 +382,7 @@ class TransformerEncoder:
 
     __call__ = forward
 
-    def attention(self, qkv: torch.Tensor, lengths=None, out: torch.Tensor = None, *, is_causal=False, window=0) -> torch.Tensor:
+    def attention(self, qkv: torch.Tensor, lengths=None, out: torch.Tensor = None, *, is_causal=False, window=0, mask=None) -> torch.Tensor:
         """softmax(q k^T / sqrt(head_dim)) v per head of qkv [B, L, 3 * model_dim] in the handle's dtype -> [B, L, model_dim], by
         the kernel a forward of this (B, L) would launch under the current options; its id is kept in `last_attn_kernel`.  Needs no
         weights.  `out`: a contiguous tensor of the result's shape and dtype to write into.
@@ -321,8 +390,15 @@ class TransformerEncoder:
         sum(lengths[:b]) onwards; the result is the packed [T, model_dim].
         `is_causal`: query i attends to keys <= i of its own sequence; the kernel is the one the shape picks without it.
         `window=W` (with `is_causal=True`): keys i - W < j <= i, by the generic kernel with `window_mfma=0`, by the 16-bit MFMA
-        kernel the call would take without a window on a handle made with `window_mfma=1`."""
-        self._state_window(is_causal, window)
+        kernel the call would take without a window on a handle made with `window_mfma=1`.
+        `mask` (a compiled one, make_mask): softmax over the allowed keys only, by tf_attn_masked (`last_attn_kernel` = 4) for every
+        dtype and shape; with `lengths` each sequence under the mask's corner."""
+        if mask is not None and not isinstance(mask, TransformerEncoderMask):
+            raise ValueError("attention() takes a compiled mask (enc.make_mask), not a tensor")
+        if mask is not None:
+            self._compiled(mask, None, is_causal, window)
+        else:
+            self._state_window(is_causal, window)
         tdt = {"f16": torch.float16, "bf16": torch.bfloat16}.get(self.dtype, torch.float32)
         d = self.dims[1]
         if not qkv.is_cuda or qkv.device != self.device:
@@ -338,7 +414,10 @@ class TransformerEncoder:
             elif out.shape != (T, d) or out.dtype != tdt or out.device != self.device or not out.is_contiguous():
                 raise ValueError(f"out must be a contiguous {tdt} tensor {(T, d)} on {self.device}")
             with torch.cuda.device(self.device):
-                rc = self.lib.flope_tf_attention_varlen(self.handle, qkv.data_ptr(), n, lh, out.data_ptr(), _stream_ptr(self.device))
+                if mask is not None:
+                    rc = self.lib.flope_tf_attention_masked(self.handle, qkv.data_ptr(), n, mask.L, lh, mask.handle, out.data_ptr(), _stream_ptr(self.device))
+                else:
+                    rc = self.lib.flope_tf_attention_varlen(self.handle, qkv.data_ptr(), n, lh, out.data_ptr(), _stream_ptr(self.device))
             self._check_arg(rc)
             self.last_attn_kernel = rc
             self._keep = qkv
@@ -350,7 +429,12 @@ class TransformerEncoder:
             out = torch.empty((B, L, d), dtype=tdt, device=self.device)
         elif out.shape != (B, L, d) or out.dtype != tdt or out.device != self.device or not out.is_contiguous():
             raise ValueError(f"out must be a contiguous {tdt} tensor {(B, L, d)} on {self.device}")
-        rc = self.lib.flope_tf_attention(self.handle, qkv.data_ptr(), B, L, out.data_ptr(), _stream_ptr(self.device))
+        if mask is not None:
+            with torch.cuda.device(self.device):
+                rc = self.lib.flope_tf_attention_masked(self.handle, qkv.data_ptr(), B, L, None, mask.handle, out.data_ptr(), _stream_ptr(self.device))
+            self._check_arg(rc)
+        else:
+            rc = self.lib.flope_tf_attention(self.handle, qkv.data_ptr(), B, L, out.data_ptr(), _stream_ptr(self.device))
         if rc < 0:
             self._check(rc)
         self.last_attn_kernel = rc
@@ -462,6 +546,47 @@ class TransformerEncoder:
     def close(self):
         if getattr(self, "handle", None) and self.handle.value:
             self.lib.flope_tf_destroy(self.handle)
+            self.handle = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class TransformerEncoderMask:
+    """An [L, L] attention mask compiled for one encoder (include/flope_amd.h: flope_tf_mask_*): the allowed (query, key)
+    pairs as bits on the device, made once by `enc.make_mask(mask)` and passed as `mask=` to any number of forwards.  `L`: the
+    sequence length it was made for; `allowed`: the number of allowed pairs.  It keeps its encoder alive; after enc.close() or its own
+    close() its use raises RuntimeError."""
+
+    def __init__(self, enc: TransformerEncoder, mask):
+        self.enc = enc
+        self.handle = C.c_void_p()
+        if not enc.handle.value:
+            raise RuntimeError("the encoder of this mask has been closed")
+        allowed = _mask_allowed(mask)
+        self.L = int(allowed.shape[0])
+        empty = (~allowed.any(dim=1)).nonzero().reshape(-1).tolist()
+        if empty:
+            raise ValueError(f"mask row {empty[0]} has no allowed key: a softmax over nothing (the reference returns NaN for it)")
+        with torch.cuda.device(enc.device):
+            rc = enc.lib.flope_tf_mask_create(enc.handle, self.L, _pack_allowed(allowed), C.byref(self.handle))
+        enc._check_arg(rc)
+        n, pairs = C.c_int(), C.c_longlong()
+        enc._check_arg(enc.lib.flope_tf_mask_info(self.handle, C.byref(n), C.byref(pairs)))
+        self.allowed = int(pairs.value)
+
+    def _live(self):
+        if not self.enc.handle.value:
+            raise RuntimeError("the encoder of this mask has been closed")
+        if not self.handle.value:
+            raise RuntimeError("the mask has been closed")
+
+    def close(self):
+        if getattr(self, "handle", None) and self.handle.value:
+            self.enc.lib.flope_tf_mask_destroy(self.handle)      # after enc.close() this frees the host part only
             self.handle = C.c_void_p()
 
     def __del__(self):

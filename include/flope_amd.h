@@ -572,6 +572,40 @@ int flope_tf_stream_attention(flope_tf_stream s, const void* qkv_dev, int n, int
 int flope_tf_stream_extend_plan(flope_tf_stream s);
 int flope_tf_stream_attention_extend(flope_tf_stream s, const void* qkv_dev, int n, int seq_len, const int* lengths_host, const int* cached_host,
                                      void* att_dev, void* stream);
+/* Any [L, L] attention mask (scripts/tf_encoder.py: nn.TransformerEncoder.forward(mask=)), compiled once into a
+ * device-resident object and passed to any number of forwards.  A mask holds, for one sequence length L, the (query i, key j) pairs
+ * that may attend: query i is a softmax over exactly its allowed keys, and a masked key is never loaded, neither its k nor its v (NaN
+ * there reaches no output).  Attention under a mask runs tf_attn_masked -- the generic kernel's order over the allowed keys, for every
+ * dtype and head_dim, whatever kernel the unmasked shape picks -- and the forward is always the launch sequence.  Where a row's
+ * allowed keys are one contiguous range the row is the generic kernel's for that range, operation for operation.
+ *   _mask_create   (nn.TransformerEncoder.forward(mask=) of scripts/tf_encoder.py, the mask argument) allow_bits_host: uint32 words
+ *             [seq_len][ceil(seq_len / 32)], bit j % 32 of word j / 32 of row i set = query i may attend to key j, padding bits zero.
+ *             Allocates and uploads synchronously: masks are made once, a forward allocates nothing.  A handle may own several
+ *             masks; they end with the handle: after flope_tf_destroy every call on a mask but _mask_destroy returns FLOPE_ESTATE.
+ *             FLOPE_EINVAL (flope_tf_last_error names the index): NULL arguments, seq_len < 1 or > max_tokens, a set padding bit,
+ *             a row without a key (the reference returns NaN for that row and, a layer later, for its whole batch element).
+ *   _mask_info     seq_len and the number of allowed pairs (either pointer may be NULL).
+ *   _forward_masked  (nn.TransformerEncoder.forward(src, mask=, src_key_padding_mask=) of scripts/tf_encoder.py) flope_tf_forward
+ *             (lengths_host NULL) or flope_tf_forward_varlen (lengths_host: batch ints) under mask m, whose seq_len must equal the
+ *             call's.  A sequence of n tokens is encoded alone under the top-left n x n corner of the mask; rows behind it are never
+ *             read and come back as out_layer.bias.  Never the single launch of option "fused"; neither reads nor writes options
+ *             "causal" / "window"; flope_tf_last_forward reports FLOPE_TF_FWD_LAUNCHES after it.  FLOPE_EINVAL, before anything is
+ *             enqueued: NULL arguments, a seq_len that differs from the mask's, a length outside 1 .. seq_len, a length n under which
+ *             a row below n has no key (the message names b and the row), too many tokens, a mask of another handle.
+ *   _attention_masked  flope_tf_attention (lengths_host NULL: qkv_dev [batch, seq_len, 3*model_dim]) or flope_tf_attention_varlen
+ *             (lengths_host: packed rows) under mask m: the attention launch of _forward_masked alone.  Returns
+ *             FLOPE_TF_ATTN_MASKED (4), or < 0 with the refusals above.
+ *   _forward_flops_masked  algorithmic FLOPs of _forward_masked: the linears on every token, attention on the allowed pairs (of each
+ *             length's corner with lengths_host); 0 for an invalid call. */
+typedef struct flope_tf_mask* flope_tf_mask_handle;
+int flope_tf_mask_create(flope_tf_handle h, int seq_len, const uint32_t* allow_bits_host, flope_tf_mask_handle* out);
+int flope_tf_mask_destroy(flope_tf_mask_handle m);
+int flope_tf_mask_info(flope_tf_mask_handle m, int* seq_len, long long* allowed_pairs);
+int flope_tf_forward_masked(flope_tf_handle h, const float* x_dev, int batch, int seq_len, const int* lengths_host, flope_tf_mask_handle m,
+                            float* y_dev, void* stream);
+int flope_tf_attention_masked(flope_tf_handle h, const void* qkv_dev, int batch, int seq_len, const int* lengths_host, flope_tf_mask_handle m,
+                              void* out_dev, void* stream);
+double flope_tf_forward_flops_masked(flope_tf_handle h, int batch, const int* lengths_host, flope_tf_mask_handle m);
 
 /* ---- YOLO11-seg detector front end ---------------------------------------------------
  * Replaces `self.yolo = YOLO(yolo_path)` (sunflower/predictor/fast_pose_predictor.py:36) and the
