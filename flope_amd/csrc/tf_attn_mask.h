@@ -3,7 +3,9 @@
 // entry points) and tests/host_harness/harness_tf_mask.cpp (tests/test_tf_mask_host.py holds every function against brute force).
 // Layout: uint32 words [L][tf_mask_words(L)], bit j % 32 of word j / 32 of row i set = query i may attend to key j; the padding bits
 // (columns L .. 32 * words - 1) are zero.  first[i] / last[i]: the first and last allowed key of row i; a row without a key has
-// first = L and last = -1.
+// first = L and last = -1.  Below them the mask's tile map for option mask_mfma: which 64-key blocks a 128-row query block
+// loads and which 32-key steps a wave takes, tf_attn_pick_masked and the launch of tf_attn_tiled_masked
+// (tests/host_harness/harness_tf_mask16.cpp, tests/test_tf_mask16_host.py).
 #pragma once
 
 #include <stddef.h>
@@ -109,6 +111,104 @@ inline TfAttnLaunch tf_mask_launch(int head_dim, int B, int H, int max_len, int 
   TfAttnLaunch l = tf_attn_varlen_launch(FLOPE_TF_ATTN_GENERIC, head_dim, B, H, max_len);
   l.lds = (tf_mask_lds_words_at(max_len) + (size_t)4 * tf_mask_words(L)) * 4;
   return l;
+}
+
+// ---- the tile map of a mask (option "mask_mfma") ------------------------------------------------------------------------
+// tf_attn_tiled_masked walks a mask in the units of tf_attn_tiled: query blocks of kTfAttnTiledQueries = 128 rows (four waves of 32),
+// key blocks of kTfAttnTiledKB = 64 keys (two 32-key steps).  Query block qb owns the ascending list of the key blocks that hold at
+// least one allowed pair with one of its rows, entries start[qb] .. start[qb + 1] - 1 (CSR; nqb = tf_mask_query_blocks(L) lists, every
+// one non-empty: every row has a key).  An entry is 16 bytes:
+//   kblock      the key block: keys 64 kblock .. 64 kblock + 63
+//   colany      bit r: key 64 kblock + r is allowed by some row of the query block (lo: r < 32, hi: r - 32)
+//   cls         two bits per (wave w = 0 .. 3, step s = 0 .. 1) at bit 2 (2 w + s): the tile of rows 128 qb + 32 w .. + 31 below L and keys
+//               64 kblock + 32 s .. + 31 below L holds no allowed pair (kTfMaskNone; also a tile without a row or a key below L), some
+//               (kTfMaskSome) or only allowed pairs (kTfMaskAll)
+// A sequence of n < L tokens is encoded under the n x n corner: its query blocks are the first ceil(n / 128), of each list the entries
+// with 64 kblock < n, a prefix (tf_mask_tiles_corner).  The classes stay those of the whole mask: "none" and "all" stay true of the
+// corner, "some" may have become either, which costs a word load or a step over nothing and no bit.
+struct TfMaskTile { int32_t kblock; uint32_t colany_lo, colany_hi, cls; };
+static_assert(sizeof(TfMaskTile) == 16, "an entry is one 16-byte load");
+enum { kTfMaskNone = 0, kTfMaskSome = 1, kTfMaskAll = 2 };
+
+constexpr int tf_mask_query_blocks(int L) { return (L + kTfAttnTiledQueries - 1) / kTfAttnTiledQueries; }
+constexpr int tf_mask_key_blocks(int L) { return (L + kTfAttnTiledKB - 1) / kTfAttnTiledKB; }
+constexpr int tf_mask_tile_class(uint32_t cls, int wave, int step) { return (int)((cls >> (2 * (2 * wave + step))) & 3u); }
+
+// The entry of (qb, kblock) into *t; false: the block holds no allowed pair with a row of qb and is not listed
+inline bool tf_mask_tile_of(const uint32_t* bits, int L, int qb, int kblock, TfMaskTile* t) {
+  const int nw = tf_mask_words(L);
+  t->kblock = kblock; t->colany_lo = t->colany_hi = t->cls = 0;
+  for (int w = 0; w < kTfAttnTiledQueries / 32; ++w)
+    for (int s = 0; s < kTfAttnTiledKB / 32; ++s) {
+      const int word = 2 * kblock + s, r0 = qb * kTfAttnTiledQueries + 32 * w;
+      if (word >= nw || r0 >= L) continue;                                   // no key or no row below L: none
+      const uint32_t valid = word == nw - 1 && (L & 31) ? (1u << (L & 31)) - 1u : ~0u;
+      uint32_t any = 0, all = ~0u;
+      for (int r = r0; r < r0 + 32 && r < L; ++r) { const uint32_t m = bits[(size_t)r * nw + word] & valid; any |= m; all &= m; }
+      (s ? t->colany_hi : t->colany_lo) |= any;
+      t->cls |= (uint32_t)(!any ? kTfMaskNone : all == valid ? kTfMaskAll : kTfMaskSome) << (2 * (2 * w + s));
+    }
+  return (t->colany_lo | t->colany_hi) != 0;
+}
+
+// start: nqb + 1 ints, written always; tiles: the entries, or NULL to count them.  Returns start[nqb], the number of entries.
+inline long long tf_mask_tiles_build(const uint32_t* bits, int L, int* start, TfMaskTile* tiles) {
+  const int nqb = tf_mask_query_blocks(L), nkb = tf_mask_key_blocks(L);
+  int n = 0;
+  for (int qb = 0; qb < nqb; ++qb) {
+    start[qb] = n;
+    for (int kblock = 0; kblock < nkb; ++kblock) {
+      TfMaskTile t;
+      if (!tf_mask_tile_of(bits, L, qb, kblock, &t)) continue;
+      if (tiles) tiles[n] = t;
+      ++n;
+    }
+  }
+  start[nqb] = n;
+  return n;
+}
+
+// Entries of the list tiles[begin .. end - 1] a sequence of n tokens walks: those with 64 kblock < n, a prefix of the ascending list
+inline int tf_mask_tiles_corner(const TfMaskTile* tiles, int begin, int end, int n) {
+  int c = 0;
+  while (begin + c < end && (long long)tiles[begin + c].kblock * kTfAttnTiledKB < n) ++c;
+  return c;
+}
+
+// The mask word a lane of tf_attn_tiled_masked loads in a "some" step: row min(query, n - 1) of the sequence of n <= L tokens, the
+// word of the step that starts at key kb < n (a multiple of 32) -- an index into bits [L][tf_mask_words(L)]
+inline size_t tf_mask_lane_word(int L, int n, int query, int kb) { return (size_t)(query < n ? query : n - 1) * tf_mask_words(L) + (size_t)(kb >> 5); }
+// ... and the bit of that word that belongs to the key of accumulator element q = 0 .. 3 of S^T tile u = 0 .. 1 in lane group g = 0 .. 3:
+// key kb + 16 u + 4 g + q (tf_attn16_step)
+constexpr int tf_mask_lane_bit(int u, int g, int q) { return u * 16 + g * 4 + q; }
+
+// What flope_tf_mask_tiles reports: the lists' total, and the 8 (wave, step) tiles of every listed entry by class
+struct TfMaskTileStats { int query_blocks; long long blocks_listed, steps_none, steps_some, steps_all; };
+inline TfMaskTileStats tf_mask_tile_stats(int L, const int* start, const TfMaskTile* tiles) {
+  TfMaskTileStats st = {tf_mask_query_blocks(L), 0, 0, 0, 0};
+  st.blocks_listed = start[st.query_blocks];
+  for (long long i = 0; i < st.blocks_listed; ++i)
+    for (int k = 0; k < 8; ++k) {
+      const int c = tf_mask_tile_class(tiles[i].cls, k >> 1, k & 1);
+      ++(c == kTfMaskNone ? st.steps_none : c == kTfMaskSome ? st.steps_some : st.steps_all);
+    }
+  return st;
+}
+
+// One device allocation holds bits | first | last | start | tiles; the entries start on a 16-byte boundary
+inline size_t tf_mask_dev_start_at(int L) { return ((size_t)L * tf_mask_words(L) + 2 * (size_t)L) * 4; }
+inline size_t tf_mask_dev_tiles_at(int L) { return (tf_mask_dev_start_at(L) + ((size_t)tf_mask_query_blocks(L) + 1) * 4 + 15) / 16 * 16; }
+inline size_t tf_mask_dev_bytes(int L, long long entries) { return tf_mask_dev_tiles_at(L) + (size_t)entries * sizeof(TfMaskTile); }
+
+// The kernel a masked 16-bit launch takes: tf_attn_tiled_masked for a 16-bit handle under option mask_mfma = 1 (generic = 0) at every
+// head_dim tf_attn_tiled serves, whatever option attn_tiled says (head_dim 64 at L <= 512 included); tf_attn_masked otherwise.
+inline int tf_attn_pick_masked(int dtype, int head_dim, int opt_generic, int opt_mask_mfma, int aligned16) {
+  if (dtype != FLOPE_DT_F32 && opt_mask_mfma == 1 && !opt_generic && tf_attn_tiled_ok(head_dim) && aligned16) return FLOPE_TF_ATTN_MASKED16;
+  return FLOPE_TF_ATTN_MASKED;
+}
+// Grid, block and LDS of tf_attn_tiled_masked: tf_attn_tiled's, sized by the longest sequence; no mask rows in LDS
+inline TfAttnLaunch tf_mask16_launch(int head_dim, int B, int H, int max_len) {
+  return tf_attn_varlen_launch(FLOPE_TF_ATTN_TILED, head_dim, B, H, max_len);
 }
 
 }  // namespace flope_tf_plan

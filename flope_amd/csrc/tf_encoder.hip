@@ -34,6 +34,9 @@
 // sequence with tf_attn_masked where the forward has its attention kernel, for every shape: a softmax over exactly the allowed keys in the
 // generic kernel's order, a masked key never loaded; never the single launch, options causal / window neither read nor written (the host
 // side is tf_attn_mask.h).
+// Option mask_mfma = 1 (16-bit handles): a masked launch runs tf_attn_tiled_masked where tf_attn_pick_masked says so --
+// tf_attn_tiled's ring and tf_attn16_step's MASKED form over the key blocks of the mask's tile map, which every mask carries beside its
+// bits; tf_attn_tiled's bits where the mask is all-clear, causal, a causal band or block-diagonal at multiples of 32.
 #include "../../include/flope_amd.h"
 #include "common.h"
 #include "host_pack.h"
@@ -1084,11 +1087,19 @@ template <int HD32> __device__ __forceinline__ TfAttn16Lane tf_attn16_lane(int l
 // takes, so lrun > 0 at the store for every stored query.  A query at or past L is clamped for its Q rows only, its mask uses the
 // unclamped index: all its visible keys may lie at or past L and it may end with lrun = 0 and 1 / lrun = inf -- it is not stored
 // (tf_attn16_store's qi < L) and must stay unstored.
-template <typename T, int HD32, bool CAUSAL = false, bool WINDOW = false>
+// MASKED (without CAUSAL and WINDOW, option mask_mfma): mw[qt] is the word of the compiled mask that belongs to the lane's
+// query of tile qt and to this step -- bit j = key kb + j is allowed, kb a multiple of 32 -- and a key also has to have its bit set: the
+// key of accumulator element q of S^T tile u in lane group g is kb + 16 u + 4 g + q, so its bit is 16 u + 4 g + q
+// (flope_tf_plan::tf_mask_lane_bit).  Which steps a wave takes is its kernel's business again (the classes of the tile map), and as
+// under WINDOW a query may see nothing in a step its wave takes, its first one included: the same msafe keeps its state at exactly 0
+// until its first own key.  Every stored query has a key in a step its wave takes (the host refuses a row without one), so lrun > 0 at
+// the store; a query at or past L takes the word of row L - 1 or ~0 and is not stored.
+template <typename T, int HD32, bool CAUSAL = false, bool WINDOW = false, bool MASKED = false>
 __device__ __forceinline__ void tf_attn16_step(const char* Ki, const char* Vi, int kb, int kl, int L, int q0, float scale_log2e,
                                                const TfAttn16Lane& ln, const typename Elem<T>::frag (&qf)[2][HD32], float (&mrun)[2],
-                                               float (&lrun)[2], f32x4 (&o)[2][2 * HD32], int W = 0) {
+                                               float (&lrun)[2], f32x4 (&o)[2][2 * HD32], int W = 0, const uint32_t* mw = nullptr) {
   static_assert(CAUSAL || !WINDOW, "a window without causal has no meaning");
+  static_assert(!MASKED || (!CAUSAL && !WINDOW), "a compiled mask says everything itself");
   typedef typename Elem<T>::frag frag;
   constexpr int RB = 64 * HD32;
   const int g = ln.g, li = ln.li, ksw = ln.ksw, trp = ln.trp, vrow = ln.vrow, vsw = ln.vsw;
@@ -1118,6 +1129,7 @@ __device__ __forceinline__ void tf_attn16_step(const char* Ki, const char* Vi, i
         bool seen = key < L;
         if constexpr (CAUSAL) seen = seen && key <= q0 + qt * 16 + li;
         if constexpr (WINDOW) seen = seen && key > q0 + qt * 16 + li - W;      // key + W > query, without the overflow of a huge W
+        if constexpr (MASKED) seen = seen && ((mw[qt] >> (u * 16 + g * 4 + q)) & 1u);
         const float x = seen ? s[u][qt][q] * scale_log2e : -INFINITY;
         v[u * 4 + q] = x;
         mx = fmaxf(mx, x);
@@ -1126,7 +1138,7 @@ __device__ __forceinline__ void tf_attn16_step(const char* Ki, const char* Vi, i
     mx = fmaxf(mx, __shfl_xor(mx, 32));
     const float mnew = fmaxf(mrun[qt], mx);
     float msafe = mnew;
-    if constexpr (WINDOW) msafe = mnew == -INFINITY ? 0.f : mnew;
+    if constexpr (WINDOW || MASKED) msafe = mnew == -INFINITY ? 0.f : mnew;
     const float alpha = __builtin_amdgcn_exp2f(mrun[qt] - msafe);
     float ps = 0.f;
 #pragma unroll
@@ -1369,6 +1381,134 @@ __global__ __launch_bounds__(256, 2) void tf_attn_tiled(const T* __restrict__ qk
       tf_attn16_step<T, HD32, CAUSAL>(Ki, Vi, kb, kl, L, q0, scale_log2e, ln, qf, mrun, lrun, o);
     }
     lwrite((t + 1) & 1);
+  }
+  tf_attn16_store<T, HD32>(out, VARLEN ? row0 : (size_t)b * L, d, h * HD, q0, L, lane, lrun, o);
+}
+
+// tf_attn_tiled_masked (option mask_mfma): tf_attn_tiled under a compiled mask.  Workgroup, waves, grid, LDS ring, register
+// staging, swizzles, the one barrier per trip and the store are tf_attn_tiled's; what differs is which key blocks a workgroup loads and
+// which steps a wave takes, both read from the mask's tile map (tf_attn_mask.h: start, tiles).
+// Trips: the barrier loop runs over the entries of the workgroup's query block, tiles[start[qb]] .. tiles[start[qb + 1] - 1] (VARLEN: the
+// prefix with 64 kblock < the sequence's own length), a count every wave of the workgroup shares: one load, LDS-write and barrier count.
+// The list may skip blocks, so a trip's ring stage is its trip index & 1, not its block index.  The prefetch of the trip past the end
+// loads the rows of the last entry again, as zeros, into a stage nobody reads.
+// Staging: the rows of entry (kblock, colany); a row at or past L is clamped to row L - 1 and staged as zeros, and so is a row whose colany
+// bit is clear, in K and in V: NaN or Inf in a key that no query of the sequence allows reaches no output (0 x NaN in the PV product
+// would be NaN).  The scope is the 128-row query block: a key allowed by SOME query of the block is staged as it is, and if it holds NaN
+// the rows of that block that mask it get 0 x NaN.
+// Steps: a wave reads its class of the step from the entry (wave-uniform).  kTfMaskNone and a step at or past L: the uniform `continue` of
+// the causal skip.  kTfMaskAll: mw = ~0 without a load.  kTfMaskSome: the lane loads word kb / 32 of row min(query, L - 1) of the mask
+// for its two query tiles -- query and L are the sequence's own, so no word outside the mask is read -- in front of the step's MFMAs.
+// Every stored query has a key in a taken step, so lrun > 0 at the store (tf_mask_length_row under VARLEN).
+template <typename T, int HD32, bool VARLEN = false>
+__global__ __launch_bounds__(256, 2) void tf_attn_tiled_masked(const T* __restrict__ qkv, T* __restrict__ out, int L, int d, int H,
+                                                               float scale_log2e, const int* __restrict__ off, int mwords,
+                                                               const uint32_t* __restrict__ bits, const int* __restrict__ start,
+                                                               const flope_tf_plan::TfMaskTile* __restrict__ tiles) {
+  typedef typename Elem<T>::frag frag;
+  constexpr int HD = 32 * HD32, RB = 64 * HD32, NCH = 4 * HD32;     // head_dim, bytes and 16-byte chunks of a row
+  constexpr int KB = flope_tf_plan::kTfAttnTiledKB, BLK = KB * RB, STAGE = 2 * BLK;
+  static_assert(flope_tf_plan::kTfAttnTiledRing == 2 && KB == 64, "the loop below is written for two stages of two 32-key steps");
+  extern __shared__ __attribute__((aligned(16))) char smem[];      // [2 stages][K block [64][RB] | V block [64][RB]]
+  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), g = lane >> 4, li = lane & 15;
+  const int b = blockIdx.x / H, h = blockIdx.x - b * H;
+  size_t row0 = 0;
+  if constexpr (VARLEN) {
+    row0 = (size_t)off[b]; L = off[b + 1] - off[b];
+    if ((int)blockIdx.y * flope_tf_plan::kTfAttnTiledQueries >= L) return;
+  }
+  const T* base = VARLEN ? qkv + row0 * 3 * d + h * HD : qkv + (size_t)b * L * 3 * d + h * HD;
+  const int e0 = start[blockIdx.y];
+  int e1 = start[blockIdx.y + 1];
+  if constexpr (VARLEN) { while (e1 - 1 > e0 && tiles[e1 - 1].kblock * KB >= L) --e1; }      // the corner's prefix; its first entry always stays
+
+  // staging role: HD32 chunks of K and of V per thread and block
+  int srow[HD32], ssrc[HD32], sdk[HD32], sdv[HD32];
+#pragma unroll
+  for (int i = 0; i < HD32; ++i) {
+    const int idx = tid + i * 256, row = idx / NCH, ch = idx - row * NCH;
+    srow[i] = row;
+    ssrc[i] = ch * 8;
+    sdk[i] = row * RB + ((ch ^ tf_tiled_kswz<HD32>(row)) << 4);
+    sdv[i] = BLK + row * RB + ((ch ^ tf_tiled_vswz<HD32>(row)) << 4);
+  }
+  u32x4 kr[HD32], vr[HD32];
+  auto gload = [&](int kb0, uint32_t clo, uint32_t chi) {
+#pragma unroll
+    for (int i = 0; i < HD32; ++i) {
+      const int row = kb0 + srow[i];
+      const T* src = base + (size_t)(row < L ? row : L - 1) * 3 * d + ssrc[i];
+      const u32x4 kv = *(const u32x4*)(src + d), vv = *(const u32x4*)(src + 2 * d);
+      const u32x4 z = {0, 0, 0, 0};
+      const bool keep = row < L && (((srow[i] < 32 ? clo : chi) >> (srow[i] & 31)) & 1u);
+      kr[i] = keep ? kv : z;
+      vr[i] = keep ? vv : z;
+    }
+  };
+  auto lwrite = [&](int stage) {
+    char* s = smem + stage * STAGE;
+#pragma unroll
+    for (int i = 0; i < HD32; ++i) {
+      *(u32x4*)(s + sdk[i]) = kr[i];
+      *(u32x4*)(s + sdv[i]) = vr[i];
+    }
+  };
+  // the entry of a trip, the same for every lane
+  auto entry = [&](int e, int& kblock, uint32_t& clo, uint32_t& chi, uint32_t& cls) {
+    const flope_tf_plan::TfMaskTile t = tiles[e];
+    kblock = __builtin_amdgcn_readfirstlane(t.kblock);
+    clo = (uint32_t)__builtin_amdgcn_readfirstlane((int)t.colany_lo);
+    chi = (uint32_t)__builtin_amdgcn_readfirstlane((int)t.colany_hi);
+    cls = (uint32_t)__builtin_amdgcn_readfirstlane((int)t.cls);
+  };
+  int kblock, nkblock;
+  uint32_t clo, chi, cls, nclo, nchi, ncls;
+  entry(e0, kblock, clo, chi, cls);
+  gload(kblock * KB, clo, chi);
+  lwrite(0);
+
+  const int q0 = blockIdx.y * flope_tf_plan::kTfAttnTiledQueries + wave * 32;
+  frag qf[2][HD32];
+  int mrow[2];                                   // the lane's two rows of the mask, in words
+#pragma unroll
+  for (int qt = 0; qt < 2; ++qt) {
+    int qi = q0 + qt * 16 + li;
+    qi = qi < L ? qi : L - 1;
+    mrow[qt] = qi * mwords;
+#pragma unroll
+    for (int ks = 0; ks < HD32; ++ks) qf[qt][ks] = *(const frag*)(base + (size_t)qi * 3 * d + (ks * 4 + g) * 8);
+  }
+  float mrun[2] = {-INFINITY, -INFINITY}, lrun[2] = {0.f, 0.f};
+  f32x4 o[2][2 * HD32];
+#pragma unroll
+  for (int qt = 0; qt < 2; ++qt)
+#pragma unroll
+    for (int dt = 0; dt < 2 * HD32; ++dt) o[qt][dt] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+  const TfAttn16Lane ln = tf_attn16_lane<HD32>(lane);
+  for (int e = e0; e < e1; ++e) {
+    const int trip = e - e0;
+    if (e + 1 < e1) entry(e + 1, nkblock, nclo, nchi, ncls);
+    else { nkblock = kblock; nclo = nchi = ncls = 0; }      // past the last entry: its rows again, zeros, a stage nobody reads
+    gload(nkblock * KB, nclo, nchi);
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    BLOCK_BARRIER();
+    const char* Ki = smem + (trip & 1) * STAGE;
+    const char* Vi = Ki + BLK;
+#pragma unroll
+    for (int st = 0; st < KB / 32; ++st) {
+      const int kl = st * 32, kb = kblock * KB + kl;
+      const int c = flope_tf_plan::tf_mask_tile_class(cls, wave, st);      // per wave, uniform
+      if (kb >= L || c == flope_tf_plan::kTfMaskNone) continue;            // uniform: EXEC stays all ones
+      uint32_t mw[2] = {~0u, ~0u};
+      if (c == flope_tf_plan::kTfMaskSome) {
+#pragma unroll
+        for (int qt = 0; qt < 2; ++qt) mw[qt] = bits[mrow[qt] + (kb >> 5)];
+      }
+      tf_attn16_step<T, HD32, false, false, true>(Ki, Vi, kb, kl, L, q0, scale_log2e, ln, qf, mrun, lrun, o, 0, mw);
+    }
+    lwrite((trip + 1) & 1);
+    kblock = nkblock; clo = nclo; chi = nchi; cls = ncls;
   }
   tf_attn16_store<T, HD32>(out, VARLEN ? row0 : (size_t)b * L, d, h * HD, q0, L, lane, lrun, o);
 }
@@ -1840,7 +1980,9 @@ struct flope_tf_encoder {
   int opt_window = 0;                        // W > 0 (honoured with opt_causal = 1, refused without): keys i - W < j <= i, on tf_attn_generic unless opt_window_mfma, never tf_fused_f32
   int opt_window_mfma = 0;                   // 1: under causal with a window a 16-bit launch keeps tf_attn_pick's tf_attn_mfma / tf_attn_tiled, their WINDOW instantiations (stored and ignored by float32 handles)
   int opt_step_split = 0;                    // 1: flope_tf_stream_step / _extend split a token's keys over the four waves of a workgroup where tf_step_split_ok (every dtype)
+  int opt_mask_mfma = 0;                     // 1: a 16-bit launch under a compiled mask is tf_attn_tiled_masked where tf_attn_pick_masked says so (stored and ignored by float32 handles)
   int opt_extend_mfma = 0;                   // 1: flope_tf_stream_extend's attention is tf_attn16_extend where tf_extend_mfma_ok (stored and ignored by float32 handles); wins over opt_step_split for _extend only
+  int last_masked_attn = -1;                 // FLOPE_TF_ATTN_* id of the attention launches of the last flope_tf_forward_masked that enqueued anything (flope_tf_last_forward_masked), -1: none yet
   int last_fwd = FLOPE_TF_FWD_LAUNCHES;       // what the last forward that enqueued anything ran (flope_tf_last_forward)
   const float** fused_tab = nullptr;         // device table of the float32 weight arrays tf_fused_f32 reads (FLOPE_DT_F32 handles, built by flope_tf_load_weights)
   int opt_f32m_lds = 0;                      // KiB of untouched LDS a tf_linear_f32m launch reserves (> 80: one workgroup per CU)
@@ -1873,18 +2015,22 @@ struct flope_tf_stream_s {
   std::vector<char> seen;                    // scratch of the argument checks
 };
 
-// A compiled attention mask (flope_tf_mask_*; tf_attn_mask.h): one device allocation bits | first | last, and the host
-// copies the per-call checks and the FLOP count read.
+// A compiled attention mask (flope_tf_mask_*; tf_attn_mask.h): one device allocation bits | first | last | start |
+// tiles, and the host copies the per-call checks, the FLOP count and flope_tf_mask_tiles read.
 struct flope_tf_mask {
   flope_tf_encoder* e = nullptr;             // nullptr once the handle is destroyed: every call but destroy then fails with FLOPE_ESTATE
   int L = 0;
   long long pairs = 0;
-  void* dev = nullptr;                       // uint32 bits [L][words] | int first [L] | int last [L]
+  void* dev = nullptr;                       // uint32 bits [L][words] | int first [L] | int last [L] | int start [nqb + 1] | TfMaskTile tiles [start[nqb]]
   std::vector<uint32_t> bits;
   std::vector<int> first, last;
+  std::vector<int> start;                    // the tile map (tf_attn_mask.h), built for every mask: option mask_mfma may be flipped between forwards
+  std::vector<flope_tf_plan::TfMaskTile> tiles;
   const uint32_t* bits_dev() const { return (const uint32_t*)dev; }
   const int* first_dev() const { return (const int*)(bits_dev() + bits.size()); }
   const int* last_dev() const { return first_dev() + L; }
+  const int* start_dev() const { return (const int*)((const char*)dev + flope_tf_plan::tf_mask_dev_start_at(L)); }
+  const flope_tf_plan::TfMaskTile* tiles_dev() const { return (const flope_tf_plan::TfMaskTile*)((const char*)dev + flope_tf_plan::tf_mask_dev_tiles_at(L)); }
 };
 
 namespace {
@@ -2310,6 +2456,11 @@ extern "C" int flope_tf_create(int device_id, int input_dim, int model_dim, int 
     for (const void* f : ext16)
       if (hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)flope_tf_plan::tf_attn_tiled_lds(128)) != hipSuccess)
         return fin(tf_fail(nullptr, FLOPE_EHIP, "flope_tf_create: hipFuncSetAttribute failed"));
+    const void* const masked16[] = {(const void*)tf_attn_tiled_masked<f16_t, 4>, (const void*)tf_attn_tiled_masked<bf16_t, 4>,
+                                    (const void*)tf_attn_tiled_masked<f16_t, 4, true>, (const void*)tf_attn_tiled_masked<bf16_t, 4, true>};
+    for (const void* f : masked16)
+      if (hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)flope_tf_plan::tf_attn_tiled_lds(128)) != hipSuccess)
+        return fin(tf_fail(nullptr, FLOPE_EHIP, "flope_tf_create: hipFuncSetAttribute failed"));
     const void* const masked[] = {(const void*)tf_attn_masked<float, false>, (const void*)tf_attn_masked<float, true>, (const void*)tf_attn_masked<f16_t, false>,
                                   (const void*)tf_attn_masked<f16_t, true>, (const void*)tf_attn_masked<bf16_t, false>, (const void*)tf_attn_masked<bf16_t, true>};
     for (const void* f : masked)                     // four score rows of up to max_tokens floats and the mask words behind them
@@ -2360,6 +2511,10 @@ extern "C" int flope_tf_set_option(flope_tf_handle e, const char* name, int valu
   if (!strcmp(name, "window_mfma")) {
     if (value < 0 || value > 1) return tf_fail(e, FLOPE_EINVAL, "flope_tf_set_option: window_mfma is 0 or 1");
     const int old = e->opt_window_mfma; e->opt_window_mfma = value; return old;
+  }
+  if (!strcmp(name, "mask_mfma")) {
+    if (value < 0 || value > 1) return tf_fail(e, FLOPE_EINVAL, "flope_tf_set_option: mask_mfma is 0 or 1");
+    const int old = e->opt_mask_mfma; e->opt_mask_mfma = value; return old;
   }
   if (!strcmp(name, "step_split")) {
     if (value < 0 || value > 1) return tf_fail(e, FLOPE_EINVAL, "flope_tf_set_option: step_split is 0 or 1");
@@ -2628,10 +2783,33 @@ extern "C" double flope_tf_forward_flops_varlen(flope_tf_handle e, int batch, co
 // ---- attention under a compiled mask ------------------------------------------------------------------------------------
 namespace {
 
-// The masked attention launch: tf_attn_masked for every dtype and head_dim, launched as the generic kernel always is plus the mask rows
-// in LDS (tf_mask_launch).  off == nullptr: qkv [B][L][3 d], L == m->L; otherwise the packed rows of a ragged batch, L its longest length.
+// The masked attention launch, tf_attn_pick_masked's answer: tf_attn_masked for every dtype and head_dim, launched as the generic kernel
+// always is plus the mask rows in LDS (tf_mask_launch), unless option mask_mfma sends a 16-bit launch to tf_attn_tiled_masked, launched
+// as tf_attn_tiled is (tf_mask16_launch).  off == nullptr: qkv [B][L][3 d], L == m->L; otherwise the packed rows of a ragged batch, L
+// its longest length.  Returns the kernel's FLOPE_TF_ATTN_* id, or < 0.
+int tf_masked_pick(const flope_tf_encoder* e, const void* qkv, const void* att) {
+  return flope_tf_plan::tf_attn_pick_masked(e->dtype, e->d / e->H, e->opt_generic, e->opt_mask_mfma, !(((uintptr_t)qkv | (uintptr_t)att) & 15));
+}
 template <typename T>
 int launch_attention_masked(flope_tf_encoder* e, const flope_tf_mask* m, const void* qkv, void* att, int B, int L, const int* off, hipStream_t st) {
+  if constexpr (!std::is_same<T, float>::value) {
+    if (tf_masked_pick(e, qkv, att) == FLOPE_TF_ATTN_MASKED16) {
+      const int dh = e->d / e->H;
+      const flope_tf_plan::TfAttnLaunch l = flope_tf_plan::tf_mask16_launch(dh, B, e->H, L);
+      const dim3 grid(l.grid_x, l.grid_y), block(l.block);
+      const float scale_log2e = 1.4426950408889634f / sqrtf((float)dh);
+      auto launch = [&](auto varlen) {
+        constexpr bool VL = decltype(varlen)::value;
+#define TF_ATT(HD32_) hipLaunchKernelGGL((tf_attn_tiled_masked<T, HD32_, VL>), grid, block, l.lds, st, (const T*)qkv, (T*)att, L, e->d, e->H, scale_log2e, off, \
+                                         flope_tf_plan::tf_mask_words(m->L), m->bits_dev(), m->start_dev(), m->tiles_dev())
+        if (dh == 32) TF_ATT(1); else if (dh == 64) TF_ATT(2); else if (dh == 96) TF_ATT(3); else TF_ATT(4);
+#undef TF_ATT
+      };
+      if (off) launch(std::true_type{}); else launch(std::false_type{});
+      TF_HIP(e, hipGetLastError());
+      return FLOPE_TF_ATTN_MASKED16;
+    }
+  }
   const flope_tf_plan::TfAttnLaunch l = flope_tf_plan::tf_mask_launch(e->d / e->H, B, e->H, L, m->L);
   const dim3 grid(l.grid_x, l.grid_y), block(l.block);
   if (off)
@@ -2646,7 +2824,7 @@ int launch_attention_masked(flope_tf_encoder* e, const flope_tf_mask* m, const v
 // seq_len tokens.  Otherwise the ragged batch is planned into off_host (batch + 1 ints) and *rg, and every length n is held against
 // the mask's n x n corner.
 int tf_masked_check(flope_tf_encoder* e, const std::string& who, const flope_tf_mask* m, int batch, int seq_len, const int* lengths, int* off_host,
-                    TfRagged* rg) {
+                    TfRagged* rg, const void* qkv, const void* att) {
   if (!e) return tf_fail(nullptr, FLOPE_EINVAL, who + ": NULL handle");
   if (!m) return tf_fail(e, FLOPE_EINVAL, who + ": NULL mask");
   if (!m->e) return tf_fail(e, FLOPE_ESTATE, who + ": the encoder handle of this mask has been destroyed");
@@ -2667,7 +2845,8 @@ int tf_masked_check(flope_tf_encoder* e, const std::string& who, const flope_tf_
     }
     max_len = rg->max_len;
   }
-  if (flope_tf_plan::tf_mask_launch(e->d / e->H, batch, e->H, max_len, m->L).lds > flope_tf_plan::kTfAttnLds)
+  if (tf_masked_pick(e, qkv, att) == FLOPE_TF_ATTN_MASKED &&           // tf_attn_tiled_masked keeps no row in LDS
+      flope_tf_plan::tf_mask_launch(e->d / e->H, batch, e->H, max_len, m->L).lds > flope_tf_plan::kTfAttnLds)
     return tf_fail(e, FLOPE_EINVAL, who + ": seq_len too long for the score rows of one workgroup");
   return 0;
 }
@@ -2695,13 +2874,18 @@ extern "C" int flope_tf_mask_create(flope_tf_handle e, int seq_len, const uint32
   m->last.resize(seq_len);
   tf_mask_first_last(m->bits.data(), seq_len, m->first.data(), m->last.data());
   m->pairs = tf_mask_pairs(m->bits.data(), seq_len);
-  const size_t nb = m->bits.size() * sizeof(uint32_t), nt = (size_t)seq_len * sizeof(int);
+  m->start.resize((size_t)tf_mask_query_blocks(seq_len) + 1);
+  m->tiles.resize((size_t)tf_mask_tiles_build(m->bits.data(), seq_len, m->start.data(), nullptr));
+  tf_mask_tiles_build(m->bits.data(), seq_len, m->start.data(), m->tiles.data());
+  const size_t nb = m->bits.size() * sizeof(uint32_t), nt = (size_t)seq_len * sizeof(int), all = tf_mask_dev_bytes(seq_len, (long long)m->tiles.size());
   auto fin = [&](const std::string& what) { hipFree(m->dev); delete m; return tf_fail(e, FLOPE_EHIP, who + ": " + what); };
   if (hipSetDevice(e->device) != hipSuccess) return fin("hipSetDevice failed");
-  if (hipMalloc(&m->dev, nb + 2 * nt) != hipSuccess) { m->dev = nullptr; return fin("hipMalloc of " + std::to_string(nb + 2 * nt) + " bytes failed"); }
+  if (hipMalloc(&m->dev, all) != hipSuccess) { m->dev = nullptr; return fin("hipMalloc of " + std::to_string(all) + " bytes failed"); }
   if (hipMemcpy(m->dev, m->bits.data(), nb, hipMemcpyHostToDevice) != hipSuccess ||
       hipMemcpy((char*)m->dev + nb, m->first.data(), nt, hipMemcpyHostToDevice) != hipSuccess ||
-      hipMemcpy((char*)m->dev + nb + nt, m->last.data(), nt, hipMemcpyHostToDevice) != hipSuccess)
+      hipMemcpy((char*)m->dev + nb + nt, m->last.data(), nt, hipMemcpyHostToDevice) != hipSuccess ||
+      hipMemcpy((char*)m->dev + tf_mask_dev_start_at(seq_len), m->start.data(), m->start.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess ||
+      hipMemcpy((char*)m->dev + tf_mask_dev_tiles_at(seq_len), m->tiles.data(), m->tiles.size() * sizeof(TfMaskTile), hipMemcpyHostToDevice) != hipSuccess)
     return fin("hipMemcpy failed");
   m->e = e;
   e->masks.push_back(m);
@@ -2729,6 +2913,19 @@ extern "C" int flope_tf_mask_info(flope_tf_mask_handle m, int* seq_len, long lon
   return FLOPE_OK;
 }
 
+extern "C" int flope_tf_mask_tiles(flope_tf_mask_handle m, int* query_blocks, long long* blocks_listed, long long* steps_none, long long* steps_some,
+                                   long long* steps_all) {
+  if (!m) return tf_fail(nullptr, FLOPE_EINVAL, "flope_tf_mask_tiles: NULL mask");
+  if (!m->e) return tf_fail(nullptr, FLOPE_ESTATE, "flope_tf_mask_tiles: the encoder handle of this mask has been destroyed");
+  const flope_tf_plan::TfMaskTileStats st = flope_tf_plan::tf_mask_tile_stats(m->L, m->start.data(), m->tiles.data());
+  if (query_blocks) *query_blocks = st.query_blocks;
+  if (blocks_listed) *blocks_listed = st.blocks_listed;
+  if (steps_none) *steps_none = st.steps_none;
+  if (steps_some) *steps_some = st.steps_some;
+  if (steps_all) *steps_all = st.steps_all;
+  return FLOPE_OK;
+}
+
 extern "C" int flope_tf_forward_masked(flope_tf_handle e, const float* x_dev, int batch, int seq_len, const int* lengths_host, flope_tf_mask_handle m,
                                        float* y_dev, void* stream) {
   const std::string who = "flope_tf_forward_masked";
@@ -2736,7 +2933,7 @@ extern "C" int flope_tf_forward_masked(flope_tf_handle e, const float* x_dev, in
   if (!x_dev || !y_dev) return tf_fail(e, FLOPE_EINVAL, who + ": NULL buffer");
   TfRagged rg;
   int rc;
-  if ((rc = tf_masked_check(e, who, m, batch, seq_len, lengths_host, e->vl_host.data(), &rg))) return rc;
+  if ((rc = tf_masked_check(e, who, m, batch, seq_len, lengths_host, e->vl_host.data(), &rg, e->qkv, e->att))) return rc;
   if (!e->loaded) return tf_fail(e, FLOPE_ESTATE, who + ": weights not loaded");
   if (lengths_host && (rc = tf_check_forward_varlen(e, who, batch, seq_len, true))) return rc;
   TF_HIP(e, hipSetDevice(e->device));
@@ -2747,9 +2944,14 @@ extern "C" int flope_tf_forward_masked(flope_tf_handle e, const float* x_dev, in
   return tf_by_dtype(e, [&](auto tag) {
     using T = typename decltype(tag)::type;
     return run_forward_with<T>(e, x_dev, batch, seq_len, y_dev, st, rgp, [&](int) {
-      return launch_attention_masked<T>(e, m, e->qkv, e->att, batch, rgp ? rg.max_len : seq_len, rgp ? e->vl_off : nullptr, st);
+      return e->last_masked_attn = launch_attention_masked<T>(e, m, e->qkv, e->att, batch, rgp ? rg.max_len : seq_len, rgp ? e->vl_off : nullptr, st);
     });
   });
+}
+
+extern "C" int flope_tf_last_forward_masked(flope_tf_handle e) {
+  if (!e) return tf_fail(nullptr, FLOPE_EINVAL, "flope_tf_last_forward_masked: NULL handle");
+  return e->last_masked_attn;
 }
 
 extern "C" int flope_tf_attention_masked(flope_tf_handle e, const void* qkv_dev, int batch, int seq_len, const int* lengths_host, flope_tf_mask_handle m,
@@ -2760,7 +2962,7 @@ extern "C" int flope_tf_attention_masked(flope_tf_handle e, const void* qkv_dev,
   if (((uintptr_t)qkv_dev | (uintptr_t)out_dev) & (uintptr_t)(e->esz - 1)) return tf_fail(e, FLOPE_EINVAL, who + ": buffer not aligned to its element type");
   TfRagged rg;
   int rc;
-  if ((rc = tf_masked_check(e, who, m, batch, seq_len, lengths_host, e->vl_host.data(), &rg))) return rc;
+  if ((rc = tf_masked_check(e, who, m, batch, seq_len, lengths_host, e->vl_host.data(), &rg, qkv_dev, out_dev))) return rc;
   TF_HIP(e, hipSetDevice(e->device));
   hipStream_t st = (hipStream_t)stream;
   if (lengths_host && (rc = tf_upload_ragged(e, batch, st))) return rc;

@@ -12,7 +12,8 @@ An encoder made with `step_split=1` splits the keys of a stream's step() / exten
 A 16-bit encoder made with `extend_mfma=1` runs a stream's extend() on the MFMA attention step: the MFMA forward's rows in bits.
 Any other [L, L] mask is compiled once with `enc.make_mask(mask)` and passed as `mask=` to any number of calls: query i is a softmax over
 exactly its allowed keys, a masked key is never loaded, and a sequence of a ragged batch is encoded under the mask's top-left corner
-(DESIGN.md 37).
+(DESIGN.md 37).  A 16-bit encoder made with `mask_mfma=1` runs attention under a compiled mask on the MFMA attention step over the mask's
+tile map, loading only the 64-key blocks some query of a 128-row block allows.
 
 Eval-mode semantics only (dropout is identity), as everywhere in this package.  There is no CPU
 path: construction fails loudly without a HIP device or without the built library.
@@ -161,7 +162,8 @@ def _pack_allowed(allowed):
 
 class TransformerEncoder:
     def __init__(self, input_dim, model_dim, out_dim, num_heads, num_layers, ff_dim, dropout=0.1,
-                 dtype="f32", max_tokens=4096, device=None, attn_tiled=0, fused=0, window_mfma=0, step_split=0, extend_mfma=0):
+                 dtype="f32", max_tokens=4096, device=None, attn_tiled=0, fused=0, window_mfma=0, step_split=0, extend_mfma=0,
+                 mask_mfma=0):
         _require_gpu()
         self.lib = _lib.load()
         self.device = torch.device(device if device is not None else "cuda:0")
@@ -212,6 +214,11 @@ class TransformerEncoder:
             if rc < 0:
                 self.close()
                 raise ValueError(f"extend_mfma must be 0 or 1 (got {extend_mfma!r})")
+        if mask_mfma:                            # 16-bit handles: attention under a compiled mask runs on the MFMA step (0 or 1, include/flope_amd.h)
+            rc = self.lib.flope_tf_set_option(self.handle, b"mask_mfma", int(mask_mfma))
+            if rc < 0:
+                self.close()
+                raise ValueError(f"mask_mfma must be 0 or 1 (got {mask_mfma!r})")
 
     def _check(self, rc):
         if rc:
@@ -243,7 +250,7 @@ class TransformerEncoder:
             self._check(self.lib.flope_tf_load_weights(self.handle, n, names, ptrs, ndims, shapes))
 
     def set_option(self, name: str, value: int) -> int:
-        if name in ("step_split", "extend_mfma"):    # the newer options raise on a refused value (the others keep returning the code)
+        if name in ("step_split", "extend_mfma", "mask_mfma"):    # the newer options raise on a refused value (the others keep returning the code)
             rc = self.lib.flope_tf_set_option(self.handle, name.encode(), int(value))
             self._check_arg(rc)
             return rc
@@ -352,13 +359,15 @@ class TransformerEncoder:
         if isinstance(mask, TransformerEncoderMask):
             # a compiled mask (make_mask): any [L, L] set of allowed pairs.  Sequence b of a ragged batch is encoded
             # alone under the mask's top-left lengths[b] x lengths[b] corner.  Always the launch sequence; options "causal" and
-            # "window" are neither read nor written.
+            # "window" are neither read nor written.  On an encoder with `mask_mfma=1` a 16-bit forward runs its attention on the
+            # MFMA kernel over the mask's tile map; the id of the attention launches is kept in `last_attn_kernel`.
             self._compiled(mask, L, is_causal, window)
             y = torch.empty((B, L, self.dims[2]), dtype=torch.float32, device=self.device)
             lh = None if lengths is None else _host_lengths(lengths, B)
             with torch.cuda.device(self.device):
                 self._check_arg(self.lib.flope_tf_forward_masked(self.handle, x.data_ptr(), B, L, lh, mask.handle, y.data_ptr(), _stream_ptr(self.device)))
             self.last_forward_fused = False
+            self.last_attn_kernel = self.lib.flope_tf_last_forward_masked(self.handle)       # tf_attn_masked, or tf_attn_tiled_masked under mask_mfma
             self._keep = x
             return y
         causal, band = _mask_window(mask, L)
@@ -392,7 +401,8 @@ class TransformerEncoder:
         `window=W` (with `is_causal=True`): keys i - W < j <= i, by the generic kernel with `window_mfma=0`, by the 16-bit MFMA
         kernel the call would take without a window on a handle made with `window_mfma=1`.
         `mask` (a compiled one, make_mask): softmax over the allowed keys only, by tf_attn_masked (`last_attn_kernel` = 4) for every
-        dtype and shape; with `lengths` each sequence under the mask's corner."""
+        dtype and shape, or, on a 16-bit encoder with `mask_mfma=1` and head_dim 32 / 64 / 96 / 128, by tf_attn_tiled_masked
+        (`last_attn_kernel` = 5); with `lengths` each sequence under the mask's corner."""
         if mask is not None and not isinstance(mask, TransformerEncoderMask):
             raise ValueError("attention() takes a compiled mask (enc.make_mask), not a tensor")
         if mask is not None:
@@ -558,7 +568,9 @@ class TransformerEncoder:
 class TransformerEncoderMask:
     """An [L, L] attention mask compiled for one encoder (include/flope_amd.h: flope_tf_mask_*): the allowed (query, key)
     pairs as bits on the device, made once by `enc.make_mask(mask)` and passed as `mask=` to any number of forwards.  `L`: the
-    sequence length it was made for; `allowed`: the number of allowed pairs.  It keeps its encoder alive; after enc.close() or its own
+    sequence length it was made for; `allowed`: the number of allowed pairs; `tile_stats`: what option `mask_mfma` walks,
+    a dict of query_blocks (of 128 rows), blocks_listed (64-key blocks over all of them) and steps_none / steps_some / steps_all (the 8
+    (wave, 32-key step) tiles of every listed block by class).  It keeps its encoder alive; after enc.close() or its own
     close() its use raises RuntimeError."""
 
     def __init__(self, enc: TransformerEncoder, mask):
@@ -577,6 +589,9 @@ class TransformerEncoderMask:
         n, pairs = C.c_int(), C.c_longlong()
         enc._check_arg(enc.lib.flope_tf_mask_info(self.handle, C.byref(n), C.byref(pairs)))
         self.allowed = int(pairs.value)
+        qb, st = C.c_int(), [C.c_longlong() for _ in range(4)]
+        enc._check_arg(enc.lib.flope_tf_mask_tiles(self.handle, C.byref(qb), *[C.byref(v) for v in st]))
+        self.tile_stats = dict(zip(("query_blocks", "blocks_listed", "steps_none", "steps_some", "steps_all"), [int(qb.value)] + [int(v.value) for v in st]))
 
     def _live(self):
         if not self.enc.handle.value:

@@ -395,7 +395,18 @@ int flope_tf_forward(flope_tf_handle h, const float* x_dev, int batch, int seq_l
  *       one of the 32-key steps its wave of 32 chunk rows takes (those from the step of the wave's first query's first visible key
  *       to the step of its last query), at or above the first key its workgroup of 128 chunk rows sees and below position + length
  *       -- a key below the query's own window, or a later token of the same chunk, included.  Fed one token per call, a ring
- *       forgets NaN tokens as fast as under option 0. */
+ *       forgets NaN tokens as fast as under option 0;
+ *   "mask_mfma" (default 0; 0 or 1, FLOPE_EINVAL outside; returns the old value; stored and ignored by float32 handles): 1 = attention
+ *       under a compiled mask (flope_tf_forward_masked / flope_tf_attention_masked, fixed and ragged) runs tf_attn_tiled_masked
+ *       (FLOPE_TF_ATTN_MASKED16 = 5) where tf_attn_pick_masked says so: a 16-bit dtype, "generic" = 0, head_dim 32 / 64 /
+ *       96 / 128 and 16-byte aligned buffers -- tf_attn_tiled's LDS ring and 32-key MFMA step over the key blocks of the mask's tile
+ *       map; "attn_tiled" is not consulted.  Other handles and shapes keep tf_attn_masked and its bits.  The result is then NOT
+ *       tf_attn_masked's bits: where the mask is all-clear, causal, a causal band or block-diagonal at multiples of 32 it is
+ *       tf_attn_tiled's for that pattern, bit for bit (the band: with "window_mfma" = 1), every other mask is held element-wise
+ *       within a derived bound of fp64.  A key that no query of the sequence allows is still never read into a product (NaN there
+ *       reaches no output); a key that holds NaN and is allowed by SOME query of a 128-row query block makes every row of that block
+ *       that takes its 32-key step NaN, the rows that mask it included.  Read when a call enqueues, so it may be flipped between
+ *       calls; every mask carries its tile map, a forward builds and allocates nothing.  No other call reads or is changed by it. */
 int flope_tf_set_option(flope_tf_handle h, const char* name, int value);
 /* softmax(q k^T / sqrt(head_dim)) v per head on a caller's buffer: qkv_dev [batch, seq_len, 3*model_dim] and out_dev
  * [batch, seq_len, model_dim] in the handle's dtype (float32 for FLOPE_DT_F32).  Launches exactly what flope_tf_forward
@@ -576,7 +587,8 @@ int flope_tf_stream_attention_extend(flope_tf_stream s, const void* qkv_dev, int
  * device-resident object and passed to any number of forwards.  A mask holds, for one sequence length L, the (query i, key j) pairs
  * that may attend: query i is a softmax over exactly its allowed keys, and a masked key is never loaded, neither its k nor its v (NaN
  * there reaches no output).  Attention under a mask runs tf_attn_masked -- the generic kernel's order over the allowed keys, for every
- * dtype and head_dim, whatever kernel the unmasked shape picks -- and the forward is always the launch sequence.  Where a row's
+ * dtype and head_dim, whatever kernel the unmasked shape picks, unless option "mask_mfma" sends a 16-bit launch to tf_attn_tiled_masked
+ * (flope_tf_set_option) -- and the forward is always the launch sequence.  Where a row's
  * allowed keys are one contiguous range the row is the generic kernel's for that range, operation for operation.
  *   _mask_create   (nn.TransformerEncoder.forward(mask=) of scripts/tf_encoder.py, the mask argument) allow_bits_host: uint32 words
  *             [seq_len][ceil(seq_len / 32)], bit j % 32 of word j / 32 of row i set = query i may attend to key j, padding bits zero.
@@ -594,7 +606,14 @@ int flope_tf_stream_attention_extend(flope_tf_stream s, const void* qkv_dev, int
  *             a row below n has no key (the message names b and the row), too many tokens, a mask of another handle.
  *   _attention_masked  flope_tf_attention (lengths_host NULL: qkv_dev [batch, seq_len, 3*model_dim]) or flope_tf_attention_varlen
  *             (lengths_host: packed rows) under mask m: the attention launch of _forward_masked alone.  Returns
- *             FLOPE_TF_ATTN_MASKED (4), or < 0 with the refusals above.
+ *             FLOPE_TF_ATTN_MASKED (4), under option "mask_mfma" FLOPE_TF_ATTN_MASKED16 (5) where tf_attn_pick_masked picks it, or < 0
+ *             with the refusals above.  The refusal of a seq_len too long for tf_attn_masked's score rows in LDS applies only where
+ *             that kernel is the pick.
+ *   _last_forward_masked  the FLOPE_TF_ATTN_* id of the attention launches of the last _forward_masked that enqueued anything
+ *             (FLOPE_TF_ATTN_MASKED, or FLOPE_TF_ATTN_MASKED16 under option "mask_mfma"); -1 before the first.
+ *   _mask_tiles    the mask's tile map (flope_amd/csrc/tf_attn_mask.h; any pointer may be NULL): its query blocks of 128 rows, the
+ *             64-key blocks listed over all of them (of query_blocks * ceil(seq_len / 64)), and the 8 (wave, 32-key step) tiles of
+ *             every listed block by class: no allowed pair, some, all.
  *   _forward_flops_masked  algorithmic FLOPs of _forward_masked: the linears on every token, attention on the allowed pairs (of each
  *             length's corner with lengths_host); 0 for an invalid call. */
 typedef struct flope_tf_mask* flope_tf_mask_handle;
@@ -606,6 +625,9 @@ int flope_tf_forward_masked(flope_tf_handle h, const float* x_dev, int batch, in
 int flope_tf_attention_masked(flope_tf_handle h, const void* qkv_dev, int batch, int seq_len, const int* lengths_host, flope_tf_mask_handle m,
                               void* out_dev, void* stream);
 double flope_tf_forward_flops_masked(flope_tf_handle h, int batch, const int* lengths_host, flope_tf_mask_handle m);
+int flope_tf_last_forward_masked(flope_tf_handle h);
+int flope_tf_mask_tiles(flope_tf_mask_handle m, int* query_blocks, long long* blocks_listed, long long* steps_none, long long* steps_some,
+                        long long* steps_all);
 
 /* ---- YOLO11-seg detector front end ---------------------------------------------------
  * Replaces `self.yolo = YOLO(yolo_path)` (sunflower/predictor/fast_pose_predictor.py:36) and the
