@@ -5,9 +5,12 @@
 // (columns L .. 32 * words - 1) are zero.  first[i] / last[i]: the first and last allowed key of row i; a row without a key has
 // first = L and last = -1.  Below them the mask's tile map for option mask_mfma: which 64-key blocks a 128-row query block
 // loads and which 32-key steps a wave takes, tf_attn_pick_masked and the launch of tf_attn_tiled_masked
-// (tests/host_harness/harness_tf_mask16.cpp, tests/test_tf_mask16_host.py).
+// (tests/host_harness/harness_tf_mask16.cpp, tests/test_tf_mask16_host.py).  At the end the host side of a compiled additive bias
+// (flope_tf_bias_create): float32 planes [planes][L][L], -inf = masked, from which the same bit words are derived, and the
+// two validators a bias adds (tests/host_harness/harness_tf_bias.cpp, tests/test_tf_bias_host.py).
 #pragma once
 
+#include <math.h>
 #include <stddef.h>
 #include <stdint.h>
 
@@ -210,5 +213,58 @@ inline int tf_attn_pick_masked(int dtype, int head_dim, int opt_generic, int opt
 inline TfAttnLaunch tf_mask16_launch(int head_dim, int B, int H, int max_len) {
   return tf_attn_varlen_launch(FLOPE_TF_ATTN_TILED, head_dim, B, H, max_len);
 }
+
+// ---- a compiled additive bias (flope_tf_bias_create) --------------------------------------------------------------------------
+// bias: float32 [planes][L][L], planes = 1 (one plane for every head) or the handle's num_heads.  -inf = the pair is masked, a finite
+// value = allowed with that value added to its score; +inf and NaN have no meaning and are refused.  The allowed set is one for all
+// heads (the kernel walks one set of bit words), so every plane must hold its -inf where plane 0 does.  The launch is tf_mask_launch.
+
+// The first entry in (plane, row, col) order that is +inf or NaN: true with its index written, false: none
+inline bool tf_bias_nonfinite(const float* bias, int L, int planes, int* plane, int* row, int* col) {
+  const size_t LL = (size_t)L * L;
+  for (size_t t = 0; t < (size_t)planes * LL; ++t) {
+    const float b = bias[t];
+    if (isnan(b) || (isinf(b) && b > 0.f)) {
+      if (plane) *plane = (int)(t / LL);
+      if (row) *row = (int)(t % LL / (size_t)L);
+      if (col) *col = (int)(t % (size_t)L);
+      return true;
+    }
+  }
+  return false;
+}
+
+// The first entry in (plane >= 1, row, col) order whose masked-or-not differs from plane 0's: true with its index written, false: none
+inline bool tf_bias_plane_differs(const float* bias, int L, int planes, int* plane, int* row, int* col) {
+  const size_t LL = (size_t)L * L;
+  for (int p = 1; p < planes; ++p)
+    for (size_t t = 0; t < LL; ++t)
+      if ((bias[t] == -INFINITY) != (bias[(size_t)p * LL + t] == -INFINITY)) {
+        if (plane) *plane = p;
+        if (row) *row = (int)(t / (size_t)L);
+        if (col) *col = (int)(t % (size_t)L);
+        return true;
+      }
+  return false;
+}
+
+// Plane 0's allowed set as bits [L][tf_mask_words(L)]: the words tf_mask_pack gives for allow[i][j] = (bias[0][i][j] != -inf)
+inline void tf_bias_pack(const float* bias, int L, uint32_t* bits) {
+  const int nw = tf_mask_words(L);
+  for (int i = 0; i < L; ++i)
+    for (int w = 0; w < nw; ++w) {
+      uint32_t m = 0;
+      for (int j = w * 32; j < L && j < w * 32 + 32; ++j)
+        if (bias[(size_t)i * L + j] != -INFINITY) m |= 1u << (j & 31);
+      bits[(size_t)i * nw + w] = m;
+    }
+}
+
+// One device allocation holds bits | first | last | bias: the planes start behind the two tables, 4-byte aligned as everything in it
+inline size_t tf_bias_dev_bias_at(int L) { return tf_mask_dev_start_at(L); }
+inline size_t tf_bias_dev_bytes(int L, int planes) { return tf_bias_dev_bias_at(L) + (size_t)planes * L * L * 4; }
+// The bias entry the lane that owns key j of query i of head h loads: an index into the float32 planes (plane 0 for every head when
+// planes == 1).  i and j are positions in the mask's L x L planes whatever the length of the sequence (the corner's rows keep stride L).
+inline size_t tf_bias_index(int L, int planes, int h, int i, int j) { return ((size_t)(planes > 1 ? h : 0) * L + (size_t)i) * L + (size_t)j; }
 
 }  // namespace flope_tf_plan

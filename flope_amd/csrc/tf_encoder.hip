@@ -37,6 +37,9 @@
 // Option mask_mfma = 1 (16-bit handles): a masked launch runs tf_attn_tiled_masked where tf_attn_pick_masked says so --
 // tf_attn_tiled's ring and tf_attn16_step's MASKED form over the key blocks of the mask's tile map, which every mask carries beside its
 // bits; tf_attn_tiled's bits where the mask is all-clear, causal, a causal band or block-diagonal at multiples of 32.
+// flope_tf_bias_create (any dtype): an additive float mask -- the allowed set of its -inf entries plus a float32 value per
+// allowed pair, one [L, L] plane or one per head -- on the mask's handle type; a launch under it is tf_attn_biased for every dtype and
+// option: tf_attn_masked's order with bias[h][i][j] added to the scaled score in a rounding of its own, a zero bias giving its bits.
 #include "../../include/flope_amd.h"
 #include "common.h"
 #include "host_pack.h"
@@ -608,6 +611,117 @@ __global__ void tf_attn_masked(const T* qkv, T* out, int L, int d, int H, int Lm
     for (int w = (fi >> 5) + lane; w <= (la >> 5); w += 64) mw[w] = bits[(size_t)i * words + w];
     __builtin_amdgcn_wave_barrier();
     tf_attn_masked_row<T>(base, (size_t)3 * d, out + ((VARLEN ? row0 : (size_t)b * L) + i) * d + h * dh, s, mw, i, fi, la, d, dh, scale, lane);
+  }
+}
+
+// ---- attention under a compiled additive bias (flope_tf_bias_create; the host side is tf_attn_mask.h) ----------------------
+// softmax_j(q k_j / sqrt(dh) + brow[j]) v over exactly the allowed keys of query i: tf_attn_masked_row's order with ONE change in the
+// score pass.  brow: row i of head h's bias plane in global memory (float32, stride the mask's L), indexed by the key's own position j.
+// After a = fl(chain * scale) the lane that owns key j loads brow[j] and the score is fl(a + brow[j]): a rounding of its own, NOT an fma
+// with the scale (the reference adds the bias to the already scaled, already rounded score; with brow[j] = 0 the score is
+// tf_attn_masked_row's bit for bit, which tests/test_gpu_tf_bias.py holds).  The product and the sum are the plain operators in a block
+// under `#pragma clang fp contract(off)`.  The round-to-nearest intrinsics __fmul_rn / __fadd_rn do NOT keep them apart here: this
+// toolchain's header defines both as the plain operators in functions of its own, outside the pragma's lexical reach, and with them
+// -- with and without the pragma -- the compiler contracted the pair into one v_fma_f32 (the -S dump: one fma more and one v_mul_f32
+// fewer than tf_attn_masked).  As written the dump holds tf_attn_masked's v_fma / v_mul counts and one v_add_f32 more.
+// Max, sum and value passes are tf_attn_masked_row's, statement for statement.
+// A third definition beside tf_attn_row and tf_attn_masked_row, for the reason given there: a flag on tf_attn_masked_row would change
+// the loops tf_attn_masked compiles from.  A masked key is never addressed -- not its k, not its v, not its bias entry (which holds -inf).
+template <typename T>
+__device__ __forceinline__ void tf_attn_biased_row(const T* base, size_t ld, T* orow, float* s, const uint32_t* mw, const float* __restrict__ brow, int i,
+                                                   int first, int last, int d, int dh, float scale, int lane) {
+  const T* q = base + (size_t)i * ld;
+  float mx = -INFINITY;
+  for (int j0 = first; j0 <= last; j0 += 64) {
+    const int j = j0 + lane;
+    const bool on = j <= last && ((mw[j >> 5] >> (j & 31)) & 1u);
+    if (!__builtin_amdgcn_ballot_w64(on)) continue;
+    if (on) {
+      const T* k = base + (size_t)j * ld + d;
+      const float bj = brow[j];
+      float a = 0.f;
+      for (int c = 0; c < dh; ++c) a = fmaf(to_f32<T>(q[c]), to_f32<T>(k[c]), a);
+      {
+#pragma clang fp contract(off)
+        a = a * scale;
+        a = a + bj;
+      }
+      s[j] = a;
+      mx = fmaxf(mx, a);
+    }
+  }
+  mx = wave_max(mx);
+  float sum = 0.f;
+  for (int j0 = first; j0 <= last; j0 += 64) {
+    const int j = j0 + lane;
+    const bool on = j <= last && ((mw[j >> 5] >> (j & 31)) & 1u);
+    if (on) { const float p = expf(s[j] - mx); s[j] = p; sum += p; }
+  }
+  sum = wave_sum(sum);
+  __builtin_amdgcn_wave_barrier();
+  const float inv = 1.f / sum;
+  const int w0 = first >> 5, w1 = last >> 5;
+  for (int c = lane; c < dh; c += 64) {
+    const T* v = base + 2 * d + c;
+    float o = 0.f;
+    for (int w = w0; w <= w1; ++w) {
+      uint32_t m = __builtin_amdgcn_readfirstlane(mw[w]);
+      if (w == w0) m &= ~0u << (first & 31);
+      if (w == w1) m &= (2u << (last & 31)) - 1u;
+      const int jb = w * 32;
+      while (__builtin_popcount(m) >= kTfMaskUnroll) {
+        int js[kTfMaskUnroll];
+        float vv[kTfMaskUnroll];
+#pragma unroll
+        for (int u = 0; u < kTfMaskUnroll; ++u) { js[u] = jb + __builtin_ctz(m); m &= m - 1u; }
+#pragma unroll
+        for (int u = 0; u < kTfMaskUnroll; ++u) vv[u] = to_f32<T>(v[(size_t)js[u] * ld]);
+#pragma unroll
+        for (int u = 0; u < kTfMaskUnroll; ++u) o = fmaf(s[js[u]], vv[u], o);
+      }
+      while (m) {
+        const int j = jb + __builtin_ctz(m);
+        m &= m - 1u;
+        o = fmaf(s[j], to_f32<T>(v[(size_t)j * ld]), o);
+      }
+    }
+    if constexpr (std::is_same<T, f16_t>::value) *(unsigned short*)(orow + c) = (unsigned short)tf_mul_f16_bits(o, inv);
+    else orow[c] = from_f32<T>(o * inv);
+  }
+  __builtin_amdgcn_wave_barrier();
+}
+
+// tf_attn_masked's workgroup, grid, LDS and row guards (tf_mask_launch, unchanged), plus the bias: float32 [planes][Lm][Lm] behind the
+// mask's tables in the same allocation, planes = 1 (every head reads plane 0) or H.  Memory safety as there, and for the bias: a row
+// reaches tf_attn_biased_row only with i < n <= Lm and first <= last <= n - 1, the plane index is 0 or h < H = planes, and the row
+// loads brow[j] only for an allowed key first <= j <= last -- so every bias address lies inside the planes whatever the tables hold.
+template <typename T, bool VARLEN>
+__global__ void tf_attn_biased(const T* qkv, T* out, int L, int d, int H, int Lm, const uint32_t* __restrict__ bits, const int* __restrict__ first,
+                               const int* __restrict__ last, const float* __restrict__ bias, int planes, const int* __restrict__ off) {
+  extern __shared__ float sc[];                 // [waves][L] | [waves][words]
+  const int nw = blockDim.x >> 6, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int b = blockIdx.x / H, h = blockIdx.x - b * H, dh = d / H;
+  const int words = flope_tf_plan::tf_mask_words(Lm);
+  const float scale = 1.f / sqrtf((float)dh);
+  size_t row0 = 0;                              // first row of this sequence
+  int n = L;
+  if constexpr (VARLEN) { row0 = (size_t)off[b]; n = off[b + 1] - off[b]; }
+  if (n > L) n = L;
+  if (n > Lm) n = Lm;
+  float* s = sc + (size_t)wave * L;
+  uint32_t* mw = (uint32_t*)(sc + (size_t)nw * L) + (size_t)wave * words;
+  const T* base = VARLEN ? qkv + row0 * 3 * d + h * dh : qkv + (size_t)b * L * 3 * d + h * dh;
+  const float* plane = bias + (size_t)(planes > 1 ? h : 0) * Lm * Lm;
+  for (int i = blockIdx.y * nw + wave; i < n; i += gridDim.y * nw) {
+    const int fi = __builtin_amdgcn_readfirstlane(first[i]);
+    int la = __builtin_amdgcn_readfirstlane(last[i]);
+    if ((unsigned)fi >= (unsigned)n) continue;
+    if (la > n - 1) la = n - 1;
+    if (la < fi) continue;
+    for (int w = (fi >> 5) + lane; w <= (la >> 5); w += 64) mw[w] = bits[(size_t)i * words + w];
+    __builtin_amdgcn_wave_barrier();
+    tf_attn_biased_row<T>(base, (size_t)3 * d, out + ((VARLEN ? row0 : (size_t)b * L) + i) * d + h * dh, s, mw, plane + (size_t)i * Lm, i, fi, la, d, dh, scale,
+                          lane);
   }
 }
 
@@ -2026,6 +2140,8 @@ struct flope_tf_mask {
   std::vector<int> first, last;
   std::vector<int> start;                    // the tile map (tf_attn_mask.h), built for every mask: option mask_mfma may be flipped between forwards
   std::vector<flope_tf_plan::TfMaskTile> tiles;
+  int planes = 0;                            // 0: a plain mask.  1 or num_heads: a compiled additive bias (flope_tf_bias_create): dev is bits | first | last | float bias [planes][L][L], the tile map stays on the host
+  const float* bias_dev() const { return (const float*)((const char*)dev + flope_tf_plan::tf_bias_dev_bias_at(L)); }
   const uint32_t* bits_dev() const { return (const uint32_t*)dev; }
   const int* first_dev() const { return (const int*)(bits_dev() + bits.size()); }
   const int* last_dev() const { return first_dev() + L; }
@@ -2466,6 +2582,11 @@ extern "C" int flope_tf_create(int device_id, int input_dim, int model_dim, int 
     for (const void* f : masked)                     // four score rows of up to max_tokens floats and the mask words behind them
       if (hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kTfAttnLds) != hipSuccess)
         return fin(tf_fail(nullptr, FLOPE_EHIP, "flope_tf_create: hipFuncSetAttribute failed"));
+    const void* const biased[] = {(const void*)tf_attn_biased<float, false>, (const void*)tf_attn_biased<float, true>, (const void*)tf_attn_biased<f16_t, false>,
+                                  (const void*)tf_attn_biased<f16_t, true>, (const void*)tf_attn_biased<bf16_t, false>, (const void*)tf_attn_biased<bf16_t, true>};
+    for (const void* f : biased)                     // tf_attn_masked's LDS
+      if (hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kTfAttnLds) != hipSuccess)
+        return fin(tf_fail(nullptr, FLOPE_EHIP, "flope_tf_create: hipFuncSetAttribute failed"));
     if (hipDeviceGetAttribute(&e->cus, hipDeviceAttributeMultiprocessorCount, device_id) != hipSuccess || e->cus < 1) e->cus = 256;
   }
   *out = e;
@@ -2787,13 +2908,16 @@ namespace {
 // always is plus the mask rows in LDS (tf_mask_launch), unless option mask_mfma sends a 16-bit launch to tf_attn_tiled_masked, launched
 // as tf_attn_tiled is (tf_mask16_launch).  off == nullptr: qkv [B][L][3 d], L == m->L; otherwise the packed rows of a ragged batch, L
 // its longest length.  Returns the kernel's FLOPE_TF_ATTN_* id, or < 0.
-int tf_masked_pick(const flope_tf_encoder* e, const void* qkv, const void* att) {
+// A handle that carries a bias (m->planes > 0) takes tf_attn_biased on every dtype and under every option, launched by
+// tf_mask_launch as tf_attn_masked is.
+int tf_masked_pick(const flope_tf_encoder* e, const flope_tf_mask* m, const void* qkv, const void* att) {
+  if (m->planes) return FLOPE_TF_ATTN_BIASED;
   return flope_tf_plan::tf_attn_pick_masked(e->dtype, e->d / e->H, e->opt_generic, e->opt_mask_mfma, !(((uintptr_t)qkv | (uintptr_t)att) & 15));
 }
 template <typename T>
 int launch_attention_masked(flope_tf_encoder* e, const flope_tf_mask* m, const void* qkv, void* att, int B, int L, const int* off, hipStream_t st) {
   if constexpr (!std::is_same<T, float>::value) {
-    if (tf_masked_pick(e, qkv, att) == FLOPE_TF_ATTN_MASKED16) {
+    if (tf_masked_pick(e, m, qkv, att) == FLOPE_TF_ATTN_MASKED16) {
       const int dh = e->d / e->H;
       const flope_tf_plan::TfAttnLaunch l = flope_tf_plan::tf_mask16_launch(dh, B, e->H, L);
       const dim3 grid(l.grid_x, l.grid_y), block(l.block);
@@ -2812,6 +2936,16 @@ int launch_attention_masked(flope_tf_encoder* e, const flope_tf_mask* m, const v
   }
   const flope_tf_plan::TfAttnLaunch l = flope_tf_plan::tf_mask_launch(e->d / e->H, B, e->H, L, m->L);
   const dim3 grid(l.grid_x, l.grid_y), block(l.block);
+  if (m->planes) {
+    if (off)
+      hipLaunchKernelGGL((tf_attn_biased<T, true>), grid, block, l.lds, st, (const T*)qkv, (T*)att, L, e->d, e->H, m->L, m->bits_dev(), m->first_dev(), m->last_dev(),
+                         m->bias_dev(), m->planes, off);
+    else
+      hipLaunchKernelGGL((tf_attn_biased<T, false>), grid, block, l.lds, st, (const T*)qkv, (T*)att, L, e->d, e->H, m->L, m->bits_dev(), m->first_dev(), m->last_dev(),
+                         m->bias_dev(), m->planes, off);
+    TF_HIP(e, hipGetLastError());
+    return FLOPE_TF_ATTN_BIASED;
+  }
   if (off)
     hipLaunchKernelGGL((tf_attn_masked<T, true>), grid, block, l.lds, st, (const T*)qkv, (T*)att, L, e->d, e->H, m->L, m->bits_dev(), m->first_dev(), m->last_dev(), off);
   else
@@ -2845,7 +2979,7 @@ int tf_masked_check(flope_tf_encoder* e, const std::string& who, const flope_tf_
     }
     max_len = rg->max_len;
   }
-  if (tf_masked_pick(e, qkv, att) == FLOPE_TF_ATTN_MASKED &&           // tf_attn_tiled_masked keeps no row in LDS
+  if (tf_masked_pick(e, m, qkv, att) != FLOPE_TF_ATTN_MASKED16 &&      // tf_attn_tiled_masked keeps no row in LDS
       flope_tf_plan::tf_mask_launch(e->d / e->H, batch, e->H, max_len, m->L).lds > flope_tf_plan::kTfAttnLds)
     return tf_fail(e, FLOPE_EINVAL, who + ": seq_len too long for the score rows of one workgroup");
   return 0;
@@ -2891,6 +3025,65 @@ extern "C" int flope_tf_mask_create(flope_tf_handle e, int seq_len, const uint32
   e->masks.push_back(m);
   *out = m;
   return FLOPE_OK;
+}
+
+// A compiled additive bias: the mask of its -inf entries plus a float32 value per allowed pair, on the same handle type
+extern "C" int flope_tf_bias_create(flope_tf_handle e, int seq_len, int planes, const float* bias_host, flope_tf_mask_handle* out) {
+  using namespace flope_tf_plan;
+  const std::string who = "flope_tf_bias_create";
+  if (out) *out = nullptr;
+  if (!e) return tf_fail(nullptr, FLOPE_EINVAL, who + ": NULL handle");
+  if (!out || !bias_host) return tf_fail(e, FLOPE_EINVAL, who + ": NULL argument");
+  if (seq_len < 1 || seq_len > e->max_tokens)
+    return tf_fail(e, FLOPE_EINVAL, who + ": seq_len = " + std::to_string(seq_len) + " is outside 1 .. max_tokens = " + std::to_string(e->max_tokens));
+  if (planes != 1 && planes != e->H)
+    return tf_fail(e, FLOPE_EINVAL, who + ": planes = " + std::to_string(planes) + " is neither 1 nor num_heads = " + std::to_string(e->H));
+  int pl = -1, row = -1, col = -1;
+  auto at = [&] { return "(plane " + std::to_string(pl) + ", row " + std::to_string(row) + ", col " + std::to_string(col) + ")"; };
+  if (tf_bias_nonfinite(bias_host, seq_len, planes, &pl, &row, &col))
+    return tf_fail(e, FLOPE_EINVAL, who + ": the entry at " + at() + " is +inf or NaN (a bias entry is finite, or -inf for a masked pair)");
+  if (tf_bias_plane_differs(bias_host, seq_len, planes, &pl, &row, &col))
+    return tf_fail(e, FLOPE_EINVAL, who + ": the entry at " + at() + " is masked in one of plane 0 and plane " + std::to_string(pl) +
+                                        " and allowed in the other: the allowed set is one for all heads (write a per-head difference as a large negative finite value)");
+  flope_tf_mask* m = new flope_tf_mask();
+  m->L = seq_len;
+  m->planes = planes;
+  m->bits.resize((size_t)seq_len * tf_mask_words(seq_len));
+  tf_bias_pack(bias_host, seq_len, m->bits.data());
+  row = tf_mask_empty_row(m->bits.data(), seq_len);
+  if (row >= 0) {
+    delete m;
+    return tf_fail(e, FLOPE_EINVAL, who + ": row " + std::to_string(row) + " has no allowed key (a softmax over nothing; the reference returns NaN there)");
+  }
+  m->first.resize(seq_len);
+  m->last.resize(seq_len);
+  tf_mask_first_last(m->bits.data(), seq_len, m->first.data(), m->last.data());
+  m->pairs = tf_mask_pairs(m->bits.data(), seq_len);
+  m->start.resize((size_t)tf_mask_query_blocks(seq_len) + 1);               // host only: what flope_tf_mask_tiles reports
+  m->tiles.resize((size_t)tf_mask_tiles_build(m->bits.data(), seq_len, m->start.data(), nullptr));
+  tf_mask_tiles_build(m->bits.data(), seq_len, m->start.data(), m->tiles.data());
+  const size_t nb = m->bits.size() * sizeof(uint32_t), nt = (size_t)seq_len * sizeof(int), all = tf_bias_dev_bytes(seq_len, planes);
+  auto fin = [&](const std::string& what) { hipFree(m->dev); delete m; return tf_fail(e, FLOPE_EHIP, who + ": " + what); };
+  if (hipSetDevice(e->device) != hipSuccess) return fin("hipSetDevice failed");
+  if (hipMalloc(&m->dev, all) != hipSuccess) {
+    m->dev = nullptr;
+    return fin("hipMalloc of " + std::to_string(all) + " bytes failed (" + std::to_string(planes) + " float32 planes of " + std::to_string((size_t)seq_len * seq_len * 4) + " bytes)");
+  }
+  if (hipMemcpy(m->dev, m->bits.data(), nb, hipMemcpyHostToDevice) != hipSuccess ||
+      hipMemcpy((char*)m->dev + nb, m->first.data(), nt, hipMemcpyHostToDevice) != hipSuccess ||
+      hipMemcpy((char*)m->dev + nb + nt, m->last.data(), nt, hipMemcpyHostToDevice) != hipSuccess ||
+      hipMemcpy((char*)m->dev + tf_bias_dev_bias_at(seq_len), bias_host, (size_t)planes * seq_len * seq_len * sizeof(float), hipMemcpyHostToDevice) != hipSuccess)
+    return fin("hipMemcpy failed");
+  m->e = e;
+  e->masks.push_back(m);
+  *out = m;
+  return FLOPE_OK;
+}
+
+extern "C" int flope_tf_mask_bias_planes(flope_tf_mask_handle m) {
+  if (!m) return tf_fail(nullptr, FLOPE_EINVAL, "flope_tf_mask_bias_planes: NULL mask");
+  if (!m->e) return tf_fail(nullptr, FLOPE_ESTATE, "flope_tf_mask_bias_planes: the encoder handle of this mask has been destroyed");
+  return m->planes;
 }
 
 extern "C" int flope_tf_mask_destroy(flope_tf_mask_handle m) {

@@ -14,6 +14,9 @@ Any other [L, L] mask is compiled once with `enc.make_mask(mask)` and passed as 
 exactly its allowed keys, a masked key is never loaded, and a sequence of a ragged batch is encoded under the mask's top-left corner
 (DESIGN.md 37).  A 16-bit encoder made with `mask_mfma=1` runs attention under a compiled mask on the MFMA attention step over the mask's
 tile map, loading only the 64-key blocks some query of a 128-row block allows.
+An additive float mask -- torch's `mask=` with values other than -inf / 0, one [L, L] plane or one per head -- is compiled with
+`enc.make_bias(bias)` and passed the same way; `alibi_bias(L, slopes)` builds the distance bias this encoder, which has no positional
+term, needs to tell the order of the poses behind a query.
 
 Eval-mode semantics only (dropout is identity), as everywhere in this package.  There is no CPU
 path: construction fails loudly without a HIP device or without the built library.
@@ -160,6 +163,18 @@ def _pack_allowed(allowed):
     return (C.c_uint32 * (L * words))(*packed.reshape(-1).tolist())
 
 
+def alibi_bias(L, slopes, causal=True):
+    """The ALiBi bias for sequences of L tokens, float32 [len(slopes), L, L]: -slopes[h] * |i - j| for query i and key j of head h, and
+    with `causal` -inf above the diagonal.  Pass it to `enc.make_bias` (len(slopes) = num_heads, or 1).  This encoder has no
+    positional term, so without it a causal or windowed forward cannot tell in which order the poses behind a query came."""
+    slopes = torch.as_tensor(slopes, dtype=torch.float32).reshape(-1)
+    i, j = torch.arange(int(L))[:, None], torch.arange(int(L))[None, :]
+    bias = -slopes[:, None, None] * (i - j).abs().to(torch.float32)[None]
+    if causal:
+        bias = bias.masked_fill((j > i)[None], float("-inf"))
+    return bias
+
+
 class TransformerEncoder:
     def __init__(self, input_dim, model_dim, out_dim, num_heads, num_layers, ff_dim, dropout=0.1,
                  dtype="f32", max_tokens=4096, device=None, attn_tiled=0, fused=0, window_mfma=0, step_split=0, extend_mfma=0,
@@ -281,6 +296,17 @@ class TransformerEncoder:
         value (the first offending entry is named), a row without an allowed key (the reference returns NaN there), L > max_tokens."""
         return TransformerEncoderMask(self, mask)
 
+    def make_bias(self, bias) -> "TransformerEncoderMask":
+        """Compiles an additive attention bias -- a floating [L, L] tensor (one plane for every head) or [H, L, L] (one per head), on
+        any device -- into a TransformerEncoderMask that forward() and attention() take as `mask=`, fixed-length and ragged (DESIGN.md
+        39).  -inf = masked, as in make_mask: never loaded.  Any finite value is added to the pair's scaled score before the softmax
+        (torch's float `mask`); the values are kept as float32 whatever the encoder's dtype.  Torch's 3-D form [B * H, L, L] is this
+        [H, L, L] repeated batch-major: pass one batch element's H planes.  A sequence of n tokens of a ragged batch is encoded under
+        the top-left n x n corner of every plane.  `.planes` of the result is 1 or H.  ValueError: another shape or dtype, +inf or NaN
+        (the message names plane, row, col), planes whose -inf entries differ (write a per-head difference as a large negative finite
+        value), a row without an allowed key, L > max_tokens."""
+        return TransformerEncoderMask(self, None, bias=bias)
+
     def _compiled(self, mask, seq_len, is_causal, window):
         """The checks every call that takes a compiled mask starts with"""
         if mask.enc is not self:
@@ -345,7 +371,8 @@ class TransformerEncoder:
         single launch.  A banded mask together with another `window` raises
         ValueError.  The option is stated per call: a plain call after a windowed one has no window.
         `mask` = a TransformerEncoderMask (make_mask): any set of allowed (query, key) pairs, see there; with `is_causal=True` or a
-        `window` it raises ValueError."""
+        `window` it raises ValueError.  One made by make_bias also adds its float32 value to every allowed pair's score, per head
+        where it has H planes."""
         if not x.is_cuda or x.device != self.device:
             raise RuntimeError(f"input must live on {self.device} (got {x.device}); no CPU path")
         if x.dim() != 3 or x.shape[2] != self.dims[0]:
@@ -367,7 +394,7 @@ class TransformerEncoder:
             with torch.cuda.device(self.device):
                 self._check_arg(self.lib.flope_tf_forward_masked(self.handle, x.data_ptr(), B, L, lh, mask.handle, y.data_ptr(), _stream_ptr(self.device)))
             self.last_forward_fused = False
-            self.last_attn_kernel = self.lib.flope_tf_last_forward_masked(self.handle)       # tf_attn_masked, or tf_attn_tiled_masked under mask_mfma
+            self.last_attn_kernel = self.lib.flope_tf_last_forward_masked(self.handle)       # tf_attn_masked, tf_attn_tiled_masked under mask_mfma, tf_attn_biased under a bias
             self._keep = x
             return y
         causal, band = _mask_window(mask, L)
@@ -402,7 +429,8 @@ class TransformerEncoder:
         kernel the call would take without a window on a handle made with `window_mfma=1`.
         `mask` (a compiled one, make_mask): softmax over the allowed keys only, by tf_attn_masked (`last_attn_kernel` = 4) for every
         dtype and shape, or, on a 16-bit encoder with `mask_mfma=1` and head_dim 32 / 64 / 96 / 128, by tf_attn_tiled_masked
-        (`last_attn_kernel` = 5); with `lengths` each sequence under the mask's corner."""
+        (`last_attn_kernel` = 5); with `lengths` each sequence under the mask's corner.  A compiled bias (make_bias) is
+        passed the same way and runs tf_attn_biased (`last_attn_kernel` = 6) on every dtype and under every option."""
         if mask is not None and not isinstance(mask, TransformerEncoderMask):
             raise ValueError("attention() takes a compiled mask (enc.make_mask), not a tensor")
         if mask is not None:
@@ -568,24 +596,38 @@ class TransformerEncoder:
 class TransformerEncoderMask:
     """An [L, L] attention mask compiled for one encoder (include/flope_amd.h: flope_tf_mask_*): the allowed (query, key)
     pairs as bits on the device, made once by `enc.make_mask(mask)` and passed as `mask=` to any number of forwards.  `L`: the
-    sequence length it was made for; `allowed`: the number of allowed pairs; `tile_stats`: what option `mask_mfma` walks,
+    sequence length it was made for; `allowed`: the number of allowed pairs; `planes`: 0, or the 1 or num_heads float32 planes of an
+    additive bias when it was made by `enc.make_bias(bias)` (attention then runs tf_attn_biased); `tile_stats`: what option `mask_mfma` walks,
     a dict of query_blocks (of 128 rows), blocks_listed (64-key blocks over all of them) and steps_none / steps_some / steps_all (the 8
     (wave, 32-key step) tiles of every listed block by class).  It keeps its encoder alive; after enc.close() or its own
     close() its use raises RuntimeError."""
 
-    def __init__(self, enc: TransformerEncoder, mask):
+    def __init__(self, enc: TransformerEncoder, mask, bias=None):
         self.enc = enc
         self.handle = C.c_void_p()
         if not enc.handle.value:
             raise RuntimeError("the encoder of this mask has been closed")
-        allowed = _mask_allowed(mask)
-        self.L = int(allowed.shape[0])
-        empty = (~allowed.any(dim=1)).nonzero().reshape(-1).tolist()
-        if empty:
-            raise ValueError(f"mask row {empty[0]} has no allowed key: a softmax over nothing (the reference returns NaN for it)")
-        with torch.cuda.device(enc.device):
-            rc = enc.lib.flope_tf_mask_create(enc.handle, self.L, _pack_allowed(allowed), C.byref(self.handle))
-        enc._check_arg(rc)
+        if bias is not None:
+            # a compiled additive bias (make_bias; DESIGN.md 39): the same handle type, its allowed set derived from the -inf entries
+            # and every refusal made on the C side, which names (plane, row, col)
+            bias = torch.as_tensor(bias)
+            if bias.dim() not in (2, 3) or bias.shape[-1] != bias.shape[-2] or bias.shape[-1] < 1 or not bias.dtype.is_floating_point:
+                raise ValueError(f"bias must be a floating tensor [L, L] or [H, L, L] with L >= 1, got {bias.dtype} {tuple(bias.shape)}")
+            b = bias.detach().to(device="cpu", dtype=torch.float32).reshape(-1, bias.shape[-1], bias.shape[-1]).contiguous()
+            self.L = int(b.shape[-1])
+            with torch.cuda.device(enc.device):
+                rc = enc.lib.flope_tf_bias_create(enc.handle, self.L, int(b.shape[0]), C.cast(b.data_ptr(), C.POINTER(C.c_float)), C.byref(self.handle))
+            enc._check_arg(rc)
+        else:
+            allowed = _mask_allowed(mask)
+            self.L = int(allowed.shape[0])
+            empty = (~allowed.any(dim=1)).nonzero().reshape(-1).tolist()
+            if empty:
+                raise ValueError(f"mask row {empty[0]} has no allowed key: a softmax over nothing (the reference returns NaN for it)")
+            with torch.cuda.device(enc.device):
+                rc = enc.lib.flope_tf_mask_create(enc.handle, self.L, _pack_allowed(allowed), C.byref(self.handle))
+            enc._check_arg(rc)
+        self.planes = int(enc.lib.flope_tf_mask_bias_planes(self.handle))        # 0: a plain mask; 1 or num_heads: a bias
         n, pairs = C.c_int(), C.c_longlong()
         enc._check_arg(enc.lib.flope_tf_mask_info(self.handle, C.byref(n), C.byref(pairs)))
         self.allowed = int(pairs.value)

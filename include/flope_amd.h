@@ -628,6 +628,25 @@ double flope_tf_forward_flops_masked(flope_tf_handle h, int batch, const int* le
 int flope_tf_last_forward_masked(flope_tf_handle h);
 int flope_tf_mask_tiles(flope_tf_mask_handle m, int* query_blocks, long long* blocks_listed, long long* steps_none, long long* steps_some,
                         long long* steps_all);
+/* An additive attention bias (nn.TransformerEncoder.forward(mask=) with a float mask of scripts/tf_encoder.py), compiled
+ * once as a mask is: the [L, L] set of allowed pairs a compiled mask holds plus a float32 value for every allowed pair, in one plane for
+ * all heads or one plane per head.  Query i of head h is softmax_j(q . k_j / sqrt(head_dim) + bias[h][i][j]) over exactly its allowed
+ * keys; a masked key is never loaded: not its k, not its v, not its bias entry.  The bias is kept as float32 on every handle dtype.
+ *   _bias_create   bias_host: float32 [planes][seq_len][seq_len], planes = 1 or num_heads; -inf = masked, any finite value = allowed
+ *             with that value added to the scaled score (the sum is a rounding of its own).  Returns the handle type of _mask_create:
+ *             _forward_masked, _attention_masked (fixed and ragged: a sequence of n tokens under the top-left n x n corner of every
+ *             plane), _mask_destroy, _mask_info, _forward_flops_masked (the adds are not counted) and _mask_tiles take it as they
+ *             take a mask.  One device allocation bits | first | last | bias, uploaded synchronously; a failed allocation is
+ *             FLOPE_EHIP and the message names the size (at seq_len 4096 a plane is 64 MiB).  FLOPE_EINVAL before anything is
+ *             enqueued, the index (plane, row, col) in flope_tf_last_error: NULL arguments, seq_len < 1 or > max_tokens, planes
+ *             neither 1 nor num_heads, an entry that is +inf or NaN, a plane whose masked entries differ from plane 0's (a per-head
+ *             difference is written as a large negative finite value), a row without a key.
+ *             Attention under a bias runs tf_attn_biased (FLOPE_TF_ATTN_BIASED = 6, what _attention_masked returns and
+ *             _last_forward_masked reports) on every dtype and under every option, "mask_mfma", "f32mfma" and "generic" included:
+ *             tf_attn_masked's order with the one add, so an all-zero bias gives tf_attn_masked's bits for the same allowed set.
+ *   _mask_bias_planes  the planes of a compiled bias, 0 for a plain mask. */
+int flope_tf_bias_create(flope_tf_handle h, int seq_len, int planes, const float* bias_host, flope_tf_mask_handle* out);
+int flope_tf_mask_bias_planes(flope_tf_mask_handle m);
 
 /* ---- YOLO11-seg detector front end ---------------------------------------------------
  * Replaces `self.yolo = YOLO(yolo_path)` (sunflower/predictor/fast_pose_predictor.py:36) and the
