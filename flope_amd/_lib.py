@@ -21,6 +21,8 @@ TF_EXTEND_ROW, TF_EXTEND_SPLIT, TF_EXTEND_MFMA = 0, 1, 2                        
 TF_STEP_ROW, TF_STEP_SPLIT = 0, 1                                              # flope_tf_stream_step_plan's / _attention's return
 TF_LN_SCALAR, TF_LN_VEC = 0, 1                                                 # flope_tf_layernorm's return
 STAGE_STEM, STAGE_POOL, STAGE_FEAT, STAGE_HIDDEN = 0, 1, 10, 11
+HEAD_FC1 = ("packed", "row-major", "simple")                                   # flope_head_plan's *fc1 (plan.h: HeadFc1)
+HEAD_FC2 = ("k4", "wave-vector", "wave-scalar")                                # flope_head_plan's *fc2 (plan.h: HeadFc2)
 
 
 def STAGE_LAYER(li: int, bi: int) -> int:
@@ -64,6 +66,7 @@ SIGNATURES = {
     "flope_describe_plan": (_I, [_P, C.c_char_p, _I]),
     "flope_version": (C.c_char_p, []),
     "flope_engine_geometry": (_I, [_P, C.POINTER(_I), C.POINTER(_I), C.POINTER(_I), C.POINTER(_I), C.POINTER(_I)]),
+    "flope_head_plan": (_I, [_P, C.POINTER(_I), C.POINTER(_I)]),
     "flope_frame_create": (_I, [_P, _I, _I, _I, _I, C.POINTER(_P)]),
     "flope_frame_destroy": (_I, [_P]),
     "flope_frame_last_error": (C.c_char_p, [_P]),
@@ -80,6 +83,7 @@ SIGNATURES = {
     "flope_guard_repair": (_I, [_P, _I, _P]),
     "flope_guard_forward_repaired": (_I, [_P, _P, _I, _I, _P, _I, _P, _P, _P, _P, _P]),
     "flope_guard_read_selection": (_I, [_P, _I, _P, _I]),
+    "flope_guard_select_rows": (_I, [_P, _I, _F, _P, _P, _P]),
     "flope_frame_create_guarded": (_I, [_P, _I, _I, _I, _I, C.POINTER(_P)]),
     "flope_frame_read_gaps": (_I, [_P, _I, _P, _I]),
     "flope_stream_create_cu_mask": (_I, [_I, C.POINTER(C.c_uint32), _I, C.POINTER(_P)]),

@@ -363,6 +363,15 @@ extern "C" int flope_engine_geometry(flope_handle h, int* max_batch, int* dtype,
 // library-internal (guard.h): the guard checks that its two engines share the head's width
 extern "C" int flope_engine_bod(flope_handle h) { return h ? h->bod : FLOPE_EINVAL; }
 
+// which head kernels a forward of this handle launches under its current options (plan.h: head_plan, the launchers' own rule)
+extern "C" int flope_head_plan(flope_handle h, int* fc1, int* fc2) {
+  if (!h) return FLOPE_EINVAL;
+  const HeadPlan hp = head_plan(h->opt, h->bod);
+  if (fc1) *fc1 = hp.fc1;
+  if (fc2) *fc2 = hp.fc2;
+  return FLOPE_OK;
+}
+
 extern "C" const char* flope_last_error(flope_handle h) { return h ? h->err.c_str() : g_last_error.c_str(); }
 
 extern "C" int flope_create(int device_id, int height, int width, int max_batch, int dtype, int backbone_out_dim,

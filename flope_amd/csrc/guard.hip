@@ -283,6 +283,23 @@ extern "C" int flope_guard_forward_repaired(flope_guard_handle g, const void* x_
   return flope_guard_repair(g, 0, stream);
 }
 
+// test hook: the selection kernel with flope_guard_forward's launch shape and its mapped-host count, on a caller's M [n, 9]
+extern "C" int flope_guard_select_rows(const float* M_dev, int n, float gap_min, float* gap_dev, int32_t* sel_dev, void* stream) {
+  if (!M_dev || !sel_dev || n < 1) return gfail(nullptr, FLOPE_EINVAL, "flope_guard_select_rows: M_dev, sel_dev and n >= 1 are needed");
+  int *count_host = nullptr, *count_dev = nullptr;
+  if (hipHostMalloc((void**)&count_host, sizeof(int), hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess)
+    return gfail(nullptr, FLOPE_EHIP, "flope_guard_select_rows: allocation failed");
+  *count_host = -1;
+  int rc = FLOPE_EHIP;
+  if (hipHostGetDevicePointer((void**)&count_dev, count_host, 0) == hipSuccess) {
+    hipLaunchKernelGGL(guard_select_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, M_dev, n, gap_min, gap_dev, sel_dev, count_dev);
+    if (hipGetLastError() == hipSuccess && hipStreamSynchronize((hipStream_t)stream) == hipSuccess) rc = *count_host;
+  }
+  hipHostFree(count_host);
+  if (rc < 0 || rc > n) return gfail(nullptr, FLOPE_EHIP, "flope_guard_select_rows: launch, wait or count failed");
+  return rc;
+}
+
 // test hook: the flagged crops of the slot's last repair, ascending; returns their number
 extern "C" int flope_guard_read_selection(flope_guard_handle g, int slot, int32_t* idx_host, int cap) {
   if (!g || slot < 0 || slot >= g->nslots) return gfail(g, FLOPE_EINVAL, "flope_guard_read_selection: bad handle / slot");

@@ -712,6 +712,32 @@ inline int forward_launches(const Plan& pl, const PlanOptions& o) {
   return n;
 }
 
+// ---- the regression head behind layer4.1 (pool_head.hip): which kernel fc.0 and fc_rot run on ------------------------------------
+// The ONE statement of that choice: the launchers of pool_head.hip ask these functions, flope_head_plan reports them, and
+// tests/test_host.py pins them over the widths tests/test_gpu_head.py runs.  (launch_name below labels the head "fc1_kernel" /
+// "fc2_procrustes_kernel" whatever ran: tests/golden/plan_matrix.json pins those labels.)
+enum HeadFc1 { kFc1Packed = 0, kFc1RowMajor = 1, kFc1Simple = 2 };           // fc1_packed_kernel<1>, fc1_kernel, fc1_simple_kernel
+enum HeadFc2 { kFc2K4 = 0, kFc2WaveVector = 1, kFc2WaveScalar = 2 };         // fc2_procrustes_k4_kernel, fc2_procrustes_kernel<vector / scalar K loop>
+constexpr int kHeadK = 512;                                                  // layer4.1's channels: K of fc.0
+
+// fc.0 [N, K]: the MFMA kernels walk K in blocks of 32 and N in tiles of 16; the packed one also stages 16 feature rows of
+// K + 4 floats in LDS (inside the default 64 KiB dynamic-LDS limit) and needs the fragment-order image of the weights
+inline int head_fc1_variant(bool have_packed, int K, int N) {
+  const bool mfma = K % 32 == 0 && N % 16 == 0;
+  if (mfma && have_packed && (size_t)16 * (K + 4) * sizeof(float) <= 64 * 1024) return kFc1Packed;
+  return mfma ? kFc1RowMajor : kFc1Simple;
+}
+// fc_rot [9, K]: four waves per image take K / 4 each in steps of 256; else one wave per image, 16-byte loads where K allows
+inline int head_fc2_variant(bool k4, int K) {
+  if (k4 && K % 1024 == 0) return kFc2K4;
+  return K % 4 == 0 ? kFc2WaveVector : kFc2WaveScalar;
+}
+struct HeadPlan { int fc1, fc2; };
+// (the engine uploads the packed image whenever bod % 16 == 0, which the packed kernel needs anyway)
+inline HeadPlan head_plan(const PlanOptions& o, int bod) {
+  return {head_fc1_variant(o.fc1_packed != 0 && bod % 16 == 0, kHeadK, bod), head_fc2_variant(o.fc2_k4 != 0, bod)};
+}
+
 // launch idx of a forward whose convs launch L[conv]: "layer|kernel", the conv behind it (-1: none) and its FLOPs per crop;
 // empty for a bad index
 inline std::string launch_name(const Plan& pl, const PlanOptions& o, const std::vector<Launch>& L, int bod, int idx, int* conv, double* flops) {

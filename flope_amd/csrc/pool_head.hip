@@ -11,6 +11,7 @@
 // The whole head is fp32 (fp64 inside the 4x4 eigen-solve): it is 0.06 % of the
 // FLOPs and carries the 1e-3 rotation tolerance.
 #include "common.h"
+#include "plan.h"
 #include "pose_math.h"
 
 // ---------------------------------------------------------------------------
@@ -298,17 +299,23 @@ extern "C" int flope_fc1_launch(const float* feat, const float* W1, const float*
                                 int N, void* stream) {
   hipStream_t st = (hipStream_t)stream;
   const size_t lds = (size_t)16 * (K + 4) * sizeof(float);  // 33 KB at K = 512: inside the default dynamic-LDS limit (no per-device attribute)
-  if (W1p && K % 32 == 0 && N % 16 == 0 && lds <= 64 * 1024) {
-    const int waves = 4;                                    // (one wave per workgroup for small batches measured slower: 20.9 vs 19.0 us)
-    const dim3 grid((N / 16 + waves - 1) / waves, (B + 15) / 16);
-    hipLaunchKernelGGL(fc1_packed_kernel<1>, grid, dim3(64 * waves), lds, st, feat, W1p, b1, hidden, B, K, N);
-  } else if (K % 32 == 0 && N % 16 == 0) {
-    const dim3 grid((N / 16 + 3) / 4, (B + 31) / 32);
-    hipLaunchKernelGGL(fc1_kernel, grid, dim3(256), 0, st, feat, W1, b1, hidden, B, K, N);
-  } else {
-    const size_t total = (size_t)B * N;
-    hipLaunchKernelGGL(fc1_simple_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, feat, W1, b1,
-                       hidden, B, K, N);
+  switch (flope_plan::head_fc1_variant(W1p != nullptr, K, N)) {
+    case flope_plan::kFc1Packed: {
+      const int waves = 4;                                  // (one wave per workgroup for small batches measured slower: 20.9 vs 19.0 us)
+      const dim3 grid((N / 16 + waves - 1) / waves, (B + 15) / 16);
+      hipLaunchKernelGGL(fc1_packed_kernel<1>, grid, dim3(64 * waves), lds, st, feat, W1p, b1, hidden, B, K, N);
+      break;
+    }
+    case flope_plan::kFc1RowMajor: {
+      const dim3 grid((N / 16 + 3) / 4, (B + 31) / 32);
+      hipLaunchKernelGGL(fc1_kernel, grid, dim3(256), 0, st, feat, W1, b1, hidden, B, K, N);
+      break;
+    }
+    default: {
+      const size_t total = (size_t)B * N;
+      hipLaunchKernelGGL(fc1_simple_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, feat, W1, b1,
+                         hidden, B, K, N);
+    }
   }
   return (int)hipGetLastError();
 }
@@ -316,6 +323,7 @@ extern "C" int flope_fc1_launch(const float* feat, const float* W1, const float*
 // fc_rot + Procrustes: one wave per image.
 // Optional pose assembly in the same launch (fast_pose_predictor.py:131-144): Rt_out [B,16] = [[R', xyz],[0,0,0,1]] with
 // R' = yaw-nullified R when `nullify`; xyz [B,3] may be NULL (zeros).
+template <bool VEC>                                         // the K loop: 16-byte loads (K % 4 == 0) or scalar; chosen by flope_plan::head_fc2_variant
 __global__ __launch_bounds__(256) void fc2_procrustes_kernel(const float* __restrict__ hidden,
                                                              const float* __restrict__ W2,
                                                              const float* __restrict__ b2, float* r9_out,
@@ -328,7 +336,7 @@ __global__ __launch_bounds__(256) void fc2_procrustes_kernel(const float* __rest
 #pragma unroll
   for (int j = 0; j < 9; ++j) acc[j] = 0.f;
   const float* h = hidden + (size_t)img * K;
-  if ((K & 3) == 0) {
+  if (VEC) {
 #pragma unroll 2
     for (int k = lane * 4; k < K; k += 256) {
       const f32x4 hv = *(const f32x4*)(h + k);
@@ -434,7 +442,7 @@ __global__ __launch_bounds__(256) void fc2_procrustes_k4_kernel(const float* __r
 
 extern "C" int flope_fc2_procrustes_k4_launch(const float* hidden, const float* W2, const float* b2, float* r9, float* R, int B,
                                               int K, const float* xyz, int nullify, float* Rt, void* stream) {
-  if (K % 1024 || B < 1) return 0;
+  if (flope_plan::head_fc2_variant(true, K) != flope_plan::kFc2K4 || B < 1) return 0;
   hipLaunchKernelGGL(fc2_procrustes_k4_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, hidden, W2, b2, r9, R, B, K, xyz, nullify, Rt);
   return hipGetLastError() == hipSuccess ? 1 : -1;
 }
@@ -442,8 +450,10 @@ extern "C" int flope_fc2_procrustes_k4_launch(const float* hidden, const float* 
 extern "C" int flope_fc2_procrustes_launch(const float* hidden, const float* W2, const float* b2, float* r9,
                                            float* R, int B, int K, const float* xyz, int nullify, float* Rt,
                                            void* stream) {
-  hipLaunchKernelGGL(fc2_procrustes_kernel, dim3((B + 3) / 4), dim3(256), 0, (hipStream_t)stream, hidden, W2, b2, r9,
-                     R, B, K, xyz, nullify, Rt);
+  if (flope_plan::head_fc2_variant(false, K) == flope_plan::kFc2WaveVector)
+    hipLaunchKernelGGL(fc2_procrustes_kernel<true>, dim3((B + 3) / 4), dim3(256), 0, (hipStream_t)stream, hidden, W2, b2, r9, R, B, K, xyz, nullify, Rt);
+  else
+    hipLaunchKernelGGL(fc2_procrustes_kernel<false>, dim3((B + 3) / 4), dim3(256), 0, (hipStream_t)stream, hidden, W2, b2, r9, R, B, K, xyz, nullify, Rt);
   return (int)hipGetLastError();
 }
 

@@ -269,6 +269,12 @@ class PoseEngine:
             out.append((layer, kern, fl.value))
         return out
 
+    def head_plan(self):
+        """(fc.0 kernel, fc_rot kernel) a forward launches under the current options: one of _lib.HEAD_FC1, one of _lib.HEAD_FC2."""
+        fc1, fc2 = C.c_int(), C.c_int()
+        _lib.check(self.lib.flope_head_plan(self.handle, C.byref(fc1), C.byref(fc2)), self.handle)
+        return _lib.HEAD_FC1[fc1.value], _lib.HEAD_FC2[fc2.value]
+
     def profile_read(self):
         """per-launch GPU milliseconds of the last forward (needs set_option('profile', 1))."""
         n = self.launches()
@@ -423,6 +429,23 @@ class GuardedPoseEngine:
 
 
 # ---- handle-less kernels ---------------------------------------------------------
+
+def guard_select_rows(M: torch.Tensor, gap_min: float):
+    """test hook: the guard's selection kernel, launched as flope_guard_forward launches it, on M [n, 9] or [n, 3, 3] (float32 on
+    the GPU) -> (gap float32 [n], flagged row indices int32 [count], both on the device; the count the kernel gave the host)."""
+    _require_gpu()
+    d = M.detach().reshape(-1, 9).to(torch.float32).contiguous()
+    if not d.is_cuda:
+        raise RuntimeError("guard_select_rows: M must live on the GPU")
+    n = d.shape[0]
+    gap = torch.empty(n, dtype=torch.float32, device=d.device)
+    sel = torch.full((1 + n,), -1, dtype=torch.int32, device=d.device)
+    with torch.cuda.device(d.device):
+        rc = _lib.load().flope_guard_select_rows(d.data_ptr(), n, float(gap_min), gap.data_ptr(), sel.data_ptr(), _stream_ptr(d.device))
+    if rc < 0:
+        raise RuntimeError(f"flope_amd error {rc}: {(_lib.load().flope_guard_last_error(None) or b'').decode()}")
+    return gap, sel, rc
+
 
 def _as_dev_f32(t: torch.Tensor, cols: int):
     _require_gpu()

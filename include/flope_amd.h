@@ -219,6 +219,11 @@ int flope_launch_info(flope_handle h, int idx, int batch, char* name, int name_c
 int flope_describe_plan(flope_handle h, char* buf, int buflen);
 /* what a handle was created with (max_batch, FLOPE_DT_*, crop height / width, device ordinal); any pointer may be NULL */
 int flope_engine_geometry(flope_handle h, int* max_batch, int* dtype, int* height, int* width, int* device_id);
+/* which kernels the head behind layer4.1 runs on under the handle's current options and backbone_out_dim (flope_amd/csrc/plan.h:
+ * head_plan, the rule the launchers themselves ask).  *fc1: 0 fc1_packed_kernel, 1 fc1_kernel (row-major weights), 2 fc1_simple_kernel;
+ * *fc2: 0 fc2_procrustes_k4_kernel, 1 fc2_procrustes_kernel with 16-byte loads, 2 the same with the scalar K loop.  Either pointer may
+ * be NULL.  (flope_launch_info labels the head's launches "fc1_kernel" / "fc2_procrustes_kernel" whichever ran.) */
+int flope_head_plan(flope_handle h, int* fc1, int* fc2);
 /* library / build identification */
 const char* flope_version(void);
 /* A stream restricted to the compute units set in mask[words] (bit i of word i / 32 = CU i in the runtime's enumeration;
@@ -293,6 +298,11 @@ int flope_guard_forward_repaired(flope_guard_handle g, const void* x_dev, int in
                                  float* r9_dev, float* R_dev, float* Rt_dev, float* gap_dev, void* stream);
 /* test hook: the crops the slot's last repair found flagged, ascending, int32 [n]; returns n */
 int flope_guard_read_selection(flope_guard_handle g, int slot, int32_t* idx_host, int cap);
+/* test hook: guard_select_kernel exactly as flope_guard_forward launches it (one workgroup of 256 threads), on a caller's
+ * M_dev [n, 9] with threshold gap_min, on `stream`.  gap_dev: float32 [n] (may be NULL); sel_dev: int32 [1 + n] -- the number of
+ * flagged rows, then their indices in ascending order.  Waits for the kernel; returns the number of flagged rows (the value the
+ * kernel stored to mapped host memory, as flope_guard_repair reads it), or < 0.  Needs no handle. */
+int flope_guard_select_rows(const float* M_dev, int n, float gap_min, float* gap_dev, int32_t* sel_dev, void* stream);
 /* flope_frame_* over a guard: slot i of the frame uses slot i of the guard (slots <= the guard's).  Crops are float32 NCHW;
  * flope_frame_enqueue calls flope_guard_forward, flope_frame_finish runs flope_guard_repair before it reads the poses (its host
  * wait is where the guard's belongs); a frame with more boxes than the f16 engine's max_batch repairs all but its last forward

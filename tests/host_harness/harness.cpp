@@ -29,6 +29,19 @@ int hh_procrustes_newton_count(const float* M, int n) {
   return c;
 }
 
+// procrustes3x3 with its choice made visible: path[i] = 1 where input i took the Newton fast path, 0 where it fell back to Jacobi
+void hh_procrustes_paths(const float* M, float* R, unsigned char* path, int n) {
+  for (int i = 0; i < n; ++i) {
+    const bool fast = procrustes3x3_newton(M + 9 * i, R + 9 * i);
+    if (!fast) procrustes3x3_jacobi(M + 9 * i, R + 9 * i);
+    path[i] = fast ? 1 : 0;
+  }
+}
+
+void hh_gap(const float* M, float* gap, int n) {
+  for (int i = 0; i < n; ++i) gap[i] = procrustes_gap3x3(M + 9 * i);
+}
+
 void hh_nullify_yaw(const float* R, float* O, int n) {
   for (int i = 0; i < n; ++i) nullify_yaw3x3(R + 9 * i, O + 9 * i);
 }
@@ -136,6 +149,14 @@ int flope_host_option_default(const char* name, int* value) {
   if (!d) return FLOPE_EINVAL;
   *value = flope_plan::PlanOptions().*(d->member);
   return 0;
+}
+
+// the head-kernel rule of plan.h under "name=value,..." options at width bod: fc1 * 16 + fc2, FLOPE_EINVAL for an unknown option
+int flope_host_head_plan(const char* opts, int bod) {
+  flope_plan::PlanOptions o;
+  if (!apply_options(o, opts, nullptr)) return FLOPE_EINVAL;
+  const flope_plan::HeadPlan hp = flope_plan::head_plan(o, bod);
+  return hp.fc1 * 16 + hp.fc2;
 }
 
 }  // extern "C"

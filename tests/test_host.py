@@ -530,3 +530,27 @@ def test_option_table_stores_what_the_recorded_engine_stored(harness):
         assert harness.flope_host_option_default(name.encode(), C.byref(lib_default)) == 0 and lib_default.value == rec["default"], name
     assert harness.flope_host_set_options(b"no_such_option=1", (C.c_int * 2)(), 2) == doc["unknown_option"] == -1
     assert harness.flope_host_plan_dump(224, 224, 4, 1, 256, b"no_such_option=1", 4, C.create_string_buffer(64), 64) == -1
+
+
+def test_head_plan_rule_over_the_widths_the_gpu_head_test_runs(harness):
+    """plan.h: head_plan -- the one statement of which kernel fc.0 and fc_rot run on (pool_head.hip's launchers ask it, flope_head_plan
+    reports it, tests/test_gpu_head.py asserts it per case).  fc.0: 0 packed, 1 row-major, 2 simple; fc_rot: 0 k4, 1 wave with
+    16-byte loads, 2 wave with the scalar K loop."""
+    import ctypes as C
+    harness.flope_host_head_plan.argtypes = [C.c_char_p, C.c_int]
+    P, RM, S, K4, WV, WS = 0, 1, 2, 0, 1, 2
+    want = {  # bod: (defaults, fc1_packed=0, fc2_k4=0)
+        2048: ((P, K4), (RM, K4), (P, WV)), 1024: ((P, K4), (RM, K4), (P, WV)), 3072: ((P, K4), (RM, K4), (P, WV)),
+        4096: ((P, K4), (RM, K4), (P, WV)), 272: ((P, WV), (RM, WV), (P, WV)), 48: ((P, WV), (RM, WV), (P, WV)),
+        16: ((P, WV), (RM, WV), (P, WV)), 1000: ((S, WV), (S, WV), (S, WV)), 1028: ((S, WV), (S, WV), (S, WV)),
+        8: ((S, WV), (S, WV), (S, WV)), 30: ((S, WS), (S, WS), (S, WS)), 1023: ((S, WS), (S, WS), (S, WS)), 1: ((S, WS), (S, WS), (S, WS)),
+    }
+    for bod, rows in want.items():
+        for opts, (fc1, fc2) in zip((b"", b"fc1_packed=0", b"fc2_k4=0"), rows):
+            assert harness.flope_host_head_plan(opts, bod) == fc1 * 16 + fc2, (bod, opts)
+    assert harness.flope_host_head_plan(b"fc1_packed=0,fc2_k4=0", 2048) == RM * 16 + WV
+    assert harness.flope_host_head_plan(b"no_such_option=1", 2048) < 0
+    # the rule as stated, over every width up to 4200: MFMA fc.0 needs whole 16-output tiles, k4 whole 1024-wide quarters' steps
+    for bod in range(1, 4201):
+        got = harness.flope_host_head_plan(b"", bod)
+        assert got == (P if bod % 16 == 0 else S) * 16 + (K4 if bod % 1024 == 0 else WV if bod % 4 == 0 else WS), bod
