@@ -38,8 +38,9 @@
 // tf_attn_tiled's ring and tf_attn16_step's MASKED form over the key blocks of the mask's tile map, which every mask carries beside its
 // bits; tf_attn_tiled's bits where the mask is all-clear, causal, a causal band or block-diagonal at multiples of 32.
 // flope_tf_bias_create (any dtype): an additive float mask -- the allowed set of its -inf entries plus a float32 value per
-// allowed pair, one [L, L] plane or one per head -- on the mask's handle type; a launch under it is tf_attn_biased for every dtype and
-// option: tf_attn_masked's order with bias[h][i][j] added to the scaled score in a rounding of its own, a zero bias giving its bits.
+// allowed pair, one [L, L] plane or one per head -- on the mask's handle type; a launch under it is tf_attn_masked's BIASED instantiation
+// for every dtype and option: the unbiased order with bias[h][i][j] added to the scaled score in a rounding of its own, a zero bias
+// giving its bits (why a flag and not a kernel of its own).
 #include "../../include/flope_amd.h"
 #include "common.h"
 #include "host_pack.h"
@@ -503,10 +504,10 @@ __device__ __forceinline__ void tf_attn_stream_row(const T* chunk, const T* kv, 
   __builtin_amdgcn_wave_barrier();
 }
 
-// ---- attention under a compiled mask (flope_tf_*_masked; the host side is tf_attn_mask.h) ---------------------------------
-// softmax(q k^T / sqrt(dh)) v for query i of one head on one wave, over exactly the keys the mask allows it: bit j % 32 of mw[j / 32]
-// (mw: this wave's copy of row i's mask words in LDS).  first / last: the first and last allowed key of the row, last already clamped
-// to the sequence's last token.  The order, fixed here once:
+// ---- attention under a compiled mask or additive bias (flope_tf_*_masked, flope_tf_bias_create; host side tf_attn_mask.h) ----
+// softmax(q k^T / sqrt(dh) [+ brow]) v for query i of one head on one wave, over exactly the keys the mask allows it: bit j % 32 of
+// mw[j / 32] (mw: this wave's copy of row i's mask words in LDS).  first / last: the first and last allowed key of the row, last already
+// clamped to the sequence's last token.  The order, fixed here once for both instantiations:
 //   score pass  lane l takes keys first + l, first + l + 64, .. up to last.  An allowed key gets tf_attn_row's fmaf chain over
 //               c = 0 .. dh - 1 from 0.f, then * scale, into s[j] and the maximum.  A masked key is skipped: no load, no store to the
 //               score row, not in the maximum.  A 64-key trip in which no lane has an allowed key (one wave-wide vote) issues nothing.
@@ -516,14 +517,24 @@ __device__ __forceinline__ void tf_attn_stream_row(const T* chunk, const T* kv, 
 //               * (1 / sum) and the store as tf_attn_row makes them: float16 in ONE rounding (tf_mul_f16_bits).
 // Where the allowed keys of a row are the contiguous range lo .. hi this is tf_attn_row's order for that range, operation for
 // operation, and so are the bits (tests/test_gpu_tf_mask.py: all-clear, causal, bands and block-diagonal masks against tf_attn_generic's
-// instantiations).  It is a second definition beside tf_attn_row, not a flag on it, for tf_attn_stream_row's reason: what differs is
-// the loops themselves (a vote per trip, a predicate per key, a bit walk in place of the counted value loop), and each would change
-// the loops tf_attn_generic and tf_fused_f32 compile from.
-// A masked key is never addressed, so NaN or Inf in a key that no query allows reaches no output.
+// instantiations).  It is a second definition beside tf_attn_row because the loops themselves differ (a vote per trip, a predicate per
+// key, a bit walk in place of the counted value loop); BIASED is a compile-time flag on it, which costs neither instantiation an
+// instruction of its loops.
+// BIASED (brow: row i of head h's bias plane in global memory, float32, stride the mask's L, indexed by the key's own position j;
+// unread otherwise): ONE change, in the score pass.  After a = fl(chain * scale) the lane that owns key j loads brow[j] and the score is
+// fl(a + brow[j]): a rounding of its own, NOT an fma with the scale (the reference adds the bias to the already scaled, already rounded
+// score; with brow[j] = 0 the score is the unbiased instantiation's bit for bit, which tests/test_gpu_tf_bias.py holds).  The product and
+// the sum are the plain operators in a block under `#pragma clang fp contract(off)`.  The round-to-nearest intrinsics __fmul_rn /
+// __fadd_rn do NOT keep them apart here: this toolchain's header defines both as the plain operators in functions of its own, outside
+// the pragma's lexical reach, and with them -- with and without the pragma -- the compiler contracted the pair into one v_fma_f32 (the
+// -S dump: one fma more and one v_mul_f32 fewer than the unbiased kernel).  As written the dump holds the unbiased kernel's v_fma /
+// v_mul counts and one v_add_f32 more.
+// A masked key is never addressed -- not its k, not its v, not its bias entry (which holds -inf) -- so NaN or Inf in a key that no query
+// allows reaches no output.
 constexpr int kTfMaskUnroll = 8;
-template <typename T>
-__device__ __forceinline__ void tf_attn_masked_row(const T* base, size_t ld, T* orow, float* s, const uint32_t* mw, int i, int first, int last, int d,
-                                                   int dh, float scale, int lane) {
+template <typename T, bool BIASED>
+__device__ __forceinline__ void tf_attn_masked_row(const T* base, size_t ld, T* orow, float* s, const uint32_t* mw, const float* __restrict__ brow, int i,
+                                                   int first, int last, int d, int dh, float scale, int lane) {
   const T* q = base + (size_t)i * ld;
   float mx = -INFINITY;
   for (int j0 = first; j0 <= last; j0 += 64) {
@@ -532,9 +543,15 @@ __device__ __forceinline__ void tf_attn_masked_row(const T* base, size_t ld, T* 
     if (!__builtin_amdgcn_ballot_w64(on)) continue;
     if (on) {
       const T* k = base + (size_t)j * ld + d;
+      float bj = 0.f;
+      if constexpr (BIASED) bj = brow[j];
       float a = 0.f;
       for (int c = 0; c < dh; ++c) a = fmaf(to_f32<T>(q[c]), to_f32<T>(k[c]), a);
-      a *= scale;
+      if constexpr (BIASED) {
+#pragma clang fp contract(off)
+        a = a * scale;
+        a = a + bj;
+      } else a *= scale;
       s[j] = a;
       mx = fmaxf(mx, a);
     }
@@ -586,9 +603,13 @@ __device__ __forceinline__ void tf_attn_masked_row(const T* base, size_t ld, T* 
 // Memory safety does not hang on the tables' contents: a sequence has n <= min(L, Lm) tokens here whatever `off` says about it, row
 // i < n reads the words first / 32 .. last / 32 of its own mask row only, last is clamped to n - 1, and a row whose first is not inside
 // its sequence leaves before its first store (the host refuses such a call: tf_mask_length_row).
-template <typename T, bool VARLEN>
+// BIASED: bias is float32 [planes][Lm][Lm] behind the mask's tables in the same allocation, planes = 1 (every head reads plane 0) or H;
+// otherwise both are unread, and sit behind `off` so that the unbiased kernels find every argument where they always did.  A row reaches
+// tf_attn_masked_row only with i < n <= Lm and first <= last <= n - 1, the plane index is 0 or h < H = planes, and the row loads brow[j]
+// only for an allowed key first <= j <= last -- so every bias address lies inside the planes whatever the tables hold.
+template <typename T, bool VARLEN, bool BIASED>
 __global__ void tf_attn_masked(const T* qkv, T* out, int L, int d, int H, int Lm, const uint32_t* __restrict__ bits, const int* __restrict__ first,
-                               const int* __restrict__ last, const int* __restrict__ off) {
+                               const int* __restrict__ last, const int* __restrict__ off, const float* __restrict__ bias, int planes) {
   extern __shared__ float sc[];                 // [waves][L] | [waves][words]
   const int nw = blockDim.x >> 6, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int b = blockIdx.x / H, h = blockIdx.x - b * H, dh = d / H;
@@ -602,6 +623,8 @@ __global__ void tf_attn_masked(const T* qkv, T* out, int L, int d, int H, int Lm
   float* s = sc + (size_t)wave * L;
   uint32_t* mw = (uint32_t*)(sc + (size_t)nw * L) + (size_t)wave * words;
   const T* base = VARLEN ? qkv + row0 * 3 * d + h * dh : qkv + (size_t)b * L * 3 * d + h * dh;
+  const float* plane = nullptr;
+  if constexpr (BIASED) plane = bias + (size_t)(planes > 1 ? h : 0) * Lm * Lm;
   for (int i = blockIdx.y * nw + wave; i < n; i += gridDim.y * nw) {
     const int fi = __builtin_amdgcn_readfirstlane(first[i]);
     int la = __builtin_amdgcn_readfirstlane(last[i]);
@@ -610,118 +633,8 @@ __global__ void tf_attn_masked(const T* qkv, T* out, int L, int d, int H, int Lm
     if (la < fi) continue;
     for (int w = (fi >> 5) + lane; w <= (la >> 5); w += 64) mw[w] = bits[(size_t)i * words + w];
     __builtin_amdgcn_wave_barrier();
-    tf_attn_masked_row<T>(base, (size_t)3 * d, out + ((VARLEN ? row0 : (size_t)b * L) + i) * d + h * dh, s, mw, i, fi, la, d, dh, scale, lane);
-  }
-}
-
-// ---- attention under a compiled additive bias (flope_tf_bias_create; the host side is tf_attn_mask.h) ----------------------
-// softmax_j(q k_j / sqrt(dh) + brow[j]) v over exactly the allowed keys of query i: tf_attn_masked_row's order with ONE change in the
-// score pass.  brow: row i of head h's bias plane in global memory (float32, stride the mask's L), indexed by the key's own position j.
-// After a = fl(chain * scale) the lane that owns key j loads brow[j] and the score is fl(a + brow[j]): a rounding of its own, NOT an fma
-// with the scale (the reference adds the bias to the already scaled, already rounded score; with brow[j] = 0 the score is
-// tf_attn_masked_row's bit for bit, which tests/test_gpu_tf_bias.py holds).  The product and the sum are the plain operators in a block
-// under `#pragma clang fp contract(off)`.  The round-to-nearest intrinsics __fmul_rn / __fadd_rn do NOT keep them apart here: this
-// toolchain's header defines both as the plain operators in functions of its own, outside the pragma's lexical reach, and with them
-// -- with and without the pragma -- the compiler contracted the pair into one v_fma_f32 (the -S dump: one fma more and one v_mul_f32
-// fewer than tf_attn_masked).  As written the dump holds tf_attn_masked's v_fma / v_mul counts and one v_add_f32 more.
-// Max, sum and value passes are tf_attn_masked_row's, statement for statement.
-// A third definition beside tf_attn_row and tf_attn_masked_row, for the reason given there: a flag on tf_attn_masked_row would change
-// the loops tf_attn_masked compiles from.  A masked key is never addressed -- not its k, not its v, not its bias entry (which holds -inf).
-template <typename T>
-__device__ __forceinline__ void tf_attn_biased_row(const T* base, size_t ld, T* orow, float* s, const uint32_t* mw, const float* __restrict__ brow, int i,
-                                                   int first, int last, int d, int dh, float scale, int lane) {
-  const T* q = base + (size_t)i * ld;
-  float mx = -INFINITY;
-  for (int j0 = first; j0 <= last; j0 += 64) {
-    const int j = j0 + lane;
-    const bool on = j <= last && ((mw[j >> 5] >> (j & 31)) & 1u);
-    if (!__builtin_amdgcn_ballot_w64(on)) continue;
-    if (on) {
-      const T* k = base + (size_t)j * ld + d;
-      const float bj = brow[j];
-      float a = 0.f;
-      for (int c = 0; c < dh; ++c) a = fmaf(to_f32<T>(q[c]), to_f32<T>(k[c]), a);
-      {
-#pragma clang fp contract(off)
-        a = a * scale;
-        a = a + bj;
-      }
-      s[j] = a;
-      mx = fmaxf(mx, a);
-    }
-  }
-  mx = wave_max(mx);
-  float sum = 0.f;
-  for (int j0 = first; j0 <= last; j0 += 64) {
-    const int j = j0 + lane;
-    const bool on = j <= last && ((mw[j >> 5] >> (j & 31)) & 1u);
-    if (on) { const float p = expf(s[j] - mx); s[j] = p; sum += p; }
-  }
-  sum = wave_sum(sum);
-  __builtin_amdgcn_wave_barrier();
-  const float inv = 1.f / sum;
-  const int w0 = first >> 5, w1 = last >> 5;
-  for (int c = lane; c < dh; c += 64) {
-    const T* v = base + 2 * d + c;
-    float o = 0.f;
-    for (int w = w0; w <= w1; ++w) {
-      uint32_t m = __builtin_amdgcn_readfirstlane(mw[w]);
-      if (w == w0) m &= ~0u << (first & 31);
-      if (w == w1) m &= (2u << (last & 31)) - 1u;
-      const int jb = w * 32;
-      while (__builtin_popcount(m) >= kTfMaskUnroll) {
-        int js[kTfMaskUnroll];
-        float vv[kTfMaskUnroll];
-#pragma unroll
-        for (int u = 0; u < kTfMaskUnroll; ++u) { js[u] = jb + __builtin_ctz(m); m &= m - 1u; }
-#pragma unroll
-        for (int u = 0; u < kTfMaskUnroll; ++u) vv[u] = to_f32<T>(v[(size_t)js[u] * ld]);
-#pragma unroll
-        for (int u = 0; u < kTfMaskUnroll; ++u) o = fmaf(s[js[u]], vv[u], o);
-      }
-      while (m) {
-        const int j = jb + __builtin_ctz(m);
-        m &= m - 1u;
-        o = fmaf(s[j], to_f32<T>(v[(size_t)j * ld]), o);
-      }
-    }
-    if constexpr (std::is_same<T, f16_t>::value) *(unsigned short*)(orow + c) = (unsigned short)tf_mul_f16_bits(o, inv);
-    else orow[c] = from_f32<T>(o * inv);
-  }
-  __builtin_amdgcn_wave_barrier();
-}
-
-// tf_attn_masked's workgroup, grid, LDS and row guards (tf_mask_launch, unchanged), plus the bias: float32 [planes][Lm][Lm] behind the
-// mask's tables in the same allocation, planes = 1 (every head reads plane 0) or H.  Memory safety as there, and for the bias: a row
-// reaches tf_attn_biased_row only with i < n <= Lm and first <= last <= n - 1, the plane index is 0 or h < H = planes, and the row
-// loads brow[j] only for an allowed key first <= j <= last -- so every bias address lies inside the planes whatever the tables hold.
-template <typename T, bool VARLEN>
-__global__ void tf_attn_biased(const T* qkv, T* out, int L, int d, int H, int Lm, const uint32_t* __restrict__ bits, const int* __restrict__ first,
-                               const int* __restrict__ last, const float* __restrict__ bias, int planes, const int* __restrict__ off) {
-  extern __shared__ float sc[];                 // [waves][L] | [waves][words]
-  const int nw = blockDim.x >> 6, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int b = blockIdx.x / H, h = blockIdx.x - b * H, dh = d / H;
-  const int words = flope_tf_plan::tf_mask_words(Lm);
-  const float scale = 1.f / sqrtf((float)dh);
-  size_t row0 = 0;                              // first row of this sequence
-  int n = L;
-  if constexpr (VARLEN) { row0 = (size_t)off[b]; n = off[b + 1] - off[b]; }
-  if (n > L) n = L;
-  if (n > Lm) n = Lm;
-  float* s = sc + (size_t)wave * L;
-  uint32_t* mw = (uint32_t*)(sc + (size_t)nw * L) + (size_t)wave * words;
-  const T* base = VARLEN ? qkv + row0 * 3 * d + h * dh : qkv + (size_t)b * L * 3 * d + h * dh;
-  const float* plane = bias + (size_t)(planes > 1 ? h : 0) * Lm * Lm;
-  for (int i = blockIdx.y * nw + wave; i < n; i += gridDim.y * nw) {
-    const int fi = __builtin_amdgcn_readfirstlane(first[i]);
-    int la = __builtin_amdgcn_readfirstlane(last[i]);
-    if ((unsigned)fi >= (unsigned)n) continue;
-    if (la > n - 1) la = n - 1;
-    if (la < fi) continue;
-    for (int w = (fi >> 5) + lane; w <= (la >> 5); w += 64) mw[w] = bits[(size_t)i * words + w];
-    __builtin_amdgcn_wave_barrier();
-    tf_attn_biased_row<T>(base, (size_t)3 * d, out + ((VARLEN ? row0 : (size_t)b * L) + i) * d + h * dh, s, mw, plane + (size_t)i * Lm, i, fi, la, d, dh, scale,
-                          lane);
+    tf_attn_masked_row<T, BIASED>(base, (size_t)3 * d, out + ((VARLEN ? row0 : (size_t)b * L) + i) * d + h * dh, s, mw,
+                                  BIASED ? plane + (size_t)i * Lm : nullptr, i, fi, la, d, dh, scale, lane);
   }
 }
 
@@ -1387,6 +1300,37 @@ __global__ __launch_bounds__(1024) void tf_attn_mfma(const T* __restrict__ qkv, 
   }
 }
 
+// The staging role of a thread in the ring of tf_attn_tiled and tf_attn_tiled_masked (tf_attn16_extend: below): HD32 16-byte
+// chunks of K and of V per 64-key block -- key row srow and element ssrc of the block, swizzled bytes sdk / sdv in an LDS stage
+// [K block [64][RB] | V block [64][RB]] -- and the registers kr / vr a block waits in between its loads and its LDS writes.  Each kernel
+// fills kr / vr in a gload of its own (where a row comes from and when it is zeros is what they differ in); lwrite is the same.
+// tf_attn16_extend takes the constants from here and keeps the role written out: see there.
+template <int HD32>
+struct TfTiledStaging {
+  static constexpr int RB = 64 * HD32, NCH = 4 * HD32;             // bytes and 16-byte chunks of a row
+  static constexpr int KB = flope_tf_plan::kTfAttnTiledKB, BLK = KB * RB, STAGE = 2 * BLK;
+  static_assert(flope_tf_plan::kTfAttnTiledRing == 2 && KB == 64, "the kernels' loops are written for two stages of two 32-key steps");
+  int srow[HD32], ssrc[HD32], sdk[HD32], sdv[HD32];
+  u32x4 kr[HD32], vr[HD32];
+  __device__ __forceinline__ void init(int tid) {
+#pragma unroll
+    for (int i = 0; i < HD32; ++i) {
+      const int idx = tid + i * 256, row = idx / NCH, ch = idx - row * NCH;
+      srow[i] = row;
+      ssrc[i] = ch * 8;
+      sdk[i] = row * RB + ((ch ^ tf_tiled_kswz<HD32>(row)) << 4);
+      sdv[i] = BLK + row * RB + ((ch ^ tf_tiled_vswz<HD32>(row)) << 4);
+    }
+  }
+  __device__ __forceinline__ void lwrite(char* s) const {          // s: the stage
+#pragma unroll
+    for (int i = 0; i < HD32; ++i) {
+      *(u32x4*)(s + sdk[i]) = kr[i];
+      *(u32x4*)(s + sdv[i]) = vr[i];
+    }
+  }
+};
+
 // tf_attn_tiled (option attn_tiled): K and V streamed instead of resident.  Workgroup = 128 queries of one
 // (batch, head): four waves of 32 queries; grid (B H, ceil(L / 128)).  Keys arrive in blocks of kTfAttnTiledKB = 64 (two 32-key
 // steps) through a ring of kTfAttnTiledRing = 2 LDS stages (K block | V block).  Register staging: block t + 1 is loaded into VGPRs
@@ -1411,9 +1355,7 @@ __global__ __launch_bounds__(256, 2) void tf_attn_tiled(const T* __restrict__ qk
                                                         float scale_log2e, const int* __restrict__ off, int W) {
   static_assert(CAUSAL || !WINDOW, "a window without causal has no meaning");
   typedef typename Elem<T>::frag frag;
-  constexpr int HD = 32 * HD32, RB = 64 * HD32, NCH = 4 * HD32;     // head_dim, bytes and 16-byte chunks of a row
-  constexpr int KB = flope_tf_plan::kTfAttnTiledKB, BLK = KB * RB, STAGE = 2 * BLK;
-  static_assert(flope_tf_plan::kTfAttnTiledRing == 2 && KB == 64, "the loop below is written for two stages of two 32-key steps");
+  constexpr int HD = 32 * HD32, KB = TfTiledStaging<HD32>::KB, BLK = TfTiledStaging<HD32>::BLK, STAGE = TfTiledStaging<HD32>::STAGE;
   extern __shared__ __attribute__((aligned(16))) char smem[];      // [2 stages][K block [64][RB] | V block [64][RB]]
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, g = lane >> 4, li = lane & 15;
   const int b = blockIdx.x / H, h = blockIdx.x - b * H;
@@ -1425,40 +1367,23 @@ __global__ __launch_bounds__(256, 2) void tf_attn_tiled(const T* __restrict__ qk
   const T* base = VARLEN ? qkv + row0 * 3 * d + h * HD : qkv + (size_t)b * L * 3 * d + h * HD;
   const int nb = CAUSAL ? flope_tf_plan::tf_causal_tiled_blocks((int)blockIdx.y, L) : (L + KB - 1) / KB;
 
-  // staging role: HD32 chunks of K and of V per thread and block
-  int srow[HD32], ssrc[HD32], sdk[HD32], sdv[HD32];
-#pragma unroll
-  for (int i = 0; i < HD32; ++i) {
-    const int idx = tid + i * 256, row = idx / NCH, ch = idx - row * NCH;
-    srow[i] = row;
-    ssrc[i] = ch * 8;
-    sdk[i] = row * RB + ((ch ^ tf_tiled_kswz<HD32>(row)) << 4);
-    sdv[i] = BLK + row * RB + ((ch ^ tf_tiled_vswz<HD32>(row)) << 4);
-  }
-  u32x4 kr[HD32], vr[HD32];
+  TfTiledStaging<HD32> sg;
+  sg.init(tid);
   auto gload = [&](int kb0) {
 #pragma unroll
     for (int i = 0; i < HD32; ++i) {
-      const int row = kb0 + srow[i];
-      const T* src = base + (size_t)(row < L ? row : L - 1) * 3 * d + ssrc[i];
+      const int row = kb0 + sg.srow[i];
+      const T* src = base + (size_t)(row < L ? row : L - 1) * 3 * d + sg.ssrc[i];
       const u32x4 kv = *(const u32x4*)(src + d), vv = *(const u32x4*)(src + 2 * d);
       const u32x4 z = {0, 0, 0, 0};
-      kr[i] = row < L ? kv : z;
-      vr[i] = row < L ? vv : z;
-    }
-  };
-  auto lwrite = [&](int stage) {
-    char* s = smem + stage * STAGE;
-#pragma unroll
-    for (int i = 0; i < HD32; ++i) {
-      *(u32x4*)(s + sdk[i]) = kr[i];
-      *(u32x4*)(s + sdv[i]) = vr[i];
+      sg.kr[i] = row < L ? kv : z;
+      sg.vr[i] = row < L ? vv : z;
     }
   };
   int t0 = 0;
   if constexpr (WINDOW) t0 = flope_tf_plan::tf_window_tiled_first_block((int)blockIdx.y, W);
-  if constexpr (WINDOW) { gload(t0 * KB); lwrite(t0 & 1); }
-  else { gload(0); lwrite(0); }
+  if constexpr (WINDOW) { gload(t0 * KB); sg.lwrite(smem + (t0 & 1) * STAGE); }
+  else { gload(0); sg.lwrite(smem); }
 
   const int q0 = blockIdx.y * flope_tf_plan::kTfAttnTiledQueries + wave * 32;
   frag qf[2][HD32];
@@ -1494,7 +1419,7 @@ __global__ __launch_bounds__(256, 2) void tf_attn_tiled(const T* __restrict__ qk
       } else
       tf_attn16_step<T, HD32, CAUSAL>(Ki, Vi, kb, kl, L, q0, scale_log2e, ln, qf, mrun, lrun, o);
     }
-    lwrite((t + 1) & 1);
+    sg.lwrite(smem + ((t + 1) & 1) * STAGE);
   }
   tf_attn16_store<T, HD32>(out, VARLEN ? row0 : (size_t)b * L, d, h * HD, q0, L, lane, lrun, o);
 }
@@ -1520,9 +1445,7 @@ __global__ __launch_bounds__(256, 2) void tf_attn_tiled_masked(const T* __restri
                                                                const uint32_t* __restrict__ bits, const int* __restrict__ start,
                                                                const flope_tf_plan::TfMaskTile* __restrict__ tiles) {
   typedef typename Elem<T>::frag frag;
-  constexpr int HD = 32 * HD32, RB = 64 * HD32, NCH = 4 * HD32;     // head_dim, bytes and 16-byte chunks of a row
-  constexpr int KB = flope_tf_plan::kTfAttnTiledKB, BLK = KB * RB, STAGE = 2 * BLK;
-  static_assert(flope_tf_plan::kTfAttnTiledRing == 2 && KB == 64, "the loop below is written for two stages of two 32-key steps");
+  constexpr int HD = 32 * HD32, KB = TfTiledStaging<HD32>::KB, BLK = TfTiledStaging<HD32>::BLK, STAGE = TfTiledStaging<HD32>::STAGE;
   extern __shared__ __attribute__((aligned(16))) char smem[];      // [2 stages][K block [64][RB] | V block [64][RB]]
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), g = lane >> 4, li = lane & 15;
   const int b = blockIdx.x / H, h = blockIdx.x - b * H;
@@ -1536,35 +1459,18 @@ __global__ __launch_bounds__(256, 2) void tf_attn_tiled_masked(const T* __restri
   int e1 = start[blockIdx.y + 1];
   if constexpr (VARLEN) { while (e1 - 1 > e0 && tiles[e1 - 1].kblock * KB >= L) --e1; }      // the corner's prefix; its first entry always stays
 
-  // staging role: HD32 chunks of K and of V per thread and block
-  int srow[HD32], ssrc[HD32], sdk[HD32], sdv[HD32];
-#pragma unroll
-  for (int i = 0; i < HD32; ++i) {
-    const int idx = tid + i * 256, row = idx / NCH, ch = idx - row * NCH;
-    srow[i] = row;
-    ssrc[i] = ch * 8;
-    sdk[i] = row * RB + ((ch ^ tf_tiled_kswz<HD32>(row)) << 4);
-    sdv[i] = BLK + row * RB + ((ch ^ tf_tiled_vswz<HD32>(row)) << 4);
-  }
-  u32x4 kr[HD32], vr[HD32];
+  TfTiledStaging<HD32> sg;
+  sg.init(tid);
   auto gload = [&](int kb0, uint32_t clo, uint32_t chi) {
 #pragma unroll
     for (int i = 0; i < HD32; ++i) {
-      const int row = kb0 + srow[i];
-      const T* src = base + (size_t)(row < L ? row : L - 1) * 3 * d + ssrc[i];
+      const int row = kb0 + sg.srow[i];
+      const T* src = base + (size_t)(row < L ? row : L - 1) * 3 * d + sg.ssrc[i];
       const u32x4 kv = *(const u32x4*)(src + d), vv = *(const u32x4*)(src + 2 * d);
       const u32x4 z = {0, 0, 0, 0};
-      const bool keep = row < L && (((srow[i] < 32 ? clo : chi) >> (srow[i] & 31)) & 1u);
-      kr[i] = keep ? kv : z;
-      vr[i] = keep ? vv : z;
-    }
-  };
-  auto lwrite = [&](int stage) {
-    char* s = smem + stage * STAGE;
-#pragma unroll
-    for (int i = 0; i < HD32; ++i) {
-      *(u32x4*)(s + sdk[i]) = kr[i];
-      *(u32x4*)(s + sdv[i]) = vr[i];
+      const bool keep = row < L && (((sg.srow[i] < 32 ? clo : chi) >> (sg.srow[i] & 31)) & 1u);
+      sg.kr[i] = keep ? kv : z;
+      sg.vr[i] = keep ? vv : z;
     }
   };
   // the entry of a trip, the same for every lane
@@ -1579,7 +1485,7 @@ __global__ __launch_bounds__(256, 2) void tf_attn_tiled_masked(const T* __restri
   uint32_t clo, chi, cls, nclo, nchi, ncls;
   entry(e0, kblock, clo, chi, cls);
   gload(kblock * KB, clo, chi);
-  lwrite(0);
+  sg.lwrite(smem);
 
   const int q0 = blockIdx.y * flope_tf_plan::kTfAttnTiledQueries + wave * 32;
   frag qf[2][HD32];
@@ -1621,7 +1527,7 @@ __global__ __launch_bounds__(256, 2) void tf_attn_tiled_masked(const T* __restri
       }
       tf_attn16_step<T, HD32, false, false, true>(Ki, Vi, kb, kl, L, q0, scale_log2e, ln, qf, mrun, lrun, o, 0, mw);
     }
-    lwrite((trip + 1) & 1);
+    sg.lwrite(smem + ((trip + 1) & 1) * STAGE);
     kblock = nkblock; clo = nclo; chi = nchi; cls = ncls;
   }
   tf_attn16_store<T, HD32>(out, VARLEN ? row0 : (size_t)b * L, d, h * HD, q0, L, lane, lrun, o);
@@ -1649,9 +1555,8 @@ __global__ __launch_bounds__(256, 2) void tf_attn16_extend(const T* __restrict__
                                                            const int* __restrict__ tab, const int* __restrict__ off, int n, int d, int H,
                                                            int tracks, int capacity, float scale_log2e, int W) {
   typedef typename Elem<T>::frag frag;
-  constexpr int HD = 32 * HD32, RB = 64 * HD32, NCH = 4 * HD32;
-  constexpr int KB = flope_tf_plan::kTfAttnTiledKB, BLK = KB * RB, STAGE = 2 * BLK;
-  static_assert(flope_tf_plan::kTfAttnTiledRing == 2 && KB == 64, "the loop below is written for two stages of two 32-key steps");
+  typedef TfTiledStaging<HD32> Stg;                                // its constants alone: the role is written out below
+  constexpr int HD = 32 * HD32, RB = Stg::RB, NCH = Stg::NCH, KB = Stg::KB, BLK = Stg::BLK, STAGE = Stg::STAGE;
   extern __shared__ __attribute__((aligned(16))) char smem[];      // [2 stages][K block [64][RB] | V block [64][RB]]
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, g = lane >> 4, li = lane & 15;
   const int b = blockIdx.x / H, h = blockIdx.x - b * H, y = (int)blockIdx.y;
@@ -1665,7 +1570,8 @@ __global__ __launch_bounds__(256, 2) void tf_attn16_extend(const T* __restrict__
   const T* kv = cache + (size_t)track * capacity * 2 * d + h * HD;           // cache row r: k at + 0, v at + d
   const int t0 = flope_tf_plan::tf_extend_mfma_first_block(pos0, y, Wk), t1 = flope_tf_plan::tf_extend_mfma_last_block(pos0, len, y);
 
-  // staging role: HD32 chunks of K and of V per thread and block
+  // staging role: TfTiledStaging's, statement for statement.  Through the struct the four linear instantiations compile to other code
+  // in front of and inside the block loop (head_dim 128: 3 instructions fewer, outside the +-2 this merge was held to)
   int srow[HD32], ssrc[HD32], sdk[HD32], sdv[HD32];
 #pragma unroll
   for (int i = 0; i < HD32; ++i) {
@@ -2170,6 +2076,15 @@ template <typename F> int tf_by_dtype(const flope_tf_encoder* e, F&& f) {
   return f(TfType<bf16_t>{});
 }
 
+// f(std::integral_constant<int, HD32>{}) for the head_dim = 32 HD32 of a launch on the 16-bit ring kernels (32 / 64 / 96 / 128: their
+// picks answer for no other)
+template <typename F> void tf_by_hd32(int dh, F&& f) {
+  if (dh == 32) f(std::integral_constant<int, 1>{});
+  else if (dh == 64) f(std::integral_constant<int, 2>{});
+  else if (dh == 96) f(std::integral_constant<int, 3>{});
+  else f(std::integral_constant<int, 4>{});
+}
+
 // [N][K] fp32 -> [N/128][K/64][128 rows][8 slots x 8 k] 16-bit, rows permuted so that MFMA row 4g+q of channel tile
 // ct is feature 16g + 4ct + q of the wave's 64-feature half, slots pre-swizzled (slot j holds chunk j ^ ((r>>1)&7)).
 std::vector<uint16_t> pack_linear(const float* W, int N, int K, int dtype) {
@@ -2292,41 +2207,21 @@ int launch_attention(flope_tf_encoder* e, const void* qkv, void* att, int B, int
                           : tf_attn_pick(e->dtype, dh, L, e->opt_generic, e->opt_f32m, e->opt_tiled, aligned16);
   const TfAttnLaunch l = tf_attn_varlen_launch(pick, dh, B, H, L);
   const dim3 grid(l.grid_x, l.grid_y), block(l.block);
-  if (window) {
-    auto launch_w = [&](auto varlen) {
-      constexpr bool VL = decltype(varlen)::value;
-      if constexpr (!std::is_same<T, float>::value) {
-        if (pick == FLOPE_TF_ATTN_MFMA64) {
-          hipLaunchKernelGGL((tf_attn_mfma<T, VL, true, true>), grid, block, l.lds, st, (const T*)qkv, (T*)att, L, d, H, tf_attn_pad32(L),
-                             1.4426950408889634f / sqrtf(64.f), e->opt_window, off);
-        } else if (pick == FLOPE_TF_ATTN_TILED) {
-          const float scale_log2e = 1.4426950408889634f / sqrtf((float)dh);
-#define TF_ATT(HD32_) hipLaunchKernelGGL((tf_attn_tiled<T, HD32_, VL, true, true>), grid, block, l.lds, st, (const T*)qkv, (T*)att, L, d, H, scale_log2e, off, e->opt_window)
-          if (dh == 32) TF_ATT(1); else if (dh == 64) TF_ATT(2); else if (dh == 96) TF_ATT(3); else TF_ATT(4);
-#undef TF_ATT
-        }
-      }
-      if (pick == FLOPE_TF_ATTN_GENERIC)
-        hipLaunchKernelGGL((tf_attn_generic<T, VL, true, true>), grid, block, l.lds, st, (const T*)qkv, (T*)att, L, d, H, e->opt_window, off);
-    };
-    if (off) launch_w(std::true_type{}); else launch_w(std::false_type{});
-    TF_HIP(e, hipGetLastError());
-    return pick;
-  }
-  auto launch = [&](auto varlen, auto causal) {
-    constexpr bool VL = decltype(varlen)::value, CA = decltype(causal)::value;
+  const int W = window ? e->opt_window : 0;      // kernel, grid, block and LDS of a causal launch are those of the option at 0
+  auto launch = [&](auto varlen, auto causal, auto win) {
+    constexpr bool VL = decltype(varlen)::value, CA = decltype(causal)::value, WIN = decltype(win)::value;
     if constexpr (!std::is_same<T, float>::value) {
       if (pick == FLOPE_TF_ATTN_MFMA64) {
-        hipLaunchKernelGGL((tf_attn_mfma<T, VL, CA>), grid, block, l.lds, st, (const T*)qkv, (T*)att, L, d, H, tf_attn_pad32(L),
-                           1.4426950408889634f / sqrtf(64.f), 0, off);
+        hipLaunchKernelGGL((tf_attn_mfma<T, VL, CA, WIN>), grid, block, l.lds, st, (const T*)qkv, (T*)att, L, d, H, tf_attn_pad32(L),
+                           1.4426950408889634f / sqrtf(64.f), W, off);
       } else if (pick == FLOPE_TF_ATTN_TILED) {
         const float scale_log2e = 1.4426950408889634f / sqrtf((float)dh);
-#define TF_ATT(HD32_) hipLaunchKernelGGL((tf_attn_tiled<T, HD32_, VL, CA>), grid, block, l.lds, st, (const T*)qkv, (T*)att, L, d, H, scale_log2e, off, 0)
-        if (dh == 32) TF_ATT(1); else if (dh == 64) TF_ATT(2); else if (dh == 96) TF_ATT(3); else TF_ATT(4);
-#undef TF_ATT
+        tf_by_hd32(dh, [&](auto hd32) {
+          hipLaunchKernelGGL((tf_attn_tiled<T, decltype(hd32)::value, VL, CA, WIN>), grid, block, l.lds, st, (const T*)qkv, (T*)att, L, d, H, scale_log2e, off, W);
+        });
       }
     }
-    if constexpr (std::is_same<T, float>::value) {
+    if constexpr (std::is_same<T, float>::value && !WIN) {       // no F32M under a window: tf_attn_pick_window never answers it
       if (pick == FLOPE_TF_ATTN_F32M) {
         const int nt = tf_attn_f32m_nt(dh);
         const float scale = 1.f / sqrtf((float)dh);
@@ -2336,11 +2231,14 @@ int launch_attention(flope_tf_encoder* e, const void* qkv, void* att, int B, int
       }
     }
     if (pick == FLOPE_TF_ATTN_GENERIC)
-      hipLaunchKernelGGL((tf_attn_generic<T, VL, CA>), grid, block, l.lds, st, (const T*)qkv, (T*)att, L, d, H, 0, off);
+      hipLaunchKernelGGL((tf_attn_generic<T, VL, CA, WIN>), grid, block, l.lds, st, (const T*)qkv, (T*)att, L, d, H, W, off);
   };
-  if (e->opt_causal) {                           // kernel, grid, block and LDS are those of the option at 0
-    if (off) launch(std::true_type{}, std::true_type{}); else launch(std::false_type{}, std::true_type{});
-  } else if (off) launch(std::true_type{}, std::false_type{}); else launch(std::false_type{}, std::false_type{});
+  auto by_varlen = [&](auto causal, auto win) {
+    if (off) launch(std::true_type{}, causal, win); else launch(std::false_type{}, causal, win);
+  };
+  if (window) by_varlen(std::true_type{}, std::true_type{});   // a window only under causal
+  else if (e->opt_causal) by_varlen(std::true_type{}, std::false_type{});
+  else by_varlen(std::false_type{}, std::false_type{});
   TF_HIP(e, hipGetLastError());
   return pick;
 }
@@ -2577,14 +2475,11 @@ extern "C" int flope_tf_create(int device_id, int input_dim, int model_dim, int 
     for (const void* f : masked16)
       if (hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)flope_tf_plan::tf_attn_tiled_lds(128)) != hipSuccess)
         return fin(tf_fail(nullptr, FLOPE_EHIP, "flope_tf_create: hipFuncSetAttribute failed"));
-    const void* const masked[] = {(const void*)tf_attn_masked<float, false>, (const void*)tf_attn_masked<float, true>, (const void*)tf_attn_masked<f16_t, false>,
-                                  (const void*)tf_attn_masked<f16_t, true>, (const void*)tf_attn_masked<bf16_t, false>, (const void*)tf_attn_masked<bf16_t, true>};
+#define TF_MASKED(BI_) (const void*)tf_attn_masked<float, false, BI_>, (const void*)tf_attn_masked<float, true, BI_>, (const void*)tf_attn_masked<f16_t, false, BI_>, \
+                       (const void*)tf_attn_masked<f16_t, true, BI_>, (const void*)tf_attn_masked<bf16_t, false, BI_>, (const void*)tf_attn_masked<bf16_t, true, BI_>
+    const void* const masked[] = {TF_MASKED(false), TF_MASKED(true)};
+#undef TF_MASKED
     for (const void* f : masked)                     // four score rows of up to max_tokens floats and the mask words behind them
-      if (hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kTfAttnLds) != hipSuccess)
-        return fin(tf_fail(nullptr, FLOPE_EHIP, "flope_tf_create: hipFuncSetAttribute failed"));
-    const void* const biased[] = {(const void*)tf_attn_biased<float, false>, (const void*)tf_attn_biased<float, true>, (const void*)tf_attn_biased<f16_t, false>,
-                                  (const void*)tf_attn_biased<f16_t, true>, (const void*)tf_attn_biased<bf16_t, false>, (const void*)tf_attn_biased<bf16_t, true>};
-    for (const void* f : biased)                     // tf_attn_masked's LDS
       if (hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kTfAttnLds) != hipSuccess)
         return fin(tf_fail(nullptr, FLOPE_EHIP, "flope_tf_create: hipFuncSetAttribute failed"));
     if (hipDeviceGetAttribute(&e->cus, hipDeviceAttributeMultiprocessorCount, device_id) != hipSuccess || e->cus < 1) e->cus = 256;
@@ -2908,50 +2803,39 @@ namespace {
 // always is plus the mask rows in LDS (tf_mask_launch), unless option mask_mfma sends a 16-bit launch to tf_attn_tiled_masked, launched
 // as tf_attn_tiled is (tf_mask16_launch).  off == nullptr: qkv [B][L][3 d], L == m->L; otherwise the packed rows of a ragged batch, L
 // its longest length.  Returns the kernel's FLOPE_TF_ATTN_* id, or < 0.
-// A handle that carries a bias (m->planes > 0) takes tf_attn_biased on every dtype and under every option, launched by
-// tf_mask_launch as tf_attn_masked is.
+// A handle that carries a bias (m->planes > 0) takes tf_attn_masked's BIASED instantiation on every dtype and under every
+// option, launched by tf_mask_launch as the unbiased one is.
 int tf_masked_pick(const flope_tf_encoder* e, const flope_tf_mask* m, const void* qkv, const void* att) {
   if (m->planes) return FLOPE_TF_ATTN_BIASED;
   return flope_tf_plan::tf_attn_pick_masked(e->dtype, e->d / e->H, e->opt_generic, e->opt_mask_mfma, !(((uintptr_t)qkv | (uintptr_t)att) & 15));
 }
 template <typename T>
 int launch_attention_masked(flope_tf_encoder* e, const flope_tf_mask* m, const void* qkv, void* att, int B, int L, const int* off, hipStream_t st) {
-  if constexpr (!std::is_same<T, float>::value) {
-    if (tf_masked_pick(e, m, qkv, att) == FLOPE_TF_ATTN_MASKED16) {
-      const int dh = e->d / e->H;
-      const flope_tf_plan::TfAttnLaunch l = flope_tf_plan::tf_mask16_launch(dh, B, e->H, L);
-      const dim3 grid(l.grid_x, l.grid_y), block(l.block);
-      const float scale_log2e = 1.4426950408889634f / sqrtf((float)dh);
-      auto launch = [&](auto varlen) {
-        constexpr bool VL = decltype(varlen)::value;
-#define TF_ATT(HD32_) hipLaunchKernelGGL((tf_attn_tiled_masked<T, HD32_, VL>), grid, block, l.lds, st, (const T*)qkv, (T*)att, L, e->d, e->H, scale_log2e, off, \
-                                         flope_tf_plan::tf_mask_words(m->L), m->bits_dev(), m->start_dev(), m->tiles_dev())
-        if (dh == 32) TF_ATT(1); else if (dh == 64) TF_ATT(2); else if (dh == 96) TF_ATT(3); else TF_ATT(4);
-#undef TF_ATT
-      };
-      if (off) launch(std::true_type{}); else launch(std::false_type{});
-      TF_HIP(e, hipGetLastError());
-      return FLOPE_TF_ATTN_MASKED16;
-    }
-  }
-  const flope_tf_plan::TfAttnLaunch l = flope_tf_plan::tf_mask_launch(e->d / e->H, B, e->H, L, m->L);
+  const int dh = e->d / e->H, pick = tf_masked_pick(e, m, qkv, att);
+  const flope_tf_plan::TfAttnLaunch l = pick == FLOPE_TF_ATTN_MASKED16 ? flope_tf_plan::tf_mask16_launch(dh, B, e->H, L)
+                                                                       : flope_tf_plan::tf_mask_launch(dh, B, e->H, L, m->L);
   const dim3 grid(l.grid_x, l.grid_y), block(l.block);
-  if (m->planes) {
-    if (off)
-      hipLaunchKernelGGL((tf_attn_biased<T, true>), grid, block, l.lds, st, (const T*)qkv, (T*)att, L, e->d, e->H, m->L, m->bits_dev(), m->first_dev(), m->last_dev(),
-                         m->bias_dev(), m->planes, off);
-    else
-      hipLaunchKernelGGL((tf_attn_biased<T, false>), grid, block, l.lds, st, (const T*)qkv, (T*)att, L, e->d, e->H, m->L, m->bits_dev(), m->first_dev(), m->last_dev(),
-                         m->bias_dev(), m->planes, off);
-    TF_HIP(e, hipGetLastError());
-    return FLOPE_TF_ATTN_BIASED;
-  }
-  if (off)
-    hipLaunchKernelGGL((tf_attn_masked<T, true>), grid, block, l.lds, st, (const T*)qkv, (T*)att, L, e->d, e->H, m->L, m->bits_dev(), m->first_dev(), m->last_dev(), off);
-  else
-    hipLaunchKernelGGL((tf_attn_masked<T, false>), grid, block, l.lds, st, (const T*)qkv, (T*)att, L, e->d, e->H, m->L, m->bits_dev(), m->first_dev(), m->last_dev(), off);
+  auto launch = [&](auto varlen, auto biased) {
+    constexpr bool VL = decltype(varlen)::value, BI = decltype(biased)::value;
+    if constexpr (!std::is_same<T, float>::value && !BI) {
+      if (pick == FLOPE_TF_ATTN_MASKED16) {
+        const float scale_log2e = 1.4426950408889634f / sqrtf((float)dh);
+        tf_by_hd32(dh, [&](auto hd32) {
+          hipLaunchKernelGGL((tf_attn_tiled_masked<T, decltype(hd32)::value, VL>), grid, block, l.lds, st, (const T*)qkv, (T*)att, L, e->d, e->H, scale_log2e, off,
+                             flope_tf_plan::tf_mask_words(m->L), m->bits_dev(), m->start_dev(), m->tiles_dev());
+        });
+        return;
+      }
+    }
+    hipLaunchKernelGGL((tf_attn_masked<T, VL, BI>), grid, block, l.lds, st, (const T*)qkv, (T*)att, L, e->d, e->H, m->L, m->bits_dev(), m->first_dev(), m->last_dev(), off,
+                       BI ? m->bias_dev() : nullptr, m->planes);
+  };
+  auto by_varlen = [&](auto biased) {
+    if (off) launch(std::true_type{}, biased); else launch(std::false_type{}, biased);
+  };
+  if (m->planes) by_varlen(std::true_type{}); else by_varlen(std::false_type{});
   TF_HIP(e, hipGetLastError());
-  return FLOPE_TF_ATTN_MASKED;
+  return pick;
 }
 
 // The checks every masked call starts with, before anything is enqueued.  lengths == NULL: a fixed-length batch of `batch` sequences of
@@ -2985,6 +2869,41 @@ int tf_masked_check(flope_tf_encoder* e, const std::string& who, const flope_tf_
   return 0;
 }
 
+// What flope_tf_mask_create and flope_tf_bias_create end in once m->bits are final (m->L and m->planes set, every validator passed): the
+// first / last tables, the pair count and the tile map on the host (under a bias host only: what flope_tf_mask_tiles reports), one
+// allocation laid out by tf_mask_dev_* / tf_bias_dev_* (tf_attn_mask.h) with bits | first | last and behind them the tile map or the
+// bias planes, and the mask on the handle's list.  Owns m: a failure frees it.
+int tf_mask_finish(flope_tf_encoder* e, const std::string& who, flope_tf_mask* m, const float* bias_host, flope_tf_mask_handle* out) {
+  using namespace flope_tf_plan;
+  const int L = m->L, planes = m->planes;
+  m->first.resize(L);
+  m->last.resize(L);
+  tf_mask_first_last(m->bits.data(), L, m->first.data(), m->last.data());
+  m->pairs = tf_mask_pairs(m->bits.data(), L);
+  m->start.resize((size_t)tf_mask_query_blocks(L) + 1);
+  m->tiles.resize((size_t)tf_mask_tiles_build(m->bits.data(), L, m->start.data(), nullptr));
+  tf_mask_tiles_build(m->bits.data(), L, m->start.data(), m->tiles.data());
+  const size_t nb = m->bits.size() * sizeof(uint32_t), nt = (size_t)L * sizeof(int);
+  const size_t all = planes ? tf_bias_dev_bytes(L, planes) : tf_mask_dev_bytes(L, (long long)m->tiles.size());
+  auto fin = [&](const std::string& what) { hipFree(m->dev); delete m; return tf_fail(e, FLOPE_EHIP, who + ": " + what); };
+  auto put = [&](size_t at, const void* src, size_t bytes) { return hipMemcpy((char*)m->dev + at, src, bytes, hipMemcpyHostToDevice) == hipSuccess; };
+  if (hipSetDevice(e->device) != hipSuccess) return fin("hipSetDevice failed");
+  if (hipMalloc(&m->dev, all) != hipSuccess) {
+    m->dev = nullptr;
+    return fin("hipMalloc of " + std::to_string(all) + " bytes failed" +
+               (planes ? " (" + std::to_string(planes) + " float32 planes of " + std::to_string((size_t)L * L * 4) + " bytes)" : std::string()));
+  }
+  if (!put(0, m->bits.data(), nb) || !put(nb, m->first.data(), nt) || !put(nb + nt, m->last.data(), nt) ||
+      !(planes ? put(tf_bias_dev_bias_at(L), bias_host, (size_t)planes * L * L * sizeof(float))
+               : put(tf_mask_dev_start_at(L), m->start.data(), m->start.size() * sizeof(int)) &&
+                     put(tf_mask_dev_tiles_at(L), m->tiles.data(), m->tiles.size() * sizeof(TfMaskTile))))
+    return fin("hipMemcpy failed");
+  m->e = e;
+  e->masks.push_back(m);
+  *out = m;
+  return FLOPE_OK;
+}
+
 }  // namespace
 
 extern "C" int flope_tf_mask_create(flope_tf_handle e, int seq_len, const uint32_t* allow_bits_host, flope_tf_mask_handle* out) {
@@ -3004,27 +2923,7 @@ extern "C" int flope_tf_mask_create(flope_tf_handle e, int seq_len, const uint32
   flope_tf_mask* m = new flope_tf_mask();
   m->L = seq_len;
   m->bits.assign(allow_bits_host, allow_bits_host + (size_t)seq_len * tf_mask_words(seq_len));
-  m->first.resize(seq_len);
-  m->last.resize(seq_len);
-  tf_mask_first_last(m->bits.data(), seq_len, m->first.data(), m->last.data());
-  m->pairs = tf_mask_pairs(m->bits.data(), seq_len);
-  m->start.resize((size_t)tf_mask_query_blocks(seq_len) + 1);
-  m->tiles.resize((size_t)tf_mask_tiles_build(m->bits.data(), seq_len, m->start.data(), nullptr));
-  tf_mask_tiles_build(m->bits.data(), seq_len, m->start.data(), m->tiles.data());
-  const size_t nb = m->bits.size() * sizeof(uint32_t), nt = (size_t)seq_len * sizeof(int), all = tf_mask_dev_bytes(seq_len, (long long)m->tiles.size());
-  auto fin = [&](const std::string& what) { hipFree(m->dev); delete m; return tf_fail(e, FLOPE_EHIP, who + ": " + what); };
-  if (hipSetDevice(e->device) != hipSuccess) return fin("hipSetDevice failed");
-  if (hipMalloc(&m->dev, all) != hipSuccess) { m->dev = nullptr; return fin("hipMalloc of " + std::to_string(all) + " bytes failed"); }
-  if (hipMemcpy(m->dev, m->bits.data(), nb, hipMemcpyHostToDevice) != hipSuccess ||
-      hipMemcpy((char*)m->dev + nb, m->first.data(), nt, hipMemcpyHostToDevice) != hipSuccess ||
-      hipMemcpy((char*)m->dev + nb + nt, m->last.data(), nt, hipMemcpyHostToDevice) != hipSuccess ||
-      hipMemcpy((char*)m->dev + tf_mask_dev_start_at(seq_len), m->start.data(), m->start.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess ||
-      hipMemcpy((char*)m->dev + tf_mask_dev_tiles_at(seq_len), m->tiles.data(), m->tiles.size() * sizeof(TfMaskTile), hipMemcpyHostToDevice) != hipSuccess)
-    return fin("hipMemcpy failed");
-  m->e = e;
-  e->masks.push_back(m);
-  *out = m;
-  return FLOPE_OK;
+  return tf_mask_finish(e, who, m, nullptr, out);
 }
 
 // A compiled additive bias: the mask of its -inf entries plus a float32 value per allowed pair, on the same handle type
@@ -3055,29 +2954,7 @@ extern "C" int flope_tf_bias_create(flope_tf_handle e, int seq_len, int planes, 
     delete m;
     return tf_fail(e, FLOPE_EINVAL, who + ": row " + std::to_string(row) + " has no allowed key (a softmax over nothing; the reference returns NaN there)");
   }
-  m->first.resize(seq_len);
-  m->last.resize(seq_len);
-  tf_mask_first_last(m->bits.data(), seq_len, m->first.data(), m->last.data());
-  m->pairs = tf_mask_pairs(m->bits.data(), seq_len);
-  m->start.resize((size_t)tf_mask_query_blocks(seq_len) + 1);               // host only: what flope_tf_mask_tiles reports
-  m->tiles.resize((size_t)tf_mask_tiles_build(m->bits.data(), seq_len, m->start.data(), nullptr));
-  tf_mask_tiles_build(m->bits.data(), seq_len, m->start.data(), m->tiles.data());
-  const size_t nb = m->bits.size() * sizeof(uint32_t), nt = (size_t)seq_len * sizeof(int), all = tf_bias_dev_bytes(seq_len, planes);
-  auto fin = [&](const std::string& what) { hipFree(m->dev); delete m; return tf_fail(e, FLOPE_EHIP, who + ": " + what); };
-  if (hipSetDevice(e->device) != hipSuccess) return fin("hipSetDevice failed");
-  if (hipMalloc(&m->dev, all) != hipSuccess) {
-    m->dev = nullptr;
-    return fin("hipMalloc of " + std::to_string(all) + " bytes failed (" + std::to_string(planes) + " float32 planes of " + std::to_string((size_t)seq_len * seq_len * 4) + " bytes)");
-  }
-  if (hipMemcpy(m->dev, m->bits.data(), nb, hipMemcpyHostToDevice) != hipSuccess ||
-      hipMemcpy((char*)m->dev + nb, m->first.data(), nt, hipMemcpyHostToDevice) != hipSuccess ||
-      hipMemcpy((char*)m->dev + nb + nt, m->last.data(), nt, hipMemcpyHostToDevice) != hipSuccess ||
-      hipMemcpy((char*)m->dev + tf_bias_dev_bias_at(seq_len), bias_host, (size_t)planes * seq_len * seq_len * sizeof(float), hipMemcpyHostToDevice) != hipSuccess)
-    return fin("hipMemcpy failed");
-  m->e = e;
-  e->masks.push_back(m);
-  *out = m;
-  return FLOPE_OK;
+  return tf_mask_finish(e, who, m, bias_host, out);
 }
 
 extern "C" int flope_tf_mask_bias_planes(flope_tf_mask_handle m) {
@@ -3314,12 +3191,13 @@ int launch_extend_attn(flope_tf_stream_s* s, int plan, const T* qkv, const T* ca
       const int dh = tf_head_dim(e);
       const flope_tf_plan::TfExtendLaunch lm = flope_tf_plan::tf_extend_mfma_launch(n, e->H, max_len, dh);
       const float scale_log2e = 1.4426950408889634f / sqrtf((float)dh);
-#define TF_EXTM(HD32_, WIN_) hipLaunchKernelGGL((tf_attn16_extend<T, HD32_, WIN_>), dim3(lm.grid_x, lm.grid_y), dim3(lm.block), lm.lds, st, qkv, cache, att, \
-                                               (const int*)s->tab, (const int*)e->vl_off, n, e->d, e->H, s->tracks, s->capacity, scale_log2e, s->window)
-#define TF_EXTM2(HD32_) do { if (s->window) TF_EXTM(HD32_, true); else TF_EXTM(HD32_, false); } while (0)
-      if (dh == 32) TF_EXTM2(1); else if (dh == 64) TF_EXTM2(2); else if (dh == 96) TF_EXTM2(3); else TF_EXTM2(4);
-#undef TF_EXTM2
-#undef TF_EXTM
+      auto launch = [&](auto hd32, auto win) {
+        hipLaunchKernelGGL((tf_attn16_extend<T, decltype(hd32)::value, decltype(win)::value>), dim3(lm.grid_x, lm.grid_y), dim3(lm.block), lm.lds, st, qkv, cache, att,
+                           (const int*)s->tab, (const int*)e->vl_off, n, e->d, e->H, s->tracks, s->capacity, scale_log2e, s->window);
+      };
+      tf_by_hd32(dh, [&](auto hd32) {
+        if (s->window) launch(hd32, std::true_type{}); else launch(hd32, std::false_type{});
+      });
     } else {
       return tf_fail(e, FLOPE_EINVAL, "tf_attn16_extend has no float32 form");
     }

@@ -394,7 +394,7 @@ class TransformerEncoder:
             with torch.cuda.device(self.device):
                 self._check_arg(self.lib.flope_tf_forward_masked(self.handle, x.data_ptr(), B, L, lh, mask.handle, y.data_ptr(), _stream_ptr(self.device)))
             self.last_forward_fused = False
-            self.last_attn_kernel = self.lib.flope_tf_last_forward_masked(self.handle)       # tf_attn_masked, tf_attn_tiled_masked under mask_mfma, tf_attn_biased under a bias
+            self.last_attn_kernel = self.lib.flope_tf_last_forward_masked(self.handle)       # tf_attn_masked, tf_attn_tiled_masked under mask_mfma, its BIASED instantiation under a bias
             self._keep = x
             return y
         causal, band = _mask_window(mask, L)
@@ -430,7 +430,7 @@ class TransformerEncoder:
         `mask` (a compiled one, make_mask): softmax over the allowed keys only, by tf_attn_masked (`last_attn_kernel` = 4) for every
         dtype and shape, or, on a 16-bit encoder with `mask_mfma=1` and head_dim 32 / 64 / 96 / 128, by tf_attn_tiled_masked
         (`last_attn_kernel` = 5); with `lengths` each sequence under the mask's corner.  A compiled bias (make_bias) is
-        passed the same way and runs tf_attn_biased (`last_attn_kernel` = 6) on every dtype and under every option."""
+        passed the same way and runs the BIASED instantiation of tf_attn_masked (`last_attn_kernel` = 6) on every dtype and under every option."""
         if mask is not None and not isinstance(mask, TransformerEncoderMask):
             raise ValueError("attention() takes a compiled mask (enc.make_mask), not a tensor")
         if mask is not None:
@@ -597,7 +597,7 @@ class TransformerEncoderMask:
     """An [L, L] attention mask compiled for one encoder (include/flope_amd.h: flope_tf_mask_*): the allowed (query, key)
     pairs as bits on the device, made once by `enc.make_mask(mask)` and passed as `mask=` to any number of forwards.  `L`: the
     sequence length it was made for; `allowed`: the number of allowed pairs; `planes`: 0, or the 1 or num_heads float32 planes of an
-    additive bias when it was made by `enc.make_bias(bias)` (attention then runs tf_attn_biased); `tile_stats`: what option `mask_mfma` walks,
+    additive bias when it was made by `enc.make_bias(bias)` (attention then runs the BIASED instantiation of tf_attn_masked); `tile_stats`: what option `mask_mfma` walks,
     a dict of query_blocks (of 128 rows), blocks_listed (64-key blocks over all of them) and steps_none / steps_some / steps_all (the 8
     (wave, 32-key step) tiles of every listed block by class).  It keeps its encoder alive; after enc.close() or its own
     close() its use raises RuntimeError."""

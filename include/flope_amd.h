@@ -651,7 +651,7 @@ int flope_tf_mask_tiles(flope_tf_mask_handle m, int* query_blocks, long long* bl
  *             enqueued, the index (plane, row, col) in flope_tf_last_error: NULL arguments, seq_len < 1 or > max_tokens, planes
  *             neither 1 nor num_heads, an entry that is +inf or NaN, a plane whose masked entries differ from plane 0's (a per-head
  *             difference is written as a large negative finite value), a row without a key.
- *             Attention under a bias runs tf_attn_biased (FLOPE_TF_ATTN_BIASED = 6, what _attention_masked returns and
+ *             Attention under a bias runs the BIASED instantiation of tf_attn_masked (FLOPE_TF_ATTN_BIASED = 6, what _attention_masked returns and
  *             _last_forward_masked reports) on every dtype and under every option, "mask_mfma", "f32mfma" and "generic" included:
  *             tf_attn_masked's order with the one add, so an all-zero bias gives tf_attn_masked's bits for the same allowed set.
  *   _mask_bias_planes  the planes of a compiled bias, 0 for a plain mask. */

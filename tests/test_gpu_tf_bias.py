@@ -1,7 +1,7 @@
 """An additive attention bias, per head, compiled once, on the device (enc.make_bias, forward / attention(..., mask=<compiled bias>);
 DESIGN.md 39).
 
-The contract: a compiled bias runs tf_attn_biased on every dtype and under every option -- tf_attn_masked's order with one float32 add
+The contract: a compiled bias runs the BIASED instantiation of tf_attn_masked on every dtype and under every option -- the unbiased order with one float32 add
 of the pair's bias after the scale -- so a zero bias over an allowed set is enc.make_mask of that set IN BITS (and so, by DESIGN.md 37,
 the causal / window / ragged kernels' bits where those hold), equal planes are the one plane, a masked key is never loaded (not its k,
 not its v, not its bias entry); every other bias is held element-wise to fp64 within the bound of tests/tf_attn_bias_bound.py, and the
@@ -137,7 +137,7 @@ def test_equal_planes_are_the_one_plane(sds, shape, dtype):
 
 @pytest.mark.parametrize("dtype", ["f16", "bf16"])
 def test_mask_mfma_handle_returns_the_same_bits(sds, dtype):
-    """a bias keeps tf_attn_biased on a handle whose masks run the MFMA kernel, and under `generic`"""
+    """a bias keeps the BIASED tf_attn_masked on a handle whose masks run the MFMA kernel, and under `generic`"""
     L = 65
     plain, mfma = _encoder(WIDE, sds["wide"], dtype, 2 * L), _encoder(WIDE, sds["wide"], dtype, 2 * L, mask_mfma=1)
     qkv = MB.make_qkv(2, L, 2, 64, dtype).cuda()

@@ -1,4 +1,4 @@
-"""Checker of the encoder's attention under a compiled additive bias (tf_attn_biased_row in flope_amd/csrc/tf_encoder.hip; DESIGN.md
+"""Checker of the encoder's attention under a compiled additive bias (tf_attn_masked_row<T, BIASED> in flope_amd/csrc/tf_encoder.hip; DESIGN.md
 39): the fp64 restatement of the whole biased forward, the test biases, an element-wise bound for the biased attention row, and an
 emulation of the row's walk that can be broken the way this kernel breaks.  Helper of tests/test_tf_bias_bound.py (CPU: the
 restatement against the reference's fixture, the bound against the emulation and its broken copies) and tests/test_gpu_tf_bias.py

@@ -8,7 +8,7 @@ The handle is the build-defined cfg5 (d = 384, 6 heads, 12 layers, f16) at B = 6
 at the whole forward:
 
   mask   (a) the compiled causal mask: tf_attn_masked
-  bias   (b) the per-head causal ALiBi bias (slopes 2^-(h + 1)): tf_attn_biased -- the same walk plus one float32 load and one add
+  bias   (b) the per-head causal ALiBi bias (slopes 2^-(h + 1)): tf_attn_masked<T, VARLEN, BIASED = true> -- the same walk plus one float32 load and one add
          per allowed pair
 
 Nothing is gated: the feature replaces nothing.  Recorded beside the times: the bias bytes one launch reads, H * L^2 * 4 per layer
