@@ -19,6 +19,7 @@
 #include <stdint.h>
 #include <string>
 #include "../../include/flope_amd.h"
+#include "frame_plan.h"
 #include "guard.h"
 
 namespace {
@@ -60,33 +61,25 @@ int ffail(flope_frame* f, int code, const std::string& msg) {
   return code;
 }
 
-// (:55-56) float32 xyxy -> int16 like numpy's astype (truncation toward zero; the detector clips its boxes to the frame, so the
-// value is in range), then squarify_bb / bb_in_frame in integer arithmetic exactly as sunflower/utils/mvg.py states them
+// (:55-56) float32 xyxy -> int16 like numpy's astype, then squarify_bb / bb_in_frame in integer arithmetic exactly as
+// sunflower/utils/mvg.py states them: frame_plan.h's frame_count and frame_box (one definition, shared with the CPU tests); here
+// only the order: 64 rows per pass, a ballot for the ranks, the kept boxes of earlier passes carried in `base`
 __global__ __launch_bounds__(64) void frame_select_kernel(const float* __restrict__ det, const int* __restrict__ count, int max_det,
                                                           int H, int W, int cap, int32_t* __restrict__ boxes, int* __restrict__ nsel) {
   const int lane = threadIdx.x;
-  int n = *count;
-  n = n < 0 ? 0 : (n > max_det ? max_det : n);
+  const int n = frame_count(*count, max_det);
   int base = 0;
   for (int i0 = 0; i0 < n; i0 += 64) {
     const int i = i0 + lane;
     bool keep = false;
-    int x0 = 0, y0 = 0, x1 = 0, y1 = 0, sx0 = 0, sy0 = 0, sx1 = 0, sy1 = 0;
-    if (i < n) {
-      x0 = (int)(short)(int)det[i * 8 + 0]; y0 = (int)(short)(int)det[i * 8 + 1];
-      x1 = (int)(short)(int)det[i * 8 + 2]; y1 = (int)(short)(int)det[i * 8 + 3];
-      const int w = x1 - x0, h = y1 - y0, d = w > h ? w - h : h - w;
-      const int lo = (d + 1) / 2, hi = d / 2;                       // the min edge moves by ceil(d / 2), the max edge by floor(d / 2)
-      sx0 = x0; sy0 = y0; sx1 = x1; sy1 = y1;
-      if (w > h) { sy0 -= lo; sy1 += hi; } else if (h > w) { sx0 -= lo; sx1 += hi; }
-      keep = !(sx0 < 0 || sy0 < 0 || sx1 > W || sy1 > H);           // xmax == w and ymax == h are accepted
-    }
+    int good[4] = {0, 0, 0, 0}, sq[4] = {0, 0, 0, 0};
+    if (i < n) keep = frame_box(det + (size_t)i * kFrameDetRow, W, H, good, sq);
     const unsigned long long m = __ballot(keep);
     const int rank = base + __popcll(m & ((1ull << lane) - 1ull));
     if (keep && rank < cap) {
-      boxes[rank * 4 + 0] = x0; boxes[rank * 4 + 1] = y0; boxes[rank * 4 + 2] = x1; boxes[rank * 4 + 3] = y1;
-      int32_t* s = boxes + (size_t)cap * 4 + rank * 4;
-      s[0] = sx0; s[1] = sy0; s[2] = sx1; s[3] = sy1;
+      int32_t *g = boxes + rank * 4, *s = boxes + (size_t)cap * 4 + rank * 4;
+      g[0] = good[0]; g[1] = good[1]; g[2] = good[2]; g[3] = good[3];
+      s[0] = sq[0]; s[1] = sq[1]; s[2] = sq[2]; s[3] = sq[3];
     }
     base += __popcll(m);
   }
@@ -193,18 +186,33 @@ extern "C" int flope_frame_enqueue(flope_frame_handle f, int slot, const uint8_t
   if (slot < 0 || slot >= f->nslots || !frame_dev || !mask_dev || !depth_dev || !K4_host) return ffail(f, FLOPE_EINVAL, "flope_frame_enqueue: bad slot / NULL input");
   Slot& s = f->slots[slot];
   if (s.state != 1) return ffail(f, FLOPE_ESTATE, "flope_frame_enqueue: call flope_frame_select for this slot first");
-  if (hipSetDevice(f->device) != hipSuccess) return ffail(f, FLOPE_EHIP, "hipSetDevice failed");
-  if (hipEventSynchronize(s.ev_sel) != hipSuccess) return ffail(f, FLOPE_EHIP, "flope_frame_enqueue: waiting for the box count failed");
+  // Every negative return from here on leaves the slot idle (state 0) and, on a guarded handle, the guard slot un-armed: a slot left
+  // in state 2 by a failed call would let flope_frame_finish wait on an event of an earlier frame and return that frame's rows.
+  if (hipSetDevice(f->device) != hipSuccess) { s.state = 0; return ffail(f, FLOPE_EHIP, "hipSetDevice failed"); }
+  if (hipEventSynchronize(s.ev_sel) != hipSuccess) { s.state = 0; return ffail(f, FLOPE_EHIP, "flope_frame_enqueue: waiting for the box count failed"); }
   const int n = s.nsel_host[0];
   if (s.nsel_host[1] > f->cap) { s.state = 0; return ffail(f, FLOPE_EINVAL, "flope_frame_enqueue: more in-frame boxes than max_boxes (" + std::to_string(s.nsel_host[1]) + ")"); }
+  // What flope_depth_lift refuses before it launches anything is refused here first, whatever the number of boxes.
+  if (!(depth_div > 0.f) || depth_format < 0 || depth_format > 1) {
+    s.state = 0;
+    return ffail(f, FLOPE_EINVAL, "flope_frame_enqueue: depth_div must be > 0 and depth_format 0 (uint16) or 1 (float32)");
+  }
   s.n = n; s.state = 2;
   hipStream_t st = (hipStream_t)stream;
-  if (n == 0) return hipEventRecord(s.ev_done, st) == hipSuccess ? 0 : ffail(f, FLOPE_EHIP, "hipEventRecord failed");
+  if (n == 0) {
+    if (hipEventRecord(s.ev_done, st) == hipSuccess) return 0;
+    s.state = 0;
+    return ffail(f, FLOPE_EHIP, "hipEventRecord failed");
+  }
   if (flope_depth_lift(depth_dev, depth_format, mask_dev, f->H, f->W, depth_div, near_plane, far_plane, s.boxes, n, K4_host, s.depth_scratch, s.dv,
-                       s.rel, s.xyz, stream) != 0)
+                       s.rel, s.xyz, stream) != 0) {
+    s.state = 0;
     return ffail(f, FLOPE_EHIP, "flope_frame_enqueue: depth lift failed");
-  if (flope_crop_resize_mask(frame_dev, mask_dev, f->H, f->W, s.boxes + (size_t)f->cap * 4, n, f->crop, f->fmt, s.crops, stream) != 0)
+  }
+  if (flope_crop_resize_mask(frame_dev, mask_dev, f->H, f->W, s.boxes + (size_t)f->cap * 4, n, f->crop, f->fmt, s.crops, stream) != 0) {
+    s.state = 0;
     return ffail(f, FLOPE_EHIP, "flope_frame_enqueue: crop kernel failed");
+  }
   s.stream = stream;
   for (int off = 0; f->guard && off < n; off += f->eng_maxB) {
     // guarded: the f16 forward and the guard's selection per chunk; every chunk but the last is repaired here (one guard slot holds
@@ -219,11 +227,12 @@ extern "C" int flope_frame_enqueue(flope_frame_handle f, int slot, const uint8_t
     const int m = n - off < f->eng_maxB ? n - off : f->eng_maxB;
     const int rc = flope_forward_poses(f->eng, (const char*)s.crops + (size_t)off * f->crop_bytes, f->fmt, m, s.xyz + (size_t)off * 3, 1, nullptr, nullptr,
                                        s.Rt + (size_t)off * 16, stream);
-    if (rc != FLOPE_OK) return ffail(f, rc, std::string("flope_frame_enqueue: ") + flope_last_error(f->eng));
+    if (rc != FLOPE_OK) { s.state = 0; return ffail(f, rc, std::string("flope_frame_enqueue: ") + flope_last_error(f->eng)); }
   }
   if (hipMemcpyAsync(s.Rt_host, s.Rt, (size_t)n * 16 * sizeof(float), hipMemcpyDeviceToHost, st) != hipSuccess ||
       hipMemcpyAsync(s.rel_host, s.rel, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, st) != hipSuccess || hipEventRecord(s.ev_done, st) != hipSuccess) {
-    if (f->guard) { flope_guard_cancel(f->guard, slot); s.state = 0; }
+    if (f->guard) flope_guard_cancel(f->guard, slot);
+    s.state = 0;
     return ffail(f, FLOPE_EHIP, "flope_frame_enqueue: result copy failed");
   }
   return n;
@@ -244,8 +253,8 @@ extern "C" int flope_frame_finish(flope_frame_handle f, int slot, double* poses_
       return ffail(f, FLOPE_EHIP, "flope_frame_finish: copy of the repaired poses failed");
     }
   }
+  s.state = 0;                                                     // whatever happens below, the slot is idle afterwards
   if (hipSetDevice(f->device) != hipSuccess || hipEventSynchronize(s.ev_done) != hipSuccess) return ffail(f, FLOPE_EHIP, "flope_frame_finish: waiting for the poses failed");
-  s.state = 0;
   s.gap_n = s.n;
   int k = 0;
   for (int i = 0; i < s.n; ++i) {

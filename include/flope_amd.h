@@ -246,6 +246,10 @@ int flope_stream_destroy(int device_id, void* stream);
  *                        returns n (0 = the reference's `None`)
  * flope_frame_to_poses = the three in sequence on slot 0.  max_boxes bounds the in-frame boxes of one frame (ultralytics' max_det = 300);
  * a frame with more is refused by flope_frame_enqueue.  More boxes than the engine's max_batch run as several forwards.
+ * Call order: enqueue without select, finish without enqueue, or select on a slot that holds an unfinished frame is FLOPE_ESTATE
+ * and changes nothing; a failed call leaves the slot idle (and, on a guarded handle, its guard slot un-armed): flope_frame_finish
+ * on it is FLOPE_ESTATE and returns no rows, and the next flope_frame_select is accepted.  flope_frame_enqueue refuses
+ * depth_div <= 0 and an unknown depth_format itself, before anything is launched.
  * The PoseResNet engine must outlive the frame handle and must not run another forward concurrently. */
 typedef struct flope_frame* flope_frame_handle;
 int flope_frame_create(flope_handle pose_engine, int frame_h, int frame_w, int max_boxes, int slots, flope_frame_handle* out);
