@@ -19,6 +19,7 @@ TF_LIN_GENERIC, TF_LIN_ROWWAVE, TF_LIN_ROWWAVE_VEC, TF_LIN_MFMA, TF_LIN_F32M = 0
 TF_FWD_LAUNCHES, TF_FWD_FUSED = 0, 1                                           # flope_tf_forward_plan's return
 TF_EXTEND_ROW, TF_EXTEND_SPLIT, TF_EXTEND_MFMA = 0, 1, 2                         # flope_tf_stream_extend_plan's / _attention_extend's return
 TF_STEP_ROW, TF_STEP_SPLIT = 0, 1                                              # flope_tf_stream_step_plan's / _attention's return
+TF_STEP_BIASED, TF_EXTEND_BIASED = 2, 3                                        # ... on a state with a distance table (flope_tf_stream_open_bias)
 TF_LN_SCALAR, TF_LN_VEC = 0, 1                                                 # flope_tf_layernorm's return
 STAGE_STEM, STAGE_POOL, STAGE_FEAT, STAGE_HIDDEN = 0, 1, 10, 11
 HEAD_FC1 = ("packed", "row-major", "simple")                                   # flope_head_plan's *fc1 (plan.h: HeadFc1)
@@ -122,6 +123,9 @@ SIGNATURES = {
     "flope_tf_last_forward": (_I, [_P]),
     "flope_tf_stream_open": (_I, [_P, _I, _I, C.POINTER(_P)]),
     "flope_tf_stream_open_window": (_I, [_P, _I, _I, _I, C.POINTER(_P)]),
+    # ... with a distance table, a relative attention bias [planes][distances]
+    "flope_tf_stream_open_bias": (_I, [_P, _I, _I, _I, _I, _I, C.POINTER(C.c_float), C.POINTER(_P)]),
+    "flope_tf_stream_bias_planes": (_I, [_P]),
     "flope_tf_stream_close": (_I, [_P]),
     "flope_tf_stream_reset": (_I, [_P, _I, C.POINTER(_I)]),
     "flope_tf_stream_position": (_I, [_P, _I]),

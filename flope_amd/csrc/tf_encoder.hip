@@ -22,6 +22,8 @@
 // track, with tf_attn_step over a per-track cache of every layer's keys and values where the forward has its attention kernel
 // (the checks and launch shapes are in tf_encoder_stream.h).  flope_tf_stream_open_window: the same over a ring cache
 // with sliding-window attention, never full.
+// flope_tf_stream_open_bias: a state with a distance table [planes][D], a relative bias such as ALiBi -- step, extend and
+// prefill run the BIASED instantiations of tf_attn_step / tf_attn_extend, the bits of the forward under the expanded compiled bias.
 // flope_tf_stream_extend: several tokens per track and call behind what the track holds -- the ragged launch sequence over the packed
 // chunks with tf_attn_extend over cache and chunk, tf_cache_append behind it in every layer; the bits of the same steps.
 // Option step_split = 1 (any dtype): _step and _extend run tf_attn_step_split / tf_attn_extend_split where tf_step_split_ok --
@@ -405,6 +407,16 @@ template <typename T, bool VEC> struct TfSlice {
 // at s[j - lo] (the loops count from key lo: an absolute position may be near INT_MAX).
 // ONE: the caller's promise that the chunk is the single row `chunk` (i = 0), which is what a step is: then nc = p - lo, c0 = 0 and
 // the last run is one row.  Without it the compiler cannot see that and unrolls the last run again.
+// BIASED (a state with a distance table, flope_tf_stream_open_bias; brel: the head's row of the table in global memory,
+// float32 [D], indexed by the distance p - key; unread otherwise): ONE change, in the score pass, the one tf_attn_masked_row<T, true>
+// makes.  The lane that owns the visible key with index j (0 .. L - 1 counted from lo, as s[j] is) loads brel[L - 1 - j]
+// (tf_stream_bias_index: the query's own key has distance 0), and the score is fl(fl(chain * scale) + brel[L - 1 - j]): the product
+// and the sum are the plain operators under `#pragma clang fp contract(off)`, two roundings, never one fma -- so over the contiguous key
+// range lo .. p this row is tf_attn_masked_row<T, true>'s, operation for operation, and with a zero table the unbiased row's.  The
+// caller guarantees L <= D (tf_stream_bias_keys_ok), so 0 <= L - 1 - j <= D - 1.  The table is read from global memory, as the planes
+// of a compiled bias are, not staged in LDS: an entry is read once per row, by one lane, a trip's 64 entries are one contiguous 256
+// bytes, and no other wave of the workgroup shares them in a step (every wave is another track or head) -- staging would add a barrier
+// and LDS beside score rows that already take up to 64 KiB.
 constexpr int kTfStepUnroll = 16;
 // (float16)(a * b) in ONE rounding, as bits: what the compiler makes of tf_attn_row's `from_f32<f16_t>(o * inv)`, one v_fma_mixlo_f16.
 // A packed store of two such products (v_mul_f32, then v_cvt_pk_f16_f32) rounds to float32 first and to float16 second, and the two
@@ -416,9 +428,9 @@ __device__ __forceinline__ unsigned tf_mul_f16_bits(float a, float b) {
   asm("v_fma_mixlo_f16 %0, %1, %2, 0" : "+v"(r) : "v"(a), "v"(b));
   return r & 0xffffu;
 }
-template <typename T, bool VEC, bool WINDOW, bool ONE>
+template <typename T, bool VEC, bool WINDOW, bool ONE, bool BIASED = false>
 __device__ __forceinline__ void tf_attn_stream_row(const T* chunk, const T* kv, T* orow, float* s, int pos0, int i, int d, int dh, float scale,
-                                                   int lane, int capacity, int W) {
+                                                   int lane, int capacity, int W, const float* __restrict__ brel = nullptr) {
   typedef TfSlice<T, VEC> Sl;
   constexpr int VE = Sl::VE;
   const size_t ld = (size_t)2 * d, ldc = (size_t)3 * d;
@@ -436,6 +448,8 @@ __device__ __forceinline__ void tf_attn_stream_row(const T* chunk, const T* kv, 
       if constexpr (WINDOW) { row = slo + j; if (row >= capacity) row -= capacity; }
       k = kv + (size_t)row * ld;
     } else k = chunk + (ONE ? 0 : (size_t)(c0 + j - nc) * ldc) + d;
+    float bj = 0.f;
+    if constexpr (BIASED) bj = brel[flope_tf_plan::tf_stream_bias_index(L, j)];
     float a = 0.f;
     for (int c = 0; c < dh; c += VE) {
       Sl qv, kx;
@@ -444,7 +458,11 @@ __device__ __forceinline__ void tf_attn_stream_row(const T* chunk, const T* kv, 
 #pragma unroll
       for (int e = 0; e < VE; ++e) a = fmaf(qv.f[e], kx.f[e], a);
     }
-    a *= scale;
+    if constexpr (BIASED) {
+#pragma clang fp contract(off)
+      a = a * scale;
+      a = a + bj;
+    } else a *= scale;
     s[j] = a;
     mx = fmaxf(mx, a);
   }
@@ -665,9 +683,19 @@ __device__ __forceinline__ bool tf_stream_entry_ok(int track, int pos0, int len,
 // pos - capacity <= pos - W, which is outside every window that includes pos, so no wave of this launch reads it (the launch's rows
 // are distinct tracks, and the heads of one row touch distinct columns).  Left alone: a row whose track is out of range, whose pos is
 // negative or whose visible keys exceed the score row; pos % capacity is a row of the track whatever else the table holds.
-template <typename T, bool VEC, bool WINDOW = false>
+// BIASED: REL is (const float* rel, int planes, int D) -- rel the state's distance table, float32 [planes][D], planes = 1
+// (every head reads plane 0) or H -- and the empty pack otherwise: an unbiased instantiation's argument block is byte for byte what it
+// was, and with it the offset of the hidden arguments behind it (three unread arguments at the end moved that offset, one immediate
+// in every tf_attn_extend that reads gridDim.y).  A row whose
+// visible key count exceeds D leaves with the others above, before its first load from or store to the cache
+// (tf_stream_bias_keys_ok, beside the smax test): the plane index is 0 or h < H = planes and the row loads brel[L - 1 - j] for
+// 0 <= j <= L - 1 <= D - 1 only -- so every table address lies inside the planes whatever the device table of positions holds.
+// the arguments of a BIASED instantiation behind W, as one value
+struct TfRel { const float* rel; int planes, D; };
+template <typename T, bool VEC, bool WINDOW = false, bool BIASED = false, typename... REL>
 __global__ __launch_bounds__(256) void tf_attn_step(const T* __restrict__ qkv, T* cache, T* __restrict__ att, const int* __restrict__ tab, int n,
-                                                    int d, int H, int tracks, int capacity, int smax, int W) {
+                                                    int d, int H, int tracks, int capacity, int smax, int W, REL... rel_args) {
+  static_assert(sizeof...(REL) == (BIASED ? 3 : 0), "a BIASED instantiation takes (rel, planes, D), an unbiased one nothing");
   extern __shared__ __attribute__((aligned(16))) float sc[];     // [waves][smax]
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int it = blockIdx.x * flope_tf_plan::kTfStepWaves + wave;
@@ -675,6 +703,7 @@ __global__ __launch_bounds__(256) void tf_attn_step(const T* __restrict__ qkv, T
   const int r = it / H, h = it - r * H, dh = d / H;
   const int track = tab[2 * r], pos = tab[2 * r + 1];
   if (!tf_stream_entry_ok<WINDOW>(track, pos, 1, tracks, capacity, W) || flope_tf_plan::tf_window_keys(pos, WINDOW ? W : 0) > smax) return;
+  if constexpr (BIASED) { if (!flope_tf_plan::tf_stream_bias_keys_ok(flope_tf_plan::tf_window_keys(pos, WINDOW ? W : 0), TfRel{rel_args...}.D)) return; }
   const int slot = WINDOW ? flope_tf_plan::tf_stream_slot(pos, capacity) : pos;      // the cache row of the token
   const float scale = 1.f / sqrtf((float)dh);
   const size_t ld = (size_t)2 * d;
@@ -687,7 +716,12 @@ __global__ __launch_bounds__(256) void tf_attn_step(const T* __restrict__ qkv, T
     else kv[slot * ld + col] = tok[d + col];
   }
   // a step is an extend of one row: chunk = the token's row, pos0 = pos, i = 0
-  tf_attn_stream_row<T, VEC, WINDOW, true>(tok, kv, att + (size_t)r * d + h * dh, sc + (size_t)wave * smax, pos, 0, d, dh, scale, lane, capacity, W);
+  if constexpr (BIASED) {
+    const TfRel t{rel_args...};
+    tf_attn_stream_row<T, VEC, WINDOW, true, true>(tok, kv, att + (size_t)r * d + h * dh, sc + (size_t)wave * smax, pos, 0, d, dh, scale, lane, capacity, W,
+                                                   t.rel + (size_t)(t.planes == H ? h : 0) * t.D);
+  } else
+    tf_attn_stream_row<T, VEC, WINDOW, true>(tok, kv, att + (size_t)r * d + h * dh, sc + (size_t)wave * smax, pos, 0, d, dh, scale, lane, capacity, W);
 }
 
 // ---- extend: several tokens per track and call (flope_tf_stream_extend) ----------------------------------------------
@@ -698,10 +732,16 @@ __global__ __launch_bounds__(256) void tf_attn_step(const T* __restrict__ qkv, T
 // smax: floats of a wave's score row, the call's largest visible key count.  Reads the cache, writes att alone; a workgroup whose
 // table entry is no track, whose positions leave the cache (linear: pos0 + len > capacity; a ring: past INT_MAX, or a window that is
 // none of this cache's) or whose keys exceed the score row exits before it stores anything (tf_stream_entry_ok, and smax).
-template <typename T, bool VEC, bool WINDOW>
+// BIASED: REL = (rel, planes, D) as in tf_attn_step, behind W, and the empty pack otherwise.  A workgroup whose largest visible key count
+// (its last query's, tf_extend_keys) exceeds D exits with the others above, before its first load (tf_stream_bias_keys_ok): every query
+// of the chunk then has L <= D keys, the plane index is 0 or h < H = planes, and a row loads brel[L - 1 - j] for 0 <= j <= L - 1 only --
+// every table address lies inside the planes whatever the device tables hold.  A prefill of a biased state is this kernel at pos0 = 0,
+// where no cached key is read (nc = 0) and the row is the biased forward's.
+template <typename T, bool VEC, bool WINDOW, bool BIASED = false, typename... REL>
 __global__ __launch_bounds__(256) void tf_attn_extend(const T* __restrict__ qkv, const T* __restrict__ cache, T* __restrict__ att,
                                                       const int* __restrict__ tab, const int* __restrict__ off, int n, int d, int H, int tracks,
-                                                      int capacity, int smax, int W) {
+                                                      int capacity, int smax, int W, REL... rel_args) {
+  static_assert(sizeof...(REL) == (BIASED ? 3 : 0), "a BIASED instantiation takes (rel, planes, D), an unbiased one nothing");
   extern __shared__ __attribute__((aligned(16))) float sc[];     // [waves][smax]
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int b = blockIdx.x / H, h = blockIdx.x - b * H, dh = d / H;
@@ -709,12 +749,19 @@ __global__ __launch_bounds__(256) void tf_attn_extend(const T* __restrict__ qkv,
   const int track = tab[2 * b], pos0 = tab[2 * b + 1];
   const int o = off[b], len = off[b + 1] - o;
   if (!tf_stream_entry_ok<WINDOW>(track, pos0, len, tracks, capacity, W) || flope_tf_plan::tf_extend_keys(pos0, len, WINDOW ? W : 0) > smax) return;
+  if constexpr (BIASED) { if (!flope_tf_plan::tf_stream_bias_keys_ok(flope_tf_plan::tf_extend_keys(pos0, len, WINDOW ? W : 0), TfRel{rel_args...}.D)) return; }
   const float scale = 1.f / sqrtf((float)dh);
   const T* chunk = qkv + (size_t)o * 3 * d + h * dh;
   const T* kv = cache + (size_t)track * capacity * 2 * d + h * dh;
   float* s = sc + (size_t)wave * smax;
-  for (int i = blockIdx.y * flope_tf_plan::kTfStepWaves + wave; i < len; i += gridDim.y * flope_tf_plan::kTfStepWaves)
-    tf_attn_stream_row<T, VEC, WINDOW, false>(chunk, kv, att + (size_t)(o + i) * d + h * dh, s, pos0, i, d, dh, scale, lane, capacity, W);
+  for (int i = blockIdx.y * flope_tf_plan::kTfStepWaves + wave; i < len; i += gridDim.y * flope_tf_plan::kTfStepWaves) {
+    if constexpr (BIASED) {
+      const TfRel t{rel_args...};
+      tf_attn_stream_row<T, VEC, WINDOW, false, true>(chunk, kv, att + (size_t)(o + i) * d + h * dh, s, pos0, i, d, dh, scale, lane, capacity, W,
+                                                      t.rel + (size_t)(t.planes == H ? h : 0) * t.D);
+    } else
+      tf_attn_stream_row<T, VEC, WINDOW, false>(chunk, kv, att + (size_t)(o + i) * d + h * dh, s, pos0, i, d, dh, scale, lane, capacity, W);
+  }
 }
 
 // The one cache copy: the k | v columns (d .. 3 d) of the valid packed rows of qkv [T][3 d] -> the cache [tracks][capacity][2 d]: row
@@ -2033,6 +2080,8 @@ struct flope_tf_stream_s {
   int* tab = nullptr;                        // device table of one call (4 ints per track): step (track, position) per row, prefill the track per sequence, attention both and its fills' offsets
   std::vector<int> pos, tab_host;            // tokens held per track; the pageable copy tab is uploaded from
   std::vector<char> seen;                    // scratch of the argument checks
+  float* rel = nullptr;                      // a biased state's distance table (flope_tf_stream_open_bias): float32 [planes][rel_d], nullptr otherwise
+  int planes = 0, rel_d = 0;                 // 0 planes: no table; else 1 or num_heads, and rel_d = window ? window : capacity
 };
 
 // A compiled attention mask (flope_tf_mask_*; tf_attn_mask.h): one device allocation bits | first | last | start |
@@ -2492,8 +2541,8 @@ extern "C" int flope_tf_destroy(flope_tf_handle e) {
   if (!e) return FLOPE_OK;
   hipSetDevice(e->device);
   for (flope_tf_stream_s* s : e->streams) {      // their device memory goes with the handle; the states stay until closed and refuse every call
-    hipFree(s->cache); hipFree(s->tab);
-    s->cache = nullptr; s->tab = nullptr; s->e = nullptr;
+    hipFree(s->cache); hipFree(s->tab); hipFree(s->rel);
+    s->cache = nullptr; s->tab = nullptr; s->rel = nullptr; s->e = nullptr;
   }
   for (flope_tf_mask* m : e->masks) {            // the same for the compiled masks
     hipFree(m->dev);
@@ -3099,8 +3148,10 @@ int tf_stream_refuse(flope_tf_stream_s* s, const std::string& who, int rc, int b
 inline int tf_head_dim(const flope_tf_encoder* e) { return e->d / e->H; }
 template <typename T> bool tf_row_vec(const flope_tf_encoder* e) { return flope_tf_plan::tf_step_vec_ok(tf_head_dim(e), (int)sizeof(T)); }
 
-// which of FLOPE_TF_STEP_ROW / _SPLIT a step or extend of this state launches now
-template <typename T> int tf_step_plan(const flope_tf_encoder* e) {
+// which of FLOPE_TF_STEP_ROW / _SPLIT a step or extend of this state launches now; a state with a distance table: _BIASED, whatever
+// the options say
+template <typename T> int tf_step_plan(const flope_tf_encoder* e, const flope_tf_stream_s* s) {
+  if (s->planes) return FLOPE_TF_STEP_BIASED;
   return e->opt_step_split && flope_tf_plan::tf_step_split_ok(tf_head_dim(e), (int)sizeof(T)) ? FLOPE_TF_STEP_SPLIT : FLOPE_TF_STEP_ROW;
 }
 
@@ -3109,7 +3160,7 @@ template <typename T> int tf_step_plan(const flope_tf_encoder* e) {
 template <typename T>
 int launch_step_attn(flope_tf_stream_s* s, const T* qkv, T* cache, T* att, int n, int max_pos, hipStream_t st) {
   flope_tf_encoder* e = s->e;
-  const int plan = tf_step_plan<T>(e);
+  const int plan = tf_step_plan<T>(e, s);
   if (plan == FLOPE_TF_STEP_SPLIT) {
     const flope_tf_plan::TfStreamLaunch l = flope_tf_plan::tf_step_split_launch(n, e->H, tf_head_dim(e));
 #define TF_SPLIT(WIN_) hipLaunchKernelGGL((tf_attn_step_split<T, WIN_>), dim3(l.grid_x), dim3(l.block), l.lds, st, qkv, cache, att, (const int*)s->tab, n, e->d, \
@@ -3120,8 +3171,15 @@ int launch_step_attn(flope_tf_stream_s* s, const T* qkv, T* cache, T* att, int n
     const flope_tf_plan::TfStreamLaunch l = flope_tf_plan::tf_step_launch(n, e->H, max_pos);
 #define TF_STEP(VEC_, WIN_) hipLaunchKernelGGL((tf_attn_step<T, VEC_, WIN_>), dim3(l.grid_x), dim3(l.block), l.lds, st, qkv, cache, att, \
                                               (const int*)s->tab, n, e->d, e->H, s->tracks, s->capacity, max_pos + 1, s->window)
-    if (tf_row_vec<T>(e)) { if (s->window) TF_STEP(true, true); else TF_STEP(true, false); }
+#define TF_STEPB(VEC_, WIN_) hipLaunchKernelGGL((tf_attn_step<T, VEC_, WIN_, true, const float*, int, int>), dim3(l.grid_x), dim3(l.block), l.lds, st, qkv, cache, \
+                                               att, (const int*)s->tab, n, e->d, e->H, s->tracks, s->capacity, max_pos + 1, s->window,                      \
+                                               (const float*)s->rel, s->planes, s->rel_d)
+    if (plan == FLOPE_TF_STEP_BIASED) {
+      if (tf_row_vec<T>(e)) { if (s->window) TF_STEPB(true, true); else TF_STEPB(true, false); }
+      else { if (s->window) TF_STEPB(false, true); else TF_STEPB(false, false); }
+    } else if (tf_row_vec<T>(e)) { if (s->window) TF_STEP(true, true); else TF_STEP(true, false); }
     else { if (s->window) TF_STEP(false, true); else TF_STEP(false, false); }
+#undef TF_STEPB
 #undef TF_STEP
   }
   TF_HIP(e, hipGetLastError());
@@ -3159,7 +3217,10 @@ int launch_cache_copy(flope_tf_stream_s* s, const T* src_qkv, T* cache, const in
 }
 
 // the causal ragged forward's launch sequence, each layer's k | v rows copied into the cache in front of its attention (a windowed
-// state: the last min(len, capacity) rows of a sequence, into the ring).  s->tab: (track, 0) per sequence
+// state: the last min(len, capacity) rows of a sequence, into the ring).  s->tab: (track, 0) per sequence.
+// A state with a distance table has no compiled [L, L] bias to give launch_attention: behind the same copy it launches the biased
+// tf_attn_extend with that table of (track, 0) -- at pos0 = 0 no cached key is read and a row is the biased forward's
+template <typename T> int launch_extend_attn(flope_tf_stream_s* s, int plan, const T* qkv, const T* cache, T* att, int n, int max_len, int smax, hipStream_t st);
 template <typename T>
 int run_prefill(flope_tf_stream_s* s, const float* x, int n, int L, const TfRagged& rg, float* y, hipStream_t st) {
   flope_tf_encoder* e = s->e;
@@ -3167,6 +3228,11 @@ int run_prefill(flope_tf_stream_s* s, const float* x, int n, int L, const TfRagg
   return run_forward_with<T>(e, x, n, L, y, st, &rg, [&](int li) {
     const int rc = launch_cache_copy<T>(s, (const T*)e->qkv, (T*)s->cache + (size_t)li * layer, (const int*)e->vl_off, (const int*)s->tab, n, rg.max_len, st);
     if (rc) return rc;
+    if (s->planes) {
+      const int ra = launch_extend_attn<T>(s, FLOPE_TF_EXTEND_BIASED, (const T*)e->qkv, (const T*)s->cache + (size_t)li * layer, (T*)e->att, n, rg.max_len,
+                                           flope_tf_plan::tf_extend_keys(0, rg.max_len, s->window), st);
+      return ra < 0 ? ra : 0;
+    }
     return launch_attention<T>(e, e->qkv, e->att, n, rg.max_len, e->vl_off, st);
   });
 }
@@ -3176,9 +3242,10 @@ int run_prefill(flope_tf_stream_s* s, const float* x, int n, int L, const TfRagg
 // tf_encoder_stream.h).  smax: the call's largest visible key count (tf_stream_check_extend)
 // which of FLOPE_TF_EXTEND_ROW / _SPLIT / _MFMA an extend of this state launches now: option extend_mfma where tf_extend_mfma_ok, in
 // front of option step_split.  pos_ok: every chunk of the call stays below kTfExtendMfmaPosMax (a plan without a call: true)
-template <typename T> int tf_extend_plan(const flope_tf_encoder* e, bool pos_ok = true) {
+template <typename T> int tf_extend_plan(const flope_tf_encoder* e, const flope_tf_stream_s* s, bool pos_ok = true) {
+  if (s->planes) return FLOPE_TF_EXTEND_BIASED;              // a state with a distance table: the options do not reach it
   if (e->opt_extend_mfma && pos_ok && flope_tf_plan::tf_extend_mfma_ok(e->dtype, tf_head_dim(e), e->d)) return FLOPE_TF_EXTEND_MFMA;
-  return tf_step_plan<T>(e) == FLOPE_TF_STEP_SPLIT ? FLOPE_TF_EXTEND_SPLIT : FLOPE_TF_EXTEND_ROW;
+  return tf_step_plan<T>(e, s) == FLOPE_TF_STEP_SPLIT ? FLOPE_TF_EXTEND_SPLIT : FLOPE_TF_EXTEND_ROW;
 }
 
 // the attention launch of an extend: the packed chunks in qkv [T][3 d] (offsets e->vl_off, table s->tab) against one layer's part of
@@ -3208,11 +3275,19 @@ int launch_extend_attn(flope_tf_stream_s* s, int plan, const T* qkv, const T* ca
   const flope_tf_plan::TfExtendLaunch ls = flope_tf_plan::tf_extend_split_launch(n, e->H, max_len, tf_head_dim(e));
 #define TF_EXT(VEC_, WIN_) hipLaunchKernelGGL((tf_attn_extend<T, VEC_, WIN_>), dim3(la.grid_x, la.grid_y), dim3(la.block), la.lds, st, qkv, cache, \
                                              att, (const int*)s->tab, (const int*)e->vl_off, n, e->d, e->H, s->tracks, s->capacity, smax, s->window)
+#define TF_EXTB(VEC_, WIN_) hipLaunchKernelGGL((tf_attn_extend<T, VEC_, WIN_, true, const float*, int, int>), dim3(la.grid_x, la.grid_y), dim3(la.block), la.lds, st, \
+                                              qkv, cache, att, (const int*)s->tab, (const int*)e->vl_off, n, e->d, e->H, s->tracks, s->capacity, smax, s->window,     \
+                                              (const float*)s->rel, s->planes, s->rel_d)
 #define TF_EXTS(WIN_) hipLaunchKernelGGL((tf_attn_extend_split<T, WIN_>), dim3(ls.grid_x, ls.grid_y), dim3(ls.block), ls.lds, st, qkv, cache, \
                                         att, (const int*)s->tab, (const int*)e->vl_off, n, e->d, e->H, s->tracks, s->capacity, s->window)
   if (plan == FLOPE_TF_EXTEND_SPLIT) { if (s->window) TF_EXTS(true); else TF_EXTS(false); }   // option step_split: tf_attn_extend_split, the bits of the split steps
-  else if (tf_row_vec<T>(e)) { if (s->window) TF_EXT(true, true); else TF_EXT(true, false); }
+  else if (plan == FLOPE_TF_EXTEND_BIASED) {
+    if (!s->planes) return tf_fail(e, FLOPE_ESTATE, "tf_attn_extend's biased form needs a state with a distance table");
+    if (tf_row_vec<T>(e)) { if (s->window) TF_EXTB(true, true); else TF_EXTB(true, false); }
+    else { if (s->window) TF_EXTB(false, true); else TF_EXTB(false, false); }
+  } else if (tf_row_vec<T>(e)) { if (s->window) TF_EXT(true, true); else TF_EXT(true, false); }
   else { if (s->window) TF_EXT(false, true); else TF_EXT(false, false); }
+#undef TF_EXTB
 #undef TF_EXTS
 #undef TF_EXT
   TF_HIP(e, hipGetLastError());
@@ -3230,7 +3305,7 @@ template <typename T>
 int run_extend(flope_tf_stream_s* s, const float* x, int n, int L, const TfRagged& rg, const int* lengths, int smax, float* y, hipStream_t st) {
   flope_tf_encoder* e = s->e;
   const size_t layer = (size_t)s->tracks * s->capacity * 2 * e->d;
-  const int plan = tf_extend_plan<T>(e, tf_extend_positions_ok(s, n, lengths));
+  const int plan = tf_extend_plan<T>(e, s, tf_extend_positions_ok(s, n, lengths));
   return run_forward_with<T>(e, x, n, L, y, st, &rg, [&](int li) {
     T* cache = (T*)s->cache + (size_t)li * layer;
     const int rc = launch_extend_attn<T>(s, plan, (const T*)e->qkv, (const T*)cache, (T*)e->att, n, rg.max_len, smax, st);
@@ -3242,8 +3317,11 @@ int run_extend(flope_tf_stream_s* s, const float* x, int n, int L, const TfRagge
 }  // namespace
 
 namespace {
-// window = 0: flope_tf_stream_open, the linear cache; window >= 1: flope_tf_stream_open_window, the ring
-int tf_stream_open(flope_tf_handle e, const std::string& who, int tracks, int capacity, int window, flope_tf_stream* out) {
+// window = 0: flope_tf_stream_open, the linear cache; window >= 1: flope_tf_stream_open_window, the ring.
+// planes >= 1: flope_tf_stream_open_bias -- the state's distance table rel [planes][rel_d], already checked, is uploaded here, once and
+// synchronously, into an allocation of the state's own
+int tf_stream_open(flope_tf_handle e, const std::string& who, int tracks, int capacity, int window, flope_tf_stream* out, int planes = 0, int rel_d = 0,
+                   const float* rel_host = nullptr) {
   if (!out) return tf_fail(e, FLOPE_EINVAL, who + ": NULL out");
   *out = nullptr;
   if (!e) return tf_fail(nullptr, FLOPE_EINVAL, who + ": NULL handle");
@@ -3263,6 +3341,20 @@ int tf_stream_open(flope_tf_handle e, const std::string& who, int tracks, int ca
     hipFree(s->cache); hipFree(s->tab);
     delete s;
     return tf_fail(e, FLOPE_EHIP, who + ": hipMalloc failed for a cache of " + std::to_string(bytes) + " bytes (num_layers x tracks x capacity x 2 model_dim)");
+  }
+  if (planes) {
+    const size_t rb = flope_tf_plan::tf_stream_bias_bytes(planes, rel_d);
+    hipError_t err = hipMalloc((void**)&s->rel, rb);
+    const bool alloc_failed = err != hipSuccess;
+    if (!alloc_failed) err = hipMemcpy(s->rel, rel_host, rb, hipMemcpyHostToDevice);
+    if (err != hipSuccess) {
+      (void)hipGetLastError();
+      hipFree(s->cache); hipFree(s->tab); hipFree(s->rel);
+      delete s;
+      return tf_fail(e, FLOPE_EHIP, who + (alloc_failed ? ": hipMalloc failed for" : ": the upload failed of") + " a distance table of " + std::to_string(rb) +
+                                        " bytes (planes x distances x 4): " + hipGetErrorString(err));
+    }
+    s->planes = planes; s->rel_d = rel_d;
   }
   s->pos.assign((size_t)tracks, 0);
   s->tab_host.assign((size_t)5 * tracks, 0);
@@ -3285,11 +3377,46 @@ extern "C" int flope_tf_stream_open_window(flope_tf_handle e, int tracks, int ca
   return tf_stream_open(e, "flope_tf_stream_open_window", tracks, capacity, window, out);
 }
 
+extern "C" int flope_tf_stream_open_bias(flope_tf_handle e, int tracks, int capacity, int window, int planes, int distances, const float* table_host,
+                                         flope_tf_stream* out) {
+  using namespace flope_tf_plan;
+  const std::string who = "flope_tf_stream_open_bias";
+  if (!out) return tf_fail(e, FLOPE_EINVAL, who + ": NULL out");
+  *out = nullptr;
+  if (!e) return tf_fail(nullptr, FLOPE_EINVAL, who + ": NULL handle");
+  if (window < 0) return tf_fail(e, FLOPE_EINVAL, who + ": window = " + std::to_string(window) + " is negative (0: the linear state; 1 .. capacity: the ring)");
+  // the state's own refusals first: a table is judged against a capacity and a window that are ones
+  if (tf_stream_check_open(tracks, capacity) == kTfStreamOk && (!window || tf_stream_check_open_window(tracks, capacity, window) == kTfStreamOk)) {
+    int bp = -1, bd = -1;
+    switch (tf_stream_check_open_bias(capacity, window, e->H, planes, distances, table_host, &bp, &bd)) {
+      case kTfStreamBiasPlanes:
+        return tf_fail(e, FLOPE_EINVAL, who + ": planes = " + std::to_string(planes) + " is neither 1 nor num_heads = " + std::to_string(e->H));
+      case kTfStreamBiasDistances:
+        return tf_fail(e, FLOPE_EINVAL, who + ": distances = " + std::to_string(distances) + ", but this state needs " +
+                                            std::to_string(tf_stream_bias_distances(capacity, window)) + (window ? " (its window)" : " (its capacity)"));
+      case kTfStreamBiasNull:
+        return tf_fail(e, FLOPE_EINVAL, who + ": NULL table");
+      case kTfStreamBiasValue:
+        return tf_fail(e, FLOPE_EINVAL, who + ": table[" + std::to_string(bp) + "][" + std::to_string(bd) + "] = " + std::to_string(table_host[(size_t)bp * distances + bd]) +
+                                            " (plane, distance) is not finite (-inf is no way to mask here: visibility stays with the window)");
+      default: break;
+    }
+  }
+  return tf_stream_open(e, who, tracks, capacity, window, out, planes, distances, table_host);
+}
+
+extern "C" int flope_tf_stream_bias_planes(flope_tf_stream s) {
+  flope_tf_encoder* e;
+  int rc;
+  if ((rc = tf_stream_enter(s, "flope_tf_stream_bias_planes", &e))) return rc;
+  return s->planes;
+}
+
 extern "C" int flope_tf_stream_close(flope_tf_stream s) {
   if (!s) return FLOPE_OK;
   if (flope_tf_encoder* e = s->e) {
     hipSetDevice(e->device);
-    hipFree(s->cache); hipFree(s->tab);
+    hipFree(s->cache); hipFree(s->tab); hipFree(s->rel);
     for (auto it = e->streams.begin(); it != e->streams.end(); ++it)
       if (*it == s) { e->streams.erase(it); break; }
   }
@@ -3411,7 +3538,7 @@ extern "C" int flope_tf_stream_step_plan(flope_tf_stream s) {
   flope_tf_encoder* e;
   int rc;
   if ((rc = tf_stream_enter(s, "flope_tf_stream_step_plan", &e))) return rc;
-  return tf_by_dtype(e, [&](auto tag) { return tf_step_plan<typename decltype(tag)::type>(e); });
+  return tf_by_dtype(e, [&](auto tag) { return tf_step_plan<typename decltype(tag)::type>(e, s); });
 }
 
 namespace {
@@ -3483,7 +3610,7 @@ extern "C" int flope_tf_stream_extend_plan(flope_tf_stream s) {
   flope_tf_encoder* e;
   int rc;
   if ((rc = tf_stream_enter(s, "flope_tf_stream_extend_plan", &e))) return rc;
-  return tf_by_dtype(e, [&](auto tag) { return tf_extend_plan<typename decltype(tag)::type>(e); });
+  return tf_by_dtype(e, [&](auto tag) { return tf_extend_plan<typename decltype(tag)::type>(e, s); });
 }
 
 namespace {
@@ -3501,7 +3628,7 @@ int run_stream_attention_extend(flope_tf_stream_s* s, const T* qkv, int n, int L
   }
   std::vector<int> chunk((size_t)n);
   for (int b = 0; b < n; ++b) chunk[(size_t)b] = lengths[b] - cached[b];
-  const int plan = tf_extend_plan<T>(e, tf_extend_positions_ok(s, n, chunk.data()));
+  const int plan = tf_extend_plan<T>(e, s, tf_extend_positions_ok(s, n, chunk.data()));
   const int rc = launch_extend_attn<T>(s, plan, (const T*)e->qkv, (const T*)s->cache, (T*)e->att, n, max_len, smax, st);
   if (rc < 0) return rc;
   for (int b = 0; b < n; ++b)

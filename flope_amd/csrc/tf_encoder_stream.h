@@ -16,6 +16,9 @@
 // Below those, option extend_mfma: which 64-key blocks a workgroup of tf_attn16_extend loads, where key j of a block comes
 // from (zeros, a cache row, a chunk row), the output row of a query, the launch, the eligibility rule, and the checks of
 // flope_tf_stream_attention_extend (tests/host_harness/harness_tf_extend16.cpp, tests/test_tf_extend_mfma_host.py).
+// Below those, a state with a distance table (flope_tf_stream_open_bias): how many distances a state needs, the planes
+// check, the first non-finite entry, the entry a visible key reads and the test the biased kernels make in front of their first load
+// (tests/host_harness/harness_tf_stream_bias.cpp, tests/test_tf_stream_bias_host.py).
 #pragma once
 
 #include <limits.h>
@@ -355,5 +358,42 @@ inline int tf_stream_check_attention_extend(int tracks, int capacity, int window
   *smax = mx; *max_len = ml; *total = (int)sum;
   return kTfStreamOk;
 }
+
+// ---- a distance table: a relative attention bias on a stream state (flope_tf_stream_open_bias) --------------------------
+// rel: float32 [planes][D], planes = 1 (every head) or num_heads.  The query at position p scores key j (lo <= j <= p) as
+// fl(fl(chain * scale) + rel[plane][p - j]).  A query never sees more than `capacity` keys of a linear state or W of a windowed one, so
+// that is how many distances the table must hold -- exactly: a table of another length was made for another state.
+constexpr int tf_stream_bias_distances(int capacity, int window) { return window ? window : capacity; }
+constexpr bool tf_stream_bias_planes_ok(int planes, int H) { return planes == 1 || (H >= 1 && planes == H); }
+// The entry of the visible key with index j counted from lo (as the score row counts, j = 0 .. L - 1; the query's own key is L - 1):
+// its distance p - (lo + j) = L - 1 - j
+constexpr int tf_stream_bias_index(int L, int j) { return L - 1 - j; }
+// What tf_attn_step / tf_attn_extend test beside smax before their first load: `keys` visible keys index a table of D distances
+constexpr bool tf_stream_bias_keys_ok(int keys, int D) { return keys <= D; }
+// The first entry that is not finite, in (plane, distance) order: -inf is no way to mask here (visibility stays with the window), so
+// every non-finite value counts.  By bits: the test holds under any floating-point option of the compiler.
+inline bool tf_stream_bias_nonfinite(const float* rel, int planes, int D, int* plane, int* dist) {
+  for (int h = 0; h < planes; ++h)
+    for (int t = 0; t < D; ++t) {
+      uint32_t u;
+      memcpy(&u, rel + (size_t)h * D + t, sizeof(u));
+      if ((u & 0x7f800000u) == 0x7f800000u) { *plane = h; *dist = t; return true; }
+    }
+  return false;
+}
+// open: the refusals of a table in the order the call makes them.  *bad_plane / *bad_dist: the entry kTfStreamBiasValue names
+enum {
+  kTfStreamBiasPlanes = -10,      // planes is neither 1 nor num_heads
+  kTfStreamBiasDistances = -11,   // distances != tf_stream_bias_distances(capacity, window)
+  kTfStreamBiasNull = -12,        // no table
+  kTfStreamBiasValue = -13        // rel[*bad_plane][*bad_dist] is NaN or +-inf
+};
+inline int tf_stream_check_open_bias(int capacity, int window, int H, int planes, int distances, const float* rel, int* bad_plane, int* bad_dist) {
+  if (!tf_stream_bias_planes_ok(planes, H)) return kTfStreamBiasPlanes;
+  if (distances != tf_stream_bias_distances(capacity, window)) return kTfStreamBiasDistances;
+  if (!rel) return kTfStreamBiasNull;
+  return tf_stream_bias_nonfinite(rel, planes, distances, bad_plane, bad_dist) ? (int)kTfStreamBiasValue : (int)kTfStreamOk;
+}
+constexpr size_t tf_stream_bias_bytes(int planes, int D) { return (size_t)planes * (size_t)D * sizeof(float); }
 
 }  // namespace flope_tf_plan

@@ -175,6 +175,35 @@ def alibi_bias(L, slopes, causal=True):
     return bias
 
 
+def alibi_distances(D, slopes):
+    """The ALiBi distance table for a stream (`enc.open_stream(..., bias=)`), float32 [len(slopes), D]: -slopes[h] * dist for
+    dist = 0 .. D - 1, the products `alibi_bias` makes, so that distance_bias(alibi_distances(L, s), L) is alibi_bias(L, s) bit for
+    bit.  D is the state's window, or its capacity without one."""
+    slopes = torch.as_tensor(slopes, dtype=torch.float32).reshape(-1)
+    return -slopes[:, None] * torch.arange(int(D)).abs().to(torch.float32)[None]
+
+
+def distance_bias(table, L, window=0):
+    """The [planes, L, L] bias a distance table stands for, float32: entry [h][i][j] is table[h][i - j] for j <= i and, with `window`,
+    i - j < window, and -inf elsewhere -- what `enc.make_bias` takes, and the forward under it is what a stream opened with
+    `bias=table` returns row by row.  table: floating [D] or [planes, D] with D >= min(L, window or L) (ValueError)."""
+    table = torch.as_tensor(table)
+    L, window = int(L), int(window)
+    if table.dim() not in (1, 2) or not table.dtype.is_floating_point:
+        raise ValueError(f"table must be a floating tensor [D] or [planes, D], got {table.dtype} {tuple(table.shape)}")
+    if L < 1 or window < 0:
+        raise ValueError(f"L must be positive and window 0 (none) or positive, got L = {L}, window = {window}")
+    t = table.detach().to(device="cpu", dtype=torch.float32).reshape(-1, table.shape[-1])
+    need = min(L, window or L)
+    if t.shape[1] < need:
+        raise ValueError(f"table has {t.shape[1]} distances, a forward of L = {L}" + (f" under window = {window}" if window else "") + f" needs {need}")
+    i, j = torch.arange(L)[:, None], torch.arange(L)[None, :]
+    dist = i - j
+    seen = (dist >= 0) & ((dist < window) if window else torch.ones_like(dist, dtype=torch.bool))
+    bias = t[:, dist.clamp(0, t.shape[1] - 1)]
+    return bias.masked_fill(~seen[None], float("-inf")).contiguous()
+
+
 class TransformerEncoder:
     def __init__(self, input_dim, model_dim, out_dim, num_heads, num_layers, ff_dim, dropout=0.1,
                  dtype="f32", max_tokens=4096, device=None, attn_tiled=0, fused=0, window_mfma=0, step_split=0, extend_mfma=0,
@@ -571,15 +600,20 @@ class TransformerEncoder:
         self._keep = (x, weight, bias)
         return out
 
-    def open_stream(self, tracks: int, capacity: int, window: int = 0) -> "TransformerEncoderStream":
+    def open_stream(self, tracks: int, capacity: int, window: int = 0, bias=None) -> "TransformerEncoderStream":
         """A stream state for `tracks` live tracks of up to `capacity` tokens each (TransformerEncoderStream): feed one new token per
         track with step() and get the row a causal forward of the whole track would end with, without running it again;
         extend() appends several tokens per track in one call, with the bits of those steps.
         `window=W` (1 <= W <= capacity): sliding-window attention over a ring cache -- a track is never full, positions are absolute,
         and step() at position t returns row t of enc(track[: t + 1], is_causal=True, window=W), bit for bit with `window_mfma=0`
         (with `window_mfma=1`: in bits where that forward's attention is the generic kernel, within the attention kernels'
-        tolerances elsewhere)."""
-        return TransformerEncoderStream(self, tracks, capacity, window)
+        tolerances elsewhere).
+        `bias=table`: a distance table, floating [D], [1, D] or [num_heads, D] with D = window, or capacity without
+        one -- a relative bias such as `alibi_distances(D, slopes)`; every entry finite.  The query at position p then scores key j
+        as its scaled score + table[h][p - j], and step(), extend() and prefill() return, in bits and in every dtype and under every
+        option, the rows of enc(x, mask=enc.make_bias(distance_bias(table, L, window))).  Without it the encoder has no positional
+        term and a track's last row does not depend on the order of the poses behind it."""
+        return TransformerEncoderStream(self, tracks, capacity, window, bias)
 
     def close(self):
         if getattr(self, "handle", None) and self.handle.value:
@@ -691,9 +725,13 @@ class TransformerEncoderStream:
     On a 16-bit encoder with option `extend_mfma` = 1 (it may be flipped between calls too) extend() runs its attention on
     the MFMA step where `extend_plan()` says "mfma" (head_dim 32 / 64 / 96 / 128): its rows are then, in bits, the rows of
     enc(track, is_causal=True[, window=W]) where that forward's attention is an MFMA kernel, whatever the split into chunks, and the
-    cache it leaves is prefill()'s.  It wins over `step_split` for extend() alone; step(), prefill() and the forwards do not read it."""
+    cache it leaves is prefill()'s.  It wins over `step_split` for extend() alone; step(), prefill() and the forwards do not read it.
+    With `bias` (`enc.open_stream(..., bias=table)`) the state carries a distance table [planes, D], planes = 1 or
+    num_heads (`bias_planes`; 0 without one), D = window or capacity: step(), extend() and prefill() add table[h][p - j] to the scaled
+    score of query p and key j and return the rows of the forward under enc.make_bias(distance_bias(table, L, window)) in bits, in
+    every dtype and whatever `attn_tiled`, `step_split` or `extend_mfma` say -- `step_plan` / `extend_plan()` answer "biased"."""
 
-    def __init__(self, enc: TransformerEncoder, tracks: int, capacity: int, window: int = 0):
+    def __init__(self, enc: TransformerEncoder, tracks: int, capacity: int, window: int = 0, bias=None):
         self.enc = enc
         self.state = C.c_void_p()
         self.tracks, self.capacity, self.window = int(tracks), int(capacity), int(window)
@@ -701,6 +739,21 @@ class TransformerEncoderStream:
         self._handle()
         if self.window < 0:
             raise ValueError(f"window must be 0 (a linear cache) or 1 .. capacity, got {self.window}")
+        self.bias_planes = 0
+        if bias is not None:
+            # every refusal of the table's contents is made on the C side, which names (plane, distance)
+            if not isinstance(bias, torch.Tensor) or bias.dim() not in (1, 2) or not bias.dtype.is_floating_point or bias.shape[-1] < 1:
+                what = f"{bias.dtype} {tuple(bias.shape)}" if isinstance(bias, torch.Tensor) else type(bias).__name__
+                raise ValueError(f"bias must be a floating tensor [D], [1, D] or [{enc.dims[3]}, D], got {what}")
+            if bias.is_cuda and bias.device != enc.device:
+                raise ValueError(f"bias lives on {bias.device}, the encoder on {enc.device}")
+            t = bias.detach().to(device="cpu", dtype=torch.float32).reshape(-1, bias.shape[-1]).contiguous()
+            with torch.cuda.device(enc.device):
+                rc = enc.lib.flope_tf_stream_open_bias(enc.handle, self.tracks, self.capacity, self.window, int(t.shape[0]), int(t.shape[1]),
+                                                       C.cast(t.data_ptr(), C.POINTER(C.c_float)), C.byref(self.state))
+            enc._check_arg(rc)
+            self.bias_planes = int(enc.lib.flope_tf_stream_bias_planes(self.state))
+            return
         with torch.cuda.device(enc.device):
             if self.window:
                 rc = enc.lib.flope_tf_stream_open_window(enc.handle, self.tracks, self.capacity, self.window, C.byref(self.state))
@@ -791,12 +844,13 @@ class TransformerEncoderStream:
 
     @property
     def step_plan(self) -> str:
-        """"row" or "split": the attention kernel a step() / extend() of this state would launch now -- "split" under the encoder's
-        option `step_split` where the head slice is a power-of-two count of 16-byte vectors.  Enqueues nothing."""
+        """"row", "split" or "biased": the attention kernel a step() / extend() of this state would launch now -- "split" under the
+        encoder's option `step_split` where the head slice is a power-of-two count of 16-byte vectors, "biased" on a
+        state with a distance table, whatever the options.  Enqueues nothing."""
         self._live()
         rc = self.enc.lib.flope_tf_stream_step_plan(self.state)
         self.enc._check_arg(rc)
-        return "split" if rc == _lib.TF_STEP_SPLIT else "row"
+        return {_lib.TF_STEP_SPLIT: "split", _lib.TF_STEP_BIASED: "biased"}.get(rc, "row")
 
     def attention(self, qkv: torch.Tensor, lengths=None, out: torch.Tensor = None) -> torch.Tensor:
         """A test hook: the attention launch of step() alone, on a caller's tensor.  qkv [n, L, 3 * model_dim] in the handle's dtype
@@ -827,12 +881,12 @@ class TransformerEncoderStream:
 
     def extend_plan(self) -> str:
         """"row", "split" or "mfma": the attention kernel an extend() of this state would launch now -- "mfma" under the encoder's option
-        `extend_mfma` on a 16-bit handle with head_dim 32 / 64 / 96 / 128, otherwise what `step_plan` says.  Enqueues
-        nothing."""
+        `extend_mfma` on a 16-bit handle with head_dim 32 / 64 / 96 / 128, otherwise what `step_plan` says ("biased" on a
+        state with a distance table, in front of every option).  Enqueues nothing."""
         self._live()
         rc = self.enc.lib.flope_tf_stream_extend_plan(self.state)
         self.enc._check_arg(rc)
-        return {_lib.TF_EXTEND_MFMA: "mfma", _lib.TF_EXTEND_SPLIT: "split"}.get(rc, "row")
+        return {_lib.TF_EXTEND_MFMA: "mfma", _lib.TF_EXTEND_SPLIT: "split", _lib.TF_EXTEND_BIASED: "biased"}.get(rc, "row")
 
     def attention_extend(self, qkv: torch.Tensor, lengths, cached, out: torch.Tensor = None) -> torch.Tensor:
         """A test hook: the attention launch of extend() alone, on a caller's tensor.  qkv [n, L, 3 * model_dim] in the handle's dtype

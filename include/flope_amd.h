@@ -574,15 +574,40 @@ double flope_tf_forward_flops_varlen(flope_tf_handle h, int batch, const int* le
  *             those cache rows and the handle's scratch buffers and leaves tracks 0 .. n - 1 at position 0; needs no weights.
  *             Refused with FLOPE_EINVAL, nothing enqueued: n outside 1 .. min(tracks, max_tokens), NULL lengths_host / cached_host,
  *             a length outside 1 .. seq_len, cached[b] outside 0 .. lengths[b] - 1, on a linear state a length above capacity, chunks
- *             of more than max_tokens rows together, NULL or misaligned buffers, a handle with num_layers = 0. */
+ *             of more than max_tokens rows together, NULL or misaligned buffers, a handle with num_layers = 0.
+ * flope_tf_stream_open_bias: a state whose attention carries a DISTANCE TABLE, a relative bias such as ALiBi -- the
+ * encoder has no positional term, so without one a track's last row is a function of the set of poses behind it, not of their order.
+ *   table_host: float32 [planes][distances], planes = 1 (every head) or num_heads, distances = window ? window : capacity (window = 0
+ *             is the linear state).  The query at position p of head h scores key j (the keys the state shows it, as above) as
+ *             fl(fl(q . k * scale) + table[h or 0][p - j]); everything else is the unbiased state's.  Every entry must be finite: -inf
+ *             is no way to mask here, visibility stays with `window`.  The table is copied to the device once, synchronously, into an
+ *             allocation the state owns until _close (or flope_tf_destroy); it cannot be changed on an open state.
+ *   Contracts: _step returns, in bits, the last row of the forward of the track so far under flope_tf_bias_create's bias
+ *             [h][i][j] = table[h][i - j] for the visible j, -inf elsewhere (Python: distance_bias(table, L, window)), in EVERY dtype
+ *             and under every option, because a compiled bias sends each of them to tf_attn_masked's BIASED form, whose order over a
+ *             contiguous key range is this row's.  _prefill returns that forward's rows in bits (it runs tf_attn_extend's biased form
+ *             at position 0 behind its cache copy).  _extend returns the bits of the same tokens fed by _step, whatever the split.  A
+ *             zero table gives the bits of the unbiased state.
+ *   Plans:    _step_plan returns FLOPE_TF_STEP_BIASED and _extend_plan FLOPE_TF_EXTEND_BIASED on such a state, whatever "step_split"
+ *             and "extend_mfma" say (they do not reach it, as a compiled bias overrides mask_mfma / f32mfma / generic); the two test
+ *             hooks run the biased kernels and return these ids.
+ *   Refused with FLOPE_EINVAL, nothing allocated, the figure named: planes other than 1 or num_heads, distances other than
+ *             window ? window : capacity, a NULL table, a NaN or +-inf entry (the message names (plane, distance)), and what
+ *             _open / _open_window refuse.  FLOPE_EHIP: the allocation failed (the message names its size).
+ *   _bias_planes: the planes of the state's table, 0 for a state without one; < 0 on error. */
 #define FLOPE_TF_STEP_ROW         0
 #define FLOPE_TF_STEP_SPLIT       1
 #define FLOPE_TF_EXTEND_ROW       0
 #define FLOPE_TF_EXTEND_SPLIT     1
 #define FLOPE_TF_EXTEND_MFMA      2
+#define FLOPE_TF_STEP_BIASED      2
+#define FLOPE_TF_EXTEND_BIASED    3
 typedef struct flope_tf_stream_s* flope_tf_stream;
 int flope_tf_stream_open(flope_tf_handle h, int tracks, int capacity, flope_tf_stream* out);
 int flope_tf_stream_open_window(flope_tf_handle h, int tracks, int capacity, int window, flope_tf_stream* out);
+int flope_tf_stream_open_bias(flope_tf_handle h, int tracks, int capacity, int window, int planes, int distances, const float* table_host,
+                              flope_tf_stream* out);
+int flope_tf_stream_bias_planes(flope_tf_stream s);
 int flope_tf_stream_close(flope_tf_stream s);
 int flope_tf_stream_reset(flope_tf_stream s, int n, const int* tracks_host);
 /* tokens held by `track`, or < 0 */
