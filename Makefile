@@ -24,6 +24,7 @@ HARNESS_TF_MASK := tests/host_harness/libflope_host_tf_mask.so
 HARNESS_TF_MASK16 := tests/host_harness/libflope_host_tf_mask16.so
 HARNESS_TF_BIAS := tests/host_harness/libflope_host_tf_bias.so
 HARNESS_TF_STREAM_BIAS := tests/host_harness/libflope_host_tf_stream_bias.so
+HARNESS_TF_BIAS16 := tests/host_harness/libflope_host_tf_bias16.so
 HARNESS_DEPTH := tests/host_harness/libflope_host_depth.so
 HARNESS_CROP := tests/host_harness/libflope_host_crop.so
 HARNESS_FRAME := tests/host_harness/libflope_host_frame.so
@@ -32,7 +33,7 @@ OBJS     := $(patsubst $(CSRC)/%.hip,$(OBJDIR)/%.o,$(SRCS))
 HDRS     := $(wildcard $(CSRC)/*.h) include/flope_amd.h
 HIPFLAGS := --offload-arch=$(ARCH) -O3 -fPIC -std=c++17 -Wno-unused-value -Iinclude
 
-all: $(LIB) $(HARNESS) $(HARNESS_F32M) $(HARNESS_F32M_KSPLIT) $(HARNESS_GUARD) $(HARNESS_TF_F32M) $(HARNESS_TF_ATTN) $(HARNESS_TF_VARLEN) $(HARNESS_TF_FUSED) $(HARNESS_TF_CAUSAL) $(HARNESS_TF_STREAM) $(HARNESS_TF_WINDOW) $(HARNESS_TF_WINDOW16) $(HARNESS_TF_EXTEND) $(HARNESS_TF_SPLIT) $(HARNESS_TF_EXTEND16) $(HARNESS_TF_MASK) $(HARNESS_TF_MASK16) $(HARNESS_TF_BIAS) $(HARNESS_TF_STREAM_BIAS) $(HARNESS_DEPTH) $(HARNESS_CROP) $(HARNESS_FRAME)
+all: $(LIB) $(HARNESS) $(HARNESS_F32M) $(HARNESS_F32M_KSPLIT) $(HARNESS_GUARD) $(HARNESS_TF_F32M) $(HARNESS_TF_ATTN) $(HARNESS_TF_VARLEN) $(HARNESS_TF_FUSED) $(HARNESS_TF_CAUSAL) $(HARNESS_TF_STREAM) $(HARNESS_TF_WINDOW) $(HARNESS_TF_WINDOW16) $(HARNESS_TF_EXTEND) $(HARNESS_TF_SPLIT) $(HARNESS_TF_EXTEND16) $(HARNESS_TF_MASK) $(HARNESS_TF_MASK16) $(HARNESS_TF_BIAS) $(HARNESS_TF_STREAM_BIAS) $(HARNESS_TF_BIAS16) $(HARNESS_DEPTH) $(HARNESS_CROP) $(HARNESS_FRAME)
 
 $(OBJDIR)/%.o: $(CSRC)/%.hip $(HDRS)
 	@mkdir -p $(OBJDIR)
@@ -137,6 +138,12 @@ $(HARNESS_TF_BIAS): tests/host_harness/harness_tf_bias.cpp $(CSRC)/tf_attn_mask.
 $(HARNESS_TF_STREAM_BIAS): tests/host_harness/harness_tf_stream_bias.cpp $(CSRC)/tf_encoder_stream.h $(CSRC)/tf_attn_plan.h include/flope_amd.h
 	g++ -O2 -fPIC -shared -std=c++17 -I$(CSRC) -o $@ $<
 
+# a compiled bias on the 16-bit MFMA attention (option bias_mfma): tf_attn_pick_biased, the device layout with the tile map behind the
+# planes, the entry a lane of a taken step loads and the form of the load (tests/test_tf_bias16_host.py, tests/test_gpu_tf_bias16.py); the
+# test also builds the file as a stand-alone program under AddressSanitizer + UBSan (-DTF_BIAS16_MAIN) and runs it as a child process
+$(HARNESS_TF_BIAS16): tests/host_harness/harness_tf_bias16.cpp $(CSRC)/tf_attn_mask.h $(CSRC)/tf_attn_plan.h include/flope_amd.h
+	g++ -O2 -fPIC -shared -std=c++17 -I$(CSRC) -o $@ $<
+
 # conditioning figure and flag predicate of the guarded mode (tests/test_guard_host.py)
 $(HARNESS_GUARD): tests/host_harness/harness_guard.cpp $(CSRC)/pose_math.h
 	g++ -O2 -fPIC -shared -std=c++17 -I$(CSRC) -o $@ $<
@@ -177,7 +184,7 @@ dbg: $(DBGOBJS)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $(DBGDIR)/libflope_amd_dbg.so $(DBGOBJS)
 
 clean:
-	rm -rf build $(LIB) $(HARNESS) $(HARNESS_F32M) $(HARNESS_F32M_KSPLIT) $(HARNESS_GUARD) $(HARNESS_TF_F32M) $(HARNESS_TF_ATTN) $(HARNESS_TF_VARLEN) $(HARNESS_TF_FUSED) $(HARNESS_TF_CAUSAL) $(HARNESS_TF_STREAM) $(HARNESS_TF_WINDOW) $(HARNESS_TF_WINDOW16) $(HARNESS_TF_EXTEND) $(HARNESS_TF_SPLIT) $(HARNESS_TF_EXTEND16) $(HARNESS_TF_MASK) $(HARNESS_TF_MASK16) $(HARNESS_TF_BIAS) $(HARNESS_TF_STREAM_BIAS) $(HARNESS_DEPTH) $(HARNESS_CROP) $(HARNESS_FRAME)
+	rm -rf build $(LIB) $(HARNESS) $(HARNESS_F32M) $(HARNESS_F32M_KSPLIT) $(HARNESS_GUARD) $(HARNESS_TF_F32M) $(HARNESS_TF_ATTN) $(HARNESS_TF_VARLEN) $(HARNESS_TF_FUSED) $(HARNESS_TF_CAUSAL) $(HARNESS_TF_STREAM) $(HARNESS_TF_WINDOW) $(HARNESS_TF_WINDOW16) $(HARNESS_TF_EXTEND) $(HARNESS_TF_SPLIT) $(HARNESS_TF_EXTEND16) $(HARNESS_TF_MASK) $(HARNESS_TF_MASK16) $(HARNESS_TF_BIAS) $(HARNESS_TF_STREAM_BIAS) $(HARNESS_TF_BIAS16) $(HARNESS_DEPTH) $(HARNESS_CROP) $(HARNESS_FRAME)
 
 # stand-alone measurement programs used by tools/collect_profiles.sh and DESIGN.md section 9 (not part of the library)
 TOOLBINS := build/fetch_calib build/launch_floor build/loop_probe build/loop_probe32 build/dma_issue_probe

@@ -14,6 +14,7 @@ IN_F32_NCHW, IN_BF16_NHWC, IN_F16_NHWC, IN_U8_NHWC = 0, 1, 2, 3
 TF_ATTN_GENERIC, TF_ATTN_MFMA64, TF_ATTN_TILED, TF_ATTN_F32M = 0, 1, 2, 3     # flope_tf_attention's return (tf_attn_plan.h)
 TF_ATTN_MASKED16 = 5                                                           # ... under option mask_mfma where tf_attn_pick_masked picks tf_attn_tiled_masked
 TF_ATTN_MASKED = 4                                                             # flope_tf_attention_masked's return
+TF_ATTN_BIASED16 = 7                                                           # ... under a compiled bias and option bias_mfma where tf_attn_pick_biased picks tf_attn_tiled_masked, BIASED
 TF_ATTN_BIASED = 6                                                             # ... under a compiled bias (flope_tf_bias_create): tf_attn_masked, BIASED
 TF_LIN_GENERIC, TF_LIN_ROWWAVE, TF_LIN_ROWWAVE_VEC, TF_LIN_MFMA, TF_LIN_F32M = 0, 1, 2, 3, 4      # flope_tf_linear's return
 TF_FWD_LAUNCHES, TF_FWD_FUSED = 0, 1                                           # flope_tf_forward_plan's return

@@ -267,4 +267,38 @@ inline size_t tf_bias_dev_bytes(int L, int planes) { return tf_bias_dev_bias_at(
 // planes == 1).  i and j are positions in the mask's L x L planes whatever the length of the sequence (the corner's rows keep stride L).
 inline size_t tf_bias_index(int L, int planes, int h, int i, int j) { return ((size_t)(planes > 1 ? h : 0) * L + (size_t)i) * L + (size_t)j; }
 
+// ---- a compiled bias on the 16-bit MFMA attention (option "bias_mfma") ----------------------------------------------------
+// tf_attn_tiled_masked's BIASED instantiation walks the tile map of the bias's allowed set (the -inf entries of plane 0) and so needs it on
+// the device: a bias handle's allocation is bits | first | last | bias | start | tiles, the map BEHIND the planes, so that
+// tf_bias_dev_bias_at and tf_bias_dev_bytes (the end of the planes) keep their values; the entries start on a 16-byte boundary.  Uploaded
+// for every bias: the option may be flipped between forwards.
+inline size_t tf_bias_dev_start_at(int L, int planes) { return tf_bias_dev_bytes(L, planes); }
+inline size_t tf_bias_dev_tiles_at(int L, int planes) { return (tf_bias_dev_start_at(L, planes) + ((size_t)tf_mask_query_blocks(L) + 1) * 4 + 15) / 16 * 16; }
+inline size_t tf_bias_dev_bytes_tiled(int L, int planes, long long entries) { return tf_bias_dev_tiles_at(L, planes) + (size_t)entries * sizeof(TfMaskTile); }
+
+// The head_dims whose BIASED instantiation of tf_attn_tiled_masked was built without scratch (all four that
+// tf_attn_tiled_ok admits); a head_dim that is not listed here keeps tf_attn_masked under a bias.
+constexpr bool tf_attn_biased16_built(int head_dim) { return head_dim == 32 || head_dim == 64 || head_dim == 96 || head_dim == 128; }
+
+// The kernel a launch under a compiled bias takes: tf_attn_tiled_masked's BIASED instantiation for a 16-bit handle under option
+// bias_mfma = 1 (generic = 0) at every head_dim tf_attn_tiled serves and that instantiation was built for without scratch, 16-byte aligned
+// buffers; tf_attn_masked's otherwise.  Option mask_mfma has no say: it is the plain masks' option.
+inline int tf_attn_pick_biased(int dtype, int head_dim, int opt_generic, int opt_bias_mfma, int aligned16) {
+  if (dtype != FLOPE_DT_F32 && opt_bias_mfma == 1 && !opt_generic && tf_attn_tiled_ok(head_dim) && tf_attn_biased16_built(head_dim) && aligned16)
+    return FLOPE_TF_ATTN_BIASED16;
+  return FLOPE_TF_ATTN_BIASED;
+}
+
+// The bias entry a lane of the BIASED tf_attn_tiled_masked loads for accumulator element q = 0 .. 3 of S^T tile u = 0 .. 1 in lane group
+// g = 0 .. 3 in the step that starts at key kb < n (a multiple of 32): row min(query, n - 1) of the sequence of n <= L tokens in plane h
+// (plane 0 when planes == 1), the column of the key kb + 16 u + 4 g + q itself, clamped to L - 1 -- a key at or past L is never seen, and
+// no address outside [0, L) of the row is formed.  An index into the float32 planes.
+inline size_t tf_bias16_lane_index(int L, int planes, int n, int h, int query, int kb, int u, int g, int q) {
+  const int col = kb + 16 * u + 4 * g + q;
+  return tf_bias_index(L, planes, h, query < n ? query : n - 1, col < L ? col : L - 1);
+}
+// ... and whether the lanes of that step take one 16-byte load per (query tile, u) in place of four clamped dword loads: the plane rows
+// start on 16-byte boundaries (L a multiple of 4; tf_bias_dev_bias_at(L) then is a multiple of 16) and the step's 32 columns lie inside the row
+constexpr bool tf_bias16_step_vec(int L, int kb) { return !(L & 3) && kb + 32 <= L; }
+
 }  // namespace flope_tf_plan

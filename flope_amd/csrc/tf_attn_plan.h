@@ -18,6 +18,7 @@ enum {
   FLOPE_TF_ATTN_F32M = 3,      // tf_attn_f32m: float32 on v_mfma_f32_16x16x4_f32 (option f32mfma)
   FLOPE_TF_ATTN_MASKED = 4,    // tf_attn_masked: any shape under a compiled mask (flope_tf_attention_masked; tf_attn_mask.h)
   FLOPE_TF_ATTN_MASKED16 = 5,  // tf_attn_tiled_masked: 16-bit, head_dim 32 / 64 / 96 / 128 under a compiled mask (option mask_mfma; tf_attn_mask.h)
+  FLOPE_TF_ATTN_BIASED16 = 7,  // tf_attn_tiled_masked, BIASED: 16-bit, head_dim 32 / 64 / 96 / 128 under a compiled bias (option bias_mfma; tf_attn_mask.h)
   FLOPE_TF_ATTN_BIASED = 6     // tf_attn_masked, BIASED: any shape under a compiled additive bias (flope_tf_bias_create; tf_attn_mask.h)
 };
 

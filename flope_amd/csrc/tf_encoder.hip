@@ -41,8 +41,11 @@
 // bits; tf_attn_tiled's bits where the mask is all-clear, causal, a causal band or block-diagonal at multiples of 32.
 // flope_tf_bias_create (any dtype): an additive float mask -- the allowed set of its -inf entries plus a float32 value per
 // allowed pair, one [L, L] plane or one per head -- on the mask's handle type; a launch under it is tf_attn_masked's BIASED instantiation
-// for every dtype and option: the unbiased order with bias[h][i][j] added to the scaled score in a rounding of its own, a zero bias
-// giving its bits (why a flag and not a kernel of its own).
+// for every dtype and option but bias_mfma: the unbiased order with bias[h][i][j] added to the scaled score in a rounding of its own, a
+// zero bias giving its bits (why a flag and not a kernel of its own).
+// Option bias_mfma = 1 (16-bit handles): a launch under a compiled bias runs tf_attn_tiled_masked's BIASED instantiation where
+// tf_attn_pick_biased says so -- the walk of mask_mfma over the tile map of the bias's allowed set, which every bias carries behind its
+// planes, with tf_attn16_step's BIASED form: one fma per score; a zero bias gives the bits of the compiled mask under mask_mfma = 1.
 #include "../../include/flope_amd.h"
 #include "common.h"
 #include "host_pack.h"
@@ -1168,12 +1171,22 @@ template <int HD32> __device__ __forceinline__ TfAttn16Lane tf_attn16_lane(int l
 // under WINDOW a query may see nothing in a step its wave takes, its first one included: the same msafe keeps its state at exactly 0
 // until its first own key.  Every stored query has a key in a step its wave takes (the host refuses a row without one), so lrun > 0 at
 // the store; a query at or past L takes the word of row L - 1 or ~0 and is not stored.
-template <typename T, int HD32, bool CAUSAL = false, bool WINDOW = false, bool MASKED = false>
+// BIASED (with MASKED, option bias_mfma): bl(qt, u)[q] is the float32 entry of the compiled bias that belongs to the lane's
+// query of tile qt and to key kb + 16 u + 4 g + q (flope_tf_plan::tf_bias16_lane_index).  bl is the kernel's: values it loaded in front
+// of the step, or the loads themselves, made per query tile where sixteen live values do not fit (head_dim 128).  The score of a seen key is
+// fma(b, log2e, fl(s scale_log2e)) -- the scores live in the log2 domain -- ONE fma with one rounding on top of the product, which keeps the
+// rounding it has in every other instantiation: product and fma stand in a block under `#pragma clang fp contract(off)`, so the compiler
+// can merge the multiply into nothing (tf_attn_masked_row: the round-to-nearest intrinsics do not achieve that here).  With b = 0 the fma
+// returns the product up to the sign of a zero, which reaches no output: a zero bias gives the MASKED bits.  The entry of a pair that is
+// not seen may have been loaded (its -inf under a mask bit that is clear, any entry of a key at or past L); the select discards it.
+template <typename T, int HD32, bool CAUSAL = false, bool WINDOW = false, bool MASKED = false, bool BIASED = false, typename BL = int>
 __device__ __forceinline__ void tf_attn16_step(const char* Ki, const char* Vi, int kb, int kl, int L, int q0, float scale_log2e,
                                                const TfAttn16Lane& ln, const typename Elem<T>::frag (&qf)[2][HD32], float (&mrun)[2],
-                                               float (&lrun)[2], f32x4 (&o)[2][2 * HD32], int W = 0, const uint32_t* mw = nullptr) {
+                                               float (&lrun)[2], f32x4 (&o)[2][2 * HD32], int W = 0, const uint32_t* mw = nullptr,
+                                               BL bl = BL()) {
   static_assert(CAUSAL || !WINDOW, "a window without causal has no meaning");
   static_assert(!MASKED || (!CAUSAL && !WINDOW), "a compiled mask says everything itself");
+  static_assert(MASKED || !BIASED, "a bias comes with its compiled mask");
   typedef typename Elem<T>::frag frag;
   constexpr int RB = 64 * HD32;
   const int g = ln.g, li = ln.li, ksw = ln.ksw, trp = ln.trp, vrow = ln.vrow, vsw = ln.vsw;
@@ -1195,6 +1208,11 @@ __device__ __forceinline__ void tf_attn16_step(const char* Ki, const char* Vi, i
   for (int qt = 0; qt < 2; ++qt) {
     float v[8];
     float mx = -INFINITY;
+    f32x4 bv[2];
+    if constexpr (BIASED) {
+      if constexpr (HD32 == 4) __builtin_amdgcn_sched_barrier(0);      // per query tile: the loads stay behind the QK MFMAs and the other tile's pass
+      bv[0] = bl(qt, 0); bv[1] = bl(qt, 1);
+    }
 #pragma unroll
     for (int u = 0; u < 2; ++u)
 #pragma unroll
@@ -1204,7 +1222,12 @@ __device__ __forceinline__ void tf_attn16_step(const char* Ki, const char* Vi, i
         if constexpr (CAUSAL) seen = seen && key <= q0 + qt * 16 + li;
         if constexpr (WINDOW) seen = seen && key > q0 + qt * 16 + li - W;      // key + W > query, without the overflow of a huge W
         if constexpr (MASKED) seen = seen && ((mw[qt] >> (u * 16 + g * 4 + q)) & 1u);
-        const float x = seen ? s[u][qt][q] * scale_log2e : -INFINITY;
+        float x;
+        if constexpr (BIASED) {
+#pragma clang fp contract(off)
+          const float a = s[u][qt][q] * scale_log2e;
+          x = seen ? __builtin_fmaf(bv[u][q], 1.4426950408889634f, a) : -INFINITY;
+        } else x = seen ? s[u][qt][q] * scale_log2e : -INFINITY;
         v[u * 4 + q] = x;
         mx = fmaxf(mx, x);
       }
@@ -1486,11 +1509,23 @@ __global__ __launch_bounds__(256, 2) void tf_attn_tiled(const T* __restrict__ qk
 // the causal skip.  kTfMaskAll: mw = ~0 without a load.  kTfMaskSome: the lane loads word kb / 32 of row min(query, L - 1) of the mask
 // for its two query tiles -- query and L are the sequence's own, so no word outside the mask is read -- in front of the step's MFMAs.
 // Every stored query has a key in a taken step, so lrun > 0 at the store (tf_mask_length_row under VARLEN).
-template <typename T, int HD32, bool VARLEN = false>
+// BIASED (option bias_mfma): BIAS is (const float* bias, int planes, int Lm) -- the handle's float32 planes [planes][Lm][Lm]
+// (planes = 1: every head reads plane 0), Lm the mask's seq_len, the row stride whatever the sequence's own length -- and the empty pack
+// otherwise: an unbiased instantiation's argument block is byte for byte what it was.  In a taken step, of class "some" or
+// "all", the lane loads its sixteen entries in front of the step's MFMAs, where the mask words are loaded: row min(query, n - 1) of plane h
+// or 0, columns kb + 16 u + 4 g .. + 3 for u = 0, 1 and both query tiles (flope_tf_plan::tf_bias16_lane_index's arithmetic).  A plane row
+// starts on a 4-byte boundary only (Lm is arbitrary), so the 16-byte load is taken where Lm is a multiple of 4 and the step lies inside the
+// row (kb + 32 <= Lm; both uniform), and four dword loads with the column clamped to Lm - 1 otherwise: no address outside [0, Lm) of that
+// row is formed, whatever lies behind the planes.  An entry of a masked pair may be loaded (-inf) and is never used (tf_attn16_step).
+// "none" steps and steps at or past n load nothing.  Head_dim 128 (230 VGPRs of 256 without a bias) loads per query tile inside the step,
+// eight values live at a time, by dword loads alone and makes each row address anew: as built it uses all 256 VGPRs and no scratch.
+struct TfBias16 { const float* bias; int planes, Lm; };
+template <typename T, int HD32, bool VARLEN = false, bool BIASED = false, typename... BIAS>
 __global__ __launch_bounds__(256, 2) void tf_attn_tiled_masked(const T* __restrict__ qkv, T* __restrict__ out, int L, int d, int H,
                                                                float scale_log2e, const int* __restrict__ off, int mwords,
                                                                const uint32_t* __restrict__ bits, const int* __restrict__ start,
-                                                               const flope_tf_plan::TfMaskTile* __restrict__ tiles) {
+                                                               const flope_tf_plan::TfMaskTile* __restrict__ tiles, BIAS... bias_args) {
+  static_assert(sizeof...(BIAS) == (BIASED ? 3 : 0), "a BIASED instantiation takes (bias, planes, Lm), an unbiased one nothing");
   typedef typename Elem<T>::frag frag;
   constexpr int HD = 32 * HD32, KB = TfTiledStaging<HD32>::KB, BLK = TfTiledStaging<HD32>::BLK, STAGE = TfTiledStaging<HD32>::STAGE;
   extern __shared__ __attribute__((aligned(16))) char smem[];      // [2 stages][K block [64][RB] | V block [64][RB]]
@@ -1537,11 +1572,18 @@ __global__ __launch_bounds__(256, 2) void tf_attn_tiled_masked(const T* __restri
   const int q0 = blockIdx.y * flope_tf_plan::kTfAttnTiledQueries + wave * 32;
   frag qf[2][HD32];
   int mrow[2];                                   // the lane's two rows of the mask, in words
+  const float* brow[2] = {nullptr, nullptr};     // BIASED, head_dim < 128: ... and of its head's bias plane
+  int Lm = 0;
+  if constexpr (BIASED) Lm = TfBias16{bias_args...}.Lm;
 #pragma unroll
   for (int qt = 0; qt < 2; ++qt) {
     int qi = q0 + qt * 16 + li;
     qi = qi < L ? qi : L - 1;
     mrow[qt] = qi * mwords;
+    if constexpr (BIASED && HD32 < 4) {
+      const TfBias16 t{bias_args...};
+      brow[qt] = t.bias + ((size_t)(t.planes > 1 ? h : 0) * t.Lm + (size_t)qi) * t.Lm;
+    }
 #pragma unroll
     for (int ks = 0; ks < HD32; ++ks) qf[qt][ks] = *(const frag*)(base + (size_t)qi * 3 * d + (ks * 4 + g) * 8);
   }
@@ -1572,6 +1614,35 @@ __global__ __launch_bounds__(256, 2) void tf_attn_tiled_masked(const T* __restri
 #pragma unroll
         for (int qt = 0; qt < 2; ++qt) mw[qt] = bits[mrow[qt] + (kb >> 5)];
       }
+      if constexpr (BIASED) {
+        // uniform: 16-byte loads where the plane rows start on 16-byte boundaries.  Not at head_dim 128: with both forms of the load in
+        // the kernel that instantiation needs scratch (22 VGPRs spilled), with the dword form alone it fits its 256
+        const bool vec = HD32 < 4 && flope_tf_plan::tf_bias16_step_vec(Lm, kb);
+        auto bload = [&](int qt, int u) {
+          const float* row = brow[qt];
+          if constexpr (HD32 == 4) {               // the row's address is made anew at every load: no register holds it across the steps
+            const TfBias16 t{bias_args...};
+            const int qi = q0 + qt * 16 + li;
+            row = t.bias + ((size_t)(t.planes > 1 ? h : 0) * t.Lm + (size_t)(qi < L ? qi : L - 1)) * t.Lm;
+          }
+          f32x4 r;
+          if (vec) r = *(const f32x4*)(row + kb + 16 * u + 4 * g);
+          else {
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+              const int col = kb + 16 * u + 4 * g + q;
+              r[q] = row[col < Lm ? col : Lm - 1];
+            }
+          }
+          return r;
+        };
+        if constexpr (HD32 < 4) {                  // sixteen values, loaded in front of the step's MFMAs
+          const f32x4 bv[4] = {bload(0, 0), bload(0, 1), bload(1, 0), bload(1, 1)};
+          tf_attn16_step<T, HD32, false, false, true, true>(Ki, Vi, kb, kl, L, q0, scale_log2e, ln, qf, mrun, lrun, o, 0, mw,
+                                                            [&](int qt, int u) { return bv[2 * qt + u]; });
+        } else                                     // head_dim 128: eight live at a time, loaded per query tile inside the step (no scratch)
+          tf_attn16_step<T, HD32, false, false, true, true>(Ki, Vi, kb, kl, L, q0, scale_log2e, ln, qf, mrun, lrun, o, 0, mw, bload);
+      } else
       tf_attn16_step<T, HD32, false, false, true>(Ki, Vi, kb, kl, L, q0, scale_log2e, ln, qf, mrun, lrun, o, 0, mw);
     }
     sg.lwrite(smem + ((trip + 1) & 1) * STAGE);
@@ -2047,6 +2118,7 @@ struct flope_tf_encoder {
   int opt_window = 0;                        // W > 0 (honoured with opt_causal = 1, refused without): keys i - W < j <= i, on tf_attn_generic unless opt_window_mfma, never tf_fused_f32
   int opt_window_mfma = 0;                   // 1: under causal with a window a 16-bit launch keeps tf_attn_pick's tf_attn_mfma / tf_attn_tiled, their WINDOW instantiations (stored and ignored by float32 handles)
   int opt_step_split = 0;                    // 1: flope_tf_stream_step / _extend split a token's keys over the four waves of a workgroup where tf_step_split_ok (every dtype)
+  int opt_bias_mfma = 0;                     // 1: a 16-bit launch under a compiled bias is tf_attn_tiled_masked's BIASED instantiation where tf_attn_pick_biased says so (stored and ignored by float32 handles)
   int opt_mask_mfma = 0;                     // 1: a 16-bit launch under a compiled mask is tf_attn_tiled_masked where tf_attn_pick_masked says so (stored and ignored by float32 handles)
   int opt_extend_mfma = 0;                   // 1: flope_tf_stream_extend's attention is tf_attn16_extend where tf_extend_mfma_ok (stored and ignored by float32 handles); wins over opt_step_split for _extend only
   int last_masked_attn = -1;                 // FLOPE_TF_ATTN_* id of the attention launches of the last flope_tf_forward_masked that enqueued anything (flope_tf_last_forward_masked), -1: none yet
@@ -2095,13 +2167,15 @@ struct flope_tf_mask {
   std::vector<int> first, last;
   std::vector<int> start;                    // the tile map (tf_attn_mask.h), built for every mask: option mask_mfma may be flipped between forwards
   std::vector<flope_tf_plan::TfMaskTile> tiles;
-  int planes = 0;                            // 0: a plain mask.  1 or num_heads: a compiled additive bias (flope_tf_bias_create): dev is bits | first | last | float bias [planes][L][L], the tile map stays on the host
+  int planes = 0;                            // 0: a plain mask.  1 or num_heads: a compiled additive bias (flope_tf_bias_create): dev is bits | first | last | float bias [planes][L][L] | start | tiles (the tile map behind the planes: option bias_mfma)
   const float* bias_dev() const { return (const float*)((const char*)dev + flope_tf_plan::tf_bias_dev_bias_at(L)); }
   const uint32_t* bits_dev() const { return (const uint32_t*)dev; }
   const int* first_dev() const { return (const int*)(bits_dev() + bits.size()); }
   const int* last_dev() const { return first_dev() + L; }
-  const int* start_dev() const { return (const int*)((const char*)dev + flope_tf_plan::tf_mask_dev_start_at(L)); }
-  const flope_tf_plan::TfMaskTile* tiles_dev() const { return (const flope_tf_plan::TfMaskTile*)((const char*)dev + flope_tf_plan::tf_mask_dev_tiles_at(L)); }
+  const int* start_dev() const { return (const int*)((const char*)dev + (planes ? flope_tf_plan::tf_bias_dev_start_at(L, planes) : flope_tf_plan::tf_mask_dev_start_at(L))); }
+  const flope_tf_plan::TfMaskTile* tiles_dev() const {
+    return (const flope_tf_plan::TfMaskTile*)((const char*)dev + (planes ? flope_tf_plan::tf_bias_dev_tiles_at(L, planes) : flope_tf_plan::tf_mask_dev_tiles_at(L)));
+  }
 };
 
 namespace {
@@ -2521,6 +2595,13 @@ extern "C" int flope_tf_create(int device_id, int input_dim, int model_dim, int 
         return fin(tf_fail(nullptr, FLOPE_EHIP, "flope_tf_create: hipFuncSetAttribute failed"));
     const void* const masked16[] = {(const void*)tf_attn_tiled_masked<f16_t, 4>, (const void*)tf_attn_tiled_masked<bf16_t, 4>,
                                     (const void*)tf_attn_tiled_masked<f16_t, 4, true>, (const void*)tf_attn_tiled_masked<bf16_t, 4, true>};
+    const void* const biased16[] = {(const void*)tf_attn_tiled_masked<f16_t, 4, false, true, const float*, int, int>,
+                                    (const void*)tf_attn_tiled_masked<bf16_t, 4, false, true, const float*, int, int>,
+                                    (const void*)tf_attn_tiled_masked<f16_t, 4, true, true, const float*, int, int>,
+                                    (const void*)tf_attn_tiled_masked<bf16_t, 4, true, true, const float*, int, int>};
+    for (const void* f : biased16)
+      if (hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)flope_tf_plan::tf_attn_tiled_lds(128)) != hipSuccess)
+        return fin(tf_fail(nullptr, FLOPE_EHIP, "flope_tf_create: hipFuncSetAttribute failed"));
     for (const void* f : masked16)
       if (hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)flope_tf_plan::tf_attn_tiled_lds(128)) != hipSuccess)
         return fin(tf_fail(nullptr, FLOPE_EHIP, "flope_tf_create: hipFuncSetAttribute failed"));
@@ -2580,6 +2661,10 @@ extern "C" int flope_tf_set_option(flope_tf_handle e, const char* name, int valu
   if (!strcmp(name, "mask_mfma")) {
     if (value < 0 || value > 1) return tf_fail(e, FLOPE_EINVAL, "flope_tf_set_option: mask_mfma is 0 or 1");
     const int old = e->opt_mask_mfma; e->opt_mask_mfma = value; return old;
+  }
+  if (!strcmp(name, "bias_mfma")) {
+    if (value < 0 || value > 1) return tf_fail(e, FLOPE_EINVAL, "flope_tf_set_option: bias_mfma is 0 or 1");
+    const int old = e->opt_bias_mfma; e->opt_bias_mfma = value; return old;
   }
   if (!strcmp(name, "step_split")) {
     if (value < 0 || value > 1) return tf_fail(e, FLOPE_EINVAL, "flope_tf_set_option: step_split is 0 or 1");
@@ -2852,26 +2937,32 @@ namespace {
 // always is plus the mask rows in LDS (tf_mask_launch), unless option mask_mfma sends a 16-bit launch to tf_attn_tiled_masked, launched
 // as tf_attn_tiled is (tf_mask16_launch).  off == nullptr: qkv [B][L][3 d], L == m->L; otherwise the packed rows of a ragged batch, L
 // its longest length.  Returns the kernel's FLOPE_TF_ATTN_* id, or < 0.
-// A handle that carries a bias (m->planes > 0) takes tf_attn_masked's BIASED instantiation on every dtype and under every
-// option, launched by tf_mask_launch as the unbiased one is.
+// A handle that carries a bias (m->planes > 0) takes tf_attn_masked's BIASED instantiation on every dtype, launched by
+// tf_mask_launch as the unbiased one is, unless option bias_mfma (not mask_mfma) sends a 16-bit launch to tf_attn_tiled_masked's
+// BIASED instantiation (tf_attn_pick_biased), launched by tf_mask16_launch.
 int tf_masked_pick(const flope_tf_encoder* e, const flope_tf_mask* m, const void* qkv, const void* att) {
-  if (m->planes) return FLOPE_TF_ATTN_BIASED;
+  if (m->planes) return flope_tf_plan::tf_attn_pick_biased(e->dtype, e->d / e->H, e->opt_generic, e->opt_bias_mfma, !(((uintptr_t)qkv | (uintptr_t)att) & 15));
   return flope_tf_plan::tf_attn_pick_masked(e->dtype, e->d / e->H, e->opt_generic, e->opt_mask_mfma, !(((uintptr_t)qkv | (uintptr_t)att) & 15));
 }
 template <typename T>
 int launch_attention_masked(flope_tf_encoder* e, const flope_tf_mask* m, const void* qkv, void* att, int B, int L, const int* off, hipStream_t st) {
   const int dh = e->d / e->H, pick = tf_masked_pick(e, m, qkv, att);
-  const flope_tf_plan::TfAttnLaunch l = pick == FLOPE_TF_ATTN_MASKED16 ? flope_tf_plan::tf_mask16_launch(dh, B, e->H, L)
-                                                                       : flope_tf_plan::tf_mask_launch(dh, B, e->H, L, m->L);
+  const bool tiled = pick == FLOPE_TF_ATTN_MASKED16 || pick == FLOPE_TF_ATTN_BIASED16;
+  const flope_tf_plan::TfAttnLaunch l = tiled ? flope_tf_plan::tf_mask16_launch(dh, B, e->H, L) : flope_tf_plan::tf_mask_launch(dh, B, e->H, L, m->L);
   const dim3 grid(l.grid_x, l.grid_y), block(l.block);
   auto launch = [&](auto varlen, auto biased) {
     constexpr bool VL = decltype(varlen)::value, BI = decltype(biased)::value;
-    if constexpr (!std::is_same<T, float>::value && !BI) {
-      if (pick == FLOPE_TF_ATTN_MASKED16) {
+    if constexpr (!std::is_same<T, float>::value) {
+      if (tiled) {
         const float scale_log2e = 1.4426950408889634f / sqrtf((float)dh);
         tf_by_hd32(dh, [&](auto hd32) {
-          hipLaunchKernelGGL((tf_attn_tiled_masked<T, decltype(hd32)::value, VL>), grid, block, l.lds, st, (const T*)qkv, (T*)att, L, e->d, e->H, scale_log2e, off,
-                             flope_tf_plan::tf_mask_words(m->L), m->bits_dev(), m->start_dev(), m->tiles_dev());
+          if constexpr (BI)
+            hipLaunchKernelGGL((tf_attn_tiled_masked<T, decltype(hd32)::value, VL, true, const float*, int, int>), grid, block, l.lds, st, (const T*)qkv, (T*)att, L,
+                               e->d, e->H, scale_log2e, off, flope_tf_plan::tf_mask_words(m->L), m->bits_dev(), m->start_dev(), m->tiles_dev(), m->bias_dev(),
+                               m->planes, m->L);
+          else
+            hipLaunchKernelGGL((tf_attn_tiled_masked<T, decltype(hd32)::value, VL>), grid, block, l.lds, st, (const T*)qkv, (T*)att, L, e->d, e->H, scale_log2e, off,
+                               flope_tf_plan::tf_mask_words(m->L), m->bits_dev(), m->start_dev(), m->tiles_dev());
         });
         return;
       }
@@ -2912,16 +3003,17 @@ int tf_masked_check(flope_tf_encoder* e, const std::string& who, const flope_tf_
     }
     max_len = rg->max_len;
   }
-  if (tf_masked_pick(e, m, qkv, att) != FLOPE_TF_ATTN_MASKED16 &&      // tf_attn_tiled_masked keeps no row in LDS
+  const int pick = tf_masked_pick(e, m, qkv, att);
+  if (pick != FLOPE_TF_ATTN_MASKED16 && pick != FLOPE_TF_ATTN_BIASED16 &&      // tf_attn_tiled_masked keeps no row in LDS
       flope_tf_plan::tf_mask_launch(e->d / e->H, batch, e->H, max_len, m->L).lds > flope_tf_plan::kTfAttnLds)
     return tf_fail(e, FLOPE_EINVAL, who + ": seq_len too long for the score rows of one workgroup");
   return 0;
 }
 
 // What flope_tf_mask_create and flope_tf_bias_create end in once m->bits are final (m->L and m->planes set, every validator passed): the
-// first / last tables, the pair count and the tile map on the host (under a bias host only: what flope_tf_mask_tiles reports), one
-// allocation laid out by tf_mask_dev_* / tf_bias_dev_* (tf_attn_mask.h) with bits | first | last and behind them the tile map or the
-// bias planes, and the mask on the handle's list.  Owns m: a failure frees it.
+// first / last tables, the pair count and the tile map on the host, one allocation laid out by tf_mask_dev_* / tf_bias_dev_*
+// (tf_attn_mask.h) with bits | first | last and behind them the tile map, or the bias planes and then the tile map (every bias: option
+// bias_mfma may be flipped between forwards), and the mask on the handle's list.  Owns m: a failure frees it.
 int tf_mask_finish(flope_tf_encoder* e, const std::string& who, flope_tf_mask* m, const float* bias_host, flope_tf_mask_handle* out) {
   using namespace flope_tf_plan;
   const int L = m->L, planes = m->planes;
@@ -2933,7 +3025,7 @@ int tf_mask_finish(flope_tf_encoder* e, const std::string& who, flope_tf_mask* m
   m->tiles.resize((size_t)tf_mask_tiles_build(m->bits.data(), L, m->start.data(), nullptr));
   tf_mask_tiles_build(m->bits.data(), L, m->start.data(), m->tiles.data());
   const size_t nb = m->bits.size() * sizeof(uint32_t), nt = (size_t)L * sizeof(int);
-  const size_t all = planes ? tf_bias_dev_bytes(L, planes) : tf_mask_dev_bytes(L, (long long)m->tiles.size());
+  const size_t all = planes ? tf_bias_dev_bytes_tiled(L, planes, (long long)m->tiles.size()) : tf_mask_dev_bytes(L, (long long)m->tiles.size());
   auto fin = [&](const std::string& what) { hipFree(m->dev); delete m; return tf_fail(e, FLOPE_EHIP, who + ": " + what); };
   auto put = [&](size_t at, const void* src, size_t bytes) { return hipMemcpy((char*)m->dev + at, src, bytes, hipMemcpyHostToDevice) == hipSuccess; };
   if (hipSetDevice(e->device) != hipSuccess) return fin("hipSetDevice failed");
@@ -2943,9 +3035,9 @@ int tf_mask_finish(flope_tf_encoder* e, const std::string& who, flope_tf_mask* m
                (planes ? " (" + std::to_string(planes) + " float32 planes of " + std::to_string((size_t)L * L * 4) + " bytes)" : std::string()));
   }
   if (!put(0, m->bits.data(), nb) || !put(nb, m->first.data(), nt) || !put(nb + nt, m->last.data(), nt) ||
-      !(planes ? put(tf_bias_dev_bias_at(L), bias_host, (size_t)planes * L * L * sizeof(float))
-               : put(tf_mask_dev_start_at(L), m->start.data(), m->start.size() * sizeof(int)) &&
-                     put(tf_mask_dev_tiles_at(L), m->tiles.data(), m->tiles.size() * sizeof(TfMaskTile))))
+      (planes && !put(tf_bias_dev_bias_at(L), bias_host, (size_t)planes * L * L * sizeof(float))) ||
+      !put(planes ? tf_bias_dev_start_at(L, planes) : tf_mask_dev_start_at(L), m->start.data(), m->start.size() * sizeof(int)) ||
+      !put(planes ? tf_bias_dev_tiles_at(L, planes) : tf_mask_dev_tiles_at(L), m->tiles.data(), m->tiles.size() * sizeof(TfMaskTile)))
     return fin("hipMemcpy failed");
   m->e = e;
   e->masks.push_back(m);

@@ -16,7 +16,8 @@ exactly its allowed keys, a masked key is never loaded, and a sequence of a ragg
 tile map, loading only the 64-key blocks some query of a 128-row block allows.
 An additive float mask -- torch's `mask=` with values other than -inf / 0, one [L, L] plane or one per head -- is compiled with
 `enc.make_bias(bias)` and passed the same way; `alibi_bias(L, slopes)` builds the distance bias this encoder, which has no positional
-term, needs to tell the order of the poses behind a query.
+term, needs to tell the order of the poses behind a query.  A 16-bit encoder made with `bias_mfma=1` runs attention
+under a compiled bias on the MFMA attention step over the tile map of the bias's allowed set.
 
 Eval-mode semantics only (dropout is identity), as everywhere in this package.  There is no CPU
 path: construction fails loudly without a HIP device or without the built library.
@@ -207,7 +208,7 @@ def distance_bias(table, L, window=0):
 class TransformerEncoder:
     def __init__(self, input_dim, model_dim, out_dim, num_heads, num_layers, ff_dim, dropout=0.1,
                  dtype="f32", max_tokens=4096, device=None, attn_tiled=0, fused=0, window_mfma=0, step_split=0, extend_mfma=0,
-                 mask_mfma=0):
+                 mask_mfma=0, bias_mfma=0):
         _require_gpu()
         self.lib = _lib.load()
         self.device = torch.device(device if device is not None else "cuda:0")
@@ -263,6 +264,11 @@ class TransformerEncoder:
             if rc < 0:
                 self.close()
                 raise ValueError(f"mask_mfma must be 0 or 1 (got {mask_mfma!r})")
+        if bias_mfma:                            # 16-bit handles: attention under a compiled bias runs on the MFMA step (0 or 1, include/flope_amd.h)
+            rc = self.lib.flope_tf_set_option(self.handle, b"bias_mfma", int(bias_mfma))
+            if rc < 0:
+                self.close()
+                raise ValueError(f"bias_mfma must be 0 or 1 (got {bias_mfma!r})")
 
     def _check(self, rc):
         if rc:
@@ -294,7 +300,7 @@ class TransformerEncoder:
             self._check(self.lib.flope_tf_load_weights(self.handle, n, names, ptrs, ndims, shapes))
 
     def set_option(self, name: str, value: int) -> int:
-        if name in ("step_split", "extend_mfma", "mask_mfma"):    # the newer options raise on a refused value (the others keep returning the code)
+        if name in ("step_split", "extend_mfma", "mask_mfma", "bias_mfma"):    # the newer options raise on a refused value (the others keep returning the code)
             rc = self.lib.flope_tf_set_option(self.handle, name.encode(), int(value))
             self._check_arg(rc)
             return rc
@@ -423,7 +429,7 @@ class TransformerEncoder:
             with torch.cuda.device(self.device):
                 self._check_arg(self.lib.flope_tf_forward_masked(self.handle, x.data_ptr(), B, L, lh, mask.handle, y.data_ptr(), _stream_ptr(self.device)))
             self.last_forward_fused = False
-            self.last_attn_kernel = self.lib.flope_tf_last_forward_masked(self.handle)       # tf_attn_masked, tf_attn_tiled_masked under mask_mfma, its BIASED instantiation under a bias
+            self.last_attn_kernel = self.lib.flope_tf_last_forward_masked(self.handle)       # tf_attn_masked, tf_attn_tiled_masked under mask_mfma, the BIASED instantiation of either under a bias (of the second: bias_mfma)
             self._keep = x
             return y
         causal, band = _mask_window(mask, L)
@@ -459,7 +465,9 @@ class TransformerEncoder:
         `mask` (a compiled one, make_mask): softmax over the allowed keys only, by tf_attn_masked (`last_attn_kernel` = 4) for every
         dtype and shape, or, on a 16-bit encoder with `mask_mfma=1` and head_dim 32 / 64 / 96 / 128, by tf_attn_tiled_masked
         (`last_attn_kernel` = 5); with `lengths` each sequence under the mask's corner.  A compiled bias (make_bias) is
-        passed the same way and runs the BIASED instantiation of tf_attn_masked (`last_attn_kernel` = 6) on every dtype and under every option."""
+        passed the same way and runs the BIASED instantiation of tf_attn_masked (`last_attn_kernel` = 6) on every dtype and under every option
+        but `bias_mfma=1`, under which a 16-bit encoder at head_dim 32 / 64 / 96 / 128 runs the BIASED instantiation of tf_attn_tiled_masked
+        (`last_attn_kernel` = 7)."""
         if mask is not None and not isinstance(mask, TransformerEncoderMask):
             raise ValueError("attention() takes a compiled mask (enc.make_mask), not a tensor")
         if mask is not None:
@@ -611,7 +619,8 @@ class TransformerEncoder:
         `bias=table`: a distance table, floating [D], [1, D] or [num_heads, D] with D = window, or capacity without
         one -- a relative bias such as `alibi_distances(D, slopes)`; every entry finite.  The query at position p then scores key j
         as its scaled score + table[h][p - j], and step(), extend() and prefill() return, in bits and in every dtype and under every
-        option, the rows of enc(x, mask=enc.make_bias(distance_bias(table, L, window))).  Without it the encoder has no positional
+        option, the rows of enc(x, mask=enc.make_bias(distance_bias(table, L, window))) with `bias_mfma=0` (the option does not reach a
+        stream: DESIGN.md 44).  Without it the encoder has no positional
         term and a track's last row does not depend on the order of the poses behind it."""
         return TransformerEncoderStream(self, tracks, capacity, window, bias)
 

@@ -420,7 +420,19 @@ int flope_tf_forward(flope_tf_handle h, const float* x_dev, int batch, int seq_l
  *       within a derived bound of fp64.  A key that no query of the sequence allows is still never read into a product (NaN there
  *       reaches no output); a key that holds NaN and is allowed by SOME query of a 128-row query block makes every row of that block
  *       that takes its 32-key step NaN, the rows that mask it included.  Read when a call enqueues, so it may be flipped between
- *       calls; every mask carries its tile map, a forward builds and allocates nothing.  No other call reads or is changed by it. */
+ *       calls; every mask carries its tile map, a forward builds and allocates nothing.  No other call reads or is changed by it;
+ *   "bias_mfma" (default 0; 0 or 1, FLOPE_EINVAL outside; returns the old value; stored and ignored by float32 handles): 1 = attention
+ *       under a compiled BIAS (flope_tf_bias_create; fixed and ragged) runs the BIASED instantiation of tf_attn_tiled_masked
+ *       (FLOPE_TF_ATTN_BIASED16 = 7) where tf_attn_pick_biased says so: a 16-bit dtype, "generic" = 0, head_dim 32 / 64 /
+ *       96 / 128 (every head_dim whose instantiation was built without scratch: all four) and 16-byte aligned buffers -- the walk of
+ *       "mask_mfma" over the tile map of the bias's allowed set with one fma per score, fma(bias, log2e, fl(s scale log2e)).  An option
+ *       of its own: "mask_mfma" has no say over a bias, "bias_mfma" none over a plain mask.  Other handles and shapes keep
+ *       FLOPE_TF_ATTN_BIASED and its bits.  The result is NOT tf_attn_masked's bits: an all-zero bias gives the bits of the compiled
+ *       mask of its allowed set under "mask_mfma" = 1, every other bias is held element-wise within a derived bound of fp64.  A seq_len
+ *       too long for tf_attn_masked's score rows is accepted where the pick is 7.  The bias entry of a masked pair may be LOADED
+ *       (it is -inf) and is never USED; a key that no query of the sequence allows is never read into a product, as under
+ *       "mask_mfma", with the same rule for a NaN key that some query of a 128-row block allows.  Read when a call enqueues; every
+ *       bias carries its tile map on the device behind its planes, a forward builds and allocates nothing. */
 int flope_tf_set_option(flope_tf_handle h, const char* name, int value);
 /* softmax(q k^T / sqrt(head_dim)) v per head on a caller's buffer: qkv_dev [batch, seq_len, 3*model_dim] and out_dev
  * [batch, seq_len, model_dim] in the handle's dtype (float32 for FLOPE_DT_F32).  Launches exactly what flope_tf_forward
@@ -670,12 +682,13 @@ int flope_tf_mask_tiles(flope_tf_mask_handle m, int* query_blocks, long long* bl
 /* An additive attention bias (nn.TransformerEncoder.forward(mask=) with a float mask of scripts/tf_encoder.py), compiled
  * once as a mask is: the [L, L] set of allowed pairs a compiled mask holds plus a float32 value for every allowed pair, in one plane for
  * all heads or one plane per head.  Query i of head h is softmax_j(q . k_j / sqrt(head_dim) + bias[h][i][j]) over exactly its allowed
- * keys; a masked key is never loaded: not its k, not its v, not its bias entry.  The bias is kept as float32 on every handle dtype.
+ * keys; a masked key is never loaded: not its k, not its v, and its bias entry is never used (never loaded either unless option
+ * "bias_mfma" picks the MFMA kernel, which may load its -inf and discards it).  The bias is kept as float32 on every handle dtype.
  *   _bias_create   bias_host: float32 [planes][seq_len][seq_len], planes = 1 or num_heads; -inf = masked, any finite value = allowed
  *             with that value added to the scaled score (the sum is a rounding of its own).  Returns the handle type of _mask_create:
  *             _forward_masked, _attention_masked (fixed and ragged: a sequence of n tokens under the top-left n x n corner of every
  *             plane), _mask_destroy, _mask_info, _forward_flops_masked (the adds are not counted) and _mask_tiles take it as they
- *             take a mask.  One device allocation bits | first | last | bias, uploaded synchronously; a failed allocation is
+ *             take a mask.  One device allocation bits | first | last | bias | start | tiles, uploaded synchronously; a failed allocation is
  *             FLOPE_EHIP and the message names the size (at seq_len 4096 a plane is 64 MiB).  FLOPE_EINVAL before anything is
  *             enqueued, the index (plane, row, col) in flope_tf_last_error: NULL arguments, seq_len < 1 or > max_tokens, planes
  *             neither 1 nor num_heads, an entry that is +inf or NaN, a plane whose masked entries differ from plane 0's (a per-head
@@ -683,6 +696,7 @@ int flope_tf_mask_tiles(flope_tf_mask_handle m, int* query_blocks, long long* bl
  *             Attention under a bias runs the BIASED instantiation of tf_attn_masked (FLOPE_TF_ATTN_BIASED = 6, what _attention_masked returns and
  *             _last_forward_masked reports) on every dtype and under every option, "mask_mfma", "f32mfma" and "generic" included:
  *             tf_attn_masked's order with the one add, so an all-zero bias gives tf_attn_masked's bits for the same allowed set.
+ *             The one exception is option "bias_mfma" = 1 on a 16-bit handle (above): FLOPE_TF_ATTN_BIASED16 = 7.
  *   _mask_bias_planes  the planes of a compiled bias, 0 for a plain mask. */
 int flope_tf_bias_create(flope_tf_handle h, int seq_len, int planes, const float* bias_host, flope_tf_mask_handle* out);
 int flope_tf_mask_bias_planes(flope_tf_mask_handle m);
