@@ -28,12 +28,13 @@ HARNESS_TF_BIAS16 := tests/host_harness/libflope_host_tf_bias16.so
 HARNESS_DEPTH := tests/host_harness/libflope_host_depth.so
 HARNESS_CROP := tests/host_harness/libflope_host_crop.so
 HARNESS_FRAME := tests/host_harness/libflope_host_frame.so
-SRCS     := $(wildcard $(CSRC)/*.hip)
+HARNESS_TRACK := tests/host_harness/libflope_host_track.so
+SRCS    := $(wildcard $(CSRC)/*.hip)
 OBJS     := $(patsubst $(CSRC)/%.hip,$(OBJDIR)/%.o,$(SRCS))
 HDRS     := $(wildcard $(CSRC)/*.h) include/flope_amd.h
 HIPFLAGS := --offload-arch=$(ARCH) -O3 -fPIC -std=c++17 -Wno-unused-value -Iinclude
 
-all: $(LIB) $(HARNESS) $(HARNESS_F32M) $(HARNESS_F32M_KSPLIT) $(HARNESS_GUARD) $(HARNESS_TF_F32M) $(HARNESS_TF_ATTN) $(HARNESS_TF_VARLEN) $(HARNESS_TF_FUSED) $(HARNESS_TF_CAUSAL) $(HARNESS_TF_STREAM) $(HARNESS_TF_WINDOW) $(HARNESS_TF_WINDOW16) $(HARNESS_TF_EXTEND) $(HARNESS_TF_SPLIT) $(HARNESS_TF_EXTEND16) $(HARNESS_TF_MASK) $(HARNESS_TF_MASK16) $(HARNESS_TF_BIAS) $(HARNESS_TF_STREAM_BIAS) $(HARNESS_TF_BIAS16) $(HARNESS_DEPTH) $(HARNESS_CROP) $(HARNESS_FRAME)
+all: $(LIB) $(HARNESS) $(HARNESS_F32M) $(HARNESS_F32M_KSPLIT) $(HARNESS_GUARD) $(HARNESS_TF_F32M) $(HARNESS_TF_ATTN) $(HARNESS_TF_VARLEN) $(HARNESS_TF_FUSED) $(HARNESS_TF_CAUSAL) $(HARNESS_TF_STREAM) $(HARNESS_TF_WINDOW) $(HARNESS_TF_WINDOW16) $(HARNESS_TF_EXTEND) $(HARNESS_TF_SPLIT) $(HARNESS_TF_EXTEND16) $(HARNESS_TF_MASK) $(HARNESS_TF_MASK16) $(HARNESS_TF_BIAS) $(HARNESS_TF_STREAM_BIAS) $(HARNESS_TF_BIAS16) $(HARNESS_DEPTH) $(HARNESS_CROP) $(HARNESS_FRAME) $(HARNESS_TRACK)
 
 $(OBJDIR)/%.o: $(CSRC)/%.hip $(HDRS)
 	@mkdir -p $(OBJDIR)
@@ -163,6 +164,13 @@ $(HARNESS_CROP): tests/host_harness/harness_crop.cpp $(CSRC)/crop_plan.h
 $(HARNESS_FRAME): tests/host_harness/harness_frame.cpp $(CSRC)/frame_plan.h
 	g++ -O2 -fPIC -shared -std=c++17 -I$(CSRC) -o $@ $<
 
+# the device tracker's arithmetic (track_math.h, which track.hip's kernels call) and a scalar walk of a whole update with every
+# index checked, with the broken copies the cases must notice (tests/track_cases.py, tests/test_track_host.py,
+# tests/test_gpu_track.py); the test also builds the file as a stand-alone program under AddressSanitizer + UBSan (-DTRACK_MAIN)
+# and runs it as a child process
+$(HARNESS_TRACK): tests/host_harness/harness_track.cpp $(CSRC)/track_math.h
+	g++ -O2 -fPIC -shared -std=c++17 -I$(CSRC) -o $@ $<
+
 # the same host code under AddressSanitizer + UBSan (sanitizers run on the CPU build only):
 #   make asan-test      (builds the sanitized harness and runs tests/test_host.py against it; leak detection is off because the
 #                        interpreter's own libcrypto allocations are reported as leaks at exit)
@@ -184,7 +192,7 @@ dbg: $(DBGOBJS)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $(DBGDIR)/libflope_amd_dbg.so $(DBGOBJS)
 
 clean:
-	rm -rf build $(LIB) $(HARNESS) $(HARNESS_F32M) $(HARNESS_F32M_KSPLIT) $(HARNESS_GUARD) $(HARNESS_TF_F32M) $(HARNESS_TF_ATTN) $(HARNESS_TF_VARLEN) $(HARNESS_TF_FUSED) $(HARNESS_TF_CAUSAL) $(HARNESS_TF_STREAM) $(HARNESS_TF_WINDOW) $(HARNESS_TF_WINDOW16) $(HARNESS_TF_EXTEND) $(HARNESS_TF_SPLIT) $(HARNESS_TF_EXTEND16) $(HARNESS_TF_MASK) $(HARNESS_TF_MASK16) $(HARNESS_TF_BIAS) $(HARNESS_TF_STREAM_BIAS) $(HARNESS_TF_BIAS16) $(HARNESS_DEPTH) $(HARNESS_CROP) $(HARNESS_FRAME)
+	rm -rf build $(LIB) $(HARNESS) $(HARNESS_F32M) $(HARNESS_F32M_KSPLIT) $(HARNESS_GUARD) $(HARNESS_TF_F32M) $(HARNESS_TF_ATTN) $(HARNESS_TF_VARLEN) $(HARNESS_TF_FUSED) $(HARNESS_TF_CAUSAL) $(HARNESS_TF_STREAM) $(HARNESS_TF_WINDOW) $(HARNESS_TF_WINDOW16) $(HARNESS_TF_EXTEND) $(HARNESS_TF_SPLIT) $(HARNESS_TF_EXTEND16) $(HARNESS_TF_MASK) $(HARNESS_TF_MASK16) $(HARNESS_TF_BIAS) $(HARNESS_TF_STREAM_BIAS) $(HARNESS_TF_BIAS16) $(HARNESS_DEPTH) $(HARNESS_CROP) $(HARNESS_FRAME) $(HARNESS_TRACK)
 
 # stand-alone measurement programs used by tools/collect_profiles.sh and DESIGN.md section 9 (not part of the library)
 TOOLBINS := build/fetch_calib build/launch_floor build/loop_probe build/loop_probe32 build/dma_issue_probe

@@ -10,6 +10,7 @@ LIB_PATH = os.environ.get("FLOPE_AMD_LIB") or os.path.join(_HERE, "lib", "libflo
 
 DT_BF16, DT_F16, DT_F32 = 0, 1, 2
 EINVAL = -1                                                                      # FLOPE_EINVAL of include/flope_amd.h
+ESTATE = -3                                                                      # FLOPE_ESTATE
 IN_F32_NCHW, IN_BF16_NHWC, IN_F16_NHWC, IN_U8_NHWC = 0, 1, 2, 3
 TF_ATTN_GENERIC, TF_ATTN_MFMA64, TF_ATTN_TILED, TF_ATTN_F32M = 0, 1, 2, 3     # flope_tf_attention's return (tf_attn_plan.h)
 TF_ATTN_MASKED16 = 5                                                           # ... under option mask_mfma where tf_attn_pick_masked picks tf_attn_tiled_masked
@@ -88,6 +89,18 @@ SIGNATURES = {
     "flope_guard_select_rows": (_I, [_P, _I, _F, _P, _P, _P]),
     "flope_frame_create_guarded": (_I, [_P, _I, _I, _I, _I, C.POINTER(_P)]),
     "flope_frame_read_gaps": (_I, [_P, _I, _P, _I]),
+    # the multi-frame tracker on the device (csrc/track.hip)
+    "flope_track_create": (_I, [_I, _I, _I, _D, _D, _D, _D, C.POINTER(_P)]),
+    "flope_track_destroy": (_I, [_P]),
+    "flope_track_last_error": (C.c_char_p, [_P]),
+    "flope_track_reset": (_I, [_P]),
+    "flope_track_update": (_I, [_P, _P, _I, _P, _I, _P, _P]),
+    "flope_track_count": (_I, [_P]),
+    "flope_track_read": (_I, [_P, _P, _P, _P, _P, _I]),
+    "flope_track_read_assoc": (_I, [_P, _P, _I]),
+    "flope_track_debug_sentinels": (_I, [_P]),
+    "flope_track_debug_read": (_I, [_P, _P, _P, _P, _P, _P, _I]),
+    "flope_frame_track": (_I, [_P, _I, _P, _P]),
     "flope_stream_create_cu_mask": (_I, [_I, C.POINTER(C.c_uint32), _I, C.POINTER(_P)]),
     "flope_stream_destroy": (_I, [_I, _P]),
     "flope_yolo_create": (_I, [_I, _I, _I, _I, _I, C.POINTER(_P)]),

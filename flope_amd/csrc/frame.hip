@@ -266,6 +266,21 @@ extern "C" int flope_frame_finish(flope_frame_handle f, int slot, double* poses_
   return k;
 }
 
+// the slot's pose rows and reliability flags into a device tracker (track.hip), behind the slot's pose kernels on the stream
+// flope_frame_enqueue ran on: the rows flope_frame_finish would return (it drops rel == 0 and widens float32 exactly; so does the
+// tracker), without the host seeing a pose
+extern "C" int flope_frame_track(flope_frame_handle f, int slot, flope_track_handle t, const double* cam16_host) {
+  if (!f) return ffail(nullptr, FLOPE_EINVAL, "flope_frame_track: NULL handle");
+  if (slot < 0 || slot >= f->nslots || !t || !cam16_host) return ffail(f, FLOPE_EINVAL, "flope_frame_track: bad slot / NULL tracker or camera pose");
+  if (f->guard) return ffail(f, FLOPE_EINVAL, "flope_frame_track: a guarded frame handle repairs its poses in flope_frame_finish; track the rows it returns");
+  Slot& s = f->slots[slot];
+  if (s.state != 2) return ffail(f, FLOPE_ESTATE, "flope_frame_track: nothing enqueued in this slot");
+  if (s.n == 0) return 0;
+  const int rc = flope_track_update(t, s.Rt, 0, s.rel, s.n, cam16_host, s.stream);
+  if (rc < 0) return ffail(f, rc, std::string("flope_frame_track: ") + flope_track_last_error(t));
+  return 0;
+}
+
 extern "C" int flope_frame_to_poses(flope_frame_handle f, const float* det_dev, const int32_t* count_dev, int max_det, const uint8_t* frame_dev,
                                     const uint8_t* mask_dev, const void* depth_dev, int depth_format, float depth_div, const float* K4_host,
                                     float near_plane, float far_plane, double* poses_out, int cap, void* stream) {

@@ -83,6 +83,14 @@ class FramePoses:
                                                             self._depth_format(depth_d), float(depth_div), k4, float(near), float(far),
                                                             _stream_ptr(self.device)))
 
+    def track(self, slot: int, tracker, cam_pose) -> None:
+        """the slot's poses into a DeviceTracker (flope_amd/track.py), on the device behind the slot's pose kernels: legal between an
+        enqueue and the slot's finish, a frame without boxes is a no-op; cam_pose: the reference's 7-vector (or a 4x4 matrix)"""
+        from .track import cam_matrix16
+        cam = cam_matrix16(cam_pose)
+        with torch.cuda.device(self.device):
+            self._check(self.lib.flope_frame_track(self.handle, slot, tracker.handle, cam.ctypes.data))
+
     def finish(self, slot: int):
         """-> float64 [N,4,4] or None (fast_pose_predictor.py:86-87, :101-102)"""
         n = self._check(self.lib.flope_frame_finish(self.handle, slot, self._out.ctypes.data, self.max_boxes))

@@ -167,17 +167,28 @@ class FastPosePredictor:
         return poses_from_detections(self.posenet, rgb, depth, bb, mask, self.K, depth_div=1000.0,
                                      device=self.device)
 
-    def iter_flower_poses(self, frames, detectors: int = 2):
+    def iter_flower_poses(self, frames, detectors: int = 2, tracker=None, cam_poses=None):
         """`get_flower_poses` over a stream of (rgb, depth) frames, software-pipelined.  The detector is a chain of ~75 short,
         narrow launches that leaves most of the GPU idle, so `detectors` (1..4, default 2) instances of it work on consecutive frames
         on their own HIP streams (replaying captured hipGraphs: one host call per frame) while crops -> PoseResNet ->
         Procrustes of an earlier frame run on another stream and the uploads of the next frame on a third; the host only ever
         waits for the oldest detector.  Yields exactly what get_flower_poses returns, frame by frame, in order,
         `detectors + 1` frames late.  The reference loop (scripts/live_pose.py:31-41) is sequential; this is the same
-        computation with several frames in flight."""
+        computation with several frames in flight.
+        tracker (a flope_amd.track.DeviceTracker) with cam_poses (one camera 7-vector per frame, in frame order): every frame's
+        poses also go into the tracker ON THE DEVICE, right behind the frame's pose kernels on the pose stream (FramePoses.track),
+        so the tracker sees the frames in order without the host touching a pose.  What is yielded does not change.
+        (A frame reaches the tracker when its pose stage is enqueued, up to one frame before it is yielded: a consumer that stops
+        early has a tracker that is at most that one frame ahead.)"""
+        if (tracker is None) != (cam_poses is None):
+            raise ValueError("iter_flower_poses: tracker= and cam_poses= go together")
+        cams = iter(cam_poses) if cam_poses is not None else None
         if self.yolo is None:
             for rgb, depth in frames:
-                yield self.get_flower_poses(rgb, depth)
+                poses = self.get_flower_poses(rgb, depth)
+                if tracker is not None:
+                    tracker.update(poses, next(cams))
+                yield poses
             return
         dev = torch.device(self.device)
         nd = max(1, min(int(detectors), 4))
@@ -193,7 +204,7 @@ class FastPosePredictor:
         H, W = self.yolo.frame_h, self.yolo.frame_w
         NS = 2 * (nd + 1)                               # frames in flight: nd detecting, one in the pose stage, one being uploaded
         slots = [dict(frame=torch.empty((H, W, 3), dtype=torch.uint8, device=dev), out=self.yolo.new_outputs(), depth=None,
-                      ready=None, pose_done=None, shape=None) for _ in range(NS)]
+                      ready=None, pose_done=None, shape=None, cam=None) for _ in range(NS)]
         # the slot buffers were filled on the caller's stream: every side stream starts behind that fill
         cur = torch.cuda.current_stream(dev)
         for s_ in [s_io, s_pose] + s_det:
@@ -214,6 +225,7 @@ class FastPosePredictor:
                 up = torch.cuda.Event()
                 up.record(s_io)
             sl["shape"] = rgb.shape
+            sl["cam"] = next(cams) if cams is not None else None
             st = s_det[t % nd]
             with torch.cuda.stream(st):
                 st.wait_event(up)
@@ -229,6 +241,8 @@ class FastPosePredictor:
             with torch.cuda.stream(s_pose):
                 s_pose.wait_event(sl["ready"])
                 fctx.enqueue(t % NS, sl["frame"], sl["out"][2], sl["depth"], self.K, 1000.0)   # waits (host) for frame t's box count only
+                if tracker is not None:
+                    fctx.track(t % NS, tracker, sl["cam"])      # the frame's poses into the tracker, on the device, in frame order
                 sl["pose_done"] = torch.cuda.Event()
                 sl["pose_done"].record(s_pose)
             return t % NS

@@ -82,18 +82,47 @@ def poses_to_measurements(flower_pose_world):
 
 
 class FlowerModel:
-    def __init__(self, dist_th=50, intrin_path=None, get_plots=False, pose_predictor=None):
+    def __init__(self, dist_th=50, intrin_path=None, get_plots=False, pose_predictor=None, tracker="host"):
+        """tracker: "host" (default) = the reference's numpy tracker below; "device" = the same association and filters with the
+        state in GPU memory (flope_amd.track.DeviceTracker): `state`, `scores`, `get_state()` and `filtered_state()`
+        read from it, `add_stream` feeds it behind the frame's pose kernels without the host touching a pose, and `kfs` (the 7 x 7
+        filter objects) is not offered."""
         if get_plots:
             raise NotImplementedError("the live matplotlib plots of the reference are display code and are not reproduced")
+        if tracker not in ("host", "device"):
+            raise ValueError(f"FlowerModel: tracker must be 'host' or 'device', got {tracker!r}")
         self.get_plots = False
-        self.state = None
-        self.scores = None
-        self.kfs = []
+        self.tracker = tracker
+        self._device_tracker = None
+        if tracker == "host":
+            self.state = None
+            self.scores = None
+            self.kfs = []
+        else:
+            from flope_amd.track import DeviceTracker
+            self._device_tracker = DeviceTracker(getattr(pose_predictor, "device", "cuda"), dist_th=dist_th)
         self.th = dist_th / 1000
         self.intrin_path = intrin_path
         self.pose_predictor = pose_predictor          # anything with get_flower_poses(rgb, depth)
 
+    def __getattr__(self, name):
+        # only reached where normal lookup fails: tracker="device" keeps no state, scores or kfs attribute of its own
+        dt = self.__dict__.get("_device_tracker")
+        if dt is not None and name in ("state", "scores"):
+            return getattr(dt, name)
+        if dt is not None and name == "kfs":
+            raise AttributeError("FlowerModel(tracker='device') keeps one variance per track on the device, not 7 x 7 filter objects: "
+                                 "use filtered_state() and device_tracker.p, or tracker='host'")
+        raise AttributeError(f"{type(self).__name__!r} object has no attribute {name!r}")
+
+    @property
+    def device_tracker(self):
+        """the DeviceTracker behind tracker="device" (None with tracker="host")"""
+        return self._device_tracker
+
     def assign_meas_to_state(self, meas):
+        if self._device_tracker is not None:
+            raise RuntimeError("FlowerModel(tracker='device') takes poses, not measurements: use add_poses / add_data / add_stream")
         meas = np.asarray(meas, dtype=np.float64)
         if self.state is None:
             self.state = meas
@@ -121,7 +150,9 @@ class FlowerModel:
         if flower_pose_cam is None:
             return None, None
         flower_pose = pose_cam_to_world(flower_pose_cam, cam_pose_to_matrix(cam_pose))
-        if ignore:
+        if ignore and self._device_tracker is not None:
+            self._device_tracker.update(flower_pose_cam, cam_pose)
+        elif ignore:
             self.assign_meas_to_state(poses_to_measurements(flower_pose))
         return flower_pose_cam, flower_pose.astype(np.float32)
 
@@ -140,6 +171,13 @@ class FlowerModel:
             raise RuntimeError("FlowerModel: pass pose_predictor= (PosePredictor / FastPosePredictor)")
         frames = list(frames)
         it = getattr(self.pose_predictor, "iter_flower_poses", None)
+        if it is not None and ignore and self._device_tracker is not None:
+            # the predictor's loop feeds the tracker on the device, behind each frame's pose kernels and in frame order; the host
+            # only moves the poses it hands back to the world frame
+            poses = it(((f[0], f[1]) for f in frames), detectors=detectors, tracker=self._device_tracker, cam_poses=[f[2] for f in frames])
+            for f, pose_cam in zip(frames, poses):
+                yield self.add_poses(pose_cam, f[2], False)
+            return
         poses = it(((f[0], f[1]) for f in frames), detectors=detectors) if it is not None else \
             (self.pose_predictor.get_flower_poses(f[0], f[1]) for f in frames)
         for f, pose_cam in zip(frames, poses):
@@ -150,4 +188,6 @@ class FlowerModel:
 
     def filtered_state(self):
         """(T,7) current filter means, one row per track (the reference keeps these only inside ``kfs``)."""
+        if self._device_tracker is not None:
+            return self._device_tracker.filtered_state()
         return np.array([kf.x for kf in self.kfs]).reshape(-1, 7)

@@ -315,6 +315,48 @@ int flope_frame_create_guarded(flope_guard_handle g, int frame_h, int frame_w, i
 /* test hook (guarded frame handles): gap of every crop of the slot's last finished frame, float32 [n]; returns n */
 int flope_frame_read_gaps(flope_frame_handle f, int slot, float* gap_host, int cap);
 
+/* ---- Multi-frame tracker on the device (reference sunflower/predictor/flower_model.py:146-213) ----
+ * FlowerModel.assign_meas_to_state with its state in device memory: world pose = camera pose x flower pose, measurement =
+ * [translation | scalar-last quaternion], nearest ANCHOR (a track's first measurement, never overwritten) under the gate
+ * dist_th_m (d < dist_th_m matches), one identity-model Kalman filter per track as the scalar recursion
+ *     p += q;  k = p / (p + r);  x += k (z - x);  p = (1 - k)^2 p + k^2 r;  quaternion part divided by its norm
+ * (all float64, csrc/track_math.h).  Within a frame every distance goes to the anchors as they stood at the start of the frame,
+ * a track opened in a frame is invisible to the rest of it, two measurements may update one track (in measurement order), and
+ * new tracks get their indices in measurement order.
+ *   _create   max_tracks >= 1, max_meas >= 1, dist_th_m, q, r and p0 finite and positive; otherwise FLOPE_EINVAL.
+ *   _update   asynchronous on `stream`, ordered behind the handle's previous update whatever stream that used (an event of the
+ *             handle).  Rt_dev [n,16] row-major 4x4 poses in the camera frame, float32 (rt_f64 = 0, widened exactly) or float64
+ *             (rt_f64 = 1); rel_dev int32 [n] or NULL = all reliable; rows with rel == 0 are skipped; cam16_host: row-major 4x4
+ *             camera pose, read before the call returns.  n = 0 is a no-op, n > max_meas is FLOPE_EINVAL and enqueues nothing.
+ *             Two launches, no allocation, no host wait.  An update that would open more than max_tracks tracks applies
+ *             nothing of its frame and sets a flag that stays until _reset: later updates apply nothing either, and _count,
+ *             _read and _read_assoc return FLOPE_ESTATE.
+ *   _count    waits for the last update; the number of tracks.
+ *   _read     waits; anchors / means float64 [tracks,7], p float64 [tracks], hits int32 [tracks] (any may be NULL); returns the
+ *             number of tracks, FLOPE_EINVAL when it exceeds cap.
+ *   _read_assoc  test hook: the last update's association, int32 [n]: >= 0 the matched track, -1 - t = opened track t,
+ *             INT32_MIN = skipped as unreliable; returns n, FLOPE_ESTATE before the first update.
+ *   _reset    waits, then empties the state and clears the flag.
+ *   _debug_sentinels  test hook: waits; how many of the sentinel words behind the state arrays have changed (0 is right). */
+typedef struct flope_track* flope_track_handle;
+int flope_track_create(int device_id, int max_tracks, int max_meas, double dist_th_m, double q, double r, double p0, flope_track_handle* out);
+int flope_track_destroy(flope_track_handle t);
+const char* flope_track_last_error(flope_track_handle t);
+int flope_track_reset(flope_track_handle t);
+int flope_track_update(flope_track_handle t, const void* Rt_dev, int rt_f64, const int32_t* rel_dev, int n, const double* cam16_host, void* stream);
+int flope_track_count(flope_track_handle t);
+int flope_track_read(flope_track_handle t, double* anchors, double* means, double* p, int32_t* hits, int cap);
+int flope_track_read_assoc(flope_track_handle t, int32_t* assoc_host, int cap);
+int flope_track_debug_sentinels(flope_track_handle t);
+/* test hook: waits; the first `rows` rows of every state array as they are in device memory and count2 = {tracks, overflow flag},
+ * whatever the flag says (what an update that overflowed has left behind); returns rows */
+int flope_track_debug_read(flope_track_handle t, double* anchors, double* means, double* p, int32_t* hits, int32_t* count2, int rows);
+/* The slot's device-resident poses and depth-reliability flags (the rows flope_frame_finish would return) into the tracker,
+ * behind the slot's pose kernels on the slot's stream, without a host wait.  Legal between a flope_frame_enqueue that returned
+ * n > 0 and that slot's flope_frame_finish; a slot whose enqueue returned 0 is a no-op returning 0; an idle slot is FLOPE_ESTATE; a
+ * guarded frame handle is FLOPE_EINVAL (the guard's repairs land in flope_frame_finish). */
+int flope_frame_track(flope_frame_handle f, int slot, flope_track_handle t, const double* cam16_host);
+
 /* ---- TransformerEncoder (reference scripts/tf_encoder.py:5-27) -------------
  * Replaces `TransformerEncoder(input_dim, model_dim, out_dim, num_heads, num_layers, ff_dim,
  * dropout)` + `.load_state_dict()` + `forward(x)` in eval mode (dropout = identity):
