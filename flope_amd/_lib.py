@@ -22,6 +22,8 @@ TF_FWD_LAUNCHES, TF_FWD_FUSED = 0, 1                                           #
 TF_EXTEND_ROW, TF_EXTEND_SPLIT, TF_EXTEND_MFMA = 0, 1, 2                         # flope_tf_stream_extend_plan's / _attention_extend's return
 TF_STEP_ROW, TF_STEP_SPLIT = 0, 1                                              # flope_tf_stream_step_plan's / _attention's return
 TF_STEP_BIASED, TF_EXTEND_BIASED = 2, 3                                        # ... on a state with a distance table (flope_tf_stream_open_bias)
+TF_FEED_SKIPPED, TF_FEED_OVERFLOW, TF_FEED_RANGE, TF_FEED_DUPLICATE, TF_FEED_FULL = -1, -2, -3, -4, -5   # FLOPE_TF_FEED_*: flope_tf_stream_read_feed's codes
+TF_FEED_MEAS, TF_FEED_MEAN = 0, 1                                              # flope_tf_stream_step_tracker's source
 TF_LN_SCALAR, TF_LN_VEC = 0, 1                                                 # flope_tf_layernorm's return
 STAGE_STEM, STAGE_POOL, STAGE_FEAT, STAGE_HIDDEN = 0, 1, 10, 11
 HEAD_FC1 = ("packed", "row-major", "simple")                                   # flope_head_plan's *fc1 (plan.h: HeadFc1)
@@ -42,6 +44,14 @@ def STAGE_DS(li: int) -> int:
 
 # every symbol include/flope_amd.h declares: name -> (restype, argtypes)
 _P, _I, _F, _D = C.c_void_p, C.c_int, C.c_float, C.c_double
+
+
+class TrackView(C.Structure):
+    """flope_track_view of include/flope_amd.h (flope_track_device_view)"""
+    _fields_ = [("assoc", _P), ("meas", _P), ("means", _P), ("count", _P), ("event", _P), ("device", _I), ("max_tracks", _I), ("max_meas", _I),
+                ("n", _I), ("serial", C.c_ulonglong)]
+
+
 SIGNATURES = {
     "flope_create": (_I, [_I, _I, _I, _I, _I, _I, C.POINTER(_P)]),
     "flope_destroy": (_I, [_P]),
@@ -100,6 +110,7 @@ SIGNATURES = {
     "flope_track_read_assoc": (_I, [_P, _P, _I]),
     "flope_track_debug_sentinels": (_I, [_P]),
     "flope_track_debug_read": (_I, [_P, _P, _P, _P, _P, _P, _I]),
+    "flope_track_device_view": (_I, [_P, _P]),
     "flope_frame_track": (_I, [_P, _I, _P, _P]),
     "flope_stream_create_cu_mask": (_I, [_I, C.POINTER(C.c_uint32), _I, C.POINTER(_P)]),
     "flope_stream_destroy": (_I, [_I, _P]),
@@ -150,6 +161,14 @@ SIGNATURES = {
     "flope_tf_stream_attention": (_I, [_P, _P, _I, _I, C.POINTER(_I), _P, _P]),
     "flope_tf_stream_extend_plan": (_I, [_P]),
     "flope_tf_stream_attention_extend": (_I, [_P, _P, _I, _I, C.POINTER(_I), C.POINTER(_I), _P, _P]),
+    # a device-positioned state, stepped by the device tracker's association
+    "flope_tf_stream_open_device": (_I, [_P, _I, _I, _I, _I, _I, _I, C.POINTER(C.c_float), C.POINTER(_P)]),
+    "flope_tf_stream_step_assoc": (_I, [_P, _P, _P, _P, _I, _P, _P]),
+    "flope_tf_stream_step_tracker": (_I, [_P, _P, _I, _P, _P]),
+    "flope_tf_stream_reset_device": (_I, [_P, _P]),
+    "flope_tf_stream_read_positions": (_I, [_P, _P, _I]),
+    "flope_tf_stream_read_feed": (_I, [_P, _P, _P, _I]),
+    "flope_tf_stream_read_tokens": (_I, [_P, _P, _I]),
     # scripts/tf_encoder.py: nn.TransformerEncoder.forward(mask=) for any [L, L] mask, compiled once
     "flope_tf_mask_create": (_I, [_P, _I, C.POINTER(C.c_uint32), C.POINTER(_P)]),
     "flope_tf_mask_destroy": (_I, [_P]),

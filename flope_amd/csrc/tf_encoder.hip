@@ -46,6 +46,10 @@
 // Option bias_mfma = 1 (16-bit handles): a launch under a compiled bias runs tf_attn_tiled_masked's BIASED instantiation where
 // tf_attn_pick_biased says so -- the walk of mask_mfma over the tile map of the bias's allowed set, which every bias carries behind its
 // planes, with tf_attn16_step's BIASED form: one fma per score; a zero bias gives the bits of the compiled mask under mask_mfma = 1.
+// flope_tf_stream_open_device / _step_assoc / _step_tracker (any dtype): a windowed state whose positions live on the device,
+// stepped by an association only the device knows (the device tracker's): tf_stream_feed_kernel turns it into the step's table and the
+// token rows by the rule of tf_stream_feed.h, the step's launch sequence runs for every row at smax = window, tf_feed_fill_bias writes
+// out_layer's bias into the rows that fed nothing.
 #include "../../include/flope_amd.h"
 #include "common.h"
 #include "host_pack.h"
@@ -53,6 +57,7 @@
 #include "tf_attn_mask.h"
 #include "tf_encoder_stream.h"
 #include "tf_fused_plan.h"
+#include "tf_stream_feed.h"
 
 #include <math.h>
 #include <string.h>
@@ -791,6 +796,45 @@ __global__ void tf_cache_append(const V* __restrict__ qkv, V* __restrict__ cache
     row = flope_tf_plan::tf_stream_append_slot(pos0, i, capacity);
   }
   cache[((size_t)t * capacity + row) * 2 * dv + c] = qkv[(size_t)(o + i) * 3 * dv + dv + c];
+}
+
+// ---- a device-positioned state: the step's table and tokens from an association (flope_tf_stream_step_assoc / _step_tracker)
+
+// One thread per row m < n of a frame: the feed rule of tf_stream_feed.h (tf_feed_row: the table entry tab[2 m], tab[2 m + 1] and, for a
+// row that feeds, its track's position) and the float32 token row tok[m][0 .. input_dim - 1].  No two feeding rows name one track and
+// a row reads pos[] only for the track it feeds, so the threads need no order among themselves: no LDS, no atomics, no barrier.
+// assoc: int32 [n] in the tracker's encoding; overflow: one int32 or nullptr (clear).  The token of a feeding row:
+//   SOURCE FLOPE_TF_FEED_MEAS   vec7 [n][7] float64, row m           (the frame's measurements)
+//   SOURCE FLOPE_TF_FEED_MEAN   vec7 [vec_rows][7] float64, row track (the filtered means; track < vec_rows is tested, a tracker's
+//                               association never names a track it has not opened)
+//   SOURCE kTfFeedRows          x [n][input_dim] float32, row m       (flope_tf_stream_step_assoc: the caller's rows)
+// the first two rounded once to float32 with zeros behind column 6 (tf_feed_token).  A row that feeds nothing is all zero.  Every
+// address is bounded by n, tracks or vec_rows whatever the association holds: the track of a feeding row is below `tracks` by rule.
+constexpr int kTfFeedRows = 2;
+constexpr int kTfFeedBlock = 64;
+template <int SOURCE>
+__global__ __launch_bounds__(kTfFeedBlock) void tf_stream_feed_kernel(const int* __restrict__ assoc, const int* __restrict__ overflow, int n, int tracks,
+                                                                      int* pos, int* __restrict__ tab, const double* __restrict__ vec7, int vec_rows,
+                                                                      const float* __restrict__ x, int input_dim, float* __restrict__ tok) {
+  const int m = blockIdx.x * kTfFeedBlock + threadIdx.x;
+  if (m >= n) return;
+  const int t = flope_tf_plan::tf_feed_row(assoc, m, overflow ? overflow[0] : 0, tracks, pos, tab);
+  float* row = tok + (size_t)m * input_dim;
+  if constexpr (SOURCE == kTfFeedRows) {
+    for (int c = 0; c < input_dim; ++c) row[c] = t >= 0 ? x[(size_t)m * input_dim + c] : 0.f;
+  } else {
+    const int src = SOURCE == FLOPE_TF_FEED_MEAN ? t : m;
+    flope_tf_plan::tf_feed_token(t >= 0 && src < vec_rows ? vec7 + (size_t)src * flope_tf_plan::kTfFeedDim : nullptr, input_dim, row);
+  }
+}
+
+// The last launch of such a step: out_layer's bias into the rows of y [n][out_dim] whose table entry is a code -- what the library
+// returns behind a ragged length (tf_scatter_rows).  The rows that fed are left as the forward wrote them.
+__global__ void tf_feed_fill_bias(const int* __restrict__ tab, const float* __restrict__ bias, float* __restrict__ y, int out_dim, size_t total) {
+  const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= total) return;
+  const size_t r = idx / out_dim;
+  if (tab[2 * r] < 0) y[idx] = bias[idx - r * out_dim];
 }
 
 // ---- step_split: a token's visible keys over the four waves of a workgroup (option "step_split") -----------------------
@@ -2154,6 +2198,15 @@ struct flope_tf_stream_s {
   std::vector<char> seen;                    // scratch of the argument checks
   float* rel = nullptr;                      // a biased state's distance table (flope_tf_stream_open_bias): float32 [planes][rel_d], nullptr otherwise
   int planes = 0, rel_d = 0;                 // 0 planes: no table; else 1 or num_heads, and rel_d = window ? window : capacity
+  // a device-positioned state (flope_tf_stream_open_device): max_rows > 0, window > 0, `pos` stays empty and tab holds
+  // 2 max_rows ints, the table tf_stream_feed_kernel writes
+  int max_rows = 0;                          // 0: positions on the host, everything above
+  int* pos_dev = nullptr;                    // [tracks]: tokens held per track
+  float* tok = nullptr;                      // [max_rows][input_dim]: the token rows of the last call
+  hipEvent_t ev = nullptr;                   // recorded behind every call that enqueues; the readers wait for it
+  int feed_n = 0;                            // rows of the last _step_assoc / _step_tracker
+  const void* fed_tracker = nullptr;         // the tracker and the serial number of the update fed last (_step_tracker)
+  unsigned long long fed_serial = 0;
 };
 
 // A compiled attention mask (flope_tf_mask_*; tf_attn_mask.h): one device allocation bits | first | last | start |
@@ -2622,8 +2675,9 @@ extern "C" int flope_tf_destroy(flope_tf_handle e) {
   if (!e) return FLOPE_OK;
   hipSetDevice(e->device);
   for (flope_tf_stream_s* s : e->streams) {      // their device memory goes with the handle; the states stay until closed and refuse every call
-    hipFree(s->cache); hipFree(s->tab); hipFree(s->rel);
-    s->cache = nullptr; s->tab = nullptr; s->rel = nullptr; s->e = nullptr;
+    hipFree(s->cache); hipFree(s->tab); hipFree(s->rel); hipFree(s->pos_dev); hipFree(s->tok);
+    if (s->ev) { hipEventSynchronize(s->ev); hipEventDestroy(s->ev); }
+    s->cache = nullptr; s->tab = nullptr; s->rel = nullptr; s->pos_dev = nullptr; s->tok = nullptr; s->ev = nullptr; s->e = nullptr;
   }
   for (flope_tf_mask* m : e->masks) {            // the same for the compiled masks
     hipFree(m->dev);
@@ -3211,6 +3265,20 @@ int tf_stream_enter(flope_tf_stream_s* s, const std::string& who, flope_tf_encod
   *e = s->e;
   return 0;
 }
+// ... of a call that reads or moves positions on the host: a device-positioned state has none there.  instead: the call to use
+int tf_stream_enter_host(flope_tf_stream_s* s, const std::string& who, flope_tf_encoder** e, const char* instead) {
+  const int rc = tf_stream_enter(s, who, e);
+  if (rc) return rc;
+  if (s->max_rows) return tf_fail(*e, FLOPE_ESTATE, who + ": this state keeps its positions on the device (flope_tf_stream_open_device); " + instead);
+  return 0;
+}
+// ... and of a call that needs them there
+int tf_stream_enter_device(flope_tf_stream_s* s, const std::string& who, flope_tf_encoder** e) {
+  const int rc = tf_stream_enter(s, who, e);
+  if (rc) return rc;
+  if (!s->max_rows) return tf_fail(*e, FLOPE_ESTATE, who + ": this state keeps its positions on the host; open one with flope_tf_stream_open_device");
+  return 0;
+}
 
 // the refusals of tf_encoder_stream.h in words; bad: the index they name
 int tf_stream_refuse(flope_tf_stream_s* s, const std::string& who, int rc, int bad, int n, const int* rows, const int* lengths, int seq_len) {
@@ -3413,7 +3481,7 @@ namespace {
 // planes >= 1: flope_tf_stream_open_bias -- the state's distance table rel [planes][rel_d], already checked, is uploaded here, once and
 // synchronously, into an allocation of the state's own
 int tf_stream_open(flope_tf_handle e, const std::string& who, int tracks, int capacity, int window, flope_tf_stream* out, int planes = 0, int rel_d = 0,
-                   const float* rel_host = nullptr) {
+                   const float* rel_host = nullptr, int max_rows = 0) {
   if (!out) return tf_fail(e, FLOPE_EINVAL, who + ": NULL out");
   *out = nullptr;
   if (!e) return tf_fail(nullptr, FLOPE_EINVAL, who + ": NULL handle");
@@ -3427,12 +3495,27 @@ int tf_stream_open(flope_tf_handle e, const std::string& who, int tracks, int ca
   const size_t bytes = (size_t)e->nl * tracks * capacity * 2 * e->d * e->esz;
   flope_tf_stream_s* s = new flope_tf_stream_s();
   s->e = e; s->tracks = tracks; s->capacity = capacity; s->window = window;
-  // num_layers = 0 has no cache; the allocation keeps one row so that the pointer is a pointer
-  if (hipMalloc(&s->cache, bytes ? bytes : 16) != hipSuccess || hipMalloc((void**)&s->tab, (size_t)5 * tracks * sizeof(int)) != hipSuccess) {
+  // num_layers = 0 has no cache; the allocation keeps one row so that the pointer is a pointer.  The table: 5 ints per track, or the 2
+  // per row of a device-positioned state
+  const size_t tab_ints = max_rows ? (size_t)2 * max_rows : (size_t)5 * tracks;
+  if (hipMalloc(&s->cache, bytes ? bytes : 16) != hipSuccess || hipMalloc((void**)&s->tab, tab_ints * sizeof(int)) != hipSuccess) {
     (void)hipGetLastError();
     hipFree(s->cache); hipFree(s->tab);
     delete s;
     return tf_fail(e, FLOPE_EHIP, who + ": hipMalloc failed for a cache of " + std::to_string(bytes) + " bytes (num_layers x tracks x capacity x 2 model_dim)");
+  }
+  if (max_rows) {                                  // positions, zeroed; the token rows; the table starts as "no row" (feed_n = 0)
+    const size_t tb = (size_t)max_rows * e->in_dim * sizeof(float);
+    if (hipMalloc((void**)&s->pos_dev, (size_t)tracks * sizeof(int)) != hipSuccess || hipMalloc((void**)&s->tok, tb) != hipSuccess ||
+        hipMemset(s->pos_dev, 0, (size_t)tracks * sizeof(int)) != hipSuccess || hipMemset(s->tok, 0, tb) != hipSuccess ||
+        hipMemset(s->tab, 0, tab_ints * sizeof(int)) != hipSuccess || hipEventCreateWithFlags(&s->ev, hipEventDisableTiming) != hipSuccess) {
+      (void)hipGetLastError();
+      hipFree(s->cache); hipFree(s->tab); hipFree(s->pos_dev); hipFree(s->tok);
+      if (s->ev) hipEventDestroy(s->ev);
+      delete s;
+      return tf_fail(e, FLOPE_EHIP, who + ": allocating " + std::to_string(tracks) + " positions and " + std::to_string(tb) + " bytes of token rows failed");
+    }
+    s->max_rows = max_rows;
   }
   if (planes) {
     const size_t rb = flope_tf_plan::tf_stream_bias_bytes(planes, rel_d);
@@ -3441,16 +3524,19 @@ int tf_stream_open(flope_tf_handle e, const std::string& who, int tracks, int ca
     if (!alloc_failed) err = hipMemcpy(s->rel, rel_host, rb, hipMemcpyHostToDevice);
     if (err != hipSuccess) {
       (void)hipGetLastError();
-      hipFree(s->cache); hipFree(s->tab); hipFree(s->rel);
+      hipFree(s->cache); hipFree(s->tab); hipFree(s->rel); hipFree(s->pos_dev); hipFree(s->tok);
+      if (s->ev) hipEventDestroy(s->ev);
       delete s;
       return tf_fail(e, FLOPE_EHIP, who + (alloc_failed ? ": hipMalloc failed for" : ": the upload failed of") + " a distance table of " + std::to_string(rb) +
                                         " bytes (planes x distances x 4): " + hipGetErrorString(err));
     }
     s->planes = planes; s->rel_d = rel_d;
   }
-  s->pos.assign((size_t)tracks, 0);
-  s->tab_host.assign((size_t)5 * tracks, 0);
-  s->seen.assign((size_t)tracks, 0);
+  if (!max_rows) {
+    s->pos.assign((size_t)tracks, 0);
+    s->tab_host.assign((size_t)5 * tracks, 0);
+    s->seen.assign((size_t)tracks, 0);
+  }
   e->streams.push_back(s);
   *out = s;
   return FLOPE_OK;
@@ -3469,14 +3555,11 @@ extern "C" int flope_tf_stream_open_window(flope_tf_handle e, int tracks, int ca
   return tf_stream_open(e, "flope_tf_stream_open_window", tracks, capacity, window, out);
 }
 
-extern "C" int flope_tf_stream_open_bias(flope_tf_handle e, int tracks, int capacity, int window, int planes, int distances, const float* table_host,
-                                         flope_tf_stream* out) {
+namespace {
+// a state with a distance table, host- or device-positioned (max_rows > 0): the table's refusals, then the open
+int tf_stream_open_biased(flope_tf_handle e, const std::string& who, int tracks, int capacity, int window, int planes, int distances, const float* table_host,
+                          flope_tf_stream* out, int max_rows) {
   using namespace flope_tf_plan;
-  const std::string who = "flope_tf_stream_open_bias";
-  if (!out) return tf_fail(e, FLOPE_EINVAL, who + ": NULL out");
-  *out = nullptr;
-  if (!e) return tf_fail(nullptr, FLOPE_EINVAL, who + ": NULL handle");
-  if (window < 0) return tf_fail(e, FLOPE_EINVAL, who + ": window = " + std::to_string(window) + " is negative (0: the linear state; 1 .. capacity: the ring)");
   // the state's own refusals first: a table is judged against a capacity and a window that are ones
   if (tf_stream_check_open(tracks, capacity) == kTfStreamOk && (!window || tf_stream_check_open_window(tracks, capacity, window) == kTfStreamOk)) {
     int bp = -1, bd = -1;
@@ -3494,7 +3577,32 @@ extern "C" int flope_tf_stream_open_bias(flope_tf_handle e, int tracks, int capa
       default: break;
     }
   }
-  return tf_stream_open(e, who, tracks, capacity, window, out, planes, distances, table_host);
+  return tf_stream_open(e, who, tracks, capacity, window, out, planes, distances, table_host, max_rows);
+}
+}  // namespace
+
+extern "C" int flope_tf_stream_open_bias(flope_tf_handle e, int tracks, int capacity, int window, int planes, int distances, const float* table_host,
+                                         flope_tf_stream* out) {
+  const std::string who = "flope_tf_stream_open_bias";
+  if (!out) return tf_fail(e, FLOPE_EINVAL, who + ": NULL out");
+  *out = nullptr;
+  if (!e) return tf_fail(nullptr, FLOPE_EINVAL, who + ": NULL handle");
+  if (window < 0) return tf_fail(e, FLOPE_EINVAL, who + ": window = " + std::to_string(window) + " is negative (0: the linear state; 1 .. capacity: the ring)");
+  return tf_stream_open_biased(e, who, tracks, capacity, window, planes, distances, table_host, out, 0);
+}
+
+extern "C" int flope_tf_stream_open_device(flope_tf_handle e, int tracks, int capacity, int window, int max_rows, int planes, int distances,
+                                           const float* table_host, flope_tf_stream* out) {
+  const std::string who = "flope_tf_stream_open_device";
+  if (!out) return tf_fail(e, FLOPE_EINVAL, who + ": NULL out");
+  *out = nullptr;
+  if (!e) return tf_fail(nullptr, FLOPE_EINVAL, who + ": NULL handle");
+  if (window < 1)
+    return tf_fail(e, FLOPE_EINVAL, who + ": window = " + std::to_string(window) + " is outside 1 .. capacity (a device-positioned state is windowed: its launches are sized by the window, not by a position)");
+  if (max_rows < 1 || max_rows > e->max_tokens)
+    return tf_fail(e, FLOPE_EINVAL, who + ": max_rows = " + std::to_string(max_rows) + " is outside 1 .. max_tokens = " + std::to_string(e->max_tokens));
+  if (planes == 0 && !table_host) return tf_stream_open(e, who, tracks, capacity, window, out, 0, 0, nullptr, max_rows);
+  return tf_stream_open_biased(e, who, tracks, capacity, window, planes, distances, table_host, out, max_rows);
 }
 
 extern "C" int flope_tf_stream_bias_planes(flope_tf_stream s) {
@@ -3508,7 +3616,8 @@ extern "C" int flope_tf_stream_close(flope_tf_stream s) {
   if (!s) return FLOPE_OK;
   if (flope_tf_encoder* e = s->e) {
     hipSetDevice(e->device);
-    hipFree(s->cache); hipFree(s->tab); hipFree(s->rel);
+    if (s->ev) { hipEventSynchronize(s->ev); hipEventDestroy(s->ev); }
+    hipFree(s->cache); hipFree(s->tab); hipFree(s->rel); hipFree(s->pos_dev); hipFree(s->tok);
     for (auto it = e->streams.begin(); it != e->streams.end(); ++it)
       if (*it == s) { e->streams.erase(it); break; }
   }
@@ -3519,7 +3628,7 @@ extern "C" int flope_tf_stream_close(flope_tf_stream s) {
 extern "C" int flope_tf_stream_reset(flope_tf_stream s, int n, const int* tracks_host) {
   flope_tf_encoder* e;
   int rc, bad = -1;
-  if ((rc = tf_stream_enter(s, "flope_tf_stream_reset", &e))) return rc;
+  if ((rc = tf_stream_enter_host(s, "flope_tf_stream_reset", &e, "use flope_tf_stream_reset_device"))) return rc;
   if ((rc = flope_tf_plan::tf_stream_check_reset(s->tracks, n, tracks_host, &bad)))
     return tf_stream_refuse(s, "flope_tf_stream_reset", rc, bad, n, tracks_host, nullptr, 0);
   if (!tracks_host) s->pos.assign((size_t)s->tracks, 0);
@@ -3530,7 +3639,7 @@ extern "C" int flope_tf_stream_reset(flope_tf_stream s, int n, const int* tracks
 extern "C" int flope_tf_stream_position(flope_tf_stream s, int track) {
   flope_tf_encoder* e;
   int rc;
-  if ((rc = tf_stream_enter(s, "flope_tf_stream_position", &e))) return rc;
+  if ((rc = tf_stream_enter_host(s, "flope_tf_stream_position", &e, "use flope_tf_stream_read_positions"))) return rc;
   if (track < 0 || track >= s->tracks)
     return tf_fail(e, FLOPE_EINVAL, "flope_tf_stream_position: track " + std::to_string(track) + " is outside 0 .. " + std::to_string(s->tracks - 1));
   return s->pos[(size_t)track];
@@ -3540,7 +3649,7 @@ extern "C" int flope_tf_stream_step(flope_tf_stream s, const float* x_dev, int n
   const std::string who = "flope_tf_stream_step";
   flope_tf_encoder* e;
   int rc, bad = -1, max_pos = 0;
-  if ((rc = tf_stream_enter(s, who, &e))) return rc;
+  if ((rc = tf_stream_enter_host(s, who, &e, "use flope_tf_stream_step_assoc or flope_tf_stream_step_tracker"))) return rc;
   if (!e->loaded) return tf_fail(e, FLOPE_ESTATE, who + ": weights not loaded");
   rc = s->window ? flope_tf_plan::tf_stream_check_step_window(s->pos.data(), s->tracks, s->window, e->max_tokens, n, tracks_host, s->seen.data(), &bad, &max_pos)
                  : flope_tf_plan::tf_stream_check_step(s->pos.data(), s->tracks, s->capacity, e->max_tokens, n, tracks_host, s->seen.data(), &bad, &max_pos);
@@ -3561,7 +3670,7 @@ extern "C" int flope_tf_stream_prefill(flope_tf_stream s, const float* x_dev, in
   const std::string who = "flope_tf_stream_prefill";
   flope_tf_encoder* e;
   int rc, bad = -1;
-  if ((rc = tf_stream_enter(s, who, &e))) return rc;
+  if ((rc = tf_stream_enter_host(s, who, &e, "a device-positioned state has no prefill: feed it with flope_tf_stream_step_assoc or flope_tf_stream_step_tracker"))) return rc;
   if ((rc = tf_check_forward_varlen(e, who, n, seq_len, x_dev && y_dev))) return rc;
   std::vector<int> full;                            // lengths_host NULL: every sequence has seq_len tokens
   if (!lengths_host && n > 0) full.assign((size_t)n, seq_len);
@@ -3592,7 +3701,7 @@ extern "C" int flope_tf_stream_extend(flope_tf_stream s, const float* x_dev, int
   const std::string who = "flope_tf_stream_extend";
   flope_tf_encoder* e;
   int rc, bad = -1, smax = 0;
-  if ((rc = tf_stream_enter(s, who, &e))) return rc;
+  if ((rc = tf_stream_enter_host(s, who, &e, "a device-positioned state has no extend: use flope_tf_stream_step_assoc or flope_tf_stream_step_tracker"))) return rc;
   if ((rc = tf_check_forward_varlen(e, who, n, seq_len, x_dev && y_dev))) return rc;
   std::vector<int> full;                            // lengths_host NULL: every chunk has seq_len tokens
   if (!lengths_host && n > 0) full.assign((size_t)n, seq_len);
@@ -3631,6 +3740,140 @@ extern "C" int flope_tf_stream_step_plan(flope_tf_stream s) {
   int rc;
   if ((rc = tf_stream_enter(s, "flope_tf_stream_step_plan", &e))) return rc;
   return tf_by_dtype(e, [&](auto tag) { return tf_step_plan<typename decltype(tag)::type>(e, s); });
+}
+
+// ---- a device-positioned state stepped by an association ----------------------------------------------------------------
+namespace {
+// What _step_assoc and _step_tracker share behind their checks: tf_stream_feed_kernel (the table, the positions, the token rows),
+// _step's launch sequence for all n rows over the token buffer at smax = window, tf_feed_fill_bias.  SOURCE and its arrays as the
+// kernel takes them.
+int run_step_feed(flope_tf_stream_s* s, int source, const int* assoc, const int* overflow, int n, const double* vec7, int vec_rows, const float* x, float* y,
+                  hipStream_t st) {
+  flope_tf_encoder* e = s->e;
+  const dim3 grid((unsigned)((n + kTfFeedBlock - 1) / kTfFeedBlock)), block(kTfFeedBlock);
+#define TF_FEED(SRC_) hipLaunchKernelGGL((tf_stream_feed_kernel<SRC_>), grid, block, 0, st, assoc, overflow, n, s->tracks, s->pos_dev, s->tab, vec7, vec_rows, x, \
+                                         e->in_dim, s->tok)
+  if (source == kTfFeedRows) TF_FEED(kTfFeedRows);
+  else if (source == FLOPE_TF_FEED_MEAN) TF_FEED(FLOPE_TF_FEED_MEAN);
+  else TF_FEED(FLOPE_TF_FEED_MEAS);
+#undef TF_FEED
+  TF_HIP(e, hipGetLastError());
+  s->feed_n = n;
+  // no position is known here: a score row holds at most `window` keys (tf_window_keys <= W), which is what the launch is sized for
+  int rc = tf_by_dtype(e, [&](auto tag) { return run_step<typename decltype(tag)::type>(s, s->tok, n, s->window - 1, y, st); });
+  if (rc < 0) return rc;
+  const size_t total = (size_t)n * e->out_dim;
+  hipLaunchKernelGGL(tf_feed_fill_bias, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, (const int*)s->tab, (const float*)e->outl.b, y, e->out_dim, total);
+  TF_HIP(e, hipGetLastError());
+  TF_HIP(e, hipEventRecord(s->ev, st));
+  return 0;
+}
+
+// the checks both start with; n: the call's rows
+int tf_feed_enter(flope_tf_stream_s* s, const std::string& who, flope_tf_encoder** e) {
+  int rc;
+  if ((rc = tf_stream_enter_device(s, who, e))) return rc;
+  if (!(*e)->loaded) return tf_fail(*e, FLOPE_ESTATE, who + ": weights not loaded");
+  return 0;
+}
+int tf_feed_rows_ok(flope_tf_stream_s* s, const std::string& who, int n) {
+  if (n < 0 || n > s->max_rows)
+    return tf_fail(s->e, FLOPE_EINVAL, who + ": n = " + std::to_string(n) + " is outside 0 .. max_rows = " + std::to_string(s->max_rows));
+  return 0;
+}
+}  // namespace
+
+extern "C" int flope_tf_stream_step_assoc(flope_tf_stream s, const float* x_dev, const int32_t* assoc_dev, const int32_t* overflow_dev, int n, float* y_dev,
+                                          void* stream) {
+  const std::string who = "flope_tf_stream_step_assoc";
+  flope_tf_encoder* e;
+  int rc;
+  if ((rc = tf_feed_enter(s, who, &e))) return rc;
+  if ((rc = tf_feed_rows_ok(s, who, n))) return rc;
+  if (n == 0) return FLOPE_OK;
+  if (!x_dev || !assoc_dev || !y_dev) return tf_fail(e, FLOPE_EINVAL, who + ": NULL buffer");
+  TF_HIP(e, hipSetDevice(e->device));
+  return run_step_feed(s, kTfFeedRows, assoc_dev, overflow_dev, n, nullptr, 0, x_dev, y_dev, (hipStream_t)stream);
+}
+
+extern "C" int flope_tf_stream_step_tracker(flope_tf_stream s, flope_track_handle t, int source, float* y_dev, void* stream) {
+  const std::string who = "flope_tf_stream_step_tracker";
+  flope_tf_encoder* e;
+  int rc;
+  if ((rc = tf_feed_enter(s, who, &e))) return rc;
+  flope_track_view v;
+  if (!t || flope_track_device_view(t, &v) != FLOPE_OK) return tf_fail(e, FLOPE_EINVAL, who + ": NULL tracker");
+  if (source != FLOPE_TF_FEED_MEAS && source != FLOPE_TF_FEED_MEAN)
+    return tf_fail(e, FLOPE_EINVAL, who + ": source = " + std::to_string(source) + " is neither FLOPE_TF_FEED_MEAS nor FLOPE_TF_FEED_MEAN");
+  if (e->in_dim < flope_tf_plan::kTfFeedDim)
+    return tf_fail(e, FLOPE_EINVAL, who + ": input_dim = " + std::to_string(e->in_dim) + " is below 7, the tracker's vector (world position, quaternion x y z w)");
+  if (v.device != e->device) return tf_fail(e, FLOPE_EINVAL, who + ": the tracker lives on device " + std::to_string(v.device) + ", the encoder on " + std::to_string(e->device));
+  if (v.n < 0) return tf_fail(e, FLOPE_ESTATE, who + ": the tracker has had no update since flope_track_create / flope_track_reset");
+  if (s->fed_tracker == (const void*)t && s->fed_serial == v.serial)
+    return tf_fail(e, FLOPE_ESTATE, who + ": update " + std::to_string(v.serial) + " of this tracker has been fed to this state already (one token per track and update)");
+  if ((rc = tf_feed_rows_ok(s, who, v.n))) return rc;
+  if (!y_dev) return tf_fail(e, FLOPE_EINVAL, who + ": NULL buffer");
+  TF_HIP(e, hipSetDevice(e->device));
+  hipStream_t st = (hipStream_t)stream;
+  TF_HIP(e, hipStreamWaitEvent(st, (hipEvent_t)v.event, 0));
+  s->fed_tracker = (const void*)t;
+  s->fed_serial = v.serial;
+  const bool mean = source == FLOPE_TF_FEED_MEAN;
+  if ((rc = run_step_feed(s, source, v.assoc, v.count + 1, v.n, mean ? v.means : v.meas, mean ? v.max_tracks : v.n, nullptr, y_dev, st))) return rc;
+  return v.n;
+}
+
+extern "C" int flope_tf_stream_reset_device(flope_tf_stream s, void* stream) {
+  flope_tf_encoder* e;
+  int rc;
+  if ((rc = tf_stream_enter_device(s, "flope_tf_stream_reset_device", &e))) return rc;
+  TF_HIP(e, hipSetDevice(e->device));
+  TF_HIP(e, hipMemsetAsync(s->pos_dev, 0, (size_t)s->tracks * sizeof(int), (hipStream_t)stream));
+  TF_HIP(e, hipEventRecord(s->ev, (hipStream_t)stream));
+  s->fed_tracker = nullptr;                        // (a tracker that was reset too starts a new run of updates: none of them has been fed)
+  return FLOPE_OK;
+}
+
+extern "C" int flope_tf_stream_read_positions(flope_tf_stream s, int32_t* pos_host, int cap) {
+  const std::string who = "flope_tf_stream_read_positions";
+  flope_tf_encoder* e;
+  int rc;
+  if ((rc = tf_stream_enter_device(s, who, &e))) return rc;
+  if (!pos_host || cap < s->tracks) return tf_fail(e, FLOPE_EINVAL, who + ": pos_host is NULL or holds fewer than tracks = " + std::to_string(s->tracks) + " ints");
+  TF_HIP(e, hipSetDevice(e->device));
+  TF_HIP(e, hipEventSynchronize(s->ev));
+  TF_HIP(e, hipMemcpy(pos_host, s->pos_dev, (size_t)s->tracks * sizeof(int), hipMemcpyDeviceToHost));
+  return s->tracks;
+}
+
+extern "C" int flope_tf_stream_read_feed(flope_tf_stream s, int32_t* track_host, int32_t* pos_host, int cap) {
+  const std::string who = "flope_tf_stream_read_feed";
+  flope_tf_encoder* e;
+  int rc;
+  if ((rc = tf_stream_enter_device(s, who, &e))) return rc;
+  const int n = s->feed_n;
+  if (n == 0) return 0;
+  if (!track_host || !pos_host || cap < n) return tf_fail(e, FLOPE_EINVAL, who + ": NULL buffer, or room for fewer than the last call's " + std::to_string(n) + " rows");
+  TF_HIP(e, hipSetDevice(e->device));
+  TF_HIP(e, hipEventSynchronize(s->ev));
+  std::vector<int> tab((size_t)2 * n);
+  TF_HIP(e, hipMemcpy(tab.data(), s->tab, tab.size() * sizeof(int), hipMemcpyDeviceToHost));
+  for (int m = 0; m < n; ++m) { track_host[m] = tab[(size_t)2 * m]; pos_host[m] = tab[(size_t)2 * m + 1]; }
+  return n;
+}
+
+extern "C" int flope_tf_stream_read_tokens(flope_tf_stream s, float* tok_host, int cap_rows) {
+  const std::string who = "flope_tf_stream_read_tokens";
+  flope_tf_encoder* e;
+  int rc;
+  if ((rc = tf_stream_enter_device(s, who, &e))) return rc;
+  const int n = s->feed_n;
+  if (n == 0) return 0;
+  if (!tok_host || cap_rows < n) return tf_fail(e, FLOPE_EINVAL, who + ": NULL buffer, or room for fewer than the last call's " + std::to_string(n) + " rows");
+  TF_HIP(e, hipSetDevice(e->device));
+  TF_HIP(e, hipEventSynchronize(s->ev));
+  TF_HIP(e, hipMemcpy(tok_host, s->tok, (size_t)n * e->in_dim * sizeof(float), hipMemcpyDeviceToHost));
+  return n;
 }
 
 namespace {
@@ -3682,7 +3925,7 @@ extern "C" int flope_tf_stream_attention(flope_tf_stream s, const void* qkv_dev,
   const std::string who = "flope_tf_stream_attention";
   flope_tf_encoder* e;
   int rc, bad = -1, max_pos = 0;
-  if ((rc = tf_stream_enter(s, who, &e))) return rc;
+  if ((rc = tf_stream_enter_host(s, who, &e, "the hook moves positions on the host: use a state of flope_tf_stream_open_window"))) return rc;
   if (e->nl < 1) return tf_fail(e, FLOPE_EINVAL, who + ": an encoder without layers has no cache");
   if ((rc = flope_tf_plan::tf_stream_check_attention(s->tracks, s->capacity, s->window, e->max_tokens, n, seq_len, lengths_host, &bad, &max_pos)))
     return tf_hook_refuse(s, who, rc, bad, n, seq_len, lengths_host, ", or seq_len < 1");
@@ -3736,7 +3979,7 @@ extern "C" int flope_tf_stream_attention_extend(flope_tf_stream s, const void* q
   const std::string who = "flope_tf_stream_attention_extend";
   flope_tf_encoder* e;
   int rc, bad = -1, smax = 0, max_len = 0, total = 0;
-  if ((rc = tf_stream_enter(s, who, &e))) return rc;
+  if ((rc = tf_stream_enter_host(s, who, &e, "the hook moves positions on the host: use a state of flope_tf_stream_open_window"))) return rc;
   if (e->nl < 1) return tf_fail(e, FLOPE_EINVAL, who + ": an encoder without layers has no cache");
   if ((rc = tf_stream_check_attention_extend(s->tracks, s->capacity, s->window, e->max_tokens, n, seq_len, lengths_host, cached_host, &bad, &smax, &max_len, &total))) {
     if (rc == kTfStreamCached)

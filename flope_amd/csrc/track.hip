@@ -36,6 +36,7 @@ struct flope_track {
   int32_t *hits = nullptr, *count = nullptr, *assoc = nullptr, *cand = nullptr;     // count[0] tracks, count[1] overflow flag
   hipEvent_t ev = nullptr;
   int last_n = -1;                               // measurements of the last update; -1: none since create / reset
+  unsigned long long serial = 0;                 // updates that enqueued anything, never reset (flope_track_device_view)
   std::string err;
 };
 
@@ -258,6 +259,16 @@ extern "C" int flope_track_update(flope_track_handle t, const void* Rt_dev, int 
                      t->hits, t->count, t->assoc);
   if (hipGetLastError() != hipSuccess || hipEventRecord(t->ev, st) != hipSuccess) return tfail(t, FLOPE_EHIP, "flope_track_update: launch failed");
   t->last_n = n;
+  ++t->serial;
+  return FLOPE_OK;
+}
+
+extern "C" int flope_track_device_view(flope_track_handle t, flope_track_view* out) {
+  if (!t || !out) return tfail(t, FLOPE_EINVAL, "flope_track_device_view: NULL handle or view");
+  out->assoc = t->assoc; out->meas = t->meas; out->means = t->means; out->count = t->count;
+  out->event = (void*)t->ev;
+  out->device = t->device; out->max_tracks = t->max_tracks; out->max_meas = t->max_meas; out->n = t->last_n;
+  out->serial = t->serial;
   return FLOPE_OK;
 }
 

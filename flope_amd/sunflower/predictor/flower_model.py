@@ -82,11 +82,16 @@ def poses_to_measurements(flower_pose_world):
 
 
 class FlowerModel:
-    def __init__(self, dist_th=50, intrin_path=None, get_plots=False, pose_predictor=None, tracker="host"):
+    def __init__(self, dist_th=50, intrin_path=None, get_plots=False, pose_predictor=None, tracker="host", track_stream=None, track_source="measurement"):
         """tracker: "host" (default) = the reference's numpy tracker below; "device" = the same association and filters with the
         state in GPU memory (flope_amd.track.DeviceTracker): `state`, `scores`, `get_state()` and `filtered_state()`
         read from it, `add_stream` feeds it behind the frame's pose kernels without the host touching a pose, and `kfs` (the 7 x 7
-        filter objects) is not offered."""
+        filter objects) is not offered.
+        track_stream (tracker="device" only): a device-positioned encoder stream
+        (`enc.open_stream(..., window=W, positions="device")`).  `add_poses(..., ignore=True)` then steps it right behind the tracker's
+        update, on the device and without a host wait -- one token per track the frame touched, its `track_source` ("measurement" or
+        "mean") -- and keeps the encoder's rows as `track_rows` (a device tensor [n, out_dim], row m for measurement m) and which row
+        fed which track as `track_feed` ((tracks_or_codes, positions), read back only when asked for)."""
         if get_plots:
             raise NotImplementedError("the live matplotlib plots of the reference are display code and are not reproduced")
         if tracker not in ("host", "device"):
@@ -94,6 +99,12 @@ class FlowerModel:
         self.get_plots = False
         self.tracker = tracker
         self._device_tracker = None
+        if track_stream is not None and tracker != "device":
+            raise ValueError("FlowerModel: track_stream needs tracker='device' (the host tracker keeps no association on the device)")
+        if track_stream is not None and getattr(track_stream, "positions_on", None) != "device":
+            raise ValueError("FlowerModel: track_stream must be a device-positioned stream (enc.open_stream(..., positions='device'))")
+        self.track_stream, self.track_source = track_stream, track_source
+        self.track_rows = None                        # the encoder's rows of the last frame that fed track_stream
         if tracker == "host":
             self.state = None
             self.scores = None
@@ -114,6 +125,14 @@ class FlowerModel:
             raise AttributeError("FlowerModel(tracker='device') keeps one variance per track on the device, not 7 x 7 filter objects: "
                                  "use filtered_state() and device_tracker.p, or tracker='host'")
         raise AttributeError(f"{type(self).__name__!r} object has no attribute {name!r}")
+
+    @property
+    def track_feed(self):
+        """(tracks_or_codes, positions) of the last frame that fed track_stream: which track row m of `track_rows` belongs to, or a
+        negative code for a row that fed nothing; None before the first.  Reading it waits for that frame's kernels."""
+        if self.track_stream is None or self.track_rows is None:
+            return None
+        return self.track_stream.last_feed()
 
     @property
     def device_tracker(self):
@@ -152,6 +171,8 @@ class FlowerModel:
         flower_pose = pose_cam_to_world(flower_pose_cam, cam_pose_to_matrix(cam_pose))
         if ignore and self._device_tracker is not None:
             self._device_tracker.update(flower_pose_cam, cam_pose)
+            if self.track_stream is not None and np.asarray(flower_pose_cam).size:      # (an empty frame is no update)
+                self.track_rows = self.track_stream.step_tracker(self._device_tracker, self.track_source)
         elif ignore:
             self.assign_meas_to_state(poses_to_measurements(flower_pose))
         return flower_pose_cam, flower_pose.astype(np.float32)

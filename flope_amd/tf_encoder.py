@@ -26,6 +26,7 @@ from __future__ import annotations
 
 import ctypes as C
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -608,7 +609,7 @@ class TransformerEncoder:
         self._keep = (x, weight, bias)
         return out
 
-    def open_stream(self, tracks: int, capacity: int, window: int = 0, bias=None) -> "TransformerEncoderStream":
+    def open_stream(self, tracks: int, capacity: int, window: int = 0, bias=None, positions: str = "host", max_rows=None) -> "TransformerEncoderStream":
         """A stream state for `tracks` live tracks of up to `capacity` tokens each (TransformerEncoderStream): feed one new token per
         track with step() and get the row a causal forward of the whole track would end with, without running it again;
         extend() appends several tokens per track in one call, with the bits of those steps.
@@ -621,8 +622,12 @@ class TransformerEncoder:
         as its scaled score + table[h][p - j], and step(), extend() and prefill() return, in bits and in every dtype and under every
         option, the rows of enc(x, mask=enc.make_bias(distance_bias(table, L, window))) with `bias_mfma=0` (the option does not reach a
         stream: DESIGN.md 44).  Without it the encoder has no positional
-        term and a track's last row does not depend on the order of the poses behind it."""
-        return TransformerEncoderStream(self, tracks, capacity, window, bias)
+        term and a track's last row does not depend on the order of the poses behind it.
+        `positions="device"` (needs `window`): the positions live in device memory and the state is stepped by an
+        association only the device knows -- `step_tracker(tracker)` behind a DeviceTracker's update, or `step_assoc(x, assoc)` --
+        without a host wait; `max_rows` (default: max_tokens) is the most rows one call takes.  step(), extend() and
+        prefill() are not offered on such a state."""
+        return TransformerEncoderStream(self, tracks, capacity, window, bias, positions, max_rows)
 
     def close(self):
         if getattr(self, "handle", None) and self.handle.value:
@@ -740,7 +745,7 @@ class TransformerEncoderStream:
     score of query p and key j and return the rows of the forward under enc.make_bias(distance_bias(table, L, window)) in bits, in
     every dtype and whatever `attn_tiled`, `step_split` or `extend_mfma` say -- `step_plan` / `extend_plan()` answer "biased"."""
 
-    def __init__(self, enc: TransformerEncoder, tracks: int, capacity: int, window: int = 0, bias=None):
+    def __init__(self, enc: TransformerEncoder, tracks: int, capacity: int, window: int = 0, bias=None, positions: str = "host", max_rows=None):
         self.enc = enc
         self.state = C.c_void_p()
         self.tracks, self.capacity, self.window = int(tracks), int(capacity), int(window)
@@ -748,6 +753,14 @@ class TransformerEncoderStream:
         self._handle()
         if self.window < 0:
             raise ValueError(f"window must be 0 (a linear cache) or 1 .. capacity, got {self.window}")
+        if positions not in ("host", "device"):
+            raise ValueError(f"positions must be 'host' or 'device', got {positions!r}")
+        self.positions_on = positions
+        self.max_rows = 0
+        if positions == "host" and max_rows is not None:
+            raise ValueError("max_rows belongs to positions='device'")
+        if positions == "device":
+            self.max_rows = enc.max_tokens if max_rows is None else int(max_rows)
         self.bias_planes = 0
         if bias is not None:
             # every refusal of the table's contents is made on the C side, which names (plane, distance)
@@ -758,13 +771,19 @@ class TransformerEncoderStream:
                 raise ValueError(f"bias lives on {bias.device}, the encoder on {enc.device}")
             t = bias.detach().to(device="cpu", dtype=torch.float32).reshape(-1, bias.shape[-1]).contiguous()
             with torch.cuda.device(enc.device):
-                rc = enc.lib.flope_tf_stream_open_bias(enc.handle, self.tracks, self.capacity, self.window, int(t.shape[0]), int(t.shape[1]),
-                                                       C.cast(t.data_ptr(), C.POINTER(C.c_float)), C.byref(self.state))
+                if positions == "device":
+                    rc = enc.lib.flope_tf_stream_open_device(enc.handle, self.tracks, self.capacity, self.window, self.max_rows, int(t.shape[0]),
+                                                             int(t.shape[1]), C.cast(t.data_ptr(), C.POINTER(C.c_float)), C.byref(self.state))
+                else:
+                    rc = enc.lib.flope_tf_stream_open_bias(enc.handle, self.tracks, self.capacity, self.window, int(t.shape[0]), int(t.shape[1]),
+                                                           C.cast(t.data_ptr(), C.POINTER(C.c_float)), C.byref(self.state))
             enc._check_arg(rc)
             self.bias_planes = int(enc.lib.flope_tf_stream_bias_planes(self.state))
             return
         with torch.cuda.device(enc.device):
-            if self.window:
+            if positions == "device":
+                rc = enc.lib.flope_tf_stream_open_device(enc.handle, self.tracks, self.capacity, self.window, self.max_rows, 0, 0, None, C.byref(self.state))
+            elif self.window:
                 rc = enc.lib.flope_tf_stream_open_window(enc.handle, self.tracks, self.capacity, self.window, C.byref(self.state))
             else:
                 rc = enc.lib.flope_tf_stream_open(enc.handle, self.tracks, self.capacity, C.byref(self.state))
@@ -933,9 +952,77 @@ class TransformerEncoderStream:
             raise ValueError(f"out must be a contiguous float32 tensor {tuple(shape)} on {self.enc.device}")
         return out
 
-    def reset(self, tracks=None) -> None:
-        """The given tracks (None: all) hold nothing again; their stale cache rows are never read.  Enqueues nothing."""
+    def step_assoc(self, x: torch.Tensor, assoc: torch.Tensor, overflow: torch.Tensor = None, out: torch.Tensor = None) -> torch.Tensor:
+        """A device-positioned state.  x [n, input_dim] float32 and assoc int32 [n] on the device: assoc[m] >= 0 names
+        the track row m belongs to, a negative value -1 - t the track t it opened, INT32_MIN a row to skip (a DeviceTracker's
+        encoding); `overflow`: an int32 tensor of one element on the device, non-zero = every row is refused.  -> [n, out_dim]: the
+        row step() would return for each row that feeds its track (the first row of the call that names the track, a track below
+        `tracks`), out_layer.bias for the others -- `last_feed()` tells which.  No host wait.  n = 0 returns an empty result."""
         self._live()
+        enc = self.enc
+        x = self._check_x(x, 2)
+        n = x.shape[0]
+        if not (isinstance(assoc, torch.Tensor) and assoc.device == enc.device and assoc.dtype == torch.int32 and assoc.is_contiguous() and assoc.numel() == n):
+            raise ValueError(f"assoc must be a contiguous int32 tensor [{n}] on {enc.device}")
+        if overflow is not None and not (isinstance(overflow, torch.Tensor) and overflow.device == enc.device and overflow.dtype == torch.int32 and
+                                         overflow.numel() == 1):
+            raise ValueError(f"overflow must be an int32 tensor of one element on {enc.device}")
+        y = self._out(out, (n, enc.dims[2]))
+        with torch.cuda.device(enc.device):
+            rc = enc.lib.flope_tf_stream_step_assoc(self.state, x.data_ptr(), assoc.data_ptr(), None if overflow is None else overflow.data_ptr(), n,
+                                                    y.data_ptr(), _stream_ptr(enc.device))
+        enc._check_arg(rc)
+        self._keep = (x, assoc, overflow)
+        return y
+
+    def step_tracker(self, tracker, source: str = "measurement", out: torch.Tensor = None) -> torch.Tensor:
+        """A device-positioned state, right behind `tracker.update(...)` on the same stream: one token for every
+        track the update touched, taken on the device from the tracker's last frame -- source "measurement": the row's measurement
+        [x y z | qx qy qz qw] in the world frame; "mean": its track's filtered mean after the frame -- rounded to float32, zeros
+        behind column 6.  -> [n, out_dim], n the frame's measurements: row m is the encoder's row for measurement m where it feeds
+        its track (the first measurement of the frame on a track below `tracks`), out_layer.bias elsewhere; `last_feed()` tells
+        which.  No host wait.  RuntimeError: the same update fed twice, or no update since the tracker was made or reset."""
+        self._live()
+        enc = self.enc
+        if source not in ("measurement", "mean"):
+            raise ValueError(f"source must be 'measurement' or 'mean', got {source!r}")
+        n = int(tracker.last_n)
+        if n < 0:
+            n = 0                                  # (the call refuses it with the reason)
+        y = self._out(out, (n, enc.dims[2]))
+        with torch.cuda.device(enc.device):
+            rc = enc.lib.flope_tf_stream_step_tracker(self.state, tracker.handle, _lib.TF_FEED_MEAN if source == "mean" else _lib.TF_FEED_MEAS,
+                                                      y.data_ptr() if n else None, _stream_ptr(enc.device))
+        enc._check_arg(rc)
+        return y
+
+    def last_feed(self):
+        """-> (tracks_or_codes int32 [n], positions int32 [n]) of the last step_assoc() / step_tracker(): per row the track it fed and
+        the position its token took, or a negative code (_lib.TF_FEED_*) and 0.  Waits for that call."""
+        self._live()
+        t, p = np.empty(max(self.max_rows, 1), dtype=np.int32), np.empty(max(self.max_rows, 1), dtype=np.int32)
+        n = self.enc.lib.flope_tf_stream_read_feed(self.state, t.ctypes.data, p.ctypes.data, len(t))
+        self.enc._check_arg(n)
+        return t[:n].copy(), p[:n].copy()
+
+    def last_tokens(self) -> np.ndarray:
+        """test hook: the float32 token rows [n, input_dim] the last step_assoc() / step_tracker() ran on.  Waits for that call."""
+        self._live()
+        tok = np.empty((max(self.max_rows, 1), self.enc.dims[0]), dtype=np.float32)
+        n = self.enc.lib.flope_tf_stream_read_tokens(self.state, tok.ctypes.data, len(tok))
+        self.enc._check_arg(n)
+        return tok[:n].copy()
+
+    def reset(self, tracks=None) -> None:
+        """The given tracks (None: all) hold nothing again; their stale cache rows are never read.  Enqueues nothing; a
+        device-positioned state resets all its tracks, by a memset on the current stream."""
+        self._live()
+        if self.max_rows:
+            if tracks is not None:
+                raise ValueError("a device-positioned state resets all its tracks: reset()")
+            with torch.cuda.device(self.enc.device):
+                self.enc._check_arg(self.enc.lib.flope_tf_stream_reset_device(self.state, _stream_ptr(self.enc.device)))
+            return
         cnt, th = _host_tracks(tracks)
         self.enc._check_arg(self.enc.lib.flope_tf_stream_reset(self.state, cnt or 0, th))
 
@@ -948,6 +1035,12 @@ class TransformerEncoderStream:
 
     @property
     def positions(self) -> list:
+        """tokens held per track; a device-positioned state reads them back (and waits for its last call)"""
+        if self.max_rows:
+            self._live()
+            pos = np.empty(self.tracks, dtype=np.int32)
+            self.enc._check_arg(self.enc.lib.flope_tf_stream_read_positions(self.state, pos.ctypes.data, self.tracks))
+            return pos.tolist()
         return [self.position(t) for t in range(self.tracks)]
 
     def close(self):

@@ -92,6 +92,14 @@ class DeviceTracker:
         self._check(self.lib.flope_track_reset(self.handle))
 
     @property
+    def last_n(self) -> int:
+        """measurements of the last update that enqueued anything, -1 when there was none since the tracker was made or reset: the
+        rows TransformerEncoderStream.step_tracker returns.  Kept on the host; waits for nothing."""
+        v = _lib.TrackView()
+        self._check(self.lib.flope_track_device_view(self.handle, C.byref(v)))
+        return int(v.n)
+
+    @property
     def count(self) -> int:
         return self._check(self.lib.flope_track_count(self.handle))
 

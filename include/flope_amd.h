@@ -351,6 +351,21 @@ int flope_track_debug_sentinels(flope_track_handle t);
 /* test hook: waits; the first `rows` rows of every state array as they are in device memory and count2 = {tracks, overflow flag},
  * whatever the flag says (what an update that overflowed has left behind); returns rows */
 int flope_track_debug_read(flope_track_handle t, double* anchors, double* means, double* p, int32_t* hits, int32_t* count2, int rows);
+/* What a consumer on the device needs of the handle's state behind its last update (flope_tf_stream_step_tracker): device
+ * pointers that stay valid until _destroy, the event a reader's stream must wait for, and host-side counts.  Enqueues nothing and
+ * waits for nothing.  n: the measurements of the last update, -1 when there was none since _create / _reset.  serial: counts the
+ * updates of the handle that enqueued anything (n > 0), from 1; it is kept on the host and never reset, so two views with one
+ * serial speak of the same update.  The arrays are overwritten by the next update: a reader orders that update behind itself. */
+typedef struct flope_track_view {
+  const int32_t* assoc;        /* [max_meas]: the last update's association (flope_track_read_assoc's encoding) */
+  const double* meas;          /* [max_meas][7]: its measurements, world position then quaternion x y z w; rows the update skipped are stale */
+  const double* means;         /* [max_tracks][7]: the filtered means */
+  const int32_t* count;        /* [2]: tracks, overflow flag */
+  void* event;                 /* a hipEvent_t recorded behind every update */
+  int device, max_tracks, max_meas, n;
+  unsigned long long serial;
+} flope_track_view;
+int flope_track_device_view(flope_track_handle t, flope_track_view* out);
 /* The slot's device-resident poses and depth-reliability flags (the rows flope_frame_finish would return) into the tracker,
  * behind the slot's pose kernels on the slot's stream, without a host wait.  Legal between a flope_frame_enqueue that returned
  * n > 0 and that slot's flope_frame_finish; a slot whose enqueue returned 0 is a no-op returning 0; an idle slot is FLOPE_ESTATE; a
@@ -656,6 +671,15 @@ double flope_tf_forward_flops_varlen(flope_tf_handle h, int batch, const int* le
 #define FLOPE_TF_EXTEND_MFMA      2
 #define FLOPE_TF_STEP_BIASED      2
 #define FLOPE_TF_EXTEND_BIASED    3
+/* what a row that feeds nothing carries in place of its track (flope_tf_stream_read_feed; csrc/tf_stream_feed.h) */
+#define FLOPE_TF_FEED_SKIPPED     (-1)   /* the tracker skipped the row as unreliable */
+#define FLOPE_TF_FEED_OVERFLOW    (-2)   /* the tracker's overflow flag is set: every row of the call */
+#define FLOPE_TF_FEED_RANGE       (-3)   /* the track is none of the stream's */
+#define FLOPE_TF_FEED_DUPLICATE   (-4)   /* an earlier row of the frame names the same track */
+#define FLOPE_TF_FEED_FULL        (-5)   /* the track holds INT_MAX tokens */
+/* what flope_tf_stream_step_tracker takes a token from */
+#define FLOPE_TF_FEED_MEAS        0      /* the frame's measurement of the row */
+#define FLOPE_TF_FEED_MEAN        1      /* the filtered mean of the row's track after the frame's updates */
 typedef struct flope_tf_stream_s* flope_tf_stream;
 int flope_tf_stream_open(flope_tf_handle h, int tracks, int capacity, flope_tf_stream* out);
 int flope_tf_stream_open_window(flope_tf_handle h, int tracks, int capacity, int window, flope_tf_stream* out);
@@ -676,6 +700,59 @@ int flope_tf_stream_attention(flope_tf_stream s, const void* qkv_dev, int n, int
 int flope_tf_stream_extend_plan(flope_tf_stream s);
 int flope_tf_stream_attention_extend(flope_tf_stream s, const void* qkv_dev, int n, int seq_len, const int* lengths_host, const int* cached_host,
                                      void* att_dev, void* stream);
+/* A DEVICE-POSITIONED stream state: the state above with its positions in device memory, stepped by an association
+ * that only the device knows -- the device tracker's (flope_track_*): the host sees neither a pose nor a track id.
+ *   _open_device  windowed only, 1 <= window <= capacity <= 4096: a ring is never full and a score row never holds more than
+ *             `window` keys, so every launch is sized with smax = window without knowing a position.  planes = 0 with a NULL table
+ *             opens an unbiased state; otherwise (planes, distances, table_host) are _open_bias's, refusals included.  The cache has
+ *             the shape of every other state's; beside it the state owns int pos_dev[tracks] (zeroed), a table of 2 max_rows ints and a
+ *             float32 token buffer [max_rows][input_dim], all allocated here.  max_rows: 1 .. max_tokens, the most rows one call takes.
+ *             On such a state _step, _extend, _prefill, _reset, _position, _attention and _attention_extend return FLOPE_ESTATE and
+ *             the message names the call to use instead; the calls below return FLOPE_ESTATE on every other state, which behaves
+ *             exactly as before.
+ *   The feed rule (csrc/tf_stream_feed.h, one definition for host and device).  Row m of a frame has association a in the tracker's
+ *             encoding (a >= 0: matched track a; a < 0: opened track -1 - a; INT32_MIN: skipped).  It FEEDS its track iff the
+ *             overflow flag is clear (else every row is FLOPE_TF_FEED_OVERFLOW), it was not skipped (_SKIPPED), the track is below the
+ *             state's `tracks` (_RANGE), no row e < m of the frame names the same track (_DUPLICATE: the first measurement in
+ *             measurement order is the frame's token) and the track's position is below INT_MAX (_FULL).  A feeding row takes the
+ *             table entry (track, position) and advances the position by one; every other row takes (code, 0) and moves nothing.
+ *   _step_assoc   x_dev float32 [n, input_dim], assoc_dev int32 [n], overflow_dev one int32 (non-zero: the flag; may be NULL = clear)
+ *             -> y_dev float32 [n, out_dim], asynchronous on `stream`.  tf_stream_feed_kernel applies the rule on the device and
+ *             copies the feeding rows of x_dev into the token buffer (the others become zero rows); then _step's launch sequence
+ *             runs for n rows -- the forward's linears and LayerNorms, the attention kernel _step_plan names (ROW, SPLIT under
+ *             "step_split", BIASED on a state with a table) at smax = window, which leaves a row alone whose table entry is a code;
+ *             one last launch writes out_layer's bias into the rows of y_dev whose entry is a code, the value the library returns
+ *             behind a ragged length.  A feeding row of y_dev is, in bits, what _step returns on a host-positioned state of the same
+ *             window, capacity and table for the same tokens; so is the cache.  n = 0 enqueues nothing and returns 0.
+ *   _step_tracker the same with n, the association, the flag and the 7-vectors taken from the tracker's device memory behind its
+ *             last update (`stream` is made to wait for the tracker's event): columns 0 .. 6 of a feeding row's token are the row's
+ *             measurement (source FLOPE_TF_FEED_MEAS) or its track's filtered mean after the frame's updates (FLOPE_TF_FEED_MEAN),
+ *             world position then quaternion [x y z w], each rounded once to float32; columns 7 .. input_dim - 1 are zero.
+ *             tf_stream_feed_kernel is the only launch of the call that reads the tracker's memory.  Returns the row count n.
+ *             FLOPE_EINVAL: input_dim < 7, a source other than the two, n > max_rows, another device.  FLOPE_ESTATE: no update
+ *             since flope_track_create / _reset, or the update that was fed to this state last (a host-side serial number of
+ *             flope_track_update tells them apart).
+ *   Refused by both, nothing enqueued and no position moved: NULL buffers, n outside 0 .. max_rows, a state that is not
+ *             device-positioned (FLOPE_ESTATE), weights not loaded or the handle destroyed (FLOPE_ESTATE).
+ *   Contracts: THE CALLS ON ONE STATE ARE ORDERED ON ONE STREAM BY THE CALLER, as above.  THE TRACKER'S NEXT UPDATE MUST BE ORDERED
+ *             BEHIND _step_tracker BY THE CALLER (it overwrites what the call reads); issuing both on one stream does that, as the
+ *             frame handle's pose stream does.  After flope_track_reset the caller resets the stream state too (_reset_device): the
+ *             tracker's track numbers start again.  A call that fails on the way with FLOPE_EHIP may have moved positions.
+ *   _reset_device every position back to 0, an asynchronous memset on `stream`.
+ *   _read_positions  waits for the state's last call; int32 [tracks] into pos_host (cap >= tracks); returns tracks.
+ *   _read_feed    waits for the state's last call; the table of the last _step_assoc / _step_tracker: track_host[m] the track row m
+ *             fed or its FLOPE_TF_FEED_* code, pos_host[m] the position its token took (0 beside a code); returns the row count
+ *             (0 before the first call), FLOPE_EINVAL when it exceeds cap.
+ *   _read_tokens  test hook: waits; the float32 token rows [n][input_dim] of the last call into tok_host (cap_rows >= n); returns n. */
+int flope_tf_stream_open_device(flope_tf_handle h, int tracks, int capacity, int window, int max_rows, int planes, int distances,
+                                const float* table_host, flope_tf_stream* out);
+int flope_tf_stream_step_assoc(flope_tf_stream s, const float* x_dev, const int32_t* assoc_dev, const int32_t* overflow_dev, int n, float* y_dev,
+                               void* stream);
+int flope_tf_stream_step_tracker(flope_tf_stream s, flope_track_handle t, int source, float* y_dev, void* stream);
+int flope_tf_stream_reset_device(flope_tf_stream s, void* stream);
+int flope_tf_stream_read_positions(flope_tf_stream s, int32_t* pos_host, int cap);
+int flope_tf_stream_read_feed(flope_tf_stream s, int32_t* track_host, int32_t* pos_host, int cap);
+int flope_tf_stream_read_tokens(flope_tf_stream s, float* tok_host, int cap_rows);
 /* Any [L, L] attention mask (scripts/tf_encoder.py: nn.TransformerEncoder.forward(mask=)), compiled once into a
  * device-resident object and passed to any number of forwards.  A mask holds, for one sequence length L, the (query i, key j) pairs
  * that may attend: query i is a softmax over exactly its allowed keys, and a masked key is never loaded, neither its k nor its v (NaN
