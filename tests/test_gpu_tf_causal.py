@@ -5,7 +5,8 @@ depend on how long the sequence is -- so besides the tolerances against fp64 the
 
   1. the four attention kernels stand-alone, the case table of tests/test_gpu_tf_varlen.py, at lengths with a single key, a diagonal
      inside a ragged step, a second query block with skipped blocks, and a reused ring stage: the kernel id of the non-causal pick,
-     the fp64 causal reference (element-wise bound for 16 bits, 2e-4 for float32), row 0 = v[0], the last row = the non-causal last
+     the fp64 causal reference (element-wise bound for 16 bits; 2e-4 for float32 and beside it the element-wise bound of
+     tests/tf_attn_f32m_bound.py for tf_attn_f32m, the row bound of tests/tf_attn_mask_bound.py for the generic kernel), row 0 = v[0], the last row = the non-causal last
      row, prefix = prefix, a sentinel behind the output, two runs equal, and ragged x causal = each sequence alone;
   2. the whole encoder in every mode on two shapes: the fp64 causal restatement, the reference module's own causal output, mask= in
      both forms, prefix = prefix, lengths (valid rows, the reference's padded-and-masked rows, out_layer.bias behind them), the
@@ -22,6 +23,8 @@ import torch
 
 import tf_attn_bound as AB
 import tf_attn_causal_bound as CB
+import tf_attn_f32m_bound as FB
+import tf_attn_mask_bound as MB
 
 pytestmark = pytest.mark.gpu
 
@@ -75,8 +78,15 @@ def _within_reference(got, qkv, dtype, what):
         assert r <= 1.0, (what, where)
     else:
         err = float((got.double().cpu() - CB.attention_fp64(qkv, H)).abs().max())
-        print(f"{what}: |out - fp64|max {err:.2e}")
+        r2 = 0.0
+        if dtype == "f32m":                                   # tf_attn_f32m: tests/tf_attn_f32m_bound.py, both assertions
+            r, where, r2 = FB.verdict(got, FB.reference_of(qkv, H, causal=True))
+        else:                                                 # the row kernel over the contiguous keys 0 .. i
+            ref, bound = MB.reference_of(qkv, MB.make_allowed("causal", qkv.shape[1]), H, "f32")
+            r, where = MB.ratio(got, ref, bound)
+        print(f"{what}: |out - fp64|max {err:.2e}; err / bound {r:.3f} at {where}" + (f"; relL2 / yardstick {r2:.3f}" if dtype == "f32m" else ""))
         assert err < 2e-4, what
+        assert r <= 1.0 and r2 <= 1.0, (what, where)          # every element within its derived bound
 
 
 def _check_attention(dtype, hd, opts, want):

@@ -21,6 +21,8 @@ import pytest
 import torch
 
 import tf_attn_bound as AB
+import tf_attn_f32m_bound as FB
+import tf_attn_mask_bound as MB
 
 pytestmark = pytest.mark.gpu
 
@@ -109,16 +111,22 @@ def _check_attention(dtype, hd, opts, want):
         ref = _fp64(seqs[i], hd)
         err = float((fwd[i].double().cpu() - ref).abs().max())
         line = f"{dtype} hd={hd} len={n}: {diff} of {alone.numel()} elements differ in bits from the sequence alone; |out - fp64|max {err:.2e}"
+        r2 = 0.0
         if dtype in ("f16", "bf16"):
             r64, bound = AB.reference_of(seqs[i][None], H, dtype)
             r, where = AB.ratio(fwd[i][None], r64, bound)
-            line += f"; err / bound {r:.3f}"
-        print(line)
+        elif dtype == "f32m":                                 # tf_attn_f32m: tests/tf_attn_f32m_bound.py, both assertions
+            r, where, r2 = FB.verdict(fwd[i][None], FB.reference_of(seqs[i][None], H))
+        else:                                                 # the row kernel over the contiguous keys 0 .. n - 1
+            r64, bound = MB.reference_of(seqs[i][None], MB.make_allowed("clear", n), H, "f32")
+            r, where = MB.ratio(fwd[i][None], r64, bound)
+        print(line + f"; err / bound {r:.3f}" + (f"; relL2 / yardstick {r2:.3f}" if dtype == "f32m" else ""))
         assert diff == 0                                      # (b)
         if dtype in ("f16", "bf16"):
             assert r <= 1.0, (n, where)                       # (c) (the generic kernel keeps float32 probabilities: inside the same bound)
         else:
             assert err < 2e-4                                 # (d)
+            assert r <= 1.0 and r2 <= 1.0, (n, where)         # ... and every element within its derived bound
     rev = run(list(range(len(LENGTHS)))[::-1])
     for i in range(len(LENGTHS)):
         assert torch.equal(_bits(rev[i]), _bits(fwd[i])), f"sequence {i} depends on its place in the batch"      # (f)
