@@ -50,6 +50,9 @@
 // stepped by an association only the device knows (the device tracker's): tf_stream_feed_kernel turns it into the step's table and the
 // token rows by the rule of tf_stream_feed.h, the step's launch sequence runs for every row at smax = window, tf_feed_fill_bias writes
 // out_layer's bias into the rows that fed nothing.
+// Option skinny = 1 (16-bit handles): a linear that would run tf_gemm_mfma on 1 .. 32 rows runs tf_gemm_skinny -- one wave
+// per 16-row feature tile of the same packed image, the operands from global memory straight into registers, the same MFMAs over the
+// same operands in the same order: tf_gemm_mfma's bits (the planner is tf_skinny_plan.h).  Every caller of launch_linear takes it.
 #include "../../include/flope_amd.h"
 #include "common.h"
 #include "host_pack.h"
@@ -57,6 +60,7 @@
 #include "tf_attn_mask.h"
 #include "tf_encoder_stream.h"
 #include "tf_fused_plan.h"
+#include "tf_skinny_plan.h"
 #include "tf_stream_feed.h"
 
 #include <math.h>
@@ -1144,6 +1148,94 @@ __global__ __launch_bounds__(256, 2) void tf_gemm_mfma(const T* __restrict__ X, 
 #endif
 }
 
+// ---- skinny MFMA linear: at most 32 tokens, one wave per 16-row feature tile of tf_gemm_mfma's packed image (option "skinny") ----
+// tf_gemm_mfma gives 1 .. 32 rows ceil(M / 128) N / 128 = 3 .. 12 workgroups at cfg5, each pushing a 128-row token tile through a
+// barrier-stepped LDS ring.  Here a wave owns one feature tile (tf_skinny_plan.h: 16 rows of the image, the A operand of one MFMA) and the
+// MT token tiles of 16 rows: N / 16 waves, each in a workgroup of its own.  A lane loads its A and B fragments from global memory as 16-byte
+// vectors into a register ring of kTfSkinnyDepth chunks, refilled as the MFMAs drain it -- no LDS, no barrier, no word between waves.
+// An output element is what it is in tf_gemm_mfma, operation for operation: the accumulator starts at the bias, takes one
+// v_mfma_f32_16x16x32 per 32 k with the same 16 feature rows as A and its token in the same column of B, chunks ascending and ks = 0, 1
+// inside a chunk, then residual, 16-bit pack, ReLU.  The same bits, so the option changes no result.
+// Reads token and residual rows 0 .. 16 MT - 1 (inside the roundup(rows, 128) rows every caller allocates) and writes those rows of Y only.
+template <typename T, bool RELU, bool RES, int MT>
+__global__ __launch_bounds__(64 * flope_tf_plan::kTfSkinnyWaves) void tf_gemm_skinny(const T* __restrict__ X, const void* __restrict__ Wp,
+                                                                                     const float* __restrict__ bias, const T* __restrict__ res,
+                                                                                     T* __restrict__ Y, int K, int N) {
+  typedef typename Elem<T>::frag frag;
+  constexpr int D = flope_tf_plan::kTfSkinnyDepth;
+  const int lane = threadIdx.x & 63, nch = K >> 6;
+  const int ft = flope_tf_plan::tf_skinny_tile(blockIdx.x, threadIdx.x >> 6);
+  const char* wsrc = (const char*)Wp + flope_tf_plan::tf_skinny_w_off(ft, 0, 0, lane, nch);
+  const int wks = (int)flope_tf_plan::tf_skinny_w_off(ft, 0, 1, lane, nch) - (int)flope_tf_plan::tf_skinny_w_off(ft, 0, 0, lane, nch);
+  const char* xsrc[MT];
+#pragma unroll
+  for (int tt = 0; tt < MT; ++tt) xsrc[tt] = (const char*)X + flope_tf_plan::tf_skinny_x_off(tt, 0, 0, lane, K);
+  const int n0 = flope_tf_plan::tf_skinny_feature(ft, lane);
+
+  f32x4 acc[MT];
+  {
+    const f32x4 bv = *(const f32x4*)(bias + n0);
+#pragma unroll
+    for (int tt = 0; tt < MT; ++tt) acc[tt] = bv;
+  }
+
+  frag wf[D][2], xf[D][MT][2];
+  // chunk c_ into ring slot i_: a chunk is 16384 bytes of the image further and 128 bytes along a token row, ks = 1 is 64 bytes along the
+  // token row and wks bytes along the (swizzled) image row
+#define TF_SK_LOAD(i_, c_)                                                                        \
+  do {                                                                                            \
+    wf[i_][0] = *(const frag*)(wsrc + (size_t)(c_) * 16384);                                      \
+    wf[i_][1] = *(const frag*)(wsrc + (size_t)(c_) * 16384 + wks);                                \
+    _Pragma("unroll") for (int tt = 0; tt < MT; ++tt) {                                           \
+      xf[i_][tt][0] = *(const frag*)(xsrc[tt] + (size_t)(c_) * 128);                              \
+      xf[i_][tt][1] = *(const frag*)(xsrc[tt] + (size_t)(c_) * 128 + 64);                         \
+    }                                                                                             \
+  } while (0)
+
+#pragma unroll
+  for (int i = 0; i < D; ++i)
+    if (i < nch) TF_SK_LOAD(i, i);
+#define TF_SK_MFMA(i_)                                                                            \
+  _Pragma("unroll") for (int ks = 0; ks < 2; ++ks)                                                \
+    _Pragma("unroll") for (int tt = 0; tt < MT; ++tt) acc[tt] = Elem<T>::mfma(wf[i_][ks], xf[i_][tt][ks], acc[tt])
+  int c0 = 0;
+  for (; c0 + 2 * D <= nch; c0 += D) {             // a whole turn of the ring with every refill in range: straight-line code, no test per slot
+#pragma unroll
+    for (int i = 0; i < D; ++i) {
+      TF_SK_MFMA(i);
+      TF_SK_LOAD(i, c0 + i + D);
+    }
+  }
+  for (; c0 < nch; c0 += D) {                      // the last one or two turns: chunks and refills that end at nch
+#pragma unroll
+    for (int i = 0; i < D; ++i) {
+      const int c = c0 + i;
+      if (c < nch) {
+        TF_SK_MFMA(i);
+        if (c + D < nch) TF_SK_LOAD(i, c + D);
+      }
+    }
+  }
+#undef TF_SK_MFMA
+#undef TF_SK_LOAD
+
+#pragma unroll
+  for (int tt = 0; tt < MT; ++tt) {
+    const size_t off = (size_t)flope_tf_plan::tf_skinny_x_row(tt, lane) * N + n0;
+    float v[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) v[q] = acc[tt][q];
+    if constexpr (RES) {
+      const u32x2 r = *(const u32x2*)(res + off);
+      v[0] += unpack_lo<T>(r[0]); v[1] += unpack_hi<T>(r[0]);
+      v[2] += unpack_lo<T>(r[1]); v[3] += unpack_hi<T>(r[1]);
+    }
+    u32x2 o = {pack2<T>(v[0], v[1]), pack2<T>(v[2], v[3])};
+    if constexpr (RELU) { o[0] = pk_relu16(o[0]); o[1] = pk_relu16(o[1]); }
+    *(u32x2*)(Y + off) = o;
+  }
+}
+
 // ---- MFMA attention, 16-bit: head_dim 64 with the keys resident (tf_attn_mfma), head_dim 32 HD32 with the keys streamed (tf_attn_tiled) ----
 // A wave owns 32 queries of one (batch, head), Q fragments in registers, and walks the keys 32 at a time in ascending order, K and V
 // rows of the step in LDS images (row-major [key][head_dim], rows of RB = 64 HD32 bytes).  One 32-key step (tf_attn16_step):
@@ -2168,7 +2260,8 @@ struct flope_tf_encoder {
   int last_masked_attn = -1;                 // FLOPE_TF_ATTN_* id of the attention launches of the last flope_tf_forward_masked that enqueued anything (flope_tf_last_forward_masked), -1: none yet
   int last_fwd = FLOPE_TF_FWD_LAUNCHES;       // what the last forward that enqueued anything ran (flope_tf_last_forward)
   const float** fused_tab = nullptr;         // device table of the float32 weight arrays tf_fused_f32 reads (FLOPE_DT_F32 handles, built by flope_tf_load_weights)
-  int opt_f32m_lds = 0;                      // KiB of untouched LDS a tf_linear_f32m launch reserves (> 80: one workgroup per CU)
+  int opt_skinny = 0;                        // 1: a linear that would run tf_gemm_mfma on 1 .. 32 rows runs tf_gemm_skinny, the same bits (stored and ignored by float32 handles)
+  int opt_f32m_lds = 0;                     // KiB of untouched LDS a tf_linear_f32m launch reserves (> 80: one workgroup per CU)
   int cus = 256;
   bool loaded = false;
   TfLinear emb, outl;
@@ -2292,12 +2385,14 @@ template <typename V> int tf_upload(flope_tf_encoder* e, const V* src, size_t co
 
 // One linear under the handle's options; returns the FLOPE_TF_LIN_* id of the kernel launched, or < 0.  The 16-bit vector paths
 // (tf_gemm_mfma, tf_linear_rowwave_vec) take X, R and Y 16-byte aligned and, tf_gemm_mfma, allocated for whole 128-row tiles: true of
-// the handle's own buffers, checked for a caller's by flope_tf_linear.
+// the handle's own buffers, checked for a caller's by flope_tf_linear.  plan: nothing is launched and no buffer is read -- the id alone,
+// by the same tests (flope_tf_linear_plan; X, R and Y are then looked at for NULL and alignment only).
 template <typename T>
 int launch_linear(flope_tf_encoder* e, const TfLinear& l, const void* X, int x_f32, const void* R, void* Y, int y_f32,
-                  int M, int relu, hipStream_t st) {
+                  int M, int relu, hipStream_t st, bool plan = false) {
   if constexpr (std::is_same<T, float>::value) {
     if (e->opt_f32m && l.pk32 && !(((uintptr_t)X | (uintptr_t)Y | (uintptr_t)R) & 15)) {
+      if (plan) return relu && R ? tf_fail(e, FLOPE_EINVAL, "tf_linear_f32m: no ReLU + residual form") : FLOPE_TF_LIN_F32M;
       const size_t lds = (size_t)e->opt_f32m_lds * 1024;
       const int mp = tf_f32m_mp(M, l.N, e->cus * (lds > 80 * 1024 ? 1 : 2)), nsteps = tf_f32m_steps(l.K);
       const dim3 grid((unsigned)((M + 64 * mp - 1) / (64 * mp) * ((l.N + 63) / 64)));
@@ -2314,10 +2409,25 @@ int launch_linear(flope_tf_encoder* e, const TfLinear& l, const void* X, int x_f
   }
   if (l.packed && !y_f32 && !e->opt_generic) {
     if constexpr (!std::is_same<T, float>::value) {
+      const bool skinny = flope_tf_plan::tf_skinny_ok(1, e->opt_skinny, e->opt_generic, l.packed != nullptr, y_f32, M);
+      if (plan) return skinny ? FLOPE_TF_LIN_SKINNY : FLOPE_TF_LIN_MFMA;
       if (x_f32) {                                   // network input: fp32 [M][K] -> 16-bit [M][Kp]
         const size_t tot = (size_t)M * l.Kp;
         hipLaunchKernelGGL((tf_cast_pad<T>), dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, (const float*)X, (T*)e->xin, M, l.K, l.Kp);
         X = e->xin;
+      }
+      if (skinny) {                                  // option "skinny", 1 .. 32 rows: a wave per 16-row feature tile, tf_gemm_mfma's bits
+        const int MT = flope_tf_plan::tf_skinny_mt(M);
+        const flope_tf_plan::TfSkinnyLaunch sl = flope_tf_plan::tf_skinny_launch(l.N, MT);
+#define TF_SK(RELU_, RES_, MT_)                                                                                              \
+  hipLaunchKernelGGL((tf_gemm_skinny<T, RELU_, RES_, MT_>), dim3(sl.grid), dim3(sl.block), 0, st, (const T*)X, l.packed, l.b, \
+                     (const T*)R, (T*)Y, l.Kp, l.N)
+#define TF_SK2(RELU_, RES_) do { if (MT == 1) TF_SK(RELU_, RES_, 1); else TF_SK(RELU_, RES_, 2); } while (0)
+        if (relu && R) TF_SK2(true, true); else if (relu) TF_SK2(true, false); else if (R) TF_SK2(false, true); else TF_SK2(false, false);
+#undef TF_SK2
+#undef TF_SK
+        TF_HIP(e, hipGetLastError());
+        return FLOPE_TF_LIN_SKINNY;
       }
       const int grid = ((M + 127) / 128) * (l.N / 128);
       const size_t lds = 65536;
@@ -2332,6 +2442,7 @@ int launch_linear(flope_tf_encoder* e, const TfLinear& l, const void* X, int x_f
   }
   if constexpr (!std::is_same<T, float>::value) {
     if (l.N <= 16 && !R && !x_f32 && l.K % 8 == 0 && (size_t)l.N * l.K * 4 <= 48 * 1024) {
+      if (plan) return FLOPE_TF_LIN_ROWWAVE_VEC;
       const int blocks = (M + 7) / 8 < 2048 ? (M + 7) / 8 : 2048;
       hipLaunchKernelGGL((tf_linear_rowwave_vec<T>), dim3(blocks), dim3(256), (size_t)l.N * l.K * 4, st, (const T*)X, l.w, l.b, Y, y_f32, M, l.K, l.N, relu);
       TF_HIP(e, hipGetLastError());
@@ -2339,11 +2450,13 @@ int launch_linear(flope_tf_encoder* e, const TfLinear& l, const void* X, int x_f
     }
   }
   if (l.N <= 16 && !R) {
+    if (plan) return FLOPE_TF_LIN_ROWWAVE;
     const int blocks = (M + 3) / 4 < 8192 ? (M + 3) / 4 : 8192;
     hipLaunchKernelGGL((tf_linear_rowwave<T>), dim3(blocks), dim3(256), 0, st, X, x_f32, l.w, l.b, Y, y_f32, M, l.K, l.N, relu);
     TF_HIP(e, hipGetLastError());
     return FLOPE_TF_LIN_ROWWAVE;
   }
+  if (plan) return FLOPE_TF_LIN_GENERIC;
   const size_t total = (size_t)M * l.N;
   hipLaunchKernelGGL((tf_linear_generic<T>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, X, x_f32, l.w, l.b,
                      R, Y, y_f32, M, l.K, l.N, relu);
@@ -2724,6 +2837,10 @@ extern "C" int flope_tf_set_option(flope_tf_handle e, const char* name, int valu
     if (value < 0 || value > 1) return tf_fail(e, FLOPE_EINVAL, "flope_tf_set_option: step_split is 0 or 1");
     const int old = e->opt_step_split; e->opt_step_split = value; return old;
   }
+  if (!strcmp(name, "skinny")) {
+    if (value < 0 || value > 1) return tf_fail(e, FLOPE_EINVAL, "flope_tf_set_option: skinny is 0 or 1");
+    const int old = e->opt_skinny; e->opt_skinny = value; return old;
+  }
   if (!strcmp(name, "extend_mfma")) {
     if (value < 0 || value > 1) return tf_fail(e, FLOPE_EINVAL, "flope_tf_set_option: extend_mfma is 0 or 1");
     const int old = e->opt_extend_mfma; e->opt_extend_mfma = value; return old;
@@ -2843,23 +2960,25 @@ extern "C" int flope_tf_attention(flope_tf_handle e, const void* qkv_dev, int ba
   });
 }
 
+// the loaded linear a name of flope_tf_linear / flope_tf_linear_plan means, or nullptr
+static const TfLinear* tf_find_linear(const flope_tf_encoder* e, const std::string& nm) {
+  if (nm == "embedding") return &e->emb;
+  if (nm == "out_layer") return &e->outl;
+  if (nm.compare(0, 7, "layers.") != 0) return nullptr;
+  const size_t dot = nm.find('.', 7);
+  const std::string idx = dot == std::string::npos ? "" : nm.substr(7, dot - 7), op = dot == std::string::npos ? "" : nm.substr(dot + 1);
+  if (idx.empty() || idx.size() > 6 || idx.find_first_not_of("0123456789") != std::string::npos || std::stoi(idx) >= e->nl) return nullptr;
+  const TfLayer& ly = e->layers[std::stoi(idx)];
+  return op == "in_proj" ? &ly.in_proj : op == "out_proj" ? &ly.out_proj : op == "linear1" ? &ly.lin1 : op == "linear2" ? &ly.lin2 : nullptr;
+}
+
 extern "C" int flope_tf_linear(flope_tf_handle e, const char* name, const void* x_dev, int x_f32, const void* res_dev, void* y_dev, int y_f32, int rows,
                                int relu, void* stream) {
   if (!e) return tf_fail(nullptr, FLOPE_EINVAL, "flope_tf_linear: NULL handle");
   if (!e->loaded) return tf_fail(e, FLOPE_ESTATE, "flope_tf_linear: weights not loaded");
   if (!name || !x_dev || !y_dev) return tf_fail(e, FLOPE_EINVAL, "flope_tf_linear: NULL argument");
-  const TfLinear* l = nullptr;
   const std::string nm(name);
-  if (nm == "embedding") l = &e->emb;
-  else if (nm == "out_layer") l = &e->outl;
-  else if (nm.compare(0, 7, "layers.") == 0) {
-    const size_t dot = nm.find('.', 7);
-    const std::string idx = dot == std::string::npos ? "" : nm.substr(7, dot - 7), op = dot == std::string::npos ? "" : nm.substr(dot + 1);
-    if (!idx.empty() && idx.size() <= 6 && idx.find_first_not_of("0123456789") == std::string::npos && std::stoi(idx) < e->nl) {
-      const TfLayer& ly = e->layers[std::stoi(idx)];
-      l = op == "in_proj" ? &ly.in_proj : op == "out_proj" ? &ly.out_proj : op == "linear1" ? &ly.lin1 : op == "linear2" ? &ly.lin2 : nullptr;
-    }
-  }
+  const TfLinear* l = tf_find_linear(e, nm);
   if (!l) return tf_fail(e, FLOPE_EINVAL, "flope_tf_linear: unknown linear " + nm + " (embedding, out_layer, layers.<i>.in_proj / out_proj / linear1 / linear2)");
   if (rows < 1) return tf_fail(e, FLOPE_EINVAL, "flope_tf_linear: non-positive rows");
   if (rows > e->max_tokens) return tf_fail(e, FLOPE_EINVAL, "flope_tf_linear: rows exceeds max_tokens given to flope_tf_create");
@@ -2880,6 +2999,26 @@ extern "C" int flope_tf_linear(flope_tf_handle e, const char* name, const void* 
     using T = typename decltype(tag)::type;
     constexpr bool f32 = std::is_same<T, float>::value;                // a float32 handle's buffers are float32 whatever the flags say
     return launch_linear<T>(e, *l, x_dev, f32 || x_f32 ? 1 : 0, res_dev, y_dev, f32 || y_f32 ? 1 : 0, rows, relu ? 1 : 0, (hipStream_t)stream);
+  });
+}
+
+// The id flope_tf_linear returns for this linear at this row count in the form the forward runs it -- embedding: float32 in; out_layer:
+// float32 out; out_proj and linear2: with a residual; linear1: with ReLU -- under the handle's current options; launches nothing.
+extern "C" int flope_tf_linear_plan(flope_tf_handle e, const char* name, int rows) {
+  if (!e) return tf_fail(nullptr, FLOPE_EINVAL, "flope_tf_linear_plan: NULL handle");
+  if (!e->loaded) return tf_fail(e, FLOPE_ESTATE, "flope_tf_linear_plan: weights not loaded");
+  if (!name) return tf_fail(e, FLOPE_EINVAL, "flope_tf_linear_plan: NULL argument");
+  const std::string nm(name);
+  const TfLinear* l = tf_find_linear(e, nm);
+  if (!l) return tf_fail(e, FLOPE_EINVAL, "flope_tf_linear_plan: unknown linear " + nm + " (embedding, out_layer, layers.<i>.in_proj / out_proj / linear1 / linear2)");
+  if (rows < 1) return tf_fail(e, FLOPE_EINVAL, "flope_tf_linear_plan: non-positive rows");
+  if (rows > e->max_tokens) return tf_fail(e, FLOPE_EINVAL, "flope_tf_linear_plan: rows exceeds max_tokens given to flope_tf_create");
+  const bool res = nm.size() > 9 && (nm.compare(nm.size() - 9, 9, ".out_proj") == 0 || nm.compare(nm.size() - 8, 8, ".linear2") == 0);
+  const bool relu = nm.size() > 8 && nm.compare(nm.size() - 8, 8, ".linear1") == 0;
+  void* const any = (void*)(uintptr_t)16;          // an aligned non-NULL pointer: plan mode looks at NULL and alignment only
+  return tf_by_dtype(e, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    return launch_linear<T>(e, *l, any, l == &e->emb ? 1 : 0, res ? any : nullptr, any, l == &e->outl ? 1 : 0, rows, relu ? 1 : 0, nullptr, true);
   });
 }
 

@@ -18,6 +18,8 @@ An additive float mask -- torch's `mask=` with values other than -inf / 0, one [
 `enc.make_bias(bias)` and passed the same way; `alibi_bias(L, slopes)` builds the distance bias this encoder, which has no positional
 term, needs to tell the order of the poses behind a query.  A 16-bit encoder made with `bias_mfma=1` runs attention
 under a compiled bias on the MFMA attention step over the tile map of the bias's allowed set.
+A 16-bit encoder made with `skinny=1` runs every MFMA linear of 1 .. 32 rows -- a live step, a short extend, prefill or forward -- with one
+wave per 16-row feature tile instead of a few 128-row workgroups: the same bits, another launch shape.
 
 Eval-mode semantics only (dropout is identity), as everywhere in this package.  There is no CPU
 path: construction fails loudly without a HIP device or without the built library.
@@ -209,7 +211,7 @@ def distance_bias(table, L, window=0):
 class TransformerEncoder:
     def __init__(self, input_dim, model_dim, out_dim, num_heads, num_layers, ff_dim, dropout=0.1,
                  dtype="f32", max_tokens=4096, device=None, attn_tiled=0, fused=0, window_mfma=0, step_split=0, extend_mfma=0,
-                 mask_mfma=0, bias_mfma=0):
+                 mask_mfma=0, bias_mfma=0, skinny=0):
         _require_gpu()
         self.lib = _lib.load()
         self.device = torch.device(device if device is not None else "cuda:0")
@@ -270,6 +272,11 @@ class TransformerEncoder:
             if rc < 0:
                 self.close()
                 raise ValueError(f"bias_mfma must be 0 or 1 (got {bias_mfma!r})")
+        if skinny:                               # 16-bit handles: an MFMA linear of 1 .. 32 rows runs one wave per 16-row feature tile, the same bits (0 or 1, include/flope_amd.h)
+            rc = self.lib.flope_tf_set_option(self.handle, b"skinny", int(skinny))
+            if rc < 0:
+                self.close()
+                raise ValueError(f"skinny must be 0 or 1 (got {skinny!r})")
 
     def _check(self, rc):
         if rc:
@@ -301,7 +308,7 @@ class TransformerEncoder:
             self._check(self.lib.flope_tf_load_weights(self.handle, n, names, ptrs, ndims, shapes))
 
     def set_option(self, name: str, value: int) -> int:
-        if name in ("step_split", "extend_mfma", "mask_mfma", "bias_mfma"):    # the newer options raise on a refused value (the others keep returning the code)
+        if name in ("step_split", "extend_mfma", "mask_mfma", "bias_mfma", "skinny"):    # the newer options raise on a refused value (the others keep returning the code)
             rc = self.lib.flope_tf_set_option(self.handle, name.encode(), int(value))
             self._check_arg(rc)
             return rc
@@ -585,6 +592,15 @@ class TransformerEncoder:
         self.last_linear_kernel = rc
         self._keep = (x, res)
         return out
+
+    def linear_plan(self, name, rows):
+        """The FLOPE_TF_LIN_* id linear() would launch for the loaded linear `name` at `rows` rows under the current options, in the form
+        a forward runs it (embedding: float32 in; out_layer: float32 out; out_proj / linear2: with a residual; linear1: with ReLU).
+        Launches nothing."""
+        self._linear_dims(name)
+        rc = self.lib.flope_tf_linear_plan(self.handle, name.encode(), int(rows))
+        self._check_arg(rc)
+        return rc
 
     def layernorm(self, x, weight, bias, out=None):
         """LayerNorm (eps 1e-5, biased variance) of x [rows, model_dim] in the handle's dtype with device float32 weight / bias

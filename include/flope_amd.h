@@ -489,7 +489,17 @@ int flope_tf_forward(flope_tf_handle h, const float* x_dev, int batch, int seq_l
  *       too long for tf_attn_masked's score rows is accepted where the pick is 7.  The bias entry of a masked pair may be LOADED
  *       (it is -inf) and is never USED; a key that no query of the sequence allows is never read into a product, as under
  *       "mask_mfma", with the same rule for a NaN key that some query of a 128-row block allows.  Read when a call enqueues; every
- *       bias carries its tile map on the device behind its planes, a forward builds and allocates nothing. */
+ *       bias carries its tile map on the device behind its planes, a forward builds and allocates nothing;
+ *   "skinny" (default 0; 0 or 1, FLOPE_EINVAL outside; returns the old value; stored and ignored by float32 handles): 1 = a linear
+ *       that would run tf_gemm_mfma (FLOPE_TF_LIN_MFMA) on 1 .. 32 rows runs tf_gemm_skinny instead (FLOPE_TF_LIN_SKINNY = 5;
+ *       DESIGN.md 48): one wave per 16-row feature tile of the same packed weights (N / 16 workgroups of 64 lanes where tf_gemm_mfma
+ *       has N / 128 of 256), the operands loaded from global memory straight into registers, no LDS.  Each output element takes the
+ *       same MFMAs over the same operands in the same order, so rows < `rows` hold tf_gemm_mfma's BITS: the option changes no result
+ *       of any call.  Every caller of a linear takes it with no setting of its own: flope_tf_forward* at batch * seq_len <= 32,
+ *       flope_tf_stream_step / _step_assoc / _step_tracker / _extend / _prefill at that many rows, flope_tf_linear.  Reads token and
+ *       residual rows 0 .. 15 (rows <= 16) or 0 .. 31 only, which lie inside the roundup(rows, 128) rows tf_gemm_mfma requires, and
+ *       writes those rows only: rows `rows` .. 15 / 31 of the result may hold anything, as under 0, later rows are left alone.  More
+ *       than 32 rows, option "generic", float32 results and unpacked linears keep their kernel.  Read when a call enqueues. */
 int flope_tf_set_option(flope_tf_handle h, const char* name, int value);
 /* softmax(q k^T / sqrt(head_dim)) v per head on a caller's buffer: qkv_dev [batch, seq_len, 3*model_dim] and out_dev
  * [batch, seq_len, model_dim] in the handle's dtype (float32 for FLOPE_DT_F32).  Launches exactly what flope_tf_forward
@@ -519,8 +529,14 @@ double flope_tf_forward_flops(flope_tf_handle h, int batch, int seq_len);
 #define FLOPE_TF_LIN_ROWWAVE_VEC  2   /* tf_linear_rowwave_vec: 16-bit input, N <= 16, K % 8 == 0, N K floats within 48 KiB of LDS */
 #define FLOPE_TF_LIN_MFMA         3   /* tf_gemm_mfma: 16-bit, N % 128 == 0, K % 64 == 0 (embedding: K zero-padded) */
 #define FLOPE_TF_LIN_F32M         4   /* tf_linear_f32m: float32, option f32mfma, K % 4 == 0 */
+#define FLOPE_TF_LIN_SKINNY       5   /* tf_gemm_skinny: option skinny, where tf_gemm_mfma would run on 1 .. 32 rows; its bits (rows 0 .. 15 / 31 touched only) */
 int flope_tf_linear(flope_tf_handle h, const char* name, const void* x_dev, int x_f32, const void* res_dev, void* y_dev, int y_f32,
                     int rows, int relu, void* stream);
+/* The FLOPE_TF_LIN_* id flope_tf_linear would return for linear `name` at `rows` rows under the handle's current options, in the form
+ * flope_tf_forward runs that linear: "embedding" with a float32 input, "out_layer" with a float32 result, ".out_proj" and ".linear2"
+ * with a residual, ".linear1" with ReLU, all buffers aligned.  Launches nothing and touches no buffer.  The same refusals: weights not
+ * loaded (FLOPE_ESTATE), an unknown name, rows < 1 or rows > max_tokens (FLOPE_EINVAL). */
+int flope_tf_linear_plan(flope_tf_handle h, const char* name, int rows);
 /* The LayerNorm flope_tf_forward runs for this handle's dtype and model_dim (eps 1e-5, biased variance) on a caller's buffers:
  * in_dev [rows, model_dim] -> out_dev [rows, model_dim] in the handle's dtype, gamma_dev / beta_dev device float32 [model_dim].
  * Needs no weights.  Returns the FLOPE_TF_LN_* id of the kernel, or < 0 and nothing launched.  rows <= max_tokens; 16-bit handles
