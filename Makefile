@@ -31,12 +31,13 @@ HARNESS_FRAME := tests/host_harness/libflope_host_frame.so
 HARNESS_TRACK := tests/host_harness/libflope_host_track.so
 HARNESS_TF_FEED := tests/host_harness/libflope_host_tf_feed.so
 HARNESS_TF_SKINNY := tests/host_harness/libflope_host_tf_skinny.so
+HARNESS_TF_SKINNY_LN := tests/host_harness/libflope_host_tf_skinny_ln.so
 SRCS    := $(wildcard $(CSRC)/*.hip)
 OBJS     := $(patsubst $(CSRC)/%.hip,$(OBJDIR)/%.o,$(SRCS))
 HDRS     := $(wildcard $(CSRC)/*.h) include/flope_amd.h
 HIPFLAGS := --offload-arch=$(ARCH) -O3 -fPIC -std=c++17 -Wno-unused-value -Iinclude
 
-all: $(LIB) $(HARNESS) $(HARNESS_F32M) $(HARNESS_F32M_KSPLIT) $(HARNESS_GUARD) $(HARNESS_TF_F32M) $(HARNESS_TF_ATTN) $(HARNESS_TF_VARLEN) $(HARNESS_TF_FUSED) $(HARNESS_TF_CAUSAL) $(HARNESS_TF_STREAM) $(HARNESS_TF_WINDOW) $(HARNESS_TF_WINDOW16) $(HARNESS_TF_EXTEND) $(HARNESS_TF_SPLIT) $(HARNESS_TF_EXTEND16) $(HARNESS_TF_MASK) $(HARNESS_TF_MASK16) $(HARNESS_TF_BIAS) $(HARNESS_TF_STREAM_BIAS) $(HARNESS_TF_BIAS16) $(HARNESS_DEPTH) $(HARNESS_CROP) $(HARNESS_FRAME) $(HARNESS_TRACK) $(HARNESS_TF_FEED) $(HARNESS_TF_SKINNY)
+all: $(LIB) $(HARNESS) $(HARNESS_F32M) $(HARNESS_F32M_KSPLIT) $(HARNESS_GUARD) $(HARNESS_TF_F32M) $(HARNESS_TF_ATTN) $(HARNESS_TF_VARLEN) $(HARNESS_TF_FUSED) $(HARNESS_TF_CAUSAL) $(HARNESS_TF_STREAM) $(HARNESS_TF_WINDOW) $(HARNESS_TF_WINDOW16) $(HARNESS_TF_EXTEND) $(HARNESS_TF_SPLIT) $(HARNESS_TF_EXTEND16) $(HARNESS_TF_MASK) $(HARNESS_TF_MASK16) $(HARNESS_TF_BIAS) $(HARNESS_TF_STREAM_BIAS) $(HARNESS_TF_BIAS16) $(HARNESS_DEPTH) $(HARNESS_CROP) $(HARNESS_FRAME) $(HARNESS_TRACK) $(HARNESS_TF_FEED) $(HARNESS_TF_SKINNY) $(HARNESS_TF_SKINNY_LN)
 
 $(OBJDIR)/%.o: $(CSRC)/%.hip $(HDRS)
 	@mkdir -p $(OBJDIR)
@@ -187,6 +188,14 @@ $(HARNESS_TF_FEED): tests/host_harness/harness_tf_feed.cpp $(CSRC)/tf_stream_fee
 $(HARNESS_TF_SKINNY): tests/host_harness/harness_tf_skinny.cpp $(CSRC)/tf_skinny_plan.h $(CSRC)/host_pack.h
 	g++ -O2 -fPIC -shared -std=c++17 -I$(CSRC) -o $@ $<
 
+# the planner of option skinny_ln (tf_skinny_plan.h, which tf_gemm_skinny_ln calls per lane): the eligibility rule, the summation order of
+# the statistics against tf_layernorm_vec's wave butterfly in float32 bit patterns (every product and sum rounded on its own: no
+# contraction), and a walk of a whole launch that checks the store of the post-norm rows (tests/test_tf_skinny_ln_host.py,
+# tests/test_gpu_tf_skinny_ln.py); the test also builds the file as a stand-alone program under AddressSanitizer + UBSan
+# (-DTF_SKINNY_LN_MAIN) and runs it as a child process
+$(HARNESS_TF_SKINNY_LN): tests/host_harness/harness_tf_skinny_ln.cpp $(CSRC)/tf_skinny_plan.h
+	g++ -O2 -ffp-contract=off -fPIC -shared -std=c++17 -I$(CSRC) -o $@ $<
+
 # the same host code under AddressSanitizer + UBSan (sanitizers run on the CPU build only):
 #   make asan-test      (builds the sanitized harness and runs tests/test_host.py against it; leak detection is off because the
 #                        interpreter's own libcrypto allocations are reported as leaks at exit)
@@ -208,7 +217,7 @@ dbg: $(DBGOBJS)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $(DBGDIR)/libflope_amd_dbg.so $(DBGOBJS)
 
 clean:
-	rm -rf build $(LIB) $(HARNESS) $(HARNESS_F32M) $(HARNESS_F32M_KSPLIT) $(HARNESS_GUARD) $(HARNESS_TF_F32M) $(HARNESS_TF_ATTN) $(HARNESS_TF_VARLEN) $(HARNESS_TF_FUSED) $(HARNESS_TF_CAUSAL) $(HARNESS_TF_STREAM) $(HARNESS_TF_WINDOW) $(HARNESS_TF_WINDOW16) $(HARNESS_TF_EXTEND) $(HARNESS_TF_SPLIT) $(HARNESS_TF_EXTEND16) $(HARNESS_TF_MASK) $(HARNESS_TF_MASK16) $(HARNESS_TF_BIAS) $(HARNESS_TF_STREAM_BIAS) $(HARNESS_TF_BIAS16) $(HARNESS_DEPTH) $(HARNESS_CROP) $(HARNESS_FRAME) $(HARNESS_TRACK) $(HARNESS_TF_FEED) $(HARNESS_TF_SKINNY)
+	rm -rf build $(LIB) $(HARNESS) $(HARNESS_F32M) $(HARNESS_F32M_KSPLIT) $(HARNESS_GUARD) $(HARNESS_TF_F32M) $(HARNESS_TF_ATTN) $(HARNESS_TF_VARLEN) $(HARNESS_TF_FUSED) $(HARNESS_TF_CAUSAL) $(HARNESS_TF_STREAM) $(HARNESS_TF_WINDOW) $(HARNESS_TF_WINDOW16) $(HARNESS_TF_EXTEND) $(HARNESS_TF_SPLIT) $(HARNESS_TF_EXTEND16) $(HARNESS_TF_MASK) $(HARNESS_TF_MASK16) $(HARNESS_TF_BIAS) $(HARNESS_TF_STREAM_BIAS) $(HARNESS_TF_BIAS16) $(HARNESS_DEPTH) $(HARNESS_CROP) $(HARNESS_FRAME) $(HARNESS_TRACK) $(HARNESS_TF_FEED) $(HARNESS_TF_SKINNY) $(HARNESS_TF_SKINNY_LN)
 
 # stand-alone measurement programs used by tools/collect_profiles.sh and DESIGN.md section 9 (not part of the library)
 TOOLBINS := build/fetch_calib build/launch_floor build/loop_probe build/loop_probe32 build/dma_issue_probe

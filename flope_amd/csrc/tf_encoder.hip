@@ -53,6 +53,9 @@
 // Option skinny = 1 (16-bit handles): a linear that would run tf_gemm_mfma on 1 .. 32 rows runs tf_gemm_skinny -- one wave
 // per 16-row feature tile of the same packed image, the operands from global memory straight into registers, the same MFMAs over the
 // same operands in the same order: tf_gemm_mfma's bits (the planner is tf_skinny_plan.h).  Every caller of launch_linear takes it.
+// Option skinny_ln = 1 (with skinny = 1): a LayerNorm of the forward directly in front of such a linear of K = model_dim
+// <= 512 is not launched; the linear runs as tf_gemm_skinny_ln, which normalises the rows in its token load by tf_layernorm_vec's own
+// definitions in its summation order and stores them: the bits of the two launches (run_forward_with: tf_ln_then_linear).
 #include "../../include/flope_amd.h"
 #include "common.h"
 #include "host_pack.h"
@@ -143,16 +146,47 @@ __device__ __forceinline__ void tf_rowwave_row(const void* X, int xld, int x_f32
     }
 }
 
-// LayerNorm of one row of d on one wave (eps 1e-5, biased variance)
+// LayerNorm (eps 1e-5, biased variance), one definition per expression: every LayerNorm kernel and tf_gemm_skinny_ln
+// call these, so a caller only decides which lane holds which elements and in which order the partial sums meet.
+// mean and 1 / std of a row of d from the row's sum and the sum of its squared deviations
+__device__ __forceinline__ float tf_ln_mean(float sum, int d) { return sum / d; }
+__device__ __forceinline__ float tf_ln_rstd(float sqsum, int d) { return 1.f / sqrtf(sqsum / d + 1e-5f); }
+// one element of the result
+__device__ __forceinline__ float tf_ln_elem(float x, float mean, float rstd, float w, float b) { return (x - mean) * rstd * w + b; }
+// a 16-byte vector of eight 16-bit elements: its sum onto s (s += lo + hi, q = 0 .. 3), ...
+template <typename T> __device__ __forceinline__ float tf_ln_vec_sum(const u32x4& r, float s) {
+#pragma unroll
+  for (int q = 0; q < 4; ++q) s += unpack_lo<T>(r[q]) + unpack_hi<T>(r[q]);
+  return s;
+}
+// ... its squared deviations onto v (one fmaf chain, hi then lo of q = 0 .. 3), ...
+template <typename T> __device__ __forceinline__ float tf_ln_vec_sq(const u32x4& r, float mean, float v) {
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const float a = unpack_lo<T>(r[q]) - mean, c = unpack_hi<T>(r[q]) - mean;
+    v = fmaf(a, a, fmaf(c, c, v));
+  }
+  return v;
+}
+// ... and its normalised elements, rounded to 16 bits: w and b are the eight columns of the vector
+template <typename T> __device__ __forceinline__ u32x4 tf_ln_vec_out(const u32x4& r, float mean, float rstd, const float* w, const float* b) {
+  u32x4 o;
+#pragma unroll
+  for (int q = 0; q < 4; ++q)
+    o[q] = pack2<T>(tf_ln_elem(unpack_lo<T>(r[q]), mean, rstd, w[q * 2], b[q * 2]), tf_ln_elem(unpack_hi<T>(r[q]), mean, rstd, w[q * 2 + 1], b[q * 2 + 1]));
+  return o;
+}
+
+// LayerNorm of one row of d on one wave
 template <typename T>
 __device__ __forceinline__ void tf_layernorm_row(const T* x, T* y, const float* w, const float* b, int d, int lane) {
   float s = 0.f;
   for (int c = lane; c < d; c += 64) s += to_f32<T>(x[c]);
-  const float mean = wave_sum(s) / d;
+  const float mean = tf_ln_mean(wave_sum(s), d);
   float v = 0.f;
   for (int c = lane; c < d; c += 64) { const float t = to_f32<T>(x[c]) - mean; v = fmaf(t, t, v); }
-  const float rstd = 1.f / sqrtf(wave_sum(v) / d + 1e-5f);
-  for (int c = lane; c < d; c += 64) y[c] = from_f32<T>((to_f32<T>(x[c]) - mean) * rstd * w[c] + b[c]);
+  const float rstd = tf_ln_rstd(wave_sum(v), d);
+  for (int c = lane; c < d; c += 64) y[c] = from_f32<T>(tf_ln_elem(to_f32<T>(x[c]), mean, rstd, w[c], b[c]));
 }
 
 // softmax(q k^T / sqrt(dh)) v for query i of one head on one wave.  base: the head's q columns of the sequence's first row, rows of
@@ -316,36 +350,20 @@ __global__ void tf_layernorm_vec(const T* in, T* out, const float* w, const floa
     const int c = lane + i * 64;
     if (c < nv) {
       r[i] = x[c];
-#pragma unroll
-      for (int q = 0; q < 4; ++q) s += unpack_lo<T>(r[i][q]) + unpack_hi<T>(r[i][q]);
+      s = tf_ln_vec_sum<T>(r[i], s);
     }
   }
-  const float mean = wave_sum(s) / d;
+  const float mean = tf_ln_mean(wave_sum(s), d);
   float v = 0.f;
 #pragma unroll
   for (int i = 0; i < 4; ++i)
-    if (lane + i * 64 < nv) {
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const float a = unpack_lo<T>(r[i][q]) - mean, c = unpack_hi<T>(r[i][q]) - mean;
-        v = fmaf(a, a, fmaf(c, c, v));
-      }
-    }
-  const float rstd = 1.f / sqrtf(wave_sum(v) / d + 1e-5f);
+    if (lane + i * 64 < nv) v = tf_ln_vec_sq<T>(r[i], mean, v);
+  const float rstd = tf_ln_rstd(wave_sum(v), d);
   u32x4* y = (u32x4*)(out + (size_t)row * d);
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
     const int c = lane + i * 64;
-    if (c < nv) {
-      u32x4 o;
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const int ch = c * 8 + q * 2;
-        o[q] = pack2<T>((unpack_lo<T>(r[i][q]) - mean) * rstd * w[ch] + b[ch],
-                        (unpack_hi<T>(r[i][q]) - mean) * rstd * w[ch + 1] + b[ch + 1]);
-      }
-      y[c] = o;
-    }
+    if (c < nv) y[c] = tf_ln_vec_out<T>(r[i], mean, rstd, w + c * 8, b + c * 8);
   }
 }
 
@@ -1233,6 +1251,137 @@ __global__ __launch_bounds__(64 * flope_tf_plan::kTfSkinnyWaves) void tf_gemm_sk
     u32x2 o = {pack2<T>(v[0], v[1]), pack2<T>(v[2], v[3])};
     if constexpr (RELU) { o[0] = pk_relu16(o[0]); o[1] = pk_relu16(o[1]); }
     *(u32x2*)(Y + off) = o;
+  }
+}
+
+// ---- ... with the LayerNorm in front of it inside its token load (option "skinny_ln") ----
+// Y = act(LayerNorm(X) W^T + b) and H = LayerNorm(X) in one launch, where tf_skinny_ln_ok: K = model_dim <= 64 kTfSkinnyDepth, so the
+// whole ring is loaded once and the four lanes (li, g) of token li hold its full pre-norm row, lane g the 16-byte vectors
+// 8 chunk + 4 ks + g.  A wave issues its token fragments and its weight fragments, and while the
+// weights are on their way turns the token fragments into the normalised, 16-bit-rounded row: per-vector partials by tf_layernorm_vec's
+// own definitions (tf_ln_vec_sum / _sq), summed in tf_layernorm_vec's wave_sum order -- the in-lane tree over the ring slots, then the
+// lanes at xor 32 and 16 (tf_skinny_plan.h) --, tf_ln_mean / tf_ln_rstd / tf_ln_vec_out.  The fragments then hold the bits
+// tf_layernorm_vec would have stored, and the MFMAs and the epilogue are tf_gemm_skinny's: the bits of the two launches.
+// Every wave normalises every token (no word between waves); wave ft < K / 64 also stores chunk ft of H.  Statistics stay inside the
+// four lanes of a token, so what rows M .. 16 MT - 1 of X hold reaches those rows of H and Y only.  X must not alias H or Y.
+// NCH = K / 64 is a template parameter of the wave's work: with the chunk count known, the ring, the tree and the rewrite are straight-line
+// code over registers (as a runtime value it put a merge of the whole ring behind every test: five times the instructions)
+template <typename T, bool RELU, int MT, int NCH>
+__device__ __forceinline__ void tf_skinny_ln_wave(const T* __restrict__ X, const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                  const void* __restrict__ Wp, const float* __restrict__ bias, T* __restrict__ H, T* __restrict__ Y, int N) {
+  using namespace flope_tf_plan;
+  typedef typename Elem<T>::frag frag;
+  constexpr int D = kTfSkinnyDepth, S = kTfSkinnyLnSlots;
+  constexpr int nch = NCH, K = 64 * NCH;         // constants: every test on a ring slot below is decided when the kernel is compiled
+  const int lane = threadIdx.x & 63;
+  const int ft = tf_skinny_tile(blockIdx.x, threadIdx.x >> 6);
+  const char* wsrc = (const char*)Wp + tf_skinny_w_off(ft, 0, 0, lane, nch);
+  const int wks = (int)tf_skinny_w_off(ft, 0, 1, lane, nch) - (int)tf_skinny_w_off(ft, 0, 0, lane, nch);
+  const int n0 = tf_skinny_feature(ft, lane);
+
+  // the whole ring at once, the tokens first: the statistics wait for them alone, the weights arrive under the arithmetic
+  u32x4 xr[MT][S];
+  frag wf[D][2];
+#pragma unroll
+  for (int i = 0; i < D; ++i)
+    if (i < nch) {
+#pragma unroll
+      for (int tt = 0; tt < MT; ++tt)
+#pragma unroll
+        for (int ks = 0; ks < 2; ++ks) xr[tt][tf_skinny_ln_slot(i, ks)] = *(const u32x4*)((const char*)X + tf_skinny_x_off(tt, i, ks, lane, K));
+    }
+#pragma unroll
+  for (int i = 0; i < D; ++i)
+    if (i < nch) {
+      wf[i][0] = *(const frag*)(wsrc + (size_t)i * 16384);
+      wf[i][1] = *(const frag*)(wsrc + (size_t)i * 16384 + wks);
+    }
+  f32x4 acc[MT];
+  {
+    const f32x4 bv = *(const f32x4*)(bias + n0);
+#pragma unroll
+    for (int tt = 0; tt < MT; ++tt) acc[tt] = bv;
+  }
+
+  float mean[MT], rstd[MT];
+#pragma unroll
+  for (int tt = 0; tt < MT; ++tt) {
+    float p[S];
+#pragma unroll
+    for (int sl = 0; sl < S; ++sl) {
+      p[sl] = 0.f;
+      if ((sl >> 1) < nch) p[sl] = tf_ln_vec_sum<T>(xr[tt][sl], 0.f);
+    }
+    float s = tf_skinny_ln_lane_tree(p);
+    s += __shfl_xor(s, tf_skinny_ln_lane_xor(0));
+    s += __shfl_xor(s, tf_skinny_ln_lane_xor(1));
+    mean[tt] = tf_ln_mean(s, K);
+#pragma unroll
+    for (int sl = 0; sl < S; ++sl) {
+      p[sl] = 0.f;
+      if ((sl >> 1) < nch) p[sl] = tf_ln_vec_sq<T>(xr[tt][sl], mean[tt], 0.f);
+    }
+    float v = tf_skinny_ln_lane_tree(p);
+    v += __shfl_xor(v, tf_skinny_ln_lane_xor(0));
+    v += __shfl_xor(v, tf_skinny_ln_lane_xor(1));
+    rstd[tt] = tf_ln_rstd(v, K);
+  }
+  // the fragments in place: a slot's eight gamma / beta columns (two 32-byte loads, the same for both token tiles) only while it is
+  // being rewritten -- all K of them at once would be 256 registers at K = 512
+#pragma unroll
+  for (int sl = 0; sl < S; ++sl)
+    if ((sl >> 1) < nch) {
+      const int col = tf_skinny_ln_col(sl >> 1, sl & 1, lane);
+      const f32x4 w0 = *(const f32x4*)(gamma + col), w1 = *(const f32x4*)(gamma + col + 4);
+      const f32x4 b0 = *(const f32x4*)(beta + col), b1 = *(const f32x4*)(beta + col + 4);
+      const float w8[8] = {w0[0], w0[1], w0[2], w0[3], w1[0], w1[1], w1[2], w1[3]};
+      const float b8[8] = {b0[0], b0[1], b0[2], b0[3], b1[0], b1[1], b1[2], b1[3]};
+#pragma unroll
+      for (int tt = 0; tt < MT; ++tt) xr[tt][sl] = tf_ln_vec_out<T>(xr[tt][sl], mean[tt], rstd[tt], w8, b8);
+    }
+
+  // H: this wave's chunk of the post-norm rows, from its own fragments (the test per slot keeps every register index a constant)
+  const int hc = tf_skinny_ln_h_chunk(ft, nch);
+#pragma unroll
+  for (int i = 0; i < D; ++i)
+    if (i == hc) {
+#pragma unroll
+      for (int tt = 0; tt < MT; ++tt)
+#pragma unroll
+        for (int ks = 0; ks < 2; ++ks) *(u32x4*)((char*)H + tf_skinny_ln_h_off(tt, i, ks, lane, K)) = xr[tt][tf_skinny_ln_slot(i, ks)];
+    }
+
+  // tf_gemm_skinny's MFMAs in its order: chunks ascending, ks = 0, 1 inside a chunk, the token tiles inside a ks
+#pragma unroll
+  for (int i = 0; i < D; ++i)
+    if (i < nch) {
+#pragma unroll
+      for (int ks = 0; ks < 2; ++ks)
+#pragma unroll
+        for (int tt = 0; tt < MT; ++tt)
+          acc[tt] = Elem<T>::mfma(wf[i][ks], __builtin_bit_cast(frag, xr[tt][tf_skinny_ln_slot(i, ks)]), acc[tt]);
+    }
+
+#pragma unroll
+  for (int tt = 0; tt < MT; ++tt) {
+    const size_t off = (size_t)tf_skinny_x_row(tt, lane) * N + n0;
+    u32x2 o = {pack2<T>(acc[tt][0], acc[tt][1]), pack2<T>(acc[tt][2], acc[tt][3])};
+    if constexpr (RELU) { o[0] = pk_relu16(o[0]); o[1] = pk_relu16(o[1]); }
+    *(u32x2*)(Y + off) = o;
+  }
+}
+
+template <typename T, bool RELU, int MT>
+__global__ __launch_bounds__(64 * flope_tf_plan::kTfSkinnyWaves) void tf_gemm_skinny_ln(const T* __restrict__ X, const float* __restrict__ gamma,
+                                                                                        const float* __restrict__ beta, const void* __restrict__ Wp,
+                                                                                        const float* __restrict__ bias, T* __restrict__ H,
+                                                                                        T* __restrict__ Y, int K, int N) {
+  static_assert(flope_tf_plan::kTfSkinnyDepth == 8, "one case per chunk count");
+  switch (K >> 6) {                                 // tf_skinny_ln_ok: 1 .. kTfSkinnyDepth
+#define TF_SKL_CASE(n_) case n_: tf_skinny_ln_wave<T, RELU, MT, n_>(X, gamma, beta, Wp, bias, H, Y, N); break
+    TF_SKL_CASE(1); TF_SKL_CASE(2); TF_SKL_CASE(3); TF_SKL_CASE(4); TF_SKL_CASE(5); TF_SKL_CASE(6); TF_SKL_CASE(7); TF_SKL_CASE(8);
+#undef TF_SKL_CASE
+    default: break;
   }
 }
 
@@ -2261,6 +2410,8 @@ struct flope_tf_encoder {
   int last_fwd = FLOPE_TF_FWD_LAUNCHES;       // what the last forward that enqueued anything ran (flope_tf_last_forward)
   const float** fused_tab = nullptr;         // device table of the float32 weight arrays tf_fused_f32 reads (FLOPE_DT_F32 handles, built by flope_tf_load_weights)
   int opt_skinny = 0;                        // 1: a linear that would run tf_gemm_mfma on 1 .. 32 rows runs tf_gemm_skinny, the same bits (stored and ignored by float32 handles)
+  int opt_skinny_ln = 0;                     // 1: a LayerNorm directly in front of a skinny linear of K = model_dim <= 512 runs inside that linear's launch (tf_gemm_skinny_ln), the bits of the two launches (stored and ignored where tf_skinny_ln_ok says no, option skinny at 0 included)
+  int last_ln_launched = 0, last_ln_folded = 0;   // the stand-alone LayerNorm launches of the last run_forward_with and the LayerNorms it folded (flope_tf_last_ln)
   int opt_f32m_lds = 0;                     // KiB of untouched LDS a tf_linear_f32m launch reserves (> 80: one workgroup per CU)
   int cus = 256;
   bool loaded = false;
@@ -2469,15 +2620,54 @@ template <typename T>
 int launch_layernorm(flope_tf_encoder* e, const void* in, void* out, const float* w, const float* b, int M, hipStream_t st) {
   const int d = e->d;
   int id = FLOPE_TF_LN_SCALAR;
-  if constexpr (!std::is_same<T, float>::value) {
-    if (d % 8 == 0 && d <= 2048) id = FLOPE_TF_LN_VEC;
-  }
+  if (flope_tf_plan::tf_ln_vec_ok(!std::is_same<T, float>::value, d)) id = FLOPE_TF_LN_VEC;
   if constexpr (!std::is_same<T, float>::value) {
     if (id == FLOPE_TF_LN_VEC) hipLaunchKernelGGL((tf_layernorm_vec<T>), dim3((M + 3) / 4), dim3(256), 0, st, (const T*)in, (T*)out, w, b, M, d);
   }
   if (id == FLOPE_TF_LN_SCALAR) hipLaunchKernelGGL((tf_layernorm<T>), dim3((M + 3) / 4), dim3(256), 0, st, (const T*)in, (T*)out, w, b, M, d);
   TF_HIP(e, hipGetLastError());
   return id;
+}
+
+// Whether a LayerNorm over model_dim directly in front of linear l on M rows runs inside the linear's launch (option "skinny_ln";
+// tf_skinny_plan.h: tf_skinny_ln_ok).  The consumer's form has no residual and a 16-bit result.
+template <typename T>
+bool tf_linear_ln_ok(const flope_tf_encoder* e, const TfLinear& l, int M) {
+  if (std::is_same<T, float>::value) return false;
+  return flope_tf_plan::tf_skinny_ln_ok(flope_tf_plan::tf_skinny_ok(1, e->opt_skinny, e->opt_generic, l.packed != nullptr, 0, M), e->opt_skinny_ln, l.K, l.Kp, e->d);
+}
+
+// H = LayerNorm(X; gamma, beta), Y = act(H W^T + b) in the one launch of tf_gemm_skinny_ln; the caller has asked tf_linear_ln_ok.
+// X, H: [roundup(M, 16)][model_dim] at least, Y the same rows of N; X aliases neither.  Returns FLOPE_TF_LIN_SKINNY_LN, or < 0.
+template <typename T>
+int launch_linear_ln(flope_tf_encoder* e, const TfLinear& l, const void* X, const float* gamma, const float* beta, void* H, void* Y, int M, int relu,
+                     hipStream_t st) {
+  if constexpr (!std::is_same<T, float>::value) {
+    const int MT = flope_tf_plan::tf_skinny_mt(M);
+    const flope_tf_plan::TfSkinnyLaunch sl = flope_tf_plan::tf_skinny_launch(l.N, MT);
+#define TF_SKL(RELU_, MT_)                                                                                                           \
+  hipLaunchKernelGGL((tf_gemm_skinny_ln<T, RELU_, MT_>), dim3(sl.grid), dim3(sl.block), 0, st, (const T*)X, gamma, beta, l.packed, l.b, \
+                     (T*)H, (T*)Y, l.Kp, l.N)
+    if (relu) { if (MT == 1) TF_SKL(true, 1); else TF_SKL(true, 2); } else { if (MT == 1) TF_SKL(false, 1); else TF_SKL(false, 2); }
+#undef TF_SKL
+    TF_HIP(e, hipGetLastError());
+    return FLOPE_TF_LIN_SKINNY_LN;
+  }
+  return tf_fail(e, FLOPE_EINVAL, "tf_gemm_skinny_ln: 16-bit handles only");
+}
+
+// e->h = LayerNorm(e->h2; w, b), then Y = act(linear l of e->h): the pair as it stands in the forward -- one launch where
+// tf_linear_ln_ok, the two launches otherwise.  Counts into the handle's last_ln_*.
+template <typename T>
+int tf_ln_then_linear(flope_tf_encoder* e, const float* w, const float* b, const TfLinear& l, void* Y, int M, int relu, hipStream_t st) {
+  int rc;
+  if (tf_linear_ln_ok<T>(e, l, M)) {
+    ++e->last_ln_folded;
+    return launch_linear_ln<T>(e, l, e->h2, w, b, e->h, Y, M, relu, st);
+  }
+  ++e->last_ln_launched;
+  if ((rc = launch_layernorm<T>(e, e->h2, e->h, w, b, M, st)) < 0) return rc;
+  return launch_linear<T>(e, l, e->h, 0, nullptr, Y, 0, M, relu, st);
 }
 
 // One attention launch: softmax(q k^T / sqrt(head_dim)) v per head.  off == nullptr: qkv [B][L][3 d] -> att [B][L][d].  Otherwise a
@@ -2573,6 +2763,7 @@ int run_forward_with(flope_tf_encoder* e, const float* x, int B, int L, float* y
   const int M = rg ? rg->T : B * L;
   int li = 0;
   int rc;
+  e->last_ln_launched = e->last_ln_folded = 0;
   if (rg) {
     const bool cast = !std::is_same<T, float>::value && e->emb.packed && !e->opt_generic;     // where launch_linear would run tf_cast_pad
     const int Kp = cast ? e->emb.Kp : e->in_dim;
@@ -2583,14 +2774,22 @@ int run_forward_with(flope_tf_encoder* e, const float* x, int B, int L, float* y
     TF_HIP(e, hipGetLastError());
     if ((rc = launch_linear<T>(e, e->emb, cast ? (const void*)e->xin : (const void*)e->xpk, cast ? 0 : 1, nullptr, e->h, 0, M, 0, st)) < 0) return rc;
   } else if ((rc = launch_linear<T>(e, e->emb, x, 1, nullptr, e->h, 0, M, 0, st)) < 0) return rc;
+  // a layer's second LayerNorm stands directly in front of the next layer's in_proj, its first in front of its linear1: the two pairs
+  // option skinny_ln may run as one launch each (tf_ln_then_linear); the last LayerNorm, in front of out_layer, is a launch of its own
+  const TfLayer* prev = nullptr;
   for (TfLayer& ly : e->layers) {
-    if ((rc = launch_linear<T>(e, ly.in_proj, e->h, 0, nullptr, e->qkv, 0, M, 0, st)) < 0) return rc;
+    if (!prev) rc = launch_linear<T>(e, ly.in_proj, e->h, 0, nullptr, e->qkv, 0, M, 0, st);
+    else rc = tf_ln_then_linear<T>(e, prev->n2w, prev->n2b, ly.in_proj, e->qkv, M, 0, st);
+    if (rc < 0) return rc;
     if ((rc = attention(li++)) < 0) return rc;
     if ((rc = launch_linear<T>(e, ly.out_proj, e->att, 0, e->h, e->h2, 0, M, 0, st)) < 0) return rc;
-    if ((rc = launch_layernorm<T>(e, e->h2, e->h, ly.n1w, ly.n1b, M, st)) < 0) return rc;
-    if ((rc = launch_linear<T>(e, ly.lin1, e->h, 0, nullptr, e->ffb, 0, M, 1, st)) < 0) return rc;
+    if ((rc = tf_ln_then_linear<T>(e, ly.n1w, ly.n1b, ly.lin1, e->ffb, M, 1, st)) < 0) return rc;
     if ((rc = launch_linear<T>(e, ly.lin2, e->ffb, 0, e->h, e->h2, 0, M, 0, st)) < 0) return rc;
-    if ((rc = launch_layernorm<T>(e, e->h2, e->h, ly.n2w, ly.n2b, M, st)) < 0) return rc;
+    prev = &ly;
+  }
+  if (prev) {
+    ++e->last_ln_launched;
+    if ((rc = launch_layernorm<T>(e, e->h2, e->h, prev->n2w, prev->n2b, M, st)) < 0) return rc;
   }
   if (!rg) return (rc = launch_linear<T>(e, e->outl, e->h, 0, nullptr, y, 1, M, 0, st)) < 0 ? rc : 0;
   if ((rc = launch_linear<T>(e, e->outl, e->h, 0, nullptr, e->ypk, 1, M, 0, st)) < 0) return rc;
@@ -2841,6 +3040,10 @@ extern "C" int flope_tf_set_option(flope_tf_handle e, const char* name, int valu
     if (value < 0 || value > 1) return tf_fail(e, FLOPE_EINVAL, "flope_tf_set_option: skinny is 0 or 1");
     const int old = e->opt_skinny; e->opt_skinny = value; return old;
   }
+  if (!strcmp(name, "skinny_ln")) {
+    if (value < 0 || value > 1) return tf_fail(e, FLOPE_EINVAL, "flope_tf_set_option: skinny_ln is 0 or 1");
+    const int old = e->opt_skinny_ln; e->opt_skinny_ln = value; return old;
+  }
   if (!strcmp(name, "extend_mfma")) {
     if (value < 0 || value > 1) return tf_fail(e, FLOPE_EINVAL, "flope_tf_set_option: extend_mfma is 0 or 1");
     const int old = e->opt_extend_mfma; e->opt_extend_mfma = value; return old;
@@ -3020,6 +3223,60 @@ extern "C" int flope_tf_linear_plan(flope_tf_handle e, const char* name, int row
     using T = typename decltype(tag)::type;
     return launch_linear<T>(e, *l, any, l == &e->emb ? 1 : 0, res ? any : nullptr, any, l == &e->outl ? 1 : 0, rows, relu ? 1 : 0, nullptr, true);
   });
+}
+
+// the checks flope_tf_linear_ln and flope_tf_linear_ln_plan share; *l: the linear
+static int tf_check_linear_ln(flope_tf_encoder* e, const char* who, const char* name, int rows, const TfLinear** l) {
+  const std::string w(who);
+  if (!e) return tf_fail(nullptr, FLOPE_EINVAL, w + ": NULL handle");
+  if (!e->loaded) return tf_fail(e, FLOPE_ESTATE, w + ": weights not loaded");
+  if (!name) return tf_fail(e, FLOPE_EINVAL, w + ": NULL argument");
+  if (!(*l = tf_find_linear(e, name))) return tf_fail(e, FLOPE_EINVAL, w + ": unknown linear " + name + " (embedding, out_layer, layers.<i>.in_proj / out_proj / linear1 / linear2)");
+  if (rows < 1) return tf_fail(e, FLOPE_EINVAL, w + ": non-positive rows");
+  if (rows > e->max_tokens) return tf_fail(e, FLOPE_EINVAL, w + ": rows exceeds max_tokens given to flope_tf_create");
+  return 0;
+}
+
+extern "C" int flope_tf_linear_ln(flope_tf_handle e, const char* name, const void* x_dev, const float* gamma_dev, const float* beta_dev, void* normed_dev,
+                                  void* y_dev, int rows, int relu, void* stream) {
+  const TfLinear* l = nullptr;
+  if (int rc = tf_check_linear_ln(e, "flope_tf_linear_ln", name, rows, &l)) return rc;
+  if (!x_dev || !gamma_dev || !beta_dev || !normed_dev || !y_dev) return tf_fail(e, FLOPE_EINVAL, "flope_tf_linear_ln: NULL argument");
+  if (((uintptr_t)x_dev | (uintptr_t)normed_dev | (uintptr_t)y_dev) & 15) return tf_fail(e, FLOPE_EINVAL, "flope_tf_linear_ln: x, normed and y are 16-byte aligned");
+  if (((uintptr_t)gamma_dev | (uintptr_t)beta_dev) & 15) return tf_fail(e, FLOPE_EINVAL, "flope_tf_linear_ln: gamma and beta are 16-byte aligned");
+  const bool ok = tf_by_dtype(e, [&](auto tag) { return (int)tf_linear_ln_ok<typename decltype(tag)::type>(e, *l, rows); }) != 0;
+  if (!ok) return tf_fail(e, FLOPE_EINVAL, std::string("flope_tf_linear_ln: no LayerNorm form of ") + name + " at " + std::to_string(rows) +
+                                               " rows under the handle's options (16-bit handle, options skinny and skinny_ln at 1, generic at 0, 1 .. 32 rows, a packed linear of K = model_dim, model_dim % 64 == 0, model_dim <= 512)");
+  // the launch reads the 16 MT rows of x while other waves write those rows of normed and y
+  const uintptr_t rb = (uintptr_t)16 * flope_tf_plan::tf_skinny_mt(rows) * e->esz;
+  const uintptr_t x0 = (uintptr_t)x_dev, x1 = x0 + rb * e->d, h0 = (uintptr_t)normed_dev, h1 = h0 + rb * e->d, y0 = (uintptr_t)y_dev, y1 = y0 + rb * l->N;
+  if ((x0 < h1 && h0 < x1) || (x0 < y1 && y0 < x1) || (h0 < y1 && y0 < h1)) return tf_fail(e, FLOPE_EINVAL, "flope_tf_linear_ln: x, normed and y must not overlap");
+  TF_HIP(e, hipSetDevice(e->device));
+  return tf_by_dtype(e, [&](auto tag) {
+    return launch_linear_ln<typename decltype(tag)::type>(e, *l, x_dev, gamma_dev, beta_dev, normed_dev, y_dev, rows, relu ? 1 : 0, (hipStream_t)stream);
+  });
+}
+
+// FLOPE_TF_LIN_SKINNY_LN where flope_tf_linear_ln would launch, else the id of the separate form's linear (no residual; linear1 with
+// ReLU); launches nothing
+extern "C" int flope_tf_linear_ln_plan(flope_tf_handle e, const char* name, int rows) {
+  const TfLinear* l = nullptr;
+  if (int rc = tf_check_linear_ln(e, "flope_tf_linear_ln_plan", name, rows, &l)) return rc;
+  const std::string nm(name);
+  const bool relu = nm.size() > 8 && nm.compare(nm.size() - 8, 8, ".linear1") == 0;
+  void* const any = (void*)(uintptr_t)16;
+  return tf_by_dtype(e, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    if (tf_linear_ln_ok<T>(e, *l, rows)) return (int)FLOPE_TF_LIN_SKINNY_LN;
+    return launch_linear<T>(e, *l, any, l == &e->emb ? 1 : 0, nullptr, any, l == &e->outl ? 1 : 0, rows, relu ? 1 : 0, nullptr, true);
+  });
+}
+
+extern "C" int flope_tf_last_ln(flope_tf_handle e, int* launched, int* folded) {
+  if (!e) return tf_fail(nullptr, FLOPE_EINVAL, "flope_tf_last_ln: NULL handle");
+  if (launched) *launched = e->last_ln_launched;
+  if (folded) *folded = e->last_ln_folded;
+  return FLOPE_OK;
 }
 
 extern "C" int flope_tf_layernorm(flope_tf_handle e, const void* in_dev, void* out_dev, const float* gamma_dev, const float* beta_dev, int rows, void* stream) {

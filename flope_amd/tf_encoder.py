@@ -19,7 +19,9 @@ An additive float mask -- torch's `mask=` with values other than -inf / 0, one [
 term, needs to tell the order of the poses behind a query.  A 16-bit encoder made with `bias_mfma=1` runs attention
 under a compiled bias on the MFMA attention step over the tile map of the bias's allowed set.
 A 16-bit encoder made with `skinny=1` runs every MFMA linear of 1 .. 32 rows -- a live step, a short extend, prefill or forward -- with one
-wave per 16-row feature tile instead of a few 128-row workgroups: the same bits, another launch shape.
+wave per 16-row feature tile instead of a few 128-row workgroups: the same bits, another launch shape.  With
+`skinny_ln=1` on top of it, a LayerNorm directly in front of such a linear (model_dim % 64 == 0, at most 512) runs inside the linear's
+launch: the same bits again, 2 num_layers - 1 launches fewer per forward; `enc.last_ln` counts them.
 
 Eval-mode semantics only (dropout is identity), as everywhere in this package.  There is no CPU
 path: construction fails loudly without a HIP device or without the built library.
@@ -211,7 +213,7 @@ def distance_bias(table, L, window=0):
 class TransformerEncoder:
     def __init__(self, input_dim, model_dim, out_dim, num_heads, num_layers, ff_dim, dropout=0.1,
                  dtype="f32", max_tokens=4096, device=None, attn_tiled=0, fused=0, window_mfma=0, step_split=0, extend_mfma=0,
-                 mask_mfma=0, bias_mfma=0, skinny=0):
+                 mask_mfma=0, bias_mfma=0, skinny=0, skinny_ln=0):
         _require_gpu()
         self.lib = _lib.load()
         self.device = torch.device(device if device is not None else "cuda:0")
@@ -277,6 +279,11 @@ class TransformerEncoder:
             if rc < 0:
                 self.close()
                 raise ValueError(f"skinny must be 0 or 1 (got {skinny!r})")
+        if skinny_ln:                            # 16-bit handles under skinny=1: a LayerNorm in front of a skinny linear of K = model_dim <= 512 runs inside that linear's launch, the same bits (0 or 1, include/flope_amd.h)
+            rc = self.lib.flope_tf_set_option(self.handle, b"skinny_ln", int(skinny_ln))
+            if rc < 0:
+                self.close()
+                raise ValueError(f"skinny_ln must be 0 or 1 (got {skinny_ln!r})")
 
     def _check(self, rc):
         if rc:
@@ -308,7 +315,7 @@ class TransformerEncoder:
             self._check(self.lib.flope_tf_load_weights(self.handle, n, names, ptrs, ndims, shapes))
 
     def set_option(self, name: str, value: int) -> int:
-        if name in ("step_split", "extend_mfma", "mask_mfma", "bias_mfma", "skinny"):    # the newer options raise on a refused value (the others keep returning the code)
+        if name in ("step_split", "extend_mfma", "mask_mfma", "bias_mfma", "skinny", "skinny_ln"):    # the newer options raise on a refused value (the others keep returning the code)
             rc = self.lib.flope_tf_set_option(self.handle, name.encode(), int(value))
             self._check_arg(rc)
             return rc
@@ -601,6 +608,55 @@ class TransformerEncoder:
         rc = self.lib.flope_tf_linear_plan(self.handle, name.encode(), int(rows))
         self._check_arg(rc)
         return rc
+
+    def linear_ln(self, name, x, weight, bias, relu=False, out=None, normed=None):
+        """(y, normed): normed = LayerNorm(x; weight, bias) and y = act(normed W^T + b) of the loaded linear `name` in the ONE launch a
+        forward runs for the pair under option skinny_ln (tf_gemm_skinny_ln); the id (FLOPE_TF_LIN_SKINNY_LN = 6) is kept
+        in `last_linear_kernel`.  x [rows, model_dim] in the handle's 16-bit dtype, weight / bias device float32 [model_dim].  ValueError
+        where the option's rule has no such launch for this handle, linear and row count (linear_ln_plan tells).  The storage rule of
+        linear(): x, y and normed live in storage of roundup(rows, 128) rows; `out` / `normed`: tensors to write into, never copied.
+        x must not share storage with either result."""
+        tdt, d = self._tdt(), self.dims[1]
+        N, K = self._linear_dims(name)
+        if x.dim() != 2 or x.shape[1] != d:
+            raise ValueError(f"{name}: expected [rows, {d}], got {tuple(x.shape)}")
+        rows = x.shape[0]
+        for t in (weight, bias):
+            if t.device != self.device or tuple(t.shape) != (d,) or t.dtype != torch.float32 or not t.is_contiguous():
+                raise ValueError(f"weight and bias must be contiguous float32 [{d}] on {self.device}")
+        x = self._padded(x, rows, d, tdt, "x")
+        rpad = (rows + 127) // 128 * 128
+        res = []
+        for t, cols, what in ((out, N, "out"), (normed, d, "normed")):
+            if t is None:
+                t = torch.empty((rpad, cols), dtype=tdt, device=self.device)[:rows]
+            elif self._padded(t, rows, cols, tdt, what) is not t:
+                raise ValueError(f"{what} must be a contiguous {tdt} tensor [{rows}, {cols}] with storage for {rpad} rows")
+            res.append(t)
+        out, normed = res
+        with torch.cuda.device(self.device):
+            rc = self.lib.flope_tf_linear_ln(self.handle, name.encode(), x.data_ptr(), weight.data_ptr(), bias.data_ptr(), normed.data_ptr(),
+                                             out.data_ptr(), rows, int(bool(relu)), _stream_ptr(self.device))
+        self._check_arg(rc)
+        self.last_linear_kernel = rc
+        self._keep = (x, weight, bias)
+        return out, normed
+
+    def linear_ln_plan(self, name, rows):
+        """FLOPE_TF_LIN_SKINNY_LN (6) where linear_ln() would launch for the loaded linear `name` at `rows` rows under the current
+        options, otherwise the FLOPE_TF_LIN_* id of the linear of the separate form.  Launches nothing."""
+        self._linear_dims(name)
+        rc = self.lib.flope_tf_linear_ln_plan(self.handle, name.encode(), int(rows))
+        self._check_arg(rc)
+        return rc
+
+    @property
+    def last_ln(self):
+        """(launched, folded): the stand-alone LayerNorm launches of the last forward / stream call that ran kernel by kernel, and the
+        LayerNorms that ran inside the next linear's launch (option skinny_ln)"""
+        a, b = C.c_int(0), C.c_int(0)
+        self._check_arg(self.lib.flope_tf_last_ln(self.handle, C.byref(a), C.byref(b)))
+        return a.value, b.value
 
     def layernorm(self, x, weight, bias, out=None):
         """LayerNorm (eps 1e-5, biased variance) of x [rows, model_dim] in the handle's dtype with device float32 weight / bias

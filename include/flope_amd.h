@@ -499,7 +499,15 @@ int flope_tf_forward(flope_tf_handle h, const float* x_dev, int batch, int seq_l
  *       flope_tf_stream_step / _step_assoc / _step_tracker / _extend / _prefill at that many rows, flope_tf_linear.  Reads token and
  *       residual rows 0 .. 15 (rows <= 16) or 0 .. 31 only, which lie inside the roundup(rows, 128) rows tf_gemm_mfma requires, and
  *       writes those rows only: rows `rows` .. 15 / 31 of the result may hold anything, as under 0, later rows are left alone.  More
- *       than 32 rows, option "generic", float32 results and unpacked linears keep their kernel.  Read when a call enqueues. */
+ *       than 32 rows, option "generic", float32 results and unpacked linears keep their kernel.  Read when a call enqueues;
+ *   "skinny_ln" (default 0; 0 or 1, FLOPE_EINVAL outside; returns the old value; stored and ignored wherever the rule below says no,
+ *       option "skinny" at 0 and float32 handles included): 1 = a LayerNorm of the forward that stands directly in front of a linear
+ *       option "skinny" takes -- a layer's first in front of its linear1, its second in front of the next layer's in_proj -- is not
+ *       launched; the linear runs as tf_gemm_skinny_ln (FLOPE_TF_LIN_SKINNY_LN = 6), which normalises the pre-norm rows
+ *       in its token load, stores the post-norm rows and runs tf_gemm_skinny's MFMAs: rows < `rows` of both results hold the BITS of
+ *       the two launches, so the option changes no result of any call; it takes 2 num_layers - 1 launches out of a forward.  The
+ *       rule: option "skinny" takes the linear (1 .. 32 rows), K = model_dim, model_dim % 64 == 0 and model_dim <= 512.  The last
+ *       LayerNorm (in front of out_layer) keeps its launch.  flope_tf_last_ln counts both.  Read when a call enqueues. */
 int flope_tf_set_option(flope_tf_handle h, const char* name, int value);
 /* softmax(q k^T / sqrt(head_dim)) v per head on a caller's buffer: qkv_dev [batch, seq_len, 3*model_dim] and out_dev
  * [batch, seq_len, model_dim] in the handle's dtype (float32 for FLOPE_DT_F32).  Launches exactly what flope_tf_forward
@@ -537,6 +545,24 @@ int flope_tf_linear(flope_tf_handle h, const char* name, const void* x_dev, int 
  * with a residual, ".linear1" with ReLU, all buffers aligned.  Launches nothing and touches no buffer.  The same refusals: weights not
  * loaded (FLOPE_ESTATE), an unknown name, rows < 1 or rows > max_tokens (FLOPE_EINVAL). */
 int flope_tf_linear_plan(flope_tf_handle h, const char* name, int rows);
+/* The forward's launch of a LayerNorm together with the linear behind it (option "skinny_ln") on a caller's buffers:
+ * normed_dev [rows, model_dim] = LayerNorm(x_dev [rows, model_dim]; gamma_dev, beta_dev float32 [model_dim], eps 1e-5) and
+ * y_dev [rows, N] = act(normed W^T + b) of linear `name`, all three in the handle's 16-bit dtype, relu != 0: ReLU.  Returns
+ * FLOPE_TF_LIN_SKINNY_LN, or < 0 and nothing launched: FLOPE_EINVAL wherever the option's rule says no for this handle, linear and row
+ * count (flope_tf_linear_ln_plan tells without an error).  The buffer rules of flope_tf_linear: x_dev, normed_dev and y_dev 16-byte
+ * aligned (gamma_dev and beta_dev too) and allocated for roundup(rows, 128) rows; the launch reads rows 0 .. 15 (rows <= 16) or 0 .. 31
+ * of x_dev and writes those rows of normed_dev and y_dev only; rows >= `rows` of x_dev may hold anything (NaN included), which reaches
+ * those rows of the results only.  x_dev, normed_dev and y_dev must not overlap (FLOPE_EINVAL). */
+#define FLOPE_TF_LIN_SKINNY_LN    6   /* tf_gemm_skinny_ln: option skinny_ln, a LayerNorm and the skinny linear behind it in one launch; the bits of the two */
+int flope_tf_linear_ln(flope_tf_handle h, const char* name, const void* x_dev, const float* gamma_dev, const float* beta_dev, void* normed_dev,
+                       void* y_dev, int rows, int relu, void* stream);
+/* FLOPE_TF_LIN_SKINNY_LN where flope_tf_linear_ln would launch for linear `name` at `rows` rows under the handle's current options,
+ * otherwise the FLOPE_TF_LIN_* id of the linear of the separate form (no residual; ".linear1" with ReLU).  Launches nothing. */
+int flope_tf_linear_ln_plan(flope_tf_handle h, const char* name, int rows);
+/* The LayerNorms of the last forward of any kind that went through the per-kernel launches (flope_tf_forward*, flope_tf_stream_step* /
+ * _extend / _prefill): *launched stand-alone launches, *folded run inside the next linear's launch (option "skinny_ln").  Either
+ * pointer may be NULL.  (0, 0) before the first forward. */
+int flope_tf_last_ln(flope_tf_handle h, int* launched, int* folded);
 /* The LayerNorm flope_tf_forward runs for this handle's dtype and model_dim (eps 1e-5, biased variance) on a caller's buffers:
  * in_dev [rows, model_dim] -> out_dev [rows, model_dim] in the handle's dtype, gamma_dev / beta_dev device float32 [model_dim].
  * Needs no weights.  Returns the FLOPE_TF_LN_* id of the kernel, or < 0 and nothing launched.  rows <= max_tokens; 16-bit handles
