@@ -32,12 +32,13 @@ HARNESS_TRACK := tests/host_harness/libflope_host_track.so
 HARNESS_TF_FEED := tests/host_harness/libflope_host_tf_feed.so
 HARNESS_TF_SKINNY := tests/host_harness/libflope_host_tf_skinny.so
 HARNESS_TF_SKINNY_LN := tests/host_harness/libflope_host_tf_skinny_ln.so
+HARNESS_TF_ARCH := tests/host_harness/libflope_host_tf_arch.so
 SRCS    := $(wildcard $(CSRC)/*.hip)
 OBJS     := $(patsubst $(CSRC)/%.hip,$(OBJDIR)/%.o,$(SRCS))
 HDRS     := $(wildcard $(CSRC)/*.h) include/flope_amd.h
 HIPFLAGS := --offload-arch=$(ARCH) -O3 -fPIC -std=c++17 -Wno-unused-value -Iinclude
 
-all: $(LIB) $(HARNESS) $(HARNESS_F32M) $(HARNESS_F32M_KSPLIT) $(HARNESS_GUARD) $(HARNESS_TF_F32M) $(HARNESS_TF_ATTN) $(HARNESS_TF_VARLEN) $(HARNESS_TF_FUSED) $(HARNESS_TF_CAUSAL) $(HARNESS_TF_STREAM) $(HARNESS_TF_WINDOW) $(HARNESS_TF_WINDOW16) $(HARNESS_TF_EXTEND) $(HARNESS_TF_SPLIT) $(HARNESS_TF_EXTEND16) $(HARNESS_TF_MASK) $(HARNESS_TF_MASK16) $(HARNESS_TF_BIAS) $(HARNESS_TF_STREAM_BIAS) $(HARNESS_TF_BIAS16) $(HARNESS_DEPTH) $(HARNESS_CROP) $(HARNESS_FRAME) $(HARNESS_TRACK) $(HARNESS_TF_FEED) $(HARNESS_TF_SKINNY) $(HARNESS_TF_SKINNY_LN)
+all: $(LIB) $(HARNESS) $(HARNESS_F32M) $(HARNESS_F32M_KSPLIT) $(HARNESS_GUARD) $(HARNESS_TF_F32M) $(HARNESS_TF_ATTN) $(HARNESS_TF_VARLEN) $(HARNESS_TF_FUSED) $(HARNESS_TF_CAUSAL) $(HARNESS_TF_STREAM) $(HARNESS_TF_WINDOW) $(HARNESS_TF_WINDOW16) $(HARNESS_TF_EXTEND) $(HARNESS_TF_SPLIT) $(HARNESS_TF_EXTEND16) $(HARNESS_TF_MASK) $(HARNESS_TF_MASK16) $(HARNESS_TF_BIAS) $(HARNESS_TF_STREAM_BIAS) $(HARNESS_TF_BIAS16) $(HARNESS_DEPTH) $(HARNESS_CROP) $(HARNESS_FRAME) $(HARNESS_TRACK) $(HARNESS_TF_FEED) $(HARNESS_TF_SKINNY) $(HARNESS_TF_SKINNY_LN) $(HARNESS_TF_ARCH)
 
 $(OBJDIR)/%.o: $(CSRC)/%.hip $(HDRS)
 	@mkdir -p $(OBJDIR)
@@ -196,6 +197,13 @@ $(HARNESS_TF_SKINNY): tests/host_harness/harness_tf_skinny.cpp $(CSRC)/tf_skinny
 $(HARNESS_TF_SKINNY_LN): tests/host_harness/harness_tf_skinny_ln.cpp $(CSRC)/tf_skinny_plan.h
 	g++ -O2 -ffp-contract=off -fPIC -shared -std=c++17 -I$(CSRC) -o $@ $<
 
+# the encoder's architecture list (tf_arch_plan.h, which run_forward_with walks) against a brute-force statement of the post-norm and
+# pre-norm orders, the skinny_ln fold rule, and tf_gelu_f32 (tf_act.h, which every linear kernel applies) measured against fp64 with every
+# product and sum rounded on its own (tests/test_tf_arch_host.py, tests/test_gpu_tf_arch.py); the test also builds the file as a stand-alone
+# program under AddressSanitizer + UBSan (-DTF_ARCH_MAIN) and runs it as a child process
+$(HARNESS_TF_ARCH): tests/host_harness/harness_tf_arch.cpp $(CSRC)/tf_arch_plan.h $(CSRC)/tf_act.h
+	g++ -O2 -ffp-contract=off -fPIC -shared -std=c++17 -I$(CSRC) -o $@ $<
+
 # the same host code under AddressSanitizer + UBSan (sanitizers run on the CPU build only):
 #   make asan-test      (builds the sanitized harness and runs tests/test_host.py against it; leak detection is off because the
 #                        interpreter's own libcrypto allocations are reported as leaks at exit)
@@ -217,7 +225,7 @@ dbg: $(DBGOBJS)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $(DBGDIR)/libflope_amd_dbg.so $(DBGOBJS)
 
 clean:
-	rm -rf build $(LIB) $(HARNESS) $(HARNESS_F32M) $(HARNESS_F32M_KSPLIT) $(HARNESS_GUARD) $(HARNESS_TF_F32M) $(HARNESS_TF_ATTN) $(HARNESS_TF_VARLEN) $(HARNESS_TF_FUSED) $(HARNESS_TF_CAUSAL) $(HARNESS_TF_STREAM) $(HARNESS_TF_WINDOW) $(HARNESS_TF_WINDOW16) $(HARNESS_TF_EXTEND) $(HARNESS_TF_SPLIT) $(HARNESS_TF_EXTEND16) $(HARNESS_TF_MASK) $(HARNESS_TF_MASK16) $(HARNESS_TF_BIAS) $(HARNESS_TF_STREAM_BIAS) $(HARNESS_TF_BIAS16) $(HARNESS_DEPTH) $(HARNESS_CROP) $(HARNESS_FRAME) $(HARNESS_TRACK) $(HARNESS_TF_FEED) $(HARNESS_TF_SKINNY) $(HARNESS_TF_SKINNY_LN)
+	rm -rf build $(LIB) $(HARNESS) $(HARNESS_F32M) $(HARNESS_F32M_KSPLIT) $(HARNESS_GUARD) $(HARNESS_TF_F32M) $(HARNESS_TF_ATTN) $(HARNESS_TF_VARLEN) $(HARNESS_TF_FUSED) $(HARNESS_TF_CAUSAL) $(HARNESS_TF_STREAM) $(HARNESS_TF_WINDOW) $(HARNESS_TF_WINDOW16) $(HARNESS_TF_EXTEND) $(HARNESS_TF_SPLIT) $(HARNESS_TF_EXTEND16) $(HARNESS_TF_MASK) $(HARNESS_TF_MASK16) $(HARNESS_TF_BIAS) $(HARNESS_TF_STREAM_BIAS) $(HARNESS_TF_BIAS16) $(HARNESS_DEPTH) $(HARNESS_CROP) $(HARNESS_FRAME) $(HARNESS_TRACK) $(HARNESS_TF_FEED) $(HARNESS_TF_SKINNY) $(HARNESS_TF_SKINNY_LN) $(HARNESS_TF_ARCH)
 
 # stand-alone measurement programs used by tools/collect_profiles.sh and DESIGN.md section 9 (not part of the library)
 TOOLBINS := build/fetch_calib build/launch_floor build/loop_probe build/loop_probe32 build/dma_issue_probe

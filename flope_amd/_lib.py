@@ -20,6 +20,7 @@ TF_ATTN_BIASED = 6                                                             #
 TF_LIN_GENERIC, TF_LIN_ROWWAVE, TF_LIN_ROWWAVE_VEC, TF_LIN_MFMA, TF_LIN_F32M = 0, 1, 2, 3, 4      # flope_tf_linear's return
 TF_LIN_SKINNY = 5                                                              # ... under option skinny where tf_gemm_mfma would run on 1 .. 32 rows
 TF_LIN_SKINNY_LN = 6                                                           # flope_tf_linear_ln's return: option skinny_ln, a LayerNorm and the skinny linear behind it in one launch
+TF_ACT_NONE, TF_ACT_RELU, TF_ACT_GELU = 0, 1, 2                                # flope_tf_linear_act's act, option "activation" 
 TF_FWD_LAUNCHES, TF_FWD_FUSED = 0, 1                                          # flope_tf_forward_plan's return
 TF_EXTEND_ROW, TF_EXTEND_SPLIT, TF_EXTEND_MFMA = 0, 1, 2                         # flope_tf_stream_extend_plan's / _attention_extend's return
 TF_STEP_ROW, TF_STEP_SPLIT = 0, 1                                              # flope_tf_stream_step_plan's / _attention's return
@@ -142,6 +143,8 @@ SIGNATURES = {
     "flope_tf_forward_flops": (_D, [_P, _I, _I]),
     "flope_tf_attention": (_I, [_P, _P, _I, _I, _P, _P]),
     "flope_tf_linear": (_I, [_P, C.c_char_p, _P, _I, _P, _P, _I, _I, _I, _P]),
+    "flope_tf_linear_act": (_I, [_P, C.c_char_p, _P, _I, _P, _P, _I, _I, _I, _P]),
+    "flope_tf_linear_ln_act": (_I, [_P, C.c_char_p, _P, _P, _P, _P, _P, _I, _I, _P]),
     "flope_tf_linear_plan": (_I, [_P, C.c_char_p, _I]),
     "flope_tf_layernorm": (_I, [_P, _P, _P, _P, _P, _I, _P]),
     "flope_tf_linear_ln": (_I, [_P, C.c_char_p, _P, _P, _P, _P, _P, _I, _I, _P]),

@@ -56,9 +56,15 @@
 // Option skinny_ln = 1 (with skinny = 1): a LayerNorm of the forward directly in front of such a linear of K = model_dim
 // <= 512 is not launched; the linear runs as tf_gemm_skinny_ln, which normalises the rows in its token load by tf_layernorm_vec's own
 // definitions in its summation order and stores them: the bits of the two launches (run_forward_with: tf_ln_then_linear).
+// Options norm_first / activation / final_norm (any dtype): torch's pre-norm layer, its erf GELU and
+// nn.TransformerEncoder(norm=LayerNorm), stated before the weights are loaded.  The order of a forward and the buffers of every op are
+// tf_arch_plan.h's list, which run_forward_with walks; GELU is tf_act.h's tf_gelu_f32 on the float32 accumulator of every linear kernel.
+// The defaults are the architecture of the first line above: the same launches and bits.  tf_fused_f32 runs the default alone.
 #include "../../include/flope_amd.h"
 #include "common.h"
 #include "host_pack.h"
+#include "tf_act.h"
+#include "tf_arch_plan.h"
 #include "tf_attn_plan.h"
 #include "tf_attn_mask.h"
 #include "tf_encoder_stream.h"
@@ -97,6 +103,12 @@ template <typename T> __device__ __forceinline__ float ld_any(const void* p, siz
 template <typename T> __device__ __forceinline__ void st_any(void* p, size_t i, int f32, float v) {
   if (f32) ((float*)p)[i] = v; else ((T*)p)[i] = from_f32<T>(v);
 }
+// the runtime activation of the generic linears: 0 none, FLOPE_TF_ACT_RELU, FLOPE_TF_ACT_GELU (tf_act.h), on the float32 accumulator
+__device__ __forceinline__ float tf_act_f32(float v, int act) {
+  if (act == FLOPE_TF_ACT_RELU) return fmaxf(v, 0.f);
+  if (act == FLOPE_TF_ACT_GELU) return tf_gelu_f32(v);
+  return v;
+}
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
@@ -111,23 +123,23 @@ __device__ __forceinline__ float wave_max(float v) {
 // ---- generic kernels (any shape; fp32 accumulate) ------------------------------------------------------------
 // The float32 summation orders, one definition each: the generic kernels below and tf_fused_f32 (its float instantiations, on LDS
 // rows) call these, so a caller only decides which thread or wave takes which element or row.  Row strides are parameters.
-// One element of Y = act(X W^T + b (+ R)): one fmaf chain k = 0 .. K - 1 from 0.f, + b[n], + residual, ReLU
+// One element of Y = act(X W^T + b (+ R)): one fmaf chain k = 0 .. K - 1 from 0.f, + b[n], + residual, the activation (tf_act_f32)
 template <typename T>
 __device__ __forceinline__ void tf_linear_elem(const void* X, int xld, int x_f32, const float* W, const float* b, const void* R, int rld,
-                                               void* Y, int yld, int y_f32, int m, int n, int K, int relu) {
+                                               void* Y, int yld, int y_f32, int m, int n, int K, int act) {
   const float* w = W + (size_t)n * K;
   float acc = 0.f;
   for (int k = 0; k < K; ++k) acc = fmaf(ld_any<T>(X, (size_t)m * xld + k, x_f32), w[k], acc);
   acc += b[n];
   if (R) acc += ld_any<T>(R, (size_t)m * rld + n, 0);
-  if (relu) acc = fmaxf(acc, 0.f);
+  acc = tf_act_f32(acc, act);
   st_any<T>(Y, (size_t)m * yld + n, y_f32, acc);
 }
 
 // One row of a narrow linear (N <= 16, no residual) on one wave: lanes stride K, one wave reduction per output feature, lane 0 stores
 template <typename T>
 __device__ __forceinline__ void tf_rowwave_row(const void* X, int xld, int x_f32, const float* W, const float* b, void* Y, int yld,
-                                               int y_f32, int m, int K, int N, int relu, int lane) {
+                                               int y_f32, int m, int K, int N, int act, int lane) {
   float acc[16];
 #pragma unroll
   for (int n = 0; n < 16; ++n) acc[n] = 0.f;
@@ -141,7 +153,7 @@ __device__ __forceinline__ void tf_rowwave_row(const void* X, int xld, int x_f32
   for (int n = 0; n < 16; ++n)
     if (n < N) {
       float v = wave_sum(acc[n]) + b[n];
-      if (relu) v = fmaxf(v, 0.f);
+      v = tf_act_f32(v, act);
       if (lane == 0) st_any<T>(Y, (size_t)m * yld + n, y_f32, v);
     }
 }
@@ -230,21 +242,21 @@ __device__ __forceinline__ void tf_attn_row(const T* base, size_t ld, T* orow, f
 // Y[m][n] = act(sum_k X[m][k] * W[n][k] + b[n] (+ R[m][n]))        W fp32 [N][K] as stored in the checkpoint
 template <typename T>
 __global__ void tf_linear_generic(const void* X, int x_f32, const float* W, const float* b, const void* R, void* Y,
-                                  int y_f32, int M, int K, int N, int relu) {
+                                  int y_f32, int M, int K, int N, int act) {
   const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (idx >= (size_t)M * N) return;
   const int m = (int)(idx / N), n = (int)(idx - (size_t)m * N);
-  tf_linear_elem<T>(X, K, x_f32, W, b, R, N, Y, N, y_f32, m, n, K, relu);
+  tf_linear_elem<T>(X, K, x_f32, W, b, R, N, Y, N, y_f32, m, n, K, act);
 }
 
 // Narrow outputs (N <= 16, e.g. out_layer): one wave per token row, lanes stride K (coalesced X and W reads), one
 // wave reduction per output feature.
 template <typename T>
 __global__ void tf_linear_rowwave(const void* X, int x_f32, const float* W, const float* b, void* Y, int y_f32, int M,
-                                  int K, int N, int relu) {
+                                  int K, int N, int act) {
   const int lane = threadIdx.x & 63, nw = blockDim.x >> 6;
   for (int m = blockIdx.x * nw + (threadIdx.x >> 6); m < M; m += gridDim.x * nw)
-    tf_rowwave_row<T>(X, K, x_f32, W, b, Y, N, y_f32, m, K, N, relu, lane);
+    tf_rowwave_row<T>(X, K, x_f32, W, b, Y, N, y_f32, m, K, N, act, lane);
 }
 
 // The same for 16-bit activations with K % 8 == 0 (r03: the kernel above took 184 us for the out_layer of the throughput shape --
@@ -252,7 +264,7 @@ __global__ void tf_linear_rowwave(const void* X, int x_f32, const float* W, cons
 // (N x K floats), a lane reads 16 bytes of its row per step and keeps two rows in flight.
 template <typename T>
 __global__ __launch_bounds__(256) void tf_linear_rowwave_vec(const T* __restrict__ X, const float* __restrict__ W,
-                                                             const float* __restrict__ b, void* Y, int y_f32, int M, int K, int N, int relu) {
+                                                             const float* __restrict__ b, void* Y, int y_f32, int M, int K, int N, int act) {
   extern __shared__ __attribute__((aligned(16))) float sw[];          // [N][K]
   for (int i = threadIdx.x; i < N * K; i += 256) sw[i] = W[i];
   __syncthreads();
@@ -289,7 +301,7 @@ __global__ __launch_bounds__(256) void tf_linear_rowwave_vec(const T* __restrict
       for (int n = 0; n < 16; ++n)
         if (n < N) {
           float v = wave_sum(acc[r][n]) + b[n];
-          if (relu) v = fmaxf(v, 0.f);
+          v = tf_act_f32(v, act);
           if (lane == 0 && m0 + r < M) st_any<T>(Y, (size_t)(m0 + r) * N + n, y_f32, v);
         }
   }
@@ -1053,7 +1065,9 @@ __device__ unsigned g_tfdbg_n;
 #define TFDBG_STAMP(i_) do {} while (0)
 #endif
 
-template <typename T, bool RELU, bool RES>
+// ACT (this kernel, tf_gemm_skinny, tf_gemm_skinny_ln): FLOPE_TF_ACT_* of tf_act.h.  ReLU works on the packed 16-bit pair; GELU
+// (never with a residual: DESIGN.md 50) is tf_gelu_f32 on the float32 accumulator in front of the pack.
+template <typename T, int ACT, bool RES>
 __global__ __launch_bounds__(256, 2) void tf_gemm_mfma(const T* __restrict__ X, const void* __restrict__ Wp,
                                                        const float* __restrict__ bias, const T* __restrict__ res,
                                                        T* __restrict__ Y, int K, int N) {
@@ -1146,12 +1160,17 @@ __global__ __launch_bounds__(256, 2) void tf_gemm_mfma(const T* __restrict__ X, 
         v[8 + q * 2] += unpack_lo<T>(r1[q]); v[8 + q * 2 + 1] += unpack_hi<T>(r1[q]);
       }
     }
+    if constexpr (ACT == FLOPE_TF_ACT_GELU) {
+      static_assert(!RES, "GELU has no residual form");
+#pragma unroll
+      for (int q = 0; q < 16; ++q) v[q] = tf_gelu_f32(v[q]);
+    }
     u32x4 o0, o1;
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
       o0[q] = pack2<T>(v[q * 2], v[q * 2 + 1]);
       o1[q] = pack2<T>(v[8 + q * 2], v[8 + q * 2 + 1]);
-      if constexpr (RELU) { o0[q] = pk_relu16(o0[q]); o1[q] = pk_relu16(o1[q]); }
+      if constexpr (ACT == FLOPE_TF_ACT_RELU) { o0[q] = pk_relu16(o0[q]); o1[q] = pk_relu16(o1[q]); }
     }
     *(u32x4*)(Y + off) = o0;
     *(u32x4*)(Y + off + 8) = o1;
@@ -1175,7 +1194,7 @@ __global__ __launch_bounds__(256, 2) void tf_gemm_mfma(const T* __restrict__ X, 
 // v_mfma_f32_16x16x32 per 32 k with the same 16 feature rows as A and its token in the same column of B, chunks ascending and ks = 0, 1
 // inside a chunk, then residual, 16-bit pack, ReLU.  The same bits, so the option changes no result.
 // Reads token and residual rows 0 .. 16 MT - 1 (inside the roundup(rows, 128) rows every caller allocates) and writes those rows of Y only.
-template <typename T, bool RELU, bool RES, int MT>
+template <typename T, int ACT, bool RES, int MT>
 __global__ __launch_bounds__(64 * flope_tf_plan::kTfSkinnyWaves) void tf_gemm_skinny(const T* __restrict__ X, const void* __restrict__ Wp,
                                                                                      const float* __restrict__ bias, const T* __restrict__ res,
                                                                                      T* __restrict__ Y, int K, int N) {
@@ -1248,8 +1267,13 @@ __global__ __launch_bounds__(64 * flope_tf_plan::kTfSkinnyWaves) void tf_gemm_sk
       v[0] += unpack_lo<T>(r[0]); v[1] += unpack_hi<T>(r[0]);
       v[2] += unpack_lo<T>(r[1]); v[3] += unpack_hi<T>(r[1]);
     }
+    if constexpr (ACT == FLOPE_TF_ACT_GELU) {
+      static_assert(!RES, "GELU has no residual form");
+#pragma unroll
+      for (int q = 0; q < 4; ++q) v[q] = tf_gelu_f32(v[q]);
+    }
     u32x2 o = {pack2<T>(v[0], v[1]), pack2<T>(v[2], v[3])};
-    if constexpr (RELU) { o[0] = pk_relu16(o[0]); o[1] = pk_relu16(o[1]); }
+    if constexpr (ACT == FLOPE_TF_ACT_RELU) { o[0] = pk_relu16(o[0]); o[1] = pk_relu16(o[1]); }
     *(u32x2*)(Y + off) = o;
   }
 }
@@ -1266,7 +1290,7 @@ __global__ __launch_bounds__(64 * flope_tf_plan::kTfSkinnyWaves) void tf_gemm_sk
 // four lanes of a token, so what rows M .. 16 MT - 1 of X hold reaches those rows of H and Y only.  X must not alias H or Y.
 // NCH = K / 64 is a template parameter of the wave's work: with the chunk count known, the ring, the tree and the rewrite are straight-line
 // code over registers (as a runtime value it put a merge of the whole ring behind every test: five times the instructions)
-template <typename T, bool RELU, int MT, int NCH>
+template <typename T, int ACT, int MT, int NCH>
 __device__ __forceinline__ void tf_skinny_ln_wave(const T* __restrict__ X, const float* __restrict__ gamma, const float* __restrict__ beta,
                                                   const void* __restrict__ Wp, const float* __restrict__ bias, T* __restrict__ H, T* __restrict__ Y, int N) {
   using namespace flope_tf_plan;
@@ -1365,20 +1389,24 @@ __device__ __forceinline__ void tf_skinny_ln_wave(const T* __restrict__ X, const
 #pragma unroll
   for (int tt = 0; tt < MT; ++tt) {
     const size_t off = (size_t)tf_skinny_x_row(tt, lane) * N + n0;
+    if constexpr (ACT == FLOPE_TF_ACT_GELU) {
+#pragma unroll
+      for (int q = 0; q < 4; ++q) acc[tt][q] = tf_gelu_f32(acc[tt][q]);
+    }
     u32x2 o = {pack2<T>(acc[tt][0], acc[tt][1]), pack2<T>(acc[tt][2], acc[tt][3])};
-    if constexpr (RELU) { o[0] = pk_relu16(o[0]); o[1] = pk_relu16(o[1]); }
+    if constexpr (ACT == FLOPE_TF_ACT_RELU) { o[0] = pk_relu16(o[0]); o[1] = pk_relu16(o[1]); }
     *(u32x2*)(Y + off) = o;
   }
 }
 
-template <typename T, bool RELU, int MT>
+template <typename T, int ACT, int MT>
 __global__ __launch_bounds__(64 * flope_tf_plan::kTfSkinnyWaves) void tf_gemm_skinny_ln(const T* __restrict__ X, const float* __restrict__ gamma,
                                                                                         const float* __restrict__ beta, const void* __restrict__ Wp,
                                                                                         const float* __restrict__ bias, T* __restrict__ H,
                                                                                         T* __restrict__ Y, int K, int N) {
   static_assert(flope_tf_plan::kTfSkinnyDepth == 8, "one case per chunk count");
   switch (K >> 6) {                                 // tf_skinny_ln_ok: 1 .. kTfSkinnyDepth
-#define TF_SKL_CASE(n_) case n_: tf_skinny_ln_wave<T, RELU, MT, n_>(X, gamma, beta, Wp, bias, H, Y, N); break
+#define TF_SKL_CASE(n_) case n_: tf_skinny_ln_wave<T, ACT, MT, n_>(X, gamma, beta, Wp, bias, H, Y, N); break
     TF_SKL_CASE(1); TF_SKL_CASE(2); TF_SKL_CASE(3); TF_SKL_CASE(4); TF_SKL_CASE(5); TF_SKL_CASE(6); TF_SKL_CASE(7); TF_SKL_CASE(8);
 #undef TF_SKL_CASE
     default: break;
@@ -2060,7 +2088,7 @@ __global__ __launch_bounds__(256, 2) void tf_attn16_extend(const T* __restrict__
 // Epilogue: accumulators start at the bias (padded to whole blocks); a lane ends with 4 nct consecutive features of its token ->
 // residual by 16-byte loads, ReLU, 16-byte stores (element-wise where N % 4 != 0: out_layer); tokens past M are clamped in the
 // loop and masked here, features past N masked here.
-template <int MP, bool RELU, bool RES>
+template <int MP, int ACT, bool RES>
 __global__ __launch_bounds__(256) void tf_linear_f32m(const float* __restrict__ X, const float* __restrict__ Wp, const float* __restrict__ bp,
                                                       const float* __restrict__ R, float* __restrict__ Y, int M, int K, int N, int nsteps) {
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -2140,7 +2168,8 @@ __global__ __launch_bounds__(256) void tf_linear_f32m(const float* __restrict__ 
           const f32x4 rv = *(const f32x4*)(R + o);
           v[0] += rv[0]; v[1] += rv[1]; v[2] += rv[2]; v[3] += rv[3];
         }
-        if constexpr (RELU) { v[0] = fmaxf(v[0], 0.f); v[1] = fmaxf(v[1], 0.f); v[2] = fmaxf(v[2], 0.f); v[3] = fmaxf(v[3], 0.f); }
+        if constexpr (ACT == FLOPE_TF_ACT_RELU) { v[0] = fmaxf(v[0], 0.f); v[1] = fmaxf(v[1], 0.f); v[2] = fmaxf(v[2], 0.f); v[3] = fmaxf(v[3], 0.f); }
+        if constexpr (ACT == FLOPE_TF_ACT_GELU) { v[0] = tf_gelu_f32(v[0]); v[1] = tf_gelu_f32(v[1]); v[2] = tf_gelu_f32(v[2]); v[3] = tf_gelu_f32(v[3]); }
         *(f32x4*)(Y + o) = v;
       } else {
 #pragma unroll
@@ -2148,7 +2177,8 @@ __global__ __launch_bounds__(256) void tf_linear_f32m(const float* __restrict__ 
           if (f + q < N) {
             float s = v[q];
             if constexpr (RES) s += R[o + q];
-            if constexpr (RELU) s = fmaxf(s, 0.f);
+            if constexpr (ACT == FLOPE_TF_ACT_RELU) s = fmaxf(s, 0.f);
+            if constexpr (ACT == FLOPE_TF_ACT_GELU) s = tf_gelu_f32(s);
             Y[o + q] = s;
           }
       }
@@ -2307,13 +2337,13 @@ constexpr int kTfFusedTabHead = 4, kTfFusedTabLayer = 12;
 
 // the order launch_linear gives this linear in the float32 launch sequence
 __device__ __forceinline__ void tf_fz_linear(const float* X, int xld, const float* W, const float* b, const float* R, int rld, float* Y,
-                                             int yld, int M, int K, int N, int relu) {
+                                             int yld, int M, int K, int N, int act) {
   if (flope_tf_plan::tf_fused_rowwave_order(N, R != nullptr)) {
-    for (int m = threadIdx.x >> 6; m < M; m += 4) tf_rowwave_row<float>(X, xld, 1, W, b, Y, yld, 1, m, K, N, relu, threadIdx.x & 63);
+    for (int m = threadIdx.x >> 6; m < M; m += 4) tf_rowwave_row<float>(X, xld, 1, W, b, Y, yld, 1, m, K, N, act, threadIdx.x & 63);
   } else {
     for (int idx = threadIdx.x; idx < M * N; idx += 256) {
       const int m = idx / N;
-      tf_linear_elem<float>(X, xld, 1, W, b, R, rld, Y, yld, 1, m, idx - m * N, K, relu);
+      tf_linear_elem<float>(X, xld, 1, W, b, R, rld, Y, yld, 1, m, idx - m * N, K, act);
     }
   }
 }
@@ -2412,6 +2442,9 @@ struct flope_tf_encoder {
   int opt_skinny = 0;                        // 1: a linear that would run tf_gemm_mfma on 1 .. 32 rows runs tf_gemm_skinny, the same bits (stored and ignored by float32 handles)
   int opt_skinny_ln = 0;                     // 1: a LayerNorm directly in front of a skinny linear of K = model_dim <= 512 runs inside that linear's launch (tf_gemm_skinny_ln), the bits of the two launches (stored and ignored where tf_skinny_ln_ok says no, option skinny at 0 included)
   int last_ln_launched = 0, last_ln_folded = 0;   // the stand-alone LayerNorm launches of the last run_forward_with and the LayerNorms it folded (flope_tf_last_ln)
+  flope_tf_plan::TfArch arch = {0, FLOPE_TF_ACT_RELU, 0};   // options norm_first / activation / final_norm, fixed once the weights are loaded (tf_arch_plan.h)
+  bool arch_fixed = false;                   // set by the first flope_tf_load_weights that succeeds, never cleared
+  float *fnw = nullptr, *fnb = nullptr;      // transformer_encoder.norm.weight / .bias where arch.final_norm
   int opt_f32m_lds = 0;                     // KiB of untouched LDS a tf_linear_f32m launch reserves (> 80: one workgroup per CU)
   int cus = 256;
   bool loaded = false;
@@ -2540,7 +2573,10 @@ template <typename V> int tf_upload(flope_tf_encoder* e, const V* src, size_t co
 // by the same tests (flope_tf_linear_plan; X, R and Y are then looked at for NULL and alignment only).
 template <typename T>
 int launch_linear(flope_tf_encoder* e, const TfLinear& l, const void* X, int x_f32, const void* R, void* Y, int y_f32,
-                  int M, int relu, hipStream_t st, bool plan = false) {
+                  int M, int act, hipStream_t st, bool plan = false) {
+  // act: 0 or FLOPE_TF_ACT_*.  GELU works on the accumulator and has no residual form in any kernel
+  if (act == FLOPE_TF_ACT_GELU && R) return tf_fail(e, FLOPE_EINVAL, "linear: GELU with a residual has no kernel");
+  const bool relu = act == FLOPE_TF_ACT_RELU, gelu = act == FLOPE_TF_ACT_GELU;
   if constexpr (std::is_same<T, float>::value) {
     if (e->opt_f32m && l.pk32 && !(((uintptr_t)X | (uintptr_t)Y | (uintptr_t)R) & 15)) {
       if (plan) return relu && R ? tf_fail(e, FLOPE_EINVAL, "tf_linear_f32m: no ReLU + residual form") : FLOPE_TF_LIN_F32M;
@@ -2550,7 +2586,7 @@ int launch_linear(flope_tf_encoder* e, const TfLinear& l, const void* X, int x_f
 #define TF_GO3(MP_, RELU_, RES_)                                                                                       \
   hipLaunchKernelGGL((tf_linear_f32m<MP_, RELU_, RES_>), grid, dim3(256), lds, st, (const float*)X, l.pk32, l.bpad, \
                      (const float*)R, (float*)Y, M, l.K, l.N, nsteps)
-#define TF_GO2(MP_) do { if (relu && !R) TF_GO3(MP_, true, false); else if (R && !relu) TF_GO3(MP_, false, true); else if (!R) TF_GO3(MP_, false, false); else return tf_fail(e, FLOPE_EINVAL, "tf_linear_f32m: no ReLU + residual form"); } while (0)
+#define TF_GO2(MP_) do { if (gelu) TF_GO3(MP_, FLOPE_TF_ACT_GELU, false); else if (relu && !R) TF_GO3(MP_, FLOPE_TF_ACT_RELU, false); else if (R && !relu) TF_GO3(MP_, 0, true); else if (!R) TF_GO3(MP_, 0, false); else return tf_fail(e, FLOPE_EINVAL, "tf_linear_f32m: no ReLU + residual form"); } while (0)
       if (mp == 4) TF_GO2(4); else if (mp == 2) TF_GO2(2); else TF_GO2(1);
 #undef TF_GO2
 #undef TF_GO3
@@ -2574,7 +2610,7 @@ int launch_linear(flope_tf_encoder* e, const TfLinear& l, const void* X, int x_f
   hipLaunchKernelGGL((tf_gemm_skinny<T, RELU_, RES_, MT_>), dim3(sl.grid), dim3(sl.block), 0, st, (const T*)X, l.packed, l.b, \
                      (const T*)R, (T*)Y, l.Kp, l.N)
 #define TF_SK2(RELU_, RES_) do { if (MT == 1) TF_SK(RELU_, RES_, 1); else TF_SK(RELU_, RES_, 2); } while (0)
-        if (relu && R) TF_SK2(true, true); else if (relu) TF_SK2(true, false); else if (R) TF_SK2(false, true); else TF_SK2(false, false);
+        if (gelu) TF_SK2(FLOPE_TF_ACT_GELU, false); else if (relu && R) TF_SK2(FLOPE_TF_ACT_RELU, true); else if (relu) TF_SK2(FLOPE_TF_ACT_RELU, false); else if (R) TF_SK2(0, true); else TF_SK2(0, false);
 #undef TF_SK2
 #undef TF_SK
         TF_HIP(e, hipGetLastError());
@@ -2585,7 +2621,7 @@ int launch_linear(flope_tf_encoder* e, const TfLinear& l, const void* X, int x_f
 #define TF_GO(RELU_, RES_)                                                                                       \
   hipLaunchKernelGGL((tf_gemm_mfma<T, RELU_, RES_>), dim3(grid), dim3(256), lds, st, (const T*)X, l.packed, l.b, \
                      (const T*)R, (T*)Y, l.Kp, l.N)
-      if (relu && R) TF_GO(true, true); else if (relu) TF_GO(true, false); else if (R) TF_GO(false, true); else TF_GO(false, false);
+      if (gelu) TF_GO(FLOPE_TF_ACT_GELU, false); else if (relu && R) TF_GO(FLOPE_TF_ACT_RELU, true); else if (relu) TF_GO(FLOPE_TF_ACT_RELU, false); else if (R) TF_GO(0, true); else TF_GO(0, false);
 #undef TF_GO
       TF_HIP(e, hipGetLastError());
       return FLOPE_TF_LIN_MFMA;
@@ -2595,7 +2631,7 @@ int launch_linear(flope_tf_encoder* e, const TfLinear& l, const void* X, int x_f
     if (l.N <= 16 && !R && !x_f32 && l.K % 8 == 0 && (size_t)l.N * l.K * 4 <= 48 * 1024) {
       if (plan) return FLOPE_TF_LIN_ROWWAVE_VEC;
       const int blocks = (M + 7) / 8 < 2048 ? (M + 7) / 8 : 2048;
-      hipLaunchKernelGGL((tf_linear_rowwave_vec<T>), dim3(blocks), dim3(256), (size_t)l.N * l.K * 4, st, (const T*)X, l.w, l.b, Y, y_f32, M, l.K, l.N, relu);
+      hipLaunchKernelGGL((tf_linear_rowwave_vec<T>), dim3(blocks), dim3(256), (size_t)l.N * l.K * 4, st, (const T*)X, l.w, l.b, Y, y_f32, M, l.K, l.N, act);
       TF_HIP(e, hipGetLastError());
       return FLOPE_TF_LIN_ROWWAVE_VEC;
     }
@@ -2603,14 +2639,14 @@ int launch_linear(flope_tf_encoder* e, const TfLinear& l, const void* X, int x_f
   if (l.N <= 16 && !R) {
     if (plan) return FLOPE_TF_LIN_ROWWAVE;
     const int blocks = (M + 3) / 4 < 8192 ? (M + 3) / 4 : 8192;
-    hipLaunchKernelGGL((tf_linear_rowwave<T>), dim3(blocks), dim3(256), 0, st, X, x_f32, l.w, l.b, Y, y_f32, M, l.K, l.N, relu);
+    hipLaunchKernelGGL((tf_linear_rowwave<T>), dim3(blocks), dim3(256), 0, st, X, x_f32, l.w, l.b, Y, y_f32, M, l.K, l.N, act);
     TF_HIP(e, hipGetLastError());
     return FLOPE_TF_LIN_ROWWAVE;
   }
   if (plan) return FLOPE_TF_LIN_GENERIC;
   const size_t total = (size_t)M * l.N;
   hipLaunchKernelGGL((tf_linear_generic<T>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, X, x_f32, l.w, l.b,
-                     R, Y, y_f32, M, l.K, l.N, relu);
+                     R, Y, y_f32, M, l.K, l.N, act);
   TF_HIP(e, hipGetLastError());
   return FLOPE_TF_LIN_GENERIC;
 }
@@ -2640,7 +2676,7 @@ bool tf_linear_ln_ok(const flope_tf_encoder* e, const TfLinear& l, int M) {
 // H = LayerNorm(X; gamma, beta), Y = act(H W^T + b) in the one launch of tf_gemm_skinny_ln; the caller has asked tf_linear_ln_ok.
 // X, H: [roundup(M, 16)][model_dim] at least, Y the same rows of N; X aliases neither.  Returns FLOPE_TF_LIN_SKINNY_LN, or < 0.
 template <typename T>
-int launch_linear_ln(flope_tf_encoder* e, const TfLinear& l, const void* X, const float* gamma, const float* beta, void* H, void* Y, int M, int relu,
+int launch_linear_ln(flope_tf_encoder* e, const TfLinear& l, const void* X, const float* gamma, const float* beta, void* H, void* Y, int M, int act,
                      hipStream_t st) {
   if constexpr (!std::is_same<T, float>::value) {
     const int MT = flope_tf_plan::tf_skinny_mt(M);
@@ -2648,7 +2684,9 @@ int launch_linear_ln(flope_tf_encoder* e, const TfLinear& l, const void* X, cons
 #define TF_SKL(RELU_, MT_)                                                                                                           \
   hipLaunchKernelGGL((tf_gemm_skinny_ln<T, RELU_, MT_>), dim3(sl.grid), dim3(sl.block), 0, st, (const T*)X, gamma, beta, l.packed, l.b, \
                      (T*)H, (T*)Y, l.Kp, l.N)
-    if (relu) { if (MT == 1) TF_SKL(true, 1); else TF_SKL(true, 2); } else { if (MT == 1) TF_SKL(false, 1); else TF_SKL(false, 2); }
+#define TF_SKL2(ACT_) do { if (MT == 1) TF_SKL(ACT_, 1); else TF_SKL(ACT_, 2); } while (0)
+    if (act == FLOPE_TF_ACT_GELU) TF_SKL2(FLOPE_TF_ACT_GELU); else if (act == FLOPE_TF_ACT_RELU) TF_SKL2(FLOPE_TF_ACT_RELU); else TF_SKL2(0);
+#undef TF_SKL2
 #undef TF_SKL
     TF_HIP(e, hipGetLastError());
     return FLOPE_TF_LIN_SKINNY_LN;
@@ -2656,18 +2694,20 @@ int launch_linear_ln(flope_tf_encoder* e, const TfLinear& l, const void* X, cons
   return tf_fail(e, FLOPE_EINVAL, "tf_gemm_skinny_ln: 16-bit handles only");
 }
 
-// e->h = LayerNorm(e->h2; w, b), then Y = act(linear l of e->h): the pair as it stands in the forward -- one launch where
-// tf_linear_ln_ok, the two launches otherwise.  Counts into the handle's last_ln_*.
+// dst = LayerNorm(src; w, b), then Y = act(linear l of dst): the pair as it stands in the forward (src and dst are e->h2 and e->h, in
+// the order the architecture gives them: tf_arch_plan.h) -- one launch where tf_linear_ln_ok, the two launches otherwise.  Counts into
+// the handle's last_ln_*.
 template <typename T>
-int tf_ln_then_linear(flope_tf_encoder* e, const float* w, const float* b, const TfLinear& l, void* Y, int M, int relu, hipStream_t st) {
+int tf_ln_then_linear(flope_tf_encoder* e, const float* w, const float* b, const void* src, void* dst, const TfLinear& l, void* Y, int M, int act,
+                      hipStream_t st) {
   int rc;
   if (tf_linear_ln_ok<T>(e, l, M)) {
     ++e->last_ln_folded;
-    return launch_linear_ln<T>(e, l, e->h2, w, b, e->h, Y, M, relu, st);
+    return launch_linear_ln<T>(e, l, src, w, b, dst, Y, M, act, st);
   }
   ++e->last_ln_launched;
-  if ((rc = launch_layernorm<T>(e, e->h2, e->h, w, b, M, st)) < 0) return rc;
-  return launch_linear<T>(e, l, e->h, 0, nullptr, Y, 0, M, relu, st);
+  if ((rc = launch_layernorm<T>(e, src, dst, w, b, M, st)) < 0) return rc;
+  return launch_linear<T>(e, l, dst, 0, nullptr, Y, 0, M, act, st);
 }
 
 // One attention launch: softmax(q k^T / sqrt(head_dim)) v per head.  off == nullptr: qkv [B][L][3 d] -> att [B][L][d].  Otherwise a
@@ -2760,10 +2800,18 @@ int tf_plan_ragged(flope_tf_encoder* e, const char* who, const int* lengths, int
 // attention(li): what stands between in_proj and out_proj of layer li (qkv of the M rows in e->qkv -> e->att); < 0 ends the forward.
 template <typename T, typename ATT>
 int run_forward_with(flope_tf_encoder* e, const float* x, int B, int L, float* y, hipStream_t st, const TfRagged* rg, ATT&& attention) {
+  using namespace flope_tf_plan;
   const int M = rg ? rg->T : B * L;
-  int li = 0;
   int rc;
   e->last_ln_launched = e->last_ln_folded = 0;
+  // the order, the buffers and the activation are the architecture's op list (tf_arch_plan.h), stated there alone
+  const int nops = tf_arch_op_count(e->arch, e->nl);
+  auto buf = [&](int b) -> void* { return b == kTfBufH ? e->h : b == kTfBufH2 ? e->h2 : b == kTfBufQkv ? e->qkv : b == kTfBufAtt ? e->att : b == kTfBufFfb ? e->ffb : nullptr; };
+  auto lin = [&](const TfOp& o) -> const TfLinear& {
+    const TfLayer& ly = e->layers[o.layer < 0 ? 0 : o.layer];
+    return o.name == kTfLinInProj ? ly.in_proj : o.name == kTfLinOutProj ? ly.out_proj : o.name == kTfLinLinear1 ? ly.lin1 : ly.lin2;
+  };
+  // op 0, the embedding, from the caller's float32 rows
   if (rg) {
     const bool cast = !std::is_same<T, float>::value && e->emb.packed && !e->opt_generic;     // where launch_linear would run tf_cast_pad
     const int Kp = cast ? e->emb.Kp : e->in_dim;
@@ -2774,25 +2822,28 @@ int run_forward_with(flope_tf_encoder* e, const float* x, int B, int L, float* y
     TF_HIP(e, hipGetLastError());
     if ((rc = launch_linear<T>(e, e->emb, cast ? (const void*)e->xin : (const void*)e->xpk, cast ? 0 : 1, nullptr, e->h, 0, M, 0, st)) < 0) return rc;
   } else if ((rc = launch_linear<T>(e, e->emb, x, 1, nullptr, e->h, 0, M, 0, st)) < 0) return rc;
-  // a layer's second LayerNorm stands directly in front of the next layer's in_proj, its first in front of its linear1: the two pairs
-  // option skinny_ln may run as one launch each (tf_ln_then_linear); the last LayerNorm, in front of out_layer, is a launch of its own
-  const TfLayer* prev = nullptr;
-  for (TfLayer& ly : e->layers) {
-    if (!prev) rc = launch_linear<T>(e, ly.in_proj, e->h, 0, nullptr, e->qkv, 0, M, 0, st);
-    else rc = tf_ln_then_linear<T>(e, prev->n2w, prev->n2b, ly.in_proj, e->qkv, M, 0, st);
-    if (rc < 0) return rc;
-    if ((rc = attention(li++)) < 0) return rc;
-    if ((rc = launch_linear<T>(e, ly.out_proj, e->att, 0, e->h, e->h2, 0, M, 0, st)) < 0) return rc;
-    if ((rc = tf_ln_then_linear<T>(e, ly.n1w, ly.n1b, ly.lin1, e->ffb, M, 1, st)) < 0) return rc;
-    if ((rc = launch_linear<T>(e, ly.lin2, e->ffb, 0, e->h, e->h2, 0, M, 0, st)) < 0) return rc;
-    prev = &ly;
+  // ops 1 .. nops - 2.  A LayerNorm the list marks `fold` stands directly in front of the linear that reads it: the pair option
+  // skinny_ln may run as one launch (tf_ln_then_linear); every other LayerNorm is a launch of its own
+  for (int i = 1; i + 1 < nops; ++i) {
+    const TfOp o = tf_arch_op(e->arch, e->nl, i);
+    if (o.kind == kTfOpAttention) {
+      if ((rc = attention(o.layer)) < 0) return rc;
+    } else if (o.kind == kTfOpLayerNorm) {
+      const float* w = o.name == kTfLnFinal ? e->fnw : o.name == kTfLnNorm1 ? e->layers[o.layer].n1w : e->layers[o.layer].n2w;
+      const float* b = o.name == kTfLnFinal ? e->fnb : o.name == kTfLnNorm1 ? e->layers[o.layer].n1b : e->layers[o.layer].n2b;
+      if (o.fold) {
+        const TfOp n = tf_arch_op(e->arch, e->nl, ++i);       // the linear behind it: in = o.out, no residual
+        if ((rc = tf_ln_then_linear<T>(e, w, b, buf(o.in), buf(o.out), lin(n), buf(n.out), M, n.act, st)) < 0) return rc;
+      } else {
+        ++e->last_ln_launched;
+        if ((rc = launch_layernorm<T>(e, buf(o.in), buf(o.out), w, b, M, st)) < 0) return rc;
+      }
+    } else if ((rc = launch_linear<T>(e, lin(o), buf(o.in), 0, buf(o.res), buf(o.out), 0, M, o.act, st)) < 0) return rc;
   }
-  if (prev) {
-    ++e->last_ln_launched;
-    if ((rc = launch_layernorm<T>(e, e->h2, e->h, prev->n2w, prev->n2b, M, st)) < 0) return rc;
-  }
-  if (!rg) return (rc = launch_linear<T>(e, e->outl, e->h, 0, nullptr, y, 1, M, 0, st)) < 0 ? rc : 0;
-  if ((rc = launch_linear<T>(e, e->outl, e->h, 0, nullptr, e->ypk, 1, M, 0, st)) < 0) return rc;
+  // the last op, out_layer, into the caller's float32 rows
+  const void* last = buf(tf_arch_op(e->arch, e->nl, nops - 1).in);
+  if (!rg) return (rc = launch_linear<T>(e, e->outl, last, 0, nullptr, y, 1, M, 0, st)) < 0 ? rc : 0;
+  if ((rc = launch_linear<T>(e, e->outl, last, 0, nullptr, e->ypk, 1, M, 0, st)) < 0) return rc;
   const size_t tot = (size_t)B * L * e->out_dim;
   hipLaunchKernelGGL(tf_scatter_rows, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, (const float*)e->ypk, (const float*)e->outl.b, y, e->vl_off, L,
                      e->out_dim, tot);
@@ -2810,7 +2861,8 @@ int run_forward(flope_tf_encoder* e, const float* x, int B, int L, float* y, hip
 
 // Option fused: whether a float32 forward whose longest sequence has Lmax tokens runs as the single launch (never under option window)
 bool tf_fused_pick(const flope_tf_encoder* e, int Lmax) {
-  return e->fused_tab && e->opt_window == 0 && flope_tf_plan::tf_fused_ok(e->dtype, e->opt_fused, e->opt_f32m, e->in_dim, e->d, e->ff, Lmax);
+  // tf_fused_f32 is the default architecture's order alone
+  return e->fused_tab && e->opt_window == 0 && flope_tf_plan::tf_arch_default(e->arch) && flope_tf_plan::tf_fused_ok(e->dtype, e->opt_fused, e->opt_f32m, e->in_dim, e->d, e->ff, Lmax);
 }
 
 // ... and that launch: x [B][L][in] -> y [B][L][out], one workgroup per sequence.  off == nullptr: every sequence has L = Lmax tokens;
@@ -2928,18 +2980,22 @@ extern "C" int flope_tf_create(int device_id, int input_dim, int model_dim, int 
     hipFuncSetAttribute((const void*)tf_attn_mfma<bf16_t, false, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 131072);
     hipFuncSetAttribute((const void*)tf_attn_mfma<f16_t, true, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 131072);
     hipFuncSetAttribute((const void*)tf_attn_mfma<bf16_t, true, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 131072);
+    // every instantiation launch_linear launches: ACT 0 / ReLU with and without a residual, GELU without one
 #define TF_ATTR(T_, A_, B_) hipFuncSetAttribute((const void*)tf_gemm_mfma<T_, A_, B_>, hipFuncAttributeMaxDynamicSharedMemorySize, 65536)
-    TF_ATTR(f16_t, false, false); TF_ATTR(f16_t, false, true); TF_ATTR(f16_t, true, false); TF_ATTR(f16_t, true, true);
-    TF_ATTR(bf16_t, false, false); TF_ATTR(bf16_t, false, true); TF_ATTR(bf16_t, true, false); TF_ATTR(bf16_t, true, true);
+    TF_ATTR(f16_t, 0, false); TF_ATTR(f16_t, 0, true); TF_ATTR(f16_t, FLOPE_TF_ACT_RELU, false); TF_ATTR(f16_t, FLOPE_TF_ACT_RELU, true);
+    TF_ATTR(bf16_t, 0, false); TF_ATTR(bf16_t, 0, true); TF_ATTR(bf16_t, FLOPE_TF_ACT_RELU, false); TF_ATTR(bf16_t, FLOPE_TF_ACT_RELU, true);
+    TF_ATTR(f16_t, FLOPE_TF_ACT_GELU, false); TF_ATTR(bf16_t, FLOPE_TF_ACT_GELU, false);
 #undef TF_ATTR
-    const void* const f32m[] = {(const void*)tf_linear_f32m<4, false, false>, (const void*)tf_linear_f32m<4, true, false>, (const void*)tf_linear_f32m<4, false, true>,
-                                (const void*)tf_linear_f32m<2, false, false>, (const void*)tf_linear_f32m<2, true, false>, (const void*)tf_linear_f32m<2, false, true>,
-                                (const void*)tf_linear_f32m<1, false, false>, (const void*)tf_linear_f32m<1, true, false>, (const void*)tf_linear_f32m<1, false, true>,
+    // tf_linear_f32m reserves up to 160 KiB under option f32mlds: the GELU instantiations as the others
+#define TF_F32M(MP_) (const void*)tf_linear_f32m<MP_, 0, false>, (const void*)tf_linear_f32m<MP_, FLOPE_TF_ACT_RELU, false>, (const void*)tf_linear_f32m<MP_, 0, true>, \
+                     (const void*)tf_linear_f32m<MP_, FLOPE_TF_ACT_GELU, false>
+    const void* const f32m[] = {TF_F32M(4), TF_F32M(2), TF_F32M(1),
                                 (const void*)tf_attn_f32m<1>, (const void*)tf_attn_f32m<2>, (const void*)tf_attn_f32m<4>, (const void*)tf_attn_f32m<8>,
                                 (const void*)tf_attn_f32m<1, true>, (const void*)tf_attn_f32m<2, true>, (const void*)tf_attn_f32m<4, true>, (const void*)tf_attn_f32m<8, true>,
                                 (const void*)tf_attn_f32m<1, false, true>, (const void*)tf_attn_f32m<2, false, true>, (const void*)tf_attn_f32m<4, false, true>,
                                 (const void*)tf_attn_f32m<8, false, true>, (const void*)tf_attn_f32m<1, true, true>, (const void*)tf_attn_f32m<2, true, true>,
                                 (const void*)tf_attn_f32m<4, true, true>, (const void*)tf_attn_f32m<8, true, true>};
+#undef TF_F32M
     for (const void* f : f32m)
       if (hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kTfAttnLds) != hipSuccess)
         return fin(tf_fail(nullptr, FLOPE_EHIP, "flope_tf_create: hipFuncSetAttribute failed"));
@@ -3048,6 +3104,14 @@ extern "C" int flope_tf_set_option(flope_tf_handle e, const char* name, int valu
     if (value < 0 || value > 1) return tf_fail(e, FLOPE_EINVAL, "flope_tf_set_option: extend_mfma is 0 or 1");
     const int old = e->opt_extend_mfma; e->opt_extend_mfma = value; return old;
   }
+  // the architecture (tf_arch_plan.h): stated before the weights are loaded, fixed afterwards
+  if (!strcmp(name, "norm_first") || !strcmp(name, "activation") || !strcmp(name, "final_norm")) {
+    int* field = name[0] == 'n' ? &e->arch.norm_first : name[0] == 'a' ? &e->arch.act : &e->arch.final_norm;
+    const bool ok = name[0] == 'a' ? (value == FLOPE_TF_ACT_RELU || value == FLOPE_TF_ACT_GELU) : (value == 0 || value == 1);
+    if (!ok) return tf_fail(e, FLOPE_EINVAL, std::string("flope_tf_set_option: ") + name + (name[0] == 'a' ? " is 1 (ReLU) or 2 (GELU, the erf form)" : " is 0 or 1"));
+    if (e->arch_fixed) return tf_fail(e, FLOPE_ESTATE, std::string("flope_tf_set_option: ") + name + " is fixed once flope_tf_load_weights has succeeded");
+    const int old = *field; *field = value; return old;
+  }
   if (!strcmp(name, "f32mlds")) {
     if (value < 0 || value > 160) return tf_fail(e, FLOPE_EINVAL, "flope_tf_set_option: f32mlds is 0 .. 160 (KiB)");
     const int old = e->opt_f32m_lds; e->opt_f32m_lds = value; return old;
@@ -3118,6 +3182,9 @@ extern "C" int flope_tf_load_weights(flope_tf_handle e, int n, const char* const
         (rc = vec(p + "norm2.weight", e->d, &ly.n2w)) || (rc = vec(p + "norm2.bias", e->d, &ly.n2b)))
       return rc;
   }
+  if (e->arch.final_norm &&
+      ((rc = vec("transformer_encoder.norm.weight", e->d, &e->fnw)) || (rc = vec("transformer_encoder.norm.bias", e->d, &e->fnb))))
+    return rc;
   if ((rc = linear("out_layer.weight", "out_layer.bias", e->out_dim, e->d, &e->outl))) return rc;
   if (e->fused_tab) {                                  // a reload replaces the table (the weight arrays themselves stay until destroy, as before)
     for (auto it = e->allocs.begin(); it != e->allocs.end(); ++it)
@@ -3135,7 +3202,7 @@ extern "C" int flope_tf_load_weights(flope_tf_handle e, int n, const char* const
     if ((rc = tf_upload(e, tab.data(), tab.size(), (void**)&e->fused_tab))) return rc;
   }
   TF_HIP(e, hipDeviceSynchronize());
-  e->loaded = true;
+  e->loaded = e->arch_fixed = true;
   return FLOPE_OK;
 }
 
@@ -3175,8 +3242,9 @@ static const TfLinear* tf_find_linear(const flope_tf_encoder* e, const std::stri
   return op == "in_proj" ? &ly.in_proj : op == "out_proj" ? &ly.out_proj : op == "linear1" ? &ly.lin1 : op == "linear2" ? &ly.lin2 : nullptr;
 }
 
-extern "C" int flope_tf_linear(flope_tf_handle e, const char* name, const void* x_dev, int x_f32, const void* res_dev, void* y_dev, int y_f32, int rows,
-                               int relu, void* stream) {
+// flope_tf_linear and flope_tf_linear_act: act is 0 or FLOPE_TF_ACT_*
+static int tf_linear_entry(flope_tf_handle e, const char* name, const void* x_dev, int x_f32, const void* res_dev, void* y_dev, int y_f32, int rows,
+                           int act, void* stream) {
   if (!e) return tf_fail(nullptr, FLOPE_EINVAL, "flope_tf_linear: NULL handle");
   if (!e->loaded) return tf_fail(e, FLOPE_ESTATE, "flope_tf_linear: weights not loaded");
   if (!name || !x_dev || !y_dev) return tf_fail(e, FLOPE_EINVAL, "flope_tf_linear: NULL argument");
@@ -3185,6 +3253,8 @@ extern "C" int flope_tf_linear(flope_tf_handle e, const char* name, const void* 
   if (!l) return tf_fail(e, FLOPE_EINVAL, "flope_tf_linear: unknown linear " + nm + " (embedding, out_layer, layers.<i>.in_proj / out_proj / linear1 / linear2)");
   if (rows < 1) return tf_fail(e, FLOPE_EINVAL, "flope_tf_linear: non-positive rows");
   if (rows > e->max_tokens) return tf_fail(e, FLOPE_EINVAL, "flope_tf_linear: rows exceeds max_tokens given to flope_tf_create");
+  if (act < 0 || act > FLOPE_TF_ACT_GELU) return tf_fail(e, FLOPE_EINVAL, "flope_tf_linear_act: act is 0 (none), 1 (ReLU) or 2 (GELU)");
+  if (act == FLOPE_TF_ACT_GELU && res_dev) return tf_fail(e, FLOPE_EINVAL, "flope_tf_linear_act: GELU with a residual has no kernel");
   const uintptr_t bits = (uintptr_t)x_dev | (uintptr_t)res_dev | (uintptr_t)y_dev;
   if (e->dtype == FLOPE_DT_F32) {
     if (bits & 3) return tf_fail(e, FLOPE_EINVAL, "flope_tf_linear: buffer not aligned to its element type");
@@ -3201,12 +3271,22 @@ extern "C" int flope_tf_linear(flope_tf_handle e, const char* name, const void* 
   return tf_by_dtype(e, [&](auto tag) {
     using T = typename decltype(tag)::type;
     constexpr bool f32 = std::is_same<T, float>::value;                // a float32 handle's buffers are float32 whatever the flags say
-    return launch_linear<T>(e, *l, x_dev, f32 || x_f32 ? 1 : 0, res_dev, y_dev, f32 || y_f32 ? 1 : 0, rows, relu ? 1 : 0, (hipStream_t)stream);
+    return launch_linear<T>(e, *l, x_dev, f32 || x_f32 ? 1 : 0, res_dev, y_dev, f32 || y_f32 ? 1 : 0, rows, act, (hipStream_t)stream);
   });
 }
 
+extern "C" int flope_tf_linear(flope_tf_handle e, const char* name, const void* x_dev, int x_f32, const void* res_dev, void* y_dev, int y_f32, int rows,
+                               int relu, void* stream) {
+  return tf_linear_entry(e, name, x_dev, x_f32, res_dev, y_dev, y_f32, rows, relu ? FLOPE_TF_ACT_RELU : 0, stream);
+}
+
+extern "C" int flope_tf_linear_act(flope_tf_handle e, const char* name, const void* x_dev, int x_f32, const void* res_dev, void* y_dev, int y_f32, int rows,
+                                   int act, void* stream) {
+  return tf_linear_entry(e, name, x_dev, x_f32, res_dev, y_dev, y_f32, rows, act, stream);
+}
+
 // The id flope_tf_linear returns for this linear at this row count in the form the forward runs it -- embedding: float32 in; out_layer:
-// float32 out; out_proj and linear2: with a residual; linear1: with ReLU -- under the handle's current options; launches nothing.
+// float32 out; out_proj and linear2: with a residual; linear1: with the handle's activation -- under the handle's current options; launches nothing.
 extern "C" int flope_tf_linear_plan(flope_tf_handle e, const char* name, int rows) {
   if (!e) return tf_fail(nullptr, FLOPE_EINVAL, "flope_tf_linear_plan: NULL handle");
   if (!e->loaded) return tf_fail(e, FLOPE_ESTATE, "flope_tf_linear_plan: weights not loaded");
@@ -3217,11 +3297,11 @@ extern "C" int flope_tf_linear_plan(flope_tf_handle e, const char* name, int row
   if (rows < 1) return tf_fail(e, FLOPE_EINVAL, "flope_tf_linear_plan: non-positive rows");
   if (rows > e->max_tokens) return tf_fail(e, FLOPE_EINVAL, "flope_tf_linear_plan: rows exceeds max_tokens given to flope_tf_create");
   const bool res = nm.size() > 9 && (nm.compare(nm.size() - 9, 9, ".out_proj") == 0 || nm.compare(nm.size() - 8, 8, ".linear2") == 0);
-  const bool relu = nm.size() > 8 && nm.compare(nm.size() - 8, 8, ".linear1") == 0;
+  const int act = nm.size() > 8 && nm.compare(nm.size() - 8, 8, ".linear1") == 0 ? e->arch.act : 0;      // linear1 under the handle's activation
   void* const any = (void*)(uintptr_t)16;          // an aligned non-NULL pointer: plan mode looks at NULL and alignment only
   return tf_by_dtype(e, [&](auto tag) {
     using T = typename decltype(tag)::type;
-    return launch_linear<T>(e, *l, any, l == &e->emb ? 1 : 0, res ? any : nullptr, any, l == &e->outl ? 1 : 0, rows, relu ? 1 : 0, nullptr, true);
+    return launch_linear<T>(e, *l, any, l == &e->emb ? 1 : 0, res ? any : nullptr, any, l == &e->outl ? 1 : 0, rows, act, nullptr, true);
   });
 }
 
@@ -3237,10 +3317,12 @@ static int tf_check_linear_ln(flope_tf_encoder* e, const char* who, const char* 
   return 0;
 }
 
-extern "C" int flope_tf_linear_ln(flope_tf_handle e, const char* name, const void* x_dev, const float* gamma_dev, const float* beta_dev, void* normed_dev,
-                                  void* y_dev, int rows, int relu, void* stream) {
+// flope_tf_linear_ln and flope_tf_linear_ln_act: act is 0 or FLOPE_TF_ACT_*
+static int tf_linear_ln_entry(flope_tf_handle e, const char* name, const void* x_dev, const float* gamma_dev, const float* beta_dev, void* normed_dev,
+                              void* y_dev, int rows, int act, void* stream) {
   const TfLinear* l = nullptr;
   if (int rc = tf_check_linear_ln(e, "flope_tf_linear_ln", name, rows, &l)) return rc;
+  if (act < 0 || act > FLOPE_TF_ACT_GELU) return tf_fail(e, FLOPE_EINVAL, "flope_tf_linear_ln_act: act is 0 (none), 1 (ReLU) or 2 (GELU)");
   if (!x_dev || !gamma_dev || !beta_dev || !normed_dev || !y_dev) return tf_fail(e, FLOPE_EINVAL, "flope_tf_linear_ln: NULL argument");
   if (((uintptr_t)x_dev | (uintptr_t)normed_dev | (uintptr_t)y_dev) & 15) return tf_fail(e, FLOPE_EINVAL, "flope_tf_linear_ln: x, normed and y are 16-byte aligned");
   if (((uintptr_t)gamma_dev | (uintptr_t)beta_dev) & 15) return tf_fail(e, FLOPE_EINVAL, "flope_tf_linear_ln: gamma and beta are 16-byte aligned");
@@ -3253,22 +3335,32 @@ extern "C" int flope_tf_linear_ln(flope_tf_handle e, const char* name, const voi
   if ((x0 < h1 && h0 < x1) || (x0 < y1 && y0 < x1) || (h0 < y1 && y0 < h1)) return tf_fail(e, FLOPE_EINVAL, "flope_tf_linear_ln: x, normed and y must not overlap");
   TF_HIP(e, hipSetDevice(e->device));
   return tf_by_dtype(e, [&](auto tag) {
-    return launch_linear_ln<typename decltype(tag)::type>(e, *l, x_dev, gamma_dev, beta_dev, normed_dev, y_dev, rows, relu ? 1 : 0, (hipStream_t)stream);
+    return launch_linear_ln<typename decltype(tag)::type>(e, *l, x_dev, gamma_dev, beta_dev, normed_dev, y_dev, rows, act, (hipStream_t)stream);
   });
 }
 
+extern "C" int flope_tf_linear_ln(flope_tf_handle e, const char* name, const void* x_dev, const float* gamma_dev, const float* beta_dev, void* normed_dev,
+                                  void* y_dev, int rows, int relu, void* stream) {
+  return tf_linear_ln_entry(e, name, x_dev, gamma_dev, beta_dev, normed_dev, y_dev, rows, relu ? FLOPE_TF_ACT_RELU : 0, stream);
+}
+
+extern "C" int flope_tf_linear_ln_act(flope_tf_handle e, const char* name, const void* x_dev, const float* gamma_dev, const float* beta_dev, void* normed_dev,
+                                      void* y_dev, int rows, int act, void* stream) {
+  return tf_linear_ln_entry(e, name, x_dev, gamma_dev, beta_dev, normed_dev, y_dev, rows, act, stream);
+}
+
 // FLOPE_TF_LIN_SKINNY_LN where flope_tf_linear_ln would launch, else the id of the separate form's linear (no residual; linear1 with
-// ReLU); launches nothing
+// the handle's activation); launches nothing
 extern "C" int flope_tf_linear_ln_plan(flope_tf_handle e, const char* name, int rows) {
   const TfLinear* l = nullptr;
   if (int rc = tf_check_linear_ln(e, "flope_tf_linear_ln_plan", name, rows, &l)) return rc;
   const std::string nm(name);
-  const bool relu = nm.size() > 8 && nm.compare(nm.size() - 8, 8, ".linear1") == 0;
+  const int act = nm.size() > 8 && nm.compare(nm.size() - 8, 8, ".linear1") == 0 ? e->arch.act : 0;
   void* const any = (void*)(uintptr_t)16;
   return tf_by_dtype(e, [&](auto tag) {
     using T = typename decltype(tag)::type;
     if (tf_linear_ln_ok<T>(e, *l, rows)) return (int)FLOPE_TF_LIN_SKINNY_LN;
-    return launch_linear<T>(e, *l, any, l == &e->emb ? 1 : 0, nullptr, any, l == &e->outl ? 1 : 0, rows, relu ? 1 : 0, nullptr, true);
+    return launch_linear<T>(e, *l, any, l == &e->emb ? 1 : 0, nullptr, any, l == &e->outl ? 1 : 0, rows, act, nullptr, true);
   });
 }
 

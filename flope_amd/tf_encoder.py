@@ -22,6 +22,9 @@ A 16-bit encoder made with `skinny=1` runs every MFMA linear of 1 .. 32 rows -- 
 wave per 16-row feature tile instead of a few 128-row workgroups: the same bits, another launch shape.  With
 `skinny_ln=1` on top of it, a LayerNorm directly in front of such a linear (model_dim % 64 == 0, at most 512) runs inside the linear's
 launch: the same bits again, 2 num_layers - 1 launches fewer per forward; `enc.last_ln` counts them.
+The layer's architecture is torch's: `norm_first=True` (pre-norm), `activation="gelu"` (the erf form) and `final_norm=True`
+(nn.TransformerEncoder(norm=LayerNorm), state_dict keys transformer_encoder.norm.*) in any combination, through every forward, mask and
+stream; `arch_of(module)` reads the three from a torch module.  The defaults are the reference's encoder, bit for bit.
 
 Eval-mode semantics only (dropout is identity), as everywhere in this package.  There is no CPU
 path: construction fails loudly without a HIP device or without the built library.
@@ -37,13 +40,72 @@ from . import _lib
 from .engine import _DTYPES, _require_gpu, _stream_ptr
 
 
-def expected_keys(num_layers: int) -> list:
+_ACTS = {"relu": _lib.TF_ACT_RELU, "gelu": _lib.TF_ACT_GELU}
+
+
+def check_arch(norm_first=False, activation="relu", final_norm=False, layer_norm_eps=1e-5) -> dict:
+    """The architecture keywords of TransformerEncoder, validated without a device: {"norm_first", "activation", "final_norm"}.
+    ValueError on anything the kernels do not run: an activation other than the strings "relu" / "gelu" (torch's erf GELU; the tanh
+    form and callables have no kernel), a layer_norm_eps other than 1e-5, flags that are not bools."""
+    for name, v in (("norm_first", norm_first), ("final_norm", final_norm)):
+        if not isinstance(v, (bool, np.bool_)) and v not in (0, 1):
+            raise ValueError(f"{name} must be True or False (got {v!r})")
+    if not isinstance(activation, str) or activation not in _ACTS:
+        raise ValueError(f'activation must be "relu" or "gelu" (torch\'s erf form); {activation!r} has no kernel')
+    if float(layer_norm_eps) != 1e-5:
+        raise ValueError(f"layer_norm_eps must be 1e-5 (got {layer_norm_eps!r}): the LayerNorm kernels hold that constant")
+    return {"norm_first": bool(norm_first), "activation": activation, "final_norm": bool(final_norm)}
+
+
+def arch_of(module) -> dict:
+    """The three architecture keywords of TransformerEncoder for a torch module that holds an nn.TransformerEncoder as
+    `.transformer_encoder` (the reference script's shape): TransformerEncoder(..., **arch_of(m)) runs m's layers.  Works without a
+    GPU.  ValueError on anything this encoder cannot run: layers that differ, eps != 1e-5, bias=False, an activation other than ReLU or
+    the erf GELU, a final norm that is not an affine LayerNorm over model_dim."""
+    import torch.nn.functional as F
+    te = getattr(module, "transformer_encoder", None)
+    if not isinstance(te, torch.nn.TransformerEncoder):
+        raise ValueError("module.transformer_encoder must be an nn.TransformerEncoder")
+    found = set()
+    for i, ly in enumerate(te.layers):
+        if not isinstance(ly, torch.nn.TransformerEncoderLayer):
+            raise ValueError(f"layers.{i} is not an nn.TransformerEncoderLayer")
+        act = ly.activation
+        if act is F.relu or isinstance(act, torch.nn.ReLU):
+            name = "relu"
+        elif act is F.gelu or (isinstance(act, torch.nn.GELU) and getattr(act, "approximate", "none") == "none"):
+            name = "gelu"
+        else:
+            raise ValueError(f"layers.{i}.activation = {act!r}: only ReLU and the erf GELU have a kernel")
+        for n in (ly.norm1, ly.norm2):
+            if not isinstance(n, torch.nn.LayerNorm) or n.eps != 1e-5:
+                raise ValueError(f"layers.{i}: LayerNorm eps must be 1e-5 (got {getattr(n, 'eps', None)!r})")
+            if n.weight is None or n.bias is None:
+                raise ValueError(f"layers.{i}: a LayerNorm without weight or bias (bias=False) has no kernel")
+        for what, t in (("self_attn.in_proj_bias", ly.self_attn.in_proj_bias), ("self_attn.out_proj.bias", ly.self_attn.out_proj.bias),
+                        ("linear1.bias", ly.linear1.bias), ("linear2.bias", ly.linear2.bias)):
+            if t is None:
+                raise ValueError(f"layers.{i}.{what} is missing (bias=False) and has no kernel")
+        found.add((bool(ly.norm_first), name))
+    if len(found) > 1:
+        raise ValueError(f"the layers differ in (norm_first, activation): {sorted(found)}")
+    norm_first, name = found.pop() if found else (False, "relu")
+    fn = te.norm
+    if fn is not None:
+        if not isinstance(fn, torch.nn.LayerNorm) or fn.eps != 1e-5 or fn.weight is None or fn.bias is None:
+            raise ValueError("transformer_encoder.norm must be an nn.LayerNorm with eps 1e-5, weight and bias")
+    return check_arch(norm_first, name, fn is not None)
+
+
+def expected_keys(num_layers: int, final_norm: bool = False) -> list:
     keys = ["embedding.weight", "embedding.bias"]
     for i in range(num_layers):
         p = f"transformer_encoder.layers.{i}."
         keys += [p + s for s in ("self_attn.in_proj_weight", "self_attn.in_proj_bias", "self_attn.out_proj.weight",
                                  "self_attn.out_proj.bias", "linear1.weight", "linear1.bias", "linear2.weight",
                                  "linear2.bias", "norm1.weight", "norm1.bias", "norm2.weight", "norm2.bias")]
+    if final_norm:
+        keys += ["transformer_encoder.norm.weight", "transformer_encoder.norm.bias"]
     return keys + ["out_layer.weight", "out_layer.bias"]
 
 
@@ -213,7 +275,8 @@ def distance_bias(table, L, window=0):
 class TransformerEncoder:
     def __init__(self, input_dim, model_dim, out_dim, num_heads, num_layers, ff_dim, dropout=0.1,
                  dtype="f32", max_tokens=4096, device=None, attn_tiled=0, fused=0, window_mfma=0, step_split=0, extend_mfma=0,
-                 mask_mfma=0, bias_mfma=0, skinny=0, skinny_ln=0):
+                 mask_mfma=0, bias_mfma=0, skinny=0, skinny_ln=0, norm_first=False, activation="relu", final_norm=False, layer_norm_eps=1e-5):
+        self.arch = check_arch(norm_first, activation, final_norm, layer_norm_eps)       # torch's keywords, readable back
         _require_gpu()
         self.lib = _lib.load()
         self.device = torch.device(device if device is not None else "cuda:0")
@@ -235,6 +298,13 @@ class TransformerEncoder:
             if rc < 0:
                 self.close()
                 raise RuntimeError(f"flope_tf_set_option(f32mfma) failed ({rc})")
+        if self.arch != check_arch():            # the architecture, stated before the weights are loaded (include/flope_amd.h)
+            for name, value in (("norm_first", int(self.arch["norm_first"])), ("activation", _ACTS[self.arch["activation"]]),
+                                ("final_norm", int(self.arch["final_norm"]))):
+                rc = self.lib.flope_tf_set_option(self.handle, name.encode(), value)
+                if rc < 0:
+                    self.close()
+                    raise RuntimeError(f"flope_tf_set_option({name}) failed ({rc})")
         self.last_attn_kernel = None             # FLOPE_TF_ATTN_* id of the last attention() launch
         self.last_linear_kernel = None           # FLOPE_TF_LIN_* id of the last linear() launch
         self.last_ln_kernel = None               # FLOPE_TF_LN_* id of the last layernorm() launch
@@ -300,7 +370,10 @@ class TransformerEncoder:
         return self
 
     def load_state_dict(self, sd: dict) -> None:
-        want = expected_keys(self.dims[4])
+        want = expected_keys(self.dims[4], self.arch["final_norm"])
+        if not self.arch["final_norm"] and "transformer_encoder.norm.weight" in sd:
+            raise ValueError("state_dict holds transformer_encoder.norm.weight, but this encoder was made with final_norm=False: "
+                             "dropping a trained norm gives wrong poses (see arch_of)")
         missing = [k for k in want if k not in sd]
         if missing:
             raise KeyError(f"state_dict is missing {missing[:3]}{'...' if len(missing) > 3 else ''}")
@@ -315,7 +388,7 @@ class TransformerEncoder:
             self._check(self.lib.flope_tf_load_weights(self.handle, n, names, ptrs, ndims, shapes))
 
     def set_option(self, name: str, value: int) -> int:
-        if name in ("step_split", "extend_mfma", "mask_mfma", "bias_mfma", "skinny", "skinny_ln"):    # the newer options raise on a refused value (the others keep returning the code)
+        if name in ("step_split", "extend_mfma", "mask_mfma", "bias_mfma", "skinny", "skinny_ln", "norm_first", "activation", "final_norm"):    # the newer options raise on a refused value (the others keep returning the code)
             rc = self.lib.flope_tf_set_option(self.handle, name.encode(), int(value))
             self._check_arg(rc)
             return rc
@@ -566,7 +639,18 @@ class TransformerEncoder:
                 return nk
         raise ValueError(f"unknown linear {name!r}: embedding, out_layer, layers.<i>.in_proj / out_proj / linear1 / linear2")
 
-    def linear(self, name, x, res=None, relu=False, out_f32=False, out=None):
+    @staticmethod
+    def _act_id(relu, act):
+        """the FLOPE_TF_ACT_* id of linear()'s / linear_ln_act()'s `relu=` flag and `act=` name; ValueError where both are given and disagree"""
+        if act is None:
+            return _lib.TF_ACT_RELU if relu else _lib.TF_ACT_NONE
+        if not isinstance(act, str) or act not in _ACTS:
+            raise ValueError(f'act must be None, "relu" or "gelu" (got {act!r})')
+        if relu and act != "relu":
+            raise ValueError(f"relu=True together with act={act!r}")
+        return _ACTS[act]
+
+    def linear(self, name, x, res=None, relu=False, out_f32=False, out=None, act=None):
         """act(x W^T + b (+ res)) of the loaded linear `name` ("embedding", "out_layer", "layers.<i>.in_proj" / ".out_proj" /
         ".linear1" / ".linear2") by the kernel a forward launches for it at this row count under the current options; its
         FLOPE_TF_LIN_* id is kept in `last_linear_kernel`.  x [rows, K] in the handle's dtype, or float32 (the network input; the only form
@@ -575,7 +659,12 @@ class TransformerEncoder:
         16-bit handles: x, res and the result live in storage of roundup(rows, 128) rows (the MFMA linear works on whole 128-row
         tiles: pad rows of x and res may hold anything, those of the result are overwritten).  A tensor that is a view with that
         much room behind it is used in place -- the result keeps its padded storage --, any other is copied into one.
-        `out`: a [rows, N] tensor to write into, under the same rule (never copied: too little room is an error)."""
+        `out`: a [rows, N] tensor to write into, under the same rule (never copied: too little room is an error).
+        `act`: "relu" or "gelu" (torch's erf GELU on the float32 accumulator) beside the `relu` flag; ValueError if both
+        are given and disagree, and for GELU together with `res`, which has no kernel."""
+        aid = self._act_id(relu, act)
+        if aid == _lib.TF_ACT_GELU and res is not None:
+            raise ValueError("act=\"gelu\" together with res has no kernel")
         tdt = self._tdt()
         N, K = self._linear_dims(name)
         if x.dim() != 2 or x.shape[1] != K:
@@ -593,8 +682,8 @@ class TransformerEncoder:
         elif self._padded(out, rows, N, odt, "out") is not out:
             raise ValueError(f"out must be a contiguous {odt} tensor [{rows}, {N}] with storage for {(rows + 127) // 128 * 128} rows")
         with torch.cuda.device(self.device):
-            rc = self.lib.flope_tf_linear(self.handle, name.encode(), x.data_ptr(), int(x_f32), res.data_ptr() if res is not None else None,
-                                          out.data_ptr(), int(odt == torch.float32), rows, int(bool(relu)), _stream_ptr(self.device))
+            rc = self.lib.flope_tf_linear_act(self.handle, name.encode(), x.data_ptr(), int(x_f32), res.data_ptr() if res is not None else None,
+                                              out.data_ptr(), int(odt == torch.float32), rows, aid, _stream_ptr(self.device))
         self._check_arg(rc)
         self.last_linear_kernel = rc
         self._keep = (x, res)
@@ -602,7 +691,7 @@ class TransformerEncoder:
 
     def linear_plan(self, name, rows):
         """The FLOPE_TF_LIN_* id linear() would launch for the loaded linear `name` at `rows` rows under the current options, in the form
-        a forward runs it (embedding: float32 in; out_layer: float32 out; out_proj / linear2: with a residual; linear1: with ReLU).
+        a forward runs it (embedding: float32 in; out_layer: float32 out; out_proj / linear2: with a residual; linear1: with the encoder's activation).
         Launches nothing."""
         self._linear_dims(name)
         rc = self.lib.flope_tf_linear_plan(self.handle, name.encode(), int(rows))
@@ -616,6 +705,11 @@ class TransformerEncoder:
         where the option's rule has no such launch for this handle, linear and row count (linear_ln_plan tells).  The storage rule of
         linear(): x, y and normed live in storage of roundup(rows, 128) rows; `out` / `normed`: tensors to write into, never copied.
         x must not share storage with either result."""
+        return self.linear_ln_act(name, x, weight, bias, "relu" if relu else None, out=out, normed=normed)
+
+    def linear_ln_act(self, name, x, weight, bias, act, out=None, normed=None):
+        """linear_ln() with the activation named: `act` None, "relu" or "gelu" (DESIGN.md 50)."""
+        aid = self._act_id(False, act)
         tdt, d = self._tdt(), self.dims[1]
         N, K = self._linear_dims(name)
         if x.dim() != 2 or x.shape[1] != d:
@@ -635,8 +729,8 @@ class TransformerEncoder:
             res.append(t)
         out, normed = res
         with torch.cuda.device(self.device):
-            rc = self.lib.flope_tf_linear_ln(self.handle, name.encode(), x.data_ptr(), weight.data_ptr(), bias.data_ptr(), normed.data_ptr(),
-                                             out.data_ptr(), rows, int(bool(relu)), _stream_ptr(self.device))
+            rc = self.lib.flope_tf_linear_ln_act(self.handle, name.encode(), x.data_ptr(), weight.data_ptr(), bias.data_ptr(), normed.data_ptr(),
+                                                 out.data_ptr(), rows, aid, _stream_ptr(self.device))
         self._check_arg(rc)
         self.last_linear_kernel = rc
         self._keep = (x, weight, bias)

@@ -507,7 +507,18 @@ int flope_tf_forward(flope_tf_handle h, const float* x_dev, int batch, int seq_l
  *       in its token load, stores the post-norm rows and runs tf_gemm_skinny's MFMAs: rows < `rows` of both results hold the BITS of
  *       the two launches, so the option changes no result of any call; it takes 2 num_layers - 1 launches out of a forward.  The
  *       rule: option "skinny" takes the linear (1 .. 32 rows), K = model_dim, model_dim % 64 == 0 and model_dim <= 512.  The last
- *       LayerNorm (in front of out_layer) keeps its launch.  flope_tf_last_ln counts both.  Read when a call enqueues. */
+ *       LayerNorm (in front of out_layer) keeps its launch.  flope_tf_last_ln counts both.  Read when a call enqueues.  Under
+ *       "norm_first" both LayerNorms of every layer stand in front of such a linear: all 2 num_layers are folded;
+ *   "norm_first" (default 0; 0 or 1), "activation" (default FLOPE_TF_ACT_RELU = 1; 1 or FLOPE_TF_ACT_GELU = 2, torch's "gelu": the
+ *       erf form) and "final_norm" (default 0; 0 or 1): the architecture (flope_amd/csrc/tf_arch_plan.h) -- torch's
+ *       nn.TransformerEncoderLayer(norm_first=, activation=) and nn.TransformerEncoder(norm=LayerNorm).  Another value is
+ *       FLOPE_EINVAL.  Stated BEFORE the weights are loaded: once flope_tf_load_weights has succeeded they return FLOPE_ESTATE.
+ *       With "final_norm" the state_dict must hold transformer_encoder.norm.weight / .bias [model_dim].  Every forward, ragged,
+ *       causal, windowed, masked and biased, and every stream call runs the architecture; option "fused" is stored and ignored
+ *       under any but the default one (the forward is the launch sequence).  The defaults are the handle of before: the same
+ *       launches, kernels and bits. */
+#define FLOPE_TF_ACT_RELU 1
+#define FLOPE_TF_ACT_GELU 2
 int flope_tf_set_option(flope_tf_handle h, const char* name, int value);
 /* softmax(q k^T / sqrt(head_dim)) v per head on a caller's buffer: qkv_dev [batch, seq_len, 3*model_dim] and out_dev
  * [batch, seq_len, model_dim] in the handle's dtype (float32 for FLOPE_DT_F32).  Launches exactly what flope_tf_forward
@@ -540,9 +551,14 @@ double flope_tf_forward_flops(flope_tf_handle h, int batch, int seq_len);
 #define FLOPE_TF_LIN_SKINNY       5   /* tf_gemm_skinny: option skinny, where tf_gemm_mfma would run on 1 .. 32 rows; its bits (rows 0 .. 15 / 31 touched only) */
 int flope_tf_linear(flope_tf_handle h, const char* name, const void* x_dev, int x_f32, const void* res_dev, void* y_dev, int y_f32,
                     int rows, int relu, void* stream);
+/* flope_tf_linear with the activation named: act = 0 (none), FLOPE_TF_ACT_RELU or FLOPE_TF_ACT_GELU (tf_gelu_f32 of
+ * flope_amd/csrc/tf_act.h on the float32 accumulator, in front of the store).  The same kernel id as relu != 0 gives.
+ * Another act, or GELU together with res_dev, is FLOPE_EINVAL and launches nothing. */
+int flope_tf_linear_act(flope_tf_handle h, const char* name, const void* x_dev, int x_f32, const void* res_dev, void* y_dev, int y_f32,
+                        int rows, int act, void* stream);
 /* The FLOPE_TF_LIN_* id flope_tf_linear would return for linear `name` at `rows` rows under the handle's current options, in the form
  * flope_tf_forward runs that linear: "embedding" with a float32 input, "out_layer" with a float32 result, ".out_proj" and ".linear2"
- * with a residual, ".linear1" with ReLU, all buffers aligned.  Launches nothing and touches no buffer.  The same refusals: weights not
+ * with a residual, ".linear1" with the handle's activation, all buffers aligned.  Launches nothing and touches no buffer.  The same refusals: weights not
  * loaded (FLOPE_ESTATE), an unknown name, rows < 1 or rows > max_tokens (FLOPE_EINVAL). */
 int flope_tf_linear_plan(flope_tf_handle h, const char* name, int rows);
 /* The forward's launch of a LayerNorm together with the linear behind it (option "skinny_ln") on a caller's buffers:
@@ -556,8 +572,11 @@ int flope_tf_linear_plan(flope_tf_handle h, const char* name, int rows);
 #define FLOPE_TF_LIN_SKINNY_LN    6   /* tf_gemm_skinny_ln: option skinny_ln, a LayerNorm and the skinny linear behind it in one launch; the bits of the two */
 int flope_tf_linear_ln(flope_tf_handle h, const char* name, const void* x_dev, const float* gamma_dev, const float* beta_dev, void* normed_dev,
                        void* y_dev, int rows, int relu, void* stream);
+/* flope_tf_linear_ln with the activation named, as flope_tf_linear_act names it */
+int flope_tf_linear_ln_act(flope_tf_handle h, const char* name, const void* x_dev, const float* gamma_dev, const float* beta_dev, void* normed_dev,
+                           void* y_dev, int rows, int act, void* stream);
 /* FLOPE_TF_LIN_SKINNY_LN where flope_tf_linear_ln would launch for linear `name` at `rows` rows under the handle's current options,
- * otherwise the FLOPE_TF_LIN_* id of the linear of the separate form (no residual; ".linear1" with ReLU).  Launches nothing. */
+ * otherwise the FLOPE_TF_LIN_* id of the linear of the separate form (no residual; ".linear1" with the handle's activation).  Launches nothing. */
 int flope_tf_linear_ln_plan(flope_tf_handle h, const char* name, int rows);
 /* The LayerNorms of the last forward of any kind that went through the per-kernel launches (flope_tf_forward*, flope_tf_stream_step* /
  * _extend / _prefill): *launched stand-alone launches, *folded run inside the next linear's launch (option "skinny_ln").  Either
